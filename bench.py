@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: syndromes/s of the [[288,12,18]] sum-product BP decode at 50 iterations.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
 ``--gpus N`` with N > 1 starts itself: unless a launcher already set WORLD_SIZE, the process spawns
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`` as a
@@ -12,7 +12,12 @@ One "step" = one pass of the hot path (qbp_decode_batch_device, include/qbp.h) o
 synthetic syndromes already resident in HBM: BASELINE.json configs[3], [[288,12,18]], sum-product,
 max_iter 50, 1M trials over 8 GPUs = 125 000 syndromes per GPU (weak scaling).  `value` is measured
 in mode M2 of SURVEY.md 8(d): every syndrome runs all 50 iterations (QBP_FLAG_FORCE_FULL; outputs are
-still those of the first converged iteration).  Everything else in the line is measured by this run:
+still those of the first converged iteration).  `ms_per_step` is the wall time of one timed step.
+
+A plain run does only that: set up, W warm-up steps, K timed steps, the outputs of the last timed step
+if ``--dump-outputs DIR`` is given (dump_outputs below), and the JSON line (headline, `config`,
+`hbm_effective`, `converged_fraction`: all from the timed steps).  ``--full`` adds everything else, each
+measured by this run (``hbm_effective`` is in every line):
 
 * ``roofline``       the binding resource of the on-chip kernel is FP64 vector-ALU issue, not HBM.
                      achieved = vector instructions per wave and iteration, counted in the machine
@@ -30,6 +35,7 @@ still those of the first converged iteration).  Everything else in the line is m
                      mirror, host arrays and PCIe included; ``cpu_baseline`` the CPU oracle on this
                      box's cores (+ the reference's Python figure, a labelled constant measured in the
                      build container: the reference cannot travel to the GPU box).
+* ``multi_gpu``      per-rank kernel times, rates and the all-reduce's share of a step (N > 1).
 PyTorch only provides device memory, the stream, events and torch.distributed.
 """
 import argparse
@@ -269,6 +275,31 @@ def valu_roofline(lib_path, kernel_symbol, device, wave_iterations, kernel_s, nu
     return out
 
 
+DUMP_ROWS = 8192            # syndromes whose hard decisions and LLRs --dump-outputs writes
+DUMP_SEED = 20250101        # fixes which ones: the same rows in every run with the same --batch
+DUMP_BUDGET = 64 << 20      # bytes, all files together
+
+
+def dump_outputs(path, hard, conv, iters, llr):
+    """--dump-outputs: what the last timed step handed its caller (qbp_decode_batch_device's four output
+    arrays), as .npy files under `path`: converged.npy and iterations.npy (float32, one entry per syndrome),
+    hard_sample.npy (float32) and llr_sample.npy (float64) on DUMP_ROWS syndromes drawn with DUMP_SEED
+    (B x n in full would be 400 MB).  converged / iterations are sampled on the same rows too when whole
+    they would not fit in DUMP_BUDGET.  Values are exact: 0 / 1 and iteration counts in float32, LLR bits
+    unchanged."""
+    import torch
+    B, n = hard.shape
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=min(B, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(hard.device)
+    arrays = {"hard_sample": hard.index_select(0, idx).float(), "llr_sample": llr.index_select(0, idx)}
+    whole = 8 * B + len(rows) * n * 12 <= DUMP_BUDGET
+    arrays["converged" if whole else "converged_sample"] = (conv if whole else conv.index_select(0, idx)).float()
+    arrays["iterations" if whole else "iterations_sample"] = (iters if whole else iters.index_select(0, idx)).float()
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -276,11 +307,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="syndromes per GPU per step")
     ap.add_argument("--p", type=float, default=P_ERR)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--mode", choices=("both", "forced"), default="both",
-                    help="forced: only the headline mode (profiling runs)")
+                    help="with --full: forced = only the headline mode (profiling runs)")
     ap.add_argument("--sustained-seconds", type=float, default=10.0,
-                    help="length of the back-to-back forced-50 leg (0 = skip; skipped in --mode forced)")
+                    help="with --full: length of the back-to-back forced-50 leg (0 = skip; skipped in --mode "
+                         "forced)")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the N>1 "
                          "path on a box with fewer GPUs than ranks)")
@@ -288,7 +320,14 @@ def main():
                     help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--slots", type=int, default=0)
     ap.add_argument("--blocks-per-cu", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements: roofline, other modes and configs, sustained leg, "
+                         "drop-in API, CPU baseline, per-rank figures (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from qldpc_amd import launch
     launch.maybe_self_launch(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:])
@@ -313,7 +352,7 @@ def main():
             dist.init_process_group(args.backend)
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
-    full = args.mode == "both"
+    full = args.full and args.mode == "both"          # the other legs (--mode forced keeps only the headline's)
 
     code = codes.load_code(CODE)
     m, n = code.Hx.shape
@@ -383,7 +422,9 @@ def main():
     # ---- M2: forced 50 iterations (headline) ------------------------------------------------
     wall, kernel_ms, counts = timed(_lib.FLAG_FORCE_FULL, args.steps, args.warmup)
     headline_local_wall = timed.local_wall
-    clock_after_headline = shader_clock_ghz(local_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hard, conv, iters, llr)
+    clock_after_headline = shader_clock_ghz(local_rank) if args.full else None
     value = world * B * args.steps / wall
     bytes_per_launch = algorithmic_bytes(E, m, n, B * MAX_ITER, B)
     geometry = {"threads_per_block": dec.info("threads"), "grid": dec.info("grid"),
@@ -394,7 +435,7 @@ def main():
 
     # per-rank kernel times and the reduce on its own
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         km = torch.zeros(world, dtype=torch.float64, device=dev)
         km[rank] = kernel_ms
         dist.all_reduce(km)
@@ -529,7 +570,7 @@ def main():
         dropin = dropin_leg(code, local_rank)
     costs = None
     others = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             costs = valu_issue_costs(local_rank)
         except Exception:
@@ -541,21 +582,6 @@ def main():
             others = {"error": f"{type(ex).__name__}: {ex}"}
 
     if rank == 0:
-        dc = 6 if (dec.info("max_row_deg") <= 6 and dec.info("max_col_deg") <= 3) else 8
-        symbol = f"bp_fused_kernelILi{dc}ELi{3 if dc == 6 else 4}ELi0ELb0ELb1ELi1024ELi1ELb{one_bar}EE"
-        S = max(1, geometry["threads_per_block"] // m)
-        waves = (geometry["threads_per_block"] + 63) // 64
-        wave_iters = B * MAX_ITER / S * waves
-        try:
-            if kernel_kind != 1:
-                raise RuntimeError(f"the headline ran kernel kind {kernel_kind}, not the on-chip kernel")
-            roof = valu_roofline(_lib.LIB_PATH, symbol, local_rank, wave_iters, kernel_ms * 1e-3,
-                                 dec.info("num_cu"), iters_per_trip=2 if one_bar else 1, costs=costs)
-            roof["bp_iterations_per_loop_trip"] = 2 if one_bar else 1
-            roof["shader_clock_GHz_right_after"] = clock_after_headline
-        except Exception as ex:             # a bench line without a roofline is still a bench line
-            roof = {"bound": "fp64_valu", "achieved": None, "peak": None, "unit": "Tlane-instr/s",
-                    "frac": None, "traffic": None, "error": f"{type(ex).__name__}: {ex}"}
         out = {
             "metric": "syndromes/sec at 50 BP iters, [[288,12,18]] code",
             "value": value, "unit": "syndromes/s", "n_gpus": world, "steps": args.steps,
@@ -568,7 +594,6 @@ def main():
                        "sharding": f"{world} x independent syndrome shards, one all-reduce of counts "
                                    f"({'RCCL' if args.backend == 'nccl' else args.backend})",
                        **geometry},
-            "roofline": roof,
             "hbm_effective": {"achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                               "frac": achieved / HBM_PEAK, "kernel_ms": kernel_ms,
                               "algorithmic_bytes_per_launch": bytes_per_launch,
@@ -576,19 +601,38 @@ def main():
                                       "kernel (messages stay in LDS/registers, so the figure may exceed the "
                                       "HBM peak); physical HBM traffic is syndrome/LLR I/O only (PMC: "
                                       "profiles/)"},
-            "multi_gpu": multi,
-            "early_exit": early,
-            "stress_p010": stress,
-            "fast_math_flag": fast_math,
-            "sustained": sustained,
-            "hbm_streamed_variant": streamed,
-            "other_configs": others,
-            "dropin_api": dropin,
             "converged_fraction": counts[0] / (world * B),
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(code, syndromes[:100000].cpu().numpy(),
-                                               prior.cpu().numpy())
+        if args.full:
+            dc = 6 if (dec.info("max_row_deg") <= 6 and dec.info("max_col_deg") <= 3) else 8
+            symbol = f"bp_fused_kernelILi{dc}ELi{3 if dc == 6 else 4}ELi0ELb0ELb1ELi1024ELi1ELb{one_bar}EE"
+            S = max(1, geometry["threads_per_block"] // m)
+            waves = (geometry["threads_per_block"] + 63) // 64
+            wave_iters = B * MAX_ITER / S * waves
+            try:
+                if kernel_kind != 1:
+                    raise RuntimeError(f"the headline ran kernel kind {kernel_kind}, not the on-chip kernel")
+                roof = valu_roofline(_lib.LIB_PATH, symbol, local_rank, wave_iters, kernel_ms * 1e-3,
+                                     dec.info("num_cu"), iters_per_trip=2 if one_bar else 1, costs=costs)
+                roof["bp_iterations_per_loop_trip"] = 2 if one_bar else 1
+                roof["shader_clock_GHz_right_after"] = clock_after_headline
+            except Exception as ex:             # a bench line without a roofline is still a bench line
+                roof = {"bound": "fp64_valu", "achieved": None, "peak": None, "unit": "Tlane-instr/s",
+                        "frac": None, "traffic": None, "error": f"{type(ex).__name__}: {ex}"}
+            out.update({
+                "roofline": roof,
+                "multi_gpu": multi,
+                "early_exit": early,
+                "stress_p010": stress,
+                "fast_math_flag": fast_math,
+                "sustained": sustained,
+                "hbm_streamed_variant": streamed,
+                "other_configs": others,
+                "dropin_api": dropin,
+            })
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(code, syndromes[:100000].cpu().numpy(),
+                                                   prior.cpu().numpy())
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

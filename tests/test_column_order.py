@@ -3,7 +3,6 @@ reproduces numpy itself -- np.sum(R, axis=0) on a C-ordered and on a Fortran-ord
 drop-in layer picks the order from the memory order of the caller's H exactly as the reference's numpy
 code ends up doing (decoding/beliefPropagation.py:129; rework/decoding.py:61, :119, :173)."""
 import ctypes as C
-import importlib.util
 import os
 
 import numpy as np
@@ -83,31 +82,31 @@ def test_flag_choice_follows_numpy_layout_rules():
     assert bp.dense_colsum_flags(csr_matrix(Hf)) == 0
 
 
-REF = "/root/reference"
+LAYOUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "layout.npz")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="build container only: replays the reference's own numpy code")
 def test_layout_rules_against_the_reference_itself():
     """The three rules of bp.dense_colsum_flags, observed on the reference's own functions: same inputs,
-    H in C order vs Fortran order -> the LLR bits differ exactly where the rules say the order does."""
-    spec = importlib.util.spec_from_file_location("ref_rework_decoding", os.path.join(REF, "rework", "decoding.py"))
-    rework = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rework)
+    H in C order vs Fortran order -> the LLR bits differ exactly where the rules say the order does.
+    The reference's outputs are stored in tests/golden/layout.npz (tests/golden/make_golden_layout.py)."""
     from oracle import oracle
-    rng = np.random.default_rng(5)
+    g = np.load(LAYOUT)
+    max_iter = int(g["max_iter"])
+    differs = 0
     for tag in ("144", "288"):
         code = codes.load_code(tag)
-        p = 0.06
-        prior = np.log((1 - p) / p) * rng.uniform(0.7, 1.3, code.n)          # non-uniform: iteration 0 matters
-        for _ in range(6):
-            s = ((rng.random(code.n) < p).astype(np.int64) @ code.Hx.T % 2).astype(np.int8)
-            for H in (np.ascontiguousarray(code.Hx), np.asfortranarray(code.Hx)):
-                for fn, name, kw in ((rework.performBeliefPropagationFast, "fast4", {}),
-                                     (rework.performMinSum_Symmetric, "minsum", dict(alpha=0.8, damping=0.7, clip_llr=25.0)),
-                                     (rework.performBeliefPropagation_Symmetric, "sym", dict(alpha=0.9, damping=0.8, clip_llr=20.0))):
-                    h, c, llr, it = fn(H, s, prior, maxIter=30, **kw)
-                    variant = {"fast4": 0, "minsum": 2, "sym": 1}[name]
-                    o = oracle.decode_batch(H, s[None, :].astype(np.uint8), prior, 30, variant,
+        prior, syn = g[f"{tag}_prior"], g[f"{tag}_syndromes"]
+        for order, H in (("C", np.ascontiguousarray(code.Hx)), ("F", np.asfortranarray(code.Hx))):
+            for name, kw in (("fast4", {}), ("minsum", dict(alpha=0.8, damping=0.7, clip_llr=25.0)),
+                             ("sym", dict(alpha=0.9, damping=0.8, clip_llr=20.0))):
+                key = f"{tag}_{order}_{name}"
+                variant = {"fast4": 0, "minsum": 2, "sym": 1}[name]
+                other = g[f"{tag}_{'F' if order == 'C' else 'C'}_{name}_llr"]
+                differs += int((g[key + "_llr"].view(np.uint64) != other.view(np.uint64)).any())
+                for i, s in enumerate(syn):
+                    h, c, llr, it = g[key + "_hard"][i], g[key + "_converged"][i], g[key + "_llr"][i], g[key + "_iters"][i]
+                    o = oracle.decode_batch(H, s[None, :], prior, max_iter, variant,
                                             flags=oracle.colsum_flags(name, H), **kw)
                     assert o[2][0] == it and bool(o[1][0]) == bool(c) and np.array_equal(o[0][0], h)
-                    assert (o[3][0].view(np.uint64) == np.asarray(llr).view(np.uint64)).all(), (tag, name, H.flags.f_contiguous)
+                    assert (o[3][0].view(np.uint64) == llr.view(np.uint64)).all(), (tag, name, H.flags.f_contiguous)
+    assert differs, "the stored vectors no longer show the memory order mattering"

@@ -16,12 +16,12 @@ echo "== misc"; timeout -k 10 600 python tools/measure_misc.py > $OUT/misc.log 2
 echo "== kernels"; (timeout -k 10 300 python tools/bench_generic.py; timeout -k 10 300 python tools/bench_osd.py; timeout -k 10 300 python tools/ab_early.py; timeout -k 10 300 python tools/measure_latency.py) > $OUT/kernels.log 2>&1; grep -v amdgpu.ids $OUT/kernels.log
 echo "== other configs"; timeout -k 10 300 python tools/bench_configs.py > $OUT/configs.log 2>&1; cat $OUT/configs.log
 echo "== paper_results smoke"; timeout -k 10 300 python -m qldpc_amd.paper_results --codes 72 288 --p 0.05 0.02 --trials 50000 --max-iter 50 --out $OUT/paper_smoke > $OUT/paper_smoke.log 2>&1; tail -12 $OUT/paper_smoke.log
-echo "== bench"; timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json; tail -3 $OUT/bench.err
+echo "== bench"; timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; cat $OUT/bench.json; tail -3 $OUT/bench.err
 echo "== 2-rank rehearsal of the distributed path (gloo, both ranks on cuda:0)"
-timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --backend gloo --share-device --batch 20000 > $OUT/bench_2rank_rehearsal.json 2> $OUT/bench_2rank.err; echo "rehearsal exit=$?"; tail -c 600 $OUT/bench_2rank_rehearsal.json; tail -3 $OUT/bench_2rank.err
+timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 3 --warmup 1 --backend gloo --share-device --batch 20000 --full > $OUT/bench_2rank_rehearsal.json 2> $OUT/bench_2rank.err; echo "rehearsal exit=$?"; tail -c 600 $OUT/bench_2rank_rehearsal.json; tail -3 $OUT/bench_2rank.err
 echo "== rocprof"
 export TMPDIR=/tmp; cd /tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o trace -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/prof_bench.log 2>&1
 echo "rocprof exit=$?"; find $OUT/prof -name "*stats*" | head; 
 for f in $(find $OUT/prof -name "*kernel_stats.csv"); do head -8 $f; done
 

@@ -16,7 +16,7 @@ pass() {   # name, counters, program...
 }
 if [ "${ONLY:-}" != "legs" ]; then
 echo "== kernel trace of the bench command"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $OUT/trace_bench.log 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/trace_bench.log 2>&1
 echo "trace exit=$?"
 F="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --mode forced"
 pass fused_class "SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_CVT" $F
