@@ -301,12 +301,15 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 }
                 QBP_COLD_END();
             } else {
+                // the syndrome sign applied to the product once per row instead of to every quotient
+                // (check_message_signed: the same bits)
+                const double prod_s = with_syndrome_sign(prod, sb);
 #pragma unroll
                 for (int j = 0; j < DC; ++j) {
                     // prod / t, correctly rounded like numpy's division: 1e-15 <= |prod| <= 1 and
                     // 1e-15 <= |t| <= 1, so no operand scaling is needed (div_nr's precondition) and the
                     // quotient is at least 1e-15 in magnitude (check_message: NORMAL)
-                    const double r = check_message<VARIANT, true>(div_nr(prod, t[j]), sb, np_tab);     // :123-126
+                    const double r = check_message_signed<VARIANT>(div_nr(prod_s, t[j]), np_tab);     // :123-126
                     put(j, VARIANT == 1 ? r * P.alpha : r);
                     if constexpr (DC > 6) QBP_EDGE_FENCE();
                 }

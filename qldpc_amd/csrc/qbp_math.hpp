@@ -193,10 +193,17 @@ QBP_HD double atanh2(double y)
 struct NpImage {
     uint64_t tanh_row[16][18];      // {midpoint, c16, c15 .. c0}: Horner order, nine 16-byte pairs
     uint64_t log_hl[16][2];         // {log(1 + j/16) high, low}
-    uint32_t rcp_lut[64];           // by the top 6 mantissa bits: see np_make_image, np_rcp14_hi
-    uint32_t rcp_lut_p[64];         // the same + 0x03ff0000: for operands in [1, 2) taken as hi >> 4 (np_rcp14_hi_12)
+    uint64_t rcp_lut[32];           // by the top 5 mantissa bits, entry in the HIGH dword, low dword 0: see
+    uint64_t rcp_lut_p[32];         // np_make_image, np_rcp14; _p: for operands in [1, 2) (np_rcp14_12)
 };
 constexpr int NP_LDS_BYTES = (int)sizeof(NpImage);      // 3072
+constexpr bool np_rcp14_thresholds_apart()
+{
+    for (int j = 1; j < 16; ++j)
+        if (NP_RCP14_THR16[j] - NP_RCP14_THR16[j - 1] <= 0x800u) return false;
+    return true;
+}
+static_assert(np_rcp14_thresholds_apart(), "a bin of the reciprocal table would hold two thresholds");
 constexpr int NP_LDS_DOUBLES = NP_LDS_BYTES / 8;
 
 constexpr NpImage np_make_image()
@@ -209,19 +216,21 @@ constexpr NpImage np_make_image()
         im.log_hl[i][1] = NP_ATANH_LOG_LO[i];
     }
     // R_hi = 0x3ff00000 - (k << 16), k = number of thresholds <= m16 (the operand's top 16 mantissa bits).
-    // Bin b holds m16 in [b << 10, (b + 1) << 10): at most one threshold inside.  With
+    // Bin b holds m16 in [b << 11, (b + 1) << 11): at most one threshold inside (they are more than 0x800
+    // apart, checked below).  With
     //   ent = 0x3ff0ffff - (k_left << 16) - (0x10000 - thr)      (thr = 0x10000 when the bin has none)
     // (ent - m16) & 0xffff0000 is R_hi: m16 >= thr borrows exactly one unit of bit 16.  The stored entries
-    // carry, on top, the constant their reader would add next (bits >= 20: no effect on the borrow).
-    for (int b = 0; b < 64; ++b) {
+    // carry, on top, the constant their reader would add next (bits >= 20: no effect on the borrow).  They sit
+    // in the high dword of a zero low dword, so that ONE ds_read_b64 delivers both halves of R as a double.
+    for (int b = 0; b < 32; ++b) {
         uint32_t k_left = 0, thr = 0x10000u;
         for (int j = 0; j < 16; ++j) {
-            if (NP_RCP14_THR16[j] <= (uint32_t)(b << 10)) ++k_left;
-            else if (NP_RCP14_THR16[j] < (uint32_t)((b + 1) << 10)) thr = NP_RCP14_THR16[j];
+            if (NP_RCP14_THR16[j] <= (uint32_t)(b << 11)) ++k_left;
+            else if (NP_RCP14_THR16[j] < (uint32_t)((b + 1) << 11)) thr = NP_RCP14_THR16[j];
         }
         const uint32_t ent = 0x3ff0ffffu - (k_left << 16) - (0x10000u - thr);
-        im.rcp_lut[b] = ent + 0x3ff00000u;          // (+ the exponent bias of the result: np_rcp14_hi)
-        im.rcp_lut_p[b] = ent + 0x03ff0000u;        // (+ the operand's own exponent field >> 4: np_rcp14_hi_12)
+        im.rcp_lut[b] = (uint64_t)(ent + 0x3ff00000u) << 32;     // (+ the exponent bias of the result: np_rcp14)
+        im.rcp_lut_p[b] = (uint64_t)(ent + 0x03ff0000u) << 32;   // (+ the operand's own exponent field >> 4: np_rcp14_12)
     }
     return im;
 }
@@ -279,23 +288,23 @@ QBP_HD NpPair np_ld_pair(NpT t, unsigned byte_off)
 {
     return *reinterpret_cast<const __attribute__((address_space(3))) NpPair*>(t + byte_off);
 }
-QBP_HD unsigned np_ld_u32(NpT t, unsigned byte_off)
+QBP_HD double np_ld_f64(NpT t, unsigned byte_off)
 {
-    return *reinterpret_cast<const __attribute__((address_space(3))) unsigned*>(t + byte_off);
+    return *reinterpret_cast<const __attribute__((address_space(3))) double*>(t + byte_off);
 }
 #elif defined(__HIPCC__)      /* host pass of a device translation unit: same types, never executed */
 typedef unsigned NpT;
 QBP_HD NpPair np_ld_pair(NpT, unsigned) { return NpPair{0.0, 0.0}; }
-QBP_HD unsigned np_ld_u32(NpT, unsigned) { return 0u; }
+QBP_HD double np_ld_f64(NpT, unsigned) { return 0.0; }
 #else
 typedef const double* NpT;
 QBP_HD NpPair np_ld_pair(NpT t, unsigned byte_off)
 {
     return *reinterpret_cast<const NpPair*>(reinterpret_cast<const char*>(t) + byte_off);
 }
-QBP_HD unsigned np_ld_u32(NpT t, unsigned byte_off)
+QBP_HD double np_ld_f64(NpT t, unsigned byte_off)
 {
-    return *reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(t) + byte_off);
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(t) + byte_off);
 }
 #endif
 #if defined(__HIPCC__)
@@ -344,21 +353,45 @@ QBP_HD double np_tanh_half(double q, NpT T)
     return __builtin_copysign(p, x);                            // (p >= 0: the routine ORs the sign bit in)
 }
 
-// hi dword of round4(rcp14(v)) for a positive normal v (its low dword is 0)
-QBP_HD unsigned np_rcp14_hi(unsigned v_hi, NpT T)
+// bits [OFF, OFF + WIDTH) of x: one v_bfe_u32 (opaque on the device, where the compiler would otherwise split
+// it into a shift and an and that it merges into the next operation -- two instructions instead of one)
+template <unsigned OFF, unsigned WIDTH>
+QBP_HD unsigned np_bfe(unsigned x)
 {
-    const unsigned m16 = (v_hi >> 4) & 0xffffu;
-    const unsigned ent = np_ld_u32(T, NP_OFF_LUT + ((v_hi >> 12) & 0xfcu));
-    // biased mantissa part (as for v in [1, 2): exponent field 0x3ff), then the operand's exponent: 2^-e
-    return ((ent - m16) & 0xffff0000u) - (v_hi & 0x7ff00000u);
+#ifdef QBP_DEVICE_BITS
+    unsigned r;
+    asm("v_bfe_u32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "i"(OFF), "i"(WIDTH));
+    return r;
+#else
+    return (x >> OFF) & ((1u << WIDTH) - 1u);
+#endif
 }
+
+// round4(rcp14(v)) for a positive normal v.  The table entry arrives as the double {0, ent}; its high dword is
+// replaced in place, so the zero low dword of the result costs no instruction.  The operand's exponent field
+// (times 2^20) and its top 16 mantissa bits are subtracted in one go -- a bit-field extract and an and-or form
+// E << 20 | m16 -- which is the same as subtracting the exponent after the mask: E << 20 has no bits below 16.
+QBP_HD double np_rcp14(unsigned v_hi, NpT T)
+{
+    const double e = np_ld_f64(T, NP_OFF_LUT + ((v_hi >> 12) & 0xf8u));
+    const unsigned em16 = (v_hi & 0x7ff00000u) | np_bfe<4, 16>(v_hi);          // v_bfe + v_and_or
+    return np_from_hi_lo((np_hi(e) - em16) & 0xffff0000u, np_lo(e));
+}
+// its high dword (the low one is 0)
+QBP_HD unsigned np_rcp14_hi(unsigned v_hi, NpT T) { return np_hi(np_rcp14(v_hi, T)); }
 
 // the same for P in [1, 2) (P = 1 + a, a <= 0.9999999): the exponent term is a constant, folded into the
 // second table
-QBP_HD unsigned np_rcp14_hi_12(unsigned p_hi, NpT T)
+QBP_HD double np_rcp14_12(unsigned p_hi, NpT T)
 {
-    return (np_ld_u32(T, NP_OFF_LUT_P + ((p_hi >> 12) & 0xfcu)) - (p_hi >> 4)) & 0xffff0000u;
+    const double e = np_ld_f64(T, NP_OFF_LUT_P + ((p_hi >> 12) & 0xf8u));
+    return np_from_hi_lo((np_hi(e) - (p_hi >> 4)) & 0xffff0000u, np_lo(e));
 }
+
+// Byte offset of the log-table pair of R from its high dword: bits 16-19 (the top four mantissa bits) times 16.
+// Bits 12-15 of a table reciprocal are zero, so that is bits 12-19 as they stand: one v_bfe_u32 (np_bfe: the
+// compiler would otherwise take bits 16-19 from the value before the mask -- a shift and an and).
+QBP_HD unsigned np_log_row(unsigned r_hi) { return np_bfe<12, 8>(r_hi); }
 
 // 2.0 * np.arctanh(a) for 0 <= a <= 0.9999999 -- the magnitude; np.arctanh is odd in every bit (the routine
 // works on |y| and multiplies by +-0.5 at the end), so the kernels clip |y|, call this and set the sign bit.
@@ -367,13 +400,13 @@ template <bool SCALE = true>
 QBP_HD double np_arctanh_x2_abs(double a, NpT T)
 {
     const double P = a + 1.0, M = 1.0 - a;
-    const unsigned rp_hi = np_rcp14_hi_12(np_hi(P), T), rm_hi = np_rcp14_hi(np_hi(M), T);
-    const NpPair lp = np_ld_pair(T, NP_OFF_LOG + ((rp_hi >> 12) & 0xf0u));
-    const NpPair lm = np_ld_pair(T, NP_OFF_LOG + ((rm_hi >> 12) & 0xf0u));
+    const double Rp = np_rcp14_12(np_hi(P), T), Rm = np_rcp14(np_hi(M), T);
+    const unsigned rp_hi = np_hi(Rp), rm_hi = np_hi(Rm);
+    const NpPair lp = np_ld_pair(T, NP_OFF_LOG + np_log_row(rp_hi));
+    const NpPair lm = np_ld_pair(T, NP_OFF_LOG + np_log_row(rm_hi));
     const double Ph = P - 1.0, Mh = M - 1.0;
     const double Pl = a - Ph;                       // 1 + a = P + Pl
     const double Ml = a + Mh;                       // 1 - a = M - Ml
-    const double Rp = np_from_hi_lo(rp_hi, 0u), Rm = np_from_hi_lo(rm_hi, 0u);
     double rp = __builtin_fma(Rp, P, -1.0);
     rp = __builtin_fma(Pl, Rp, rp);
     double rm = __builtin_fma(M, Rm, -1.0);
@@ -489,6 +522,32 @@ QBP_HD double check_message(double x, unsigned sbit, NpT T)
     const double t = np_arctanh_x2_abs<!NORMAL>(a, T);
     return np_from_hi_lo((np_hi(t) & 0x7fffffffu) | ((np_hi(x) ^ (sbit << 31)) & 0x80000000u), np_lo(t));
 #endif
+}
+
+// The same for a quotient that already carries the syndrome sign: x = (syndrome_sign * prod) / t, |x| >= 2^-1000
+// or so (NORMAL above), never NaN.  Division's sign is the XOR of its operands' signs, exactly (div_nr is odd in
+// its dividend bit for bit: every step is an fma or product of negated terms), so the callers flip the row
+// product once per row and each edge takes its sign from the quotient: one v_bfi_b32.
+template <int VARIANT>
+QBP_HD double check_message_signed(double xs, NpT T)
+{
+#if QBP_MATH_FAST
+    return atanh2(clip_unit<VARIANT>(xs));
+#else
+    constexpr double C = 0.9999999;                          // beliefPropagation.py:110
+    const double ax = __builtin_fabs(xs);
+    double a;
+    if (VARIANT == 1) a = ax > C ? C : ax;
+    else a = __builtin_fmin(ax, C);
+    const double t = np_arctanh_x2_abs<false>(a, T);
+    return np_from_hi_lo((np_hi(t) & 0x7fffffffu) | (np_hi(xs) & 0x80000000u), np_lo(t));
+#endif
+}
+
+// x * syndrome_sign for the row product (sbit in {0, 1}): the sign bit only, so exact for every x
+QBP_HD double with_syndrome_sign(double x, unsigned sbit)
+{
+    return np_from_hi_lo(np_hi(x) ^ (sbit << 31), np_lo(x));
 }
 
 }  // namespace qbp
