@@ -36,7 +36,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qbp_math.hpp"
+#include "qbp_check.hpp"
 #include "qbp_mc.hpp"
 
 namespace qbp {
@@ -145,63 +145,36 @@ __host__ __device__ inline size_t generic_lds_bytes(int m, int E, int n, bool ld
            (lds_tables ? (size_t)8 * (size_t)n + (size_t)4 * (size_t)E : 0);
 }
 
-// Check update of one row held in registers: q[D] -> r[D]   (beliefPropagation.py:114-126 /
-// rework/decoding.py:28-56).  `scale` is false for the alpha_estimation dump of the damped variant
+// Sum-product check update of one row held in registers: q[D] -> put(j, r_j)   (beliefPropagation.py:114-126).
+// Min-sum rows take check_row (qbp_check.hpp); the sum-product ones keep this form, which needs fewer registers
+// here than check_row's.  `scale` is false for the alpha_estimation dump of the damped variant
 // (rework/decoding.py:168-169 returns R before the alpha scaling).
 // `put(j, value)` takes message j as soon as it exists (eight finished messages waiting for their stores are
 // sixteen registers the wide rows do not have).
 template <int VARIANT, int D, typename Put>
-__device__ __forceinline__ void generic_row_update(const double (&q)[D], const Put& put, unsigned sbit,
-                                                   double alpha, bool scale, NpT np_tab)
+__device__ __forceinline__ void generic_sp_row(const double (&q)[D], const Put& put, unsigned sbit,
+                                               double alpha, bool scale, NpT np_tab)
 {
-    if constexpr (VARIANT == 2) {
-        double sprod = 1.0, min1 = __builtin_inf(), min2 = __builtin_inf();
-        int min1_j = -1;
-        bool anynan = false;
+    double t[D];
+    double prod = 1.0;
 #pragma unroll
-        for (int j = 0; j < D; ++j) {
-            sprod *= q[j] < 0.0 ? -1.0 : 1.0;
-            anynan |= q[j] != q[j];
-            const double a = __builtin_fabs(q[j]);
-            if (a < min1) { min1 = a; min1_j = j; }
-        }
-        // np.sign(nan) = nan: one NaN message makes the row's sign product, hence every R of the
-        // row, NaN (rework/decoding.py:28-35; inf - inf with infinite priors)
-        if (anynan) sprod = __builtin_nan("");
+    for (int j = 0; j < D; ++j) {
+        t[j] = tanh_half_msg<VARIANT>(q[j], np_tab);
+        prod = (j == 0) ? t[0] : prod * t[j];
+        QBP_EDGE_FENCE();
+    }
+    // (t_safe, :122: |t| <= 1, so a product of at least 1e-15 has no factor below it -- one wave-uniform
+    // test instead of D compares and 2 D selects, as in the on-chip kernel)
+    if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(prod) >= 1e-15)) != 0ull) {
 #pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const double a = __builtin_fabs(q[j]);
-            if (j != min1_j && a < min2) min2 = a;
-        }
-        const double as = sbit ? -alpha : alpha;
+        for (int j = 0; j < D; ++j) t[j] = __builtin_fabs(t[j]) < 1e-15 ? 1e-15 : t[j];
+    }
 #pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const double sg = q[j] < 0.0 ? -1.0 : 1.0;
-            const double mag = (__builtin_fabs(q[j]) == min1) ? min2 : min1;
-            put(j, (as * (sprod * sg)) * mag);
-        }
-    } else {
-        double t[D];
-        double prod = 1.0;
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            t[j] = tanh_half_msg<VARIANT>(q[j], np_tab);
-            prod = (j == 0) ? t[0] : prod * t[j];
-            QBP_EDGE_FENCE();
-        }
-        // (t_safe, :122: |t| <= 1, so a product of at least 1e-15 has no factor below it -- one wave-uniform
-        // test instead of D compares and 2 D selects, as in the on-chip kernel)
-        if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(prod) >= 1e-15)) != 0ull) {
-#pragma unroll
-            for (int j = 0; j < D; ++j) t[j] = __builtin_fabs(t[j]) < 1e-15 ? 1e-15 : t[j];
-        }
-#pragma unroll
-        for (int j = 0; j < D; ++j) {
-            const double ts = t[j];
-            const double x = check_message<VARIANT>(div_nr(prod, ts), sbit, np_tab);     // :123-126
-            put(j, (VARIANT == 1 && scale) ? x * alpha : x);
-            QBP_EDGE_FENCE();
-        }
+    for (int j = 0; j < D; ++j) {
+        const double ts = t[j];
+        const double x = check_message<VARIANT>(div_nr(prod, ts), sbit, np_tab);     // :123-126
+        put(j, (VARIANT == 1 && scale) ? x * alpha : x);
+        QBP_EDGE_FENCE();
     }
 }
 
@@ -383,9 +356,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         if constexpr (VARIANT == 0) {
             Qstore(o, qn);
         } else {
-            const double q = P.damping * qn + one_minus_damping * Q[o];
-            const double y = q < -P.clip_llr ? -P.clip_llr : q;     // np.clip, NaN stays NaN
-            Q[o] = y > P.clip_llr ? P.clip_llr : y;
+            Q[o] = damped_q(qn, Q[o], P.damping, one_minus_damping, P.clip_llr);
         }
     };
 
@@ -570,8 +541,11 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                         const int base = P.row_base[DD] + i;                                       \
                         double q[DD];                                                              \
                         _Pragma("unroll") for (int j = 0; j < DD; ++j) q[j] = QBP_GEN_QLOAD(base + j * cnt);   \
-                        generic_row_update<VARIANT, DD>(q, [&](int j, double v) { Rstore(base + j * cnt, v); }, \
-                                                        sbit, P.alpha, scale, np_tab);                     \
+                        auto put = [&](int j, double v) { Rstore(base + j * cnt, v); };            \
+                        if constexpr (VARIANT == 2)                                                \
+                            check_row<VARIANT, DD, true>(q, sbit, P.alpha, scale, np_tab, put);   \
+                        else                                                                       \
+                            generic_sp_row<VARIANT, DD>(q, put, sbit, P.alpha, scale, np_tab);    \
                     }                                                                              \
                 } break;
                 switch (D) {
@@ -595,22 +569,8 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                     const int deg = P.srow_deg[first_long + i];
                     const int p0 = P.epos[P.srow_e0[first_long + i]];   // entries contiguous from here
                     if constexpr (VARIANT == 2) {
-                        double sprod = 1.0, min1 = __builtin_inf(), min2 = __builtin_inf();
-                        int min1_j = -1;
-                        bool anynan = false;
-                        for (int j = 0; j < deg; ++j) {
-                            const double x = Q[p0 + j];
-                            sprod *= x < 0.0 ? -1.0 : 1.0;
-                            anynan |= x != x;
-                            const double a = __builtin_fabs(x);
-                            if (a < min1) { min1 = a; min1_j = j; }
-                        }
-                        if (anynan) sprod = __builtin_nan("");
-                        for (int j = 0; j < deg; ++j) {
-                            const double a = __builtin_fabs(Q[p0 + j]);
-                            if (j != min1_j && a < min2) min2 = a;
-                        }
-                        L[3 * i] = sprod; L[3 * i + 1] = min1; L[3 * i + 2] = min2;
+                        const MinSumRow row = minsum_row([&](int j) { return Q[p0 + j]; }, deg);
+                        L[3 * i] = row.sprod; L[3 * i + 1] = row.min1; L[3 * i + 2] = row.min2;
                     } else {
                         // eight loads in flight, then the multiplications in ascending order
                         double prod = 1.0;
@@ -632,15 +592,10 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                     const int w = first_long + i;
                     const unsigned sbit = (synw[w >> 5] >> (w & 31)) & 1u;
                     if constexpr (VARIANT == 2) {
-                        const double x = Q[lbase + k];
-                        const double sg = x < 0.0 ? -1.0 : 1.0;
-                        const double mag = (__builtin_fabs(x) == L[3 * i + 1]) ? L[3 * i + 2] : L[3 * i + 1];
-                        const double as = sbit ? -P.alpha : P.alpha;
-                        Rstore(lbase + k, (as * (L[3 * i] * sg)) * mag);
+                        Rstore(lbase + k, minsum_message(Q[lbase + k], MinSumRow{L[3 * i], L[3 * i + 1], L[3 * i + 2]}, sbit,
+                                                         P.alpha));
                     } else {
-                        const double t = Rload(lbase + k);
-                        const double ts = __builtin_fabs(t) < 1e-15 ? 1e-15 : t;
-                        const double x = check_message<VARIANT>(div_nr(L[3 * i], ts), sbit, np_tab);
+                        const double x = sp_message<VARIANT>(L[3 * i], Rload(lbase + k), sbit, np_tab);
                         Rstore(lbase + k, (VARIANT == 1 && scale) ? x * P.alpha : x);
                     }
                 }

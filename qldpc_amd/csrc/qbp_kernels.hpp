@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "qbp_math.hpp"
+#include "qbp_check.hpp"
 #include "qbp_mc.hpp"
 
 // Register-budget choices of the shapes that do not fit 128 registers otherwise (A/B switches for
@@ -130,28 +130,12 @@ __device__ __forceinline__ ColdArgs cold_args()
     return p;
 }
 #define COLD(field) (cold_args()->field)
-// Markers around arithmetic that does not run every iteration, for the static instruction count of
-// tools/valu_mix.py (no effect on the hardware beyond two one-cycle scalar no-ops inside that path).
-#define QBP_COLD_BEGIN() asm volatile("s_nop 9")
-#define QBP_COLD_END() asm volatile("s_nop 10")
 
 // Syndromes a slot leader fetches at once when its syndromes have taken avg4 / 4 iterations on average
 // (see "Work distribution" in the kernel).
 __device__ __forceinline__ int work_chunk_for(int avg4)
 {
     return avg4 < 12 ? 8 : avg4 < 28 ? 4 : avg4 < 60 ? 2 : 1;
-}
-
-__device__ __forceinline__ double clipd(double x, double lo, double hi)
-{   // np.clip(x, lo, hi) == minimum(maximum(x, lo), hi) for non-NaN x: v_max_f64 + v_min_f64
-    return __builtin_fmin(__builtin_fmax(x, lo), hi);
-}
-
-__device__ __forceinline__ double clipd_nan(double x, double lo, double hi)
-{   // same, but a NaN stays a NaN as in np.clip (the damped variants can produce inf - inf when
-    // a check has a single edge: rework/decoding.py keeps iterating on NaNs there)
-    const double y = x < lo ? lo : x;
-    return y > hi ? hi : y;
 }
 
 // Classification of one finished trial by its slot leader (paperResults_GPU.py:127-144 without
@@ -243,78 +227,9 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         return reinterpret_cast<unsigned char*>(var_lds + DC * m) + (size_t)(sl + (err_par ? S : 0)) * n4;
     };
 
-    // ---- check step of one row: q[DC] -> put(j, r) for its DC edges --------------------------------
+    // ---- check step of one row: q[DC] -> put(j, r) for its DC edges (qbp_check.hpp) -----------------
     auto check_step = [&](const double (&q)[DC], unsigned sb, auto&& put) {
-        if constexpr (VARIANT == 2) {
-            // rework/decoding.py:28-56
-            double sprod = 1.0, min1 = __builtin_inf();
-            int min1_j = 0;
-            bool anynan = false;
-#pragma unroll
-            for (int j = 0; j < DC; ++j) {
-                const double s = q[j] < 0.0 ? -1.0 : 1.0;   // sign, 0 -> +1, padding +1
-                sprod *= s;
-                anynan |= q[j] != q[j];
-                const double a = __builtin_fabs(q[j]);
-                if (a < min1) { min1 = a; min1_j = j; }       // first occurrence
-            }
-            // np.sign(nan) = nan: one NaN message (inf - inf with infinite priors) makes the
-            // row's sign product, hence every R of the row, NaN
-            if (anynan) sprod = __builtin_nan("");
-            double min2 = __builtin_inf();
-#pragma unroll
-            for (int j = 0; j < DC; ++j) {
-                const double a = __builtin_fabs(q[j]);
-                if (j != min1_j && a < min2) min2 = a;
-            }
-            const double as = sb ? -P.alpha : P.alpha;        // alpha * syndrome_sign
-#pragma unroll
-            for (int j = 0; j < DC; ++j) {
-                const double s = q[j] < 0.0 ? -1.0 : 1.0;
-                const double mag = (__builtin_fabs(q[j]) == min1) ? min2 : min1;
-                put(j, (as * (sprod * s)) * mag);
-            }
-        } else {
-            double t[DC];
-            double prod;
-#pragma unroll
-            for (int j = 0; j < DC; ++j) {
-                t[j] = tanh_half_msg<VARIANT>(q[j], np_tab);     // np.tanh(Q * 0.5), :114
-                if constexpr (DC > 6) QBP_EDGE_FENCE();
-            }
-#pragma unroll
-            for (int j = 0; j < DC; ++j) prod = (j == 0) ? t[0] : prod * t[j];     // np.prod, ascending column
-            // t_safe = where(|t| < 1e-15, 1e-15, t) (:122).  |t| <= 1, so a row whose product is at least
-            // 1e-15 in magnitude has no such factor: one wave-uniform test on the product replaces the six
-            // compares and twelve selects in all but degenerate rows (messages of magnitude 1e-15, or six
-            // messages near 0.006 at once -- those take the selects)
-            if (__builtin_amdgcn_ballot_w64(!(__builtin_fabs(prod) >= 1e-15)) != 0ull) {
-                // (rare path, bracketed for tools/valu_mix.py: the instruction count that prices the kernel must
-                // not include it)
-                QBP_COLD_BEGIN();
-#pragma unroll
-                for (int j = 0; j < DC; ++j) {
-                    const double ts = __builtin_fabs(t[j]) < 1e-15 ? 1e-15 : t[j];
-                    // (a zero or denormal product: quotients of any size, down to the subnormals)
-                    const double r = check_message<VARIANT, false>(div_nr(prod, ts), sb, np_tab);
-                    put(j, VARIANT == 1 ? r * P.alpha : r);
-                }
-                QBP_COLD_END();
-            } else {
-                // the syndrome sign applied to the product once per row instead of to every quotient
-                // (check_message_signed: the same bits)
-                const double prod_s = with_syndrome_sign(prod, sb);
-#pragma unroll
-                for (int j = 0; j < DC; ++j) {
-                    // prod / t, correctly rounded like numpy's division: 1e-15 <= |prod| <= 1 and
-                    // 1e-15 <= |t| <= 1, so no operand scaling is needed (div_nr's precondition) and the
-                    // quotient is at least 1e-15 in magnitude (check_message: NORMAL)
-                    const double r = check_message_signed<VARIANT>(div_nr(prod_s, t[j]), np_tab);     // :123-126
-                    put(j, VARIANT == 1 ? r * P.alpha : r);
-                    if constexpr (DC > 6) QBP_EDGE_FENCE();
-                }
-            }
-        }
+        check_row<VARIANT, DC, (DC > 6)>(q, sb, P.alpha, true, np_tab, put);
     };
 
     // ---- per-lane static tables (registers for the whole kernel) ---------------------------
@@ -589,8 +504,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     if constexpr (VARIANT == 0) {
                         Q[j] = qn;
                     } else {
-                        const double q = P.damping * qn + one_minus_damping * Q[j];
-                        Q[j] = clipd_nan(q, -P.clip_llr, P.clip_llr);
+                        Q[j] = damped_q(qn, Q[j], P.damping, one_minus_damping, P.clip_llr);
                     }
                 }
             }

@@ -24,7 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "qbp_math.hpp"
+#include "qbp_check.hpp"
 
 // variables per group of the variable step (two groups are in flight)
 #ifndef QBP_STREAM_VU
@@ -93,30 +93,9 @@ __device__ __forceinline__ void stream_check_class(const double* Q, double* R, c
             for (int j = 0; j < D; ++j) qn[j] = Q[(long long)(f0 + j) * ES];
         }
         if constexpr (VARIANT == 2) {
-            double sprod = 1.0, min1 = __builtin_inf(), min2 = __builtin_inf();
-            int min1_j = -1;
-            bool anynan = false;
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                sprod *= q[j] < 0.0 ? -1.0 : 1.0;
-                anynan |= q[j] != q[j];
-                const double a = __builtin_fabs(q[j]);
-                if (a < min1) { min1 = a; min1_j = j; }          // argmin: first occurrence
-            }
-            if (anynan) sprod = __builtin_nan("");               // np.sign(nan) = nan: whole row NaN
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double a = __builtin_fabs(q[j]);
-                if (j != min1_j && a < min2) min2 = a;
-            }
-            const double as = sbit ? -alpha : alpha;             // alpha * syndrome_sign
-#pragma unroll
-            for (int j = 0; j < D; ++j) {
-                const double sg = q[j] < 0.0 ? -1.0 : 1.0;
-                const double mag = (__builtin_fabs(q[j]) == min1) ? min2 : min1;
-                R[(long long)(e0 + j) * ES] = (as * (sprod * sg)) * mag;
-            }
-        } else {
+            check_row<VARIANT, D, false>(q, sbit, alpha, true, np_tab,
+                                         [&](int j, double r) { R[(long long)(e0 + j) * ES] = r; });
+        } else {   // (sum-product: this form needs fewer registers here than check_row's)
             double t[D];
             double prod = 1.0;
 #pragma unroll
@@ -126,8 +105,7 @@ __device__ __forceinline__ void stream_check_class(const double* Q, double* R, c
             }
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                const double ts = __builtin_fabs(t[j]) < 1e-15 ? 1e-15 : t[j];
-                const double r = check_message<VARIANT>(div_nr(prod, ts), sbit, np_tab);
+                const double r = sp_message<VARIANT>(prod, t[j], sbit, np_tab);
                 R[(long long)(e0 + j) * ES] = (VARIANT == 1) ? r * alpha : r;
             }
         }
@@ -141,28 +119,9 @@ __device__ __forceinline__ void stream_check_long(const double* Q, double* R, un
                                                   NpT np_tab)
 {
     if constexpr (VARIANT == 2) {
-        double sprod = 1.0, min1 = __builtin_inf(), min2 = __builtin_inf();
-        int min1_j = -1;
-        bool anynan = false;
-        for (int j = 0; j < deg; ++j) {
-            const double x = Q[(long long)(e0 + j) * ES];
-            sprod *= x < 0.0 ? -1.0 : 1.0;
-            anynan |= x != x;
-            const double a = __builtin_fabs(x);
-            if (a < min1) { min1 = a; min1_j = j; }
-        }
-        if (anynan) sprod = __builtin_nan("");
-        for (int j = 0; j < deg; ++j) {
-            const double a = __builtin_fabs(Q[(long long)(e0 + j) * ES]);
-            if (j != min1_j && a < min2) min2 = a;
-        }
-        const double as = sbit ? -alpha : alpha;
-        for (int j = 0; j < deg; ++j) {
-            const double x = Q[(long long)(e0 + j) * ES];
-            const double sg = x < 0.0 ? -1.0 : 1.0;
-            const double mag = (__builtin_fabs(x) == min1) ? min2 : min1;
-            R[(long long)(e0 + j) * ES] = (as * (sprod * sg)) * mag;
-        }
+        auto load = [&](int j) { return Q[(long long)(e0 + j) * ES]; };
+        const MinSumRow row = minsum_row(load, deg);
+        for (int j = 0; j < deg; ++j) R[(long long)(e0 + j) * ES] = minsum_message(load(j), row, sbit, alpha);
     } else {
         double prod = 1.0;
         for (int j = 0; j < deg; ++j) {
@@ -171,9 +130,7 @@ __device__ __forceinline__ void stream_check_long(const double* Q, double* R, un
             prod = (j == 0) ? t : prod * t;
         }
         for (int j = 0; j < deg; ++j) {
-            const double t = R[(long long)(e0 + j) * ES];
-            const double ts = __builtin_fabs(t) < 1e-15 ? 1e-15 : t;
-            const double r = check_message<VARIANT>(div_nr(prod, ts), sbit, np_tab);
+            const double r = sp_message<VARIANT>(prod, R[(long long)(e0 + j) * ES], sbit, np_tab);
             R[(long long)(e0 + j) * ES] = (VARIANT == 1) ? r * alpha : r;
         }
     }
@@ -211,9 +168,7 @@ __device__ __forceinline__ void stream_var_class(double* Q, const double* R, uin
             if constexpr (VARIANT == 0) {                                                        \
                 *qp = qnew;                                                                      \
             } else {                                                                             \
-                const double x = damping * qnew + one_minus_damping * *qp;                       \
-                const double y = x < -clip_llr ? -clip_llr : x;   /* np.clip, NaN stays */       \
-                *qp = y > clip_llr ? clip_llr : y;                                               \
+                *qp = damped_q(qnew, *qp, damping, one_minus_damping, clip_llr);                 \
             }                                                                                    \
         }                                                                                        \
         if (!frozen) cand[(long long)v * Bc] = val < 0.0;                                        \
@@ -349,9 +304,7 @@ __global__ __launch_bounds__(256) void bp_stream_kernel(const StreamParams P,
                 if constexpr (VARIANT == 0) {
                     Q[o] = qnew;
                 } else {
-                    const double x = P.damping * qnew + one_minus_damping * Q[o];
-                    const double y = x < -P.clip_llr ? -P.clip_llr : x;
-                    Q[o] = y > P.clip_llr ? P.clip_llr : y;
+                    Q[o] = damped_q(qnew, Q[o], P.damping, one_minus_damping, P.clip_llr);
                 }
             }
             if (!frozen) cand[(long long)v * Bc] = val < 0.0;

@@ -14,9 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def _build(tag, extra):
     src = os.path.join(HERE, "_shim", "math_host_shim.cpp")
     so = os.path.join(HERE, "_shim", f"libmathshim{tag}.so")
-    hdr = os.path.join(HERE, "..", "qldpc_amd", "csrc", "qbp_math.hpp")
-    if (not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src),
-                                                             os.path.getmtime(hdr))):
+    hdrs = [os.path.join(HERE, "..", "qldpc_amd", "csrc", f) for f in ("qbp_math.hpp", "qbp_check.hpp")]
+    if (not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in [src] + hdrs)):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-mfma",
                                "-ffp-contract=off", *extra, "-o", so, src])
     return C.CDLL(so)

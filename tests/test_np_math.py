@@ -29,7 +29,7 @@ GOLD = np.load(os.path.join(HERE, "golden", "np_math.npz"))
 def _shim():
     src = os.path.join(HERE, "_shim", "math_host_shim.cpp")
     so = os.path.join(HERE, "_shim", "libmathshim_np.so")
-    deps = [src] + [os.path.join(HERE, "..", "qldpc_amd", "csrc", f) for f in ("qbp_math.hpp", "qbp_np_tables.hpp")]
+    deps = [src] + [os.path.join(HERE, "..", "qldpc_amd", "csrc", f) for f in ("qbp_math.hpp", "qbp_check.hpp", "qbp_np_tables.hpp")]
     if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-mfma", "-ffp-contract=off",
                                "-o", so, src])
