@@ -81,14 +81,20 @@ enum {
                                  prints the table); hard decision, converged flag and iteration were identical
                                  to the reference's on every stored vector.  +28 % throughput on forced-50
                                  [[288,12,18]].  Default (flag clear): every output bit equal to the reference's. */
-    QBP_FLAG_DENSE_F_COLSUM_ITER0 = 16u /* ... at iteration 0 only: the damped variants (rework/decoding.py:5,
+    QBP_FLAG_DENSE_F_COLSUM_ITER0 = 16u, /* ... at iteration 0 only: the damped variants (rework/decoding.py:5,
                                  :131) on a Fortran-ordered H of fewer than 32768 entries -- `Q_old = Q.copy()`
                                  is C-ordered and C order wins in `damping * Q_new + (1 - damping) * Q_old` (:65,
                                  :179) from then on (from 256 KiB numpy reuses the F-ordered temporary instead:
                                  QBP_FLAG_DENSE_F_COLSUM).  Host-pointer entry point only; implemented for
                                  the case where iteration 0 cannot depend on the order (uniform priors, checks
                                  of equal weight, columns of at most 3 entries), else QBP_E_UNSUPPORTED. */
+    QBP_FLAG_OSD_CS = 64u,    /* order-w OSD, combination sweep (qbp_osd_batch below); order: QBP_OSD_ORDER_FLAGS.
+                                 With qbp_mc_run* only together with QBP_FLAG_OSD0 */
+    QBP_FLAG_OSD_E = 128u     /* order-w OSD, exhaustive over the w least reliable non-pivot columns (same rules) */
 };
+/* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
+ * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
+#define QBP_OSD_ORDER_FLAGS(w) ((uint32_t)(w) << 16)
 #define QBP_MC_OSD_MAX_TRIALS (1 << 20) /* per qbp_mc_run call with QBP_FLAG_OSD0 (record buffers) */
 
 /*
@@ -197,6 +203,9 @@ int qbp_message_histograms(qbp_handle* h, const uint8_t* syndromes, const uint8_
  * both (matrices whose bit-packed rows exceed 64 KiB of LDS go through the workgroup-per-syndrome
  * OSD kernel, whose matrix copy lives in global memory).  With QBP_FLAG_OSD0 a call keeps per-trial
  * records (m + 10 n bytes each): at most QBP_MC_OSD_MAX_TRIALS trials and 16 GiB per call.
+ * QBP_FLAG_OSD0 | QBP_FLAG_OSD_CS (or _E) | QBP_OSD_ORDER_FLAGS(w): order-w OSD (qbp_osd_batch) instead of OSD-0,
+ * on matrices the one-wavefront OSD kernel takes (else QBP_E_UNSUPPORTED).  QBP_E_INVALID: a method bit without
+ * QBP_FLAG_OSD0, both method bits, order bits without a method bit, an order out of range.
  */
 #define QBP_NUM_COUNTERS 12
 int qbp_mc_run(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, double p,
@@ -235,6 +244,28 @@ int qbp_osd0_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, c
                    int64_t B, uint8_t* solution);
 int qbp_osd0_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_llr,
                           const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream);
+
+/*
+ * Order-w OSD of B decoder outputs (same buffers as qbp_osd0_batch).  osd_flags: 0 (or QBP_FLAG_OSD0 alone) is
+ * exactly qbp_osd0_batch; else QBP_FLAG_OSD_CS or QBP_FLAG_OSD_E with QBP_OSD_ORDER_FLAGS(w) (QBP_FLAG_OSD0 may be
+ * set: one encoding serves this call and qbp_mc_run).  Per record:
+ *   1. columns sorted by (|llr| as in OSD-0, NaN last, column index) ascending;
+ *   2. Gauss-Jordan in that order up to rank(H): pivot columns S, fully reduced matrix A, reduced syndrome s;
+ *   3. candidate 0 is OSD-0 (bit-identical to qbp_osd0_batch): e_S = s, e_T = 0, x = hard ^ e;
+ *   4. T: the k' = n - rank non-pivot columns in sort order; w' = min(w, k');
+ *   5. a candidate flips F within T: e_T = 1_F, e_S(r) = s_r ^ XOR_{j in F} A[r][j].  CS: every weight-1 set
+ *      over all of T in order, then the weight-2 sets over T[0..w') in itertools.combinations order.  E: every
+ *      non-empty subset of T[0..w'), by weight, then in combinations order.  Candidate index: 0, then that order;
+ *   6. cost(x) = sum of fabs(llr_i) over x_i = 1, added in ascending column index from +0.0 in double;
+ *   7. the result is the first candidate of least cost; an OSD-0 cost of NaN returns OSD-0, NaN costs never win;
+ *   8. a syndrome outside the column space of H returns the OSD-0 output, without a search.
+ * Order > 0 on matrices the one-wavefront OSD kernel takes (every code of codes/), else QBP_E_UNSUPPORTED;
+ * QBP_E_INVALID for any other bit or an order out of range (CS 1..64, E 1..12: at most 4095 flip sets).
+ */
+int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr,
+                  const uint8_t* hard, int64_t B, uint8_t* solution);
+int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                         const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream);
 
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */

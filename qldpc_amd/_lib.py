@@ -24,6 +24,10 @@ FLAG_PAIRWISE_COLSUM = 4     # np.sum order of the loop form (beliefPropagation.
 FLAG_DENSE_F_COLSUM = 8      # np.sum(R, axis=0) order of the dense forms on a Fortran-ordered H (include/qbp.h)
 FLAG_DENSE_F_COLSUM_ITER0 = 16   # ... at iteration 0 only (damped variants, F-ordered H below 256 KiB)
 FLAG_FAST_MATH = 32          # opt-in: round 2's tanh / arctanh approximations on the on-chip kernel (include/qbp.h)
+FLAG_OSD_CS = 64             # order-w OSD, combination sweep (qbp_osd_batch; with FLAG_OSD0 in qbp_mc_run)
+FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable non-pivot columns
+OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
+OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
 NUM_COUNTERS = 12
 COUNTER_NAMES = ("trials", "logical_error", "BPs_fault", "BPs_miscorrected", "incorrectable",
@@ -65,12 +69,31 @@ SIGNATURES = {
                                          C.c_double, C.c_int32, C.c_uint32, C.c_int32, _VP, _VP, _VP]),
     "qbp_osd0_batch": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "qbp_osd0_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
+    "qbp_osd_batch": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP]),
+    "qbp_osd_batch_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
     "qbp_last_error": (C.c_char_p, []),
     "qbp_version": (C.c_char_p, []),
 }
+
+
+def osd_flags(method="cs", order=0):
+    """Flags of an OSD pass: order 0 -> ``FLAG_OSD0`` (OSD-0); order w >= 1 -> ``FLAG_OSD0 | FLAG_OSD_CS`` (method
+    "cs", 1 <= w <= 64) or ``| FLAG_OSD_E`` ("e", 1 <= w <= 12) with the order in bits 16..23.  The same value
+    serves ``Decoder.osd`` and the Monte-Carlo calls.  Raises ValueError for anything else."""
+    m = str(method).lower()
+    if m not in OSD_MAX_ORDER:
+        raise ValueError(f"OSD method must be 'cs' or 'e', got {method!r}")
+    if isinstance(order, bool) or int(order) != order:
+        raise ValueError(f"OSD order must be an integer, got {order!r}")
+    w = int(order)
+    if w == 0:
+        return FLAG_OSD0
+    if not 1 <= w <= OSD_MAX_ORDER[m]:
+        raise ValueError(f"OSD-{m.upper()} order must be in [0, {OSD_MAX_ORDER[m]}], got {w}")
+    return FLAG_OSD0 | (FLAG_OSD_CS if m == "cs" else FLAG_OSD_E) | (w << OSD_ORDER_SHIFT)
 
 
 class QbpError(RuntimeError):
@@ -315,6 +338,28 @@ class Decoder:
         """OSD-0 on device buffers (pointers as ints), enqueued on `stream`."""
         _check(load().qbp_osd0_batch_device(self._h, d_syndromes, d_llr, d_hard, int(B), d_solution,
                                             stream or None))
+
+    @_locked
+    def osd(self, syndromes, llr, hard, method="cs", order=7):
+        """Order-w OSD (include/qbp.h, qbp_osd_batch) on B decoder outputs (host arrays) -> solution
+        uint8[B, n]; order 0 is OSD-0."""
+        fl = osd_flags(method, order)
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        l = np.ascontiguousarray(llr, np.float64)
+        hd = np.ascontiguousarray(hard, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m})")
+        if l.shape != (syn.shape[0], self.n) or hd.shape != l.shape:
+            raise ValueError(f"llr and hard must have shape ({syn.shape[0]}, {self.n})")
+        sol = np.empty_like(hd)
+        _check(load().qbp_osd_batch(self._h, fl, syn.ctypes.data, l.ctypes.data, hd.ctypes.data,
+                                    syn.shape[0], sol.ctypes.data))
+        return sol
+
+    def osd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, method="cs", order=7, stream=0):
+        """Order-w OSD on device buffers (pointers as ints), enqueued on `stream`."""
+        _check(load().qbp_osd_batch_device(self._h, osd_flags(method, order), d_syndromes, d_llr, d_hard, int(B),
+                                           d_solution, stream or None))
 
     @_locked
     def mc_sample_errors(self, p, trial_begin, T, draws=1, seed=0):

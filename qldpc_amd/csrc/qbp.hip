@@ -15,6 +15,7 @@
 #include "../../include/qbp.h"
 #include "qbp_kernels.hpp"
 #include "qbp_osd.hpp"
+#include "qbp_osd_order.hpp"
 #include "qbp_generic.hpp"
 #include "qbp_stream.hpp"
 #include "qbp_hist.hpp"
@@ -1341,10 +1342,42 @@ static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long ma
     return QBP_OK;
 }
 
+// Order-w OSD flags (include/qbp.h: QBP_FLAG_OSD_CS / _E, order in bits 16..23) -> method (0: OSD-0) and order.
+// `mc`: flags of qbp_mc_run*, where a method needs QBP_FLAG_OSD0 and the other bits are the decoder's; elsewhere
+// (qbp_osd_batch) nothing but the OSD bits may be set.
+constexpr uint32_t OSD_ORDER_BITS = 0xffu << 16;
+constexpr uint32_t OSD_METHOD_BITS = QBP_FLAG_OSD_CS | QBP_FLAG_OSD_E;
+
+static int parse_osd_flags(const qbp_handle* h, uint32_t flags, bool mc, int* method, int* order)
+{
+    *method = 0;
+    *order = (int)((flags & OSD_ORDER_BITS) >> 16);
+    const uint32_t mb = flags & OSD_METHOD_BITS;
+    if (!mc && (flags & ~(OSD_ORDER_BITS | OSD_METHOD_BITS | QBP_FLAG_OSD0)))
+        return fail(QBP_E_INVALID, "osd_flags 0x%x: unknown bits", flags);
+    if (mb == OSD_METHOD_BITS) return fail(QBP_E_INVALID, "QBP_FLAG_OSD_CS and QBP_FLAG_OSD_E together");
+    if (!mb) {
+        if (*order) return fail(QBP_E_INVALID, "an OSD order (%d) without QBP_FLAG_OSD_CS or QBP_FLAG_OSD_E", *order);
+        return QBP_OK;
+    }
+    if (mc && !(flags & QBP_FLAG_OSD0)) return fail(QBP_E_INVALID, "an OSD method bit without QBP_FLAG_OSD0");
+    *method = mb == QBP_FLAG_OSD_CS ? qbp::OSD_METHOD_CS : qbp::OSD_METHOD_E;
+    const int hi = *method == qbp::OSD_METHOD_CS ? 64 : 12;
+    if (*order < 1 || *order > hi)
+        return fail(QBP_E_INVALID, "OSD-%s order %d out of [1, %d]", *method == qbp::OSD_METHOD_CS ? "CS" : "E",
+                    *order, hi);
+    // order > 0 runs on the one-wavefront kernel only, with its added LDS
+    if (!h->osd_ok || qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) > 64 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "OSD of order > 0 needs a matrix whose rows fit the LDS of one wavefront "
+                                       "(%d x %d does not)", h->m, h->n);
+    return QBP_OK;
+}
+
 // `redo`: the caller's syndromes may lie outside the column space of H (anything but the Monte-Carlo loop, whose
 // syndromes come from errors): the fast kernels then list the records whose sweep says so, and the kernel that
 // follows the reference's row swaps recomputes them (an empty list costs one small launch).
-static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hipStream_t s, bool redo = false)
+static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hipStream_t s, bool redo = false,
+                      int method = 0, int order = 0)
 {
     O.m = h->m; O.n = h->n; O.W = h->osd_W; O.NP = h->osd_NP;
     O.row_ptr = h->d_row_ptr.p; O.col_idx = h->d_col_idx.p;
@@ -1393,6 +1426,11 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
         Wk.At = h->d_osd_At.p; Wk.sol = h->d_osd_sol.p; Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
         const int rpt = m <= 1024 ? 1 : m <= 2048 ? 2 : m <= 4096 ? 4 : 8;
         HIP_TRY(qbp::launch_osd_blocked(rpt, (unsigned)grid, lds, O, Wk, s));
+    } else if (method) {
+        // order w (parse_osd_flags has checked osd_ok and the LDS)
+        const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
+        const size_t olds = (qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
+        HIP_TRY(qbp::launch_osd_order(h->osd_W + 1, (unsigned)grid, olds, O, method, order, s));
     } else {
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
         HIP_TRY(qbp::launch_osd_small(h->osd_W + 1, (unsigned)grid, (size_t)h->osd_lds, O, s));
@@ -1447,6 +1485,55 @@ try {
 }
 QBP_ABI_CATCH
 
+int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                         const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    int method = 0, order = 0;
+    int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
+    if (rc) return rc;
+    if (!method) return qbp_osd0_batch_device(h, d_syndromes, d_llr, d_hard, B, d_solution, stream);
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_llr || !d_hard || !d_solution) return fail(QBP_E_INVALID, "null pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    qbp::OsdParams O{};
+    O.count = B; O.syndromes = d_syndromes; O.llr = d_llr; O.hard = d_hard; O.solution = d_solution;
+    return osd_launch(h, O, B, static_cast<hipStream_t>(stream), true, method, order);
+}
+QBP_ABI_CATCH
+
+int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
+                  int64_t B, uint8_t* solution)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    int method = 0, order = 0;
+    int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
+    if (rc) return rc;
+    if (!method) return qbp_osd0_batch(h, syndromes, llr, hard, B, solution);
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_llr.reserve(b * n));
+    HIP_TRY(h->d_hard.reserve(b * n));
+    HIP_TRY(h->d_sol.reserve(b * n));
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
+    rc = qbp_osd_batch_device(h, osd_flags, h->d_syn.p, h->d_llr.p, h->d_hard.p, B, h->d_sol.p, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
                        double p, int32_t draws, uint64_t seed, int64_t trial_begin,
                        int64_t trial_end, const uint8_t* d_errors_in, const double* d_prior, int32_t max_iter,
@@ -1456,6 +1543,11 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     const int64_t T = trial_end - trial_begin;
     int rc = check_decode_args(h, T, max_iter, variant);
     if (rc) return rc;
+    // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
+    int osd_method = 0, osd_order = 0;
+    rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order);
+    if (rc) return rc;
+    flags &= ~(OSD_ORDER_BITS | OSD_METHOD_BITS);
     if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
     if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", draws);
     if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", p);
@@ -1491,7 +1583,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
         O.errors = h->d_fail_err.p; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
         O.counters = reinterpret_cast<long long*>(d_counters);
-        return osd_launch(h, O, T, s);
+        return osd_launch(h, O, T, s, false, osd_method, osd_order);
     };
     if (!h->fused_ok || h->opt_kernel == 2 || h->opt_force_generic) {
         // matrices beyond the on-chip kernel: the whole loop inside the general-H kernel

@@ -51,6 +51,9 @@ hipError_t launch_stream(int variant, unsigned grid, const StreamParams& P, cons
                          const int32_t* svar, const int32_t* sedge, hipStream_t s);
 // qbp_tu_osd.hip
 hipError_t launch_osd_small(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, hipStream_t s);
+// method: OSD_METHOD_CS / OSD_METHOD_E (qbp_osd_order.hpp), order >= 1
+hipError_t launch_osd_order(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, int method, int order,
+                            hipStream_t s);
 hipError_t launch_osd_big(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_osd_blocked(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                               const OsdBigWorkspace& Wk, hipStream_t s);

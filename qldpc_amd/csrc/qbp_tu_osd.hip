@@ -1,4 +1,5 @@
-// libqbp.so, translation unit of the OSD-0 kernels (qbp_osd.hpp) and the histogram kernels (qbp_hist.hpp).
+// libqbp.so, translation unit of the OSD kernels (qbp_osd.hpp: OSD-0, qbp_osd_order.hpp: order w) and the
+// histogram kernels (qbp_hist.hpp).
 #define QBP_DEFINE_KERNELS 1
 #include <hip/hip_runtime.h>
 
@@ -6,6 +7,7 @@
 #include "qbp_hist.hpp"
 #include "qbp_launch.hpp"
 #include "qbp_osd.hpp"
+#include "qbp_osd_order.hpp"
 
 namespace qbp {
 
@@ -19,6 +21,20 @@ hipError_t launch_osd_small(int words_per_row, unsigned grid, size_t lds, const 
         QBP_OSD_CASE(7); QBP_OSD_CASE(8); QBP_OSD_CASE(9); QBP_OSD_CASE(10); QBP_OSD_CASE(11);
 #undef QBP_OSD_CASE
         default: hipLaunchKernelGGL(osd0_kernel<0>, dim3(grid), dim3(64), lds, s, O);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_osd_order(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, int method, int order,
+                            hipStream_t s)
+{
+    switch (words_per_row) {
+#define QBP_OSD_CASE(WW) \
+    case WW: hipLaunchKernelGGL(osd_order_kernel<WW>, dim3(grid), dim3(64), lds, s, O, method, order); break
+        QBP_OSD_CASE(2); QBP_OSD_CASE(3); QBP_OSD_CASE(4); QBP_OSD_CASE(5); QBP_OSD_CASE(6);
+        QBP_OSD_CASE(7); QBP_OSD_CASE(8); QBP_OSD_CASE(9); QBP_OSD_CASE(10); QBP_OSD_CASE(11);
+#undef QBP_OSD_CASE
+        default: hipLaunchKernelGGL(osd_order_kernel<0>, dim3(grid), dim3(64), lds, s, O, method, order);
     }
     return hipGetLastError();
 }

@@ -47,13 +47,27 @@ def summarize(counters: np.ndarray) -> dict:
     return c
 
 
+def osd_run_flags(osd, osd_method="cs", osd_order=0) -> int:
+    """Flags of the OSD pass of a sweep: 0 without OSD, FLAG_OSD0 for OSD-0 (order 0), else order-w OSD
+    (``_lib.osd_flags``).  ValueError for an order without ``osd`` or a method / order out of range."""
+    fl = _lib.osd_flags(osd_method, osd_order)          # (validates method and order)
+    if not osd:
+        if int(osd_order) != 0:
+            raise ValueError(f"an OSD order ({osd_order}) needs osd=True")
+        return 0
+    return fl
+
+
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
-              alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, rank=0, world=1, device=0,
-              runner=None, all_reduce=None):
+              alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1,
+              device=0, runner=None, all_reduce=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
 
+    ``osd``: OSD on the trials BP does not converge on -- OSD-0 with ``osd_order`` 0, else order-w OSD by
+    ``osd_method`` ("cs" or "e"; include/qbp.h).
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -65,7 +79,6 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev)
         priors = [torch.from_numpy(prior_of(p, code.n)).to(dev) for p in ps]
-        flags = _lib.FLAG_OSD0 if osd else 0
         step = dec.mc_osd_step() if osd else 1 << 40         # OSD keeps per-trial records
         for i, p in enumerate(ps):
             begin, end = shard_range(trials, rank, world)
@@ -100,12 +113,20 @@ def main(argv=None):
     ap.add_argument("--damping", type=float, default=1.0)
     ap.add_argument("--clip-llr", type=float, default=20.0)
     ap.add_argument("--osd", action="store_true", help="OSD-0 on the trials BP does not converge on")
+    ap.add_argument("--osd-method", choices=("cs", "e"), default="cs",
+                    help="with --osd-order W >= 1: combination sweep or exhaustive search")
+    ap.add_argument("--osd-order", type=int, default=0,
+                    help="with --osd: order-w OSD instead of OSD-0 (cs: 1..64, e: 1..12)")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a launcher: start N ranks (one per GPU) and reduce over RCCL")
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL; gloo only for rehearsals")
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank on cuda:0")
     args = ap.parse_args(argv)
+    try:
+        osd_run_flags(args.osd, args.osd_method, args.osd_order)
+    except ValueError as e:
+        ap.error(str(e))
 
     import sys
     from . import launch
@@ -133,7 +154,8 @@ def main(argv=None):
     t0 = time.perf_counter()
     run_sweep(args.code, args.p[:1], min(args.trials, 4096), draws=args.draws, seed=args.seed,
               max_iter=args.max_iter, variant=variant, alpha=args.alpha, damping=args.damping,
-              clip_llr=args.clip_llr, osd=args.osd, rank=0, world=1, device=local)
+              clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
+              rank=0, world=1, device=local)
     t_setup = time.perf_counter() - t0
     if world > 1:
         import torch.distributed as dist
@@ -141,8 +163,8 @@ def main(argv=None):
     t0 = time.perf_counter()
     table = run_sweep(args.code, args.p, args.trials, draws=args.draws, seed=args.seed,
                       max_iter=args.max_iter, variant=variant, alpha=args.alpha,
-                      damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, rank=rank,
-                      world=world, device=local)
+                      damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
+                      osd_order=args.osd_order, rank=rank, world=world, device=local)
     dt = time.perf_counter() - t0
     if rank == 0:
         rows = []
@@ -159,7 +181,7 @@ def main(argv=None):
             with open(args.out, "w") as f:
                 json.dump({"code": args.code, "trials": args.trials, "max_iter": args.max_iter,
                            "draws": args.draws, "seed": args.seed, "variant": args.variant,
-                           "osd": args.osd,
+                           "osd": args.osd, "osd_method": args.osd_method, "osd_order": args.osd_order,
                            "world_size": world, "seconds": dt, "setup_seconds": t_setup, "points": rows},
                           f, indent=1)
     if world > 1:

@@ -14,6 +14,10 @@ solution whenever that solution reproduces the syndrome (OSD_enhanced.py "if np.
 syndrome in the column space of H, i.e. every syndrome that comes from an error.  The mirror below
 therefore is OSD-0 on the GPU for every ``order``; only an INCONSISTENT syndrome with ``order > 0``
 would reach the reference's combinatorial search, which is not implemented here.
+
+A real higher-order OSD -- the OSD-0 solution, then a search over flip sets of the least reliable non-pivot
+columns (combination sweep "cs" or exhaustive "e", include/qbp.h qbp_osd_batch) -- is ``performOSD_order`` /
+``performOSD_order_batch`` (no reference counterpart: the reference's order-7 call returns OSD-0).
 """
 from __future__ import annotations
 
@@ -99,3 +103,20 @@ def performOSD_enhanced(H, syndrome, llr, hard, order=0, max_combinations=None):
         return sol                                   # the reference returns here as well
     raise NotImplementedError("performOSD_enhanced(order > 0) on a syndrome outside the column space "
                               "of H: the reference's combinatorial search is not implemented")
+
+
+def performOSD_order(H, syndrome, llr, hard, order, method="cs"):
+    """Order-w OSD of one decoder output on the GPU (include/qbp.h, qbp_osd_batch): int64 vector like
+    ``performOSD``; order 0 is OSD-0."""
+    dec = decoder_for(H)
+    syn = (np.asarray(syndrome).astype(np.int64) % 2).astype(np.uint8)
+    hd = (np.asarray(hard).astype(np.int64) % 2).astype(np.uint8)
+    l = np.asarray(llr, dtype=np.float64)
+    if syn.shape != (dec.m,) or hd.shape != (dec.n,) or l.shape != (dec.n,):
+        raise ValueError(f"expected syndrome ({dec.m},), llr ({dec.n},), hard ({dec.n},)")
+    return dec.osd(syn[None, :], l[None, :], hd[None, :], method=method, order=order)[0].astype(np.int64)
+
+
+def performOSD_order_batch(H, syndromes, llrs, hards, order, method="cs"):
+    """Batch form of ``performOSD_order``: uint8[B, n] solutions."""
+    return decoder_for(H).osd(syndromes, llrs, hards, method=method, order=order)

@@ -3,7 +3,8 @@ reference's result schema.
 
 For every code and physical error rate: ``trials`` Monte-Carlo trials (errors = XOR of two
 Bernoulli(p) draws, paperResults_GPU.py:96-105), BP, optional OSD-0 on the non-converged trials
-(paperResults.py:73-77; the GPU script's OSD-w(7) is not accelerated), classification, counters
+(paperResults.py:73-77; the GPU script's OSD-w(7) call is OSD-0 in the reference; ``--osd-order 7`` runs a real
+order-7 OSD), classification, counters
 (:113-151).  One process per GPU; trials are sharded and the counter table is reduced once with
 RCCL (``qldpc_amd.mc.run_sweep``).
 
@@ -69,7 +70,11 @@ def main(argv=None):
     ap.add_argument("--max-iter", type=int, default=150)                       # :109
     ap.add_argument("--draws", type=int, default=2, choices=(1, 2))            # :96-105
     ap.add_argument("--osd", type=int, default=0, choices=(-1, 0),
-                    help="0: OSD-0 on BP failures (paperResults.py:77); -1: BP only")
+                    help="0: OSD on BP failures (OSD-0 as paperResults.py:77 unless --osd-order); -1: BP only")
+    ap.add_argument("--osd-method", choices=("cs", "e"), default="cs",
+                    help="with --osd-order W >= 1: combination sweep or exhaustive search")
+    ap.add_argument("--osd-order", type=int, default=0,
+                    help="order-w OSD instead of OSD-0 (cs: 1..64, e: 1..12); 0: OSD-0")
     ap.add_argument("--seed", type=int, default=0)                             # :33-34
     ap.add_argument("--out", default="data/BPOSD_MI355X")
     ap.add_argument("--plot", action="store_true", help="two-panel figure as :169-185")
@@ -78,6 +83,12 @@ def main(argv=None):
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL; gloo only for rehearsals")
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank on cuda:0")
     args = ap.parse_args(argv)
+    try:
+        mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order)
+    except ValueError as e:
+        ap.error(str(e))
+    osd_name = ("no OSD" if args.osd != 0 else "OSD-0" if args.osd_order == 0
+                else f"OSD-{args.osd_method.upper()}-{args.osd_order}")
 
     import sys
     from . import launch
@@ -101,7 +112,7 @@ def main(argv=None):
     if rank == 0:
         print(f"GPU Available: True ({world} x MI355X)")
         print(f"Running {args.trials} trials per point, BP maxIter {args.max_iter}, "
-              f"{'OSD-0' if args.osd == 0 else 'no OSD'}")
+              f"{osd_name}")
         print("=" * 60)
     tables = {}
     total_start = time.time()
@@ -111,8 +122,8 @@ def main(argv=None):
             print(f"\nProcessing code: {name}")
         t0 = time.time()
         tables[name] = mc.run_sweep(name, args.p, args.trials, draws=args.draws, seed=args.seed,
-                                    max_iter=args.max_iter, osd=args.osd == 0, rank=rank,
-                                    world=world, device=local)
+                                    max_iter=args.max_iter, osd=args.osd == 0, osd_method=args.osd_method,
+                                    osd_order=args.osd_order, rank=rank, world=world, device=local)
         if rank == 0:
             dt = time.time() - t0
             for p, row in zip(args.p, tables[name]):
@@ -122,7 +133,8 @@ def main(argv=None):
         total = time.time() - total_start
         print(f"\n{'=' * 60}\nTotal time: {total:.1f}s ({total / 60:.1f} min)")
         meta = dict(physicalErrorRates=args.p, trials=args.trials, maxIter=args.max_iter,
-                    draws=args.draws, osd=args.osd, seed=args.seed, world_size=world,
+                    draws=args.draws, osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
+                    osd_decoder=osd_name, seed=args.seed, world_size=world,
                     noise="XOR of two Bernoulli(p) draws" if args.draws == 2 else "Bernoulli(p)",
                     decoder="sum-product BP (libqbp, MI355X)", seconds=total,
                     counters={n: tables[n].tolist() for n in tables},
