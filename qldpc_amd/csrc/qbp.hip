@@ -69,10 +69,15 @@ struct DeviceScope {
     DeviceScope& operator=(const DeviceScope&) = delete;
 };
 
+// Device memory owned by the handle, freed with it (qbp_destroy deletes the handle on its device).
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
     hipError_t reserve(size_t count)
     {
         if (count <= cap) return hipSuccess;
@@ -82,7 +87,13 @@ struct DevBuf {
         if (e == hipSuccess) cap = count;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    // a host table copied to the device (synchronously: the vector may go out of scope on return)
+    hipError_t upload(const std::vector<T>& v)
+    {
+        hipError_t e = reserve(v.size());
+        if (e == hipSuccess && !v.empty()) e = hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
 };
 
 }  // namespace
@@ -154,7 +165,7 @@ struct qbp_handle {
     // OSD-0
     bool osd_ok = false;            // fits the one-wavefront kernel (matrix rows in LDS)
     int opt_osd_big = 0;            // QBP_OPT_OSD_BIG
-    bool osd_big_ready = false;     // tables of the workgroup-per-syndrome kernel built (lazily)
+    bool osd_ready = false;         // d_hbits and osd_rank built (osd_prepare)
     int osd_W = 0, osd_NP = 0, osd_lds = 0, osd_rank = 0;
     DevBuf<uint32_t> d_osd_At;
     DevBuf<int32_t> d_osd_piv, d_osd_idx, d_osd_posn;
@@ -491,7 +502,7 @@ int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bo
     return QBP_OK;
 }
 
-int check_decode_args(qbp_handle* h, long long B, int max_iter, int variant, bool need_fused = false)
+int check_decode_args(qbp_handle* h, long long B, int max_iter, int variant)
 {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", B);
@@ -499,26 +510,28 @@ int check_decode_args(qbp_handle* h, long long B, int max_iter, int variant, boo
         return fail(QBP_E_INVALID, "max_iter must be >= 1 (got %d); the reference raises "
                                    "UnboundLocalError for maxIter=0", max_iter);
     if (variant < 0 || variant > 2) return fail(QBP_E_INVALID, "unknown variant %d", variant);
-    if (need_fused && !h->fused_ok)
-        return fail(QBP_E_UNSUPPORTED,
-                    "H (m=%d, max row degree %d, max column degree %d) does not fit the on-chip "
-                    "kernel (m <= 1024, row degree <= %d, column degree <= %d)",
-                    h->m, h->max_row_deg, h->max_col_deg, DC_WIDE, DV_WIDE);
     return QBP_OK;
 }
 
-void fill_static(qbp_handle* h, FusedParams& P, const LaunchCfg& cfg, bool f_order = false)
+// The BP kernel of a call: 1 on-chip, 2 general-H, 3 streaming, or QBP_E_UNSUPPORTED when the on-chip kernel is
+// forced on a matrix that does not fit it.  `B`: syndromes (trials) of the call; `col_mode`: resolve_column_order.
+int bp_kernel(const qbp_handle* h, long long B, uint32_t flags, int col_mode, bool mc)
 {
-    P.m = h->m; P.n = h->n;
-    P.S = cfg.S; P.slot_stride = cfg.slot_stride;
-    P.r0_table = cfg.r0_table;
-    P.padded = h->padded ? 1 : 0;
-    P.n_words4 = (h->n + 3) / 4;
-    P.tab_var = h->d_tab_var.p;
-    P.tab_nbr = f_order ? h->f_order.tab_nbr.p : h->d_tab_nbr.p;
-    P.tab_writer = f_order ? h->f_order.tab_writer.p : h->d_tab_writer.p;
-    P.iso_vars = h->d_iso.p; P.n_iso = h->n_iso;
-    P.work_counter = h->d_work_counter.p;
+    const int forced = h->opt_force_generic ? 2 : h->opt_kernel;
+    // Monte-Carlo: the streaming kernel has no such mode, and a matrix beyond the on-chip kernel runs the whole
+    // loop inside the general-H kernel whatever was asked for
+    if (mc) return forced == 2 || !h->fused_ok ? 2 : 1;
+    if (forced == 1 && !h->fused_ok) return QBP_E_UNSUPPORTED;
+    // automatic: the on-chip kernel when the matrix fits; otherwise one workgroup per syndrome (general-H), except
+    // for small graphs in batches that fill the chip with one LANE per syndrome, where the streaming kernel is ahead
+    // (tools/bench_generic.py: [[288,12,18]], 262144 syndromes: 3.7e6 against 2.6e6 /s; larger graphs keep their
+    // messages in L2 / Infinity Cache under the general-H kernel and win there at every batch size measured)
+    int kernel = forced ? forced : h->fused_ok ? 1 : (B >= 131072 && h->E <= 2048) ? 3 : 2;
+    // numpy's pairwise column sums only differ from 8 entries per column on; those matrices never
+    // fit the on-chip kernel, and only the general-H kernel implements that order
+    if ((flags & QBP_FLAG_PAIRWISE_COLSUM) && h->max_col_deg >= 8) kernel = 2;
+    if (col_mode == 2) kernel = 2;           // two column orders in one launch: the general-H kernel only
+    return kernel;
 }
 
 // Column-sum order of a decode call (include/qbp.h, QBP_FLAG_DENSE_F_COLSUM*): clears the two flag bits and
@@ -552,16 +565,14 @@ int resolve_column_order(qbp_handle* h, unsigned& flags, const double* host_prio
         const int rc = build_tables(h->row_ptr.data(), h->col_idx.data(), h->m, h->n, T, 1);
         if (rc == QBP_E_UNSUPPORTED) { F.state = -1; return rc; }
         if (rc) return rc;
-        hipError_t e1 = hipSuccess;
-        auto up = [&](auto& buf, const auto& vec) {
-            if (e1 != hipSuccess) return;
-            e1 = buf.reserve(vec.size());
-            if (e1 == hipSuccess && !vec.empty())
-                e1 = hipMemcpy(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice);
-        };
-        if (T.fused_ok) { up(F.tab_nbr, T.tab_nbr); up(F.tab_writer, T.tab_writer); }
-        up(F.col_edge, T.col_edge); up(F.sedge, T.sedge); up(F.vpos, T.vpos); up(F.vrow, T.vrow);
-        if (e1 != hipSuccess) return fail(QBP_E_HIP, "upload of the column-order tables failed: %s", hipGetErrorString(e1));
+        if (T.fused_ok) {
+            HIP_TRY(F.tab_nbr.upload(T.tab_nbr));
+            HIP_TRY(F.tab_writer.upload(T.tab_writer));
+        }
+        HIP_TRY(F.col_edge.upload(T.col_edge));
+        HIP_TRY(F.sedge.upload(T.sedge));
+        HIP_TRY(F.vpos.upload(T.vpos));
+        HIP_TRY(F.vrow.upload(T.vrow));
         F.state = 1;
     }
     if (F.state < 0)
@@ -630,31 +641,74 @@ static GenericGeom generic_geometry(const qbp_handle* h, long long B, bool inpla
     return g;
 }
 
-static int generic_launch(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
-                          int max_iter, int variant, double alpha, double damping, double clip_llr,
-                          unsigned flags, uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters,
-                          double* d_llr, double* d_dump, int dump_iter, double dump_div, hipStream_t s,
-                          const qbp::GenericParams* mc = nullptr, int col_mode = 0)
+// Monte-Carlo arguments of a BP launch (the on-chip and general-H kernels read the same fields).
+struct McArgs {
+    const unsigned long long* lx_cols;
+    long long trial_begin;
+    unsigned long long seed;
+    unsigned threshold;
+    int draws, half_distance;
+    long long* counters;
+    const uint8_t* errors_in;
+    // failure records for the OSD pass (QBP_FLAG_OSD0), else null
+    long long* fail_list;
+    unsigned long long* fail_count;
+    uint8_t *fail_syn, *fail_hard, *fail_err;
+    double* fail_llr;
+};
+
+template <typename Params>
+static void put_mc(Params& P, const McArgs& a)
 {
-    if ((flags & QBP_FLAG_PAIRWISE_COLSUM) && h->max_col_deg > qbp::GENERIC_PAIRWISE_MAX_COL)
+    P.lx_cols = a.lx_cols; P.trial_begin = a.trial_begin; P.seed = a.seed; P.threshold = a.threshold;
+    P.draws = a.draws; P.half_distance = a.half_distance; P.counters = a.counters; P.errors_in = a.errors_in;
+    P.fail_list = a.fail_list; P.fail_count = a.fail_count; P.fail_syn = a.fail_syn;
+    P.fail_llr = a.fail_llr; P.fail_hard = a.fail_hard; P.fail_err = a.fail_err;
+}
+
+// Per-call arguments of a BP launch, whichever kernel runs it (device pointers; outputs may be null).
+struct BpCall {
+    const uint8_t* syndromes = nullptr;
+    const double* prior = nullptr;
+    long long B = 0;
+    int max_iter = 0, variant = 0;
+    double alpha = 1.0, damping = 1.0, clip_llr = 0.0;
+    unsigned flags = 0;
+    uint8_t* hard = nullptr;
+    uint8_t* converged = nullptr;
+    int32_t* iters = nullptr;
+    double* llr = nullptr;
+    double* dump = nullptr;                  // message dump (general-H kernel only)
+    int dump_iter = 0;
+    double dump_div = 1.0;
+    int col_mode = 0;                        // resolve_column_order
+    const McArgs* mc = nullptr;              // Monte-Carlo launch
+};
+
+static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
+{
+    if ((c.flags & QBP_FLAG_PAIRWISE_COLSUM) && h->max_col_deg > qbp::GENERIC_PAIRWISE_MAX_COL)
         return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_PAIRWISE_COLSUM supports column weights up to %d (got %d)",
                     qbp::GENERIC_PAIRWISE_MAX_COL, h->max_col_deg);
     // one launch hands out its syndromes through a 32-bit counter
-    constexpr int64_t MAX_LAUNCH = (int64_t)1 << 30;
-    if (B > MAX_LAUNCH) {
-        if (!mc)
+    constexpr long long MAX_LAUNCH = (long long)1 << 30;
+    if (c.B > MAX_LAUNCH) {
+        if (!c.mc)
             return fail(QBP_E_UNSUPPORTED, "the general-H kernel decodes at most 2^30 syndromes per call (got %lld)",
-                        (long long)B);
-        for (int64_t off = 0; off < B; off += MAX_LAUNCH) {     // Monte-Carlo: trial ranges of any length
-            qbp::GenericParams part = *mc;
-            part.trial_begin += off;
-            const int rc = generic_launch(h, nullptr, d_prior, std::min(MAX_LAUNCH, B - off), max_iter, variant,
-                                          alpha, damping, clip_llr, flags, nullptr, nullptr, nullptr, nullptr,
-                                          nullptr, 0, 1.0, s, &part);
+                        c.B);
+        for (long long off = 0; off < c.B; off += MAX_LAUNCH) {     // Monte-Carlo: trial ranges of any length
+            McArgs mc = *c.mc;
+            mc.trial_begin += off;
+            BpCall part = c;
+            part.B = std::min(MAX_LAUNCH, c.B - off);
+            part.mc = &mc;
+            const int rc = generic_launch(h, part, s);
             if (rc) return rc;
         }
         return QBP_OK;
     }
+    const long long B = c.B;
+    const int variant = c.variant, col_mode = c.col_mode;
     const size_t E = (size_t)std::max(h->E, 1), n = (size_t)h->n;
     const bool inplace = QBP_GENERIC_INPLACE != 0 && variant == QBP_SUM_PRODUCT;
     const GenericGeom g = generic_geometry(h, B, inplace);
@@ -667,7 +721,7 @@ static int generic_launch(qbp_handle* h, const uint8_t* d_syndromes, const doubl
     }
     if (inplace) HIP_TRY(h->d_wsV.reserve((size_t)g.grid * n));
     HIP_TRY(h->d_prior_sorted.reserve(n));
-    HIP_TRY(qbp::launch_permute_prior(d_prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
+    HIP_TRY(qbp::launch_permute_prior(c.prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
     qbp::GenericParams G{};
     G.m = h->m; G.n = h->n; G.E = h->E;
     G.srow = h->d_srow.p; G.srow_e0 = h->d_srow_e0.p; G.srow_deg = h->d_srow_deg.p;
@@ -692,28 +746,61 @@ static int generic_launch(qbp_handle* h, const uint8_t* d_syndromes, const doubl
     G.prior_sorted = h->d_prior_sorted.p;
     G.lds_tables = g.lds_tables ? 1 : 0;
     G.r_split = g.r_split;
-    G.syndromes = d_syndromes; G.B = B; G.max_iter = max_iter; G.flags = flags;
-    G.alpha = alpha; G.damping = damping; G.clip_llr = clip_llr;
-    G.hard = d_hard; G.converged = d_converged; G.iters = d_iters; G.llr = d_llr;
+    G.syndromes = c.syndromes; G.B = B; G.max_iter = c.max_iter; G.flags = c.flags;
+    G.alpha = c.alpha; G.damping = c.damping; G.clip_llr = c.clip_llr;
+    G.hard = c.hard; G.converged = c.converged; G.iters = c.iters; G.llr = c.llr;
     G.wsQ = h->d_wsQ.p; G.wsR = h->d_wsR.p; G.wsV = h->d_wsV.p;
     G.work_counter = h->d_work_counter.p;
-    if (B > (int64_t)g.grid)     // (else every index it can yield is >= B whatever it holds)
+    if (B > (long long)g.grid)     // (else every index it can yield is >= B whatever it holds)
         HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
-    G.dump_R = d_dump; G.dump_iter = dump_iter; G.dump_div = dump_div;
+    G.dump_R = c.dump; G.dump_iter = c.dump_iter; G.dump_div = c.dump_div;
     h->last_threads = g.threads; h->last_lds = (int)g.lds; h->last_grid = g.grid;
-    if (mc) {
+    if (c.mc) {
         // Monte-Carlo mode: per-workgroup scratch for the sampled error
         HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
-        G.lx_cols = mc->lx_cols; G.trial_begin = mc->trial_begin; G.seed = mc->seed;
-        G.threshold = mc->threshold; G.draws = mc->draws; G.half_distance = mc->half_distance;
-        G.counters = mc->counters; G.wsE = h->d_wsE.p;
-        G.errors_in = mc->errors_in;
-        G.fail_list = mc->fail_list; G.fail_count = mc->fail_count; G.fail_syn = mc->fail_syn;
-        G.fail_llr = mc->fail_llr; G.fail_hard = mc->fail_hard; G.fail_err = mc->fail_err;
-        HIP_TRY(qbp::launch_generic(true, g.mem, variant, G, g.grid, g.threads, g.lds, s));
-        return QBP_OK;
+        put_mc(G, *c.mc);
+        G.wsE = h->d_wsE.p;
     }
-    HIP_TRY(qbp::launch_generic(false, g.mem, variant, G, g.grid, g.threads, g.lds, s));
+    HIP_TRY(qbp::launch_generic(c.mc != nullptr, g.mem, variant, G, g.grid, g.threads, g.lds, s));
+    return QBP_OK;
+}
+
+// OSD fits the one-wavefront kernel: the matrix rows in 64 KiB of LDS, and a lane tracks its rows in a 32-bit mask.
+static bool osd_one_wave(const qbp_handle* h)
+{
+    return qbp::osd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) <= 64 * 1024 && h->m <= 64 * 32;
+}
+
+// The rows of H bit-packed into osd_W 32-bit words each (d_hbits, read by every OSD kernel) and the rank of H over
+// GF(2) (Gaussian elimination on the host, once per code): the elimination loop of the kernels can stop as soon
+// as that many pivots are found.  qbp_create builds them for the one-wavefront kernel; matrices beyond it build
+// them on first use (about half a second for 2592 x 7776), which most users of such matrices never make.
+static int osd_prepare(qbp_handle* h)
+{
+    if (h->osd_ready) return QBP_OK;
+    const int m = h->m, n = h->n, W = h->osd_W;
+    std::vector<uint32_t> hbits((size_t)m * W, 0u);
+    for (int c = 0; c < m; ++c)
+        for (int e = h->row_ptr[c]; e < h->row_ptr[c + 1]; ++e)
+            hbits[(size_t)c * W + (h->col_idx[e] >> 5)] |= 1u << (h->col_idx[e] & 31);
+    HIP_TRY(h->d_hbits.upload(hbits));
+    std::vector<uint32_t> A = hbits;
+    int rank = 0;
+    for (int col = 0; col < n && rank < m; ++col) {
+        const int wi = col >> 5;
+        const uint32_t bit = 1u << (col & 31);
+        int piv = -1;
+        for (int r = rank; r < m; ++r) if (A[(size_t)r * W + wi] & bit) { piv = r; break; }
+        if (piv < 0) continue;
+        // (rows rank.. are zero left of `col`)
+        if (piv != rank) for (int w = wi; w < W; ++w) std::swap(A[(size_t)piv * W + w], A[(size_t)rank * W + w]);
+        for (int r = rank + 1; r < m; ++r)
+            if (A[(size_t)r * W + wi] & bit)
+                for (int w = wi; w < W; ++w) A[(size_t)r * W + w] ^= A[(size_t)rank * W + w];
+        ++rank;
+    }
+    h->osd_rank = rank;
+    h->osd_ready = true;
     return QBP_OK;
 }
 
@@ -757,27 +844,20 @@ try {
     HIP_TRY(hipGetDeviceProperties(&prop, device));
     h->num_cu = prop.multiProcessorCount;
 
-    hipError_t e1 = hipSuccess;
-    auto up = [&](auto& buf, const auto& vec) {
-        if (e1 != hipSuccess) return;
-        e1 = buf.reserve(vec.size());
-        if (e1 == hipSuccess && !vec.empty())
-            e1 = hipMemcpy(buf.p, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice);
-    };
     if (T.fused_ok) {
-        up(h->d_tab_var, T.tab_var);
-        up(h->d_tab_nbr, T.tab_nbr);
-        up(h->d_tab_writer, T.tab_writer);
+        HIP_TRY(h->d_tab_var.upload(T.tab_var));
+        HIP_TRY(h->d_tab_nbr.upload(T.tab_nbr));
+        HIP_TRY(h->d_tab_writer.upload(T.tab_writer));
     }
-    up(h->d_iso, T.iso);
-    up(h->d_col_ptr, T.col_ptr);
-    up(h->d_col_edge, T.col_edge);
-    up(h->d_epos, T.epos);
-    up(h->d_cpos, T.cpos);
-    up(h->d_long_edge_row, T.long_edge_row);
-    up(h->d_vpos, T.vpos);
-    up(h->d_vrow, T.vrow);
-    up(h->d_lcol_ptr, T.lcol_ptr);
+    HIP_TRY(h->d_iso.upload(T.iso));
+    HIP_TRY(h->d_col_ptr.upload(T.col_ptr));
+    HIP_TRY(h->d_col_edge.upload(T.col_edge));
+    HIP_TRY(h->d_epos.upload(T.epos));
+    HIP_TRY(h->d_cpos.upload(T.cpos));
+    HIP_TRY(h->d_long_edge_row.upload(T.long_edge_row));
+    HIP_TRY(h->d_vpos.upload(T.vpos));
+    HIP_TRY(h->d_vrow.upload(T.vrow));
+    HIP_TRY(h->d_lcol_ptr.upload(T.lcol_ptr));
     std::copy(std::begin(T.gcol_base), std::end(T.gcol_base), h->gcol_base);
     {   // work items of the general-H kernel: every weight class padded to whole wavefronts
         int off = 0;
@@ -794,53 +874,30 @@ try {
         h->cpad_off[qbp::GENERIC_MAX_COL_CLASS + 1] = off;
     }
     std::copy(std::begin(T.row_base), std::end(T.row_base), h->row_base);
-    up(h->d_srow, T.srow);
-    up(h->d_srow_e0, T.srow_e0);
-    up(h->d_srow_deg, T.srow_deg);
-    up(h->d_svar, T.svar);
-    up(h->d_sedge, T.sedge);
+    HIP_TRY(h->d_srow.upload(T.srow));
+    HIP_TRY(h->d_srow_e0.upload(T.srow_e0));
+    HIP_TRY(h->d_srow_deg.upload(T.srow_deg));
+    HIP_TRY(h->d_svar.upload(T.svar));
+    HIP_TRY(h->d_sedge.upload(T.sedge));
     std::copy(std::begin(T.row_off), std::end(T.row_off), h->row_off);
     std::copy(std::begin(T.col_off), std::end(T.col_off), h->col_off);
     std::copy(std::begin(T.col_edge_base), std::end(T.col_edge_base), h->col_edge_base);
-    up(h->d_row_ptr, h->row_ptr);
-    up(h->d_col_idx, h->col_idx);
-    {   // OSD-0: bit-packed rows of H and its CSR
-        const int W = (n + 31) / 32;
-        int NP = 1;
-        while (NP < n) NP <<= 1;
-        const size_t lds = qbp::osd_lds_bytes(m, n, W, NP);
-        h->osd_W = W; h->osd_NP = NP; h->osd_lds = (int)((lds + 15) & ~(size_t)15);
-        h->osd_ok = lds <= 64 * 1024 && m <= 64 * 32;   // (a lane tracks its rows in a 32-bit mask)
-        if (h->osd_ok) {
-            std::vector<uint32_t> hbits((size_t)m * W, 0u);
-            for (int c = 0; c < m; ++c)
-                for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e)
-                    hbits[(size_t)c * W + (col_idx[e] >> 5)] |= 1u << (col_idx[e] & 31);
-            up(h->d_hbits, hbits);
-            // rank of H over GF(2) (bit-packed Gaussian elimination on the host, once per code):
-            // the elimination loop of the kernel can stop as soon as that many pivots are found
-            std::vector<uint32_t> A = hbits;
-            int rank = 0;
-            for (int col = 0; col < n && rank < m; ++col) {
-                const int wi = col >> 5;
-                const uint32_t bit = 1u << (col & 31);
-                int piv = -1;
-                for (int r = rank; r < m; ++r) if (A[(size_t)r * W + wi] & bit) { piv = r; break; }
-                if (piv < 0) continue;
-                if (piv != rank) for (int w = 0; w < W; ++w) std::swap(A[(size_t)piv * W + w], A[(size_t)rank * W + w]);
-                for (int r = rank + 1; r < m; ++r)
-                    if (A[(size_t)r * W + wi] & bit)
-                        for (int w = 0; w < W; ++w) A[(size_t)r * W + w] ^= A[(size_t)rank * W + w];
-                ++rank;
-            }
-            h->osd_rank = rank;
-        }
+    HIP_TRY(h->d_row_ptr.upload(h->row_ptr));
+    HIP_TRY(h->d_col_idx.upload(h->col_idx));
+    // OSD: 32-bit words per row of H, radix-sort size; its GF(2) tables now when the one-wavefront kernel takes it
+    h->osd_W = (n + 31) / 32;
+    h->osd_NP = 1;
+    while (h->osd_NP < n) h->osd_NP <<= 1;
+    h->osd_lds = (int)((qbp::osd_lds_bytes(m, n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15);
+    h->osd_ok = osd_one_wave(h);
+    if (h->osd_ok) {
+        const int rc = osd_prepare(h);
+        if (rc) return rc;
     }
-    if (e1 == hipSuccess) e1 = h->d_work_counter.reserve(1);
-    if (e1 == hipSuccess) e1 = hipMemset(h->d_work_counter.p, 0, sizeof(unsigned long long));
-    if (e1 == hipSuccess) e1 = h->d_fail_count.reserve(1);
-    if (e1 == hipSuccess) e1 = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e1 != hipSuccess) return fail(QBP_E_HIP, "device setup failed: %s", hipGetErrorString(e1));
+    HIP_TRY(h->d_work_counter.reserve(1));
+    HIP_TRY(hipMemset(h->d_work_counter.p, 0, sizeof(unsigned long long)));
+    HIP_TRY(h->d_fail_count.reserve(1));
+    HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     guard.h = nullptr;
     *out = h;
     return QBP_OK;
@@ -884,38 +941,20 @@ void qbp_destroy(qbp_handle* h)
     if (!h) return;
     DeviceScope on_device(h->device);
     if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    h->d_tab_var.release(); h->d_tab_nbr.release(); h->d_tab_writer.release(); h->d_iso.release();
-    h->d_work_counter.release(); h->d_syn.release(); h->d_hard.release(); h->d_conv.release();
-    h->d_iters.release(); h->d_llr.release(); h->d_prior.release();
-    h->d_mathx.release(); h->d_mathy.release(); h->d_part.release(); h->d_edges.release(); h->d_hist.release(); h->d_lx_cols.release(); h->d_counters.release();
     if (h->pin_host) (void)hipHostFree(h->pin_host);
     for (int i = 0; i < 2; ++i) {
         if (h->stage[i]) (void)hipHostFree(h->stage[i]);
         if (h->stage_ev[i]) (void)hipEventDestroy(h->stage_ev[i]);
     }
-    h->d_col_ptr.release(); h->d_col_edge.release(); h->d_wsQ.release(); h->d_wsR.release();
-    h->d_wsV.release(); h->d_wsC.release(); h->d_wsS.release(); h->d_wsE.release(); h->d_svar.release(); h->d_sedge.release();
-    h->d_srow.release(); h->d_srow_e0.release(); h->d_srow_deg.release();
-    h->d_epos.release(); h->d_cpos.release(); h->d_long_edge_row.release(); h->d_wsL.release();
-    h->d_vpos.release(); h->d_vrow.release(); h->d_lcol_ptr.release(); h->d_prior_sorted.release();
-    h->d_hbits.release(); h->d_row_ptr.release(); h->d_col_idx.release(); h->d_sol.release();
-    h->f_order.tab_nbr.release(); h->f_order.tab_writer.release(); h->f_order.col_edge.release();
-    h->f_order.sedge.release(); h->f_order.vpos.release(); h->f_order.vrow.release();
-    h->d_osd_At.release(); h->d_osd_piv.release(); h->d_osd_idx.release(); h->d_osd_sol.release();
-    h->d_osd_posn.release(); h->d_osd_redo.release(); h->d_osd_next.release();
-    h->d_osd_keys.release();
-    h->d_fail_list.release(); h->d_fail_count.release(); h->d_fail_syn.release();
-    h->d_fail_hard.release(); h->d_fail_err.release(); h->d_fail_llr.release();
-    delete h;
+    delete h;                          // (the device buffers free themselves, on this device)
 }
 
-static int stream_launch(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
-                         int max_iter, int variant, double alpha, double damping, double clip_llr,
-                         unsigned flags, uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters,
-                         double* d_llr, hipStream_t s, bool f_order = false)
+static int stream_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 {
     // streaming kernel: one lane per syndrome, messages [edge][syndrome] in a global workspace;
     // long batches go through in chunks that keep the workspace under 16 GiB
+    const long long B = c.B;
+    const bool f_order = c.col_mode == 1;
     const size_t E = (size_t)std::max(h->E, 1), n = (size_t)h->n, m = (size_t)h->m;
     const size_t per_lane = 2 * E * sizeof(double) + n + m;
     long long Bc = (long long)std::min<unsigned long long>(((unsigned long long)16 << 30) / per_lane,
@@ -928,9 +967,9 @@ static int stream_launch(qbp_handle* h, const uint8_t* d_syndromes, const double
     HIP_TRY(h->d_wsS.reserve((size_t)Bc * m));
     qbp::StreamParams P{};
     P.m = h->m; P.n = h->n; P.E = h->E;
-    P.syndromes = d_syndromes; P.B = B; P.Bc = Bc;
-    P.max_iter = max_iter; P.flags = flags; P.alpha = alpha; P.damping = damping; P.clip_llr = clip_llr;
-    P.hard = d_hard; P.converged = d_converged; P.iters = d_iters; P.llr = d_llr;
+    P.syndromes = c.syndromes; P.B = B; P.Bc = Bc;
+    P.max_iter = c.max_iter; P.flags = c.flags; P.alpha = c.alpha; P.damping = c.damping; P.clip_llr = c.clip_llr;
+    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr;
     P.Q = h->d_wsQ.p; P.R = h->d_wsR.p; P.cand = h->d_wsC.p; P.synT = h->d_wsS.p;
     std::copy(std::begin(h->row_off), std::end(h->row_off), P.row_off);
     std::copy(std::begin(h->col_off), std::end(h->col_off), P.col_off);
@@ -940,11 +979,43 @@ static int stream_launch(qbp_handle* h, const uint8_t* d_syndromes, const double
         const long long lanes = std::min<long long>(Bc, B - b0);
         const unsigned grid = (unsigned)((lanes + 255) / 256);
         h->last_threads = 256; h->last_lds = 0; h->last_grid = (int)grid;
-        HIP_TRY(qbp::launch_stream(variant, grid, P, h->d_col_idx.p, h->d_col_ptr.p,
-                                   f_order ? h->f_order.col_edge.p : h->d_col_edge.p, d_prior,
+        HIP_TRY(qbp::launch_stream(c.variant, grid, P, h->d_col_idx.p, h->d_col_ptr.p,
+                                   f_order ? h->f_order.col_edge.p : h->d_col_edge.p, c.prior,
                                    h->d_srow.p, h->d_srow_e0.p, h->d_srow_deg.p, h->d_svar.p,
                                    f_order ? h->f_order.sedge.p : h->d_sedge.p, s));
     }
+    return QBP_OK;
+}
+
+static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
+{
+    const bool mc = c.mc != nullptr, f_order = c.col_mode == 1;
+    LaunchCfg cfg;
+    int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc);
+    if (rc) return rc;
+    FusedParams P{};
+    P.m = h->m; P.n = h->n;
+    P.S = cfg.S; P.slot_stride = cfg.slot_stride;
+    P.r0_table = cfg.r0_table;
+    P.padded = h->padded ? 1 : 0;
+    P.n_words4 = (h->n + 3) / 4;
+    P.tab_var = h->d_tab_var.p;
+    P.tab_nbr = f_order ? h->f_order.tab_nbr.p : h->d_tab_nbr.p;
+    P.tab_writer = f_order ? h->f_order.tab_writer.p : h->d_tab_writer.p;
+    P.iso_vars = h->d_iso.p; P.n_iso = h->n_iso;
+    P.work_counter = h->d_work_counter.p;
+    P.syndromes = c.syndromes; P.prior = c.prior; P.B = c.B;
+    P.max_iter = c.max_iter; P.flags = c.flags;
+    P.alpha = c.alpha; P.damping = c.damping; P.clip_llr = c.clip_llr;
+    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr;
+    if (mc) put_mc(P, *c.mc);
+    // The work counter hands out syndromes beyond the first one of each slot; when every syndrome
+    // is some slot's first one (small decode calls) its value is irrelevant -- any index it yields is
+    // >= B -- and the memset node is skipped (3 us of a 30 us single-syndrome call).
+    if (mc || c.B > (long long)cfg.grid * cfg.S)
+        HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY((c.flags & QBP_FLAG_FAST_MATH) ? qbp::launch_fused_fast_math(mc, c.variant, P, cfg, s)
+                                           : qbp::launch_fused(mc, c.variant, P, cfg, s));
     return QBP_OK;
 }
 
@@ -961,47 +1032,18 @@ try {
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int col_mode = 0;                        // column sums in the order of a Fortran-ordered dense R
-    rc = resolve_column_order(h, flags, nullptr, &col_mode);
+    BpCall c;
+    rc = resolve_column_order(h, flags, nullptr, &c.col_mode);
     if (rc) return rc;
-    const bool f_order = col_mode == 1;
-    // kernel choice: the on-chip kernel when the matrix fits; otherwise one workgroup per syndrome
-    // (general-H), except for small graphs in batches that fill the chip with one LANE per syndrome,
-    // where the streaming kernel is ahead (tools/bench_generic.py: [[288,12,18]], 262144 syndromes:
-    // 3.7e6 against 2.6e6 /s; larger graphs keep their messages in L2 / Infinity Cache under the
-    // general-H kernel and win there at every batch size measured)
-    int kernel = h->opt_kernel;
-    if (h->opt_force_generic) kernel = 2;
-    if (kernel == 1 && !h->fused_ok) return fail(QBP_E_UNSUPPORTED, "H does not fit the on-chip kernel");
-    if (kernel == 0) kernel = h->fused_ok ? 1 : ((B >= 131072 && h->E <= 2048) ? 3 : 2);
-    // numpy's pairwise column sums only differ from 8 entries per column on; those matrices never
-    // fit the on-chip kernel, and only the general-H kernel implements that order
-    if ((flags & QBP_FLAG_PAIRWISE_COLSUM) && h->max_col_deg >= 8) kernel = 2;
-    if (col_mode == 2) kernel = 2;           // two column orders in one launch: the general-H kernel only
+    const int kernel = bp_kernel(h, B, flags, c.col_mode, false);
+    if (kernel < 0) return fail(kernel, "H does not fit the on-chip kernel");
     h->last_kernel = kernel;
-    if (kernel == 3)
-        return stream_launch(h, d_syndromes, d_prior, B, max_iter, variant, alpha, damping, clip_llr, flags,
-                             d_hard, d_converged, d_iters, d_llr, s, f_order);
-    if (kernel == 2)
-        return generic_launch(h, d_syndromes, d_prior, B, max_iter, variant, alpha, damping, clip_llr,
-                              flags, d_hard, d_converged, d_iters, d_llr, nullptr, 0, 1.0, s, nullptr, col_mode);
-    LaunchCfg cfg;
-    rc = make_cfg(h, B, &cfg, (flags & QBP_FLAG_FORCE_FULL) != 0, false);
-    if (rc) return rc;
-    FusedParams P{};
-    fill_static(h, P, cfg, f_order);
-    P.syndromes = d_syndromes; P.prior = d_prior; P.B = B;
-    P.max_iter = max_iter; P.flags = flags;
-    P.alpha = alpha; P.damping = damping; P.clip_llr = clip_llr;
-    P.hard = d_hard; P.converged = d_converged; P.iters = d_iters; P.llr = d_llr;
-    // The work counter hands out syndromes beyond the first one of each slot; when every syndrome
-    // is some slot's first one (small calls) its value is irrelevant -- any index it yields is
-    // >= B -- and the memset node is skipped (3 us of a 30 us single-syndrome call).
-    if (B > (long long)cfg.grid * cfg.S)
-        HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY((flags & QBP_FLAG_FAST_MATH) ? qbp::launch_fused_fast_math(false, variant, P, cfg, s)
-                                         : qbp::launch_fused(false, variant, P, cfg, s));
-    return QBP_OK;
+    c.syndromes = d_syndromes; c.prior = d_prior; c.B = B; c.max_iter = max_iter; c.variant = variant;
+    c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr;
+    if (kernel == 3) return stream_launch(h, c, s);
+    if (kernel == 2) return generic_launch(h, c, s);
+    return fused_launch(h, c, s);
 }
 QBP_ABI_CATCH
 
@@ -1154,6 +1196,36 @@ try {
 }
 QBP_ABI_CATCH
 
+// The messages of iteration `iteration` of a B-syndrome decode (host inputs), [B][E] in h->d_llr: the work of
+// qbp_check_messages and qbp_message_histograms after their argument checks.
+static int dump_messages(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, int variant,
+                         double alpha, double damping, double clip_llr, int iteration, uint32_t flags, int col_mode,
+                         hipStream_t s)
+{
+    if (variant == QBP_SUM_PRODUCT) {
+        // plain sum-product = the damped update with alpha = damping = 1 and no LLR clip: the
+        // caller's alpha / damping / clip_llr are ignored, as QBP_SUM_PRODUCT ignores them everywhere
+        variant = QBP_DAMPED_SP;
+        alpha = 1.0; damping = 1.0; clip_llr = __builtin_inf();
+    }
+    const size_t m = h->m, n = h->n, b = (size_t)B, E = (size_t)std::max(h->E, 1);
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_prior.reserve(n));
+    HIP_TRY(h->d_llr.reserve(b * E));
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    BpCall c;
+    c.syndromes = h->d_syn.p; c.prior = h->d_prior.p; c.B = B; c.max_iter = iteration + 1; c.variant = variant;
+    c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr;
+    c.flags = flags | QBP_FLAG_FORCE_FULL;   // (no early exit before the dump iteration)
+    c.dump = h->d_llr.p; c.dump_iter = iteration;
+    // min-sum returns R_new / alpha (rework/decoding.py:58-59); damped SP the unscaled R (:168-169,
+    // taken before R * alpha)
+    c.dump_div = variant == QBP_MIN_SUM ? alpha : 1.0;
+    c.col_mode = col_mode;
+    return generic_launch(h, c, s);
+}
+
 int qbp_check_messages(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B,
                        int32_t variant, double alpha, double damping, double clip_llr,
                        int32_t iteration, uint32_t flags, double* messages)
@@ -1163,29 +1235,13 @@ try {
     int col_mode = 0;                    // (only the column-sum order bits of `flags` are honoured)
     flags &= QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0 | QBP_FLAG_PAIRWISE_COLSUM;
     if (prior) { rc = resolve_column_order(h, flags, prior, &col_mode); if (rc) return rc; }
-    if (variant == QBP_SUM_PRODUCT) {
-        // plain sum-product = the damped update with alpha = damping = 1 and no LLR clip: the
-        // caller's alpha / damping / clip_llr are ignored, as QBP_SUM_PRODUCT ignores them everywhere
-        variant = QBP_DAMPED_SP;
-        alpha = 1.0; damping = 1.0; clip_llr = __builtin_inf();
-    }
     if (B == 0) return QBP_OK;
     if (!syndromes || !prior || !messages) return fail(QBP_E_INVALID, "null pointer");
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B, E = (size_t)std::max(h->E, 1);
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_llr.reserve(b * E));
+    const size_t b = (size_t)B;
     hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    // min-sum returns R_new / alpha (rework/decoding.py:58-59); damped SP the unscaled R (:168-169,
-    // taken before R * alpha)
-    const double div = variant == QBP_MIN_SUM ? alpha : 1.0;
-    rc = generic_launch(h, h->d_syn.p, h->d_prior.p, B, iteration + 1, variant, alpha, damping, clip_llr,
-                        flags | QBP_FLAG_FORCE_FULL /* no early exit before the dump iteration */, nullptr,
-                        nullptr, nullptr, nullptr, h->d_llr.p, iteration, div, s, nullptr, col_mode);
+    rc = dump_messages(h, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(messages, h->d_llr.p, b * (size_t)h->E * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1207,22 +1263,13 @@ try {
     if (rc) return rc;
     if (bins < 1 || bins > 4096) return fail(QBP_E_INVALID, "bins = %d out of range (1 .. 4096)", bins);
     if (B == 0 || h->E == 0) return fail(QBP_E_INVALID, "no messages to bin (B = %lld, E = %d)", (long long)B, h->E);
-    if (variant == QBP_SUM_PRODUCT) { variant = QBP_DAMPED_SP; alpha = 1.0; damping = 1.0; clip_llr = __builtin_inf(); }
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B, E = (size_t)h->E;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_hard.reserve(b * n));               // the true error bits
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_llr.reserve(b * E));                // the messages, [B][E]
+    const size_t n = h->n, b = (size_t)B, E = (size_t)h->E;
     hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(h->d_hard.reserve(b * n));               // the true error bits
     HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, b * n, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    const double div = variant == QBP_MIN_SUM ? alpha : 1.0;
-    rc = generic_launch(h, h->d_syn.p, h->d_prior.p, B, iteration + 1, variant, alpha, damping, clip_llr,
-                        flags | QBP_FLAG_FORCE_FULL, nullptr, nullptr, nullptr, nullptr, h->d_llr.p, iteration,
-                        div, s, nullptr, col_mode);
+    rc = dump_messages(h, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
     if (rc) return rc;
     // range of all messages (rework/Alvarado.py:41-44: the two classes share one range)
     const int grid = (int)std::min<size_t>(1024, (b * E + 255) / 256);
@@ -1282,42 +1329,6 @@ static unsigned mc_threshold(double p)
     if (!(t > 0.0)) t = 0.0;
     if (t > 4294967295.0) t = 4294967295.0;
     return (unsigned)t;
-}
-
-// Rank of H over GF(2) and its bit-packed rows for matrices beyond the one-wavefront kernel: built on
-// first use (64-bit Gaussian elimination on the host: about half a second for 2592 x 7776), not in
-// qbp_create, which most users of such matrices never follow with an OSD call.
-static int osd_big_prepare(qbp_handle* h)
-{
-    if (h->osd_big_ready) return QBP_OK;
-    const int m = h->m, n = h->n, W = h->osd_W;
-    std::vector<uint32_t> hbits((size_t)m * W, 0u);
-    for (int c = 0; c < m; ++c)
-        for (int e = h->row_ptr[c]; e < h->row_ptr[c + 1]; ++e)
-            hbits[(size_t)c * W + (h->col_idx[e] >> 5)] |= 1u << (h->col_idx[e] & 31);
-    HIP_TRY(h->d_hbits.reserve(hbits.size()));
-    HIP_TRY(hipMemcpy(h->d_hbits.p, hbits.data(), hbits.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    const int W64 = (n + 63) / 64;
-    std::vector<uint64_t> A((size_t)m * W64, 0ull);
-    for (int c = 0; c < m; ++c)
-        for (int e = h->row_ptr[c]; e < h->row_ptr[c + 1]; ++e)
-            A[(size_t)c * W64 + (h->col_idx[e] >> 6)] |= 1ull << (h->col_idx[e] & 63);
-    int rank = 0;
-    for (int col = 0; col < n && rank < m; ++col) {
-        const int wi = col >> 6;
-        const uint64_t bit = 1ull << (col & 63);
-        int piv = -1;
-        for (int r = rank; r < m; ++r) if (A[(size_t)r * W64 + wi] & bit) { piv = r; break; }
-        if (piv < 0) continue;
-        if (piv != rank) for (int w = 0; w < W64; ++w) std::swap(A[(size_t)piv * W64 + w], A[(size_t)rank * W64 + w]);
-        for (int r = rank + 1; r < m; ++r)
-            if (A[(size_t)r * W64 + wi] & bit)
-                for (int w = wi; w < W64; ++w) A[(size_t)r * W64 + w] ^= A[(size_t)rank * W64 + w];
-        ++rank;
-    }
-    h->osd_rank = rank;
-    h->osd_big_ready = true;
-    return QBP_OK;
 }
 
 // The one-pivot-at-a-time kernel, which follows the reference's row swaps (qbp_osd.hpp, osd0_big_kernel): matrices
@@ -1381,11 +1392,8 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
 {
     O.m = h->m; O.n = h->n; O.W = h->osd_W; O.NP = h->osd_NP;
     O.row_ptr = h->d_row_ptr.p; O.col_idx = h->d_col_idx.p;
-    if (!h->osd_ok) {
-        // matrices whose rows do not fit 64 KiB of LDS (rank and 32-bit rows: built on first use)
-        int rc = osd_big_prepare(h);
-        if (rc) return rc;
-    }
+    const int rc = osd_prepare(h);
+    if (rc) return rc;
     O.rank = h->osd_rank; O.hbits = h->d_hbits.p;
     const size_t m = h->m, n = h->n, NP = (size_t)h->osd_NP;
     // -- matrices beyond the LDS limit: eight pivots at a time (qbp_osd.hpp, osd0_blocked_kernel)
@@ -1444,47 +1452,6 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
     return QBP_OK;
 }
 
-int qbp_osd0_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_llr,
-                          const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
-try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
-    if (B == 0) return QBP_OK;
-    if (!d_syndromes || !d_llr || !d_hard || !d_solution) return fail(QBP_E_INVALID, "null pointer");
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    qbp::OsdParams O{};
-    O.count = B; O.syndromes = d_syndromes; O.llr = d_llr; O.hard = d_hard; O.solution = d_solution;
-    return osd_launch(h, O, B, static_cast<hipStream_t>(stream), true);
-}
-QBP_ABI_CATCH
-
-int qbp_osd0_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
-                   int64_t B, uint8_t* solution)
-try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
-    if (B == 0) return QBP_OK;
-    if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_llr.reserve(b * n));
-    HIP_TRY(h->d_hard.reserve(b * n));
-    HIP_TRY(h->d_sol.reserve(b * n));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
-    int rc = qbp_osd0_batch_device(h, h->d_syn.p, h->d_llr.p, h->d_hard.p, B, h->d_sol.p, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
-}
-QBP_ABI_CATCH
-
 int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
                          const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
 try {
@@ -1492,7 +1459,6 @@ try {
     int method = 0, order = 0;
     int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
     if (rc) return rc;
-    if (!method) return qbp_osd0_batch_device(h, d_syndromes, d_llr, d_hard, B, d_solution, stream);
     if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
     if (B == 0) return QBP_OK;
     if (!d_syndromes || !d_llr || !d_hard || !d_solution) return fail(QBP_E_INVALID, "null pointer");
@@ -1511,7 +1477,6 @@ try {
     int method = 0, order = 0;
     int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
     if (rc) return rc;
-    if (!method) return qbp_osd0_batch(h, syndromes, llr, hard, B, solution);
     if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
     if (B == 0) return QBP_OK;
     if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
@@ -1531,6 +1496,20 @@ try {
     HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_osd0_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_llr,
+                          const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
+try {
+    return qbp_osd_batch_device(h, 0, d_syndromes, d_llr, d_hard, B, d_solution, stream);
+}
+QBP_ABI_CATCH
+
+int qbp_osd0_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
+                   int64_t B, uint8_t* solution)
+try {
+    return qbp_osd_batch(h, 0, syndromes, llr, hard, B, solution);
 }
 QBP_ABI_CATCH
 
@@ -1574,60 +1553,37 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         HIP_TRY(h->d_fail_err.reserve(t * n));
         HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, sizeof(unsigned long long), s));
     }
-    auto osd_pass = [&]() -> int {
-        // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
-        // read from device memory by the kernel itself (no host round trip)
-        qbp::OsdParams O{};
-        O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p);
-        O.list = h->d_fail_list.p;
-        O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
-        O.errors = h->d_fail_err.p; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
-        O.counters = reinterpret_cast<long long*>(d_counters);
-        return osd_launch(h, O, T, s, false, osd_method, osd_order);
-    };
-    if (!h->fused_ok || h->opt_kernel == 2 || h->opt_force_generic) {
-        // matrices beyond the on-chip kernel: the whole loop inside the general-H kernel
-        qbp::GenericParams M{};
-        M.lx_cols = h->d_lx_cols.p; M.trial_begin = trial_begin; M.seed = seed;
-        M.threshold = mc_threshold(p); M.draws = draws; M.half_distance = distance / 2;
-        M.counters = reinterpret_cast<long long*>(d_counters);
-        M.errors_in = d_errors_in;
-        if (osd) {
-            M.fail_list = h->d_fail_list.p; M.fail_count = h->d_fail_count.p;
-            M.fail_syn = h->d_fail_syn.p; M.fail_llr = h->d_fail_llr.p;
-            M.fail_hard = h->d_fail_hard.p; M.fail_err = h->d_fail_err.p;
-        }
+    McArgs mc{};
+    mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = trial_begin; mc.seed = seed;
+    mc.threshold = mc_threshold(p); mc.draws = draws; mc.half_distance = distance / 2;
+    mc.counters = reinterpret_cast<long long*>(d_counters);
+    mc.errors_in = d_errors_in;
+    if (osd) {
+        mc.fail_list = h->d_fail_list.p; mc.fail_count = h->d_fail_count.p;
+        mc.fail_syn = h->d_fail_syn.p; mc.fail_llr = h->d_fail_llr.p;
+        mc.fail_hard = h->d_fail_hard.p; mc.fail_err = h->d_fail_err.p;
+    }
+    BpCall c;
+    c.prior = d_prior; c.B = T; c.max_iter = max_iter; c.variant = variant;
+    c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
+    c.mc = &mc;
+    if (bp_kernel(h, T, flags, 0, true) == 2) {
         h->last_kernel = 2;
-        rc = generic_launch(h, nullptr, d_prior, T, max_iter, variant, alpha, damping, clip_llr, flags,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1.0, s, &M);
-        if (rc) return rc;
-        return osd ? osd_pass() : QBP_OK;
+        rc = generic_launch(h, c, s);
+    } else {
+        rc = fused_launch(h, c, s);
+        if (rc == QBP_OK) h->last_kernel = 1;
     }
-    LaunchCfg cfg;
-    rc = make_cfg(h, T, &cfg, (flags & QBP_FLAG_FORCE_FULL) != 0, true);
-    if (rc) return rc;
-    FusedParams P{};
-    fill_static(h, P, cfg);
-    P.prior = d_prior; P.B = T; P.max_iter = max_iter; P.flags = flags;
-    P.alpha = alpha; P.damping = damping; P.clip_llr = clip_llr;
-    P.lx_cols = h->d_lx_cols.p; P.trial_begin = trial_begin; P.seed = seed;
-    P.threshold = mc_threshold(p); P.draws = draws; P.half_distance = distance / 2;
-    P.counters = reinterpret_cast<long long*>(d_counters);
-    P.errors_in = d_errors_in;
-    if (osd) {
-        P.fail_list = h->d_fail_list.p; P.fail_count = h->d_fail_count.p;
-        P.fail_syn = h->d_fail_syn.p; P.fail_llr = h->d_fail_llr.p;
-        P.fail_hard = h->d_fail_hard.p; P.fail_err = h->d_fail_err.p;
-    }
-    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY((flags & QBP_FLAG_FAST_MATH) ? qbp::launch_fused_fast_math(true, variant, P, cfg, s)
-                                         : qbp::launch_fused(true, variant, P, cfg, s));
-    h->last_kernel = 1;
-    if (osd) {
-        rc = osd_pass();
-        if (rc) return rc;
-    }
-    return QBP_OK;
+    if (rc || !osd) return rc;
+    // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
+    // read from device memory by the kernel itself (no host round trip)
+    qbp::OsdParams O{};
+    O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p);
+    O.list = h->d_fail_list.p;
+    O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
+    O.errors = h->d_fail_err.p; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
+    O.counters = reinterpret_cast<long long*>(d_counters);
+    return osd_launch(h, O, T, s, false, osd_method, osd_order);
 }
 
 int qbp_mc_run_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
@@ -1749,12 +1705,7 @@ try {
         case QBP_OPT_OSD_BIG:
             if (value < 0 || value > 3) return fail(QBP_E_INVALID, "OSD kernel selector out of range");
             h->opt_osd_big = (int)value;
-            if (value != 0) { h->osd_ok = false; }
-            else {
-                const size_t lds = qbp::osd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP);
-                h->osd_ok = lds <= 64 * 1024 && h->m <= 64 * 32;
-                h->osd_big_ready = false;       // (osd_rank / d_hbits are shared: rebuild on next use)
-            }
+            h->osd_ok = value == 0 && osd_one_wave(h);
             return QBP_OK;
         case QBP_OPT_GENERAL_NO_LDS_TABLES:
             h->opt_no_lds_tables = value != 0; return QBP_OK;
@@ -1780,10 +1731,10 @@ try {
         case QBP_INFO_EDGES: return h->E;
         case QBP_INFO_MAX_ROW_DEG: return h->max_row_deg;
         case QBP_INFO_MAX_COL_DEG: return h->max_col_deg;
-        case QBP_INFO_KERNEL_KIND:   // the kernel a decode call would use (small batch), see also ..._LAST
-            if (h->opt_force_generic) return 2;
-            if (h->opt_kernel) return h->opt_kernel;
-            return h->fused_ok ? 1 : 2;   // (auto picks 3 for small graphs in batches >= 131072)
+        case QBP_INFO_KERNEL_KIND: {   // the kernel a decode call would use (small batch), see also ..._LAST
+            const int kernel = bp_kernel(h, 1, 0, 0, false);
+            return kernel > 0 ? kernel : h->opt_kernel;   // (the forced on-chip kernel, which that call refuses)
+        }
         case QBP_INFO_LAST_KERNEL: return h->last_kernel;
         case QBP_INFO_ONE_BARRIER: return h->last_one_barrier;
         case QBP_INFO_THREADS: return h->last_threads;
