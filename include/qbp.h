@@ -272,6 +272,31 @@ int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syn
 int qbp_mc_sample_errors(qbp_handle* h, double p, int32_t draws, uint64_t seed,
                          int64_t trial_begin, int64_t T, uint8_t* errors);
 
+/*
+ * Monte-Carlo on a detector error model: qbp_mc_run with a probability per column (error mechanism) instead of
+ * one p.  probs [n] (host; NaN, < 0, > 1 or a null pointer: QBP_E_INVALID before any GPU work).  Trial t,
+ * column v: bit = XOR over d < draws of [word v % 4 of Philox4x32-10(counter (t lo, t hi, v / 4, d), key seed)
+ * < thr[v]], thr[v] = floor(probs[v] 2^32) clamped to [0, 2^32 - 1] -- with every probs[v] == p exactly the bits
+ * of qbp_mc_run(p).  The thresholds are uploaded once per handle and re-uploaded only when probs changes.
+ * A column no check touches (an undetectable logical mechanism) is drawn like any other: with Lx it counts as a
+ * logical error.  Flags, OSD bits, limits and QBP_E_UNSUPPORTED cases are those of qbp_mc_run.
+ */
+int qbp_mc_run_probs(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                     int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                     const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                     double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form (as qbp_mc_run_device): d_prior and d_counters (ADDED to) are device pointers; Lx and probs
+ * stay host pointers. */
+int qbp_mc_run_probs_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                            const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                            int64_t trial_end, const double* d_prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr,
+                            uint32_t flags, int64_t* d_counters, void* stream);
+/* Errors the sampler of qbp_mc_run_probs draws for trials [trial_begin, trial_begin + T): errors [T][n] host
+ * bytes (tests). */
+int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,
+                               int64_t trial_begin, int64_t T, uint8_t* errors);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

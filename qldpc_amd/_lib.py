@@ -63,6 +63,13 @@ SIGNATURES = {
                                     C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
     "qbp_mc_sample_errors": (C.c_int, [_VP, C.c_double, C.c_int32, C.c_uint64, C.c_int64,
                                        C.c_int64, _VP]),
+    "qbp_mc_run_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64,
+                                   C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double,
+                                   C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_mc_run_probs_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
+                                          C.c_uint64, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_sample_errors_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
     "qbp_message_histograms": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -285,6 +292,44 @@ class Decoder:
             int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_counters, stream or None))
 
+    def _probs(self, probs):
+        pr = np.ascontiguousarray(probs, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"probs must have shape ({self.n},), got {pr.shape}")
+        return pr
+
+    @_locked
+    def mc_run_probs(self, Lx, distance, probs, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
+                     variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """``mc_run`` with a probability per column (detector error models: qbp_mc_run_probs)."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        probs = self._probs(probs)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        counters = np.zeros(NUM_COUNTERS, np.int64)
+        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        for a in range(int(trial_begin), int(trial_end), step):
+            _check(load().qbp_mc_run_probs(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
+                                           int(draws), int(seed), a, min(a + step, int(trial_end)),
+                                           pr.ctypes.data, int(max_iter), int(variant), float(alpha),
+                                           float(damping), float(clip_llr), int(flags), counters.ctypes.data))
+        return counters
+
+    def mc_run_probs_device(self, Lx, distance, probs, d_prior, trial_begin, trial_end, d_counters, draws=1,
+                            seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
+                            clip_llr=20.0, flags=0, stream=0):
+        """``mc_run_device`` with a probability per column (host array; uploaded once, re-uploaded when it
+        changes).  One call: with FLAG_OSD0 the caller splits ranges by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        probs = self._probs(probs)
+        _check(load().qbp_mc_run_probs_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
+            int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
+            float(damping), float(clip_llr), int(flags), d_counters, stream or None))
+
     @_locked
     def check_messages(self, syndromes, prior, variant, alpha=1.0, damping=1.0, clip_llr=20.0,
                        iteration=0, flags=0):
@@ -366,6 +411,14 @@ class Decoder:
         out = np.empty((int(T), self.n), np.uint8)
         _check(load().qbp_mc_sample_errors(self._h, float(p), int(draws), int(seed),
                                            int(trial_begin), int(T), out.ctypes.data))
+        return out
+
+    @_locked
+    def mc_sample_errors_probs(self, probs, trial_begin, T, draws=1, seed=0):
+        probs = self._probs(probs)
+        out = np.empty((int(T), self.n), np.uint8)
+        _check(load().qbp_mc_sample_errors_probs(self._h, probs.ctypes.data, int(draws), int(seed),
+                                                 int(trial_begin), int(T), out.ctypes.data))
         return out
 
     @_locked

@@ -128,6 +128,8 @@ struct qbp_handle {
     DevBuf<long long> d_counters;
     std::vector<uint8_t> lx_cache;   // last uploaded Lx (host copy) to skip re-uploads
     int lx_cache_k = -1;
+    DevBuf<uint32_t> d_mc_thr;       // qbp_mc_run_probs: a sampler threshold per column, [n rounded up to 4]
+    std::vector<uint32_t> thr_cache; // last uploaded thresholds (host copy) to skip re-uploads
     // general-H kernel
     DevBuf<int32_t> d_col_ptr, d_col_edge;
     DevBuf<double> d_wsQ, d_wsR, d_wsV;
@@ -647,6 +649,7 @@ struct McArgs {
     long long trial_begin;
     unsigned long long seed;
     unsigned threshold;
+    const uint32_t* thr_cols;        // per-column thresholds (qbp_mc_run_probs), else null
     int draws, half_distance;
     long long* counters;
     const uint8_t* errors_in;
@@ -662,6 +665,7 @@ static void put_mc(Params& P, const McArgs& a)
 {
     P.lx_cols = a.lx_cols; P.trial_begin = a.trial_begin; P.seed = a.seed; P.threshold = a.threshold;
     P.draws = a.draws; P.half_distance = a.half_distance; P.counters = a.counters; P.errors_in = a.errors_in;
+    P.thr_cols = a.thr_cols;
     P.fail_list = a.fail_list; P.fail_count = a.fail_count; P.fail_syn = a.fail_syn;
     P.fail_llr = a.fail_llr; P.fail_hard = a.fail_hard; P.fail_err = a.fail_err;
 }
@@ -1014,8 +1018,13 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     // >= B -- and the memset node is skipped (3 us of a 30 us single-syndrome call).
     if (mc || c.B > (long long)cfg.grid * cfg.S)
         HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
-    HIP_TRY((c.flags & QBP_FLAG_FAST_MATH) ? qbp::launch_fused_fast_math(mc, c.variant, P, cfg, s)
-                                           : qbp::launch_fused(mc, c.variant, P, cfg, s));
+    const bool fast = (c.flags & QBP_FLAG_FAST_MATH) != 0;
+    if (mc && P.thr_cols)               // a sampler threshold per qubit (qbp_mc_run_probs): builds of their own
+        HIP_TRY(fast ? qbp::launch_fused_cols_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused_cols(mc, c.variant, P, cfg, s));
+    else
+        HIP_TRY(fast ? qbp::launch_fused_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused(mc, c.variant, P, cfg, s));
     return QBP_OK;
 }
 
@@ -1331,6 +1340,32 @@ static unsigned mc_threshold(double p)
     return (unsigned)t;
 }
 
+// probs [n] of qbp_mc_run_probs: every value in [0, 1] (host only, before any GPU work)
+static int check_probs(const qbp_handle* h, const double* probs)
+{
+    if (!probs) return fail(QBP_E_INVALID, "probs is null");
+    for (int v = 0; v < h->n; ++v)
+        if (!(probs[v] >= 0.0 && probs[v] <= 1.0))
+            return fail(QBP_E_INVALID, "probs[%d] = %g out of [0, 1]", v, probs[v]);
+    return QBP_OK;
+}
+
+// Sampler thresholds of probs on the device, [n rounded up to 4] (zero in the padding: those bytes are never
+// set), uploaded once and again only when they change, like the Lx columns of mc_prepare.
+static int mc_prepare_thr(qbp_handle* h, const double* probs, hipStream_t s)
+{
+    const size_t n4 = ((size_t)h->n + 3) / 4 * 4;
+    std::vector<uint32_t> thr(n4, 0u);
+    for (int v = 0; v < h->n; ++v) thr[v] = mc_threshold(probs[v]);
+    if (h->thr_cache == thr) return QBP_OK;
+    h->thr_cache.clear();
+    HIP_TRY(h->d_mc_thr.reserve(n4));
+    HIP_TRY(hipMemcpyAsync(h->d_mc_thr.p, thr.data(), n4 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // thr is a local
+    h->thr_cache.swap(thr);
+    return QBP_OK;
+}
+
 // The one-pivot-at-a-time kernel, which follows the reference's row swaps (qbp_osd.hpp, osd0_big_kernel): matrices
 // beyond 8192 rows, QBP_OPT_OSD_BIG = 2, and the records a fast kernel found inconsistent.
 static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long max_grid, hipStream_t s)
@@ -1513,8 +1548,9 @@ try {
 }
 QBP_ABI_CATCH
 
+// probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null
 static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
-                       double p, int32_t draws, uint64_t seed, int64_t trial_begin,
+                       double p, const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
                        int64_t trial_end, const uint8_t* d_errors_in, const double* d_prior, int32_t max_iter,
                        int32_t variant, double alpha, double damping, double clip_llr,
                        uint32_t flags, int64_t* d_counters, void* stream)
@@ -1531,12 +1567,14 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", draws);
     if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", p);
     if (!d_prior || !d_counters) return fail(QBP_E_INVALID, "null pointer");
+    if (probs && (rc = check_probs(h, probs)) != QBP_OK) return rc;
     if (T == 0) return QBP_OK;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = mc_prepare(h, Lx_host, k, s);
     if (rc) return rc;
+    if (probs && (rc = mc_prepare_thr(h, probs, s)) != QBP_OK) return rc;
     const bool osd = (flags & QBP_FLAG_OSD0) != 0;
     if (osd) {
         // per-trial records of the trials BP leaves unconverged (read by the OSD kernel)
@@ -1556,6 +1594,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     McArgs mc{};
     mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = trial_begin; mc.seed = seed;
     mc.threshold = mc_threshold(p); mc.draws = draws; mc.half_distance = distance / 2;
+    mc.thr_cols = probs ? h->d_mc_thr.p : nullptr;
     mc.counters = reinterpret_cast<long long*>(d_counters);
     mc.errors_in = d_errors_in;
     if (osd) {
@@ -1592,8 +1631,8 @@ int qbp_mc_run_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t 
                       int32_t variant, double alpha, double damping, double clip_llr,
                       uint32_t flags, int64_t* d_counters, void* stream)
 try {
-    return mc_run_impl(h, Lx_host, k, distance, p, draws, seed, trial_begin, trial_end, nullptr, d_prior, max_iter,
-                       variant, alpha, damping, clip_llr, flags, d_counters, stream);
+    return mc_run_impl(h, Lx_host, k, distance, p, nullptr, draws, seed, trial_begin, trial_end, nullptr, d_prior,
+                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream);
 }
 QBP_ABI_CATCH
 
@@ -1617,8 +1656,9 @@ try {
     HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, (size_t)T * n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, QBP_NUM_COUNTERS * sizeof(long long), s));
     // (p, draws, seed are unused with stored errors)
-    const int rc = mc_run_impl(h, Lx, k, distance, 0.0, 1, 0, 0, T, h->d_hard.p, h->d_prior.p, max_iter, variant,
-                               alpha, damping, clip_llr, flags, reinterpret_cast<int64_t*>(h->d_counters.p), s);
+    const int rc = mc_run_impl(h, Lx, k, distance, 0.0, nullptr, 1, 0, 0, T, h->d_hard.p, h->d_prior.p, max_iter,
+                               variant, alpha, damping, clip_llr, flags, reinterpret_cast<int64_t*>(h->d_counters.p),
+                               s);
     if (rc) { (void)hipStreamSynchronize(s); return rc; }
     HIP_TRY(hipMemcpyAsync(counters, h->d_counters.p, QBP_NUM_COUNTERS * sizeof(long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1669,6 +1709,73 @@ try {
     // (the sampler does not depend on H: any matrix, whichever kernel decodes it)
     HIP_TRY(h->d_hard.reserve((size_t)T * n));
     HIP_TRY(qbp::launch_mc_sample(h->d_hard.p, h->n, T, trial_begin, draws, seed, mc_threshold(p), s));
+    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_probs_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                            const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                            int64_t trial_end, const double* d_prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr,
+                            uint32_t flags, int64_t* d_counters, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    const int rc = check_probs(h, probs);
+    if (rc) return rc;
+    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
+                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_probs(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                     int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                     const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                     double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    int rc = check_probs(h, probs);
+    if (rc) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    HIP_TRY(h->d_prior.reserve(h->n));
+    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
+    rc = qbp_mc_run_probs_device(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end,
+                                 h->d_prior.p, max_iter, variant, alpha, damping, clip_llr, flags,
+                                 reinterpret_cast<int64_t*>(h->d_counters.p), s);
+    if (rc) return rc;
+    long long tmp[qbp::NUM_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,
+                               int64_t trial_begin, int64_t T, uint8_t* errors)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (T < 0 || trial_begin < 0) return fail(QBP_E_INVALID, "T and trial_begin must be >= 0");
+    if (!errors) return fail(QBP_E_INVALID, "errors is null");
+    if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2");
+    int rc = check_probs(h, probs);
+    if (rc) return rc;
+    if (T == 0) return QBP_OK;
+    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    const size_t n = h->n;
+    rc = mc_prepare_thr(h, probs, s);
+    if (rc) return rc;
+    HIP_TRY(h->d_hard.reserve((size_t)T * n));
+    HIP_TRY(qbp::launch_mc_sample_cols(h->d_hard.p, h->n, T, trial_begin, draws, seed, h->d_mc_thr.p, s));
     HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QBP_OK;

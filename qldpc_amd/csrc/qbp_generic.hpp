@@ -128,6 +128,8 @@ struct GenericParams {
     double* fail_llr;                   // [B][n]
     uint8_t* fail_hard;                 // [B][n]
     uint8_t* fail_err;                  // [B][n]
+    // (last, so that adding it moved no field the other builds read)
+    const uint32_t* thr_cols;           // [n4 * 4] a threshold per qubit (QBP_MC_COLS builds: qbp_mc_run_probs)
 };
 
 // Dynamic LDS of one workgroup: messages (LDSMSG) + syndrome bits + two parity buffers + counters
@@ -382,8 +384,12 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             // (beliefPropagationGPU.py:195)
             for (int g = tid; g < n4; g += nt)
                 reinterpret_cast<unsigned*>(err)[g] =
+#if QBP_MC_COLS      // (builds of qbp_mc_run_probs: qbp_tu_generic.hip -DQBP_COLS_TU)
+                    mc_error_quad_cols((unsigned long long)(P.trial_begin + b), g, P.draws, P.seed, P.thr_cols);
+#else
                     P.errors_in ? mc_stored_quad(P.errors_in + b * n, g, n)
                                 : mc_error_quad((unsigned long long)(P.trial_begin + b), g, P.draws, P.seed, P.threshold);
+#endif
         }
         __syncthreads();      // (also: the previous syndrome's last readers of LDS are done)
         // ---- syndrome bits in sorted check order; parity buffer 0 := syndrome -------------------

@@ -115,6 +115,8 @@ struct FusedParams {
     double* fail_llr;           // [B][n]
     uint8_t* fail_hard;         // [B][n]
     uint8_t* fail_err;          // [B][n]
+    // (last, so that adding it moved no field the other builds read)
+    const uint32_t* thr_cols;   // [n4 * 4] a threshold per qubit (QBP_MC_COLS builds: qbp_mc_run_probs)
 };
 
 // Rarely used launch parameters (output pointers, Monte-Carlo settings, ...) are re-read from the
@@ -420,10 +422,16 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 err_par ^= 1u;
                 unsigned* const err_words = reinterpret_cast<unsigned*>(err_buf());
                 const unsigned long long trial = (unsigned long long)(COLD(trial_begin) + b);
+#if QBP_MC_COLS
+                const uint32_t* const thr = COLD(thr_cols);
+                for (int g = c; g < P.n_words4; g += m)
+                    err_words[g] = mc_error_quad_cols(trial, g, COLD(draws), COLD(seed), thr);
+#else
                 const uint8_t* const ein = COLD(errors_in);
                 for (int g = c; g < P.n_words4; g += m)
                     err_words[g] = ein ? mc_stored_quad(ein + b * COLD(n), g, COLD(n))
                                        : mc_error_quad(trial, g, COLD(draws), COLD(seed), COLD(threshold));
+#endif
             }
             __syncthreads();                                      // B0
         }
@@ -698,6 +706,21 @@ __global__ void mc_sample_kernel(uint8_t* errors, int n, long long T, long long 
     const long long b = i / n4;
     const int g = (int)(i - b * n4);
     const unsigned q = mc_error_quad((unsigned long long)(trial_begin + b), g, draws, seed, threshold);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (4 * g + k < n) errors[b * n + 4 * g + k] = (uint8_t)((q >> (8 * k)) & 1u);
+}
+
+// ... with a threshold per qubit (qbp_mc_sample_errors_probs; thr as in mc_error_quad_cols)
+__global__ void mc_sample_cols_kernel(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
+                                      unsigned long long seed, const uint32_t* thr)
+{
+    const int n4 = (n + 3) / 4;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * n4) return;
+    const long long b = i / n4;
+    const int g = (int)(i - b * n4);
+    const unsigned q = mc_error_quad_cols((unsigned long long)(trial_begin + b), g, draws, seed, thr);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (4 * g + k < n) errors[b * n + 4 * g + k] = (uint8_t)((q >> (8 * k)) & 1u);

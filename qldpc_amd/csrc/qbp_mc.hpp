@@ -5,6 +5,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#ifndef QBP_MC_COLS
+// 1: the Monte-Carlo kernels draw with a threshold per qubit (thr_cols; qbp_mc_run_probs).  Set by the translation
+// units compiled for that (qbp_tu_fused.hip / qbp_tu_generic.hip with -DQBP_COLS_TU), which give those kernels
+// names of their own, so that the builds of the uniform sampler keep their code, registers and scratch.
+#define QBP_MC_COLS 0
+#endif
+
 namespace qbp {
 
 constexpr int NUM_COUNTERS = 12;
@@ -33,6 +40,23 @@ __device__ __forceinline__ unsigned mc_error_quad(unsigned long long trial, int 
         philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
         bytes ^= (c[0] < thr ? 1u : 0u) | (c[1] < thr ? 0x100u : 0u) | (c[2] < thr ? 0x10000u : 0u) |
                  (c[3] < thr ? 0x1000000u : 0u);
+    }
+    return bytes;
+}
+
+// The same with a threshold per qubit (qbp_mc_run_probs: detector error models, where every column has its
+// own probability): thr [n rounded up to 4] = floor(p_v 2^32), 16-byte aligned, zero in the padding; one
+// 16-byte load per quad.  With every threshold equal this draws exactly the bytes of mc_error_quad.
+__device__ __forceinline__ unsigned mc_error_quad_cols(unsigned long long trial, int g, int draws,
+                                                       unsigned long long seed, const uint32_t* thr)
+{
+    const uint4 t = reinterpret_cast<const uint4*>(thr)[g];
+    unsigned bytes = 0;
+    for (int d = 0; d < draws; ++d) {
+        unsigned c[4] = {(unsigned)trial, (unsigned)(trial >> 32), (unsigned)g, (unsigned)d};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        bytes ^= (c[0] < t.x ? 1u : 0u) | (c[1] < t.y ? 0x100u : 0u) | (c[2] < t.z ? 0x10000u : 0u) |
+                 (c[3] < t.w ? 0x1000000u : 0u);
     }
     return bytes;
 }

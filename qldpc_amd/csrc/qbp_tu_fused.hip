@@ -1,7 +1,18 @@
 // libqbp.so, translation unit of the on-chip kernel (qbp_kernels.hpp): its 27 instantiations.
 // Compiled twice: as is (numpy's tanh / arctanh: the default), and with -DQBP_FAST_TU -DQBP_MATH_FAST=1 under
 // other names (QBP_FLAG_FAST_MATH: round 2's approximations); each build is a code object of its own.
+// Both again with -DQBP_COLS_TU: the 12 Monte-Carlo instantiations with a sampler threshold per qubit
+// (qbp_mc_run_probs), under other names again.
+#if defined(QBP_COLS_TU)
+#define QBP_MC_COLS 1
 #ifdef QBP_FAST_TU
+#define bp_fused_kernel bp_fused_cols_kernel_fast_math
+#define launch_fused launch_fused_cols_fast_math
+#else
+#define bp_fused_kernel bp_fused_cols_kernel
+#define launch_fused launch_fused_cols
+#endif
+#elif defined(QBP_FAST_TU)
 #define bp_fused_kernel bp_fused_kernel_fast_math
 #define launch_fused launch_fused_fast_math
 #else
@@ -66,10 +77,15 @@ hipError_t launch_variant(int variant, const FusedParams& P, const LaunchCfg& cf
 
 hipError_t launch_fused(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s)
 {
+#ifdef QBP_COLS_TU
+    if (!mc) return hipErrorInvalidValue;       // (Monte-Carlo builds only)
+    return launch_variant<true>(variant, P, cfg, s);
+#else
     return mc ? launch_variant<true>(variant, P, cfg, s) : launch_variant<false>(variant, P, cfg, s);
+#endif
 }
 
-#ifndef QBP_FAST_TU
+#ifdef QBP_DEFINE_KERNELS
 hipError_t launch_debug_math(int kind, const double* x, double* y, long long count, hipStream_t s)
 {
     const int threads = 256;
@@ -87,6 +103,16 @@ hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial
                        errors, n, T, trial_begin, draws, seed, threshold);
     return hipGetLastError();
 }
-#endif  // QBP_FAST_TU
+
+hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
+                                 unsigned long long seed, const uint32_t* thr, hipStream_t s)
+{
+    const long long items = T * ((n + 3) / 4);
+    const int threads = 256;
+    hipLaunchKernelGGL(mc_sample_cols_kernel, dim3((unsigned)((items + threads - 1) / threads)), dim3(threads), 0, s,
+                       errors, n, T, trial_begin, draws, seed, thr);
+    return hipGetLastError();
+}
+#endif  // QBP_DEFINE_KERNELS
 
 }  // namespace qbp

@@ -4,7 +4,12 @@
 #ifndef QBP_GENERIC_MEM
 #error "compile with -DQBP_GENERIC_MEM=0, 1 or 2"
 #endif
-#if QBP_GENERIC_MEM == 0
+// With -DQBP_COLS_TU: the three Monte-Carlo instantiations with a sampler threshold per qubit (qbp_mc_run_probs),
+// under other names.
+#if defined(QBP_COLS_TU)
+#define QBP_MC_COLS 1
+#define bp_generic_kernel bp_generic_cols_kernel
+#elif QBP_GENERIC_MEM == 0
 #define QBP_DEFINE_KERNELS 1
 #endif
 #include <hip/hip_runtime.h>
@@ -48,6 +53,14 @@ hipError_t generic_launch_v(int variant, const GenericParams& G, int grid, int t
 #define QBP_CAT2(a, b) a##b
 #define QBP_CAT(a, b) QBP_CAT2(a, b)
 
+#ifdef QBP_COLS_TU
+// launch_generic_cols_mem0 / _mem1 / _mem2 (Monte-Carlo only)
+hipError_t QBP_CAT(launch_generic_cols_mem, QBP_GENERIC_MEM)(int variant, const GenericParams& G, int grid, int threads,
+                                                             size_t lds, hipStream_t s)
+{
+    return generic_launch_v<true, QBP_GENERIC_MEM>(variant, G, grid, threads, lds, s);
+}
+#else
 // launch_generic_mem0 / _mem1 / _mem2: this unit's memory mode
 hipError_t QBP_CAT(launch_generic_mem, QBP_GENERIC_MEM)(bool mc, int variant, const GenericParams& G, int grid,
                                                         int threads, size_t lds, hipStream_t s)
@@ -55,15 +68,26 @@ hipError_t QBP_CAT(launch_generic_mem, QBP_GENERIC_MEM)(bool mc, int variant, co
     return mc ? generic_launch_v<true, QBP_GENERIC_MEM>(variant, G, grid, threads, lds, s)
               : generic_launch_v<false, QBP_GENERIC_MEM>(variant, G, grid, threads, lds, s);
 }
+#endif
 
-#if QBP_GENERIC_MEM == 0
+#if QBP_GENERIC_MEM == 0 && !defined(QBP_COLS_TU)
 hipError_t launch_generic_mem1(bool, int, const GenericParams&, int, int, size_t, hipStream_t);
 hipError_t launch_generic_mem2(bool, int, const GenericParams&, int, int, size_t, hipStream_t);
+hipError_t launch_generic_cols_mem0(int, const GenericParams&, int, int, size_t, hipStream_t);
+hipError_t launch_generic_cols_mem1(int, const GenericParams&, int, int, size_t, hipStream_t);
+hipError_t launch_generic_cols_mem2(int, const GenericParams&, int, int, size_t, hipStream_t);
 
 hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G, int grid, int threads,
                           size_t lds, hipStream_t s)
 {
     static_assert(GENERIC_MEM_GLOBAL == 0 && GENERIC_MEM_LDS == 1 && GENERIC_MEM_SPLIT == 2, "mode numbering");
+    if (mc && G.thr_cols) {           // a sampler threshold per qubit (qbp_mc_run_probs)
+        switch (mem) {
+            case GENERIC_MEM_LDS:   return launch_generic_cols_mem1(variant, G, grid, threads, lds, s);
+            case GENERIC_MEM_SPLIT: return launch_generic_cols_mem2(variant, G, grid, threads, lds, s);
+            default:                return launch_generic_cols_mem0(variant, G, grid, threads, lds, s);
+        }
+    }
     switch (mem) {
         case GENERIC_MEM_LDS:   return launch_generic_mem1(mc, variant, G, grid, threads, lds, s);
         case GENERIC_MEM_SPLIT: return launch_generic_mem2(mc, variant, G, grid, threads, lds, s);

@@ -11,6 +11,7 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
 
     python -m qldpc_amd.mc --code 288 --p 0.06 0.05 0.04 --trials 1000000
     python -m torch.distributed.run --nproc-per-node 8 -m qldpc_amd.mc --code 288 ...
+    python -m qldpc_amd.mc --dem circuit.dem --trials 1000000 --osd      (detector error model: run_dem)
 """
 from __future__ import annotations
 
@@ -99,9 +100,70 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     return all_reduce(table) if all_reduce is not None else table
 
 
+def dem_prior(probs) -> np.ndarray:
+    """Default prior of a detector error model: log((1 - p) / p) with p clipped to [1e-15, 1 - 1e-15]
+    (studies/studyComplete.py:85-86)."""
+    p = np.clip(np.asarray(probs, np.float64), 1e-15, 1 - 1e-15)
+    return np.log((1 - p) / p)
+
+
+def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
+            variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
+            osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+    """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
+    fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
+    ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
+    ``L_matrix @ prediction != actual_observables`` of studies/studyComplete.py.  Returns the GLOBAL counters
+    int64[12] (after one all-reduce), sharded over ranks like ``run_sweep``.
+
+    ``distance``: the "BPs_miscorrected" / "incorrectable" split compares the error weight with distance // 2;
+    the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
+    ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
+    tests; by default the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order)
+    L = np.ascontiguousarray(L, np.uint8)
+    probs = np.ascontiguousarray(probs, np.float64)
+    n = H.shape[1]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if L.shape[0] > 64:
+        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
+    if probs.shape != (n,):
+        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
+    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        import torch
+
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        dev = torch.device("cuda", device)
+        d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        d_prior = torch.from_numpy(prior).to(dev)
+        step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
+        for a in range(begin, end, step):
+            dec.mc_run_probs_device(L, distance, probs, d_prior.data_ptr(), a, min(a + step, end), d_cnt.data_ptr(),
+                                    draws=draws, seed=seed, max_iter=max_iter, variant=variant, alpha=alpha,
+                                    damping=damping, clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(d_cnt)
+        torch.cuda.synchronize(dev)
+        return d_cnt.cpu().numpy()
+    cnt = np.asarray(runner(H, L, probs, prior, begin, end), np.int64)
+    return all_reduce(cnt) if all_reduce is not None else cnt
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--code", default="[[288, 12, 18]]")
+    ap.add_argument("--dem", default=None,
+                    help="detector error model file (stim's text format) instead of --code / --p: run_dem")
+    ap.add_argument("--distance", type=int, default=0,
+                    help="with --dem: the distance of the miscorrected / incorrectable split (0: all incorrectable)")
     ap.add_argument("--p", type=float, nargs="+",
                     default=[0.05, 0.04, 0.03, 0.02, 0.01, 0.009, 0.008, 0.007])   # :39
     ap.add_argument("--trials", type=int, default=10000)                          # :36
@@ -127,6 +189,17 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order)
     except ValueError as e:
         ap.error(str(e))
+    dem_model = None
+    if args.dem is not None:
+        from . import dem
+        if not os.path.isfile(args.dem):
+            ap.error(f"--dem {args.dem}: no such file")
+        try:
+            dem_model = dem.load_dem(args.dem)
+        except ValueError as e:
+            ap.error(f"--dem {args.dem}: {e}")
+        if dem_model[1].shape[0] > 64:
+            ap.error(f"--dem {args.dem}: {dem_model[1].shape[0]} observables (at most 64)")
 
     import sys
     from . import launch
@@ -149,37 +222,51 @@ def main(argv=None):
             dist.init_process_group(args.backend)
     variant = {"sum-product": _lib.SUM_PRODUCT, "damped": _lib.DAMPED_SP,
                "min-sum": _lib.MIN_SUM}[args.variant]
+    common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
+                  damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
+                  osd_order=args.osd_order, device=local)
+    if dem_model is None:
+        points = args.p
+
+        def sweep(trials, ps, rank, world):
+            return run_sweep(args.code, ps, trials, rank=rank, world=world, **common)
+    else:
+        points = [None]                  # one point: the model's own probabilities
+
+        def sweep(trials, ps, rank, world):
+            return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()
-    run_sweep(args.code, args.p[:1], min(args.trials, 4096), draws=args.draws, seed=args.seed,
-              max_iter=args.max_iter, variant=variant, alpha=args.alpha, damping=args.damping,
-              clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
-              rank=0, world=1, device=local)
+    sweep(min(args.trials, 4096), points[:1], 0, 1)
     t_setup = time.perf_counter() - t0
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
     t0 = time.perf_counter()
-    table = run_sweep(args.code, args.p, args.trials, draws=args.draws, seed=args.seed,
-                      max_iter=args.max_iter, variant=variant, alpha=args.alpha,
-                      damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
-                      osd_order=args.osd_order, rank=rank, world=world, device=local)
+    table = sweep(args.trials, points, rank, world)
     dt = time.perf_counter() - t0
     if rank == 0:
         rows = []
-        for p, row in zip(args.p, table):
+        for p, row in zip(points, table):
             s = summarize(row)
-            s["p"] = p
+            if dem_model is None:
+                s["p"] = p
+                label = f"p={p}"
+            else:
+                H, L, probs = dem_model
+                s.update(dem=args.dem, m=int(H.shape[0]), n=int(H.shape[1]), k=int(L.shape[0]))
+                label = f"dem={args.dem} ({H.shape[0]} x {H.shape[1]}, k={L.shape[0]})"
             rows.append(s)
-            print(f"  p={p}: LER={s['ler']:.6f}, BP-only LER={s['ler_bp_only']:.6f}, "
+            print(f"  {label}: LER={s['ler']:.6f}, BP-only LER={s['ler_bp_only']:.6f}, "
                   f"degeneracies={s['degenerateErrors']}, not converged={s['not_converged']}, "
                   f"mean iters={s['mean_iterations']:.2f}")
-        print(f"{len(args.p)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
-              f"({len(args.p) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
+        print(f"{len(points)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
+              f"({len(points) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
         if args.out:
             with open(args.out, "w") as f:
-                json.dump({"code": args.code, "trials": args.trials, "max_iter": args.max_iter,
+                model = {"code": args.code} if dem_model is None else {"dem": args.dem, "distance": args.distance}
+                json.dump({**model, "trials": args.trials, "max_iter": args.max_iter,
                            "draws": args.draws, "seed": args.seed, "variant": args.variant,
                            "osd": args.osd, "osd_method": args.osd_method, "osd_order": args.osd_order,
                            "world_size": world, "seconds": dt, "setup_seconds": t_setup, "points": rows},

@@ -11,7 +11,10 @@ CSRC = os.path.join(ROOT, "qldpc_amd", "csrc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math".split()
 UNITS = [("qbp_tu_fused.hip", []), ("qbp_tu_generic.hip", ["-DQBP_GENERIC_MEM=0"]),
          ("qbp_tu_generic.hip", ["-DQBP_GENERIC_MEM=1"]), ("qbp_tu_generic.hip", ["-DQBP_GENERIC_MEM=2"]),
-         ("qbp_tu_stream.hip", []), ("qbp_tu_osd.hip", [])]
+         ("qbp_tu_stream.hip", []), ("qbp_tu_osd.hip", []),
+         # Monte-Carlo with a sampler threshold per qubit (qbp_mc_run_probs): bp_fused_cols_kernel, bp_generic_cols_kernel
+         ("qbp_tu_fused.hip", ["-DQBP_COLS_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_COLS_TU", f"-DQBP_GENERIC_MEM={i}"])
+                                                      for i in range(3)]
 
 
 def demangle(sym):
