@@ -292,6 +292,38 @@ int qbp_mc_run_probs_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, in
                             int64_t trial_end, const double* d_prior, int32_t max_iter,
                             int32_t variant, double alpha, double damping, double clip_llr,
                             uint32_t flags, int64_t* d_counters, void* stream);
+/*
+ * Monte-Carlo over a ladder of BP iteration budgets in one pass: the sweep of BP_per_Iteration.py:40-81 (maxIter =
+ * 10, 20, ... 90; logical errors, degeneracies and OSD invocations per limit) without sampling and decoding the
+ * same trials once per limit.  budgets [n_budgets] (host): 1 <= n_budgets <= QBP_MC_MAX_BUDGETS values >= 1,
+ * strictly ascending.  counters is [n_budgets][QBP_NUM_COUNTERS] (ADDED to), and row j equals, digit for digit, what
+ * qbp_mc_run_probs adds for the same arguments with max_iter = budgets[j] -- flooding BP does not know its limit,
+ * so a trial's state after b iterations of a longer run is the output of a b-iteration run.  One trial whose
+ * syndrome is first satisfied in (0-based) iteration k:
+ *   rows with budgets[j] > k: converged, k added to [7], classified on the hard decision of iteration k;
+ *   rows with budgets[j] <= k: not converged, budgets[j] - 1 added to [7]; what is classified -- or, with
+ *   QBP_FLAG_OSD0, handed to OSD -- is the posterior of iteration budgets[j] - 1.
+ * The trial stops at min(k, budgets[n_budgets - 1] - 1) (QBP_FLAG_FORCE_FULL: as in qbp_mc_run).  A uniform error
+ * rate p is probs filled with p (then the rows are also those of qbp_mc_run(p)).  Kernels of their own checkpoint
+ * the running trial (bp_fused_budgets_kernel, bp_generic_budgets_kernel); every matrix qbp_mc_run_probs takes.
+ * QBP_E_INVALID, before any GPU work and with the counters untouched: a null pointer, n_budgets out of range, a
+ * budget < 1, budgets not strictly ascending, and whatever qbp_mc_run refuses.  Flags, OSD bits and
+ * QBP_E_UNSUPPORTED cases are those of qbp_mc_run_probs; with QBP_FLAG_OSD0 the per-trial records are kept per
+ * budget, so a call covers at most QBP_MC_OSD_MAX_TRIALS / n_budgets trials (and 16 GiB / n_budgets of records).
+ */
+#define QBP_MC_MAX_BUDGETS 16
+int qbp_mc_run_budgets(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                       int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                       const double* prior, const int32_t* budgets, int32_t n_budgets, int32_t variant,
+                       double alpha, double damping, double clip_llr, uint32_t flags, int64_t* counters);
+/* Asynchronous form (as qbp_mc_run_probs_device): d_prior and d_counters ([n_budgets][QBP_NUM_COUNTERS], ADDED to)
+ * are device pointers; Lx, probs and budgets stay host pointers. */
+int qbp_mc_run_budgets_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                              const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                              int64_t trial_end, const double* d_prior, const int32_t* budgets, int32_t n_budgets,
+                              int32_t variant, double alpha, double damping, double clip_llr,
+                              uint32_t flags, int64_t* d_counters, void* stream);
+
 /* Errors the sampler of qbp_mc_run_probs draws for trials [trial_begin, trial_begin + T): errors [T][n] host
  * bytes (tests). */
 int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,

@@ -29,6 +29,7 @@ FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
+MC_MAX_BUDGETS = 16          # QBP_MC_MAX_BUDGETS: rows of one qbp_mc_run_budgets call
 NUM_COUNTERS = 12
 COUNTER_NAMES = ("trials", "logical_error", "BPs_fault", "BPs_miscorrected", "incorrectable",
                  "degenerateErrors", "not_converged", "sum_iterations",
@@ -69,6 +70,12 @@ SIGNATURES = {
     "qbp_mc_run_probs_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
                                           C.c_uint64, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
                                           C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_run_budgets": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64,
+                                     C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, C.c_double,
+                                     C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_mc_run_budgets_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
+                                            C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32,
+                                            C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP]),
     "qbp_mc_sample_errors_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
@@ -101,6 +108,19 @@ def osd_flags(method="cs", order=0):
     if not 1 <= w <= OSD_MAX_ORDER[m]:
         raise ValueError(f"OSD-{m.upper()} order must be in [0, {OSD_MAX_ORDER[m]}], got {w}")
     return FLAG_OSD0 | (FLAG_OSD_CS if m == "cs" else FLAG_OSD_E) | (w << OSD_ORDER_SHIFT)
+
+
+def check_budgets(budgets):
+    """The ladder of ``qbp_mc_run_budgets`` as int32[K]: 1 <= K <= MC_MAX_BUDGETS integers >= 1, strictly ascending
+    (ValueError otherwise -- the library refuses the same lists with QBP_E_INVALID)."""
+    b = np.asarray(budgets)
+    if b.ndim != 1 or not 1 <= b.size <= MC_MAX_BUDGETS:
+        raise ValueError(f"budgets must be a list of 1 to {MC_MAX_BUDGETS} iteration limits, got {budgets!r}")
+    if b.dtype.kind not in "iu" or np.any(b < 1) or np.any(b > np.iinfo(np.int32).max):
+        raise ValueError(f"budgets must be integers >= 1, got {budgets!r}")
+    if np.any(np.diff(b.astype(np.int64)) <= 0):
+        raise ValueError(f"budgets must be strictly ascending, got {budgets!r}")
+    return np.ascontiguousarray(b, np.int32)
 
 
 class QbpError(RuntimeError):
@@ -328,6 +348,45 @@ class Decoder:
         _check(load().qbp_mc_run_probs_device(
             self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
             int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
+            float(damping), float(clip_llr), int(flags), d_counters, stream or None))
+
+    def mc_budgets_step(self, n_budgets):
+        """Trials one qbp_mc_run_budgets call may cover with FLAG_OSD0: the records are kept per budget."""
+        return max(1, self.mc_osd_step() // int(n_budgets))
+
+    @_locked
+    def mc_run_budgets(self, Lx, distance, probs, prior, budgets, trial_begin, trial_end, draws=1, seed=0,
+                       variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """Counters int64[K, 12] of ONE pass over the trials: row j is ``mc_run_probs(..., max_iter=budgets[j])``
+        (qbp_mc_run_budgets; ``probs``: one probability per column, or a scalar p for all of them)."""
+        bud = check_budgets(budgets)
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        counters = np.zeros((len(bud), NUM_COUNTERS), np.int64)
+        step = self.mc_budgets_step(len(bud)) if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        for a in range(int(trial_begin), int(trial_end), step):
+            _check(load().qbp_mc_run_budgets(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
+                                             int(draws), int(seed), a, min(a + step, int(trial_end)),
+                                             pr.ctypes.data, bud.ctypes.data, len(bud), int(variant), float(alpha),
+                                             float(damping), float(clip_llr), int(flags), counters.ctypes.data))
+        return counters
+
+    def mc_run_budgets_device(self, Lx, distance, probs, d_prior, budgets, trial_begin, trial_end, d_counters,
+                              draws=1, seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
+                              stream=0):
+        """``mc_run_budgets`` on device buffers: d_counters int64[K, 12] is added to.  One call: with FLAG_OSD0 the
+        caller splits ranges by ``mc_budgets_step(K)``."""
+        bud = check_budgets(budgets)
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        _check(load().qbp_mc_run_budgets_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
+            int(trial_begin), int(trial_end), d_prior, bud.ctypes.data, len(bud), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_counters, stream or None))
 
     @_locked

@@ -22,6 +22,7 @@
 #include "qbp_launch.hpp"
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
+static_assert(QBP_MC_MAX_BUDGETS == qbp::MAX_BUDGETS, "budget ladder length");
 
 namespace {
 
@@ -200,13 +201,15 @@ using qbp::FusedParams;
 using qbp::LaunchCfg;
 
 // Dynamic LDS of one workgroup of the fused kernel (the carve is documented in qbp_kernels.hpp)
-size_t fused_lds_bytes(int dc, int m, int n, int S, bool two_copies = false, bool r0_table = false)
+// slot_counters: counter ints per slot (2 * n_budgets rows in the launches of qbp_mc_run_budgets)
+size_t fused_lds_bytes(int dc, int m, int n, int S, bool two_copies = false, bool r0_table = false,
+                       int slot_counters = qbp::NUM_COUNTERS)
 {
     const size_t slot_stride = (size_t)dc * m + 2;
     size_t lds = (size_t)qbp::NP_LDS_BYTES +      // tables of tanh / arctanh (qbp_math.hpp), at the start
                  (two_copies ? (size_t)qbp::FUSED_R2_OFF_BYTES : 0) + (r0_table ? (size_t)2 * dc * m * 8 : 0) +
                  ((size_t)S * slot_stride + (size_t)dc * m + 3 * (size_t)S) * 8 +
-                 (6 * (size_t)S + 1 + (size_t)S * qbp::NUM_COUNTERS + (size_t)dc * m) * 4 +
+                 (6 * (size_t)S + 1 + (size_t)S * (size_t)slot_counters + (size_t)dc * m) * 4 +
                  2 * (size_t)S * (((size_t)n + 3) / 4) * 4;     // err_lds[2][S][n4] (Monte-Carlo builds)
     return (lds + 15) & ~(size_t)15;
 }
@@ -447,9 +450,14 @@ int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, H
     return QBP_OK;
 }
 
-int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bool mc = false)
+// n_budgets: rows of a qbp_mc_run_budgets launch (its slots keep 2 * n_budgets counter rows in LDS), else 0
+int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bool mc = false, int n_budgets = 0)
 {
     const int m = h->m;
+    const int slot_counters = n_budgets > 0 ? 2 * n_budgets * qbp::NUM_COUNTERS : qbp::NUM_COUNTERS;
+    auto lds_bytes = [&](int dc, int m_, int n_, int S_, bool two_copies = false, bool r0_table = false) {
+        return fused_lds_bytes(dc, m_, n_, S_, two_copies, r0_table, slot_counters);
+    };
     int S = h->opt_slots;
     if (S <= 0) {
         // 16 wavefronts per workgroup (4 per SIMD at the kernel's 128-VGPR budget) was the fastest
@@ -471,20 +479,20 @@ int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bo
     if ((long long)S > B) S = (int)std::max<long long>(B, 1);
     cfg->dc = h->dc;
     cfg->slot_stride = h->dc * m + 2;
-    while (S > 1 && fused_lds_bytes(h->dc, m, h->n, S) > 160 * 1024) --S;   // LDS-limited shapes
+    while (S > 1 && lds_bytes(h->dc, m, h->n, S) > 160 * 1024) --S;   // LDS-limited shapes
     // forced-iteration decode: the one-barrier kernel when two copies of the messages fit (the first one
     // below the constant offset of the second) without giving up a slot
     const bool two = forced && !mc && !h->opt_forced_two_barriers && h->dc == DC_SMALL &&
                      (size_t)S * cfg->slot_stride * 8 <= (size_t)qbp::FUSED_R2_OFF_BYTES &&
-                     fused_lds_bytes(h->dc, m, h->n, S, true) <= 160 * 1024;
+                     lds_bytes(h->dc, m, h->n, S, true) <= 160 * 1024;
     cfg->one_barrier = two ? 1 : 0;
     h->last_one_barrier = cfg->one_barrier;
     cfg->S = S;
     cfg->threads = std::min(qbp::FUSED_MAX_THREADS, ((S * m + 63) / 64) * 64);
     // early exit: the first check step's messages as an LDS table, when it fits beside S slots
-    const bool r0 = !forced && !h->opt_no_r0_table && fused_lds_bytes(h->dc, m, h->n, S, false, true) <= 160 * 1024;
+    const bool r0 = !forced && !h->opt_no_r0_table && lds_bytes(h->dc, m, h->n, S, false, true) <= 160 * 1024;
     cfg->r0_table = r0 ? 1 : 0;
-    const size_t lds = fused_lds_bytes(h->dc, m, h->n, S, two, r0);
+    const size_t lds = lds_bytes(h->dc, m, h->n, S, two, r0);
     if (lds > 160 * 1024) return fail(QBP_E_UNSUPPORTED, "LDS need %zu B exceeds 160 KiB", lds);
     cfg->lds_bytes = (int)lds;
     int per_cu = h->opt_blocks_per_cu;
@@ -593,11 +601,12 @@ int resolve_column_order(qbp_handle* h, unsigned& flags, const double* host_prio
 struct GenericGeom { bool lds_msgs, lds_tables; int mem, r_split, threads, per_cu, grid; size_t lds; };
 
 // inplace: sum-product without damping keeps one message array (qbp_generic.hpp): 8 E bytes instead of 16 E
-static GenericGeom generic_geometry(const qbp_handle* h, long long B, bool inplace)
+// extra_lds: bytes the launch needs behind everything else (qbp_mc_run_budgets: the counter rows), part of g.lds
+static GenericGeom generic_geometry(const qbp_handle* h, long long B, bool inplace, size_t extra_lds = 0)
 {
     GenericGeom g{};
     const int E1 = std::max(h->E, 1);
-    constexpr size_t LDS_MAX = (size_t)160 * 1024;
+    const size_t LDS_MAX = (size_t)160 * 1024 - extra_lds;
     g.lds_msgs = qbp::generic_lds_bytes(h->m, E1, h->n, true, false, 0, inplace) <= LDS_MAX && h->opt_mem == 0;
     // the variable step's tables (prior, message positions) in LDS too when one workgroup per CU is
     // the geometry anyway and they fit beside (or instead of) the messages
@@ -608,7 +617,7 @@ static GenericGeom generic_geometry(const qbp_handle* h, long long B, bool inpla
     const int passes = (work + 1023) / 1024;
     int threads = (((work + passes - 1) / passes) + 63) / 64 * 64;
     int per_cu = std::max(1, 1024 / threads);
-    if (g.lds) per_cu = (int)std::min<size_t>((size_t)per_cu, std::max<size_t>(1, ((size_t)160 * 1024) / g.lds));
+    if (g.lds) per_cu = (int)std::min<size_t>((size_t)per_cu, std::max<size_t>(1, ((size_t)160 * 1024) / (g.lds + extra_lds)));
     per_cu = std::min(per_cu, 8);
     // batches that cannot fill the chip: one wide workgroup per syndrome (latency of a single decode)
     if (B < (long long)h->num_cu * per_cu) {
@@ -638,6 +647,7 @@ static GenericGeom generic_geometry(const qbp_handle* h, long long B, bool inpla
         g.lds_tables = true;
         g.lds = qbp::generic_lds_bytes(h->m, E1, h->n, g.lds_msgs, true, g.r_split, inplace);
     }
+    g.lds += extra_lds;
     g.threads = threads; g.per_cu = per_cu;
     g.grid = (int)std::max<long long>(1, std::min<long long>(B, (long long)h->num_cu * per_cu));
     return g;
@@ -658,6 +668,9 @@ struct McArgs {
     unsigned long long* fail_count;
     uint8_t *fail_syn, *fail_hard, *fail_err;
     double* fail_llr;
+    // qbp_mc_run_budgets: the ladder (host array), else 0 / null
+    int n_budgets;
+    const int32_t* budgets;
 };
 
 template <typename Params>
@@ -668,6 +681,8 @@ static void put_mc(Params& P, const McArgs& a)
     P.thr_cols = a.thr_cols;
     P.fail_list = a.fail_list; P.fail_count = a.fail_count; P.fail_syn = a.fail_syn;
     P.fail_llr = a.fail_llr; P.fail_hard = a.fail_hard; P.fail_err = a.fail_err;
+    P.n_budgets = a.n_budgets;
+    for (int j = 0; j < a.n_budgets; ++j) P.budgets[j] = a.budgets[j];
 }
 
 // Per-call arguments of a BP launch, whichever kernel runs it (device pointers; outputs may be null).
@@ -715,7 +730,9 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     const int variant = c.variant, col_mode = c.col_mode;
     const size_t E = (size_t)std::max(h->E, 1), n = (size_t)h->n;
     const bool inplace = QBP_GENERIC_INPLACE != 0 && variant == QBP_SUM_PRODUCT;
-    const GenericGeom g = generic_geometry(h, B, inplace);
+    // (qbp_mc_run_budgets: the workgroup's 2 * n_budgets counter rows behind everything else in LDS)
+    const size_t budget_lds = c.mc ? (size_t)2 * c.mc->n_budgets * qbp::NUM_COUNTERS * 4 : 0;
+    const GenericGeom g = generic_geometry(h, B, inplace, budget_lds);
     if (g.lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "m = %d checks need %zu B of LDS for the parity bits (limit 160 KiB)",
                     h->m, g.lds);
@@ -764,6 +781,7 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
         HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
         put_mc(G, *c.mc);
         G.wsE = h->d_wsE.p;
+        G.budget_tab_off = (int)(g.lds - budget_lds);
     }
     HIP_TRY(qbp::launch_generic(c.mc != nullptr, g.mem, variant, G, g.grid, g.threads, g.lds, s));
     return QBP_OK;
@@ -995,7 +1013,7 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 {
     const bool mc = c.mc != nullptr, f_order = c.col_mode == 1;
     LaunchCfg cfg;
-    int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc);
+    int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc, mc ? c.mc->n_budgets : 0);
     if (rc) return rc;
     FusedParams P{};
     P.m = h->m; P.n = h->n;
@@ -1019,7 +1037,10 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     if (mc || c.B > (long long)cfg.grid * cfg.S)
         HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
     const bool fast = (c.flags & QBP_FLAG_FAST_MATH) != 0;
-    if (mc && P.thr_cols)               // a sampler threshold per qubit (qbp_mc_run_probs): builds of their own
+    if (mc && P.n_budgets)              // a ladder of iteration budgets (qbp_mc_run_budgets): builds of their own
+        HIP_TRY(fast ? qbp::launch_fused_budgets_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused_budgets(mc, c.variant, P, cfg, s));
+    else if (mc && P.thr_cols)          // a sampler threshold per qubit (qbp_mc_run_probs): builds of their own
         HIP_TRY(fast ? qbp::launch_fused_cols_fast_math(mc, c.variant, P, cfg, s)
                      : qbp::launch_fused_cols(mc, c.variant, P, cfg, s));
     else
@@ -1548,14 +1569,35 @@ try {
 }
 QBP_ABI_CATCH
 
-// probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null
+// budgets [n_budgets] of qbp_mc_run_budgets: 1 <= n_budgets <= QBP_MC_MAX_BUDGETS values >= 1, strictly ascending
+// (host only, before any GPU work)
+static int check_budgets(const int32_t* budgets, int32_t n_budgets)
+{
+    if (!budgets) return fail(QBP_E_INVALID, "budgets is null");
+    if (n_budgets < 1 || n_budgets > QBP_MC_MAX_BUDGETS)
+        return fail(QBP_E_INVALID, "n_budgets = %d out of [1, %d]", n_budgets, QBP_MC_MAX_BUDGETS);
+    for (int j = 0; j < n_budgets; ++j) {
+        if (budgets[j] < 1) return fail(QBP_E_INVALID, "budgets[%d] = %d must be >= 1", j, budgets[j]);
+        if (j > 0 && budgets[j] <= budgets[j - 1])
+            return fail(QBP_E_INVALID, "budgets must be strictly ascending (budgets[%d] = %d after %d)", j, budgets[j],
+                        budgets[j - 1]);
+    }
+    return QBP_OK;
+}
+
+// probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null.
+// budgets (checked by the caller; needs probs): qbp_mc_run_budgets -- max_iter is unused, d_counters is
+// [n_budgets][QBP_NUM_COUNTERS]; else null / 0.
 static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
                        double p, const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
                        int64_t trial_end, const uint8_t* d_errors_in, const double* d_prior, int32_t max_iter,
                        int32_t variant, double alpha, double damping, double clip_llr,
-                       uint32_t flags, int64_t* d_counters, void* stream)
+                       uint32_t flags, int64_t* d_counters, void* stream, const int32_t* budgets = nullptr,
+                       int32_t n_budgets = 0)
 {
     const int64_t T = trial_end - trial_begin;
+    const size_t rows = budgets ? (size_t)n_budgets : 1;       // counter rows = failure-record planes
+    if (budgets) max_iter = budgets[n_budgets - 1];
     int rc = check_decode_args(h, T, max_iter, variant);
     if (rc) return rc;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
@@ -1578,20 +1620,23 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     const bool osd = (flags & QBP_FLAG_OSD0) != 0;
     if (osd) {
         // per-trial records of the trials BP leaves unconverged (read by the OSD kernel)
-        const size_t t = (size_t)T, m = h->m, n = h->n;
-        if (T > QBP_MC_OSD_MAX_TRIALS || t * (m + 10 * n) > ((size_t)16 << 30))
+        // (qbp_mc_run_budgets: a record per trial and budget)
+        const size_t t = (size_t)T * rows, m = h->m, n = h->n;
+        if (t > QBP_MC_OSD_MAX_TRIALS || t * (m + 10 * n) > ((size_t)16 << 30))
             return fail(QBP_E_INVALID, "with QBP_FLAG_OSD0 a call covers at most %lld trials of this matrix "
                                        "(got %lld); split the range",
-                        (long long)std::min<size_t>(QBP_MC_OSD_MAX_TRIALS, ((size_t)16 << 30) / (m + 10 * n)),
+                        (long long)(std::min<size_t>(QBP_MC_OSD_MAX_TRIALS, ((size_t)16 << 30) / (m + 10 * n)) / rows),
                         (long long)T);
+        HIP_TRY(h->d_fail_count.reserve(rows));
         HIP_TRY(h->d_fail_list.reserve(t));
         HIP_TRY(h->d_fail_syn.reserve(t * m));
         HIP_TRY(h->d_fail_llr.reserve(t * n));
         HIP_TRY(h->d_fail_hard.reserve(t * n));
         HIP_TRY(h->d_fail_err.reserve(t * n));
-        HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, sizeof(unsigned long long), s));
+        HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, rows * sizeof(unsigned long long), s));
     }
     McArgs mc{};
+    mc.n_budgets = budgets ? n_budgets : 0; mc.budgets = budgets;
     mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = trial_begin; mc.seed = seed;
     mc.threshold = mc_threshold(p); mc.draws = draws; mc.half_distance = distance / 2;
     mc.thr_cols = probs ? h->d_mc_thr.p : nullptr;
@@ -1606,7 +1651,11 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     c.prior = d_prior; c.B = T; c.max_iter = max_iter; c.variant = variant;
     c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
     c.mc = &mc;
-    if (bp_kernel(h, T, flags, 0, true) == 2) {
+    // (a ladder's counter rows need LDS of their own: a matrix that fills the on-chip kernel's to the last
+    // kilobyte goes to the general-H kernel)
+    const bool ladder_fits = !budgets || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false,
+                                                         2 * n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
+    if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits) {
         h->last_kernel = 2;
         rc = generic_launch(h, c, s);
     } else {
@@ -1616,13 +1665,20 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     if (rc || !osd) return rc;
     // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
     // read from device memory by the kernel itself (no host round trip)
-    qbp::OsdParams O{};
-    O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p);
-    O.list = h->d_fail_list.p;
-    O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
-    O.errors = h->d_fail_err.p; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
-    O.counters = reinterpret_cast<long long*>(d_counters);
-    return osd_launch(h, O, T, s, false, osd_method, osd_order);
+    // (qbp_mc_run_budgets: once per row, on that row's list, records and counters)
+    const size_t m = h->m, n = h->n;
+    for (size_t j = 0; j < rows; ++j) {
+        const size_t r0 = j * (size_t)T;                     // first record of plane j
+        qbp::OsdParams O{};
+        O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p + j);
+        O.list = h->d_fail_list.p + r0;
+        O.syndromes = h->d_fail_syn.p + r0 * m; O.llr = h->d_fail_llr.p + r0 * n; O.hard = h->d_fail_hard.p + r0 * n;
+        O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
+        O.counters = reinterpret_cast<long long*>(d_counters) + j * qbp::NUM_COUNTERS;
+        rc = osd_launch(h, O, T, s, false, osd_method, osd_order);
+        if (rc) return rc;
+    }
+    return QBP_OK;
 }
 
 int qbp_mc_run_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
@@ -1753,6 +1809,53 @@ try {
     HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_budgets_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                              const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                              int64_t trial_end, const double* d_prior, const int32_t* budgets, int32_t n_budgets,
+                              int32_t variant, double alpha, double damping, double clip_llr,
+                              uint32_t flags, int64_t* d_counters, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    int rc = check_budgets(budgets, n_budgets);
+    if (rc) return rc;
+    rc = check_probs(h, probs);
+    if (rc) return rc;
+    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
+                       0, variant, alpha, damping, clip_llr, flags, d_counters, stream, budgets, n_budgets);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_budgets(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                       int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                       const double* prior, const int32_t* budgets, int32_t n_budgets, int32_t variant,
+                       double alpha, double damping, double clip_llr, uint32_t flags, int64_t* counters)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    int rc = check_budgets(budgets, n_budgets);
+    if (rc) return rc;
+    rc = check_probs(h, probs);
+    if (rc) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    const size_t cells = (size_t)n_budgets * qbp::NUM_COUNTERS;
+    HIP_TRY(h->d_prior.reserve(h->n));
+    HIP_TRY(h->d_counters.reserve(cells));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, cells * sizeof(long long), s));
+    rc = qbp_mc_run_budgets_device(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end, h->d_prior.p,
+                                   budgets, n_budgets, variant, alpha, damping, clip_llr, flags,
+                                   reinterpret_cast<int64_t*>(h->d_counters.p), s);
+    if (rc) return rc;
+    long long tmp[QBP_MC_MAX_BUDGETS * qbp::NUM_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, cells * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < cells; ++i) counters[i] += tmp[i];
     return QBP_OK;
 }
 QBP_ABI_CATCH

@@ -130,6 +130,13 @@ struct GenericParams {
     uint8_t* fail_err;                  // [B][n]
     // (last, so that adding it moved no field the other builds read)
     const uint32_t* thr_cols;           // [n4 * 4] a threshold per qubit (QBP_MC_COLS builds: qbp_mc_run_probs)
+    // QBP_MC_BUDGETS builds (qbp_mc_run_budgets; same conventions as the on-chip kernel, qbp_kernels.hpp): ascending
+    // iteration budgets, max_iter = the last one; counters [n_budgets][NUM_COUNTERS]; failure record j * B + b, list j
+    // at fail_list + j * B with its length at fail_count[j].  The workgroup's counter rows, int [2][n_budgets]
+    // [NUM_COUNTERS] ("exactly row j", then "from row j upwards"), sit budget_tab_off bytes into its dynamic LDS.
+    int n_budgets;
+    int budgets[MAX_BUDGETS];
+    int budget_tab_off;
 };
 
 // Dynamic LDS of one workgroup: messages (LDSMSG) + syndrome bits + two parity buffers + counters
@@ -258,6 +265,7 @@ template <int VARIANT, bool MC, int MEM>
 __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
 {
     constexpr bool LDSMSG = MEM == GENERIC_MEM_LDS;
+    constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;     // checkpoints at a ladder of budgets (qbp_mc_run_budgets)
     extern __shared__ __attribute__((aligned(16))) double gsm_all[];
     constexpr NpT np_tab = 0u;          // = the LDS address of gsm_all (no static LDS in this kernel: checked below)
     double* const gsm = gsm_all + NP_LDS_DOUBLES;
@@ -347,6 +355,19 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             *mc_lmask = 0ull; *mc_weight = 0; *mc_diff = 0;
             for (int i = 0; i < NUM_COUNTERS; ++i) mc_cnt[i] = 0;
         }
+    }
+    // BUDGETS: the workgroup's counter rows (only thread 0 touches them), the budgets themselves (read through the
+    // kernel-argument segment: indexing the by-value copy dynamically would move it to scratch memory), and per
+    // trial the row of the next checkpoint and the iteration that ends that budget
+    int* const budget_tab = BUDGETS ? reinterpret_cast<int*>(reinterpret_cast<char*>(gsm_all) + P.budget_tab_off) : nullptr;
+    typedef const GenericParams __attribute__((address_space(4)))* KernArgs;
+    auto budget_at = [&](int j) -> int {
+        return ((KernArgs)__builtin_amdgcn_kernarg_segment_ptr())->budgets[j];
+    };
+    int bj = 0, ck_it = 0;
+    if constexpr (BUDGETS) {
+        if (tid == 0)
+            for (int i = 0; i < 2 * P.n_budgets * NUM_COUNTERS; ++i) budget_tab[i] = 0;
     }
     const int first_long = P.row_off[RC + 1], n_long = P.row_off[RC + 2] - first_long;
     const int lbase = P.row_base[RC + 1], n_ledges = E - lbase;
@@ -457,6 +478,9 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         // to OSD-0.  Called by the whole workgroup.
         auto emit = [&](int conv, int it_done) {
             const bool to_osd = MC && P.fail_list != nullptr && !conv;
+            // BUDGETS: this emission's counter row and failure record (row bj of the ladder)
+            int* const cnt_row = BUDGETS ? budget_tab + ((conv ? P.n_budgets : 0) + bj) * NUM_COUNTERS : mc_cnt;
+            const long long rec = BUDGETS ? (long long)bj * P.B + b : b;
             unsigned long long lm = 0ull;
             int ew = 0, df = 0;
             for (int x = tid; x < n; x += nt) {
@@ -484,9 +508,9 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                 if constexpr (MC) {
                     const unsigned e = err[v];
                     if (to_osd) {
-                        P.fail_llr[b * n + v] = val;
-                        P.fail_hard[b * n + v] = (uint8_t)hd;
-                        P.fail_err[b * n + v] = (uint8_t)e;
+                        P.fail_llr[rec * n + v] = val;
+                        P.fail_hard[rec * n + v] = (uint8_t)hd;
+                        P.fail_err[rec * n + v] = (uint8_t)e;
                     } else {
                         const unsigned res = hd ^ e;
                         ew += (int)e;
@@ -501,10 +525,13 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             if constexpr (MC) {
                 if (to_osd) {
                     for (int w = tid; w < m; w += nt)
-                        P.fail_syn[b * m + P.srow[w]] = (uint8_t)((synw[w >> 5] >> (w & 31)) & 1u);
+                        P.fail_syn[rec * m + P.srow[w]] = (uint8_t)((synw[w >> 5] >> (w & 31)) & 1u);
                     if (tid == 0) {
-                        P.fail_list[atomicAdd(P.fail_count, 1ull)] = b;
-                        mc_cnt[0] += 1; mc_cnt[6] += 1; mc_cnt[7] += it_done;   // BP bookkeeping only
+                        if constexpr (BUDGETS)
+                            P.fail_list[bj * P.B + (long long)atomicAdd(P.fail_count + bj, 1ull)] = b;
+                        else
+                            P.fail_list[atomicAdd(P.fail_count, 1ull)] = b;
+                        cnt_row[0] += 1; cnt_row[6] += 1; cnt_row[7] += it_done;   // BP bookkeeping only
                     }
                 } else {
                     if (lm) atomicXor(mc_lmask, lm);
@@ -512,7 +539,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                     if (df) atomicOr(mc_diff, 1);
                     __syncthreads();
                     if (tid == 0) {
-                        mc_count_trial(mc_cnt, *mc_lmask, *mc_weight, *mc_diff, conv, it_done, P.half_distance);
+                        mc_count_trial(cnt_row, *mc_lmask, *mc_weight, *mc_diff, conv, it_done, P.half_distance);
                         *mc_lmask = 0ull; *mc_weight = 0; *mc_diff = 0;
                     }
                 }
@@ -523,6 +550,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         };
 
         bool frozen = false;
+        if constexpr (BUDGETS) { bj = 0; ck_it = budget_at(0) - 1; }
         for (int it = 0; it < P.max_iter; ++it) {
             const bool scale = !(P.dump_R != nullptr && it == P.dump_iter);
             // ================= check step =======================================================
@@ -681,8 +709,17 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             __syncthreads();                                          // ---- barrier B
             if (frozen) continue;                                     // forced mode after convergence
             const bool conv = unsat[p] == 0;                          // H hard == s
-            if (conv || it == P.max_iter - 1) {
+            bool at_end = it == P.max_iter - 1;
+            if constexpr (BUDGETS) at_end = it == ck_it;                // the end of budget bj is an emission too
+            if (conv || at_end) {
                 emit(conv ? 1 : 0, it);
+                if constexpr (BUDGETS) {
+                    if (!conv && it != P.max_iter - 1) {                  // a checkpoint: on to the next budget
+                        ++bj; ck_it = budget_at(bj) - 1;
+                        __syncthreads();     // emission read R; the next check step overwrites it
+                        continue;
+                    }
+                }
                 frozen = true;
                 if (!(conv && force_full) || it == P.max_iter - 1) break;
                 __syncthreads();     // emission read R; the next check step overwrites it
@@ -696,7 +733,20 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         __syncthreads();
         b = (long long)gridDim.x + (long long)*next_item;   // (next write: after the barrier at the loop top)
     }
-    if constexpr (MC) {
+    if constexpr (BUDGETS) {
+        // counters[j][i] += exact[j][i] + from[0 .. j][i]
+        if (tid == 0)
+            for (int i = 0; i < NUM_COUNTERS; ++i) {
+                long long from = 0;
+                for (int j = 0; j < P.n_budgets; ++j) {
+                    from += budget_tab[(P.n_budgets + j) * NUM_COUNTERS + i];
+                    const long long sum = from + budget_tab[j * NUM_COUNTERS + i];
+                    if (sum)
+                        atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + j * NUM_COUNTERS + i),
+                                  (unsigned long long)sum);
+                }
+            }
+    } else if constexpr (MC) {
         if (tid == 0)
             for (int i = 0; i < NUM_COUNTERS; ++i)
                 if (mc_cnt[i])

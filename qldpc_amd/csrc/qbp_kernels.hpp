@@ -117,6 +117,11 @@ struct FusedParams {
     uint8_t* fail_err;          // [B][n]
     // (last, so that adding it moved no field the other builds read)
     const uint32_t* thr_cols;   // [n4 * 4] a threshold per qubit (QBP_MC_COLS builds: qbp_mc_run_probs)
+    // QBP_MC_BUDGETS builds (qbp_mc_run_budgets): ascending iteration budgets, max_iter = the last one.  counters is
+    // [n_budgets][NUM_COUNTERS] then; the failure records and lists are per (row j, trial b): record j * B + b,
+    // list j at fail_list + j * B, its length at fail_count[j].
+    int n_budgets;
+    int budgets[MAX_BUDGETS];
 };
 
 // Rarely used launch parameters (output pointers, Monte-Carlo settings, ...) are re-read from the
@@ -163,7 +168,8 @@ __device__ __forceinline__ void mc_classify(unsigned long long* mc_lmask, int* m
 //   [S]  end of the chunk of work indices the slot is drawing from (leader only)
 //   [S]  MC logical-mask accumulator
 //   then 32-bit words: flag[2][S], mc_weight[S], mc_diff[S], active_count,
-//   mc_count[S][NUM_COUNTERS] (Monte-Carlo mode only), var_lds[DC][m], err_lds[2][S][n4] bytes (MC)
+//   mc_count[S][NUM_COUNTERS] (Monte-Carlo mode only; [S][2][n_budgets][NUM_COUNTERS] in the QBP_MC_BUDGETS builds),
+//   var_lds[DC][m], err_lds[2][S][n4] bytes (MC)
 template <int DC, int DV, int VARIANT, bool MC, bool FORCE_FULL, int MAX_THREADS, int MIN_WAVES_PER_SIMD,
           bool ONE_BARRIER = false>
 __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kernel(const FusedParams P)
@@ -178,6 +184,12 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     // phase, so the last iteration, which must settle before the registers are reused, keeps its second
     // barrier for the whole workgroup).  With early exit the next check step would be wasted work.
     constexpr bool ONE_BAR = ONE_BARRIER && FORCE_FULL && !MC;
+    // BUDGETS (qbp_mc_run_budgets; the -DQBP_BUDGETS_TU builds only): a trial that ends iteration budgets[j] - 1
+    // unconverged is emitted for counter row j -- what a run with max_iter = budgets[j] reports -- and keeps
+    // iterating.  A slot then has 2 * n_budgets counter rows instead of one: "exactly row j" (checkpoints, and
+    // the last budget) and "from row j upwards" (a trial that converged in iteration k, entered at the first j
+    // with budgets[j] > k); row j of the result = exact[j] + sum of from[0 .. j], formed once per workgroup.
+    constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;
     // dynamic LDS: the tables of the two elementary functions (qbp_math.hpp, NpImage) first -- a constant
     // address, so that a table access is a row offset plus an immediate -- then the carve described above
     extern __shared__ __attribute__((aligned(16))) double smem_all[];
@@ -214,8 +226,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     int* const mc_diff = words + 4 * S;
     int* const work_avg = words + 5 * S;     // [0]: 4 x running mean of the workgroup's iterations per syndrome ([S] reserved)
     int* const active_count = words + 6 * S;
-    int* const mc_count = words + 6 * S + 1 + sl * NUM_COUNTERS;   // this slot's row
-    int* const var_lds = words + 6 * S + 1 + S * NUM_COUNTERS;     // [DC][m], -1 = padding
+    // counter ints per slot: one row, or (BUDGETS) [2][n_budgets] rows, "exactly row j" then "from row j upwards"
+    int slot_counters = NUM_COUNTERS;
+    if constexpr (BUDGETS) slot_counters = 2 * COLD(n_budgets) * NUM_COUNTERS;
+    int* const mc_count = words + 6 * S + 1 + sl * slot_counters;  // this slot's row(s)
+    int* const var_lds = words + 6 * S + 1 + S * slot_counters;    // [DC][m], -1 = padding
     // Monte-Carlo mode: sampled error bytes of the slot's trials, [2][S][n4] (n4 = n rounded up to a
     // multiple of 4), written by the slot's first ceil(n/4) lanes one barrier before use.  Two
     // buffers per slot, used alternately by consecutive trials: the emission of a finished trial still
@@ -318,7 +333,9 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         mc_weight[slot] = 0;
         mc_diff[slot] = 0;
         if (slot == 0) *work_avg = 4 * P.max_iter;
-        if constexpr (MC) {
+        if constexpr (BUDGETS) {
+            for (int i = 0; i < slot_counters; ++i) mc_count[i] = 0;
+        } else if constexpr (MC) {
             for (int i = 0; i < NUM_COUNTERS; ++i) mc_count[i] = 0;
         }
         // (a launch whose syndromes are all some slot's first one never touches the counter: tens of
@@ -349,10 +366,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     unsigned sbit = 0, ebits = 0;
     int it = 0;
     bool frozen = false;
+    // BUDGETS: row of the trial's next checkpoint and the iteration that ends that budget (uniform per slot);
+    // comparing `it` with ck_it is all an iteration gains
+    int bj = 0, ck_it = 0;
 
     auto start_syndrome = [&]() {
         it = 0;
         frozen = false;
+        if constexpr (BUDGETS) { bj = 0; ck_it = COLD(budgets)[0] - 1; }
 #pragma unroll
         for (int j = 0; j < DC; ++j) Q[j] = pri_lds[j * m + c];   // Q = where(mask, initialBelief, 0)
         if constexpr (MC) {
@@ -375,6 +396,15 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     int refill = 0;
     bool mc_pending = false;
     int mc_pending_conv = 0, mc_pending_it = 0;
+    int mc_pending_row = 0;       // BUDGETS: the row of the pending emission (a checkpoint and the trial's convergence
+                                  // one phase later are consecutive emissions of one slot)
+    // the slot's counter row of a pending emission
+    auto pending_row = [&]() -> int* {
+        if constexpr (BUDGETS)
+            return mc_count + ((mc_pending_conv ? COLD(n_budgets) : 0) + mc_pending_row) * NUM_COUNTERS;
+        else
+            return mc_count;
+    };
 
     double val_keep[DC];          // ONE_BAR: posterior values of the lane's edges, alive until the next phase
     // decode-mode emission of the values in val[] (one read of the output pointers per emission --
@@ -538,7 +568,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             }
             if constexpr (MC) {
                 if (mc_pending) {
-                    mc_classify(mc_lmask, mc_weight, mc_diff, mc_count, slot, mc_pending_conv,
+                    mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                                 mc_pending_it, COLD(half_distance),
                                 COLD(fail_list) != nullptr && !mc_pending_conv);
                     mc_pending = false;
@@ -555,17 +585,22 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             // (ONE_BAR: this block runs once per syndrome; reading the limit from the kernel-argument
             // segment here is also what tells tools/valu_mix.py so -- its rule for once-per-syndrome code)
             const bool last = it == (ONE_BAR ? COLD(max_iter) : max_iter) - 1;
-            if (!frozen && (conv || last)) {
+            // (BUDGETS: the end of budget bj is an emission too -- for row bj -- whether it is the last one or not)
+            bool emit_now = conv || last;
+            if constexpr (BUDGETS) emit_now = conv || it == ck_it;
+            if (!frozen && emit_now) {
                 if constexpr (MC) {
                     const ColdArgs ca = cold_args();     // one read of the cold arguments per emission
-                    const long long row = b * ca->n;
+                    long long rec = b;                   // failure record of this emission
+                    if constexpr (BUDGETS) rec = (long long)bj * ca->B + b;
+                    const long long row = rec * ca->n;
                     const int n_iso = ca->n_iso;
                     if (ca->fail_list != nullptr && !conv) {
                         // BP failed: leave the trial to the OSD kernel (record indexed by b)
                         double* const f_llr = ca->fail_llr;
                         uint8_t* const f_hard = ca->fail_hard;
                         uint8_t* const f_err = ca->fail_err;
-                        ca->fail_syn[b * m + c] = (uint8_t)sbit;
+                        ca->fail_syn[rec * m + c] = (uint8_t)sbit;
 #pragma unroll
                         for (int j = 0; j < DC; ++j) {
                             if ((wmask >> j) & 1u) {
@@ -583,7 +618,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                             f_hard[row + v] = (uint8_t)(pv < 0.0);
                             f_err[row + v] = err_lds[v];
                         }
-                        if (c == 0) ca->fail_list[atomicAdd(ca->fail_count, 1ull)] = b;
+                        if constexpr (BUDGETS) {         // list bj, of the records of plane bj
+                            if (c == 0) ca->fail_list[bj * ca->B + (long long)atomicAdd(ca->fail_count + bj, 1ull)] = b;
+                        } else {
+                            if (c == 0) ca->fail_list[atomicAdd(ca->fail_count, 1ull)] = b;
+                        }
                     } else {
                     unsigned long long lm = 0ull;
                     int ew = 0;
@@ -613,7 +652,10 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     if (ew) atomicAdd(&mc_weight[slot], ew);
                     if (df) atomicOr(&mc_diff[slot], 1);
                     }
-                    if (c == 0) { mc_pending = true; mc_pending_conv = conv; mc_pending_it = it; }
+                    if (c == 0) {
+                        mc_pending = true; mc_pending_conv = conv; mc_pending_it = it;
+                        if constexpr (BUDGETS) mc_pending_row = bj;
+                    }
                 } else {
                     emit_decode(val, conv, it);
                 }
@@ -640,6 +682,10 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     if (c == 0) atomicSub(active_count, 1);
                 }
             } else {
+                if constexpr (BUDGETS) {
+                    // budget bj ends here and is not the last one: on to the next checkpoint
+                    if (it == ck_it) { ++bj; ck_it = COLD(budgets)[bj] - 1; }
+                }
                 ++it;
             }
         } else if (active) {
@@ -663,13 +709,33 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             // the last emitted trial of this slot may still be pending (emitted after B2 of the
             // final phase; everybody passed B1 since, so the accumulators are complete)
             if (mc_pending)
-                mc_classify(mc_lmask, mc_weight, mc_diff, mc_count, slot, mc_pending_conv,
+                mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                             mc_pending_it, COLD(half_distance),
                             COLD(fail_list) != nullptr && !mc_pending_conv);
-            for (int i = 0; i < NUM_COUNTERS; ++i)
-                if (mc_count[i])
-                    atomicAdd(reinterpret_cast<unsigned long long*>(COLD(counters) + i),
-                              (unsigned long long)mc_count[i]);
+            if constexpr (!BUDGETS) {
+                for (int i = 0; i < NUM_COUNTERS; ++i)
+                    if (mc_count[i])
+                        atomicAdd(reinterpret_cast<unsigned long long*>(COLD(counters) + i),
+                                  (unsigned long long)mc_count[i]);
+            }
+        }
+        if constexpr (BUDGETS) {
+            // counters[j][i] += sum over the slots of exact[j][i] + from[0 .. j][i]: one thread per (j, i), one
+            // atomic per non-zero entry and workgroup.  (The loop above ends for all threads in the same phase.)
+            __syncthreads();
+            const int K = COLD(n_budgets);
+            const int* const tab = words + 6 * S + 1;            // [S][2][K][NUM_COUNTERS]
+            for (int t = tid; t < K * NUM_COUNTERS; t += blockDim.x) {
+                const int j = t / NUM_COUNTERS, i = t - j * NUM_COUNTERS;
+                long long sum = 0;
+                for (int s = 0; s < S; ++s) {
+                    const int* const rows = tab + s * slot_counters;
+                    sum += rows[j * NUM_COUNTERS + i];
+                    for (int jj = 0; jj <= j; ++jj) sum += rows[(K + jj) * NUM_COUNTERS + i];
+                }
+                if (sum)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(COLD(counters) + t), (unsigned long long)sum);
+            }
         }
     }
 }

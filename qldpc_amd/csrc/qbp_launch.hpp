@@ -41,13 +41,18 @@ hipError_t launch_fused_fast_math(bool mc, int variant, const FusedParams& P, co
 hipError_t launch_fused_cols(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
 hipError_t launch_fused_cols_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
                                        hipStream_t s);
+// the same again, checkpointing at a ladder of iteration budgets (P.budgets; qbp_mc_run_budgets): -DQBP_BUDGETS_TU
+hipError_t launch_fused_budgets(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
+hipError_t launch_fused_budgets_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
+                                          hipStream_t s);
 hipError_t launch_debug_math(int kind, const double* x, double* y, long long count, hipStream_t s);
 hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                             unsigned long long seed, unsigned threshold, hipStream_t s);
 // thr: [n rounded up to 4] thresholds, one per qubit (qbp_mc.hpp, mc_error_quad_cols)
 hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                                  unsigned long long seed, const uint32_t* thr, hipStream_t s);
-// qbp_tu_generic.hip (Monte-Carlo launches with G.thr_cols go to the -DQBP_COLS_TU builds)
+// qbp_tu_generic.hip (Monte-Carlo launches with G.n_budgets go to the -DQBP_BUDGETS_TU builds, others with G.thr_cols to
+// the -DQBP_COLS_TU builds)
 hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G, int grid, int threads,
                           size_t lds, hipStream_t s);
 hipError_t launch_permute_prior(const double* prior, const int32_t* svar, double* out, int n, hipStream_t s);

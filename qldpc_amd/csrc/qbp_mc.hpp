@@ -12,9 +12,18 @@
 #define QBP_MC_COLS 0
 #endif
 
+#ifndef QBP_MC_BUDGETS
+// 1: the Monte-Carlo kernels checkpoint a running trial at a ladder of iteration budgets (qbp_mc_run_budgets):
+// when a trial ends iteration budgets[j] - 1 unconverged it is emitted for counter row j and keeps iterating.
+// Set, together with QBP_MC_COLS, by the translation units compiled for that (-DQBP_BUDGETS_TU), which give those
+// kernels names of their own: the other builds keep their code, registers and scratch.
+#define QBP_MC_BUDGETS 0
+#endif
+
 namespace qbp {
 
 constexpr int NUM_COUNTERS = 12;
+constexpr int MAX_BUDGETS = 16;        // QBP_MC_MAX_BUDGETS of include/qbp.h
 
 __device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
 {

@@ -12,6 +12,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
     python -m qldpc_amd.mc --code 288 --p 0.06 0.05 0.04 --trials 1000000
     python -m torch.distributed.run --nproc-per-node 8 -m qldpc_amd.mc --code 288 ...
     python -m qldpc_amd.mc --dem circuit.dem --trials 1000000 --osd      (detector error model: run_dem)
+    python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
+                                     (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
 """
 from __future__ import annotations
 
@@ -157,6 +159,99 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     return all_reduce(cnt) if all_reduce is not None else cnt
 
 
+def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, draws, seed, variant, alpha, damping,
+                      clip_llr, osd, flags, world, device):
+    """One rank's slice of a ladder on the device, then the one all-reduce of the [K, 12] table."""
+    import torch
+    dev = torch.device("cuda", device)
+    d_table = torch.zeros((len(budgets), NUM_COUNTERS), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
+    step = dec.mc_budgets_step(len(budgets)) if osd else 1 << 40      # OSD keeps records per trial and budget
+    for a in range(begin, end, step):
+        dec.mc_run_budgets_device(L, distance, probs, d_prior.data_ptr(), budgets, a, min(a + step, end),
+                                  d_table.data_ptr(), draws=draws, seed=seed, variant=variant, alpha=alpha,
+                                  damping=damping, clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(d_table)
+    torch.cuda.synchronize(dev)
+    return d_table.cpu().numpy()
+
+
+def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
+                clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1, device=0, runner=None,
+                all_reduce=None):
+    """One error rate, a ladder of BP iteration limits, ONE pass over the trials (qbp_mc_run_budgets): returns the
+    GLOBAL counter table int64[len(budgets), 12] whose row j is the row ``run_sweep(code_name, [p], trials,
+    max_iter=budgets[j], ...)`` returns -- the sweep of BP_per_Iteration.py:40-81.  Sharded and reduced like
+    ``run_sweep`` (one all-reduce of the table).  ValueError, before any GPU work, for budgets that are not 1 to
+    ``_lib.MC_MAX_BUDGETS`` strictly ascending integers >= 1.
+    ``runner(code, p, budgets, begin, end) -> int64[K, 12]`` and ``all_reduce`` are injection points for the CPU
+    tests; by default the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
+    budgets = _lib.check_budgets(budgets)
+    code = codes.load_code(code_name)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(code.Hx, device=device)
+        return _ladder_on_device(dec, code.Lx, code.distance, float(p), prior_of(p, code.n), budgets, begin, end,
+                                 draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping,
+                                 clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
+    table = np.asarray(runner(code, p, budgets, begin, end), np.int64).reshape(len(budgets), NUM_COUNTERS)
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, draws=1, seed=0,
+                    variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
+                    osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+    """``run_dem`` over a ladder of BP iteration limits in one pass: GLOBAL int64[len(budgets), 12], row j = the
+    counters of ``run_dem(..., max_iter=budgets[j])``.  Arguments as ``run_dem``, budgets as ``run_budgets``;
+    ``runner(H, L, probs, prior, budgets, begin, end) -> int64[K, 12]``."""
+    flags = osd_run_flags(osd, osd_method, osd_order)
+    budgets = _lib.check_budgets(budgets)
+    L = np.ascontiguousarray(L, np.uint8)
+    probs = np.ascontiguousarray(probs, np.float64)
+    n = H.shape[1]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if L.shape[0] > 64:
+        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
+    if probs.shape != (n,):
+        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
+    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        return _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, draws=draws, seed=seed,
+                                 variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
+                                 flags=flags, world=world, device=device)
+    table = np.asarray(runner(H, L, probs, prior, budgets, begin, end), np.int64).reshape(len(budgets), NUM_COUNTERS)
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def bp_per_iteration(code_names, p, budgets, trials, osd=True, **kwargs):
+    """The result dictionary of BP_per_Iteration.py:85-88: per code name ``logicalErrors``, ``degeneracies`` and
+    ``OSD_invocations`` (rates per trial, one entry per iteration limit) and ``iterations`` (the limits).  One
+    ``run_budgets`` pass per code; ``kwargs`` go to it.  The script's per-limit LLR lists (``llrs_per_iter*``, its
+    violin plots) are not produced."""
+    results = {}
+    for name in code_names:
+        table = run_budgets(name, p, trials, budgets, osd=osd, **kwargs)
+        t = np.maximum(table[:, 0], 1).astype(np.float64)
+        results[name] = {
+            "logicalErrors": (table[:, 1] / t).tolist(),            # :76-79
+            "degeneracies": (table[:, 5] / t).tolist(),             # :73-74, :80
+            "OSD_invocations": (table[:, 6] / t).tolist(),          # :58-64, :81 (trials BP left unconverged)
+            "iterations": [int(b) for b in budgets],
+        }
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--code", default="[[288, 12, 18]]")
@@ -168,6 +263,9 @@ def main(argv=None):
                     default=[0.05, 0.04, 0.03, 0.02, 0.01, 0.009, 0.008, 0.007])   # :39
     ap.add_argument("--trials", type=int, default=10000)                          # :36
     ap.add_argument("--max-iter", type=int, default=50)
+    ap.add_argument("--budgets", type=int, nargs="+", default=None,
+                    help="a ladder of iteration limits decoded in ONE pass instead of --max-iter (one --p): a result "
+                         "line per limit (run_budgets / run_dem_budgets)")
     ap.add_argument("--draws", type=int, default=1, choices=(1, 2))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variant", choices=("sum-product", "damped", "min-sum"), default="sum-product")
@@ -189,6 +287,13 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order)
     except ValueError as e:
         ap.error(str(e))
+    if args.budgets is not None:
+        try:
+            _lib.check_budgets(args.budgets)
+        except ValueError as e:
+            ap.error(f"--budgets: {e}")
+        if args.dem is None and len(args.p) != 1:
+            ap.error("--budgets takes one --p")
     dem_model = None
     if args.dem is not None:
         from . import dem
@@ -225,7 +330,15 @@ def main(argv=None):
     common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
                   damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
                   osd_order=args.osd_order, device=local)
-    if dem_model is None:
+    if args.budgets is not None:
+        points = list(args.budgets)      # one row per iteration limit
+        del common["max_iter"]
+
+        def sweep(trials, ps, rank, world):          # (the whole ladder, also for the warm-up)
+            if dem_model is None:
+                return run_budgets(args.code, args.p[0], trials, points, rank=rank, world=world, **common)
+            return run_dem_budgets(*dem_model, trials, points, distance=args.distance, rank=rank, world=world, **common)
+    elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
@@ -250,7 +363,15 @@ def main(argv=None):
         rows = []
         for p, row in zip(points, table):
             s = summarize(row)
-            if dem_model is None:
+            if args.budgets is not None:
+                s["max_iter"] = p
+                if dem_model is None:
+                    s["p"] = args.p[0]
+                    label = f"p={args.p[0]}, max_iter={p}"
+                else:
+                    s.update(dem=args.dem)
+                    label = f"dem={args.dem}, max_iter={p}"
+            elif dem_model is None:
                 s["p"] = p
                 label = f"p={p}"
             else:
@@ -261,12 +382,18 @@ def main(argv=None):
             print(f"  {label}: LER={s['ler']:.6f}, BP-only LER={s['ler_bp_only']:.6f}, "
                   f"degeneracies={s['degenerateErrors']}, not converged={s['not_converged']}, "
                   f"mean iters={s['mean_iterations']:.2f}")
-        print(f"{len(points)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
-              f"({len(points) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
+        if args.budgets is not None:
+            print(f"{len(points)} iteration limits, one pass over {args.trials} trials on {world} GPU(s): {dt:.3f} s "
+                  f"({args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
+        else:
+            print(f"{len(points)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
+                  f"({len(points) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
         if args.out:
             with open(args.out, "w") as f:
                 model = {"code": args.code} if dem_model is None else {"dem": args.dem, "distance": args.distance}
-                json.dump({**model, "trials": args.trials, "max_iter": args.max_iter,
+                if args.budgets is not None:
+                    model["budgets"] = points
+                json.dump({**model, "trials": args.trials, "max_iter": points[-1] if args.budgets else args.max_iter,
                            "draws": args.draws, "seed": args.seed, "variant": args.variant,
                            "osd": args.osd, "osd_method": args.osd_method, "osd_order": args.osd_order,
                            "world_size": world, "seconds": dt, "setup_seconds": t_setup, "points": rows},

@@ -15,6 +15,9 @@ UNITS = [("qbp_tu_fused.hip", []), ("qbp_tu_generic.hip", ["-DQBP_GENERIC_MEM=0"
          # Monte-Carlo with a sampler threshold per qubit (qbp_mc_run_probs): bp_fused_cols_kernel, bp_generic_cols_kernel
          ("qbp_tu_fused.hip", ["-DQBP_COLS_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_COLS_TU", f"-DQBP_GENERIC_MEM={i}"])
                                                       for i in range(3)]
+# Monte-Carlo over a ladder of iteration budgets (qbp_mc_run_budgets): bp_fused_budgets_kernel, bp_generic_budgets_kernel
+UNITS += [("qbp_tu_fused.hip", ["-DQBP_BUDGETS_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_BUDGETS_TU", f"-DQBP_GENERIC_MEM={i}"])
+                                                         for i in range(3)]
 
 
 def demangle(sym):
