@@ -324,6 +324,48 @@ int qbp_mc_run_budgets_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, 
                               int32_t variant, double alpha, double damping, double clip_llr,
                               uint32_t flags, int64_t* d_counters, void* stream);
 
+/*
+ * Monte-Carlo with two distributions per call: qbp_mc_run_probs -- the same trials, sampler, decoder, OSD and
+ * counters, digit for digit -- plus two tables, both ADDED to like the counters (rework/main.py:65-112,
+ * spectrum.py:37-54).
+ *   spectrum [QBP_SPECTRUM_ROWS][n + 1].  Per trial: detection = BP's hard decision if BP converged or no OSD flag
+ *   is set, else the OSD output; residual = detection ^ error, w = its weight, logical = any(Lx residual), found =
+ *   BP's converged flag.  w == 0 adds nothing; otherwise spectrum[row][w] += 1 with
+ *     row 0 (weights_found_BP)        found, not logical      row 2 (weights_found_BP_error)   found, logical
+ *     row 1 (weights_found_OSD)       not found, not logical  row 3 (weights_found_OSD_error)  not found, logical
+ *   -- by `found` alone, never by whether OSD ran or its output is valid (rework/main.py:96-110).  Bins are exact
+ *   weights 0 .. n; column 0 stays zero.  spectrum.py's list is row 0 + row 1.
+ *   iter_hist [max_iter + 1], may be null: bin k < max_iter counts the trials whose syndrome was first satisfied in
+ *   0-based iteration k, bin max_iter those BP did not converge on: sum = [0], last bin = [6],
+ *   sum k bin_k + (max_iter - 1) bin_max_iter = [7].
+ * Kernels of their own (bp_fused_spectrum_kernel, bp_generic_spectrum_kernel, osd*_spectrum_kernel); every matrix
+ * qbp_mc_run_probs takes.  QBP_E_INVALID, before any GPU work and with counters and tables untouched: a null
+ * spectrum, max_iter > QBP_MC_SPECTRUM_MAX_ITER (the workgroups keep the iteration histogram on chip), and
+ * whatever qbp_mc_run_probs refuses.  Flags, OSD bits, the QBP_MC_OSD_MAX_TRIALS rule and QBP_E_UNSUPPORTED cases
+ * are those of qbp_mc_run_probs.
+ */
+#define QBP_SPECTRUM_ROWS 4
+#define QBP_MC_SPECTRUM_MAX_ITER 1024
+int qbp_mc_run_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                        int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                        const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                        double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
+                        int64_t* spectrum, int64_t* iter_hist);
+/* Asynchronous form (as qbp_mc_run_probs_device): d_prior, d_counters, d_spectrum and d_iter_hist (may be null) are
+ * device pointers, all three outputs ADDED to; Lx and probs stay host pointers. */
+int qbp_mc_run_spectrum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                               const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                               int64_t trial_end, const double* d_prior, int32_t max_iter,
+                               int32_t variant, double alpha, double damping, double clip_llr,
+                               uint32_t flags, int64_t* d_counters, int64_t* d_spectrum, int64_t* d_iter_hist,
+                               void* stream);
+/* The same on T GIVEN error patterns (as qbp_mc_run_errors, whose counters these are: SET, not added to); spectrum
+ * and iter_hist are ADDED to.  This is how a fixture made by the reference's own loop goes through the product path. */
+int qbp_mc_run_errors_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                               int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                               double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
+                               int64_t* spectrum, int64_t* iter_hist);
+
 /* Errors the sampler of qbp_mc_run_probs draws for trials [trial_begin, trial_begin + T): errors [T][n] host
  * bytes (tests). */
 int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,

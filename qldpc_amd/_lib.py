@@ -30,6 +30,8 @@ OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
 MC_MAX_BUDGETS = 16          # QBP_MC_MAX_BUDGETS: rows of one qbp_mc_run_budgets call
+SPECTRUM_ROWS = 4            # QBP_SPECTRUM_ROWS: weights_found_BP, _OSD, _BP_error, _OSD_error (rework/main.py)
+MC_SPECTRUM_MAX_ITER = 1024  # QBP_MC_SPECTRUM_MAX_ITER: iteration limit of qbp_mc_run_spectrum
 NUM_COUNTERS = 12
 COUNTER_NAMES = ("trials", "logical_error", "BPs_fault", "BPs_miscorrected", "incorrectable",
                  "degenerateErrors", "not_converged", "sum_iterations",
@@ -76,6 +78,15 @@ SIGNATURES = {
     "qbp_mc_run_budgets_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
                                             C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32,
                                             C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_run_spectrum": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64,
+                                      C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double,
+                                      C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP]),
+    "qbp_mc_run_spectrum_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
+                                             C.c_uint64, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
+                                             C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "qbp_mc_run_errors_spectrum": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int32,
+                                             C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP,
+                                             _VP]),
     "qbp_mc_sample_errors_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
@@ -349,6 +360,84 @@ class Decoder:
             self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
             int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_counters, stream or None))
+
+    def _spectrum_tables(self, max_iter, spectrum, iter_hist):
+        """The two tables of the spectrum calls (new zeroed ones, or the caller's, which are added to)."""
+        if int(max_iter) < 1:       # (beyond MC_SPECTRUM_MAX_ITER the library answers QBP_E_INVALID)
+            raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+        if spectrum is None:
+            spectrum = np.zeros((SPECTRUM_ROWS, self.n + 1), np.int64)
+        if iter_hist is None:
+            iter_hist = np.zeros(int(max_iter) + 1, np.int64)
+        for name, a, shape in (("spectrum", spectrum, (SPECTRUM_ROWS, self.n + 1)),
+                               ("iter_hist", iter_hist, (int(max_iter) + 1,))):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int64 and a.shape == shape and a.flags.c_contiguous):
+                raise ValueError(f"{name} must be a C-contiguous int64 array of shape {shape}")
+        return spectrum, iter_hist
+
+    @_locked
+    def mc_run_spectrum(self, Lx, distance, probs, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
+                        variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, spectrum=None,
+                        iter_hist=None):
+        """``mc_run_probs`` plus two distributions (qbp_mc_run_spectrum): returns ``(counters int64[12], spectrum
+        int64[4, n + 1], iter_hist int64[max_iter + 1])``.  Row r of ``spectrum`` is the histogram of residual
+        weights of rework/main.py's list r (weights_found_BP, _OSD, _BP_error, _OSD_error); bin k of ``iter_hist``
+        counts the trials first satisfied in iteration k, bin max_iter those BP did not converge on.  ``probs``: one
+        probability per column, or a scalar p.  Given ``spectrum`` / ``iter_hist`` arrays are added to."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        spectrum, iter_hist = self._spectrum_tables(max_iter, spectrum, iter_hist)
+        counters = np.zeros(NUM_COUNTERS, np.int64)
+        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        for a in range(int(trial_begin), int(trial_end), step):
+            _check(load().qbp_mc_run_spectrum(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
+                                              int(draws), int(seed), a, min(a + step, int(trial_end)),
+                                              pr.ctypes.data, int(max_iter), int(variant), float(alpha),
+                                              float(damping), float(clip_llr), int(flags), counters.ctypes.data,
+                                              spectrum.ctypes.data, iter_hist.ctypes.data))
+        return counters, spectrum, iter_hist
+
+    def mc_run_spectrum_device(self, Lx, distance, probs, d_prior, trial_begin, trial_end, d_counters, d_spectrum,
+                               d_iter_hist=0, draws=1, seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0,
+                               damping=1.0, clip_llr=20.0, flags=0, stream=0):
+        """``mc_run_spectrum`` on device buffers: d_counters int64[12], d_spectrum int64[4, n + 1] and d_iter_hist
+        int64[max_iter + 1] (0: none) are added to.  One call: with FLAG_OSD0 the caller splits ranges by
+        ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        _check(load().qbp_mc_run_spectrum_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
+            int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
+            float(damping), float(clip_llr), int(flags), d_counters, d_spectrum or None, d_iter_hist or None,
+            stream or None))
+
+    @_locked
+    def mc_run_errors_spectrum(self, Lx, distance, errors, prior, max_iter=50, variant=SUM_PRODUCT, alpha=1.0,
+                               damping=1.0, clip_llr=20.0, flags=0):
+        """``mc_run_errors`` plus the two tables of ``mc_run_spectrum`` on GIVEN error patterns uint8[T, n]
+        (qbp_mc_run_errors_spectrum): ``(counters, spectrum, iter_hist)``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        err = np.ascontiguousarray(errors, np.uint8)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
+            raise ValueError("bad shapes")
+        spectrum, iter_hist = self._spectrum_tables(max_iter, None, None)
+        total = np.zeros(NUM_COUNTERS, np.int64)
+        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(len(err), 1)
+        for a in range(0, len(err), step):
+            part = np.zeros(NUM_COUNTERS, np.int64)
+            chunk = err[a:a + step]
+            _check(load().qbp_mc_run_errors_spectrum(
+                self._h, Lx.ctypes.data, Lx.shape[0], int(distance), chunk.ctypes.data, len(chunk), pr.ctypes.data,
+                int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags),
+                part.ctypes.data, spectrum.ctypes.data, iter_hist.ctypes.data))
+            total += part
+        return total, spectrum, iter_hist
 
     def mc_budgets_step(self, n_budgets):
         """Trials one qbp_mc_run_budgets call may cover with FLAG_OSD0: the records are kept per budget."""

@@ -23,6 +23,7 @@
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
 static_assert(QBP_MC_MAX_BUDGETS == qbp::MAX_BUDGETS, "budget ladder length");
+static_assert(QBP_SPECTRUM_ROWS == qbp::SPECTRUM_ROWS, "spectrum rows");
 
 namespace {
 
@@ -127,6 +128,7 @@ struct qbp_handle {
     DevBuf<unsigned long long> d_hist;
     DevBuf<unsigned long long> d_lx_cols;
     DevBuf<long long> d_counters;
+    DevBuf<long long> d_spectrum;    // qbp_mc_run_spectrum: [QBP_SPECTRUM_ROWS][n + 1], then iter_hist [max_iter + 1]
     std::vector<uint8_t> lx_cache;   // last uploaded Lx (host copy) to skip re-uploads
     int lx_cache_k = -1;
     DevBuf<uint32_t> d_mc_thr;       // qbp_mc_run_probs: a sampler threshold per column, [n rounded up to 4]
@@ -202,15 +204,18 @@ using qbp::LaunchCfg;
 
 // Dynamic LDS of one workgroup of the fused kernel (the carve is documented in qbp_kernels.hpp)
 // slot_counters: counter ints per slot (2 * n_budgets rows in the launches of qbp_mc_run_budgets)
+// hist_words: bins of the workgroup's iteration histogram in the launches of qbp_mc_run_spectrum (max_iter + 1; with
+// them a residual-weight word per slot), else 0
 size_t fused_lds_bytes(int dc, int m, int n, int S, bool two_copies = false, bool r0_table = false,
-                       int slot_counters = qbp::NUM_COUNTERS)
+                       int slot_counters = qbp::NUM_COUNTERS, int hist_words = 0)
 {
     const size_t slot_stride = (size_t)dc * m + 2;
     size_t lds = (size_t)qbp::NP_LDS_BYTES +      // tables of tanh / arctanh (qbp_math.hpp), at the start
                  (two_copies ? (size_t)qbp::FUSED_R2_OFF_BYTES : 0) + (r0_table ? (size_t)2 * dc * m * 8 : 0) +
                  ((size_t)S * slot_stride + (size_t)dc * m + 3 * (size_t)S) * 8 +
                  (6 * (size_t)S + 1 + (size_t)S * (size_t)slot_counters + (size_t)dc * m) * 4 +
-                 2 * (size_t)S * (((size_t)n + 3) / 4) * 4;     // err_lds[2][S][n4] (Monte-Carlo builds)
+                 2 * (size_t)S * (((size_t)n + 3) / 4) * 4 +    // err_lds[2][S][n4] (Monte-Carlo builds)
+                 (hist_words ? ((size_t)S + (size_t)hist_words) * 4 : 0);
     return (lds + 15) & ~(size_t)15;
 }
 
@@ -451,12 +456,14 @@ int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, H
 }
 
 // n_budgets: rows of a qbp_mc_run_budgets launch (its slots keep 2 * n_budgets counter rows in LDS), else 0
-int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bool mc = false, int n_budgets = 0)
+// hist_words: max_iter + 1 in a qbp_mc_run_spectrum launch (the workgroup's iteration histogram in LDS), else 0
+int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bool mc = false, int n_budgets = 0,
+             int hist_words = 0)
 {
     const int m = h->m;
     const int slot_counters = n_budgets > 0 ? 2 * n_budgets * qbp::NUM_COUNTERS : qbp::NUM_COUNTERS;
     auto lds_bytes = [&](int dc, int m_, int n_, int S_, bool two_copies = false, bool r0_table = false) {
-        return fused_lds_bytes(dc, m_, n_, S_, two_copies, r0_table, slot_counters);
+        return fused_lds_bytes(dc, m_, n_, S_, two_copies, r0_table, slot_counters, hist_words);
     };
     int S = h->opt_slots;
     if (S <= 0) {
@@ -671,6 +678,9 @@ struct McArgs {
     // qbp_mc_run_budgets: the ladder (host array), else 0 / null
     int n_budgets;
     const int32_t* budgets;
+    // qbp_mc_run_spectrum: the two tables (iter_hist may be null), else null
+    long long* spectrum;
+    long long* iter_hist;
 };
 
 template <typename Params>
@@ -683,6 +693,7 @@ static void put_mc(Params& P, const McArgs& a)
     P.fail_llr = a.fail_llr; P.fail_hard = a.fail_hard; P.fail_err = a.fail_err;
     P.n_budgets = a.n_budgets;
     for (int j = 0; j < a.n_budgets; ++j) P.budgets[j] = a.budgets[j];
+    P.spectrum = a.spectrum; P.iter_hist = a.iter_hist;
 }
 
 // Per-call arguments of a BP launch, whichever kernel runs it (device pointers; outputs may be null).
@@ -732,7 +743,9 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     const bool inplace = QBP_GENERIC_INPLACE != 0 && variant == QBP_SUM_PRODUCT;
     // (qbp_mc_run_budgets: the workgroup's 2 * n_budgets counter rows behind everything else in LDS)
     const size_t budget_lds = c.mc ? (size_t)2 * c.mc->n_budgets * qbp::NUM_COUNTERS * 4 : 0;
-    const GenericGeom g = generic_geometry(h, B, inplace, budget_lds);
+    // (qbp_mc_run_spectrum: its residual-weight word and iteration histogram, likewise)
+    const size_t spectrum_lds = c.mc && c.mc->spectrum ? (((size_t)c.max_iter + 2) * 4 + 7) & ~(size_t)7 : 0;
+    const GenericGeom g = generic_geometry(h, B, inplace, budget_lds + spectrum_lds);
     if (g.lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "m = %d checks need %zu B of LDS for the parity bits (limit 160 KiB)",
                     h->m, g.lds);
@@ -781,7 +794,8 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
         HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
         put_mc(G, *c.mc);
         G.wsE = h->d_wsE.p;
-        G.budget_tab_off = (int)(g.lds - budget_lds);
+        G.budget_tab_off = (int)(g.lds - budget_lds - spectrum_lds);
+        G.spectrum_off = (int)(g.lds - spectrum_lds);
     }
     HIP_TRY(qbp::launch_generic(c.mc != nullptr, g.mem, variant, G, g.grid, g.threads, g.lds, s));
     return QBP_OK;
@@ -1013,7 +1027,8 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 {
     const bool mc = c.mc != nullptr, f_order = c.col_mode == 1;
     LaunchCfg cfg;
-    int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc, mc ? c.mc->n_budgets : 0);
+    int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc, mc ? c.mc->n_budgets : 0,
+                      mc && c.mc->spectrum ? c.max_iter + 1 : 0);
     if (rc) return rc;
     FusedParams P{};
     P.m = h->m; P.n = h->n;
@@ -1037,7 +1052,10 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     if (mc || c.B > (long long)cfg.grid * cfg.S)
         HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
     const bool fast = (c.flags & QBP_FLAG_FAST_MATH) != 0;
-    if (mc && P.n_budgets)              // a ladder of iteration budgets (qbp_mc_run_budgets): builds of their own
+    if (mc && P.spectrum)               // residual-weight and iteration tables (qbp_mc_run_spectrum): builds of their own
+        HIP_TRY(fast ? qbp::launch_fused_spectrum_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused_spectrum(mc, c.variant, P, cfg, s));
+    else if (mc && P.n_budgets)         // a ladder of iteration budgets (qbp_mc_run_budgets): builds of their own
         HIP_TRY(fast ? qbp::launch_fused_budgets_fast_math(mc, c.variant, P, cfg, s)
                      : qbp::launch_fused_budgets(mc, c.variant, P, cfg, s));
     else if (mc && P.thr_cols)          // a sampler threshold per qubit (qbp_mc_run_probs): builds of their own
@@ -1405,7 +1423,9 @@ static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long ma
     }
     Wk.At = h->d_osd_At.p; Wk.pivcol = h->d_osd_piv.p; Wk.posn = h->d_osd_posn.p; Wk.sol = h->d_osd_sol.p;
     Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
-    HIP_TRY(qbp::launch_osd_big((unsigned)grid, Wk.keys_in_lds ? NP * 12 : 0, O, Wk, s));
+    // (O.spectrum, here and in osd_launch: the builds that add residual weights to that table, qbp_mc_run_spectrum)
+    HIP_TRY((O.spectrum ? qbp::launch_osd_big_spectrum : qbp::launch_osd_big)((unsigned)grid, Wk.keys_in_lds ? NP * 12 : 0,
+                                                                            O, Wk, s));
     return QBP_OK;
 }
 
@@ -1489,15 +1509,17 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
         }
         Wk.At = h->d_osd_At.p; Wk.sol = h->d_osd_sol.p; Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
         const int rpt = m <= 1024 ? 1 : m <= 2048 ? 2 : m <= 4096 ? 4 : 8;
-        HIP_TRY(qbp::launch_osd_blocked(rpt, (unsigned)grid, lds, O, Wk, s));
+        HIP_TRY((O.spectrum ? qbp::launch_osd_blocked_spectrum : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk, s));
     } else if (method) {
         // order w (parse_osd_flags has checked osd_ok and the LDS)
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
         const size_t olds = (qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
-        HIP_TRY(qbp::launch_osd_order(h->osd_W + 1, (unsigned)grid, olds, O, method, order, s));
+        HIP_TRY((O.spectrum ? qbp::launch_osd_order_spectrum : qbp::launch_osd_order)(h->osd_W + 1, (unsigned)grid, olds, O,
+                                                                                    method, order, s));
     } else {
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
-        HIP_TRY(qbp::launch_osd_small(h->osd_W + 1, (unsigned)grid, (size_t)h->osd_lds, O, s));
+        HIP_TRY((O.spectrum ? qbp::launch_osd_small_spectrum : qbp::launch_osd_small)(h->osd_W + 1, (unsigned)grid,
+                                                                                    (size_t)h->osd_lds, O, s));
     }
     if (redo) {
         qbp::OsdParams R = O;
@@ -1588,12 +1610,14 @@ static int check_budgets(const int32_t* budgets, int32_t n_budgets)
 // probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null.
 // budgets (checked by the caller; needs probs): qbp_mc_run_budgets -- max_iter is unused, d_counters is
 // [n_budgets][QBP_NUM_COUNTERS]; else null / 0.
+// d_spectrum (not with budgets): qbp_mc_run_spectrum -- [QBP_SPECTRUM_ROWS][n + 1] and d_iter_hist [max_iter + 1] (may
+// be null), device, added to; with d_errors_in too (qbp_mc_run_errors_spectrum); else null.
 static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
                        double p, const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
                        int64_t trial_end, const uint8_t* d_errors_in, const double* d_prior, int32_t max_iter,
                        int32_t variant, double alpha, double damping, double clip_llr,
                        uint32_t flags, int64_t* d_counters, void* stream, const int32_t* budgets = nullptr,
-                       int32_t n_budgets = 0)
+                       int32_t n_budgets = 0, int64_t* d_spectrum = nullptr, int64_t* d_iter_hist = nullptr)
 {
     const int64_t T = trial_end - trial_begin;
     const size_t rows = budgets ? (size_t)n_budgets : 1;       // counter rows = failure-record planes
@@ -1637,6 +1661,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     }
     McArgs mc{};
     mc.n_budgets = budgets ? n_budgets : 0; mc.budgets = budgets;
+    mc.spectrum = reinterpret_cast<long long*>(d_spectrum); mc.iter_hist = reinterpret_cast<long long*>(d_iter_hist);
     mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = trial_begin; mc.seed = seed;
     mc.threshold = mc_threshold(p); mc.draws = draws; mc.half_distance = distance / 2;
     mc.thr_cols = probs ? h->d_mc_thr.p : nullptr;
@@ -1655,7 +1680,10 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     // kilobyte goes to the general-H kernel)
     const bool ladder_fits = !budgets || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false,
                                                          2 * n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
-    if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits) {
+    // (likewise the iteration histogram of qbp_mc_run_spectrum)
+    const bool hist_fits = !d_spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false, qbp::NUM_COUNTERS,
+                                                          max_iter + 1) <= 160 * 1024;
+    if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits || !hist_fits) {
         h->last_kernel = 2;
         rc = generic_launch(h, c, s);
     } else {
@@ -1675,6 +1703,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         O.syndromes = h->d_fail_syn.p + r0 * m; O.llr = h->d_fail_llr.p + r0 * n; O.hard = h->d_fail_hard.p + r0 * n;
         O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
         O.counters = reinterpret_cast<long long*>(d_counters) + j * qbp::NUM_COUNTERS;
+        O.spectrum = reinterpret_cast<long long*>(d_spectrum);
         rc = osd_launch(h, O, T, s, false, osd_method, osd_order);
         if (rc) return rc;
     }
@@ -1857,6 +1886,116 @@ try {
     HIP_TRY(hipStreamSynchronize(s));
     for (size_t i = 0; i < cells; ++i) counters[i] += tmp[i];
     return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// Arguments qbp_mc_run_spectrum* refuse on top of qbp_mc_run_probs (host only, before any GPU work)
+static int check_spectrum(qbp_handle* h, const int64_t* spectrum, int32_t max_iter, uint32_t flags)
+{
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!spectrum) return fail(QBP_E_INVALID, "spectrum is null");
+    if (max_iter > QBP_MC_SPECTRUM_MAX_ITER)
+        return fail(QBP_E_INVALID, "max_iter = %d beyond QBP_MC_SPECTRUM_MAX_ITER = %d", max_iter,
+                    QBP_MC_SPECTRUM_MAX_ITER);
+    int method = 0, order = 0;
+    return parse_osd_flags(h, flags, true, &method, &order);
+}
+
+int qbp_mc_run_spectrum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                               const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                               int64_t trial_end, const double* d_prior, int32_t max_iter,
+                               int32_t variant, double alpha, double damping, double clip_llr,
+                               uint32_t flags, int64_t* d_counters, int64_t* d_spectrum, int64_t* d_iter_hist,
+                               void* stream)
+try {
+    int rc = check_spectrum(h, d_spectrum, max_iter, flags);
+    if (rc) return rc;
+    rc = check_probs(h, probs);
+    if (rc) return rc;
+    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
+                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream, nullptr, 0, d_spectrum,
+                       d_iter_hist);
+}
+QBP_ABI_CATCH
+
+// Host-array forms of the two spectrum entries: tables zeroed on the device, the run, then counters and tables
+// copied back.  errors != null: qbp_mc_run_errors_spectrum (T patterns; counters set), else sampled trials
+// (counters added to).
+static int mc_run_spectrum_host(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                                int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                                const uint8_t* errors, const double* prior, int32_t max_iter, int32_t variant,
+                                double alpha, double damping, double clip_llr, uint32_t flags, int64_t* counters,
+                                int64_t* spectrum, int64_t* iter_hist)
+{
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    const size_t n = (size_t)h->n, T = (size_t)(trial_end - trial_begin);
+    const size_t spec_cells = (size_t)QBP_SPECTRUM_ROWS * (n + 1), hist_cells = (size_t)std::max(max_iter, 0) + 1;
+    HIP_TRY(h->d_prior.reserve(n));
+    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
+    HIP_TRY(h->d_spectrum.reserve(spec_cells + hist_cells));
+    if (errors) {
+        HIP_TRY(h->d_hard.reserve(T * n));                // (scratch of the host-pointer entries: the errors)
+        HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, T * n, hipMemcpyHostToDevice, s));
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
+    HIP_TRY(hipMemsetAsync(h->d_spectrum.p, 0, (spec_cells + hist_cells) * sizeof(long long), s));
+    int64_t* const d_spec = reinterpret_cast<int64_t*>(h->d_spectrum.p);
+    const int rc = mc_run_impl(h, Lx, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end,
+                               errors ? h->d_hard.p : nullptr, h->d_prior.p, max_iter, variant, alpha, damping, clip_llr,
+                               flags, reinterpret_cast<int64_t*>(h->d_counters.p), s, nullptr, 0, d_spec,
+                               iter_hist ? d_spec + spec_cells : nullptr);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    long long tmp[qbp::NUM_COUNTERS];
+    std::vector<long long> tab(spec_cells + hist_cells);
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(tab.data(), h->d_spectrum.p, tab.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] = errors ? tmp[i] : counters[i] + tmp[i];
+    for (size_t i = 0; i < spec_cells; ++i) spectrum[i] += tab[i];
+    if (iter_hist)
+        for (size_t i = 0; i < hist_cells; ++i) iter_hist[i] += tab[spec_cells + i];
+    return QBP_OK;
+}
+
+int qbp_mc_run_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                        int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                        const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                        double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
+                        int64_t* spectrum, int64_t* iter_hist)
+try {
+    int rc = check_spectrum(h, spectrum, max_iter, flags);
+    if (rc) return rc;
+    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    rc = check_probs(h, probs);
+    if (rc) return rc;
+    rc = check_decode_args(h, trial_end - trial_begin, max_iter, variant);
+    if (rc) return rc;
+    return mc_run_spectrum_host(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end, nullptr, prior, max_iter,
+                                variant, alpha, damping, clip_llr, flags, counters, spectrum, iter_hist);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_errors_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                               int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                               double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
+                               int64_t* spectrum, int64_t* iter_hist)
+try {
+    int rc = check_spectrum(h, spectrum, max_iter, flags);
+    if (rc) return rc;
+    if (!errors || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    rc = check_decode_args(h, T, max_iter, variant);
+    if (rc) return rc;
+    if (T == 0) {
+        for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] = 0;
+        return QBP_OK;
+    }
+    // (probs, draws, seed are unused with stored errors)
+    return mc_run_spectrum_host(h, Lx, k, distance, nullptr, 1, 0, 0, T, errors, prior, max_iter, variant, alpha, damping,
+                                clip_llr, flags, counters, spectrum, iter_hist);
 }
 QBP_ABI_CATCH
 

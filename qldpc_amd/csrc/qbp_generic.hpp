@@ -137,6 +137,12 @@ struct GenericParams {
     int n_budgets;
     int budgets[MAX_BUDGETS];
     int budget_tab_off;
+    // QBP_MC_SPECTRUM builds (qbp_mc_run_spectrum; as the on-chip kernel, qbp_kernels.hpp): spectrum [SPECTRUM_ROWS]
+    // [n + 1] and iter_hist [max_iter + 1] (may be null), atomically added to.  The workgroup's int words -- residual
+    // weight accumulator, then its iteration histogram [max_iter + 1] -- sit spectrum_off bytes into its dynamic LDS.
+    long long* spectrum;
+    long long* iter_hist;
+    int spectrum_off;
 };
 
 // Dynamic LDS of one workgroup: messages (LDSMSG) + syndrome bits + two parity buffers + counters
@@ -266,6 +272,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
 {
     constexpr bool LDSMSG = MEM == GENERIC_MEM_LDS;
     constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;     // checkpoints at a ladder of budgets (qbp_mc_run_budgets)
+    constexpr bool SPECTRUM = MC && QBP_MC_SPECTRUM != 0;   // residual-weight / iteration tables (qbp_mc_run_spectrum)
     extern __shared__ __attribute__((aligned(16))) double gsm_all[];
     constexpr NpT np_tab = 0u;          // = the LDS address of gsm_all (no static LDS in this kernel: checked below)
     double* const gsm = gsm_all + NP_LDS_DOUBLES;
@@ -369,6 +376,12 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         if (tid == 0)
             for (int i = 0; i < 2 * P.n_budgets * NUM_COUNTERS; ++i) budget_tab[i] = 0;
     }
+    // SPECTRUM: the workgroup's residual weight accumulator and iteration histogram (bins: thread 0 only)
+    int* const mc_resw = SPECTRUM ? reinterpret_cast<int*>(reinterpret_cast<char*>(gsm_all) + P.spectrum_off) : nullptr;
+    int* const it_hist = SPECTRUM ? mc_resw + 1 : nullptr;
+    if constexpr (SPECTRUM) {
+        for (int i = tid; i <= P.max_iter + 1; i += nt) mc_resw[i] = 0;     // (published by the syndrome loop's barriers)
+    }
     const int first_long = P.row_off[RC + 1], n_long = P.row_off[RC + 2] - first_long;
     const int lbase = P.row_base[RC + 1], n_ledges = E - lbase;
     const int first_lcol = P.col_off[CC + 1], n_lcol = P.col_off[CC + 2] - first_lcol;
@@ -405,7 +418,11 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             // (beliefPropagationGPU.py:195)
             for (int g = tid; g < n4; g += nt)
                 reinterpret_cast<unsigned*>(err)[g] =
-#if QBP_MC_COLS      // (builds of qbp_mc_run_probs: qbp_tu_generic.hip -DQBP_COLS_TU)
+#if QBP_MC_SPECTRUM  // (builds of qbp_mc_run_spectrum: per-qubit thresholds, or stored errors)
+                    P.errors_in ? mc_stored_quad(P.errors_in + b * n, g, n)
+                                : mc_error_quad_cols((unsigned long long)(P.trial_begin + b), g, P.draws, P.seed,
+                                                     P.thr_cols);
+#elif QBP_MC_COLS    // (builds of qbp_mc_run_probs: qbp_tu_generic.hip -DQBP_COLS_TU)
                     mc_error_quad_cols((unsigned long long)(P.trial_begin + b), g, P.draws, P.seed, P.thr_cols);
 #else
                     P.errors_in ? mc_stored_quad(P.errors_in + b * n, g, n)
@@ -483,6 +500,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             const long long rec = BUDGETS ? (long long)bj * P.B + b : b;
             unsigned long long lm = 0ull;
             int ew = 0, df = 0;
+            int rw = 0;                                      // SPECTRUM: weight of the residual (this thread's share)
             for (int x = tid; x < n; x += nt) {
                 double val;
                 if (x < P.col_off[1]) {
@@ -515,6 +533,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                         const unsigned res = hd ^ e;
                         ew += (int)e;
                         df |= (int)res;
+                        if constexpr (SPECTRUM) rw += (int)res;
                         if (res) lm ^= P.lx_cols[v];
                     }
                 } else {
@@ -532,13 +551,27 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                         else
                             P.fail_list[atomicAdd(P.fail_count, 1ull)] = b;
                         cnt_row[0] += 1; cnt_row[6] += 1; cnt_row[7] += it_done;   // BP bookkeeping only
+                        if constexpr (SPECTRUM) it_hist[P.max_iter] += 1;          // (its weight: the OSD kernel's)
                     }
                 } else {
                     if (lm) atomicXor(mc_lmask, lm);
                     if (ew) atomicAdd(mc_weight, ew);
                     if (df) atomicOr(mc_diff, 1);
+                    if constexpr (SPECTRUM) {
+                        if (rw) atomicAdd(mc_resw, rw);
+                    }
                     __syncthreads();
                     if (tid == 0) {
+                        if constexpr (SPECTRUM) {
+                            it_hist[conv ? it_done : P.max_iter] += 1;
+                            const int w = *mc_resw;
+                            if (w) {
+                                *mc_resw = 0;
+                                const int row = mc_spectrum_row(conv != 0, *mc_lmask != 0ull);
+                                atomicAdd(reinterpret_cast<unsigned long long*>(P.spectrum + (long long)row * (n + 1) + w),
+                                          1ull);
+                            }
+                        }
                         mc_count_trial(cnt_row, *mc_lmask, *mc_weight, *mc_diff, conv, it_done, P.half_distance);
                         *mc_lmask = 0ull; *mc_weight = 0; *mc_diff = 0;
                     }
@@ -732,6 +765,14 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
         }
         __syncthreads();
         b = (long long)gridDim.x + (long long)*next_item;   // (next write: after the barrier at the loop top)
+    }
+    if constexpr (SPECTRUM) {
+        // the workgroup's iteration histogram: one global atomic per non-zero bin
+        __syncthreads();
+        if (P.iter_hist != nullptr)
+            for (int i = tid; i <= P.max_iter; i += nt)
+                if (it_hist[i])
+                    atomicAdd(reinterpret_cast<unsigned long long*>(P.iter_hist + i), (unsigned long long)it_hist[i]);
     }
     if constexpr (BUDGETS) {
         // counters[j][i] += exact[j][i] + from[0 .. j][i]

@@ -122,6 +122,11 @@ struct FusedParams {
     // list j at fail_list + j * B, its length at fail_count[j].
     int n_budgets;
     int budgets[MAX_BUDGETS];
+    // QBP_MC_SPECTRUM builds (qbp_mc_run_spectrum): spectrum [SPECTRUM_ROWS][n + 1], the residual weights of the
+    // classified trials by row (mc_spectrum_row), and iter_hist [max_iter + 1] (may be null), the iteration a trial's
+    // syndrome was first satisfied in (bin max_iter: never); both atomically added to
+    long long* spectrum;
+    long long* iter_hist;
 };
 
 // Rarely used launch parameters (output pointers, Monte-Carlo settings, ...) are re-read from the
@@ -169,7 +174,9 @@ __device__ __forceinline__ void mc_classify(unsigned long long* mc_lmask, int* m
 //   [S]  MC logical-mask accumulator
 //   then 32-bit words: flag[2][S], mc_weight[S], mc_diff[S], active_count,
 //   mc_count[S][NUM_COUNTERS] (Monte-Carlo mode only; [S][2][n_budgets][NUM_COUNTERS] in the QBP_MC_BUDGETS builds),
-//   var_lds[DC][m], err_lds[2][S][n4] bytes (MC)
+//   var_lds[DC][m], err_lds[2][S][n4] bytes (MC),
+//   then 32-bit words again in the QBP_MC_SPECTRUM builds: mc_resw[S] (residual weight accumulator of the slot),
+//   it_hist[max_iter + 1] (the workgroup's iteration histogram)
 template <int DC, int DV, int VARIANT, bool MC, bool FORCE_FULL, int MAX_THREADS, int MIN_WAVES_PER_SIMD,
           bool ONE_BARRIER = false>
 __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kernel(const FusedParams P)
@@ -190,6 +197,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     // the last budget) and "from row j upwards" (a trial that converged in iteration k, entered at the first j
     // with budgets[j] > k); row j of the result = exact[j] + sum of from[0 .. j], formed once per workgroup.
     constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;
+    // SPECTRUM (qbp_mc_run_spectrum; the -DQBP_SPECTRUM_TU builds only): a classified trial's residual weight goes to
+    // the global table spectrum[row][w] (w > 0 only: rare at the error rates of interest, so straight to global
+    // memory with a 64-bit atomic), every trial's iteration index to the workgroup's histogram in LDS (one LDS atomic
+    // per trial by its slot leader; one global atomic per non-zero bin when the workgroup ends).
+    constexpr bool SPECTRUM = MC && QBP_MC_SPECTRUM != 0;
     // dynamic LDS: the tables of the two elementary functions (qbp_math.hpp, NpImage) first -- a constant
     // address, so that a table access is a row offset plus an immediate -- then the carve described above
     extern __shared__ __attribute__((aligned(16))) double smem_all[];
@@ -242,6 +254,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     auto err_buf = [&]() -> unsigned char* {
         const int n4 = COLD(n_words4) * 4;
         return reinterpret_cast<unsigned char*>(var_lds + DC * m) + (size_t)(sl + (err_par ? S : 0)) * n4;
+    };
+
+    // SPECTRUM: mc_resw[S] then it_hist[max_iter + 1], behind the error bytes (recomputed where used, as err_buf)
+    auto spec_words = [&]() -> int* {
+        return var_lds + DC * m + 2 * S * COLD(n_words4);
     };
 
     // ---- check step of one row: q[DC] -> put(j, r) for its DC edges (qbp_check.hpp) -----------------
@@ -332,6 +349,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         mc_lmask[slot] = 0ull;
         mc_weight[slot] = 0;
         mc_diff[slot] = 0;
+        if constexpr (SPECTRUM) spec_words()[slot] = 0;
         if (slot == 0) *work_avg = 4 * P.max_iter;
         if constexpr (BUDGETS) {
             for (int i = 0; i < slot_counters; ++i) mc_count[i] = 0;
@@ -350,6 +368,10 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         long long first = (long long)blockIdx.x * S;
         long long cnt = B - first;
         *active_count = (int)(cnt < 0 ? 0 : (cnt > S ? S : cnt));
+    }
+    if constexpr (SPECTRUM) {
+        int* const it_hist = spec_words() + S;
+        for (int i = tid; i <= P.max_iter; i += blockDim.x) it_hist[i] = 0;
     }
 
     // The lane's own check->variable messages are needed again in the variable step (Q = value - R):
@@ -406,6 +428,22 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             return mc_count;
     };
 
+    // SPECTRUM: the pending emission's share of the two tables, by the slot leader just before mc_classify (which
+    // clears the logical mask): the iteration bin of every trial, deferred to OSD or not, and the residual weight of
+    // a trial classified here (the OSD kernels add those of the deferred ones)
+    auto spectrum_pending = [&]() {
+        const ColdArgs ca = cold_args();
+        int* const sw = spec_words();
+        atomicAdd(&sw[S + (mc_pending_conv ? mc_pending_it : ca->max_iter)], 1);
+        if (ca->fail_list != nullptr && !mc_pending_conv) return;
+        const int w = sw[slot];
+        if (w) {
+            sw[slot] = 0;
+            const int row = mc_spectrum_row(mc_pending_conv != 0, mc_lmask[slot] != 0ull);
+            atomicAdd(reinterpret_cast<unsigned long long*>(ca->spectrum + (long long)row * (ca->n + 1) + w), 1ull);
+        }
+    };
+
     double val_keep[DC];          // ONE_BAR: posterior values of the lane's edges, alive until the next phase
     // decode-mode emission of the values in val[] (one read of the output pointers per emission --
     // adjacent kernel arguments: a single scalar load -- not one per use)
@@ -452,7 +490,13 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 err_par ^= 1u;
                 unsigned* const err_words = reinterpret_cast<unsigned*>(err_buf());
                 const unsigned long long trial = (unsigned long long)(COLD(trial_begin) + b);
-#if QBP_MC_COLS
+#if QBP_MC_SPECTRUM      /* per-qubit thresholds, or stored errors (qbp_mc_run_errors_spectrum) */
+                const uint32_t* const thr = COLD(thr_cols);
+                const uint8_t* const ein = COLD(errors_in);
+                for (int g = c; g < P.n_words4; g += m)
+                    err_words[g] = ein ? mc_stored_quad(ein + b * COLD(n), g, COLD(n))
+                                       : mc_error_quad_cols(trial, g, COLD(draws), COLD(seed), thr);
+#elif QBP_MC_COLS
                 const uint32_t* const thr = COLD(thr_cols);
                 for (int g = c; g < P.n_words4; g += m)
                     err_words[g] = mc_error_quad_cols(trial, g, COLD(draws), COLD(seed), thr);
@@ -568,6 +612,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             }
             if constexpr (MC) {
                 if (mc_pending) {
+                    if constexpr (SPECTRUM) spectrum_pending();
                     mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                                 mc_pending_it, COLD(half_distance),
                                 COLD(fail_list) != nullptr && !mc_pending_conv);
@@ -627,6 +672,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     unsigned long long lm = 0ull;
                     int ew = 0;
                     unsigned df = 0;
+                    int rw = 0;                          // SPECTRUM: weight of the residual (this lane's share)
                     const unsigned long long* const lx = ca->lx_cols;
 #pragma unroll
                     for (int j = 0; j < DC; ++j) {
@@ -635,6 +681,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                             const unsigned res = (val[j] < 0.0 ? 1u : 0u) ^ e;
                             ew += (int)e;
                             df |= res;
+                            if constexpr (SPECTRUM) rw += (int)res;
                             const int v = var_lds[j * m + c];
                             if (res) lm ^= lx[v];
                         }
@@ -646,7 +693,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                         const unsigned res = (COLD(prior)[v] < 0.0 ? 1u : 0u) ^ e;
                         ew += (int)e;
                         df |= res;
+                        if constexpr (SPECTRUM) rw += (int)res;
                         if (res) lm ^= lx[v];
+                    }
+                    if constexpr (SPECTRUM) {
+                        if (rw) atomicAdd(&spec_words()[slot], rw);
                     }
                     if (lm) atomicXor(&mc_lmask[slot], lm);
                     if (ew) atomicAdd(&mc_weight[slot], ew);
@@ -708,16 +759,29 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         if (leader) {
             // the last emitted trial of this slot may still be pending (emitted after B2 of the
             // final phase; everybody passed B1 since, so the accumulators are complete)
-            if (mc_pending)
+            if (mc_pending) {
+                if constexpr (SPECTRUM) spectrum_pending();
                 mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                             mc_pending_it, COLD(half_distance),
                             COLD(fail_list) != nullptr && !mc_pending_conv);
+            }
             if constexpr (!BUDGETS) {
                 for (int i = 0; i < NUM_COUNTERS; ++i)
                     if (mc_count[i])
                         atomicAdd(reinterpret_cast<unsigned long long*>(COLD(counters) + i),
                                   (unsigned long long)mc_count[i]);
             }
+        }
+        if constexpr (SPECTRUM) {
+            // the workgroup's iteration histogram: one global atomic per non-zero bin.  (The loop above ends for all
+            // threads in the same phase.)
+            __syncthreads();
+            long long* const out = COLD(iter_hist);
+            const int* const it_hist = spec_words() + S;
+            if (out != nullptr)
+                for (int i = tid; i <= COLD(max_iter); i += blockDim.x)
+                    if (it_hist[i])
+                        atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)it_hist[i]);
         }
         if constexpr (BUDGETS) {
             // counters[j][i] += sum over the slots of exact[j][i] + from[0 .. j][i]: one thread per (j, i), one

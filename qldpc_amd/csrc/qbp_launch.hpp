@@ -45,14 +45,19 @@ hipError_t launch_fused_cols_fast_math(bool mc, int variant, const FusedParams& 
 hipError_t launch_fused_budgets(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
 hipError_t launch_fused_budgets_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
                                           hipStream_t s);
+// the same again, adding residual weights and iteration indices to tables (P.spectrum; qbp_mc_run_spectrum):
+// -DQBP_SPECTRUM_TU
+hipError_t launch_fused_spectrum(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
+hipError_t launch_fused_spectrum_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
+                                           hipStream_t s);
 hipError_t launch_debug_math(int kind, const double* x, double* y, long long count, hipStream_t s);
 hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                             unsigned long long seed, unsigned threshold, hipStream_t s);
 // thr: [n rounded up to 4] thresholds, one per qubit (qbp_mc.hpp, mc_error_quad_cols)
 hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                                  unsigned long long seed, const uint32_t* thr, hipStream_t s);
-// qbp_tu_generic.hip (Monte-Carlo launches with G.n_budgets go to the -DQBP_BUDGETS_TU builds, others with G.thr_cols to
-// the -DQBP_COLS_TU builds)
+// qbp_tu_generic.hip (Monte-Carlo launches with G.spectrum go to the -DQBP_SPECTRUM_TU builds, with G.n_budgets to the
+// -DQBP_BUDGETS_TU builds, others with G.thr_cols to the -DQBP_COLS_TU builds)
 hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G, int grid, int threads,
                           size_t lds, hipStream_t s);
 hipError_t launch_permute_prior(const double* prior, const int32_t* svar, double* out, int n, hipStream_t s);
@@ -69,6 +74,15 @@ hipError_t launch_osd_order(int words_per_row, unsigned grid, size_t lds, const 
 hipError_t launch_osd_big(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_osd_blocked(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                               const OsdBigWorkspace& Wk, hipStream_t s);
+// the same four with O.spectrum set (qbp_mc_run_spectrum): qbp_tu_osd.hip -DQBP_SPECTRUM_TU, kernels under names of
+// their own that also add the residual weight of every record to rows 1 / 3 of the table
+hipError_t launch_osd_small_spectrum(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, hipStream_t s);
+hipError_t launch_osd_order_spectrum(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, int method,
+                                     int order, hipStream_t s);
+hipError_t launch_osd_big_spectrum(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk,
+                                   hipStream_t s);
+hipError_t launch_osd_blocked_spectrum(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                       const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

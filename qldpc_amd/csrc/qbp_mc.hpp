@@ -20,10 +20,26 @@
 #define QBP_MC_BUDGETS 0
 #endif
 
+#ifndef QBP_MC_SPECTRUM
+// 1: the Monte-Carlo kernels also add every classified trial's residual weight to a table spectrum[4][n + 1] and
+// the iteration its syndrome was first satisfied in to iter_hist[max_iter + 1] (qbp_mc_run_spectrum).  Set,
+// together with QBP_MC_COLS, by the translation units compiled for that (-DQBP_SPECTRUM_TU), which give those
+// kernels names of their own: the other builds keep their code, registers, scratch and LDS.
+#define QBP_MC_SPECTRUM 0
+#endif
+
 namespace qbp {
 
 constexpr int NUM_COUNTERS = 12;
 constexpr int MAX_BUDGETS = 16;        // QBP_MC_MAX_BUDGETS of include/qbp.h
+constexpr int SPECTRUM_ROWS = 4;       // QBP_SPECTRUM_ROWS of include/qbp.h
+
+// Row of spectrum[SPECTRUM_ROWS][n + 1] a trial with a non-zero residual goes to (rework/main.py:96-110): by BP's
+// converged flag and by whether the residual is a logical operator -- never by whether OSD ran or was valid.
+__host__ __device__ inline int mc_spectrum_row(bool found, bool logical)
+{
+    return (logical ? 2 : 0) + (found ? 0 : 1);
+}
 
 __device__ __forceinline__ void philox4x32_10(unsigned c[4], unsigned k0, unsigned k1)
 {

@@ -16,6 +16,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qbp_mc.hpp"
+
+#ifndef QBP_OSD_SPECTRUM
+// 1: the kernels that classify also add the residual weight of every record to OsdParams::spectrum
+// (qbp_mc_run_spectrum).  Set by qbp_tu_osd.hip -DQBP_SPECTRUM_TU, which gives those kernels names of their own: the
+// other builds keep their code, registers and LDS.
+#define QBP_OSD_SPECTRUM 0
+#endif
+
 namespace qbp {
 
 struct OsdParams {
@@ -41,6 +50,10 @@ struct OsdParams {
     const unsigned long long* lx_cols;
     int half_distance;
     long long* counters;
+    // (last: QBP_OSD_SPECTRUM builds only) [SPECTRUM_ROWS][n + 1]: the weight w > 0 of a record's residual
+    // solution ^ error is counted at [3][w] when the residual is a logical operator, else at [1][w] -- every
+    // record here is a trial BP did not converge on (qbp_mc.hpp, mc_spectrum_row)
+    long long* spectrum;
 };
 
 // Sort key of |llr|: the IEEE bit pattern of a non-negative double is monotone as an unsigned
@@ -209,11 +222,17 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
             unsigned long long lm = 0ull;
             int ew = 0;
             unsigned df = 0;
+#if QBP_OSD_SPECTRUM
+            int rw = 0;                              // weight of the residual
+#endif
             for (int i = lane; i < n; i += 64) {
                 const unsigned e = err[i] & 1u;
                 const unsigned res = sol[i] ^ e;
                 ew += (int)e;
                 df |= res;
+#if QBP_OSD_SPECTRUM
+                rw += (int)res;
+#endif
                 if (res) lm ^= P.lx_cols[i];
             }
             unsigned bad = 0;                        // is_valid_osd: (detection @ H.T) % 2 == syndrome
@@ -227,12 +246,20 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
                 ew += __shfl_xor(ew, off);
                 df |= __shfl_xor(df, off);
                 bad |= __shfl_xor(bad, off);
+#if QBP_OSD_SPECTRUM
+                rw += __shfl_xor(rw, off);
+#endif
             }
             if (lane == 0) {
                 auto add = [&](int i) {
                     atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
                 };
                 const bool logical = lm != 0ull;
+#if QBP_OSD_SPECTRUM
+                if (rw)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(
+                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + rw), 1ull);
+#endif
                 if (!bad && !logical && df) add(5);
                 if (logical) {
                     add(1);
@@ -280,6 +307,9 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
     __shared__ unsigned long long s_piv[2];   // (two slots, by column parity: see the pivot search)
     __shared__ unsigned long long s_lm;
     __shared__ int s_ew, s_df, s_bad;
+#if QBP_OSD_SPECTRUM
+    __shared__ int s_rw;                      // weight of the residual
+#endif
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = P.m, n = P.n, W = P.W, NP = P.NP, RS = P.W + 1;
     unsigned long long* keys;
@@ -383,6 +413,9 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
             if (c >= 0 && (At[(size_t)W * m + r] & 1u)) sol[c] ^= 1u;   // distinct pivot columns: no race
         }
         if (tid == 0) { s_lm = 0ull; s_ew = 0; s_df = 0; s_bad = 0; }
+#if QBP_OSD_SPECTRUM
+        if (tid == 0) s_rw = 0;
+#endif
         __syncthreads();
         if (P.solution)
             for (int i = tid; i < n; i += nt) P.solution[rec * n + i] = sol[i];
@@ -391,13 +424,22 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
             unsigned long long lm = 0ull;
             int ew = 0;
             unsigned df = 0, bad = 0;
+#if QBP_OSD_SPECTRUM
+            int rw = 0;
+#endif
             for (int i = tid; i < n; i += nt) {
                 const unsigned e = err[i] & 1u;
                 const unsigned res = sol[i] ^ e;
                 ew += (int)e;
                 df |= res;
+#if QBP_OSD_SPECTRUM
+                rw += (int)res;
+#endif
                 if (res) lm ^= P.lx_cols[i];
             }
+#if QBP_OSD_SPECTRUM
+            if (rw) atomicAdd(&s_rw, rw);
+#endif
             for (int r = tid; r < m; r += nt) {
                 unsigned par = syn[r] & 1u;
                 for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
@@ -413,6 +455,11 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
                     atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
                 };
                 const bool logical = s_lm != 0ull;
+#if QBP_OSD_SPECTRUM
+                if (s_rw)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(
+                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + s_rw), 1ull);
+#endif
                 if (!s_bad && !logical && s_df) add(5);
                 if (logical) {
                     add(1);
@@ -475,6 +522,9 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
     __shared__ unsigned s_nact[2];
     __shared__ unsigned long long s_lm, s_item;
     __shared__ int s_ew, s_df, s_bad;
+#if QBP_OSD_SPECTRUM
+    __shared__ int s_rw;                      // weight of the residual
+#endif
     typedef unsigned long long u64;
     const int tid = threadIdx.x, nt = 1024;
     const int m = P.m, n = P.n, NP = P.NP;
@@ -747,6 +797,9 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
             if (pc[i] >= 0 && ((sb >> i) & 1u)) sol[pc[i]] ^= 1u;                     // distinct pivot columns
         }
         if (tid == 0) { s_lm = 0ull; s_ew = 0; s_df = 0; s_bad = 0; }
+#if QBP_OSD_SPECTRUM
+        if (tid == 0) s_rw = 0;
+#endif
         __syncthreads();
         if (P.solution)
             for (int i = tid; i < n; i += nt) P.solution[rec * n + i] = sol[i];
@@ -755,13 +808,22 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
             u64 lm = 0ull;
             int ew = 0;
             unsigned df = 0, bad = 0;
+#if QBP_OSD_SPECTRUM
+            int rw = 0;
+#endif
             for (int i = tid; i < n; i += nt) {
                 const unsigned e = err[i] & 1u;
                 const unsigned res = sol[i] ^ e;
                 ew += (int)e;
                 df |= res;
+#if QBP_OSD_SPECTRUM
+                rw += (int)res;
+#endif
                 if (res) lm ^= P.lx_cols[i];
             }
+#if QBP_OSD_SPECTRUM
+            if (rw) atomicAdd(&s_rw, rw);
+#endif
             for (int r = tid; r < m; r += nt) {
                 unsigned par = syn[r] & 1u;
                 for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
@@ -777,6 +839,11 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
                     atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
                 };
                 const bool logical = s_lm != 0ull;
+#if QBP_OSD_SPECTRUM
+                if (s_rw)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(
+                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + s_rw), 1ull);
+#endif
                 if (!s_bad && !logical && s_df) add(5);
                 if (logical) {
                     add(1);

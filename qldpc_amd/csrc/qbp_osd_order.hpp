@@ -288,11 +288,17 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
             unsigned long long lm = 0ull;
             int ew = 0;
             unsigned df = 0;
+#if QBP_OSD_SPECTRUM
+            int rw = 0;                              // weight of the residual
+#endif
             for (int i = lane; i < n; i += 64) {
                 const unsigned e = err[i] & 1u;
                 const unsigned res = sol[i] ^ e;
                 ew += (int)e;
                 df |= res;
+#if QBP_OSD_SPECTRUM
+                rw += (int)res;
+#endif
                 if (res) lm ^= P.lx_cols[i];
             }
             unsigned bad = 0;
@@ -306,12 +312,20 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
                 ew += __shfl_xor(ew, off);
                 df |= __shfl_xor(df, off);
                 bad |= __shfl_xor(bad, off);
+#if QBP_OSD_SPECTRUM
+                rw += __shfl_xor(rw, off);
+#endif
             }
             if (lane == 0) {
                 auto add = [&](int i) {
                     atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
                 };
                 const bool logical = lm != 0ull;
+#if QBP_OSD_SPECTRUM
+                if (rw)
+                    atomicAdd(reinterpret_cast<unsigned long long*>(
+                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + rw), 1ull);
+#endif
                 if (!bad && !logical && df) add(5);
                 if (logical) {
                     add(1);

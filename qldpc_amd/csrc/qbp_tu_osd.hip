@@ -1,10 +1,26 @@
 // libqbp.so, translation unit of the OSD kernels (qbp_osd.hpp: OSD-0, qbp_osd_order.hpp: order w) and the
 // histogram kernels (qbp_hist.hpp).
+// With -DQBP_SPECTRUM_TU: the four OSD kernels that classify once more, under other names, adding the residual weight
+// of every record to a table (qbp_mc_run_spectrum); no histogram kernels in that unit.
 #define QBP_DEFINE_KERNELS 1
+#ifdef QBP_SPECTRUM_TU
+#define QBP_OSD_SPECTRUM 1
+#undef QBP_OSD_TIMING
+#define osd0_kernel osd0_spectrum_kernel
+#define osd0_big_kernel osd0_big_spectrum_kernel
+#define osd0_blocked_kernel osd0_blocked_spectrum_kernel
+#define osd_order_kernel osd_order_spectrum_kernel
+#define launch_osd_small launch_osd_small_spectrum
+#define launch_osd_order launch_osd_order_spectrum
+#define launch_osd_big launch_osd_big_spectrum
+#define launch_osd_blocked launch_osd_blocked_spectrum
+#endif
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
+#ifndef QBP_SPECTRUM_TU
 #include "qbp_hist.hpp"
+#endif
 #include "qbp_launch.hpp"
 #include "qbp_osd.hpp"
 #include "qbp_osd_order.hpp"
@@ -98,6 +114,7 @@ extern "C" int qbp_debug_osd_timing(unsigned long long* out, int reset)
 }
 #endif
 
+#ifndef QBP_SPECTRUM_TU
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s)
 {
     hipLaunchKernelGGL(hist_minmax_kernel, dim3(grid), dim3(256), 0, s, x, count, part);
@@ -111,5 +128,6 @@ hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_
     hipLaunchKernelGGL(hist_bin_kernel, dim3(grid), dim3(256), lds, s, msg, errors, col_idx, B, E, n, edges, bins, hist);
     return hipGetLastError();
 }
+#endif  // !QBP_SPECTRUM_TU
 
 }  // namespace qbp

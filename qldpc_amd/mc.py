@@ -14,6 +14,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
     python -m qldpc_amd.mc --dem circuit.dem --trials 1000000 --osd      (detector error model: run_dem)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
+    python -m qldpc_amd.mc --code 144 --p 0.05 --osd --spectrum out.npz
+                                     (residual-weight spectra and the iteration histogram per point: run_spectrum)
 """
 from __future__ import annotations
 
@@ -252,6 +254,162 @@ def bp_per_iteration(code_names, p, budgets, trials, osd=True, **kwargs):
     return results
 
 
+def _split_spectrum(flat, n, max_iter):
+    """[points, 12 + 4 (n + 1) + max_iter + 1] -> (counters [points, 12], weights [points, 4, n + 1], iterations
+    [points, max_iter + 1]): the layout the spectrum runs reduce in one piece."""
+    flat = np.asarray(flat, np.int64)
+    a, b = NUM_COUNTERS, NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)
+    return (flat[:, :a].copy(), flat[:, a:b].reshape(len(flat), _lib.SPECTRUM_ROWS, n + 1).copy(),
+            flat[:, b:b + max_iter + 1].copy())
+
+
+def _spectrum_on_device(dec, L, distance, probs_list, priors, begin, end, *, draws, seed, max_iter, variant, alpha,
+                        damping, clip_llr, osd, flags, world, device):
+    """One rank's slice of every point on the device -- counters, weights and iterations of a point side by side in
+    one int64 row -- then the one all-reduce of the whole table."""
+    import torch
+    n = dec.n
+    dev = torch.device("cuda", device)
+    width = NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1) + max_iter + 1
+    d_all = torch.zeros((len(probs_list), width), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
+    for i, (probs, prior) in enumerate(zip(probs_list, priors)):
+        d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
+        base = d_all[i].data_ptr()
+        for a in range(begin, end, step):
+            dec.mc_run_spectrum_device(L, distance, probs, d_prior.data_ptr(), a, min(a + step, end), base,
+                                       base + 8 * NUM_COUNTERS,
+                                       base + 8 * (NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)), draws=draws,
+                                       seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                       clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(d_all)                       # counters and both tables: one collective
+    torch.cuda.synchronize(dev)
+    return d_all.cpu().numpy()
+
+
+def _check_spectrum_max_iter(max_iter):
+    if not 1 <= int(max_iter) <= _lib.MC_SPECTRUM_MAX_ITER:
+        raise ValueError(f"a spectrum run takes max_iter in [1, {_lib.MC_SPECTRUM_MAX_ITER}], got {max_iter}")
+    return int(max_iter)
+
+
+def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
+                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1, device=0,
+                 runner=None, all_reduce=None):
+    """``run_sweep`` with a distribution per point (qbp_mc_run_spectrum).  Returns GLOBAL ``(counters int64[points,
+    12], weights int64[points, 4, n + 1], iterations int64[points, max_iter + 1])``: the counters are ``run_sweep``'s
+    digit for digit; ``weights[i, r, w]`` counts the trials of point i whose residual has weight w > 0 in list r of
+    rework/main.py:65-112 (0 weights_found_BP, 1 weights_found_OSD, 2 weights_found_BP_error, 3
+    weights_found_OSD_error; spectrum.py's list is rows 0 + 1); ``iterations[i, k]`` counts the trials whose syndrome
+    was first satisfied in 0-based iteration k, ``iterations[i, max_iter]`` those BP did not converge on.  Sharded
+    like ``run_sweep``; counters and tables are reduced in ONE all-reduce.
+    ``runner(code, p, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])`` and ``all_reduce`` are
+    injection points for the CPU tests; by default the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
+    max_iter = _check_spectrum_max_iter(max_iter)
+    code = codes.load_code(code_name)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(code.Hx, device=device)
+        flat = _spectrum_on_device(dec, code.Lx, code.distance, [float(p) for p in ps],
+                                   [prior_of(p, code.n) for p in ps], begin, end, draws=draws, seed=seed,
+                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
+        return _split_spectrum(flat, code.n, max_iter)
+    flat = np.stack([np.concatenate([np.asarray(a, np.int64).ravel() for a in runner(code, p, begin, end)])
+                     for p in ps]) if len(ps) else np.zeros((0, 0), np.int64)
+    flat = all_reduce(flat) if all_reduce is not None else flat
+    return _split_spectrum(flat, code.n, max_iter)
+
+
+def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
+                     variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
+                     osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+    """``run_dem`` with the two distributions of ``run_spectrum``: GLOBAL ``(counters int64[1, 12], weights int64[1,
+    4, n + 1], iterations int64[1, max_iter + 1])`` -- one point, the model's own probabilities.  Arguments as
+    ``run_dem``; ``runner(H, L, probs, prior, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])``."""
+    flags = osd_run_flags(osd, osd_method, osd_order)
+    max_iter = _check_spectrum_max_iter(max_iter)
+    L = np.ascontiguousarray(L, np.uint8)
+    probs = np.ascontiguousarray(probs, np.float64)
+    n = H.shape[1]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if L.shape[0] > 64:
+        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
+    if probs.shape != (n,):
+        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
+    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        flat = _spectrum_on_device(dec, L, distance, [probs], [prior], begin, end, draws=draws, seed=seed,
+                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
+        return _split_spectrum(flat, n, max_iter)
+    flat = np.concatenate([np.asarray(a, np.int64).ravel() for a in runner(H, L, probs, prior, begin, end)])[None, :]
+    flat = all_reduce(flat) if all_reduce is not None else flat
+    return _split_spectrum(flat, n, max_iter)
+
+
+def stabilizer_spectrum(code_names, p=0.005, trials=20000, *, max_iter=50, osd=True, **kwargs):
+    """The experiment of spectrum.py:22-54: per code name the histogram int64[n + 1] of the weights of the residuals
+    ``detection ^ error`` that are non-zero but logically trivial (the stabilisers BP(50) + OSD-0 leaves behind at p =
+    0.005): rows 0 + 1 of ``run_spectrum``.  ``np.repeat(np.arange(n + 1), hist)`` is the script's ``weights_found``
+    list, sorted.  ``kwargs`` go to ``run_spectrum``."""
+    spectra = {}
+    for name in code_names:
+        _, weights, _ = run_spectrum(name, [p], trials, max_iter=max_iter, osd=osd, **kwargs)
+        spectra[name] = weights[0, 0] + weights[0, 1]
+    return spectra
+
+
+REWORK_WEIGHT_LISTS = ("weights_found_BP", "weights_found_OSD", "weights_found_BP_error", "weights_found_OSD_error")
+
+
+def rework_point(counters, weights, iterations):
+    """One ``results[name][p]`` entry of rework/main.py:119-129 from the three outputs of a spectrum run for that
+    point.  The four weight lists are expanded from the histograms with ``np.repeat``: the same multiset as the
+    reference's lists, in ascending order of weight and not in trial order."""
+    counters, weights, iterations = (np.asarray(a, np.int64) for a in (counters, weights, iterations))
+    t = max(int(counters[0]), 1)
+    max_iter = len(iterations) - 1
+    its = iterations.copy()
+    its[max_iter - 1] += its[max_iter]      # (an unconverged trial reports iteration index max_iter - 1)
+    point = {
+        "logical": int(counters[1]) / t,                                     # :114
+        "osd": int(counters[6]) / t,                                         # :115 (trials BP left unconverged)
+        "degeneracies": int(counters[5]) / t,                                # :116
+        "average_iterations": float(np.dot(np.arange(max_iter), its[:max_iter])) / t,   # :117
+        "OSD_invocation_AND_logicalError": int(counters[8]) / t,             # :118
+    }
+    for r, name in enumerate(REWORK_WEIGHT_LISTS):
+        point[name] = np.repeat(np.arange(weights.shape[1]), weights[r]).tolist()
+    return point
+
+
+def rework_results(experiment, trials=10000, *, max_iter=100, osd=True, osd_method="cs", osd_order=0, **kwargs):
+    """The ``results[name][p]`` dictionary of rework/main.py:50-129.  ``experiment``: that script's list of {"code",
+    "name", "physicalErrorRates"} dictionaries.  One ``run_spectrum`` per code (its own sampler, not numpy's stream;
+    OSD-0 by default, which is what the reference's ``performOSD_enhanced`` returns on every syndrome that comes from
+    an error).  The weight lists hold the reference's multisets in ascending order, not in trial order
+    (``rework_point``).  ``kwargs`` go to ``run_spectrum``."""
+    results = {}
+    for exp in experiment:
+        ps = list(exp["physicalErrorRates"])
+        cnt, weights, its = run_spectrum(exp["code"], ps, trials, max_iter=max_iter, osd=osd, osd_method=osd_method,
+                                         osd_order=osd_order, **kwargs)
+        results[exp["name"]] = {p: rework_point(cnt[i], weights[i], its[i]) for i, p in enumerate(ps)}
+    return results
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--code", default="[[288, 12, 18]]")
@@ -266,6 +424,9 @@ def main(argv=None):
     ap.add_argument("--budgets", type=int, nargs="+", default=None,
                     help="a ladder of iteration limits decoded in ONE pass instead of --max-iter (one --p): a result "
                          "line per limit (run_budgets / run_dem_budgets)")
+    ap.add_argument("--spectrum", default=None, metavar="OUT.npz",
+                    help="also collect the residual-weight spectra and the iteration histogram of every point "
+                         "(run_spectrum / run_dem_spectrum) and write counters, weights, iterations to this .npz")
     ap.add_argument("--draws", type=int, default=1, choices=(1, 2))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variant", choices=("sum-product", "damped", "min-sum"), default="sum-product")
@@ -294,6 +455,11 @@ def main(argv=None):
             ap.error(f"--budgets: {e}")
         if args.dem is None and len(args.p) != 1:
             ap.error("--budgets takes one --p")
+    if args.spectrum is not None:
+        if args.budgets is not None:
+            ap.error("--spectrum does not combine with --budgets")
+        if not 1 <= args.max_iter <= _lib.MC_SPECTRUM_MAX_ITER:
+            ap.error(f"--spectrum takes --max-iter in [1, {_lib.MC_SPECTRUM_MAX_ITER}]")
     dem_model = None
     if args.dem is not None:
         from . import dem
@@ -338,6 +504,18 @@ def main(argv=None):
             if dem_model is None:
                 return run_budgets(args.code, args.p[0], trials, points, rank=rank, world=world, **common)
             return run_dem_budgets(*dem_model, trials, points, distance=args.distance, rank=rank, world=world, **common)
+    elif args.spectrum is not None:
+        points = args.p if dem_model is None else [None]
+        tables = {}                      # weights and iterations of the last sweep (the timed one)
+
+        def sweep(trials, ps, rank, world):
+            if dem_model is None:
+                cnt, tables["weights"], tables["iterations"] = run_spectrum(args.code, ps, trials, rank=rank,
+                                                                            world=world, **common)
+            else:
+                cnt, tables["weights"], tables["iterations"] = run_dem_spectrum(
+                    *dem_model, trials, distance=args.distance, rank=rank, world=world, **common)
+            return cnt
     elif dem_model is None:
         points = args.p
 
@@ -388,6 +566,11 @@ def main(argv=None):
         else:
             print(f"{len(points)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
                   f"({len(points) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
+        if args.spectrum is not None:
+            np.savez(args.spectrum, counters=table, weights=tables["weights"], iterations=tables["iterations"],
+                     p=np.asarray([np.nan if p is None else p for p in points], np.float64))
+            print(f"spectra written to {args.spectrum}: weights {tables['weights'].shape}, "
+                  f"iterations {tables['iterations'].shape}")
         if args.out:
             with open(args.out, "w") as f:
                 model = {"code": args.code} if dem_model is None else {"dem": args.dem, "distance": args.distance}

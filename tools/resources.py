@@ -18,6 +18,11 @@ UNITS = [("qbp_tu_fused.hip", []), ("qbp_tu_generic.hip", ["-DQBP_GENERIC_MEM=0"
 # Monte-Carlo over a ladder of iteration budgets (qbp_mc_run_budgets): bp_fused_budgets_kernel, bp_generic_budgets_kernel
 UNITS += [("qbp_tu_fused.hip", ["-DQBP_BUDGETS_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_BUDGETS_TU", f"-DQBP_GENERIC_MEM={i}"])
                                                          for i in range(3)]
+# Monte-Carlo with residual-weight and iteration tables (qbp_mc_run_spectrum): bp_fused_spectrum_kernel,
+# bp_generic_spectrum_kernel, and the OSD kernels that add to the table (osd*_spectrum_kernel)
+UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SPECTRUM_TU"])] +
+          [("qbp_tu_generic.hip", ["-DQBP_SPECTRUM_TU", f"-DQBP_GENERIC_MEM={i}"]) for i in range(3)] +
+          [("qbp_tu_osd.hip", ["-DQBP_SPECTRUM_TU"])])
 
 
 def demangle(sym):
