@@ -371,6 +371,40 @@ int qbp_mc_run_errors_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int3
 int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,
                                int64_t trial_begin, int64_t T, uint8_t* errors);
 
+/*
+ * Decode T RECORDED shots of a detector error model to observable predictions: the loop of
+ * studies/studyComplete.py:91-109 (sampler.sample(shots, separate_observables=True); BP per shot;
+ * L_matrix @ prediction % 2 != actual_observables[i]) for data that comes from stim's circuit sampler or from an
+ * experiment -- detection events and, if known, the observable flips that really happened; no error pattern.
+ *   det_bits [T][ceil(m / 8)]: stim's b8 layout, detector c of shot t is bit c % 8 of byte t * ceil(m / 8) + c / 8;
+ *   rows are not padded to words (any alignment), padding bits are ignored.
+ *   actual [T] (may be null) and predictions [T] (may be null): bit l = observable l, 1 <= k <= 64; Lx [k][n] 0/1
+ *   bytes as in qbp_mc_run.  converged [T] (may be null).
+ * One shot: let (hard, conv, it, llr) be what qbp_decode_batch returns for its syndrome with the same prior, max_iter,
+ * variant, alpha, damping, clip_llr and the same column-sum and QBP_FLAG_FORCE_FULL bits.  x = hard if conv is set or
+ * no OSD flag is; otherwise x = the solution of qbp_osd_batch(OSD bits of flags) on (syndrome, llr, hard).
+ * predictions[t] = Lx x mod 2, converged[t] = conv.  Nothing but the shot's bit row is read and nothing but those
+ * nine bytes written per shot BP converges on: messages, posteriors and hard decisions stay on chip.
+ * counters (ADDED to, indices of qbp_mc_run):
+ *   [0] shots  [1] predictions[t] != actual[t]  [6] shots BP did not converge on  [7] sum of `it`
+ *   [8] the [1] shots among [6]  [10] shots handed to OSD whose x misses the syndrome (H x != s: a recorded
+ *   syndrome need not lie in the column space of H); all others stay 0; with actual == NULL [1] and [8] are untouched.
+ * Flags, OSD bits, the QBP_MC_OSD_MAX_TRIALS rule and QBP_E_UNSUPPORTED cases are those of qbp_mc_run.  Kernels of
+ * their own (bp_fused_shots_kernel, bp_generic_shots_kernel, osd*_shots_kernel); every matrix qbp_mc_run takes.
+ * QBP_E_INVALID, before any GPU work and with every output untouched: a null Lx, det_bits, prior or counters, k
+ * outside 1..64, T < 0, a NaN prior (host entry), and whatever qbp_mc_run refuses.  T = 0 succeeds and changes nothing.
+ */
+int qbp_decode_shots(qbp_handle* h, const uint8_t* Lx, int32_t k, const uint8_t* det_bits, const uint64_t* actual,
+                     int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
+                     double clip_llr, uint32_t flags, uint64_t* predictions, uint8_t* converged,
+                     int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form: Lx stays a host pointer (uploaded once per handle and cached), every other pointer is a device
+ * pointer (d_actual, d_predictions, d_converged may be null; d_counters ADDED to), enqueued on `stream`. */
+int qbp_decode_shots_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, const uint8_t* d_det_bits,
+                            const uint64_t* d_actual, int64_t T, const double* d_prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            uint64_t* d_predictions, uint8_t* d_converged, int64_t* d_counters, void* stream);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

@@ -87,6 +87,10 @@ SIGNATURES = {
     "qbp_mc_run_errors_spectrum": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int32,
                                              C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP,
                                              _VP]),
+    "qbp_decode_shots": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double,
+                                   C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP]),
+    "qbp_decode_shots_device": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int64, _VP, C.c_int32, C.c_int32,
+                                          C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP, _VP]),
     "qbp_mc_sample_errors_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
@@ -438,6 +442,57 @@ class Decoder:
                 part.ctypes.data, spectrum.ctypes.data, iter_hist.ctypes.data))
             total += part
         return total, spectrum, iter_hist
+
+    @_locked
+    def decode_shots(self, Lx, det_bits, prior, actual=None, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
+                     clip_llr=20.0, flags=0, counters=None):
+        """Decode recorded shots to observable predictions (qbp_decode_shots).  ``det_bits`` uint8[T, ceil(m / 8)]:
+        detection events in stim's b8 layout (``shots.pack_bits``); ``actual`` uint64[T] or None: the recorded
+        observables, bit l = observable l (``shots.masks_of``); ``Lx`` uint8[k, n], 1 <= k <= 64.  Returns
+        ``(counters int64[12], predictions uint64[T], converged bool[T])``; a given ``counters`` array is added to.
+        With FLAG_OSD0 a call keeps per-shot records: T is split by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        det = np.ascontiguousarray(det_bits, np.uint8)
+        rb = (self.m + 7) // 8
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        if det.ndim != 2 or det.shape[1] != rb:
+            raise ValueError(f"det_bits must have shape (T, {rb}) (bit-packed rows of {self.m} detectors), "
+                             f"got {det.shape}")
+        T = det.shape[0]
+        act = None
+        if actual is not None:
+            act = np.ascontiguousarray(actual, np.uint64)
+            if act.shape != (T,):
+                raise ValueError(f"actual must have shape ({T},), got {act.shape}")
+        if counters is None:
+            counters = np.zeros(NUM_COUNTERS, np.int64)
+        elif not (isinstance(counters, np.ndarray) and counters.dtype == np.int64 and
+                  counters.shape == (NUM_COUNTERS,) and counters.flags.c_contiguous):
+            raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
+        pred = np.zeros(T, np.uint64)
+        conv = np.zeros(T, np.uint8)
+        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(T, 1)
+        for a in range(0, T, step):
+            b = min(a + step, T)
+            _check(load().qbp_decode_shots(
+                self._h, Lx.ctypes.data, Lx.shape[0], det[a:b].ctypes.data, None if act is None else act[a:b].ctypes.data,
+                b - a, pr.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr),
+                int(flags), pred[a:b].ctypes.data, conv[a:b].ctypes.data, counters.ctypes.data))
+        return counters, pred, conv.astype(bool)
+
+    def decode_shots_device(self, Lx, d_det_bits, d_actual, T, d_prior, d_predictions, d_converged, d_counters,
+                            max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, stream=0):
+        """``decode_shots`` on device buffers (pointers as ints; d_actual, d_predictions, d_converged may be 0):
+        d_counters int64[12] is added to.  One call: with FLAG_OSD0 the caller splits by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_decode_shots_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], d_det_bits, d_actual or None, int(T), d_prior, int(max_iter),
+            int(variant), float(alpha), float(damping), float(clip_llr), int(flags), d_predictions or None,
+            d_converged or None, d_counters, stream or None))
 
     def mc_budgets_step(self, n_budgets):
         """Trials one qbp_mc_run_budgets call may cover with FLAG_OSD0: the records are kept per budget."""

@@ -194,6 +194,8 @@ struct qbp_handle {
     DevBuf<unsigned long long> d_fail_count;
     DevBuf<uint8_t> d_fail_syn, d_fail_hard, d_fail_err;
     DevBuf<double> d_fail_llr;
+    // qbp_decode_shots, host-pointer entry: recorded observables and predictions of the call
+    DevBuf<unsigned long long> d_shot_actual, d_shot_pred;
 };
 
 namespace {
@@ -681,6 +683,11 @@ struct McArgs {
     // qbp_mc_run_spectrum: the two tables (iter_hist may be null), else null
     long long* spectrum;
     long long* iter_hist;
+    // qbp_decode_shots: recorded detection events instead of a sampler, predictions out (BpCall::converged too)
+    const uint8_t* det_bits;
+    int det_row_bytes;
+    const unsigned long long* actual;
+    unsigned long long* predictions;
 };
 
 template <typename Params>
@@ -694,6 +701,7 @@ static void put_mc(Params& P, const McArgs& a)
     P.n_budgets = a.n_budgets;
     for (int j = 0; j < a.n_budgets; ++j) P.budgets[j] = a.budgets[j];
     P.spectrum = a.spectrum; P.iter_hist = a.iter_hist;
+    P.det_bits = a.det_bits; P.det_row_bytes = a.det_row_bytes; P.actual = a.actual; P.predictions = a.predictions;
 }
 
 // Per-call arguments of a BP launch, whichever kernel runs it (device pointers; outputs may be null).
@@ -790,8 +798,8 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     G.dump_R = c.dump; G.dump_iter = c.dump_iter; G.dump_div = c.dump_div;
     h->last_threads = g.threads; h->last_lds = (int)g.lds; h->last_grid = g.grid;
     if (c.mc) {
-        // Monte-Carlo mode: per-workgroup scratch for the sampled error
-        HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
+        // Monte-Carlo mode: per-workgroup scratch for the sampled error (none with recorded shots)
+        if (!c.mc->det_bits) HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
         put_mc(G, *c.mc);
         G.wsE = h->d_wsE.p;
         G.budget_tab_off = (int)(g.lds - budget_lds - spectrum_lds);
@@ -1052,7 +1060,10 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     if (mc || c.B > (long long)cfg.grid * cfg.S)
         HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
     const bool fast = (c.flags & QBP_FLAG_FAST_MATH) != 0;
-    if (mc && P.spectrum)               // residual-weight and iteration tables (qbp_mc_run_spectrum): builds of their own
+    if (mc && P.det_bits)               // recorded shots (qbp_decode_shots): builds of their own
+        HIP_TRY(fast ? qbp::launch_fused_shots_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused_shots(mc, c.variant, P, cfg, s));
+    else if (mc && P.spectrum)          // residual-weight and iteration tables (qbp_mc_run_spectrum): builds of their own
         HIP_TRY(fast ? qbp::launch_fused_spectrum_fast_math(mc, c.variant, P, cfg, s)
                      : qbp::launch_fused_spectrum(mc, c.variant, P, cfg, s));
     else if (mc && P.n_budgets)         // a ladder of iteration budgets (qbp_mc_run_budgets): builds of their own
@@ -1423,9 +1434,10 @@ static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long ma
     }
     Wk.At = h->d_osd_At.p; Wk.pivcol = h->d_osd_piv.p; Wk.posn = h->d_osd_posn.p; Wk.sol = h->d_osd_sol.p;
     Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
-    // (O.spectrum, here and in osd_launch: the builds that add residual weights to that table, qbp_mc_run_spectrum)
-    HIP_TRY((O.spectrum ? qbp::launch_osd_big_spectrum : qbp::launch_osd_big)((unsigned)grid, Wk.keys_in_lds ? NP * 12 : 0,
-                                                                            O, Wk, s));
+    // (O.spectrum, here and in osd_launch: the builds that add residual weights to that table, qbp_mc_run_spectrum;
+    // O.shots: the builds that predict recorded shots, qbp_decode_shots)
+    HIP_TRY((O.shots ? qbp::launch_osd_big_shots : O.spectrum ? qbp::launch_osd_big_spectrum : qbp::launch_osd_big)(
+        (unsigned)grid, Wk.keys_in_lds ? NP * 12 : 0, O, Wk, s));
     return QBP_OK;
 }
 
@@ -1509,17 +1521,20 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
         }
         Wk.At = h->d_osd_At.p; Wk.sol = h->d_osd_sol.p; Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
         const int rpt = m <= 1024 ? 1 : m <= 2048 ? 2 : m <= 4096 ? 4 : 8;
-        HIP_TRY((O.spectrum ? qbp::launch_osd_blocked_spectrum : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk, s));
+        HIP_TRY((O.shots ? qbp::launch_osd_blocked_shots : O.spectrum ? qbp::launch_osd_blocked_spectrum
+                                                                      : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk, s));
     } else if (method) {
         // order w (parse_osd_flags has checked osd_ok and the LDS)
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
         const size_t olds = (qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
-        HIP_TRY((O.spectrum ? qbp::launch_osd_order_spectrum : qbp::launch_osd_order)(h->osd_W + 1, (unsigned)grid, olds, O,
-                                                                                    method, order, s));
+        HIP_TRY((O.shots ? qbp::launch_osd_order_shots : O.spectrum ? qbp::launch_osd_order_spectrum
+                                                                    : qbp::launch_osd_order)(h->osd_W + 1, (unsigned)grid, olds, O,
+                                                                                             method, order, s));
     } else {
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
-        HIP_TRY((O.spectrum ? qbp::launch_osd_small_spectrum : qbp::launch_osd_small)(h->osd_W + 1, (unsigned)grid,
-                                                                                    (size_t)h->osd_lds, O, s));
+        HIP_TRY((O.shots ? qbp::launch_osd_small_shots : O.spectrum ? qbp::launch_osd_small_spectrum
+                                                                    : qbp::launch_osd_small)(h->osd_W + 1, (unsigned)grid,
+                                                                                             (size_t)h->osd_lds, O, s));
     }
     if (redo) {
         qbp::OsdParams R = O;
@@ -2020,6 +2035,156 @@ try {
     HIP_TRY(qbp::launch_mc_sample_cols(h->d_hard.p, h->n, T, trial_begin, draws, seed, h->d_mc_thr.p, s));
     HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// ---- recorded shots (include/qbp.h: qbp_decode_shots) -----------------------------------------------------------
+
+// Everything qbp_decode_shots refuses, host only and before any GPU work.  `host_prior`: the priors when they are a
+// host array (NaN check), else null.
+static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const uint8_t* det_bits, int64_t T,
+                            const double* prior, const double* host_prior, int32_t max_iter, int32_t variant,
+                            uint32_t flags, const int64_t* counters, int* osd_method, int* osd_order)
+{
+    int rc = check_decode_args(h, T, max_iter, variant);
+    if (rc) return rc;
+    if (!Lx || !det_bits || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k = %d observables (need 1..64)", k);
+    if (host_prior)
+        for (int v = 0; v < h->n; ++v)
+            if (host_prior[v] != host_prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    rc = parse_osd_flags(h, flags, true, osd_method, osd_order);
+    if (rc) return rc;
+    if (flags & QBP_FLAG_OSD0) {
+        // per-shot records of the shots BP leaves unconverged, as qbp_mc_run's (without the error row)
+        const size_t t = (size_t)T, m = h->m, n = h->n;
+        if (t > QBP_MC_OSD_MAX_TRIALS || t * (m + 10 * n) > ((size_t)16 << 30))
+            return fail(QBP_E_INVALID, "with QBP_FLAG_OSD0 a call covers at most %lld shots of this matrix (got %lld); "
+                                       "split the range",
+                        (long long)std::min<size_t>(QBP_MC_OSD_MAX_TRIALS, ((size_t)16 << 30) / (m + 10 * n)), (long long)T);
+    }
+    return QBP_OK;
+}
+
+// All pointers but Lx_host are device pointers; arguments already checked.
+static int decode_shots_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, const uint8_t* d_det_bits,
+                             const uint64_t* d_actual, int64_t T, const double* d_prior, int32_t max_iter,
+                             int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                             int osd_method, int osd_order, uint64_t* d_predictions, uint8_t* d_converged,
+                             int64_t* d_counters, hipStream_t s)
+{
+    flags &= ~(OSD_ORDER_BITS | OSD_METHOD_BITS);
+    BpCall c;
+    int rc = resolve_column_order(h, flags, nullptr, &c.col_mode);      // the column-sum bits of qbp_decode_batch
+    if (rc) return rc;
+    rc = mc_prepare(h, Lx_host, k, s);
+    if (rc) return rc;
+    const bool osd = (flags & QBP_FLAG_OSD0) != 0;
+    const size_t t = (size_t)T, m = h->m, n = h->n;
+    if (osd) {
+        HIP_TRY(h->d_fail_count.reserve(1));
+        HIP_TRY(h->d_fail_list.reserve(t));
+        HIP_TRY(h->d_fail_syn.reserve(t * m));
+        HIP_TRY(h->d_fail_llr.reserve(t * n));
+        HIP_TRY(h->d_fail_hard.reserve(t * n));
+        HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, sizeof(unsigned long long), s));
+    }
+    McArgs mc{};
+    mc.lx_cols = h->d_lx_cols.p;
+    mc.counters = reinterpret_cast<long long*>(d_counters);
+    mc.det_bits = d_det_bits; mc.det_row_bytes = (h->m + 7) / 8;
+    mc.actual = reinterpret_cast<const unsigned long long*>(d_actual);
+    mc.predictions = reinterpret_cast<unsigned long long*>(d_predictions);
+    if (osd) {
+        mc.fail_list = h->d_fail_list.p; mc.fail_count = h->d_fail_count.p;
+        mc.fail_syn = h->d_fail_syn.p; mc.fail_llr = h->d_fail_llr.p; mc.fail_hard = h->d_fail_hard.p;
+    }
+    c.prior = d_prior; c.B = T; c.max_iter = max_iter; c.variant = variant;
+    c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
+    c.converged = d_converged;
+    c.mc = &mc;
+    // (two column orders in one launch: the general-H kernel only, as in bp_kernel)
+    if (bp_kernel(h, T, flags, c.col_mode, true) == 2 || c.col_mode == 2) {
+        h->last_kernel = 2;
+        rc = generic_launch(h, c, s);
+    } else {
+        rc = fused_launch(h, c, s);
+        if (rc == QBP_OK) h->last_kernel = 1;
+    }
+    if (rc || !osd) return rc;
+    // second kernel: OSD on the shots BP left unconverged (their number is read on the device), predicting them;
+    // recorded syndromes may lie outside the column space of H: with the redo pass of qbp_osd_batch
+    qbp::OsdParams O{};
+    O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p);
+    O.list = h->d_fail_list.p;
+    O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
+    O.lx_cols = h->d_lx_cols.p;
+    O.counters = reinterpret_cast<long long*>(d_counters);
+    O.shots = 1; O.actual = mc.actual; O.predictions = mc.predictions;
+    return osd_launch(h, O, T, s, true, osd_method, osd_order);
+}
+
+int qbp_decode_shots_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, const uint8_t* d_det_bits,
+                            const uint64_t* d_actual, int64_t T, const double* d_prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            uint64_t* d_predictions, uint8_t* d_converged, int64_t* d_counters, void* stream)
+try {
+    int osd_method = 0, osd_order = 0;
+    const int rc = check_shots_args(h, Lx_host, k, d_det_bits, T, d_prior, nullptr, max_iter, variant, flags,
+                                    d_counters, &osd_method, &osd_order);
+    if (rc) return rc;
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    return decode_shots_impl(h, Lx_host, k, d_det_bits, d_actual, T, d_prior, max_iter, variant, alpha, damping,
+                             clip_llr, flags, osd_method, osd_order, d_predictions, d_converged, d_counters,
+                             static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_decode_shots(qbp_handle* h, const uint8_t* Lx, int32_t k, const uint8_t* det_bits, const uint64_t* actual,
+                     int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
+                     double clip_llr, uint32_t flags, uint64_t* predictions, uint8_t* converged,
+                     int64_t counters[QBP_NUM_COUNTERS])
+try {
+    int osd_method = 0, osd_order = 0;
+    int rc = check_shots_args(h, Lx, k, det_bits, T, prior, prior, max_iter, variant, flags, counters, &osd_method,
+                              &osd_order);
+    if (rc) return rc;
+    if (T == 0) return QBP_OK;
+    if (flags & QBP_FLAG_DENSE_F_COLSUM_ITER0) {     // (the shortcut is judged on the host copy of the priors)
+        int mode = 0;
+        unsigned fl = flags;
+        rc = resolve_column_order(h, fl, prior, &mode);
+        if (rc) return rc;
+        if (mode == 0) flags = fl;
+    }
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t n = h->n, t = (size_t)T, rb = ((size_t)h->m + 7) / 8;
+    hipStream_t s = h->stream;
+    HIP_TRY(h->d_syn.reserve(t * rb));
+    HIP_TRY(h->d_prior.reserve(n));
+    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
+    if (actual) HIP_TRY(h->d_shot_actual.reserve(t));
+    if (predictions) HIP_TRY(h->d_shot_pred.reserve(t));
+    if (converged) HIP_TRY(h->d_conv.reserve(t));
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, det_bits, t * rb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    if (actual) HIP_TRY(hipMemcpyAsync(h->d_shot_actual.p, actual, t * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
+    rc = decode_shots_impl(h, Lx, k, h->d_syn.p, actual ? reinterpret_cast<const uint64_t*>(h->d_shot_actual.p) : nullptr,
+                           T, h->d_prior.p, max_iter, variant, alpha, damping, clip_llr, flags, osd_method, osd_order,
+                           predictions ? reinterpret_cast<uint64_t*>(h->d_shot_pred.p) : nullptr,
+                           converged ? h->d_conv.p : nullptr, reinterpret_cast<int64_t*>(h->d_counters.p), s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    long long tmp[qbp::NUM_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
+    if (predictions) HIP_TRY(hipMemcpyAsync(predictions, h->d_shot_pred.p, t * 8, hipMemcpyDeviceToHost, s));
+    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, t, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
     return QBP_OK;
 }
 QBP_ABI_CATCH

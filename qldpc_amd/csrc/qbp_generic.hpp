@@ -143,6 +143,13 @@ struct GenericParams {
     long long* spectrum;
     long long* iter_hist;
     int spectrum_off;
+    // QBP_MC_SHOTS builds (qbp_decode_shots; as the on-chip kernel, qbp_kernels.hpp): det_bits [B][det_row_bytes] read
+    // in place of a sampled error, actual [B] (may be null) compared with, predictions [B] (may be null) and
+    // `converged` above (may be null) written.
+    const uint8_t* det_bits;
+    int det_row_bytes;
+    const unsigned long long* actual;
+    unsigned long long* predictions;
 };
 
 // Dynamic LDS of one workgroup: messages (LDSMSG) + syndrome bits + two parity buffers + counters
@@ -273,6 +280,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
     constexpr bool LDSMSG = MEM == GENERIC_MEM_LDS;
     constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;     // checkpoints at a ladder of budgets (qbp_mc_run_budgets)
     constexpr bool SPECTRUM = MC && QBP_MC_SPECTRUM != 0;   // residual-weight / iteration tables (qbp_mc_run_spectrum)
+    constexpr bool SHOTS = MC && QBP_MC_SHOTS != 0;         // recorded shots in, observable predictions out (qbp_decode_shots)
     extern __shared__ __attribute__((aligned(16))) double gsm_all[];
     constexpr NpT np_tab = 0u;          // = the LDS address of gsm_all (no static LDS in this kernel: checked below)
     double* const gsm = gsm_all + NP_LDS_DOUBLES;
@@ -356,7 +364,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
     const bool pairwise = (P.flags & 4u) != 0;
     const double one_minus_damping = 1.0 - P.damping;
     const int n4 = (n + 3) / 4;
-    uint8_t* const err = MC ? P.wsE + (size_t)blockIdx.x * n4 * 4 : nullptr;
+    uint8_t* const err = MC && !SHOTS ? P.wsE + (size_t)blockIdx.x * n4 * 4 : nullptr;
     if constexpr (MC) {
         if (tid == 0) {
             *mc_lmask = 0ull; *mc_weight = 0; *mc_diff = 0;
@@ -413,7 +421,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             if constexpr (EARLY_FETCH)
                 if (dynamic) fetched = atomicAdd(reinterpret_cast<unsigned*>(P.work_counter), 1u);
         }
-        if constexpr (MC) {
+        if constexpr (MC && !SHOTS) {
             // errors of trial trial_begin + b: one Philox evaluation per four qubits
             // (beliefPropagationGPU.py:195)
             for (int g = tid; g < n4; g += nt)
@@ -437,7 +445,9 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                 const int w = w0 + lane;
                 unsigned bit = 0;
                 if (w < m) {
-                    if constexpr (MC) {                             // syndrome = H e mod 2 (:198)
+                    if constexpr (SHOTS) {                          // the shot's recorded detection event
+                        bit = mc_shot_bit(P.det_bits, b, P.det_row_bytes, P.srow[w]);
+                    } else if constexpr (MC) {                      // syndrome = H e mod 2 (:198)
                         const int e0 = P.srow_e0[w], deg = P.srow_deg[w];
                         for (int j = 0; j < deg; ++j) bit ^= err[P.col_idx[e0 + j]];
                         bit &= 1u;
@@ -523,7 +533,14 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                 }
                 const int v = P.svar[x];
                 const unsigned hd = val < 0.0 ? 1u : 0u;
-                if constexpr (MC) {
+                if constexpr (SHOTS) {
+                    if (to_osd) {
+                        P.fail_llr[rec * n + v] = val;
+                        P.fail_hard[rec * n + v] = (uint8_t)hd;
+                    } else if (hd) {
+                        lm ^= P.lx_cols[v];                  // prediction = Lx x mod 2 (this thread's share)
+                    }
+                } else if constexpr (MC) {
                     const unsigned e = err[v];
                     if (to_osd) {
                         P.fail_llr[rec * n + v] = val;
@@ -551,6 +568,8 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                         else
                             P.fail_list[atomicAdd(P.fail_count, 1ull)] = b;
                         cnt_row[0] += 1; cnt_row[6] += 1; cnt_row[7] += it_done;   // BP bookkeeping only
+                        if constexpr (SHOTS)
+                            if (P.converged) P.converged[b] = 0;
                         if constexpr (SPECTRUM) it_hist[P.max_iter] += 1;          // (its weight: the OSD kernel's)
                     }
                 } else {
@@ -561,6 +580,19 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                         if (rw) atomicAdd(mc_resw, rw);
                     }
                     __syncthreads();
+                    if constexpr (SHOTS) {
+                        if (tid == 0) {
+                            const unsigned long long pred = *mc_lmask;
+                            *mc_lmask = 0ull;
+                            mc_count_shot(cnt_row, conv, it_done);
+                            if (P.converged) P.converged[b] = (uint8_t)conv;
+                            if (P.predictions) P.predictions[b] = pred;
+                            if (P.actual && P.actual[b] != pred) {
+                                cnt_row[1] += 1;
+                                if (!conv) cnt_row[8] += 1;
+                            }
+                        }
+                    } else
                     if (tid == 0) {
                         if constexpr (SPECTRUM) {
                             it_hist[conv ? it_done : P.max_iter] += 1;

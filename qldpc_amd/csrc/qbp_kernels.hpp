@@ -127,6 +127,13 @@ struct FusedParams {
     // syndrome was first satisfied in (bin max_iter: never); both atomically added to
     long long* spectrum;
     long long* iter_hist;
+    // QBP_MC_SHOTS builds (qbp_decode_shots): det_bits [B][det_row_bytes], the recorded detection events bit-packed
+    // (mc_shot_bit); actual [B] (may be null), the recorded observables, bit l = observable l; predictions [B] (may be
+    // null), Lx x of the decoder's output x in the same encoding.  `converged` above (may be null) is written too.
+    const uint8_t* det_bits;
+    int det_row_bytes;
+    const unsigned long long* actual;
+    unsigned long long* predictions;
 };
 
 // Rarely used launch parameters (output pointers, Monte-Carlo settings, ...) are re-read from the
@@ -202,6 +209,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     // memory with a 64-bit atomic), every trial's iteration index to the workgroup's histogram in LDS (one LDS atomic
     // per trial by its slot leader; one global atomic per non-zero bin when the workgroup ends).
     constexpr bool SPECTRUM = MC && QBP_MC_SPECTRUM != 0;
+    // SHOTS (qbp_decode_shots; the -DQBP_SHOTS_TU builds only): a trial is a recorded shot.  Its check lanes read their
+    // syndrome bits from the shot's bit row (no sampler, hence no error bytes in LDS and no barrier B0); the emission
+    // forms the parity of lx_cols over the support of the hard decision -- the observable prediction -- which the slot
+    // leader stores, with the converged flag, and compares with the recorded observables.
+    constexpr bool SHOTS = MC && QBP_MC_SHOTS != 0;
     // dynamic LDS: the tables of the two elementary functions (qbp_math.hpp, NpImage) first -- a constant
     // address, so that a table access is a row offset plus an immediate -- then the carve described above
     extern __shared__ __attribute__((aligned(16))) double smem_all[];
@@ -398,7 +410,9 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         if constexpr (BUDGETS) { bj = 0; ck_it = COLD(budgets)[0] - 1; }
 #pragma unroll
         for (int j = 0; j < DC; ++j) Q[j] = pri_lds[j * m + c];   // Q = where(mask, initialBelief, 0)
-        if constexpr (MC) {
+        if constexpr (SHOTS) {
+            sbit = mc_shot_bit(COLD(det_bits), b, COLD(det_row_bytes), c);
+        } else if constexpr (MC) {
             ebits = 0;
             const unsigned char* const err_lds = err_buf();
 #pragma unroll
@@ -444,6 +458,28 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         }
     };
 
+    // SHOTS: the pending emission by the slot leader: bookkeeping counters, the converged flag, and -- unless the shot
+    // is left to OSD, whose kernel does the same for its records -- the prediction and its compare with the record
+    // (the shot of a pending emission -- the slot may be on its next one by then -- waits in the slot's words of
+    // mc_weight / mc_diff, its iteration and converged flag in the slot's word of the third flag buffer, none of which
+    // these builds use otherwise: written and read by the leader alone, and three registers fewer across the loop)
+    auto shots_pending = [&]() {
+        const ColdArgs ca = cold_args();
+        const int mc_pending_conv = flag0[2 * S + slot] & 1, mc_pending_it = flag0[2 * S + slot] >> 1;
+        const long long mc_pending_b = (long long)(((unsigned long long)(unsigned)mc_diff[slot] << 32) |
+                                                   (unsigned)mc_weight[slot]);
+        mc_count_shot(mc_count, mc_pending_conv, mc_pending_it);
+        if (ca->converged) ca->converged[mc_pending_b] = (uint8_t)mc_pending_conv;
+        if (ca->fail_list != nullptr && !mc_pending_conv) return;
+        const unsigned long long pred = mc_lmask[slot];
+        mc_lmask[slot] = 0ull;
+        if (ca->predictions) ca->predictions[mc_pending_b] = pred;
+        if (ca->actual && ca->actual[mc_pending_b] != pred) {
+            mc_count[1] += 1;
+            if (!mc_pending_conv) mc_count[8] += 1;
+        }
+    };
+
     double val_keep[DC];          // ONE_BAR: posterior values of the lane's edges, alive until the next phase
     // decode-mode emission of the values in val[] (one read of the output pointers per emission --
     // adjacent kernel arguments: a single scalar load -- not one per use)
@@ -482,7 +518,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         double* const Rw = ONE_BAR ? Rs + PAR * (FUSED_R2_OFF_BYTES / 8) : Rs;     // this phase's copy of R
         double val_phase[DC];     // (two-barrier builds: the values do not outlive the phase)
         double (&val)[DC] = ONE_BAR ? val_keep : val_phase;
-        if constexpr (MC) {
+        if constexpr (MC && !SHOTS) {
             // Sample the errors of a trial that starts in this phase: one Philox evaluation per
             // four qubits, by the first ceil(n/4) lanes of the slot; the extra barrier (Monte-Carlo
             // builds only) orders the bytes before the check lanes gather them.
@@ -612,10 +648,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             }
             if constexpr (MC) {
                 if (mc_pending) {
+                    if constexpr (SHOTS) {
+                        shots_pending();
+                    } else {
                     if constexpr (SPECTRUM) spectrum_pending();
                     mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                                 mc_pending_it, COLD(half_distance),
                                 COLD(fail_list) != nullptr && !mc_pending_conv);
+                    }
                     mc_pending = false;
                 }
             }
@@ -652,22 +692,34 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                                 const long long o = row + var_lds[j * m + c];
                                 f_llr[o] = val[j];
                                 f_hard[o] = (uint8_t)(val[j] < 0.0);
-                                f_err[o] = (uint8_t)((ebits >> j) & 1u);
+                                if constexpr (!SHOTS) f_err[o] = (uint8_t)((ebits >> j) & 1u);
                             }
                         }
-                        const unsigned char* const err_lds = err_buf();
+                        const unsigned char* const err_lds = SHOTS ? nullptr : err_buf();
                         for (int i = c; i < n_iso; i += m) {
                             const int v = COLD(iso_vars)[i];
                             const double pv = COLD(prior)[v];
                             f_llr[row + v] = pv;
                             f_hard[row + v] = (uint8_t)(pv < 0.0);
-                            f_err[row + v] = err_lds[v];
+                            if constexpr (!SHOTS) f_err[row + v] = err_lds[v];
                         }
                         if constexpr (BUDGETS) {         // list bj, of the records of plane bj
                             if (c == 0) ca->fail_list[bj * ca->B + (long long)atomicAdd(ca->fail_count + bj, 1ull)] = b;
                         } else {
                             if (c == 0) ca->fail_list[atomicAdd(ca->fail_count, 1ull)] = b;
                         }
+                    } else if constexpr (SHOTS) {
+                        // prediction = Lx x mod 2 over the support of the hard decision x (this lane's share)
+                        unsigned long long lm = 0ull;
+                        const unsigned long long* const lx = ca->lx_cols;
+#pragma unroll
+                        for (int j = 0; j < DC; ++j)
+                            if (((wmask >> j) & 1u) && val[j] < 0.0) lm ^= lx[var_lds[j * m + c]];
+                        for (int i = c; i < n_iso; i += m) {
+                            const int v = COLD(iso_vars)[i];
+                            if (COLD(prior)[v] < 0.0) lm ^= lx[v];
+                        }
+                        if (lm) atomicXor(&mc_lmask[slot], lm);
                     } else {
                     unsigned long long lm = 0ull;
                     int ew = 0;
@@ -704,8 +756,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     if (df) atomicOr(&mc_diff[slot], 1);
                     }
                     if (c == 0) {
-                        mc_pending = true; mc_pending_conv = conv; mc_pending_it = it;
+                        mc_pending = true;
+                        if constexpr (!SHOTS) { mc_pending_conv = conv; mc_pending_it = it; }
                         if constexpr (BUDGETS) mc_pending_row = bj;
+                        if constexpr (SHOTS) {
+                            flag0[2 * S + slot] = (it << 1) | (conv ? 1 : 0);
+                            mc_weight[slot] = (int)(unsigned)b;
+                            mc_diff[slot] = (int)(unsigned)((unsigned long long)b >> 32);
+                        }
                     }
                 } else {
                     emit_decode(val, conv, it);
@@ -760,10 +818,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             // the last emitted trial of this slot may still be pending (emitted after B2 of the
             // final phase; everybody passed B1 since, so the accumulators are complete)
             if (mc_pending) {
+                if constexpr (SHOTS) {
+                    shots_pending();
+                } else {
                 if constexpr (SPECTRUM) spectrum_pending();
                 mc_classify(mc_lmask, mc_weight, mc_diff, pending_row(), slot, mc_pending_conv,
                             mc_pending_it, COLD(half_distance),
                             COLD(fail_list) != nullptr && !mc_pending_conv);
+                }
             }
             if constexpr (!BUDGETS) {
                 for (int i = 0; i < NUM_COUNTERS; ++i)

@@ -50,13 +50,18 @@ hipError_t launch_fused_budgets_fast_math(bool mc, int variant, const FusedParam
 hipError_t launch_fused_spectrum(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
 hipError_t launch_fused_spectrum_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
                                            hipStream_t s);
+// the same again, decoding recorded shots (P.det_bits; qbp_decode_shots): -DQBP_SHOTS_TU
+hipError_t launch_fused_shots(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
+hipError_t launch_fused_shots_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
+                                        hipStream_t s);
 hipError_t launch_debug_math(int kind, const double* x, double* y, long long count, hipStream_t s);
 hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                             unsigned long long seed, unsigned threshold, hipStream_t s);
 // thr: [n rounded up to 4] thresholds, one per qubit (qbp_mc.hpp, mc_error_quad_cols)
 hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                                  unsigned long long seed, const uint32_t* thr, hipStream_t s);
-// qbp_tu_generic.hip (Monte-Carlo launches with G.spectrum go to the -DQBP_SPECTRUM_TU builds, with G.n_budgets to the
+// qbp_tu_generic.hip (Monte-Carlo launches with G.det_bits go to the -DQBP_SHOTS_TU builds, with G.spectrum to the
+// -DQBP_SPECTRUM_TU builds, with G.n_budgets to the
 // -DQBP_BUDGETS_TU builds, others with G.thr_cols to the -DQBP_COLS_TU builds)
 hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G, int grid, int threads,
                           size_t lds, hipStream_t s);
@@ -83,6 +88,14 @@ hipError_t launch_osd_big_spectrum(unsigned grid, size_t lds, const OsdParams& O
                                    hipStream_t s);
 hipError_t launch_osd_blocked_spectrum(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                                        const OsdBigWorkspace& Wk, hipStream_t s);
+// the same four with O.shots set (qbp_decode_shots): qbp_tu_osd.hip -DQBP_SHOTS_TU, kernels under names of their own
+// that store and check the observable prediction of every record
+hipError_t launch_osd_small_shots(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, hipStream_t s);
+hipError_t launch_osd_order_shots(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, int method,
+                                  int order, hipStream_t s);
+hipError_t launch_osd_big_shots(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s);
+hipError_t launch_osd_blocked_shots(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                    const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

@@ -28,6 +28,15 @@
 #define QBP_MC_SPECTRUM 0
 #endif
 
+#ifndef QBP_MC_SHOTS
+// 1: the Monte-Carlo kernels decode RECORDED shots (qbp_decode_shots): a trial's syndrome is read from a bit-packed
+// row of detection events instead of being sampled, and what is emitted is the observable prediction Lx x of the
+// decoder's output x, compared with the shot's recorded observables where those are given -- no error pattern, no
+// residual.  Set by the translation units compiled for that (-DQBP_SHOTS_TU), which give those kernels names of their
+// own: the other builds keep their code, registers, scratch and LDS.
+#define QBP_MC_SHOTS 0
+#endif
+
 namespace qbp {
 
 constexpr int NUM_COUNTERS = 12;
@@ -96,6 +105,21 @@ __device__ __forceinline__ unsigned mc_stored_quad(const uint8_t* errors, int g,
     for (int i = 0; i < 4; ++i)
         if (4 * g + i < n) bytes |= (unsigned)(errors[4 * g + i] & 1u) << (8 * i);
     return bytes;
+}
+
+// Detector c of shot t in stim's b8 layout: bit c % 8 of byte t * row_bytes + c / 8, row_bytes = ceil(m / 8).  Rows
+// are not padded to words (m = 36: five bytes), so this is a byte load whatever the address.
+__device__ __forceinline__ unsigned mc_shot_bit(const uint8_t* det_bits, long long t, int row_bytes, int c)
+{
+    return ((unsigned)det_bits[t * row_bytes + (c >> 3)] >> (c & 7)) & 1u;
+}
+
+// BP bookkeeping of one recorded shot into a counter row (qbp_decode_shots): shots, unconverged shots, iterations.
+__device__ __forceinline__ void mc_count_shot(int* cnt, int conv, int it)
+{
+    cnt[0] += 1;
+    if (!conv) cnt[6] += 1;
+    cnt[7] += it;
 }
 
 // Classification of one finished trial (paperResults_GPU.py:127-144 without the OSD call) into a

@@ -25,6 +25,14 @@
 #define QBP_OSD_SPECTRUM 0
 #endif
 
+#ifndef QBP_OSD_SHOTS
+// 1: the kernels' records are recorded shots (qbp_decode_shots): instead of classifying a residual they form the
+// observable prediction Lx x of their solution x, store it and compare it with the shot's recorded observables.
+// Set by qbp_tu_osd.hip -DQBP_SHOTS_TU, which gives those kernels names of their own: the other builds keep their code,
+// registers and LDS.
+#define QBP_OSD_SHOTS 0
+#endif
+
 namespace qbp {
 
 struct OsdParams {
@@ -54,6 +62,12 @@ struct OsdParams {
     // solution ^ error is counted at [3][w] when the residual is a logical operator, else at [1][w] -- every
     // record here is a trial BP did not converge on (qbp_mc.hpp, mc_spectrum_row)
     long long* spectrum;
+    // (last: QBP_OSD_SHOTS builds only; shots != 0 selects them) record `rec` is shot `rec` of the call: actual [*] (may
+    // be null) the recorded observables, predictions [*] (may be null) written.  A record a fast kernel lists in redo is
+    // left to the kernel that recomputes it: every shot is predicted and counted once.
+    int shots;
+    const unsigned long long* actual;
+    unsigned long long* predictions;
 };
 
 // Sort key of |llr|: the IEEE bit pattern of a non-negative double is monotone as an unsigned
@@ -96,6 +110,17 @@ __device__ __forceinline__ void osd_flag_inconsistent(const OsdParams& P, long l
         const unsigned long long at = atomicAdd(reinterpret_cast<unsigned long long*>(P.redo), 1ull);
         P.redo[1 + at] = rec;
     }
+}
+
+// QBP_OSD_SHOTS builds: the result of one record by one thread -- lm = XOR of lx_cols over the support of the solution,
+// bad = the solution misses the syndrome (counter [10]: with recorded data a syndrome need not lie in the column space
+// of H).  Every record is a shot BP did not converge on: a wrong prediction counts in [1] and [8].
+__device__ __forceinline__ void osd_shot_result(const OsdParams& P, long long rec, unsigned long long lm, bool bad)
+{
+    auto add = [&](int i) { atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull); };
+    if (P.predictions) P.predictions[rec] = lm;
+    if (P.actual && P.actual[rec] != lm) { add(1); add(8); }
+    if (bad) add(10);
 }
 
 template <int WW>
@@ -206,7 +231,12 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
             if (lane == 0) pivcol[p] = c;
             __syncthreads();
         }
+#if QBP_OSD_SHOTS
+        const bool shot_redo = P.redo != nullptr && __ballot((sb & ~used) != 0u) != 0ull;
+        if (shot_redo && lane == 0) osd_flag_inconsistent(P, rec);
+#else
         if (__ballot((sb & ~used) != 0u) && lane == 0) osd_flag_inconsistent(P, rec);
+#endif
         // ---- 4. e[pivot column] = reduced syndrome bit; solution = hard + e    OSD.py:14-26
         for (int r = lane; r < m; r += 64) {
             const int c = pivcol[r];
@@ -216,6 +246,24 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
         if (P.solution)
             for (int i = lane; i < n; i += 64) P.solution[rec * n + i] = sol[i];
 
+#if QBP_OSD_SHOTS
+        if (!shot_redo) {
+            unsigned long long lm = 0ull;
+            for (int i = lane; i < n; i += 64)
+                if (sol[i]) lm ^= P.lx_cols[i];
+            unsigned bad = 0;
+            for (int r = lane; r < m; r += 64) {
+                unsigned par = syn[r] & 1u;
+                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
+                bad |= par;
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                lm ^= __shfl_xor(lm, off);
+                bad |= __shfl_xor(bad, off);
+            }
+            if (lane == 0) osd_shot_result(P, rec, lm, bad != 0u);
+        }
+#else
         if (P.errors) {
             // classification of the OSD output (paperResults_GPU.py:127-144)
             const uint8_t* err = P.errors + rec * n;
@@ -270,6 +318,7 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
                 if (bad) add(10);                    // OSD output that misses the syndrome (never)
             }
         }
+#endif
         __syncthreads();
     }
 }
@@ -306,7 +355,11 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
     extern __shared__ double osd_smem[];
     __shared__ unsigned long long s_piv[2];   // (two slots, by column parity: see the pivot search)
     __shared__ unsigned long long s_lm;
+#if QBP_OSD_SHOTS
+    __shared__ int s_bad;
+#else
     __shared__ int s_ew, s_df, s_bad;
+#endif
 #if QBP_OSD_SPECTRUM
     __shared__ int s_rw;                      // weight of the residual
 #endif
@@ -412,13 +465,34 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
             const int c = pivcol[r];
             if (c >= 0 && (At[(size_t)W * m + r] & 1u)) sol[c] ^= 1u;   // distinct pivot columns: no race
         }
+#if QBP_OSD_SHOTS
+        if (tid == 0) { s_lm = 0ull; s_bad = 0; }
+#else
         if (tid == 0) { s_lm = 0ull; s_ew = 0; s_df = 0; s_bad = 0; }
+#endif
 #if QBP_OSD_SPECTRUM
         if (tid == 0) s_rw = 0;
 #endif
         __syncthreads();
         if (P.solution)
             for (int i = tid; i < n; i += nt) P.solution[rec * n + i] = sol[i];
+#if QBP_OSD_SHOTS
+        {
+            unsigned long long lm = 0ull;
+            unsigned bad = 0;
+            for (int i = tid; i < n; i += nt)
+                if (sol[i]) lm ^= P.lx_cols[i];
+            for (int r = tid; r < m; r += nt) {
+                unsigned par = syn[r] & 1u;
+                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
+                bad |= par;
+            }
+            if (lm) atomicXor(&s_lm, lm);
+            if (bad) atomicOr(&s_bad, 1);
+            __syncthreads();
+            if (tid == 0) osd_shot_result(P, rec, s_lm, s_bad != 0);
+        }
+#else
         if (P.errors) {
             const uint8_t* err = P.errors + rec * n;
             unsigned long long lm = 0ull;
@@ -470,6 +544,7 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
                 if (s_bad) add(10);
             }
         }
+#endif
         __syncthreads();
     }
 }
@@ -521,7 +596,11 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
     __shared__ unsigned s_piv[3];
     __shared__ unsigned s_nact[2];
     __shared__ unsigned long long s_lm, s_item;
+#if QBP_OSD_SHOTS
+    __shared__ int s_bad;
+#else
     __shared__ int s_ew, s_df, s_bad;
+#endif
 #if QBP_OSD_SPECTRUM
     __shared__ int s_rw;                      // weight of the residual
 #endif
@@ -588,6 +667,9 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
             }
         }
         OSD_T(0);
+#if QBP_OSD_SHOTS
+        bool shot_redo = false;               // listed for the kernel that follows the row swaps, which predicts it
+#endif
         int pc[RPT];                          // pivot column (original index) of this thread's rows, -1: none yet
         int Wc = 0;
         unsigned sb = 0;                      // bit i: reduced syndrome bit of row tid + i * nt
@@ -786,6 +868,9 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
             OSD_STAT(4, tid == 0 ? k0 : 0); OSD_STAT(5, tid == 0 ? rank : 0); OSD_STAT(6, tid == 0 && !open_rows ? 1 : 0);
             if (rank >= P.rank || !open_rows || K >= n) {
                 if (open_rows && tid == 0) osd_flag_inconsistent(P, rec);
+#if QBP_OSD_SHOTS
+                shot_redo = open_rows && P.redo != nullptr;
+#endif
                 break;
             }
             __syncthreads();                  // (next sweep: pos overwrites the table)
@@ -796,13 +881,34 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
             // (sb: the thread's running copy of its rows' bits in the syndrome plane)
             if (pc[i] >= 0 && ((sb >> i) & 1u)) sol[pc[i]] ^= 1u;                     // distinct pivot columns
         }
+#if QBP_OSD_SHOTS
+        if (tid == 0) { s_lm = 0ull; s_bad = 0; }
+#else
         if (tid == 0) { s_lm = 0ull; s_ew = 0; s_df = 0; s_bad = 0; }
+#endif
 #if QBP_OSD_SPECTRUM
         if (tid == 0) s_rw = 0;
 #endif
         __syncthreads();
         if (P.solution)
             for (int i = tid; i < n; i += nt) P.solution[rec * n + i] = sol[i];
+#if QBP_OSD_SHOTS
+        if (!shot_redo) {        // (uniform)
+            u64 lm = 0ull;
+            unsigned bad = 0;
+            for (int i = tid; i < n; i += nt)
+                if (sol[i]) lm ^= P.lx_cols[i];
+            for (int r = tid; r < m; r += nt) {
+                unsigned par = syn[r] & 1u;
+                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
+                bad |= par;
+            }
+            if (lm) atomicXor(&s_lm, lm);
+            if (bad) atomicOr(&s_bad, 1);
+            __syncthreads();
+            if (tid == 0) osd_shot_result(P, rec, s_lm, s_bad != 0);
+        }
+#else
         if (P.errors) {
             const uint8_t* err = P.errors + rec * n;
             u64 lm = 0ull;
@@ -854,6 +960,7 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
                 if (s_bad) add(10);
             }
         }
+#endif
         __syncthreads();
         OSD_T(7);
     }

@@ -282,6 +282,24 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         if (P.solution)
             for (int i = lane; i < n; i += 64) P.solution[rec * n + i] = sol[i];
 
+#if QBP_OSD_SHOTS
+        if (!(inconsistent && P.redo != nullptr)) {      // (else: the row-swapping kernel's record)
+            unsigned long long lm = 0ull;
+            for (int i = lane; i < n; i += 64)
+                if (sol[i]) lm ^= P.lx_cols[i];
+            unsigned bad = 0;
+            for (int r = lane; r < m; r += 64) {
+                unsigned par = syn[r] & 1u;
+                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
+                bad |= par;
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                lm ^= __shfl_xor(lm, off);
+                bad |= __shfl_xor(bad, off);
+            }
+            if (lane == 0) osd_shot_result(P, rec, lm, bad != 0u);
+        }
+#else
         if (P.errors) {
             // classification of the OSD output (paperResults_GPU.py:127-144), as osd0_kernel
             const uint8_t* err = P.errors + rec * n;
@@ -336,6 +354,7 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
                 if (bad) add(10);
             }
         }
+#endif
         __syncthreads();
     }
 }

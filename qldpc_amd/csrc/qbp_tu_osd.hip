@@ -2,7 +2,21 @@
 // histogram kernels (qbp_hist.hpp).
 // With -DQBP_SPECTRUM_TU: the four OSD kernels that classify once more, under other names, adding the residual weight
 // of every record to a table (qbp_mc_run_spectrum); no histogram kernels in that unit.
+// With -DQBP_SHOTS_TU: the four once more, whose records are recorded shots: they store the observable prediction of
+// every record and compare it with the recorded observables (qbp_decode_shots); no histogram kernels either.
 #define QBP_DEFINE_KERNELS 1
+#ifdef QBP_SHOTS_TU
+#define QBP_OSD_SHOTS 1
+#undef QBP_OSD_TIMING
+#define osd0_kernel osd0_shots_kernel
+#define osd0_big_kernel osd0_big_shots_kernel
+#define osd0_blocked_kernel osd0_blocked_shots_kernel
+#define osd_order_kernel osd_order_shots_kernel
+#define launch_osd_small launch_osd_small_shots
+#define launch_osd_order launch_osd_order_shots
+#define launch_osd_big launch_osd_big_shots
+#define launch_osd_blocked launch_osd_blocked_shots
+#endif
 #ifdef QBP_SPECTRUM_TU
 #define QBP_OSD_SPECTRUM 1
 #undef QBP_OSD_TIMING
@@ -18,7 +32,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
-#ifndef QBP_SPECTRUM_TU
+#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU)
 #include "qbp_hist.hpp"
 #endif
 #include "qbp_launch.hpp"
@@ -114,7 +128,7 @@ extern "C" int qbp_debug_osd_timing(unsigned long long* out, int reset)
 }
 #endif
 
-#ifndef QBP_SPECTRUM_TU
+#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU)
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s)
 {
     hipLaunchKernelGGL(hist_minmax_kernel, dim3(grid), dim3(256), 0, s, x, count, part);
@@ -128,6 +142,6 @@ hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_
     hipLaunchKernelGGL(hist_bin_kernel, dim3(grid), dim3(256), lds, s, msg, errors, col_idx, B, E, n, edges, bins, hist);
     return hipGetLastError();
 }
-#endif  // !QBP_SPECTRUM_TU
+#endif  // !QBP_SPECTRUM_TU && !QBP_SHOTS_TU
 
 }  // namespace qbp

@@ -12,6 +12,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
     python -m qldpc_amd.mc --code 288 --p 0.06 0.05 0.04 --trials 1000000
     python -m torch.distributed.run --nproc-per-node 8 -m qldpc_amd.mc --code 288 ...
     python -m qldpc_amd.mc --dem circuit.dem --trials 1000000 --osd      (detector error model: run_dem)
+    python -m qldpc_amd.mc --dem circuit.dem --shots dets.b8 --obs obs.b8 --osd --predictions-out pred.npy
+                                     (decode RECORDED shots to observable predictions: run_shots)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
     python -m qldpc_amd.mc --code 144 --p 0.05 --osd --spectrum out.npz
@@ -159,6 +161,93 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         return d_cnt.cpu().numpy()
     cnt = np.asarray(runner(H, L, probs, prior, begin, end), np.int64)
     return all_reduce(cnt) if all_reduce is not None else cnt
+
+
+def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
+              damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, flags=0, rank=0, world=1, device=0,
+              runner=None, all_reduce=None):
+    """Decode RECORDED shots of a detector error model to observable predictions (qbp_decode_shots): the loop of
+    studies/studyComplete.py:91-109 on data that was sampled elsewhere (stim's circuit sampler, an experiment).
+
+    ``detections``: the detection events, bit-packed uint8 [T, ceil(m / 8)] (``shots.pack_bits`` /
+    ``shots.read_shots``) or a 0/1 array [T, m]; where ceil(m / 8) == m (m = 1) a uint8 array is taken as packed.
+    ``observables``: None, the recorded flips as uint64 masks [T] (bit l = observable l) or a 0/1 array [T, k].
+    ``prior``: the decoder's LLRs [n] (``dem_prior(probs)`` for a model's own rates).  ``flags``: further
+    decoder flags (column-sum order, FLAG_FORCE_FULL), or-ed with the OSD flags of ``osd`` / ``osd_method`` /
+    ``osd_order``.
+
+    Returns ``(counters int64[12], predictions uint64[T_local], converged bool[T_local])``.  The shot range is split
+    over ranks with ``shard_range``; the counters are GLOBAL (one all-reduce: [0] shots, [1] prediction != recorded,
+    [6] not converged, [7] iterations, [8] the [1] among [6], [10] OSD outputs that miss the syndrome), while
+    predictions and converged cover THIS RANK'S slice ``shard_range(T, rank, world)`` only, in shot order.
+    ``runner(H, L, det_bits, masks, prior, begin, end) -> (int64[12], uint64[end - begin], bool[end - begin])`` and
+    ``all_reduce`` are injection points for the CPU tests; by default the HIP library and torch.distributed."""
+    from . import shots as shots_mod
+    flags = int(flags) | osd_run_flags(osd, osd_method, osd_order)     # (before any GPU work)
+    m, n = H.shape
+    rb = (m + 7) // 8
+    L = np.ascontiguousarray(L, np.uint8)
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if not 1 <= L.shape[0] <= 64:
+        raise ValueError(f"1 to 64 observables (got {L.shape[0]})")
+    det = np.asarray(detections)
+    if det.ndim != 2:
+        raise ValueError(f"detections must be [T, {rb}] packed bytes or a [T, {m}] 0/1 array, got shape {det.shape}")
+    if det.dtype == np.uint8 and det.shape[1] == rb:
+        det = np.ascontiguousarray(det)
+    elif det.shape[1] == m:
+        det = shots_mod.pack_bits(det)            # (C-contiguous whatever the order of the input)
+    else:
+        raise ValueError(f"detections must be [T, {rb}] packed bytes or a [T, {m}] 0/1 array, got {det.dtype} "
+                         f"{det.shape}")
+    T = det.shape[0]
+    masks = None
+    det = np.ascontiguousarray(det)
+    if observables is not None:
+        obs = np.asarray(observables)
+        masks = np.ascontiguousarray(shots_mod.masks_of(obs) if obs.ndim == 2 else np.asarray(obs, np.uint64))
+        if obs.ndim == 2 and obs.shape[1] != L.shape[0]:
+            raise ValueError(f"observables must have {L.shape[0]} columns, got {obs.shape[1]}")
+        if masks.shape != (T,):
+            raise ValueError(f"observables must cover the {T} shots, got shape {obs.shape}")
+    prior = np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    if np.isnan(prior).any():
+        raise ValueError("prior holds NaN")
+    if int(max_iter) < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    begin, end = shard_range(T, rank, world)
+    if runner is None:
+        import torch
+
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        dev = torch.device("cuda", device)
+        stream = torch.cuda.current_stream(dev)
+        d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
+        d_prior = torch.from_numpy(prior).to(dev)
+        d_det = torch.from_numpy(det[begin:end]).to(dev)
+        d_act = torch.from_numpy(masks[begin:end].view(np.int64)).to(dev) if masks is not None else None
+        d_pred = torch.zeros(end - begin, dtype=torch.int64, device=dev)
+        d_conv = torch.zeros(end - begin, dtype=torch.uint8, device=dev)
+        step = dec.mc_osd_step() if (flags & _lib.FLAG_OSD0) else 1 << 40     # OSD keeps per-shot records
+        for a in range(0, end - begin, step):
+            t = min(step, end - begin - a)
+            dec.decode_shots_device(L, d_det.data_ptr() + a * rb, d_act.data_ptr() + 8 * a if d_act is not None else 0,
+                                    t, d_prior.data_ptr(), d_pred.data_ptr() + 8 * a, d_conv.data_ptr() + a,
+                                    d_cnt.data_ptr(), max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                    clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
+        if world > 1:
+            import torch.distributed as dist
+            dist.all_reduce(d_cnt)
+        torch.cuda.synchronize(dev)
+        return d_cnt.cpu().numpy(), d_pred.cpu().numpy().view(np.uint64), d_conv.cpu().numpy().astype(bool)
+    cnt, pred, conv = runner(H, L, det, masks, prior, begin, end)
+    cnt = np.asarray(cnt, np.int64)
+    cnt = all_reduce(cnt) if all_reduce is not None else cnt
+    return cnt, np.asarray(pred, np.uint64), np.asarray(conv, bool)
 
 
 def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, draws, seed, variant, alpha, damping,
@@ -419,6 +508,17 @@ def main(argv=None):
                     help="with --dem: the distance of the miscorrected / incorrectable split (0: all incorrectable)")
     ap.add_argument("--p", type=float, nargs="+",
                     default=[0.05, 0.04, 0.03, 0.02, 0.01, 0.009, 0.008, 0.007])   # :39
+    ap.add_argument("--shots", default=None, metavar="DETS",
+                    help="with --dem: decode the RECORDED shots of this file (detection events, stim's b8 or 01 "
+                         "format) instead of sampling: run_shots; prints the counters as one JSON line")
+    ap.add_argument("--obs", default=None, metavar="OBS",
+                    help="with --shots: the recorded observables, a file of the same format (stim's --obs_out)")
+    ap.add_argument("--shots-format", choices=("b8", "01"), default="b8")
+    ap.add_argument("--append-observables", action="store_true",
+                    help="with --shots: every shot of DETS carries its observables behind the detection events")
+    ap.add_argument("--predictions-out", default=None, metavar="PRED.npy",
+                    help="with --shots: write the predictions (uint64 masks, bit l = observable l) of this rank's "
+                         "shots; with several ranks the file name gets .rank<r> before its extension")
     ap.add_argument("--trials", type=int, default=10000)                          # :36
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--budgets", type=int, nargs="+", default=None,
@@ -472,6 +572,30 @@ def main(argv=None):
         if dem_model[1].shape[0] > 64:
             ap.error(f"--dem {args.dem}: {dem_model[1].shape[0]} observables (at most 64)")
 
+    shot_data = None
+    if args.shots is not None:
+        from . import shots as shots_mod
+        if dem_model is None:
+            ap.error("--shots needs --dem")
+        if args.budgets is not None or args.spectrum is not None:
+            ap.error("--shots does not combine with --budgets or --spectrum")
+        if args.obs is not None and args.append_observables:
+            ap.error("--obs and --append-observables exclude each other")
+        for path in (args.shots, args.obs):
+            if path is not None and not os.path.isfile(path):
+                ap.error(f"{path}: no such file")
+        if dem_model[1].shape[0] < 1:
+            ap.error(f"--dem {args.dem}: no observables to predict")
+        try:
+            shot_data = shots_mod.read_shots(
+                args.shots, dem_model[0].shape[0],
+                dem_model[1].shape[0] if (args.obs is not None or args.append_observables) else 0,
+                args.shots_format, obs=args.obs)
+        except ValueError as e:
+            ap.error(f"--shots: {e}")
+    elif args.obs is not None or args.predictions_out is not None or args.append_observables:
+        ap.error("--obs, --append-observables and --predictions-out need --shots")
+
     import sys
     from . import launch
     if argv is None:          # (a caller passing argv runs in-process, whatever --gpus says)
@@ -496,6 +620,35 @@ def main(argv=None):
     common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
                   damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
                   osd_order=args.osd_order, device=local)
+    if shot_data is not None:
+        H, L, probs = dem_model
+        kw = {k: common[k] for k in ("max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",
+                                     "osd_order", "device")}
+        t0 = time.perf_counter()
+        cnt, pred, conv = run_shots(H, L, shot_data[0], shot_data[1], prior=dem_prior(probs), rank=rank, world=world,
+                                    **kw)
+        dt = time.perf_counter() - t0
+        if args.predictions_out:
+            out = args.predictions_out
+            if world > 1:
+                root, ext = os.path.splitext(out)
+                out = f"{root}.rank{rank}{ext}"
+            with open(out, "wb") as f:       # (np.save on a name would append .npy to other extensions)
+                np.save(f, pred)
+        if rank == 0:
+            result = {"dem": args.dem, "shots": args.shots, "m": int(H.shape[0]), "n": int(H.shape[1]),
+                      "k": int(L.shape[0]), "observables": shot_data[1] is not None, "max_iter": args.max_iter,
+                      "variant": args.variant, "osd": args.osd, "osd_method": args.osd_method,
+                      "osd_order": args.osd_order, "world_size": world, "seconds": dt,
+                      "counters": {k: int(v) for k, v in zip(_lib.COUNTER_NAMES, cnt)}}
+            print(json.dumps(result))
+            if args.out:
+                with open(args.out, "w") as f:
+                    json.dump(result, f, indent=1)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     if args.budgets is not None:
         points = list(args.budgets)      # one row per iteration limit
         del common["max_iter"]

@@ -23,6 +23,11 @@ UNITS += [("qbp_tu_fused.hip", ["-DQBP_BUDGETS_TU"])] + [("qbp_tu_generic.hip", 
 UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SPECTRUM_TU"])] +
           [("qbp_tu_generic.hip", ["-DQBP_SPECTRUM_TU", f"-DQBP_GENERIC_MEM={i}"]) for i in range(3)] +
           [("qbp_tu_osd.hip", ["-DQBP_SPECTRUM_TU"])])
+# Recorded shots in, observable predictions out (qbp_decode_shots): bp_fused_shots_kernel, bp_generic_shots_kernel,
+# and the OSD kernels that predict their records (osd*_shots_kernel)
+UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SHOTS_TU"])] +
+          [("qbp_tu_generic.hip", ["-DQBP_SHOTS_TU", f"-DQBP_GENERIC_MEM={i}"]) for i in range(3)] +
+          [("qbp_tu_osd.hip", ["-DQBP_SHOTS_TU"])])
 
 
 def demangle(sym):
