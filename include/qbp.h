@@ -267,6 +267,27 @@ int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, c
 int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
                          const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream);
 
+/*
+ * qbp_osd_batch with the column order as an input: order [B][n] int32, row b a permutation of 0..n-1, the columns
+ * of record b from the least reliable on.  Rule 1 above becomes "columns in the given order" (the |llr| keys and
+ * their NaN rule play no part in the order), rule 4 "the non-pivot columns in the given order"; everything else --
+ * the cost of rule 6 as the sum of fabs(llr), its NaN rules, the output for syndromes outside the column space,
+ * which follows the reference's row swaps in the given order -- stays.  With order[b] = the (|llr|, column) sort the
+ * call is qbp_osd_batch bit for bit; with order[b] = what the reference computes, np.argsort(np.abs(llr[b])), OSD-0 is
+ * the reference's performOSD also where equal |llr| leave np.argsort's order to the numpy build (the Python drop-in
+ * does that under QBP_OSD_NUMPY_ORDER=1: then performOSD is the reference's function on tied inputs wherever the
+ * host's numpy is the reference's numpy).  Flags, limits, kernel selection and QBP_E_UNSUPPORTED cases are those of
+ * qbp_osd_batch.  The host entry returns QBP_E_INVALID, naming the record, for a null order or a row that is not a
+ * permutation, before any GPU work and with `solution` untouched.  The _device entry cannot check d_order (null is
+ * QBP_E_INVALID): for any int32 content an entry outside [0, n) is skipped and a repeated column finds no pivot;
+ * the output of such a record is unspecified, but nothing is read or written out of bounds.
+ */
+int qbp_osd_batch_ordered(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr,
+                          const uint8_t* hard, const int32_t* order, int64_t B, uint8_t* solution);
+int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                                 const uint8_t* d_hard, const int32_t* d_order, int64_t B, uint8_t* d_solution,
+                                 void* stream);
+
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */
 int qbp_mc_sample_errors(qbp_handle* h, double p, int32_t draws, uint64_t seed,

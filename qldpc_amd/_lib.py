@@ -100,6 +100,8 @@ SIGNATURES = {
     "qbp_osd0_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     "qbp_osd_batch": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP]),
     "qbp_osd_batch_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
+    "qbp_osd_batch_ordered": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    "qbp_osd_batch_ordered_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
@@ -588,9 +590,10 @@ class Decoder:
                                             stream or None))
 
     @_locked
-    def osd(self, syndromes, llr, hard, method="cs", order=7):
+    def osd(self, syndromes, llr, hard, method="cs", order=7, column_order=None):
         """Order-w OSD (include/qbp.h, qbp_osd_batch) on B decoder outputs (host arrays) -> solution
-        uint8[B, n]; order 0 is OSD-0."""
+        uint8[B, n]; order 0 is OSD-0.  ``column_order`` int[B, n]: every record's columns from the least reliable
+        on, a permutation of 0..n-1 per row (qbp_osd_batch_ordered); None: sorted by (|llr|, column)."""
         fl = osd_flags(method, order)
         syn = np.ascontiguousarray(syndromes, np.uint8)
         l = np.ascontiguousarray(llr, np.float64)
@@ -600,12 +603,27 @@ class Decoder:
         if l.shape != (syn.shape[0], self.n) or hd.shape != l.shape:
             raise ValueError(f"llr and hard must have shape ({syn.shape[0]}, {self.n})")
         sol = np.empty_like(hd)
-        _check(load().qbp_osd_batch(self._h, fl, syn.ctypes.data, l.ctypes.data, hd.ctypes.data,
-                                    syn.shape[0], sol.ctypes.data))
+        if column_order is None:
+            _check(load().qbp_osd_batch(self._h, fl, syn.ctypes.data, l.ctypes.data, hd.ctypes.data,
+                                        syn.shape[0], sol.ctypes.data))
+            return sol
+        co = np.asarray(column_order)
+        if co.dtype.kind not in "iu" or co.shape != l.shape:
+            raise ValueError(f"column_order must be an integer array of shape ({syn.shape[0]}, {self.n})")
+        if co.size and (co.min() < -2**31 or co.max() >= 2**31):   # (the cast to int32 must not wrap a value into
+            raise ValueError("column_order entries do not fit int32")   # range; the library checks the rows)
+        co = np.ascontiguousarray(co, np.int32)
+        _check(load().qbp_osd_batch_ordered(self._h, fl, syn.ctypes.data, l.ctypes.data, hd.ctypes.data,
+                                            co.ctypes.data, syn.shape[0], sol.ctypes.data))
         return sol
 
-    def osd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, method="cs", order=7, stream=0):
-        """Order-w OSD on device buffers (pointers as ints), enqueued on `stream`."""
+    def osd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, method="cs", order=7, stream=0, d_order=0):
+        """Order-w OSD on device buffers (pointers as ints), enqueued on `stream`.  ``d_order``: int32[B, n] column
+        orders on the device (qbp_osd_batch_ordered_device: not validated there), 0: sorted by (|llr|, column)."""
+        if d_order:
+            _check(load().qbp_osd_batch_ordered_device(self._h, osd_flags(method, order), d_syndromes, d_llr, d_hard,
+                                                       d_order, int(B), d_solution, stream or None))
+            return
         _check(load().qbp_osd_batch_device(self._h, osd_flags(method, order), d_syndromes, d_llr, d_hard, int(B),
                                            d_solution, stream or None))
 

@@ -334,7 +334,7 @@ class _LastBatch:
     served, at the next batch call of the thread, or never created with QBP_NO_LAST_BATCH=1
     (qldpc_amd.bp.REMEMBER_LAST_BATCH = False)."""
     __slots__ = ("dec", "syn", "llr_ref", "hard", "conv", "addr", "rowbytes", "rows", "pos", "inputs",
-                 "solutions", "lock", "served", "n_fail")
+                 "solutions", "orders", "lock", "served", "n_fail")
 
     def __init__(self, dec, syn, llr, hard, conv):
         import weakref
@@ -343,6 +343,7 @@ class _LastBatch:
         self.addr = llr.__array_interface__["data"][0]
         self.rowbytes, self.rows = llr.strides[0], llr.shape[0]
         self.pos = self.inputs = self.solutions = None
+        self.orders = None                # the column orders the solutions were computed in (qldpc_amd/osd.py)
         self.lock = threading.Lock()
         self.served, self.n_fail = set(), int((~conv).sum())
 

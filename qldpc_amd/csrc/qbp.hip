@@ -177,6 +177,7 @@ struct qbp_handle {
     DevBuf<unsigned long long> d_osd_next;   // work counter of osd0_blocked_kernel
     DevBuf<long long> d_osd_redo;   // [0]: count, [1..]: records whose OSD sweep found the syndrome inconsistent
     DevBuf<uint8_t> d_osd_sol;
+    DevBuf<int32_t> d_osd_order;    // qbp_osd_batch_ordered: the caller's column orders
     DevBuf<unsigned long long> d_osd_keys;
     DevBuf<uint32_t> d_hbits;
     DevBuf<int32_t> d_row_ptr, d_col_idx;
@@ -1435,8 +1436,10 @@ static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long ma
     Wk.At = h->d_osd_At.p; Wk.pivcol = h->d_osd_piv.p; Wk.posn = h->d_osd_posn.p; Wk.sol = h->d_osd_sol.p;
     Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
     // (O.spectrum, here and in osd_launch: the builds that add residual weights to that table, qbp_mc_run_spectrum;
-    // O.shots: the builds that predict recorded shots, qbp_decode_shots)
-    HIP_TRY((O.shots ? qbp::launch_osd_big_shots : O.spectrum ? qbp::launch_osd_big_spectrum : qbp::launch_osd_big)(
+    // O.shots: the builds that predict recorded shots, qbp_decode_shots; O.order: the builds that take the column
+    // order from the caller, qbp_osd_batch_ordered)
+    HIP_TRY((O.order ? qbp::launch_osd_big_ordered : O.shots ? qbp::launch_osd_big_shots
+             : O.spectrum ? qbp::launch_osd_big_spectrum : qbp::launch_osd_big)(
         (unsigned)grid, Wk.keys_in_lds ? NP * 12 : 0, O, Wk, s));
     return QBP_OK;
 }
@@ -1472,6 +1475,8 @@ static int parse_osd_flags(const qbp_handle* h, uint32_t flags, bool mc, int* me
     return QBP_OK;
 }
 
+// O.order (qbp_osd_batch_ordered; null everywhere else): the column orders of the records, for the same choice of
+// kernel and for the redo pass, whose list holds record indices.
 // `redo`: the caller's syndromes may lie outside the column space of H (anything but the Monte-Carlo loop, whose
 // syndromes come from errors): the fast kernels then list the records whose sweep says so, and the kernel that
 // follows the reference's row swaps recomputes them (an empty list costs one small launch).
@@ -1521,20 +1526,21 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
         }
         Wk.At = h->d_osd_At.p; Wk.sol = h->d_osd_sol.p; Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
         const int rpt = m <= 1024 ? 1 : m <= 2048 ? 2 : m <= 4096 ? 4 : 8;
-        HIP_TRY((O.shots ? qbp::launch_osd_blocked_shots : O.spectrum ? qbp::launch_osd_blocked_spectrum
-                                                                      : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk, s));
+        HIP_TRY((O.order ? qbp::launch_osd_blocked_ordered : O.shots ? qbp::launch_osd_blocked_shots
+                 : O.spectrum ? qbp::launch_osd_blocked_spectrum : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk,
+                                                                                            s));
     } else if (method) {
         // order w (parse_osd_flags has checked osd_ok and the LDS)
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
         const size_t olds = (qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
-        HIP_TRY((O.shots ? qbp::launch_osd_order_shots : O.spectrum ? qbp::launch_osd_order_spectrum
-                                                                    : qbp::launch_osd_order)(h->osd_W + 1, (unsigned)grid, olds, O,
-                                                                                             method, order, s));
+        HIP_TRY((O.order ? qbp::launch_osd_order_ordered : O.shots ? qbp::launch_osd_order_shots
+                 : O.spectrum ? qbp::launch_osd_order_spectrum : qbp::launch_osd_order)(h->osd_W + 1, (unsigned)grid, olds, O,
+                                                                                        method, order, s));
     } else {
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
-        HIP_TRY((O.shots ? qbp::launch_osd_small_shots : O.spectrum ? qbp::launch_osd_small_spectrum
-                                                                    : qbp::launch_osd_small)(h->osd_W + 1, (unsigned)grid,
-                                                                                             (size_t)h->osd_lds, O, s));
+        HIP_TRY((O.order ? qbp::launch_osd_small_ordered : O.shots ? qbp::launch_osd_small_shots
+                 : O.spectrum ? qbp::launch_osd_small_spectrum : qbp::launch_osd_small)(h->osd_W + 1, (unsigned)grid,
+                                                                                        (size_t)h->osd_lds, O, s));
     }
     if (redo) {
         qbp::OsdParams R = O;
@@ -1545,9 +1551,10 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
     return QBP_OK;
 }
 
-int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
-                         const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
-try {
+// qbp_osd_batch_device and qbp_osd_batch_ordered_device: `d_order` null is the former
+static int osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                            const uint8_t* d_hard, const int32_t* d_order, int64_t B, uint8_t* d_solution, void* stream)
+{
     if (!h) return fail(QBP_E_INVALID, "null handle");
     int method = 0, order = 0;
     int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
@@ -1559,13 +1566,30 @@ try {
     HIP_TRY(on_device.err);
     qbp::OsdParams O{};
     O.count = B; O.syndromes = d_syndromes; O.llr = d_llr; O.hard = d_hard; O.solution = d_solution;
+    O.order = d_order;
     return osd_launch(h, O, B, static_cast<hipStream_t>(stream), true, method, order);
+}
+
+int qbp_osd_batch_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                         const uint8_t* d_hard, int64_t B, uint8_t* d_solution, void* stream)
+try {
+    return osd_batch_device(h, osd_flags, d_syndromes, d_llr, d_hard, nullptr, B, d_solution, stream);
 }
 QBP_ABI_CATCH
 
-int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
-                  int64_t B, uint8_t* solution)
+int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
+                                 const uint8_t* d_hard, const int32_t* d_order, int64_t B, uint8_t* d_solution,
+                                 void* stream)
 try {
+    if (!d_order) return fail(QBP_E_INVALID, "null column order");
+    return osd_batch_device(h, osd_flags, d_syndromes, d_llr, d_hard, d_order, B, d_solution, stream);
+}
+QBP_ABI_CATCH
+
+// qbp_osd_batch and qbp_osd_batch_ordered (`ordered`): host buffers in, solutions out
+static int osd_batch_host(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr,
+                          const uint8_t* hard, const int32_t* col_order, bool ordered, int64_t B, uint8_t* solution)
+{
     if (!h) return fail(QBP_E_INVALID, "null handle");
     int method = 0, order = 0;
     int rc = parse_osd_flags(h, osd_flags, false, &method, &order);
@@ -1573,22 +1597,56 @@ try {
     if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0");
     if (B == 0) return QBP_OK;
     if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    if (ordered) {
+        // every row a permutation of 0..n-1: checked here, before any GPU work (the kernels only stay in bounds)
+        if (!col_order) return fail(QBP_E_INVALID, "null column order");
+        std::vector<uint8_t> seen(n);
+        for (size_t r = 0; r < b; ++r) {
+            std::fill(seen.begin(), seen.end(), (uint8_t)0);
+            for (size_t i = 0; i < n; ++i) {
+                const int32_t c = col_order[r * n + i];
+                if (c < 0 || (size_t)c >= n)
+                    return fail(QBP_E_INVALID, "column order of record %lld: entry %d at position %lld is outside [0, %d)",
+                                (long long)r, (int)c, (long long)i, h->n);
+                if (seen[c])
+                    return fail(QBP_E_INVALID, "column order of record %lld: column %d appears twice (not a permutation)",
+                                (long long)r, (int)c);
+                seen[c] = 1;
+            }
+        }
+    }
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B;
     HIP_TRY(h->d_syn.reserve(b * m));
     HIP_TRY(h->d_llr.reserve(b * n));
     HIP_TRY(h->d_hard.reserve(b * n));
     HIP_TRY(h->d_sol.reserve(b * n));
+    if (ordered) HIP_TRY(h->d_osd_order.reserve(b * n));
     hipStream_t s = h->stream;
     HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
-    rc = qbp_osd_batch_device(h, osd_flags, h->d_syn.p, h->d_llr.p, h->d_hard.p, B, h->d_sol.p, s);
+    if (ordered) HIP_TRY(hipMemcpyAsync(h->d_osd_order.p, col_order, b * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    rc = osd_batch_device(h, osd_flags, h->d_syn.p, h->d_llr.p, h->d_hard.p, ordered ? h->d_osd_order.p : nullptr, B,
+                          h->d_sol.p, s);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QBP_OK;
+}
+
+int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
+                  int64_t B, uint8_t* solution)
+try {
+    return osd_batch_host(h, osd_flags, syndromes, llr, hard, nullptr, false, B, solution);
+}
+QBP_ABI_CATCH
+
+int qbp_osd_batch_ordered(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr,
+                          const uint8_t* hard, const int32_t* order, int64_t B, uint8_t* solution)
+try {
+    return osd_batch_host(h, osd_flags, syndromes, llr, hard, order, true, B, solution);
 }
 QBP_ABI_CATCH
 

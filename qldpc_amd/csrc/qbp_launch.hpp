@@ -96,6 +96,15 @@ hipError_t launch_osd_order_shots(int words_per_row, unsigned grid, size_t lds, 
 hipError_t launch_osd_big_shots(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_osd_blocked_shots(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                                     const OsdBigWorkspace& Wk, hipStream_t s);
+// the same four with O.order set (qbp_osd_batch_ordered): qbp_tu_osd.hip -DQBP_ORDERED_TU, kernels under names of their
+// own
+hipError_t launch_osd_small_ordered(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, hipStream_t s);
+hipError_t launch_osd_order_ordered(int words_per_row, unsigned grid, size_t lds, const OsdParams& O, int method,
+                                    int order, hipStream_t s);
+hipError_t launch_osd_big_ordered(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk,
+                                  hipStream_t s);
+hipError_t launch_osd_blocked_ordered(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                      const OsdBigWorkspace& Wk, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

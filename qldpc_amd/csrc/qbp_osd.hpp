@@ -33,6 +33,13 @@
 #define QBP_OSD_SHOTS 0
 #endif
 
+#ifndef QBP_OSD_ORDERED
+// 1: the column order is an input (OsdParams::order, qbp_osd_batch_ordered): step 1 of every kernel copies the
+// record's row of it instead of sorting.  Set by qbp_tu_osd.hip -DQBP_ORDERED_TU, which gives those kernels names of
+// their own: the other builds keep their code, registers and LDS.
+#define QBP_OSD_ORDERED 0
+#endif
+
 namespace qbp {
 
 struct OsdParams {
@@ -68,6 +75,13 @@ struct OsdParams {
     int shots;
     const unsigned long long* actual;
     unsigned long long* predictions;
+    // (last: QBP_OSD_ORDERED builds only; non-null selects them) [*][n]: row `rec` is the order in which record `rec`
+    // walks its columns, least reliable first -- a permutation of 0..n-1 (the host entry checks that; the _device entry
+    // cannot).  The keys of |llr| then play no part in the order.  Memory safety for ANY int32 content: an entry outside
+    // [0, n) is skipped; a repeated column is harmless (it is already eliminated: no unused row has a 1 there); a
+    // column that never appears is never a pivot.  The output of such a row is unspecified, but nothing is read or
+    // written out of bounds.
+    const int32_t* order;
 };
 
 // Sort key of |llr|: the IEEE bit pattern of a non-negative double is monotone as an unsigned
@@ -146,6 +160,20 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
 
+#if QBP_OSD_ORDERED
+        // ---- 1. ordering = the record's row of P.order (the caller's argsort)  OSD.py:10-11
+        // (0xffff: an entry outside [0, n) -- the sweep skips it -- and the padding positions, which it never reaches)
+        (void)llr; (void)keys;
+        {
+            const int32_t* ord = P.order + rec * n;
+            for (int i = lane; i < NP; i += 64) {
+                const int c = i < n ? ord[i] : -1;
+                idx[i] = (uint16_t)(c >= 0 && c < n ? c : 0xffff);
+            }
+        }
+        for (int i = lane; i < n; i += 64) sol[i] = hard[i] & 1u;
+        __syncthreads();
+#else
         // ---- 1. ordering = argsort(|llr|)                                    OSD.py:10-11
         for (int i = lane; i < NP; i += 64) {
             keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;      // padding sorts behind everything
@@ -168,6 +196,7 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
                 __syncthreads();
             }
         }
+#endif
         // ---- 2. A = [H | residual syndrome], residual = syndrome + hard @ H.T  OSD.py:7-8
         // (A overwrites the sort keys: every lane passed the sort's last barrier)
         unsigned sb = 0;                             // bit i: reduced syndrome bit of row lane + 64 i
@@ -194,6 +223,9 @@ __global__ __launch_bounds__(64) void osd0_kernel(const OsdParams P)
         for (int k = 0; k < n && rank < P.rank; ++k) {
             if (!__ballot((sb & ~used) != 0u)) break;
             const int c = idx[k];
+#if QBP_OSD_ORDERED
+            if (c >= n) continue;                    // (uniform) not a column: skipped
+#endif
             const int wi = c >> 5;
             const uint32_t bit = 1u << (c & 31);
             int p = -1;
@@ -386,6 +418,19 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
         const double* llr = P.llr + rec * n;
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
+#if QBP_OSD_ORDERED
+        // ---- 1. ordering = the record's row of P.order (-1: an entry outside [0, n), and the padding)  OSD.py:10-11
+        (void)llr;
+        {
+            const int32_t* ord = P.order + rec * n;
+            for (int i = tid; i < NP; i += nt) {
+                const int c = i < n ? ord[i] : -1;
+                idx[i] = c >= 0 && c < n ? c : -1;
+            }
+        }
+        for (int i = tid; i < n; i += nt) sol[i] = hard[i] & 1u;
+        __syncthreads();
+#else
         // ---- 1. ordering = argsort(|llr|), ties by column index                    OSD.py:10-11
         for (int i = tid; i < NP; i += nt) {
             keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;
@@ -408,6 +453,7 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
                 __syncthreads();
             }
         }
+#endif
         // ---- 2. A = [H | residual syndrome]                                         OSD.py:7-8
         for (int r = tid; r < m; r += nt) {
             for (int w = 0; w < W; ++w) At[(size_t)w * m + r] = P.hbits[(size_t)r * W + w];
@@ -424,9 +470,17 @@ __global__ __launch_bounds__(256) void osd0_big_kernel(const OsdParams P, const 
         // which swaps every pivot row up (:46-59): rows keep their place here and carry that position along.
         int rank = 0;
         for (int k = 0; k < n && rank < P.rank; ++k) {
+#if QBP_OSD_ORDERED
+            // (an entry that is no column goes through the search as a column without a 1 -- not around it: the two
+            // slots of s_piv alternate with k)
+            const int c = idx[k];
+            const uint32_t* const colw = At + (size_t)((c < 0 ? 0 : c) >> 5) * m;
+            const uint32_t bit = c < 0 ? 0u : 1u << (c & 31);
+#else
             const int c = idx[k];
             const uint32_t* const colw = At + (size_t)(c >> 5) * m;
             const uint32_t bit = 1u << (c & 31);
+#endif
             // (slot k & 1: a column without pivot leaves this iteration without a trailing barrier, so the
             // next column's reset must not touch the word the slower threads are still reading)
             unsigned long long* const piv = &s_piv[k & 1];
@@ -644,6 +698,19 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
         const double* llr = P.llr + rec * n;
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
+#if QBP_OSD_ORDERED
+        // ---- 1. ordering = the record's row of P.order (-1: an entry outside [0, n), and the padding)  OSD.py:10-11
+        (void)llr;
+        {
+            const int32_t* ord = P.order + rec * n;
+            for (int i = tid; i < NP; i += nt) {
+                const int c = i < n ? ord[i] : -1;
+                idx[i] = c >= 0 && c < n ? c : -1;
+            }
+        }
+        for (int i = tid; i < n; i += nt) sol[i] = hard[i] & 1u;
+        __syncthreads();
+#else
         // ---- 1. ordering = argsort(|llr|), ties by column index                    OSD.py:10-11
         for (int i = tid; i < NP; i += nt) {
             keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;
@@ -666,6 +733,7 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
                 __syncthreads();
             }
         }
+#endif
         OSD_T(0);
 #if QBP_OSD_SHOTS
         bool shot_redo = false;               // listed for the kernel that follows the row swaps, which predicts it
@@ -676,7 +744,15 @@ __global__ __launch_bounds__(1024) void osd0_blocked_kernel(const OsdParams P, c
         for (int K = Wk.k_first < n ? Wk.k_first : n;; K = K < n / 4 ? 4 * K : n) {
             Wc = ((K + 63) >> 6) + 1;         // word planes: K sorted columns, then the syndrome bit
             // ---- 2. A = [H[:, order[:K]] | residual syndrome]                       OSD.py:7-11
+#if QBP_OSD_ORDERED
+            // (a column the row does not name gets position n: in no sweep's working copy)
+            for (int c = tid; c < n; c += nt) pos[c] = n;
+            __syncthreads();
+            for (int k = tid; k < n; k += nt)
+                if (idx[k] >= 0) pos[idx[k]] = k;
+#else
             for (int k = tid; k < n; k += nt) pos[idx[k]] = k;
+#endif
             __syncthreads();
             sb = 0;
 #pragma unroll

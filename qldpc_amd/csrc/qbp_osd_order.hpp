@@ -111,6 +111,23 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
 
+#if QBP_OSD_ORDERED
+        // ---- 1. order: the record's row of P.order, as osd0_kernel's ordered build (0xffff: no column)
+        (void)keys;
+        {
+            const int32_t* ord = P.order + rec * n;
+            for (int i = lane; i < NP; i += 64) {
+                const int c = i < n ? ord[i] : -1;
+                idx[i] = (uint16_t)(c >= 0 && c < n ? c : 0xffff);
+            }
+        }
+        for (int i = lane; i < n; i += 64) {
+            sol[i] = hard[i] & 1u;
+            absl[i] = __builtin_fabs(llr[i]);
+            cinfo[i] = -1;
+        }
+        __syncthreads();
+#else
         // ---- 1. order: ascending (osd_order_key(llr), column), as osd0_kernel
         for (int i = lane; i < NP; i += 64) {
             keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;
@@ -137,6 +154,7 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
                 __syncthreads();
             }
         }
+#endif
         // ---- 2. A = [H | residual syndrome], residual = syndrome + hard @ H.T
         unsigned sb = 0;                             // bit i: reduced syndrome bit of row lane + 64 i
         for (int r = lane, i = 0; r < m; r += 64, ++i) {
@@ -153,6 +171,9 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         unsigned used = 0;                           // bit i: row lane + 64 i already serves as a pivot row
         for (int k = 0; k < n && rank < P.rank; ++k) {
             const int c = idx[k];
+#if QBP_OSD_ORDERED
+            if (c >= n) continue;                    // (uniform) not a column: skipped
+#endif
             const int wi = c >> 5;
             const uint32_t bit = 1u << (c & 31);
             int p = -1;
@@ -200,12 +221,17 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         }
         __syncthreads();
         if (!inconsistent) {
-            // ---- 5. T = non-pivot columns in sort order; cinfo[T[t]] = ~t
+            // ---- 5. T = non-pivot columns in sort order (ordered builds: in the given order); cinfo[T[t]] = ~t
             int kp = 0;
             for (int b0 = 0; b0 < n; b0 += 64) {
                 const int k = b0 + lane;
+#if QBP_OSD_ORDERED
+                const int c = k < n && idx[k] < n ? idx[k] : 0;
+                const bool isT = k < n && idx[k] < n && cinfo[c] < 0;
+#else
                 const int c = k < n ? idx[k] : 0;
                 const bool isT = k < n && cinfo[c] < 0;
+#endif
                 const unsigned long long bal = __ballot(isT);
                 if (isT) {
                     const int t = kp + (int)__builtin_popcountll(bal & ((1ull << lane) - 1ull));

@@ -4,7 +4,21 @@
 // of every record to a table (qbp_mc_run_spectrum); no histogram kernels in that unit.
 // With -DQBP_SHOTS_TU: the four once more, whose records are recorded shots: they store the observable prediction of
 // every record and compare it with the recorded observables (qbp_decode_shots); no histogram kernels either.
+// With -DQBP_ORDERED_TU: the four once more, which take the column order of every record from the caller instead of
+// sorting (qbp_osd_batch_ordered); no histogram kernels either.
 #define QBP_DEFINE_KERNELS 1
+#ifdef QBP_ORDERED_TU
+#define QBP_OSD_ORDERED 1
+#undef QBP_OSD_TIMING
+#define osd0_kernel osd0_ordered_kernel
+#define osd0_big_kernel osd0_big_ordered_kernel
+#define osd0_blocked_kernel osd0_blocked_ordered_kernel
+#define osd_order_kernel osd_order_ordered_kernel
+#define launch_osd_small launch_osd_small_ordered
+#define launch_osd_order launch_osd_order_ordered
+#define launch_osd_big launch_osd_big_ordered
+#define launch_osd_blocked launch_osd_blocked_ordered
+#endif
 #ifdef QBP_SHOTS_TU
 #define QBP_OSD_SHOTS 1
 #undef QBP_OSD_TIMING
@@ -32,7 +46,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
-#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU)
+#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU) && !defined(QBP_ORDERED_TU)
 #include "qbp_hist.hpp"
 #endif
 #include "qbp_launch.hpp"
@@ -128,7 +142,7 @@ extern "C" int qbp_debug_osd_timing(unsigned long long* out, int reset)
 }
 #endif
 
-#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU)
+#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU) && !defined(QBP_ORDERED_TU)
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s)
 {
     hipLaunchKernelGGL(hist_minmax_kernel, dim3(grid), dim3(256), 0, s, x, count, part);
@@ -142,6 +156,6 @@ hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_
     hipLaunchKernelGGL(hist_bin_kernel, dim3(grid), dim3(256), lds, s, msg, errors, col_idx, B, E, n, edges, bins, hist);
     return hipGetLastError();
 }
-#endif  // !QBP_SPECTRUM_TU && !QBP_SHOTS_TU
+#endif  // !QBP_SPECTRUM_TU && !QBP_SHOTS_TU && !QBP_ORDERED_TU
 
 }  // namespace qbp

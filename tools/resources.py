@@ -28,6 +28,8 @@ UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SPECTRUM_TU"])] +
 UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SHOTS_TU"])] +
           [("qbp_tu_generic.hip", ["-DQBP_SHOTS_TU", f"-DQBP_GENERIC_MEM={i}"]) for i in range(3)] +
           [("qbp_tu_osd.hip", ["-DQBP_SHOTS_TU"])])
+# OSD in a column order the caller gives (qbp_osd_batch_ordered): the OSD kernels without their sort (osd*_ordered_kernel)
+UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
 
 
 def demangle(sym):
