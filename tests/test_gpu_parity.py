@@ -82,6 +82,14 @@ def test_hip_vs_oracle_fresh(name, p, B):
           "LLR bits identical to the oracle in both column orders")
 
 
+def _other_batch(syn):
+    """A different batch of the same shape: the complement of every syndrome.  The host entry point decodes into
+    buffers the handle owns and reuses: an A/B test that decodes the same syndromes twice on one handle decodes this
+    batch in between, so that a syndrome the second kernel never wrote leaves WRONG data behind, not the first
+    call's correct result."""
+    return (1 - syn).astype(np.uint8)        # (every row differs from the one at its index)
+
+
 def test_force_full_same_outputs_and_determinism():
     code = codes.load_code("[[144, 12, 12]]")
     rng = np.random.default_rng(3)
@@ -110,13 +118,16 @@ def test_forced_mode_one_barrier_kernel_equals_two_barrier_kernel_and_early_exit
     rng = np.random.default_rng(11)
     for p, B in ((0.02, 300), (0.07, 9000)):
         syn = ((rng.random((B, code.n)) < p).astype(np.int64) @ H.T % 2).astype(np.uint8)
+        other = _other_batch(syn)
         prior = np.full(code.n, np.log((1 - p) / p)) * rng.uniform(0.8, 1.2, code.n)
         for variant, kw in ((0, {}), (1, dict(alpha=0.9, damping=0.8, clip_llr=20.0)),
                             (2, dict(alpha=0.8, damping=0.7, clip_llr=25.0))):
             for max_iter in (1, 2, 3, 17, 50):
                 early = dec.decode(syn, prior, max_iter, variant, **kw)
+                dec.decode(other, prior, max_iter, variant, **kw)              # (see _other_batch)
                 one = dec.decode(syn, prior, max_iter, variant, flags=_lib.FLAG_FORCE_FULL, **kw)
                 used_one = dec.info("one_barrier")
+                dec.decode(other, prior, max_iter, variant, **kw)
                 dec.set_option(_lib.OPT_FORCED_TWO_BARRIERS, 1)
                 try:
                     two = dec.decode(syn, prior, max_iter, variant, flags=_lib.FLAG_FORCE_FULL, **kw)
@@ -153,6 +164,7 @@ def test_first_check_step_table_changes_nothing(name):
     assert dec.info("kernel_kind") == 1
     p = 0.04
     syn = ((rng.random((5000, n)) < p).astype(np.int64) @ H.T % 2).astype(np.uint8)
+    other = _other_batch(syn)
     priors = [np.full(n, np.log((1 - p) / p)),
               np.log((1 - p) / p) * rng.uniform(0.2, 2.0, n),
               np.where(rng.random(n) < 0.1, rng.choice([0.0, -1.5, np.inf, -np.inf], n), 3.0)]
@@ -162,6 +174,7 @@ def test_first_check_step_table_changes_nothing(name):
             for max_iter in (1, 4, 30):
                 with_table = dec.decode(syn, prior, max_iter, variant, **kw)
                 mc_a = dec.mc_run(Lx, dist, p, prior, 0, 20000, seed=9, max_iter=max_iter, variant=variant, **kw)
+                dec.decode(other, prior, max_iter, variant, **kw)              # (see _other_batch)
                 dec.set_option(_lib.OPT_NO_FIRST_STEP_TABLE, 1)
                 try:
                     without = dec.decode(syn, prior, max_iter, variant, **kw)
@@ -251,20 +264,27 @@ def test_general_kernel_equals_fused_kernel_bitwise(name):
     rng = np.random.default_rng(21)
     p = 0.06
     syn = ((rng.random((700, code.n)) < p).astype(np.uint8) @ code.Hx.T % 2).astype(np.uint8)
+    other = _other_batch(syn)
     prior = np.log((1 - p) / p) * rng.uniform(0.8, 1.2, code.n)
     dec = bp.decoder_for(code.Hx)
     for variant, kw in ((_lib.SUM_PRODUCT, {}), (_lib.MIN_SUM, dict(alpha=0.8, damping=0.7, clip_llr=25.0)),
                         (_lib.DAMPED_SP, dict(alpha=0.9, damping=0.8, clip_llr=20.0))):
+        def scramble():                                         # (see _other_batch; whichever kernel is selected)
+            dec.decode(other, prior, 40, variant, **kw)
         dec.set_option(_lib.OPT_FORCE_GENERIC, 0)
         a = dec.decode(syn, prior, 40, variant, **kw)
+        scramble()
         dec.set_option(_lib.OPT_FORCE_GENERIC, 1)
         assert dec.info("kernel_kind") == 2
         b = dec.decode(syn, prior, 40, variant, **kw)
+        scramble()
         c = dec.decode(syn, prior, 40, variant, flags=_lib.FLAG_FORCE_FULL, **kw)
+        scramble()
         dec.set_option(_lib.OPT_FORCE_GENERIC, 0)
         dec.set_option(_lib.OPT_KERNEL, _lib.KERNEL_STREAM)     # lane per syndrome, messages in HBM
         assert dec.info("kernel_kind") == 3
         d = dec.decode(syn, prior, 40, variant, **kw)
+        scramble()
         e = dec.decode(syn, prior, 40, variant, flags=_lib.FLAG_FORCE_FULL, **kw)
         dec.set_option(_lib.OPT_KERNEL, _lib.KERNEL_AUTO)
         for x, y, z, u, w in zip(a, b, c, d, e):
