@@ -90,7 +90,11 @@ enum {
                                  of equal weight, columns of at most 3 entries), else QBP_E_UNSUPPORTED. */
     QBP_FLAG_OSD_CS = 64u,    /* order-w OSD, combination sweep (qbp_osd_batch below); order: QBP_OSD_ORDER_FLAGS.
                                  With qbp_mc_run* only together with QBP_FLAG_OSD0 */
-    QBP_FLAG_OSD_E = 128u     /* order-w OSD, exhaustive over the w least reliable non-pivot columns (same rules) */
+    QBP_FLAG_OSD_E = 128u,    /* order-w OSD, exhaustive over the w least reliable non-pivot columns (same rules) */
+    QBP_FLAG_OSD_LARGE = 256u /* order-w OSD also on matrices beyond the one-wavefront kernel: up to 8192 rows, on a
+                                 workgroup-per-record kernel (osd_order_blocked_kernel).  Only with QBP_FLAG_OSD_CS or
+                                 QBP_FLAG_OSD_E (else QBP_E_INVALID); same results, rule for rule.  On a matrix the
+                                 one-wavefront kernel takes it changes nothing */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -204,8 +208,9 @@ int qbp_message_histograms(qbp_handle* h, const uint8_t* syndromes, const uint8_
  * OSD kernel, whose matrix copy lives in global memory).  With QBP_FLAG_OSD0 a call keeps per-trial
  * records (m + 10 n bytes each): at most QBP_MC_OSD_MAX_TRIALS trials and 16 GiB per call.
  * QBP_FLAG_OSD0 | QBP_FLAG_OSD_CS (or _E) | QBP_OSD_ORDER_FLAGS(w): order-w OSD (qbp_osd_batch) instead of OSD-0,
- * on matrices the one-wavefront OSD kernel takes (else QBP_E_UNSUPPORTED).  QBP_E_INVALID: a method bit without
- * QBP_FLAG_OSD0, both method bits, order bits without a method bit, an order out of range.
+ * on matrices the one-wavefront OSD kernel takes; with | QBP_FLAG_OSD_LARGE also on every matrix of up to 8192 rows
+ * that OSD-0 runs eight pivots at a time on (else QBP_E_UNSUPPORTED).  QBP_E_INVALID: a method bit without
+ * QBP_FLAG_OSD0, both method bits, order bits or QBP_FLAG_OSD_LARGE without a method bit, an order out of range.
  */
 #define QBP_NUM_COUNTERS 12
 int qbp_mc_run(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, double p,
@@ -259,8 +264,13 @@ int qbp_osd0_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const doubl
  *   6. cost(x) = sum of fabs(llr_i) over x_i = 1, added in ascending column index from +0.0 in double;
  *   7. the result is the first candidate of least cost; an OSD-0 cost of NaN returns OSD-0, NaN costs never win;
  *   8. a syndrome outside the column space of H returns the OSD-0 output, without a search.
- * Order > 0 on matrices the one-wavefront OSD kernel takes (every code of codes/), else QBP_E_UNSUPPORTED;
- * QBP_E_INVALID for any other bit or an order out of range (CS 1..64, E 1..12: at most 4095 flip sets).
+ * Order > 0 on matrices the one-wavefront order-w kernel takes (every code of codes/), else QBP_E_UNSUPPORTED -- unless
+ * QBP_FLAG_OSD_LARGE is set: then every other matrix of up to 8192 rows runs on the workgroup-per-record kernel
+ * (space-time and detector-error-model matrices; eight pivots at a time, working copy in global memory), also where
+ * OSD-0 itself still fits one wavefront, and QBP_E_UNSUPPORTED is left only beyond those (more than 8192 rows,
+ * QBP_OPT_OSD_BIG = 2).  Same eight rules, same bits.
+ * QBP_E_INVALID for any other bit, QBP_FLAG_OSD_LARGE without a method bit, or an order out of range (CS 1..64,
+ * E 1..12: at most 4095 flip sets).
  */
 int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr,
                   const uint8_t* hard, int64_t B, uint8_t* solution);
@@ -445,11 +455,13 @@ enum {
                                          its messages, which depend on the priors and the syndrome bit only; A/B, tests) */
     QBP_OPT_FORCED_TWO_BARRIERS = 11, /* 1 = QBP_FLAG_FORCE_FULL launches keep both barriers of the iteration
                                          (default: one barrier, two copies of the messages in LDS; A/B, tests) */
-    QBP_OPT_OSD_BIG = 7,         /* tests: OSD-0 through a workgroup-per-syndrome kernel (matrix in global memory) even
+    QBP_OPT_OSD_BIG = 7,         /* tests: OSD through a workgroup-per-syndrome kernel (matrix in global memory) even
                                     where the one-wavefront kernel fits.  1 = the kernel such matrices get (eight
                                     pivots at a time up to 8192 rows), 2 = the one-pivot-at-a-time kernel (larger
                                     matrices), 3 = as 1 with a first sweep over too few sorted columns, so that
-                                    the full-width second sweep runs */
+                                    the full-width second sweep runs.  Order w: only with QBP_FLAG_OSD_LARGE and
+                                    values 1 or 3, which are one path there (osd_order_blocked_kernel always sweeps
+                                    the full width); 2 is QBP_E_UNSUPPORTED */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */

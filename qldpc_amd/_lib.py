@@ -26,6 +26,7 @@ FLAG_DENSE_F_COLSUM_ITER0 = 16   # ... at iteration 0 only (damped variants, F-o
 FLAG_FAST_MATH = 32          # opt-in: round 2's tanh / arctanh approximations on the on-chip kernel (include/qbp.h)
 FLAG_OSD_CS = 64             # order-w OSD, combination sweep (qbp_osd_batch; with FLAG_OSD0 in qbp_mc_run)
 FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable non-pivot columns
+FLAG_OSD_LARGE = 256         # order-w OSD also on matrices beyond the one-wavefront kernel (up to 8192 rows)
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -110,10 +111,11 @@ SIGNATURES = {
 }
 
 
-def osd_flags(method="cs", order=0):
+def osd_flags(method="cs", order=0, large=False):
     """Flags of an OSD pass: order 0 -> ``FLAG_OSD0`` (OSD-0); order w >= 1 -> ``FLAG_OSD0 | FLAG_OSD_CS`` (method
     "cs", 1 <= w <= 64) or ``| FLAG_OSD_E`` ("e", 1 <= w <= 12) with the order in bits 16..23.  The same value
-    serves ``Decoder.osd`` and the Monte-Carlo calls.  Raises ValueError for anything else."""
+    serves ``Decoder.osd`` and the Monte-Carlo calls.  ``large``: ``| FLAG_OSD_LARGE``, order w >= 1 also on
+    matrices beyond the one-wavefront OSD kernel; with order 0 a ValueError.  Raises ValueError for anything else."""
     m = str(method).lower()
     if m not in OSD_MAX_ORDER:
         raise ValueError(f"OSD method must be 'cs' or 'e', got {method!r}")
@@ -121,10 +123,13 @@ def osd_flags(method="cs", order=0):
         raise ValueError(f"OSD order must be an integer, got {order!r}")
     w = int(order)
     if w == 0:
+        if large:
+            raise ValueError("large=True needs an OSD order >= 1 (OSD-0 runs on every matrix)")
         return FLAG_OSD0
     if not 1 <= w <= OSD_MAX_ORDER[m]:
         raise ValueError(f"OSD-{m.upper()} order must be in [0, {OSD_MAX_ORDER[m]}], got {w}")
-    return FLAG_OSD0 | (FLAG_OSD_CS if m == "cs" else FLAG_OSD_E) | (w << OSD_ORDER_SHIFT)
+    return (FLAG_OSD0 | (FLAG_OSD_CS if m == "cs" else FLAG_OSD_E) | (w << OSD_ORDER_SHIFT)
+            | (FLAG_OSD_LARGE if large else 0))
 
 
 def check_budgets(budgets):
@@ -590,11 +595,12 @@ class Decoder:
                                             stream or None))
 
     @_locked
-    def osd(self, syndromes, llr, hard, method="cs", order=7, column_order=None):
+    def osd(self, syndromes, llr, hard, method="cs", order=7, column_order=None, large=False):
         """Order-w OSD (include/qbp.h, qbp_osd_batch) on B decoder outputs (host arrays) -> solution
         uint8[B, n]; order 0 is OSD-0.  ``column_order`` int[B, n]: every record's columns from the least reliable
-        on, a permutation of 0..n-1 per row (qbp_osd_batch_ordered); None: sorted by (|llr|, column)."""
-        fl = osd_flags(method, order)
+        on, a permutation of 0..n-1 per row (qbp_osd_batch_ordered); None: sorted by (|llr|, column).  ``large``:
+        FLAG_OSD_LARGE, order >= 1 also on matrices beyond the one-wavefront kernel."""
+        fl = osd_flags(method, order, large)
         syn = np.ascontiguousarray(syndromes, np.uint8)
         l = np.ascontiguousarray(llr, np.float64)
         hd = np.ascontiguousarray(hard, np.uint8)
@@ -617,14 +623,15 @@ class Decoder:
                                             co.ctypes.data, syn.shape[0], sol.ctypes.data))
         return sol
 
-    def osd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, method="cs", order=7, stream=0, d_order=0):
+    def osd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, method="cs", order=7, stream=0, d_order=0,
+                   large=False):
         """Order-w OSD on device buffers (pointers as ints), enqueued on `stream`.  ``d_order``: int32[B, n] column
         orders on the device (qbp_osd_batch_ordered_device: not validated there), 0: sorted by (|llr|, column)."""
         if d_order:
-            _check(load().qbp_osd_batch_ordered_device(self._h, osd_flags(method, order), d_syndromes, d_llr, d_hard,
+            _check(load().qbp_osd_batch_ordered_device(self._h, osd_flags(method, order, large), d_syndromes, d_llr, d_hard,
                                                        d_order, int(B), d_solution, stream or None))
             return
-        _check(load().qbp_osd_batch_device(self._h, osd_flags(method, order), d_syndromes, d_llr, d_hard, int(B),
+        _check(load().qbp_osd_batch_device(self._h, osd_flags(method, order, large), d_syndromes, d_llr, d_hard, int(B),
                                            d_solution, stream or None))
 
     @_locked

@@ -16,6 +16,7 @@
 #include "qbp_kernels.hpp"
 #include "qbp_osd.hpp"
 #include "qbp_osd_order.hpp"
+#include "qbp_osd_order_big.hpp"
 #include "qbp_generic.hpp"
 #include "qbp_stream.hpp"
 #include "qbp_hist.hpp"
@@ -174,6 +175,7 @@ struct qbp_handle {
     int osd_W = 0, osd_NP = 0, osd_lds = 0, osd_rank = 0;
     DevBuf<uint32_t> d_osd_At;
     DevBuf<int32_t> d_osd_piv, d_osd_idx, d_osd_posn;
+    DevBuf<int32_t> d_osd_tk;       // osd_order_blocked_kernel: non-pivot columns (and its spilled column table)
     DevBuf<unsigned long long> d_osd_next;   // work counter of osd0_blocked_kernel
     DevBuf<long long> d_osd_redo;   // [0]: count, [1..]: records whose OSD sweep found the syndrome inconsistent
     DevBuf<uint8_t> d_osd_sol;
@@ -1449,16 +1451,50 @@ static int osd_launch_swaps(qbp_handle* h, const qbp::OsdParams& O, long long ma
 // (qbp_osd_batch) nothing but the OSD bits may be set.
 constexpr uint32_t OSD_ORDER_BITS = 0xffu << 16;
 constexpr uint32_t OSD_METHOD_BITS = QBP_FLAG_OSD_CS | QBP_FLAG_OSD_E;
+constexpr uint32_t OSD_ALL_BITS = OSD_ORDER_BITS | OSD_METHOD_BITS | QBP_FLAG_OSD_LARGE;   // what only the OSD launch sees
+
+// Whether, and with which LDS layout, the eight-pivots-at-a-time kernels take the matrix (qbp_osd.hpp,
+// osd0_blocked_kernel; qbp_osd_order_big.hpp): up to 8192 rows, unless QBP_OPT_OSD_BIG = 2.  osd_launch uses them
+// where the one-wavefront kernels do not apply.
+struct OsdBlockedPlan {
+    bool ok;
+    int keys_in_lds;
+    size_t wc_max, want_table, region0, qs, act, lds;
+};
+static OsdBlockedPlan osd_blocked_plan(const qbp_handle* h)
+{
+    OsdBlockedPlan B{};
+    const size_t m = h->m, n = h->n, NP = (size_t)h->osd_NP;
+    B.wc_max = (n + 63) / 64 + 1;
+    const size_t LDS_MAX = 160 * 1024 - 64;                          // (static __shared__ of the kernels: 64 bytes)
+    B.qs = 8 * B.wc_max * 8;
+    B.act = m * 4;                                                   // (row, D) list of a block's updates
+    B.want_table = std::min<size_t>(96 * 1024, 256 * B.wc_max * 8);
+    B.region0 = std::max(B.want_table, NP * 8);
+    B.lds = B.region0 + B.qs + NP * 4 + ((n + 15) & ~(size_t)15) + B.act;
+    B.keys_in_lds = 1;
+    if (B.lds > LDS_MAX) { B.keys_in_lds = 0; B.region0 = B.want_table; B.lds = B.region0 + B.qs + B.act; }
+    B.ok = h->opt_osd_big != 2 && m <= 8192 && B.lds <= LDS_MAX && 2 * B.wc_max * 8 <= B.want_table;
+    return B;
+}
+
+// Order w on the one-wavefront kernel: OSD-0 runs there and osd_order_kernel's added LDS fits as well.
+static bool osd_order_one_wave(const qbp_handle* h)
+{
+    return h->osd_ok && qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) <= 64 * 1024;
+}
 
 static int parse_osd_flags(const qbp_handle* h, uint32_t flags, bool mc, int* method, int* order)
 {
     *method = 0;
     *order = (int)((flags & OSD_ORDER_BITS) >> 16);
     const uint32_t mb = flags & OSD_METHOD_BITS;
-    if (!mc && (flags & ~(OSD_ORDER_BITS | OSD_METHOD_BITS | QBP_FLAG_OSD0)))
+    if (!mc && (flags & ~(OSD_ALL_BITS | QBP_FLAG_OSD0)))
         return fail(QBP_E_INVALID, "osd_flags 0x%x: unknown bits", flags);
     if (mb == OSD_METHOD_BITS) return fail(QBP_E_INVALID, "QBP_FLAG_OSD_CS and QBP_FLAG_OSD_E together");
     if (!mb) {
+        if (flags & QBP_FLAG_OSD_LARGE)
+            return fail(QBP_E_INVALID, "QBP_FLAG_OSD_LARGE without QBP_FLAG_OSD_CS or QBP_FLAG_OSD_E");
         if (*order) return fail(QBP_E_INVALID, "an OSD order (%d) without QBP_FLAG_OSD_CS or QBP_FLAG_OSD_E", *order);
         return QBP_OK;
     }
@@ -1468,11 +1504,16 @@ static int parse_osd_flags(const qbp_handle* h, uint32_t flags, bool mc, int* me
     if (*order < 1 || *order > hi)
         return fail(QBP_E_INVALID, "OSD-%s order %d out of [1, %d]", *method == qbp::OSD_METHOD_CS ? "CS" : "E",
                     *order, hi);
-    // order > 0 runs on the one-wavefront kernel only, with its added LDS
-    if (!h->osd_ok || qbp::osd_order_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) > 64 * 1024)
-        return fail(QBP_E_UNSUPPORTED, "OSD of order > 0 needs a matrix whose rows fit the LDS of one wavefront "
-                                       "(%d x %d does not)", h->m, h->n);
-    return QBP_OK;
+    // order > 0 runs on the one-wavefront kernel where its added LDS fits -- and, with QBP_FLAG_OSD_LARGE, wherever
+    // the blocked kernel's conditions hold (osd_launch sends it there)
+    if (osd_order_one_wave(h)) return QBP_OK;
+    if (flags & QBP_FLAG_OSD_LARGE) {
+        if (osd_blocked_plan(h).ok) return QBP_OK;
+        return fail(QBP_E_UNSUPPORTED, "OSD of order > 0 with QBP_FLAG_OSD_LARGE needs a matrix the blocked OSD kernel "
+                                       "takes (%d x %d: beyond 8192 rows or its LDS, or QBP_OPT_OSD_BIG = 2)", h->m, h->n);
+    }
+    return fail(QBP_E_UNSUPPORTED, "OSD of order > 0 needs a matrix whose rows fit the LDS of one wavefront "
+                                   "(%d x %d does not), or QBP_FLAG_OSD_LARGE", h->m, h->n);
 }
 
 // O.order (qbp_osd_batch_ordered; null everywhere else): the column orders of the records, for the same choice of
@@ -1491,15 +1532,12 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
     const size_t m = h->m, n = h->n, NP = (size_t)h->osd_NP;
     // -- matrices beyond the LDS limit: eight pivots at a time (qbp_osd.hpp, osd0_blocked_kernel)
     qbp::OsdBigWorkspace Wk{};
-    const size_t wc_max = (n + 63) / 64 + 1;
-    const size_t LDS_MAX = 160 * 1024 - 64;                          // (static __shared__ of the kernel: 64 bytes)
-    const size_t qs = 8 * wc_max * 8;
-    const size_t act = m * 4;                                        // (row, D) list of a block's updates
-    const size_t want_table = std::min<size_t>(96 * 1024, 256 * wc_max * 8);
-    size_t region0 = std::max(want_table, NP * 8), lds = region0 + qs + NP * 4 + ((n + 15) & ~(size_t)15) + act;
-    Wk.keys_in_lds = 1;
-    if (lds > LDS_MAX) { Wk.keys_in_lds = 0; region0 = want_table; lds = region0 + qs + act; }
-    const bool blocked = !h->osd_ok && h->opt_osd_big != 2 && m <= 8192 && lds <= LDS_MAX && 2 * wc_max * 8 <= want_table;
+    const OsdBlockedPlan B = osd_blocked_plan(h);
+    const size_t wc_max = B.wc_max, want_table = B.want_table, region0 = B.region0, lds = B.lds, act = B.act;
+    Wk.keys_in_lds = B.keys_in_lds;
+    // (order w on a matrix OSD-0's one-wavefront kernel takes but osd_order_kernel's LDS does not fit: parse_osd_flags
+    // let it pass for QBP_FLAG_OSD_LARGE alone, and the blocked order kernel serves it)
+    const bool blocked = B.ok && (!h->osd_ok || (method && !osd_order_one_wave(h)));
     if (!h->osd_ok && !blocked) return osd_launch_swaps(h, O, max_items, s);
     if (redo) {
         HIP_TRY(h->d_osd_redo.reserve((size_t)max_items + 1));
@@ -1526,9 +1564,24 @@ static int osd_launch(qbp_handle* h, qbp::OsdParams& O, long long max_items, hip
         }
         Wk.At = h->d_osd_At.p; Wk.sol = h->d_osd_sol.p; Wk.keys = h->d_osd_keys.p; Wk.idx = h->d_osd_idx.p;
         const int rpt = m <= 1024 ? 1 : m <= 2048 ? 2 : m <= 4096 ? 4 : 8;
-        HIP_TRY((O.order ? qbp::launch_osd_blocked_ordered : O.shots ? qbp::launch_osd_blocked_shots
-                 : O.spectrum ? qbp::launch_osd_blocked_spectrum : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O, Wk,
-                                                                                            s));
+        if (method) {
+            // order w (parse_osd_flags has seen QBP_FLAG_OSD_LARGE): qbp_osd_order_big.hpp.  Its per-column table
+            // (12 n bytes) overlays the LDS the sweep is done with, or goes to the workspace
+            qbp::OsdOrderBigArgs X{};
+            X.method = method; X.order = order;
+            // (with the keys in LDS, region 0 and Qs hold 12 n bytes: n <= 8192 there and want_table >= min(96 KiB, 32 n))
+            X.spill = !Wk.keys_in_lds;
+            if (X.spill) { HIP_TRY(h->d_osd_keys.reserve((size_t)grid * NP)); }
+            HIP_TRY(h->d_osd_tk.reserve((size_t)grid * 2 * n));
+            Wk.keys = h->d_osd_keys.p; X.tk = h->d_osd_tk.p;
+            HIP_TRY((O.order ? qbp::launch_osd_order_blocked_ordered : O.shots ? qbp::launch_osd_order_blocked_shots
+                     : O.spectrum ? qbp::launch_osd_order_blocked_spectrum : qbp::launch_osd_order_blocked)(
+                rpt, (unsigned)grid, lds, O, Wk, X, s));
+        } else {
+            HIP_TRY((O.order ? qbp::launch_osd_blocked_ordered : O.shots ? qbp::launch_osd_blocked_shots
+                     : O.spectrum ? qbp::launch_osd_blocked_spectrum : qbp::launch_osd_blocked)(rpt, (unsigned)grid, lds, O,
+                                                                                                Wk, s));
+        }
     } else if (method) {
         // order w (parse_osd_flags has checked osd_ok and the LDS)
         const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * 32));
@@ -1701,7 +1754,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     int osd_method = 0, osd_order = 0;
     rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order);
     if (rc) return rc;
-    flags &= ~(OSD_ORDER_BITS | OSD_METHOD_BITS);
+    flags &= ~OSD_ALL_BITS;
     if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
     if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", draws);
     if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", p);
@@ -2132,7 +2185,7 @@ static int decode_shots_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, c
                              int osd_method, int osd_order, uint64_t* d_predictions, uint8_t* d_converged,
                              int64_t* d_counters, hipStream_t s)
 {
-    flags &= ~(OSD_ORDER_BITS | OSD_METHOD_BITS);
+    flags &= ~OSD_ALL_BITS;
     BpCall c;
     int rc = resolve_column_order(h, flags, nullptr, &c.col_mode);      // the column-sum bits of qbp_decode_batch
     if (rc) return rc;

@@ -15,6 +15,7 @@ struct GenericParams;
 struct StreamParams;
 struct OsdParams;
 struct OsdBigWorkspace;
+struct OsdOrderBigArgs;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -105,6 +106,16 @@ hipError_t launch_osd_big_ordered(unsigned grid, size_t lds, const OsdParams& O,
                                   hipStream_t s);
 hipError_t launch_osd_blocked_ordered(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                                       const OsdBigWorkspace& Wk, hipStream_t s);
+// order w on the matrices the blocked kernel serves (qbp_osd_order_big.hpp, QBP_FLAG_OSD_LARGE): one per build of
+// qbp_tu_osd.hip
+hipError_t launch_osd_order_blocked(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                    const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
+hipError_t launch_osd_order_blocked_spectrum(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                             const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
+hipError_t launch_osd_order_blocked_shots(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                          const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
+hipError_t launch_osd_order_blocked_ordered(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                            const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

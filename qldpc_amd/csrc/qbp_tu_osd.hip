@@ -1,10 +1,11 @@
-// libqbp.so, translation unit of the OSD kernels (qbp_osd.hpp: OSD-0, qbp_osd_order.hpp: order w) and the
+// libqbp.so, translation unit of the OSD kernels (qbp_osd.hpp: OSD-0, qbp_osd_order.hpp and qbp_osd_order_big.hpp:
+// order w) and the
 // histogram kernels (qbp_hist.hpp).
-// With -DQBP_SPECTRUM_TU: the four OSD kernels that classify once more, under other names, adding the residual weight
+// With -DQBP_SPECTRUM_TU: the OSD kernels that classify once more, under other names, adding the residual weight
 // of every record to a table (qbp_mc_run_spectrum); no histogram kernels in that unit.
-// With -DQBP_SHOTS_TU: the four once more, whose records are recorded shots: they store the observable prediction of
+// With -DQBP_SHOTS_TU: all of them once more, whose records are recorded shots: they store the observable prediction of
 // every record and compare it with the recorded observables (qbp_decode_shots); no histogram kernels either.
-// With -DQBP_ORDERED_TU: the four once more, which take the column order of every record from the caller instead of
+// With -DQBP_ORDERED_TU: all of them once more, which take the column order of every record from the caller instead of
 // sorting (qbp_osd_batch_ordered); no histogram kernels either.
 #define QBP_DEFINE_KERNELS 1
 #ifdef QBP_ORDERED_TU
@@ -14,10 +15,12 @@
 #define osd0_big_kernel osd0_big_ordered_kernel
 #define osd0_blocked_kernel osd0_blocked_ordered_kernel
 #define osd_order_kernel osd_order_ordered_kernel
+#define osd_order_blocked_kernel osd_order_blocked_ordered_kernel
 #define launch_osd_small launch_osd_small_ordered
 #define launch_osd_order launch_osd_order_ordered
 #define launch_osd_big launch_osd_big_ordered
 #define launch_osd_blocked launch_osd_blocked_ordered
+#define launch_osd_order_blocked launch_osd_order_blocked_ordered
 #endif
 #ifdef QBP_SHOTS_TU
 #define QBP_OSD_SHOTS 1
@@ -26,10 +29,12 @@
 #define osd0_big_kernel osd0_big_shots_kernel
 #define osd0_blocked_kernel osd0_blocked_shots_kernel
 #define osd_order_kernel osd_order_shots_kernel
+#define osd_order_blocked_kernel osd_order_blocked_shots_kernel
 #define launch_osd_small launch_osd_small_shots
 #define launch_osd_order launch_osd_order_shots
 #define launch_osd_big launch_osd_big_shots
 #define launch_osd_blocked launch_osd_blocked_shots
+#define launch_osd_order_blocked launch_osd_order_blocked_shots
 #endif
 #ifdef QBP_SPECTRUM_TU
 #define QBP_OSD_SPECTRUM 1
@@ -38,10 +43,12 @@
 #define osd0_big_kernel osd0_big_spectrum_kernel
 #define osd0_blocked_kernel osd0_blocked_spectrum_kernel
 #define osd_order_kernel osd_order_spectrum_kernel
+#define osd_order_blocked_kernel osd_order_blocked_spectrum_kernel
 #define launch_osd_small launch_osd_small_spectrum
 #define launch_osd_order launch_osd_order_spectrum
 #define launch_osd_big launch_osd_big_spectrum
 #define launch_osd_blocked launch_osd_blocked_spectrum
+#define launch_osd_order_blocked launch_osd_order_blocked_spectrum
 #endif
 #include <hip/hip_runtime.h>
 
@@ -52,6 +59,7 @@
 #include "qbp_launch.hpp"
 #include "qbp_osd.hpp"
 #include "qbp_osd_order.hpp"
+#include "qbp_osd_order_big.hpp"
 
 namespace qbp {
 
@@ -124,6 +132,36 @@ hipError_t launch_osd_blocked(int rows_per_thread, unsigned grid, size_t lds, co
         case 2: return launch_osd_blocked_rpt<2>(grid, lds, O, Wk, s);
         case 4: return launch_osd_blocked_rpt<4>(grid, lds, O, Wk, s);
         case 8: return launch_osd_blocked_rpt<8>(grid, lds, O, Wk, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+template <int RPT>
+static hipError_t launch_osd_order_blocked_rpt(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk,
+                                               const OsdOrderBigArgs& X, hipStream_t s)
+{
+    static thread_local size_t lds_set[64] = {0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(osd_order_blocked_kernel<RPT>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
+    }
+    hipLaunchKernelGGL(osd_order_blocked_kernel<RPT>, dim3(grid), dim3(1024), lds, s, O, Wk, X);
+    return hipGetLastError();
+}
+
+// order w on the blocked kernel's matrices; rows per thread as launch_osd_blocked
+hipError_t launch_osd_order_blocked(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
+                                    const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s)
+{
+    switch (rows_per_thread) {
+        case 1: return launch_osd_order_blocked_rpt<1>(grid, lds, O, Wk, X, s);
+        case 2: return launch_osd_order_blocked_rpt<2>(grid, lds, O, Wk, X, s);
+        case 4: return launch_osd_order_blocked_rpt<4>(grid, lds, O, Wk, X, s);
+        case 8: return launch_osd_order_blocked_rpt<8>(grid, lds, O, Wk, X, s);
         default: return hipErrorInvalidValue;
     }
 }

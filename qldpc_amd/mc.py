@@ -54,10 +54,11 @@ def summarize(counters: np.ndarray) -> dict:
     return c
 
 
-def osd_run_flags(osd, osd_method="cs", osd_order=0) -> int:
+def osd_run_flags(osd, osd_method="cs", osd_order=0, osd_large=False) -> int:
     """Flags of the OSD pass of a sweep: 0 without OSD, FLAG_OSD0 for OSD-0 (order 0), else order-w OSD
-    (``_lib.osd_flags``).  ValueError for an order without ``osd`` or a method / order out of range."""
-    fl = _lib.osd_flags(osd_method, osd_order)          # (validates method and order)
+    (``_lib.osd_flags``; ``osd_large``: FLAG_OSD_LARGE, order w also on matrices beyond the one-wavefront OSD
+    kernel).  ValueError for an order without ``osd``, ``osd_large`` with order 0 or a method / order out of range."""
+    fl = _lib.osd_flags(osd_method, osd_order, osd_large)   # (validates method, order and osd_large)
     if not osd:
         if int(osd_order) != 0:
             raise ValueError(f"an OSD order ({osd_order}) needs osd=True")
@@ -66,15 +67,15 @@ def osd_run_flags(osd, osd_method="cs", osd_order=0) -> int:
 
 
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
-              alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1,
-              device=0, runner=None, all_reduce=None):
+              alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
+              world=1, device=0, runner=None, all_reduce=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
 
     ``osd``: OSD on the trials BP does not converge on -- OSD-0 with ``osd_order`` 0, else order-w OSD by
     ``osd_method`` ("cs" or "e"; include/qbp.h).
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -115,7 +116,7 @@ def dem_prior(probs) -> np.ndarray:
 
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
-            osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+            osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -126,7 +127,7 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
     tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     L = np.ascontiguousarray(L, np.uint8)
     probs = np.ascontiguousarray(probs, np.float64)
     n = H.shape[1]
@@ -164,7 +165,7 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
 
 
 def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
-              damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, flags=0, rank=0, world=1, device=0,
+              damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, flags=0, rank=0, world=1, device=0,
               runner=None, all_reduce=None):
     """Decode RECORDED shots of a detector error model to observable predictions (qbp_decode_shots): the loop of
     studies/studyComplete.py:91-109 on data that was sampled elsewhere (stim's circuit sampler, an experiment).
@@ -183,7 +184,7 @@ def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant
     ``runner(H, L, det_bits, masks, prior, begin, end) -> (int64[12], uint64[end - begin], bool[end - begin])`` and
     ``all_reduce`` are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     from . import shots as shots_mod
-    flags = int(flags) | osd_run_flags(osd, osd_method, osd_order)     # (before any GPU work)
+    flags = int(flags) | osd_run_flags(osd, osd_method, osd_order, osd_large)     # (before any GPU work)
     m, n = H.shape
     rb = (m + 7) // 8
     L = np.ascontiguousarray(L, np.uint8)
@@ -271,7 +272,7 @@ def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, dr
 
 
 def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
-                clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1, device=0, runner=None,
+                clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None,
                 all_reduce=None):
     """One error rate, a ladder of BP iteration limits, ONE pass over the trials (qbp_mc_run_budgets): returns the
     GLOBAL counter table int64[len(budgets), 12] whose row j is the row ``run_sweep(code_name, [p], trials,
@@ -280,7 +281,7 @@ def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.
     ``_lib.MC_MAX_BUDGETS`` strictly ascending integers >= 1.
     ``runner(code, p, budgets, begin, end) -> int64[K, 12]`` and ``all_reduce`` are injection points for the CPU
     tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     budgets = _lib.check_budgets(budgets)
     code = codes.load_code(code_name)
     begin, end = shard_range(int(trials), rank, world)
@@ -296,11 +297,11 @@ def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.
 
 def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, draws=1, seed=0,
                     variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
-                    osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+                    osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None):
     """``run_dem`` over a ladder of BP iteration limits in one pass: GLOBAL int64[len(budgets), 12], row j = the
     counters of ``run_dem(..., max_iter=budgets[j])``.  Arguments as ``run_dem``, budgets as ``run_budgets``;
     ``runner(H, L, probs, prior, budgets, begin, end) -> int64[K, 12]``."""
-    flags = osd_run_flags(osd, osd_method, osd_order)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     budgets = _lib.check_budgets(budgets)
     L = np.ascontiguousarray(L, np.uint8)
     probs = np.ascontiguousarray(probs, np.float64)
@@ -386,7 +387,7 @@ def _check_spectrum_max_iter(max_iter):
 
 
 def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
-                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, rank=0, world=1, device=0,
+                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1, device=0,
                  runner=None, all_reduce=None):
     """``run_sweep`` with a distribution per point (qbp_mc_run_spectrum).  Returns GLOBAL ``(counters int64[points,
     12], weights int64[points, 4, n + 1], iterations int64[points, max_iter + 1])``: the counters are ``run_sweep``'s
@@ -397,7 +398,7 @@ def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant
     like ``run_sweep``; counters and tables are reduced in ONE all-reduce.
     ``runner(code, p, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])`` and ``all_reduce`` are
     injection points for the CPU tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order)   # (before any GPU work)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     max_iter = _check_spectrum_max_iter(max_iter)
     code = codes.load_code(code_name)
     begin, end = shard_range(int(trials), rank, world)
@@ -417,11 +418,11 @@ def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant
 
 def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
                      variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
-                     osd_order=0, rank=0, world=1, device=0, runner=None, all_reduce=None):
+                     osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None):
     """``run_dem`` with the two distributions of ``run_spectrum``: GLOBAL ``(counters int64[1, 12], weights int64[1,
     4, n + 1], iterations int64[1, max_iter + 1])`` -- one point, the model's own probabilities.  Arguments as
     ``run_dem``; ``runner(H, L, probs, prior, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])``."""
-    flags = osd_run_flags(osd, osd_method, osd_order)
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     max_iter = _check_spectrum_max_iter(max_iter)
     L = np.ascontiguousarray(L, np.uint8)
     probs = np.ascontiguousarray(probs, np.float64)
@@ -484,7 +485,7 @@ def rework_point(counters, weights, iterations):
     return point
 
 
-def rework_results(experiment, trials=10000, *, max_iter=100, osd=True, osd_method="cs", osd_order=0, **kwargs):
+def rework_results(experiment, trials=10000, *, max_iter=100, osd=True, osd_method="cs", osd_order=0, osd_large=False, **kwargs):
     """The ``results[name][p]`` dictionary of rework/main.py:50-129.  ``experiment``: that script's list of {"code",
     "name", "physicalErrorRates"} dictionaries.  One ``run_spectrum`` per code (its own sampler, not numpy's stream;
     OSD-0 by default, which is what the reference's ``performOSD_enhanced`` returns on every syndrome that comes from
@@ -494,7 +495,7 @@ def rework_results(experiment, trials=10000, *, max_iter=100, osd=True, osd_meth
     for exp in experiment:
         ps = list(exp["physicalErrorRates"])
         cnt, weights, its = run_spectrum(exp["code"], ps, trials, max_iter=max_iter, osd=osd, osd_method=osd_method,
-                                         osd_order=osd_order, **kwargs)
+                                         osd_order=osd_order, osd_large=osd_large, **kwargs)
         results[exp["name"]] = {p: rework_point(cnt[i], weights[i], its[i]) for i, p in enumerate(ps)}
     return results
 
@@ -538,6 +539,9 @@ def main(argv=None):
                     help="with --osd-order W >= 1: combination sweep or exhaustive search")
     ap.add_argument("--osd-order", type=int, default=0,
                     help="with --osd: order-w OSD instead of OSD-0 (cs: 1..64, e: 1..12)")
+    ap.add_argument("--osd-large", action="store_true",
+                    help="with --osd-order W >= 1: also on matrices beyond the one-wavefront OSD kernel (space-time "
+                         "and detector-error-model matrices of up to 8192 rows)")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a launcher: start N ranks (one per GPU) and reduce over RCCL")
@@ -545,7 +549,7 @@ def main(argv=None):
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank on cuda:0")
     args = ap.parse_args(argv)
     try:
-        osd_run_flags(args.osd, args.osd_method, args.osd_order)
+        osd_run_flags(args.osd, args.osd_method, args.osd_order, args.osd_large)
     except ValueError as e:
         ap.error(str(e))
     if args.budgets is not None:
@@ -619,11 +623,11 @@ def main(argv=None):
                "min-sum": _lib.MIN_SUM}[args.variant]
     common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
                   damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
-                  osd_order=args.osd_order, device=local)
+                  osd_order=args.osd_order, osd_large=args.osd_large, device=local)
     if shot_data is not None:
         H, L, probs = dem_model
         kw = {k: common[k] for k in ("max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",
-                                     "osd_order", "device")}
+                                     "osd_order", "osd_large", "device")}
         t0 = time.perf_counter()
         cnt, pred, conv = run_shots(H, L, shot_data[0], shot_data[1], prior=dem_prior(probs), rank=rank, world=world,
                                     **kw)

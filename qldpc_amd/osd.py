@@ -160,9 +160,10 @@ def performOSD_enhanced(H, syndrome, llr, hard, order=0, max_combinations=None, 
                               "of H: the reference's combinatorial search is not implemented")
 
 
-def performOSD_order(H, syndrome, llr, hard, order, method="cs", *, column_order=None):
+def performOSD_order(H, syndrome, llr, hard, order, method="cs", *, column_order=None, osd_large=False):
     """Order-w OSD of one decoder output on the GPU (include/qbp.h, qbp_osd_batch): int64 vector like
-    ``performOSD``; order 0 is OSD-0."""
+    ``performOSD``; order 0 is OSD-0.  ``osd_large``: order >= 1 also on matrices beyond the one-wavefront kernel
+    (FLAG_OSD_LARGE)."""
     dec = decoder_for(H)
     syn = (np.asarray(syndrome).astype(np.int64) % 2).astype(np.uint8)
     hd = (np.asarray(hard).astype(np.int64) % 2).astype(np.uint8)
@@ -170,8 +171,9 @@ def performOSD_order(H, syndrome, llr, hard, order, method="cs", *, column_order
     if syn.shape != (dec.m,) or hd.shape != (dec.n,) or l.shape != (dec.n,):
         raise ValueError(f"expected syndrome ({dec.m},), llr ({dec.n},), hard ({dec.n},)")
     co = _column_order(column_order, l)
+    kw = {"large": True} if osd_large else {}
     return dec.osd(syn[None, :], l[None, :], hd[None, :], method=method, order=order,
-                   column_order=None if co is None else co[None, :])[0].astype(np.int64)
+                   column_order=None if co is None else co[None, :], **kw)[0].astype(np.int64)
 
 
 def performOSD_order_batch(H, syndromes, llrs, hards, order, method="cs", *, column_order=None):
