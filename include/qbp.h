@@ -403,6 +403,48 @@ int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws
                                int64_t trial_begin, int64_t T, uint8_t* errors);
 
 /*
+ * Monte-Carlo on errors of a FIXED weight: every trial's error is a subset of exactly `weight` of the n columns,
+ * uniform among the C(n, weight) patterns, instead of n Bernoulli draws.  The failure fractions f_w of a few weights
+ * give the logical error rate at every p of uniform noise from one set of runs,
+ * LER(p) = sum_w C(n, w) p^w (1 - p)^(n - w) f_w (qldpc_amd/mc.py: run_weights, ler_from_weights), also where it is
+ * far below 1 / trials of a Bernoulli run; the reference splits its counters by sum(error) < distance // 2 already
+ * (paperResults_GPU.py:140-144).
+ * The sampler is this build's own specification, as the Philox Bernoulli sampler of qbp_mc_run is.  For global trial
+ * index t, weight w, n columns and seed, start with S empty and run Floyd's subset sampling: for i = 0 .. w - 1
+ *   j = n - w + i
+ *   r = word i % 4 of Philox4x32-10(counter = (t lo, t hi, i / 4, 2), key = (seed lo, seed hi))
+ *   u = (uint64(r) * (j + 1)) >> 32
+ *   add j to S if u is already in S, else add u.
+ * Counter word 3 is 2: the Bernoulli samplers use 0 and 1 there for their draws, so the streams never coincide.
+ * errors[t][v] = 1 iff v in S.  The rows are exactly weight w; they are uniform over subsets up to the multiply-shift
+ * bias, at most (j + 1) / 2^32 per step; and they are independent of how [trial_begin, trial_end) is split over calls,
+ * chunks or GPUs (tests/weight_oracle.py restates the sampler in numpy).
+ * Two stages: a chunk of trials is sampled into a device buffer the handle owns (mc_sample_weight_kernel, one lane per
+ * trial), then decoded and classified by the pipeline of qbp_mc_run_errors -- no BP or OSD kernel is built for this.
+ * A chunk is QBP_OPT_MC_WEIGHT_CHUNK trials; the default (option 0) is 2^28 / n trials, at least 1 and at most 2^20:
+ * a buffer of at most 256 MiB.  The result does not depend on the chunk.
+ * counters (ADDED to), flags, OSD bits, the QBP_MC_OSD_MAX_TRIALS rule (for the whole call, not per chunk) and the
+ * QBP_E_UNSUPPORTED cases are those of qbp_mc_run.  prior [n] is an input, as there, and fixes the decoder the f_w
+ * are measured for; `ew < distance / 2` ([3] against [4]) is evaluated with the actual weight.
+ * QBP_E_INVALID, before any GPU work and with the counters untouched: weight < 0 or weight > n, a null prior or
+ * counters, trial_begin < 0, trial_end < trial_begin, and whatever qbp_mc_run refuses.
+ */
+int qbp_mc_run_weight(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, int32_t weight, uint64_t seed,
+                      int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                      int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                      int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form (as qbp_mc_run_device): d_prior and d_counters (ADDED to) are device pointers; Lx stays a host
+ * pointer.  Every chunk is enqueued on `stream`, in order, on the handle's one buffer. */
+int qbp_mc_run_weight_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, int32_t weight,
+                             uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* d_prior,
+                             int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                             uint32_t flags, int64_t* d_counters, void* stream);
+/* Errors the sampler of qbp_mc_run_weight draws for trials [trial_begin, trial_begin + T): errors [T][n] host
+ * bytes (tests). */
+int qbp_mc_sample_errors_weight(qbp_handle* h, int32_t weight, uint64_t seed, int64_t trial_begin, int64_t T,
+                                uint8_t* errors);
+
+/*
  * Decode T RECORDED shots of a detector error model to observable predictions: the loop of
  * studies/studyComplete.py:91-109 (sampler.sample(shots, separate_observables=True); BP per shot;
  * L_matrix @ prediction % 2 != actual_observables[i]) for data that comes from stim's circuit sampler or from an
@@ -462,6 +504,8 @@ enum {
                                     the full-width second sweep runs.  Order w: only with QBP_FLAG_OSD_LARGE and
                                     values 1 or 3, which are one path there (osd_order_blocked_kernel always sweeps
                                     the full width); 2 is QBP_E_UNSUPPORTED */
+    QBP_OPT_MC_WEIGHT_CHUNK = 14, /* qbp_mc_run_weight*: trials sampled and decoded per chunk (0 = default, see there;
+                                    at most 2^20).  Results do not depend on it (tests force several chunks) */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */

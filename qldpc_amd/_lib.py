@@ -41,6 +41,7 @@ OPT_SLOTS_PER_BLOCK, OPT_BLOCKS_PER_CU, OPT_FORCE_GENERIC, OPT_KERNEL, OPT_GENER
 OPT_FORCED_TWO_BARRIERS = 11
 OPT_NO_FIRST_STEP_TABLE = 12
 OPT_EARLY_EXIT_FULL_WG = 13
+OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per chunk (0 = default)
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
 INFO = dict(m=100, n=101, edges=102, max_row_deg=103, max_col_deg=104, kernel_kind=105,
             threads=106, lds_bytes=107, grid=108, num_cu=109, last_kernel=110, one_barrier=111)
@@ -93,6 +94,12 @@ SIGNATURES = {
     "qbp_decode_shots_device": (C.c_int, [_VP, _VP, C.c_int32, _VP, _VP, C.c_int64, _VP, C.c_int32, C.c_int32,
                                           C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP, _VP]),
     "qbp_mc_sample_errors_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
+    "qbp_mc_run_weight": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int64,
+                                    _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_mc_run_weight_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64,
+                                           C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                           C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_sample_errors_weight": (C.c_int, [_VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
     "qbp_message_histograms": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -372,6 +379,37 @@ class Decoder:
             int(trial_begin), int(trial_end), d_prior, int(max_iter), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_counters, stream or None))
 
+    @_locked
+    def mc_run_weight(self, Lx, distance, weight, prior, trial_begin, trial_end, seed=0, max_iter=50,
+                      variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """``mc_run`` on errors of exactly ``weight`` ones, uniform among the C(n, weight) patterns
+        (qbp_mc_run_weight): counters int64[12] of trials [trial_begin, trial_end)."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        counters = np.zeros(NUM_COUNTERS, np.int64)
+        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        for a in range(int(trial_begin), int(trial_end), step):
+            _check(load().qbp_mc_run_weight(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight),
+                                            int(seed), a, min(a + step, int(trial_end)), pr.ctypes.data,
+                                            int(max_iter), int(variant), float(alpha), float(damping),
+                                            float(clip_llr), int(flags), counters.ctypes.data))
+        return counters
+
+    def mc_run_weight_device(self, Lx, distance, weight, d_prior, trial_begin, trial_end, d_counters, seed=0,
+                             max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
+                             stream=0):
+        """``mc_run_weight`` on device buffers: d_counters int64[12] is added to.  One call: with FLAG_OSD0 the
+        caller splits ranges by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_mc_run_weight_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight), int(seed), int(trial_begin),
+            int(trial_end), d_prior, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr),
+            int(flags), d_counters, stream or None))
+
     def _spectrum_tables(self, max_iter, spectrum, iter_hist):
         """The two tables of the spectrum calls (new zeroed ones, or the caller's, which are added to)."""
         if int(max_iter) < 1:       # (beyond MC_SPECTRUM_MAX_ITER the library answers QBP_E_INVALID)
@@ -647,6 +685,14 @@ class Decoder:
         out = np.empty((int(T), self.n), np.uint8)
         _check(load().qbp_mc_sample_errors_probs(self._h, probs.ctypes.data, int(draws), int(seed),
                                                  int(trial_begin), int(T), out.ctypes.data))
+        return out
+
+    @_locked
+    def mc_sample_errors_weight(self, weight, trial_begin, T, seed=0):
+        """Errors uint8[T, n] the sampler of ``mc_run_weight`` draws for trials trial_begin .. + T (tests)."""
+        out = np.empty((int(T), self.n), np.uint8)
+        _check(load().qbp_mc_sample_errors_weight(self._h, int(weight), int(seed), int(trial_begin), int(T),
+                                                  out.ctypes.data))
         return out
 
     @_locked

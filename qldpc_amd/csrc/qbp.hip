@@ -146,6 +146,8 @@ struct qbp_handle {
     int opt_kernel = 0;             // 0 auto, 1 on-chip, 2 general-H (workgroup per syndrome), 3 streaming
     DevBuf<uint8_t> d_wsS;           // streaming kernel: transposed syndromes; general-H Monte-Carlo: syndromes
     DevBuf<uint8_t> d_wsE;           // general-H Monte-Carlo: sampled errors
+    DevBuf<uint8_t> d_weight_err;    // qbp_mc_run_weight: the fixed-weight errors of one chunk, [chunk][n]
+    long long opt_weight_chunk = 0;  // QBP_OPT_MC_WEIGHT_CHUNK (0 = default)
     DevBuf<int32_t> d_srow, d_srow_e0, d_srow_deg, d_svar, d_sedge;   // weight-class tables
     DevBuf<int32_t> d_epos, d_cpos, d_long_edge_row;
     DevBuf<int32_t> d_vpos, d_vrow, d_lcol_ptr;      // general-H kernel: column-class tables
@@ -1733,6 +1735,19 @@ static int check_budgets(const int32_t* budgets, int32_t n_budgets)
     return QBP_OK;
 }
 
+// With QBP_FLAG_OSD0 a call keeps a record per trial and counter row (m + 10 n bytes each): at most
+// QBP_MC_OSD_MAX_TRIALS records and 16 GiB (host only, before any GPU work)
+static int check_mc_osd_trials(const qbp_handle* h, int64_t T, size_t rows)
+{
+    const size_t t = (size_t)T * rows, m = h->m, n = h->n;
+    if (t > QBP_MC_OSD_MAX_TRIALS || t * (m + 10 * n) > ((size_t)16 << 30))
+        return fail(QBP_E_INVALID, "with QBP_FLAG_OSD0 a call covers at most %lld trials of this matrix "
+                                   "(got %lld); split the range",
+                    (long long)(std::min<size_t>(QBP_MC_OSD_MAX_TRIALS, ((size_t)16 << 30) / (m + 10 * n)) / rows),
+                    (long long)T);
+    return QBP_OK;
+}
+
 // probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null.
 // budgets (checked by the caller; needs probs): qbp_mc_run_budgets -- max_iter is unused, d_counters is
 // [n_budgets][QBP_NUM_COUNTERS]; else null / 0.
@@ -1772,11 +1787,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         // per-trial records of the trials BP leaves unconverged (read by the OSD kernel)
         // (qbp_mc_run_budgets: a record per trial and budget)
         const size_t t = (size_t)T * rows, m = h->m, n = h->n;
-        if (t > QBP_MC_OSD_MAX_TRIALS || t * (m + 10 * n) > ((size_t)16 << 30))
-            return fail(QBP_E_INVALID, "with QBP_FLAG_OSD0 a call covers at most %lld trials of this matrix "
-                                       "(got %lld); split the range",
-                        (long long)(std::min<size_t>(QBP_MC_OSD_MAX_TRIALS, ((size_t)16 << 30) / (m + 10 * n)) / rows),
-                        (long long)T);
+        if ((rc = check_mc_osd_trials(h, T, rows)) != QBP_OK) return rc;
         HIP_TRY(h->d_fail_count.reserve(rows));
         HIP_TRY(h->d_fail_list.reserve(t));
         HIP_TRY(h->d_fail_syn.reserve(t * m));
@@ -1920,6 +1931,102 @@ try {
     // (the sampler does not depend on H: any matrix, whichever kernel decodes it)
     HIP_TRY(h->d_hard.reserve((size_t)T * n));
     HIP_TRY(qbp::launch_mc_sample(h->d_hard.p, h->n, T, trial_begin, draws, seed, mc_threshold(p), s));
+    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// What the fixed-weight calls refuse beyond qbp_mc_run's own checks (host only, before any GPU work)
+static int check_weight(const qbp_handle* h, int32_t weight, int64_t trial_begin)
+{
+    if (weight < 0 || weight > h->n)
+        return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", weight, h->n);
+    if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
+    return QBP_OK;
+}
+
+int qbp_mc_run_weight_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, int32_t weight,
+                             uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* d_prior,
+                             int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                             uint32_t flags, int64_t* d_counters, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!d_prior || !d_counters) return fail(QBP_E_INVALID, "null pointer");
+    int rc = check_weight(h, weight, trial_begin);
+    if (rc) return rc;
+    // everything mc_run_impl refuses, for the WHOLE range and before the first chunk is sampled
+    const int64_t T = trial_end - trial_begin;
+    if ((rc = check_decode_args(h, T, max_iter, variant)) != QBP_OK) return rc;
+    int osd_method = 0, osd_order = 0;
+    if ((rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order)) != QBP_OK) return rc;
+    if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
+    if (k > 0 && !Lx_host) return fail(QBP_E_INVALID, "Lx is null");
+    if ((flags & QBP_FLAG_OSD0) && (rc = check_mc_osd_trials(h, T, 1)) != QBP_OK) return rc;
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t n = (size_t)h->n;
+    const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)n));
+    const long long chunk = std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
+    HIP_TRY(h->d_weight_err.reserve((size_t)chunk * n));
+    for (int64_t a = trial_begin; a < trial_end; a += chunk) {
+        const long long t = std::min<long long>(chunk, trial_end - a);
+        // the global trial index lives in the sampler only: the pipeline indexes its stored errors from 0
+        HIP_TRY(qbp::launch_mc_sample_weight(h->d_weight_err.p, h->n, weight, t, a, seed, s));
+        rc = mc_run_impl(h, Lx_host, k, distance, 0.0, nullptr, 1, 0, 0, t, h->d_weight_err.p, d_prior, max_iter,
+                         variant, alpha, damping, clip_llr, flags, d_counters, s);
+        if (rc) return rc;
+    }
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_weight(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, int32_t weight, uint64_t seed,
+                      int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                      int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                      int64_t counters[QBP_NUM_COUNTERS])
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    int rc = check_weight(h, weight, trial_begin);
+    if (rc) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    HIP_TRY(h->d_prior.reserve(h->n));
+    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
+    rc = qbp_mc_run_weight_device(h, Lx, k, distance, weight, seed, trial_begin, trial_end, h->d_prior.p, max_iter,
+                                  variant, alpha, damping, clip_llr, flags,
+                                  reinterpret_cast<int64_t*>(h->d_counters.p), s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    long long tmp[qbp::NUM_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_sample_errors_weight(qbp_handle* h, int32_t weight, uint64_t seed, int64_t trial_begin, int64_t T,
+                                uint8_t* errors)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    if (!errors) return fail(QBP_E_INVALID, "errors is null");
+    const int rc = check_weight(h, weight, trial_begin);
+    if (rc) return rc;
+    if (T == 0) return QBP_OK;
+    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    const size_t n = h->n;
+    HIP_TRY(h->d_hard.reserve((size_t)T * n));
+    HIP_TRY(qbp::launch_mc_sample_weight(h->d_hard.p, h->n, weight, T, trial_begin, seed, s));
     HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return QBP_OK;
@@ -2339,6 +2446,9 @@ try {
         case QBP_OPT_GENERAL_MEM:
             if (value < 0 || value > 2) return fail(QBP_E_INVALID, "memory mode out of range");
             h->opt_mem = (int)value; return QBP_OK;
+        case QBP_OPT_MC_WEIGHT_CHUNK:
+            if (value < 0 || value > (1 << 20)) return fail(QBP_E_INVALID, "trials per chunk out of [0, 2^20]");
+            h->opt_weight_chunk = value; return QBP_OK;
         case QBP_OPT_GENERAL_THREADS:
             if (value < 0 || value > 1024) return fail(QBP_E_INVALID, "threads per workgroup out of range");
             h->opt_threads = (int)value; return QBP_OK;

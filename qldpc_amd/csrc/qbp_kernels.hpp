@@ -918,6 +918,34 @@ __global__ void mc_sample_cols_kernel(uint8_t* errors, int n, long long T, long 
         if (4 * g + k < n) errors[b * n + 4 * g + k] = (uint8_t)((q >> (8 * k)) & 1u);
 }
 
+// The fixed-weight sampler (qbp_mc_run_weight, qbp_mc_sample_errors_weight; specification: include/qbp.h): row b of
+// errors [T][n] becomes a uniform w-subset of the n columns, by Floyd's algorithm on the Philox stream of trial
+// trial_begin + b -- step i draws u in [0, j], j = n - w + i, and takes u, or j when u is taken already (j itself
+// cannot be: every earlier step chose below j).  One lane per trial: the w steps depend on each other, trials do
+// not.  The trial's own row is the membership map, so any n works without LDS or an indexed register array; it has
+// to be ZERO on entry (launch_mc_sample_weight clears it on the same stream).  The inner loop is unrolled so that
+// the four Philox words are indexed statically.
+__global__ void mc_sample_weight_kernel(uint8_t* errors, int n, int w, long long T, long long trial_begin,
+                                        unsigned long long seed)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= T) return;
+    const unsigned long long trial = (unsigned long long)(trial_begin + b);
+    uint8_t* const row = errors + b * n;
+    for (int i0 = 0; i0 < w; i0 += 4) {
+        unsigned c[4] = {(unsigned)trial, (unsigned)(trial >> 32), (unsigned)(i0 >> 2), 2u};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i0 + k < w) {
+                const unsigned j = (unsigned)(n - w + i0 + k);
+                const unsigned u = __umulhi(c[k], j + 1u);       // (r (j + 1)) >> 32, in [0, j]
+                row[row[u] ? j : u] = 1;
+            }
+        }
+    }
+}
+
 #endif  // QBP_DEFINE_KERNELS
 
 }  // namespace qbp

@@ -61,6 +61,9 @@ hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial
 // thr: [n rounded up to 4] thresholds, one per qubit (qbp_mc.hpp, mc_error_quad_cols)
 hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                                  unsigned long long seed, const uint32_t* thr, hipStream_t s);
+// rows of exactly `weight` ones (mc_sample_weight_kernel; 0 <= weight <= n); clears errors [T][n] first, on s
+hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
+                                   unsigned long long seed, hipStream_t s);
 // qbp_tu_generic.hip (Monte-Carlo launches with G.det_bits go to the -DQBP_SHOTS_TU builds, with G.spectrum to the
 // -DQBP_SPECTRUM_TU builds, with G.n_budgets to the
 // -DQBP_BUDGETS_TU builds, others with G.thr_cols to the -DQBP_COLS_TU builds)

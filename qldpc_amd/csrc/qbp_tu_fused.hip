@@ -146,6 +146,19 @@ hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long 
                        errors, n, T, trial_begin, draws, seed, thr);
     return hipGetLastError();
 }
+
+hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
+                                   unsigned long long seed, hipStream_t s)
+{
+    // the rows are the kernel's membership map and the buffer is reused across chunks and calls: whatever an
+    // earlier launch left in it would come out as extra ones
+    hipError_t e = hipMemsetAsync(errors, 0, (size_t)T * (size_t)n, s);
+    if (e != hipSuccess || weight == 0) return e;
+    const int threads = 256;
+    hipLaunchKernelGGL(mc_sample_weight_kernel, dim3((unsigned)((T + threads - 1) / threads)), dim3(threads), 0, s,
+                       errors, n, weight, T, trial_begin, seed);
+    return hipGetLastError();
+}
 #endif  // QBP_DEFINE_KERNELS
 
 }  // namespace qbp

@@ -18,11 +18,15 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
     python -m qldpc_amd.mc --code 144 --p 0.05 --osd --spectrum out.npz
                                      (residual-weight spectra and the iteration histogram per point: run_spectrum)
+    python -m qldpc_amd.mc --code 144 --weights 4 6 8 10 12 --prior-p 0.01 --trials 1000000 --osd --ler-at 0.001 0.003 0.01
+                                     (errors of fixed weight, and the LER at any p from their failure fractions:
+                                      run_weights, ler_from_weights)
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import time
 
@@ -449,6 +453,147 @@ def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, se
     return _split_spectrum(flat, n, max_iter)
 
 
+def check_weights(weights, n):
+    """The weights of a fixed-weight run as a list of ints in [0, n] (ValueError otherwise -- the library refuses the
+    same values with QBP_E_INVALID)."""
+    w = np.asarray(weights)
+    if w.ndim != 1 or w.dtype.kind not in "iu":
+        raise ValueError(f"weights must be a list of integers, got {weights!r}")
+    if np.any(w < 0) or np.any(w > n):
+        raise ValueError(f"weights must lie in [0, {n}] (n columns), got {weights!r}")
+    return [int(x) for x in w]
+
+
+def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, max_iter, variant, alpha, damping,
+                       clip_llr, osd, flags, world, device):
+    """One rank's slice of every weight on the device, then the one all-reduce of the [len(weights), 12] table."""
+    import torch
+    dev = torch.device("cuda", device)
+    d_table = torch.zeros((len(weights), NUM_COUNTERS), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev)
+    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
+    step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
+    for i, w in enumerate(weights):
+        for a in range(begin, end, step):
+            dec.mc_run_weight_device(L, distance, w, d_prior.data_ptr(), a, min(a + step, end), d_table[i].data_ptr(),
+                                     seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                     clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(d_table)
+    torch.cuda.synchronize(dev)
+    return d_table.cpu().numpy()
+
+
+def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
+                damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
+                device=0, runner=None, all_reduce=None):
+    """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
+    exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
+    the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
+    ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
+    does (trials of every weight are split over ranks; one all-reduce of the table).
+    ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
+    the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
+    code = codes.load_code(code_name)
+    weights = check_weights(weights, code.n)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(code.Hx, device=device)
+        return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
+                                  seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                  clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, w in enumerate(weights):
+        table[i] = runner(code, w, begin, end)
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
+                       alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False,
+                       rank=0, world=1, device=0, runner=None, all_reduce=None):
+    """``run_weights`` for any matrix H [m, n] with logical operators / observables L [k, n] (k <= 64) and the
+    decoder's LLRs ``prior`` [n].  The weight classes are the strata of UNIFORM noise -- every column failing with the
+    same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
+    does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``."""
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
+    L = np.ascontiguousarray(L, np.uint8)
+    n = H.shape[1]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if L.shape[0] > 64:
+        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
+    prior = np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    weights = check_weights(weights, n)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        return _weights_on_device(dec, L, distance, weights, prior, begin, end, seed=seed, max_iter=max_iter,
+                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
+                                  flags=flags, world=world, device=device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, w in enumerate(weights):
+        table[i] = runner(H, L, w, prior, begin, end)
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def binomial_weights(n, p):
+    """B(n, w, p) = C(n, w) p^w (1 - p)^(n - w) for w = 0 .. n as float64[n + 1], through ``math.lgamma`` (n = 7776
+    does not overflow)."""
+    n, p = int(n), float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"p = {p} out of [0, 1]")
+    out = np.zeros(n + 1)
+    if p == 0.0 or p == 1.0:
+        out[0 if p == 0.0 else n] = 1.0
+        return out
+    lp, lq, ln = math.log(p), math.log1p(-p), math.lgamma(n + 1)
+    for w in range(n + 1):
+        out[w] = math.exp(ln - math.lgamma(w + 1) - math.lgamma(n - w + 1) + w * lp + (n - w) * lq)
+    return out
+
+
+def ler_from_weights(table, weights, n, ps):
+    """The logical error rate under uniform noise of rate p, for every p of ``ps``, from the counter table of a
+    fixed-weight run (``run_weights``: row i = weight ``weights[i]``, [0] trials, [1] logical errors).  Returns a dict
+    of float64 arrays over ``ps``:
+      ``ler``      sum over the sampled w of B(n, w, p) f_w, f_w = logical_error_w / trials_w;
+      ``ler_high`` ler + sum of B(n, w, p) over the weights NOT sampled: those are unknown, not assumed zero
+                   (``unsampled_mass`` is that sum);
+      ``stderr``   sqrt(sum of B^2 f_w (1 - f_w) / trials_w), the binomial error of the sampled part;
+    and ``p`` itself.  A weight without trials counts as not sampled; a weight listed twice is a ValueError."""
+    table = np.asarray(table, np.int64)
+    weights = check_weights(weights, n)
+    if table.ndim != 2 or table.shape[0] != len(weights) or table.shape[1] < 2:
+        raise ValueError(f"table must have shape ({len(weights)}, {NUM_COUNTERS}), got {table.shape}")
+    if len(set(weights)) != len(weights):
+        raise ValueError(f"a weight is listed twice in {weights!r}")
+    ps = np.atleast_1d(np.asarray(ps, np.float64))
+    sampled = np.zeros(n + 1, bool)
+    f = np.zeros(n + 1)
+    var = np.zeros(n + 1)                      # f (1 - f) / trials
+    for w, row in zip(weights, table):
+        t = int(row[0])
+        if t > 0:
+            sampled[w] = True
+            f[w] = int(row[1]) / t
+            var[w] = f[w] * (1.0 - f[w]) / t
+    out = {k: np.zeros(len(ps)) for k in ("ler", "ler_high", "stderr", "unsampled_mass")}
+    out["p"] = ps
+    for i, p in enumerate(ps):
+        B = binomial_weights(n, p)
+        out["ler"][i] = float(np.sum(B[sampled] * f[sampled]))
+        out["unsampled_mass"][i] = float(np.sum(B[~sampled]))
+        out["ler_high"][i] = out["ler"][i] + out["unsampled_mass"][i]
+        out["stderr"][i] = math.sqrt(float(np.sum(B[sampled] ** 2 * var[sampled])))
+    return out
+
+
 def stabilizer_spectrum(code_names, p=0.005, trials=20000, *, max_iter=50, osd=True, **kwargs):
     """The experiment of spectrum.py:22-54: per code name the histogram int64[n + 1] of the weights of the residuals
     ``detection ^ error`` that are non-zero but logically trivial (the stabilisers BP(50) + OSD-0 leaves behind at p =
@@ -528,6 +673,13 @@ def main(argv=None):
     ap.add_argument("--spectrum", default=None, metavar="OUT.npz",
                     help="also collect the residual-weight spectra and the iteration histogram of every point "
                          "(run_spectrum / run_dem_spectrum) and write counters, weights, iterations to this .npz")
+    ap.add_argument("--weights", type=int, nargs="+", default=None,
+                    help="errors of exactly these weights instead of --p (run_weights): a result line per weight; "
+                         "needs --prior-p")
+    ap.add_argument("--prior-p", type=float, default=None,
+                    help="with --weights: the error rate the decoder's prior is built for")
+    ap.add_argument("--ler-at", type=float, nargs="+", default=None, metavar="P",
+                    help="with --weights: print the logical error rate at these p (ler_from_weights)")
     ap.add_argument("--draws", type=int, default=1, choices=(1, 2))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variant", choices=("sum-product", "damped", "min-sum"), default="sum-product")
@@ -564,6 +716,21 @@ def main(argv=None):
             ap.error("--spectrum does not combine with --budgets")
         if not 1 <= args.max_iter <= _lib.MC_SPECTRUM_MAX_ITER:
             ap.error(f"--spectrum takes --max-iter in [1, {_lib.MC_SPECTRUM_MAX_ITER}]")
+    if args.weights is not None:
+        if args.dem is not None or args.budgets is not None or args.spectrum is not None or args.shots is not None:
+            ap.error("--weights does not combine with --dem, --budgets, --spectrum or --shots")
+        if args.prior_p is None or not 0.0 < args.prior_p < 1.0:
+            ap.error("--weights needs --prior-p in (0, 1)")
+        if any(not 0.0 <= p <= 1.0 for p in args.ler_at or []):
+            ap.error("--ler-at takes probabilities in [0, 1]")
+        try:
+            check_weights(args.weights, codes.load_code(args.code).n)
+            if len(set(args.weights)) != len(args.weights):
+                raise ValueError("a weight is listed twice")
+        except ValueError as e:
+            ap.error(f"--weights: {e}")
+    elif args.prior_p is not None or args.ler_at is not None:
+        ap.error("--prior-p and --ler-at need --weights")
     dem_model = None
     if args.dem is not None:
         from . import dem
@@ -673,6 +840,12 @@ def main(argv=None):
                 cnt, tables["weights"], tables["iterations"] = run_dem_spectrum(
                     *dem_model, trials, distance=args.distance, rank=rank, world=world, **common)
             return cnt
+    elif args.weights is not None:
+        points = list(args.weights)      # one row per weight
+        del common["draws"]
+
+        def sweep(trials, ps, rank, world):
+            return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, **common)
     elif dem_model is None:
         points = args.p
 
@@ -706,6 +879,9 @@ def main(argv=None):
                 else:
                     s.update(dem=args.dem)
                     label = f"dem={args.dem}, max_iter={p}"
+            elif args.weights is not None:
+                s.update(weight=p, prior_p=args.prior_p)
+                label = f"weight={p}"
             elif dem_model is None:
                 s["p"] = p
                 label = f"p={p}"
@@ -723,6 +899,13 @@ def main(argv=None):
         else:
             print(f"{len(points)} points x {args.trials} trials on {world} GPU(s): {dt:.3f} s "
                   f"({len(points) * args.trials / dt:.3e} trials/s); one-time setup {t_setup:.2f} s")
+        ler_rows = []
+        if args.weights is not None and args.ler_at:
+            est = ler_from_weights(table, points, codes.load_code(args.code).n, args.ler_at)
+            for i, p in enumerate(args.ler_at):
+                ler_rows.append({k: float(est[k][i]) for k in ("p", "ler", "ler_high", "stderr", "unsampled_mass")})
+                print(f"  p={p}: LER={est['ler'][i]:.6e} +- {est['stderr'][i]:.1e} (at most {est['ler_high'][i]:.6e}: "
+                      f"the weights not sampled carry {est['unsampled_mass'][i]:.3e})")
         if args.spectrum is not None:
             np.savez(args.spectrum, counters=table, weights=tables["weights"], iterations=tables["iterations"],
                      p=np.asarray([np.nan if p is None else p for p in points], np.float64))
@@ -733,6 +916,8 @@ def main(argv=None):
                 model = {"code": args.code} if dem_model is None else {"dem": args.dem, "distance": args.distance}
                 if args.budgets is not None:
                     model["budgets"] = points
+                if args.weights is not None:
+                    model.update(weights=points, prior_p=args.prior_p, ler=ler_rows)
                 json.dump({**model, "trials": args.trials, "max_iter": points[-1] if args.budgets else args.max_iter,
                            "draws": args.draws, "seed": args.seed, "variant": args.variant,
                            "osd": args.osd, "osd_method": args.osd_method, "osd_order": args.osd_order,
