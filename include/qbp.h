@@ -91,10 +91,13 @@ enum {
     QBP_FLAG_OSD_CS = 64u,    /* order-w OSD, combination sweep (qbp_osd_batch below); order: QBP_OSD_ORDER_FLAGS.
                                  With qbp_mc_run* only together with QBP_FLAG_OSD0 */
     QBP_FLAG_OSD_E = 128u,    /* order-w OSD, exhaustive over the w least reliable non-pivot columns (same rules) */
-    QBP_FLAG_OSD_LARGE = 256u /* order-w OSD also on matrices beyond the one-wavefront kernel: up to 8192 rows, on a
+    QBP_FLAG_OSD_LARGE = 256u,/* order-w OSD also on matrices beyond the one-wavefront kernel: up to 8192 rows, on a
                                  workgroup-per-record kernel (osd_order_blocked_kernel).  Only with QBP_FLAG_OSD_CS or
                                  QBP_FLAG_OSD_E (else QBP_E_INVALID); same results, rule for rule.  On a matrix the
                                  one-wavefront kernel takes it changes nothing */
+    QBP_FLAG_RELAY = 512u     /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first-stage
+                                 BP (any variant) does not converge on go through Relay-BP (qbp_relay_decode_batch, as
+                                 configured by qbp_relay_configure) instead of OSD, then to classification */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -297,6 +300,57 @@ int qbp_osd_batch_ordered(qbp_handle* h, uint32_t osd_flags, const uint8_t* synd
 int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_t* d_syndromes, const double* d_llr,
                                  const uint8_t* d_hard, const int32_t* d_order, int64_t B, uint8_t* d_solution,
                                  void* stream);
+
+/*
+ * Relay-BP (Mueller et al. 2025): min-sum whose prior is blended with the previous posterior by a memory strength per
+ * variable, run as a chain of legs with different strengths that continue on each other's messages; it stops after a
+ * few solutions and keeps the lightest.  No elimination: the alternative to BP + OSD on the codes of codes/ and their
+ * space-time matrices.  The reference has no such decoder; the rules below are this build's specification
+ * (tests/relay_oracle.py states them in numpy, and the kernel reproduces that statement bit for bit).  With gammas all
+ * zero, L = 1 and stop_after = 1 the outputs are those of performMinSum_Symmetric (rework/decoding.py:5-75) with
+ * damping = 1.0, `iters` being its currentIter + 1.
+ *
+ * qbp_relay_configure stores the configuration in the handle (host arrays; uploaded once):
+ *   gammas [L][n] memory strengths of leg l (finite, may be negative), leg_iters [L] iterations of leg l (>= 1),
+ *   stop_after >= 1 solutions, alpha (min-sum normalisation) and clip_llr as in rework/decoding.py, finite.
+ * QBP_E_INVALID: a null pointer, L < 1, a leg_iters[l] < 1, stop_after < 1, anything not finite.  QBP_E_UNSUPPORTED: a
+ * matrix whose per-record state -- E messages and three rows of n doubles -- does not fit the 160 KiB of LDS of one
+ * workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not).
+ *
+ * One record (syndrome s, prior P [n] finite):
+ *   1. Q = P on the edges, V = P, no best solution, found = 0, total = 0;
+ *   2. for leg l = 0 .. L - 1, for t = 0 .. leg_iters[l] - 1:
+ *      a. check step of rework/decoding.py:28-56 on Q: signs with 0 -> +1, first minimum by lowest column,
+ *         R = alpha * syndrome_sign * r_signs * magnitudes;
+ *      b. bias[v] = (1.0 - gammas[l][v]) * P[v] + gammas[l][v] * V[v], every operation rounded on its own;
+ *      c. Vn = colsum(R) + bias, the column sum in ascending check order, left to right (QBP_MIN_SUM's default);
+ *      d. Q = clip(Vn - R, -clip_llr, clip_llr) on the edges (no damping term);
+ *      e. V = Vn, total += 1;
+ *      f. hard = V < 0; if H hard == s: w = sum of P[v] over hard[v] = 1, added in ascending v from +0.0; the solution
+ *         replaces the best one if there is none yet or w < the best weight (strictly); found += 1; the leg ends;
+ *   3. after a leg: stop if found >= stop_after; Q and V carry over into the next leg unchanged, however the leg ended;
+ *   4. hard, llr (= V) are those of the best solution, or of the last iteration executed if there is none;
+ *      converged = found > 0, iters = total, legs = legs entered, solutions = found.
+ * qbp_relay_decode_batch: syndromes [B][m], prior [n] (host entry: a value that is not finite is QBP_E_INVALID) ->
+ * hard [B][n], converged [B], iters [B], llr [B][n], legs [B], solutions [B]; any output may be NULL.  QBP_E_INVALID
+ * without a configuration.  One workgroup per record, all of its state in LDS (bp_relay_kernel).
+ *
+ * QBP_FLAG_RELAY in a Monte-Carlo call: the first stage is the call's BP as without the flag; every trial it leaves
+ * unconverged is decoded by the rules above from its syndrome and the call's prior (first-stage messages are not
+ * carried over) and classified on the result like an OSD output.  counters[10] counts the records Relay leaves without
+ * a solution (their hard decision misses the syndrome); [0], [6], [7] are the first stage's.  The record limits of
+ * QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with QBP_FLAG_OSD0 or any OSD bit, or without a
+ * configuration.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum and
+ * qbp_decode_shots, and on matrices qbp_relay_configure refuses.
+ */
+int qbp_relay_configure(qbp_handle* h, const double* gammas, int32_t L, const int32_t* leg_iters, int32_t stop_after,
+                        double alpha, double clip_llr);
+int qbp_relay_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, uint8_t* hard,
+                           uint8_t* converged, int32_t* iters, double* llr, int32_t* legs, int32_t* solutions);
+/* Same, all pointers are DEVICE pointers, enqueued on `stream` (may be NULL), asynchronous. */
+int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                  uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr,
+                                  int32_t* d_legs, int32_t* d_solutions, void* stream);
 
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */

@@ -27,6 +27,7 @@ FLAG_FAST_MATH = 32          # opt-in: round 2's tanh / arctanh approximations o
 FLAG_OSD_CS = 64             # order-w OSD, combination sweep (qbp_osd_batch; with FLAG_OSD0 in qbp_mc_run)
 FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable non-pivot columns
 FLAG_OSD_LARGE = 256         # order-w OSD also on matrices beyond the one-wavefront kernel (up to 8192 rows)
+FLAG_RELAY = 512             # Monte-Carlo calls: Relay-BP (qbp_relay_configure) instead of OSD on the trials BP leaves
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -110,6 +111,9 @@ SIGNATURES = {
     "qbp_osd_batch_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     "qbp_osd_batch_ordered": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     "qbp_osd_batch_ordered_device": (C.c_int, [_VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
+    "qbp_relay_configure": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double]),
+    "qbp_relay_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_relay_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
@@ -288,8 +292,45 @@ class Decoder:
             float(damping), float(clip_llr), int(flags), d_hard or None, d_converged or None,
             d_iters or None, d_llr or None, stream or None))
 
+    @_locked
+    def relay_configure(self, cfg):
+        """Store a Relay-BP configuration (``relay.RelayConfig``) in the handle: qbp_relay_configure."""
+        if cfg.n != self.n:
+            raise ValueError(f"the relay configuration is for {cfg.n} variables, the matrix has {self.n}")
+        _check(load().qbp_relay_configure(self._h, cfg.gammas.ctypes.data, cfg.gammas.shape[0],
+                                          cfg.leg_iters.ctypes.data, cfg.stop_after, cfg.alpha, cfg.clip_llr))
+
+    @_locked
+    def relay_decode(self, syndromes, prior, cfg=None, want_llr=True):
+        """Relay-BP of B syndromes (qbp_relay_decode_batch) -> ``(hard, converged, iters, llr, legs, solutions)``;
+        ``cfg``: configure first (None: the handle's configuration)."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},), got {pr.shape}")
+        if cfg is not None:
+            self.relay_configure(cfg)
+        B = syn.shape[0]
+        hard = np.empty((B, self.n), np.uint8)
+        conv = np.empty(B, np.uint8)
+        iters, legs, sols = (np.empty(B, np.int32) for _ in range(3))
+        llr = np.empty((B, self.n), np.float64) if want_llr else None
+        _check(load().qbp_relay_decode_batch(self._h, syn.ctypes.data, pr.ctypes.data, B, hard.ctypes.data,
+                                             conv.ctypes.data, iters.ctypes.data, _ptr(llr), legs.ctypes.data,
+                                             sols.ctypes.data))
+        return hard, conv.astype(bool), iters, llr, legs, sols
+
+    def relay_decode_device(self, d_syndromes, d_prior, B, d_hard, d_converged, d_iters, d_llr, d_legs, d_solutions,
+                            stream=0):
+        """``relay_decode`` on device buffers (pointers as ints; outputs may be 0), enqueued on `stream`."""
+        _check(load().qbp_relay_decode_batch_device(self._h, d_syndromes, d_prior, int(B), d_hard or None,
+                                                    d_converged or None, d_iters or None, d_llr or None, d_legs or None,
+                                                    d_solutions or None, stream or None))
+
     def mc_osd_step(self):
-        """Trials one qbp_mc_run call may cover with FLAG_OSD0 (per-trial records: m + 10 n bytes)."""
+        """Trials one qbp_mc_run call may cover with FLAG_OSD0 or FLAG_RELAY (per-trial records: m + 10 n bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
     @_locked
@@ -303,7 +344,7 @@ class Decoder:
             raise ValueError(f"prior must have shape ({self.n},)")
         counters = np.zeros(NUM_COUNTERS, np.int64)
         # with OSD a call keeps per-trial records on the device: split long ranges
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
         for a in range(int(trial_begin), int(trial_end), step):
             _check(load().qbp_mc_run(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), float(p),
                                      int(draws), int(seed), a, min(a + step, int(trial_end)),
@@ -322,7 +363,7 @@ class Decoder:
         if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
             raise ValueError("bad shapes")
         total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(len(err), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
         for a in range(0, len(err), step):
             part = np.zeros(NUM_COUNTERS, np.int64)
             chunk = err[a:a + step]
@@ -359,7 +400,7 @@ class Decoder:
         if pr.shape != (self.n,):
             raise ValueError(f"prior must have shape ({self.n},)")
         counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
         for a in range(int(trial_begin), int(trial_end), step):
             _check(load().qbp_mc_run_probs(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
                                            int(draws), int(seed), a, min(a + step, int(trial_end)),
@@ -391,7 +432,7 @@ class Decoder:
         if pr.shape != (self.n,):
             raise ValueError(f"prior must have shape ({self.n},)")
         counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
         for a in range(int(trial_begin), int(trial_end), step):
             _check(load().qbp_mc_run_weight(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight),
                                             int(seed), a, min(a + step, int(trial_end)), pr.ctypes.data,
@@ -442,7 +483,7 @@ class Decoder:
             raise ValueError(f"prior must have shape ({self.n},)")
         spectrum, iter_hist = self._spectrum_tables(max_iter, spectrum, iter_hist)
         counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
         for a in range(int(trial_begin), int(trial_end), step):
             _check(load().qbp_mc_run_spectrum(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
                                               int(draws), int(seed), a, min(a + step, int(trial_end)),
@@ -477,7 +518,7 @@ class Decoder:
             raise ValueError("bad shapes")
         spectrum, iter_hist = self._spectrum_tables(max_iter, None, None)
         total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(len(err), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
         for a in range(0, len(err), step):
             part = np.zeros(NUM_COUNTERS, np.int64)
             chunk = err[a:a + step]
@@ -520,7 +561,7 @@ class Decoder:
             raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
         pred = np.zeros(T, np.uint64)
         conv = np.zeros(T, np.uint8)
-        step = self.mc_osd_step() if (int(flags) & FLAG_OSD0) else max(T, 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(T, 1)
         for a in range(0, T, step):
             b = min(a + step, T)
             _check(load().qbp_decode_shots(
@@ -557,7 +598,7 @@ class Decoder:
         if pr.shape != (self.n,):
             raise ValueError(f"prior must have shape ({self.n},)")
         counters = np.zeros((len(bud), NUM_COUNTERS), np.int64)
-        step = self.mc_budgets_step(len(bud)) if (int(flags) & FLAG_OSD0) else max(int(trial_end) - int(trial_begin), 1)
+        step = self.mc_budgets_step(len(bud)) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
         for a in range(int(trial_begin), int(trial_end), step):
             _check(load().qbp_mc_run_budgets(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
                                              int(draws), int(seed), a, min(a + step, int(trial_end)),

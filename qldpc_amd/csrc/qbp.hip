@@ -20,6 +20,7 @@
 #include "qbp_generic.hpp"
 #include "qbp_stream.hpp"
 #include "qbp_hist.hpp"
+#include "qbp_relay.hpp"
 #include "qbp_launch.hpp"
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
@@ -201,6 +202,13 @@ struct qbp_handle {
     DevBuf<double> d_fail_llr;
     // qbp_decode_shots, host-pointer entry: recorded observables and predictions of the call
     DevBuf<unsigned long long> d_shot_actual, d_shot_pred;
+    // Relay-BP (qbp_relay_configure): the memory strengths in sorted-variable order, the legs' iteration counts, the
+    // inverse of svar; scratch of the host-pointer entry
+    bool relay_ready = false;
+    int relay_L = 0, relay_stop_after = 0;
+    double relay_alpha = 1.0, relay_clip = 0.0;
+    DevBuf<double> d_relay_gammas;
+    DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
 };
 
 namespace {
@@ -1748,6 +1756,189 @@ static int check_mc_osd_trials(const qbp_handle* h, int64_t T, size_t rows)
     return QBP_OK;
 }
 
+// ---- Relay-BP (qbp_relay.hpp) ------------------------------------------------------------------------------------
+// The kernel keeps a record's whole state in LDS: matrices beyond that are QBP_E_UNSUPPORTED.
+static int relay_supported(const qbp_handle* h, bool records)
+{
+    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
+    if (lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "Relay-BP keeps the messages and three rows of n doubles in LDS: %d x %d with %d "
+                                       "entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
+    return QBP_OK;
+}
+
+// QBP_FLAG_RELAY of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and
+// shots entries, which have no Relay stage.
+static int check_relay_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
+{
+    if (!(flags & QBP_FLAG_RELAY)) return QBP_OK;
+    if (flags & (QBP_FLAG_OSD0 | OSD_ALL_BITS))
+        return fail(QBP_E_INVALID, "QBP_FLAG_RELAY together with an OSD bit: one second stage per call");
+    if (other_entry)
+        return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_RELAY is not available with iteration budgets, spectra or recorded shots");
+    if (!h->relay_ready) return fail(QBP_E_INVALID, "QBP_FLAG_RELAY without qbp_relay_configure");
+    return relay_supported(h, true);
+}
+
+// One launch of bp_relay_kernel (device pointers): a batch of syndromes, or the failure records of a Monte-Carlo launch
+struct RelayCall {
+    const double* prior = nullptr;
+    long long max_items = 0;            // B, or the most records the list can hold
+    const uint8_t* syndromes = nullptr;
+    uint8_t* hard = nullptr;
+    uint8_t* converged = nullptr;
+    int32_t* iters = nullptr;
+    double* llr = nullptr;
+    int32_t* legs = nullptr;
+    int32_t* solutions = nullptr;
+    const unsigned long long* fail_count = nullptr;
+    const long long* fail_list = nullptr;
+    const uint8_t* fail_syn = nullptr;
+    const uint8_t* fail_err = nullptr;
+    int half_distance = 0;
+    long long* counters = nullptr;
+};
+
+static int relay_launch(qbp_handle* h, const RelayCall& c, bool records, hipStream_t s)
+{
+    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
+    constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
+    if (c.max_items > MAX_LAUNCH)
+        return fail(QBP_E_UNSUPPORTED, "Relay-BP decodes at most 2^30 syndromes per call (got %lld)", c.max_items);
+    const size_t n = (size_t)h->n;
+    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
+    const int threads = qbp::relay_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1]);
+    // resident workgroups per CU: 28 wavefronts at the kernel's registers, and the LDS
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)(28 / (threads / 64)), ((size_t)160 * 1024) / lds));
+    const int grid = (int)std::max<long long>(1, std::min<long long>(c.max_items, (long long)h->num_cu * per_cu));
+    const size_t n_long = (size_t)(h->row_off[RC + 2] - h->row_off[RC + 1]);
+    HIP_TRY(h->d_wsL.reserve((size_t)grid * 3 * std::max<size_t>(n_long, 1)));
+    HIP_TRY(h->d_prior_sorted.reserve(n));
+    HIP_TRY(qbp::launch_permute_prior(c.prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
+    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    qbp::RelayParams P{};
+    P.m = h->m; P.n = h->n; P.E = h->E;
+    P.srow = h->d_srow.p; P.srow_e0 = h->d_srow_e0.p; P.srow_deg = h->d_srow_deg.p; P.epos = h->d_epos.p;
+    P.long_edge_row = h->d_long_edge_row.p; P.svar = h->d_svar.p; P.vpos = h->d_vpos.p; P.vrow = h->d_vrow.p;
+    P.lcol_ptr = h->d_lcol_ptr.p;
+    std::copy(std::begin(h->row_off), std::end(h->row_off), P.row_off);
+    std::copy(std::begin(h->row_base), std::end(h->row_base), P.row_base);
+    std::copy(std::begin(h->rpad_off), std::end(h->rpad_off), P.rpad_off);
+    std::copy(std::begin(h->col_off), std::end(h->col_off), P.col_off);
+    std::copy(std::begin(h->gcol_base), std::end(h->gcol_base), P.col_base);
+    std::copy(std::begin(h->cpad_off), std::end(h->cpad_off), P.cpad_off);
+    P.vinv = h->d_relay_vinv.p; P.prior = c.prior; P.prior_sorted = h->d_prior_sorted.p; P.wsL = h->d_wsL.p;
+    P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    P.gammas_sorted = h->d_relay_gammas.p; P.leg_iters = h->d_relay_iters.p;
+    P.L = h->relay_L; P.stop_after = h->relay_stop_after; P.alpha = h->relay_alpha; P.clip_llr = h->relay_clip;
+    P.syndromes = c.syndromes; P.B = records ? 0 : c.max_items;
+    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr; P.legs = c.legs; P.solutions = c.solutions;
+    P.fail_count = c.fail_count; P.fail_list = c.fail_list; P.fail_syn = c.fail_syn; P.fail_err = c.fail_err;
+    P.lx_cols = h->d_lx_cols.p; P.half_distance = c.half_distance; P.counters = c.counters;
+    h->last_threads = threads; h->last_lds = (int)lds; h->last_grid = grid;
+    HIP_TRY(qbp::launch_relay(records, P, grid, threads, lds, s));
+    return QBP_OK;
+}
+
+int qbp_relay_configure(qbp_handle* h, const double* gammas, int32_t L, const int32_t* leg_iters, int32_t stop_after,
+                        double alpha, double clip_llr)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!gammas || !leg_iters) return fail(QBP_E_INVALID, "null pointer");
+    if (L < 1) return fail(QBP_E_INVALID, "L = %d legs (need >= 1)", L);
+    if (stop_after < 1) return fail(QBP_E_INVALID, "stop_after = %d (need >= 1)", stop_after);
+    if (!std::isfinite(alpha) || !std::isfinite(clip_llr))
+        return fail(QBP_E_INVALID, "alpha = %g, clip_llr = %g: both must be finite", alpha, clip_llr);
+    const size_t n = (size_t)h->n;
+    for (int l = 0; l < L; ++l) {
+        if (leg_iters[l] < 1) return fail(QBP_E_INVALID, "leg_iters[%d] = %d (need >= 1)", l, leg_iters[l]);
+        for (size_t v = 0; v < n; ++v)
+            if (!std::isfinite(gammas[(size_t)l * n + v]))
+                return fail(QBP_E_INVALID, "gammas[%d][%zu] is not finite", l, v);
+    }
+    const int rc = relay_supported(h, false);
+    if (rc) return rc;
+    // the tables follow the kernel's variable order: sorted by column weight (build_tables)
+    HostTables T;
+    const int rc2 = build_tables(h->row_ptr.data(), h->col_idx.data(), h->m, h->n, T);
+    if (rc2) return rc2;
+    std::vector<double> sorted((size_t)L * n);
+    std::vector<int32_t> vinv(n);
+    for (size_t x = 0; x < n; ++x) {
+        vinv[T.svar[x]] = (int32_t)x;
+        for (int l = 0; l < L; ++l) sorted[(size_t)l * n + x] = gammas[(size_t)l * n + T.svar[x]];
+    }
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    HIP_TRY(hipStreamSynchronize(h->stream));       // (a launch of this handle's stream may still read the old tables)
+    h->relay_ready = false;
+    HIP_TRY(h->d_relay_gammas.upload(sorted));
+    HIP_TRY(h->d_relay_vinv.upload(vinv));
+    HIP_TRY(h->d_relay_iters.upload(std::vector<int32_t>(leg_iters, leg_iters + L)));
+    h->relay_L = L; h->relay_stop_after = stop_after; h->relay_alpha = alpha; h->relay_clip = clip_llr;
+    h->relay_ready = true;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                  uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr,
+                                  int32_t* d_legs, int32_t* d_solutions, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->relay_ready) return fail(QBP_E_INVALID, "qbp_relay_decode_batch without qbp_relay_configure");
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    RelayCall c;
+    c.prior = d_prior; c.max_items = B; c.syndromes = d_syndromes;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr; c.legs = d_legs; c.solutions = d_solutions;
+    return relay_launch(h, c, false, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_relay_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, uint8_t* hard,
+                           uint8_t* converged, int32_t* iters, double* llr, int32_t* legs, int32_t* solutions)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->relay_ready) return fail(QBP_E_INVALID, "qbp_relay_decode_batch without qbp_relay_configure");
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
+    for (int v = 0; v < h->n; ++v)
+        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_prior.reserve(n));
+    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
+    if (converged) HIP_TRY(h->d_conv.reserve(b));
+    if (iters) HIP_TRY(h->d_iters.reserve(b));
+    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
+    if (legs) HIP_TRY(h->d_relay_legs.reserve(b));
+    if (solutions) HIP_TRY(h->d_relay_sol.reserve(b));
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    int rc = qbp_relay_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, hard ? h->d_hard.p : nullptr,
+                                           converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
+                                           llr ? h->d_llr.p : nullptr, legs ? h->d_relay_legs.p : nullptr,
+                                           solutions ? h->d_relay_sol.p : nullptr, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
+    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
+    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
+    if (legs) HIP_TRY(hipMemcpyAsync(legs, h->d_relay_legs.p, b * 4, hipMemcpyDeviceToHost, s));
+    if (solutions) HIP_TRY(hipMemcpyAsync(solutions, h->d_relay_sol.p, b * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 // probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null.
 // budgets (checked by the caller; needs probs): qbp_mc_run_budgets -- max_iter is unused, d_counters is
 // [n_budgets][QBP_NUM_COUNTERS]; else null / 0.
@@ -1765,6 +1956,10 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     if (budgets) max_iter = budgets[n_budgets - 1];
     int rc = check_decode_args(h, T, max_iter, variant);
     if (rc) return rc;
+    // Relay-BP instead of OSD on the trials the first stage leaves unconverged: its bit goes to no BP launch
+    const bool relay = (flags & QBP_FLAG_RELAY) != 0;
+    if ((rc = check_relay_flags(h, flags, budgets != nullptr || d_spectrum != nullptr)) != QBP_OK) return rc;
+    flags &= ~(uint32_t)QBP_FLAG_RELAY;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
     int osd_method = 0, osd_order = 0;
     rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order);
@@ -1782,9 +1977,9 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     rc = mc_prepare(h, Lx_host, k, s);
     if (rc) return rc;
     if (probs && (rc = mc_prepare_thr(h, probs, s)) != QBP_OK) return rc;
-    const bool osd = (flags & QBP_FLAG_OSD0) != 0;
+    const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay;
     if (osd) {
-        // per-trial records of the trials BP leaves unconverged (read by the OSD kernel)
+        // per-trial records of the trials BP leaves unconverged (read by the OSD kernel, or the Relay-BP one)
         // (qbp_mc_run_budgets: a record per trial and budget)
         const size_t t = (size_t)T * rows, m = h->m, n = h->n;
         if ((rc = check_mc_osd_trials(h, T, rows)) != QBP_OK) return rc;
@@ -1828,6 +2023,15 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         if (rc == QBP_OK) h->last_kernel = 1;
     }
     if (rc || !osd) return rc;
+    if (relay) {
+        // second kernel: Relay-BP + classification of the trials the first stage left unconverged
+        RelayCall r;
+        r.prior = d_prior; r.max_items = T;
+        r.fail_count = h->d_fail_count.p; r.fail_list = h->d_fail_list.p;
+        r.fail_syn = h->d_fail_syn.p; r.fail_err = h->d_fail_err.p;
+        r.half_distance = distance / 2; r.counters = reinterpret_cast<long long*>(d_counters);
+        return relay_launch(h, r, true, s);
+    }
     // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
     // read from device memory by the kernel itself (no host round trip)
     // (qbp_mc_run_budgets: once per row, on that row's list, records and counters)
@@ -1959,10 +2163,11 @@ try {
     const int64_t T = trial_end - trial_begin;
     if ((rc = check_decode_args(h, T, max_iter, variant)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
-    if ((rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order)) != QBP_OK) return rc;
+    if ((rc = check_relay_flags(h, flags, false)) != QBP_OK) return rc;
+    if ((rc = parse_osd_flags(h, flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order)) != QBP_OK) return rc;
     if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
     if (k > 0 && !Lx_host) return fail(QBP_E_INVALID, "Lx is null");
-    if ((flags & QBP_FLAG_OSD0) && (rc = check_mc_osd_trials(h, T, 1)) != QBP_OK) return rc;
+    if ((flags & (QBP_FLAG_OSD0 | QBP_FLAG_RELAY)) && (rc = check_mc_osd_trials(h, T, 1)) != QBP_OK) return rc;
     if (T == 0) return QBP_OK;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
@@ -2269,6 +2474,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if (rc) return rc;
     if (!Lx || !det_bits || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
     if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k = %d observables (need 1..64)", k);
+    if ((rc = check_relay_flags(h, flags, true)) != QBP_OK) return rc;
     if (host_prior)
         for (int v = 0; v < h->n; ++v)
             if (host_prior[v] != host_prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);

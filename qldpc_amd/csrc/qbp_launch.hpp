@@ -16,6 +16,7 @@ struct StreamParams;
 struct OsdParams;
 struct OsdBigWorkspace;
 struct OsdOrderBigArgs;
+struct RelayParams;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -119,6 +120,8 @@ hipError_t launch_osd_order_blocked_shots(int rows_per_thread, unsigned grid, si
                                           const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
 hipError_t launch_osd_order_blocked_ordered(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                                             const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
+// qbp_tu_relay.hip: bp_relay_kernel, its batch build or (records) the build that reads Monte-Carlo failure records
+hipError_t launch_relay(bool records, const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

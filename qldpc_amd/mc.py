@@ -70,16 +70,35 @@ def osd_run_flags(osd, osd_method="cs", osd_order=0, osd_large=False) -> int:
     return fl
 
 
+def relay_run_flags(flags, relay) -> int:
+    """``flags`` of a sweep with ``relay`` (None, a ``relay.RelayConfig`` or its dict form): | FLAG_RELAY, the trials BP
+    leaves unconverged go to Relay-BP.  ValueError together with OSD: one second stage per run."""
+    if relay is None:
+        return flags
+    if flags & (_lib.FLAG_OSD0 | _lib.FLAG_OSD_CS | _lib.FLAG_OSD_E | _lib.FLAG_OSD_LARGE):
+        raise ValueError("relay= and osd=True exclude each other: one second stage per run")
+    return flags | _lib.FLAG_RELAY
+
+
+def _configure_relay(dec, relay):
+    if relay is not None:
+        from . import relay as relay_mod
+        dec.relay_configure(relay_mod.as_config(relay, dec.n))
+
+
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
-              world=1, device=0, runner=None, all_reduce=None):
+              world=1, device=0, runner=None, all_reduce=None, relay=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
+
+    ``relay``: a ``relay.RelayConfig`` or its dict form -- Relay-BP instead of OSD on the trials BP does not converge
+    on (FLAG_RELAY; not together with ``osd``).
 
     ``osd``: OSD on the trials BP does not converge on -- OSD-0 with ``osd_order`` 0, else order-w OSD by
     ``osd_method`` ("cs" or "e"; include/qbp.h).
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
+    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -87,11 +106,12 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
 
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
+        _configure_relay(dec, relay)
         dev = torch.device("cuda", device)
         d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev)
         priors = [torch.from_numpy(prior_of(p, code.n)).to(dev) for p in ps]
-        step = dec.mc_osd_step() if osd else 1 << 40         # OSD keeps per-trial records
+        step = dec.mc_osd_step() if osd or relay is not None else 1 << 40         # OSD and Relay keep per-trial records
         for i, p in enumerate(ps):
             begin, end = shard_range(trials, rank, world)
             for a in range(begin, end, step):
@@ -120,7 +140,7 @@ def dem_prior(probs) -> np.ndarray:
 
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
-            osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None):
+            osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -130,8 +150,8 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     ``distance``: the "BPs_miscorrected" / "incorrectable" split compares the error weight with distance // 2;
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
-    tests; by default the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
+    tests; by default the HIP library and torch.distributed.  ``relay``: as in ``run_sweep``."""
+    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
     L = np.ascontiguousarray(L, np.uint8)
     probs = np.ascontiguousarray(probs, np.float64)
     n = H.shape[1]
@@ -150,11 +170,12 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
 
         from . import bp
         dec = bp.decoder_for(H, device=device)
+        _configure_relay(dec, relay)
         dev = torch.device("cuda", device)
         d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev)
         d_prior = torch.from_numpy(prior).to(dev)
-        step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
+        step = dec.mc_osd_step() if osd or relay is not None else 1 << 40          # OSD and Relay keep per-trial records
         for a in range(begin, end, step):
             dec.mc_run_probs_device(L, distance, probs, d_prior.data_ptr(), a, min(a + step, end), d_cnt.data_ptr(),
                                     draws=draws, seed=seed, max_iter=max_iter, variant=variant, alpha=alpha,
@@ -472,7 +493,7 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
     d_table = torch.zeros((len(weights), NUM_COUNTERS), dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream(dev)
     d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
-    step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
+    step = dec.mc_osd_step() if osd or (flags & _lib.FLAG_RELAY) else 1 << 40          # OSD and Relay keep per-trial records
     for i, w in enumerate(weights):
         for a in range(begin, end, step):
             dec.mc_run_weight_device(L, distance, w, d_prior.data_ptr(), a, min(a + step, end), d_table[i].data_ptr(),
@@ -487,21 +508,22 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
-                device=0, runner=None, all_reduce=None):
+                device=0, runner=None, all_reduce=None, relay=None):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed."""
-    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
+    the HIP library and torch.distributed.  ``relay``: as in ``run_sweep``."""
+    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
+        _configure_relay(dec, relay)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
@@ -694,6 +716,13 @@ def main(argv=None):
     ap.add_argument("--osd-large", action="store_true",
                     help="with --osd-order W >= 1: also on matrices beyond the one-wavefront OSD kernel (space-time "
                          "and detector-error-model matrices of up to 8192 rows)")
+    ap.add_argument("--relay", type=int, nargs=2, default=None, metavar=("LEGS", "ITERS"),
+                    help="Relay-BP instead of OSD on the trials BP does not converge on: LEGS legs of ITERS min-sum "
+                         "iterations each (with --alpha and --clip-llr; not with --osd, --budgets, --spectrum, --shots)")
+    ap.add_argument("--relay-gamma0", type=float, default=0.125, help="memory strength of leg 0, every variable")
+    ap.add_argument("--relay-interval", type=float, nargs=2, default=(-0.24, 0.66), metavar=("LO", "HI"),
+                    help="later legs draw a strength per variable uniformly from [LO, HI] (seeded by --seed)")
+    ap.add_argument("--relay-stop", type=int, default=1, metavar="S", help="stop after S solutions, keep the lightest")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
                     help="N > 1 without a launcher: start N ranks (one per GPU) and reduce over RCCL")
@@ -704,6 +733,20 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order, args.osd_large)
     except ValueError as e:
         ap.error(str(e))
+    relay = None
+    if args.relay is not None:
+        if args.osd:
+            ap.error("--relay and --osd exclude each other")
+        if args.budgets is not None or args.spectrum is not None or args.shots is not None:
+            ap.error("--relay does not combine with --budgets, --spectrum or --shots")
+        relay = dict(legs=args.relay[0], iters=args.relay[1], gamma0=args.relay_gamma0,
+                     interval=tuple(args.relay_interval), seed=args.seed, stop_after=args.relay_stop, alpha=args.alpha,
+                     clip_llr=args.clip_llr)
+        try:
+            from . import relay as relay_mod
+            relay_mod.as_config(relay, 1)
+        except (ValueError, TypeError) as e:
+            ap.error(f"--relay: {e}")
     if args.budgets is not None:
         try:
             _lib.check_budgets(args.budgets)
@@ -845,17 +888,19 @@ def main(argv=None):
         del common["draws"]
 
         def sweep(trials, ps, rank, world):
-            return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, **common)
+            return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
+                               **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
-            return run_sweep(args.code, ps, trials, rank=rank, world=world, **common)
+            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
-            return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, **common)[None, :]
+            return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
+                           **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

@@ -30,6 +30,8 @@ UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SHOTS_TU"])] +
           [("qbp_tu_osd.hip", ["-DQBP_SHOTS_TU"])])
 # OSD in a column order the caller gives (qbp_osd_batch_ordered): the OSD kernels without their sort (osd*_ordered_kernel)
 UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
+# Relay-BP (qbp_relay_decode_batch, QBP_FLAG_RELAY): bp_relay_kernel, batch and records builds
+UNITS += [("qbp_tu_relay.hip", [])]
 
 
 def demangle(sym):
