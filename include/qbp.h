@@ -95,9 +95,12 @@ enum {
                                  workgroup-per-record kernel (osd_order_blocked_kernel).  Only with QBP_FLAG_OSD_CS or
                                  QBP_FLAG_OSD_E (else QBP_E_INVALID); same results, rule for rule.  On a matrix the
                                  one-wavefront kernel takes it changes nothing */
-    QBP_FLAG_RELAY = 512u     /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first-stage
+    QBP_FLAG_RELAY = 512u,    /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first-stage
                                  BP (any variant) does not converge on go through Relay-BP (qbp_relay_decode_batch, as
                                  configured by qbp_relay_configure) instead of OSD, then to classification */
+    QBP_FLAG_LAYERED = 1024u  /* the layered (check-serial) schedule instead of flooding: qbp_layered_configure below.
+                                 Honoured by qbp_decode_batch(_device), qbp_mc_run(_device), qbp_mc_run_errors,
+                                 qbp_mc_run_probs(_device), qbp_mc_run_weight(_device) */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -352,6 +355,56 @@ int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, con
                                   uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr,
                                   int32_t* d_legs, int32_t* d_solutions, void* stream);
 
+/*
+ * Layered (check-serial) BP.  Flooding updates all checks from last iteration's messages, then all variables; here the
+ * checks are visited one after another and each sees the posteriors its predecessors of the same iteration just
+ * updated.  The reference has no such decoder; the rules below are this build's specification (tests/layered_oracle.py
+ * states them in numpy, in the sequential and in the level form, and the kernel reproduces that statement bit for
+ * bit).  The row update is the project's own: beliefPropagation.py:114-126 for QBP_SUM_PRODUCT, rework/decoding.py:28-56
+ * for QBP_MIN_SUM.
+ *
+ * One record (syndrome s, prior [n] finite, max_iter >= 1, `order` a permutation of the checks):
+ *   state: one check->variable message R per edge, +0.0 at start; the posterior V = prior;
+ *   iteration t = 0 .. max_iter - 1, for c in order (checks of weight 0 are skipped):
+ *     1. for each edge j of row c in ascending column order: d_j = V[v_j] - R[c,j]; q_j = d_j for QBP_SUM_PRODUCT,
+ *        clip(d_j, -clip_llr, clip_llr) for QBP_MIN_SUM;
+ *     2. r = the row update of q (sum-product: tanh, sequential product in ascending column order, t_safe, division,
+ *        syndrome sign, clip +-0.9999999, 2 arctanh; min-sum: with alpha);
+ *     3. R[c,j] = r_j, then V[v_j] = d_j + r_j;
+ *   every operation rounded on its own.  After the last check: hard = V < 0; H hard == s: converged at iteration t.
+ *   Outputs as qbp_decode_batch: hard and llr = V of the first converged iteration, else of the last; converged;
+ *   iters (0-based, max_iter - 1 if none).  Isolated variables keep V = prior.
+ * What the kernel runs is the level form: the level of a check is 1 + the largest level of the checks that share a
+ * variable with it and come earlier in the order (1 if there are none).  Checks of one level share no variable, and
+ * every ordered pair of conflicting checks keeps its order: level after level, all checks of a level at once, is the
+ * sequential statement bit for bit.
+ *
+ * qbp_layered_plan (host only, no device): order_in [m] a permutation of the checks, or NULL for the default order --
+ * greedy colouring (checks in ascending index, each the smallest colour no earlier neighbour holds) ordered by (colour,
+ * index).  Outputs: order_out [m], the order sorted by level (stable; the default order is its own), level_ptr [m + 1]
+ * of which entries 0 .. *n_levels are the level boundaries in order_out (the rest is m).  QBP_E_INVALID: a null
+ * pointer, a malformed CSR, an order that is not a permutation.
+ *
+ * qbp_layered_configure stores the level tables of `order` (host array, NULL = default) in the handle.
+ * QBP_E_INVALID: not a permutation.  QBP_E_UNSUPPORTED: a matrix whose per-record state -- E messages, the posterior and
+ * the prior -- does not fit the 160 KiB of LDS of one workgroup (864 x 2592 fits; 2592 x 7776 does not).
+ *
+ * QBP_FLAG_LAYERED in a call: qbp_decode_batch(_device) decode by the rules above (bp_layered_kernel: one workgroup
+ * decodes several records at once, all state in LDS; QBP_OPT_LAYERED_SLOTS).  QBP_FLAG_FORCE_FULL runs all iterations
+ * and keeps the outputs of the first converged one.  The Monte-Carlo entries run the layered decoder as their first
+ * stage on stored errors: qbp_mc_run_errors on the caller's, the sampled entries on the errors
+ * qbp_mc_sample_errors[_probs|_weight] return, drawn chunk by chunk (QBP_OPT_MC_WEIGHT_CHUNK) -- counters do not depend
+ * on the chunk or on how a trial range is split.  QBP_FLAG_OSD0, the order-w OSD bits and QBP_FLAG_RELAY act on the
+ * layered stage's failure records unchanged (llr and hard of the last iteration).  QBP_FLAG_FORCE_FULL changes no
+ * count and is dropped there; QBP_FLAG_FAST_MATH is ignored.
+ * QBP_E_INVALID: the flag without a configuration, with QBP_DAMPED_SP, with any column-sum order flag (there is no
+ * column sum), or a prior that is not finite at a host entry.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets,
+ * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and qbp_check_messages.
+ */
+int qbp_layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* order_in,
+                     int32_t* order_out, int32_t* level_ptr, int32_t* n_levels);
+int qbp_layered_configure(qbp_handle* h, const int32_t* order);
+
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */
 int qbp_mc_sample_errors(qbp_handle* h, double p, int32_t draws, uint64_t seed,
@@ -560,13 +613,15 @@ enum {
                                     the full width); 2 is QBP_E_UNSUPPORTED */
     QBP_OPT_MC_WEIGHT_CHUNK = 14, /* qbp_mc_run_weight*: trials sampled and decoded per chunk (0 = default, see there;
                                     at most 2^20).  Results do not depend on it (tests force several chunks) */
+    QBP_OPT_LAYERED_SLOTS = 15,  /* layered BP: records decoded at once by one workgroup (0 = auto, at most 32; fewer
+                                    where the LDS holds fewer).  Results do not depend on it (tests force 1 and 2) */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */
     QBP_INFO_M = 100, QBP_INFO_N = 101, QBP_INFO_EDGES = 102, QBP_INFO_MAX_ROW_DEG = 103,
     QBP_INFO_MAX_COL_DEG = 104, QBP_INFO_KERNEL_KIND = 105, /* 1 on-chip, 2 general-H, 3 streaming */
     QBP_INFO_THREADS = 106, QBP_INFO_LDS_BYTES = 107, QBP_INFO_GRID = 108, QBP_INFO_NUM_CU = 109,
-    QBP_INFO_LAST_KERNEL = 110, /* kernel of the last decode launch: 1 on-chip, 2 general-H, 3 streaming */
+    QBP_INFO_LAST_KERNEL = 110, /* kernel of the last decode launch: 1 on-chip, 2 general-H, 3 streaming, 4 layered */
     QBP_INFO_ONE_BARRIER = 111  /* 1 if the last on-chip launch geometry used the one-barrier forced kernel */
 };
 int qbp_set_option(qbp_handle* h, int32_t option, int64_t value);

@@ -28,6 +28,7 @@ FLAG_OSD_CS = 64             # order-w OSD, combination sweep (qbp_osd_batch; wi
 FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable non-pivot columns
 FLAG_OSD_LARGE = 256         # order-w OSD also on matrices beyond the one-wavefront kernel (up to 8192 rows)
 FLAG_RELAY = 512             # Monte-Carlo calls: Relay-BP (qbp_relay_configure) instead of OSD on the trials BP leaves
+FLAG_LAYERED = 1024          # the layered (check-serial) schedule instead of flooding (qbp_layered_configure)
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -43,6 +44,7 @@ OPT_FORCED_TWO_BARRIERS = 11
 OPT_NO_FIRST_STEP_TABLE = 12
 OPT_EARLY_EXIT_FULL_WG = 13
 OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per chunk (0 = default)
+OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
 INFO = dict(m=100, n=101, edges=102, max_row_deg=103, max_col_deg=104, kernel_kind=105,
             threads=106, lds_bytes=107, grid=108, num_cu=109, last_kernel=110, one_barrier=111)
@@ -114,6 +116,8 @@ SIGNATURES = {
     "qbp_relay_configure": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double]),
     "qbp_relay_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "qbp_relay_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "qbp_layered_configure": (C.c_int, [_VP, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
@@ -161,6 +165,7 @@ class QbpError(RuntimeError):
     code = 0
 
 
+E_INVALID = -1
 E_UNSUPPORTED = -4
 
 
@@ -216,6 +221,27 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def layered_plan(row_ptr, col_idx, m, n, order=None):
+    """Host-only: the layered schedule of a CSR matrix (qbp_layered_plan) -> ``(order, level_ptr)``: the checks level
+    after level and the level boundaries int32[n_levels + 1].  ``order``: a permutation of the checks, None = the
+    default (greedy colouring, by colour then index)."""
+    rp = np.ascontiguousarray(row_ptr, np.int32)
+    ci = np.ascontiguousarray(col_idx, np.int32)
+    if rp.shape != (int(m) + 1,):
+        raise ValueError(f"row_ptr must have shape ({int(m) + 1},)")
+    oin = None
+    if order is not None:
+        oin = np.ascontiguousarray(order, np.int32)
+        if oin.shape != (int(m),):
+            raise ValueError(f"order must have shape ({int(m)},), got {oin.shape}")
+    out = np.zeros(int(m), np.int32)
+    lptr = np.zeros(int(m) + 1, np.int32)
+    nl = C.c_int32(0)
+    _check(load().qbp_layered_plan(rp.ctypes.data, _ptr(ci), int(m), int(n), _ptr(oin), out.ctypes.data,
+                                   lptr.ctypes.data, C.byref(nl)))
+    return out, lptr[:nl.value + 1].copy()
+
+
 def _locked(method):
     """Serialise the host-buffer entry points of one Decoder: a qbp_handle owns one set of device
     scratch buffers and one stream (include/qbp.h: "not thread-safe"), while the reference's
@@ -244,6 +270,7 @@ class Decoder:
         self._h = h
         self.device = int(device)
         self._lock = threading.RLock()
+        self._layered = None          # the order of the last layered_configure (bytes; b"" = default), None = none
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -265,8 +292,32 @@ class Decoder:
 
     # ---- host buffers ----------------------------------------------------------------------
     @_locked
+    def layered_configure(self, order=None):
+        """Store the level tables of the layered schedule in the handle (qbp_layered_configure).  ``order``: a
+        permutation of the checks, None = the default order."""
+        oin = None
+        if order is not None:
+            oin = np.ascontiguousarray(order, np.int32)
+            if oin.shape != (self.m,):
+                raise ValueError(f"order must have shape ({self.m},), got {oin.shape}")
+        key = b"" if oin is None else oin.tobytes()
+        if self._layered != key:
+            self._layered = None
+            _check(load().qbp_layered_configure(self._h, _ptr(oin)))
+            self._layered = key
+
+    @_locked
     def decode(self, syndromes, prior, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
-               clip_llr=20.0, flags=0, want_llr=True):
+               clip_llr=20.0, flags=0, want_llr=True, layered=False):
+        """``layered``: True -- the layered schedule (FLAG_LAYERED) in the configured order, the default one if none
+        was configured; an array -- in that order of the checks."""
+        if layered is not False and layered is not None:
+            if layered is True:
+                if self._layered is None:
+                    self.layered_configure(None)
+            else:
+                self.layered_configure(layered)
+            flags = int(flags) | FLAG_LAYERED
         syn = np.ascontiguousarray(syndromes, np.uint8)
         if syn.ndim != 2 or syn.shape[1] != self.m:
             raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")

@@ -21,6 +21,7 @@
 #include "qbp_stream.hpp"
 #include "qbp_hist.hpp"
 #include "qbp_relay.hpp"
+#include "qbp_layered.hpp"
 #include "qbp_launch.hpp"
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
@@ -209,6 +210,11 @@ struct qbp_handle {
     double relay_alpha = 1.0, relay_clip = 0.0;
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
+    // layered BP (qbp_layered_configure): the checks level after level, the level boundaries
+    bool layered_ready = false;
+    int layered_levels = 0, layered_max_width = 0;
+    int opt_layered_slots = 0;      // QBP_OPT_LAYERED_SLOTS (0 = auto)
+    DevBuf<int32_t> d_layered_order, d_layered_level_ptr;
 };
 
 namespace {
@@ -1091,6 +1097,11 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     return QBP_OK;
 }
 
+// (layered BP, defined with its configuration further down)
+static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry);
+static int check_finite_prior(const qbp_handle* h, const double* prior);
+static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s);
+
 int qbp_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior,
                             int64_t B, int32_t max_iter, int32_t variant, double alpha,
                             double damping, double clip_llr, uint32_t flags, uint8_t* d_hard,
@@ -1098,12 +1109,22 @@ int qbp_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const dou
 try {
     int rc = check_decode_args(h, B, max_iter, variant);
     if (rc) return rc;
+    if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
     if (B == 0) return QBP_OK;
     if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
     if (B > (int64_t)1 << 40) return fail(QBP_E_INVALID, "B too large");
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     hipStream_t s = static_cast<hipStream_t>(stream);
+    if (flags & QBP_FLAG_LAYERED) {
+        // the layered schedule: a kernel of its own (QBP_FLAG_FAST_MATH is ignored)
+        BpCall c;
+        c.syndromes = d_syndromes; c.prior = d_prior; c.B = B; c.max_iter = max_iter; c.variant = variant;
+        c.alpha = alpha; c.clip_llr = clip_llr; c.flags = flags & QBP_FLAG_FORCE_FULL;
+        c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr;
+        h->last_kernel = 4;
+        return layered_launch(h, c, s);
+    }
     BpCall c;
     rc = resolve_column_order(h, flags, nullptr, &c.col_mode);
     if (rc) return rc;
@@ -1130,6 +1151,10 @@ try {
     if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
     for (int v = 0; v < h->n; ++v)
         if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if (flags & QBP_FLAG_LAYERED) {
+        if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
+        if ((rc = check_finite_prior(h, prior)) != QBP_OK) return rc;
+    }
     if (flags & QBP_FLAG_DENSE_F_COLSUM_ITER0) {     // (the shortcut is judged on the host copy of the priors)
         int mode = 0;
         unsigned fl = flags;
@@ -1304,6 +1329,7 @@ int qbp_check_messages(qbp_handle* h, const uint8_t* syndromes, const double* pr
 try {
     int rc = check_decode_args(h, B, iteration + 1, variant);
     if (rc) return rc;
+    if ((rc = check_layered_flags(h, flags, variant, true)) != QBP_OK) return rc;
     int col_mode = 0;                    // (only the column-sum order bits of `flags` are honoured)
     flags &= QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0 | QBP_FLAG_PAIRWISE_COLSUM;
     if (prior) { rc = resolve_column_order(h, flags, prior, &col_mode); if (rc) return rc; }
@@ -1756,6 +1782,193 @@ static int check_mc_osd_trials(const qbp_handle* h, int64_t T, size_t rows)
     return QBP_OK;
 }
 
+// ---- layered BP (qbp_layered.hpp) --------------------------------------------------------------------------------
+// The order and the levels of the layered schedule (include/qbp.h, qbp_layered_plan): host only.
+//   order_in null: greedy colouring -- checks in ascending index, each the smallest colour no earlier neighbour holds --
+//   ordered by (colour, index); else a permutation of the checks.
+//   level of a check: 1 + the largest level of the checks that share a variable with it and come earlier in the order.
+//   order_out: the order sorted by level (stable); level_ptr [n_levels + 1] into it.
+static int layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, const int32_t* order_in,
+                        std::vector<int32_t>& order_out, std::vector<int32_t>& level_ptr)
+{
+    std::vector<int32_t> order((size_t)m);
+    if (order_in) {
+        std::vector<uint8_t> seen((size_t)m, 0);
+        for (int i = 0; i < m; ++i) {
+            const int c = order_in[i];
+            if (c < 0 || c >= m) return fail(QBP_E_INVALID, "order[%d] = %d is not a check (m = %d)", i, c, m);
+            if (seen[c]) return fail(QBP_E_INVALID, "order holds check %d twice: not a permutation", c);
+            seen[c] = 1;
+            order[i] = c;
+        }
+    } else {
+        // colours held by the earlier checks of each variable, as a list per variable (column weights are small)
+        std::vector<std::vector<int>> var_colours((size_t)n);
+        std::vector<int> colour((size_t)m, 0);
+        std::vector<uint8_t> used;
+        int n_colours = 0;
+        for (int c = 0; c < m; ++c) {
+            used.assign((size_t)n_colours + 1, 0);
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e)
+                for (int k : var_colours[col_idx[e]]) used[k] = 1;
+            int k = 0;
+            while (used[k]) ++k;
+            colour[c] = k;
+            n_colours = std::max(n_colours, k + 1);
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) var_colours[col_idx[e]].push_back(k);
+        }
+        for (int c = 0; c < m; ++c) order[c] = c;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return colour[a] < colour[b]; });
+    }
+    std::vector<int> var_level((size_t)n, 0), level((size_t)m, 1);
+    int n_levels = m > 0 ? 1 : 0;
+    for (int i = 0; i < m; ++i) {
+        const int c = order[i];
+        int lv = 0;
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) lv = std::max(lv, var_level[col_idx[e]]);
+        level[c] = lv + 1;
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) var_level[col_idx[e]] = lv + 1;
+        n_levels = std::max(n_levels, lv + 1);
+    }
+    order_out = order;
+    std::stable_sort(order_out.begin(), order_out.end(), [&](int a, int b) { return level[a] < level[b]; });
+    level_ptr.assign((size_t)n_levels + 1, 0);
+    for (int c = 0; c < m; ++c) level_ptr[level[c]] += 1;
+    for (int l = 0; l < n_levels; ++l) level_ptr[l + 1] += level_ptr[l];
+    return QBP_OK;
+}
+
+static int check_csr(const int32_t* row_ptr, const int32_t* col_idx, int m, int n)
+{
+    if (!row_ptr || !col_idx) return fail(QBP_E_INVALID, "null pointer");
+    if (m < 1 || n < 1) return fail(QBP_E_INVALID, "m = %d, n = %d (need >= 1)", m, n);
+    if (row_ptr[0] != 0) return fail(QBP_E_INVALID, "row_ptr[0] must be 0");
+    for (int c = 0; c < m; ++c) {
+        if (row_ptr[c + 1] < row_ptr[c]) return fail(QBP_E_INVALID, "row_ptr decreases at row %d", c);
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) {
+            if (col_idx[e] < 0 || col_idx[e] >= n) return fail(QBP_E_INVALID, "column %d out of range in row %d", col_idx[e], c);
+            if (e > row_ptr[c] && col_idx[e] <= col_idx[e - 1])
+                return fail(QBP_E_INVALID, "columns of row %d are not strictly ascending", c);
+        }
+    }
+    return QBP_OK;
+}
+
+// Slots per workgroup: about one work item per thread in the widest level, at most LAYERED_MAX_SLOTS and what keeps
+// two workgroups' LDS on a CU; one slot always (qbp_layered_configure refuses what does not fit with one).
+static int layered_slots(const qbp_handle* h, long long B, bool tables)
+{
+    int S = h->opt_layered_slots;
+    if (S <= 0) {
+        S = std::max(1, std::min(qbp::LAYERED_MAX_SLOTS, qbp::LAYERED_THREADS / std::max(1, h->layered_max_width)));
+        while (S > 1 && qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables) > (size_t)80 * 1024) --S;
+    }
+    while (S > 1 && qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables) > (size_t)160 * 1024) --S;
+    return (int)std::max<long long>(1, std::min<long long>(S, B));
+}
+
+static int layered_supported(const qbp_handle* h)
+{
+    const size_t lds = qbp::layered_lds_bytes(h->m, h->n, h->E, 1, true);
+    if (lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "layered BP keeps the messages, the posterior and the prior of a record in LDS: "
+                                       "%d x %d with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
+    return QBP_OK;
+}
+
+// QBP_FLAG_LAYERED of a call (host only, before any GPU work).  `other_entry`: the entries without a layered build
+// (budgets, spectra, recorded shots, message dumps).
+static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry)
+{
+    if (!(flags & QBP_FLAG_LAYERED)) return QBP_OK;
+    if (other_entry)
+        return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_LAYERED is not available with iteration budgets, spectra, recorded shots "
+                                       "or message dumps");
+    if (!h->layered_ready) return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED without qbp_layered_configure");
+    if (variant == QBP_DAMPED_SP) return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with QBP_DAMPED_SP: no damped layered schedule");
+    if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0))
+        return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with a column-sum order flag: the layered schedule has no column sum");
+    return QBP_OK;
+}
+
+static int check_finite_prior(const qbp_handle* h, const double* prior)
+{
+    for (int v = 0; v < h->n; ++v)
+        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite (QBP_FLAG_LAYERED)", v);
+    return QBP_OK;
+}
+
+// One launch of bp_layered_kernel (device pointers): the batch build, or (c.mc) the Monte-Carlo build on stored errors
+static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
+{
+    constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
+    if (c.B > MAX_LAUNCH)
+        return fail(QBP_E_UNSUPPORTED, "layered BP decodes at most 2^30 syndromes per call (got %lld)", c.B);
+    const bool tables = c.variant == QBP_SUM_PRODUCT;
+    const int S = layered_slots(h, c.B, tables);
+    const size_t lds = qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables);
+    // resident workgroups per CU: the LDS, and five wavefronts per SIMD at the kernel's registers
+    int per_cu = (int)std::max<size_t>(1, std::min<size_t>(5, ((size_t)160 * 1024) / lds));
+    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
+    const long long groups = (c.B + S - 1) / S;
+    const int grid = (int)std::max<long long>(1, std::min<long long>(groups, (long long)h->num_cu * per_cu));
+    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    qbp::LayeredParams P{};
+    P.m = h->m; P.n = h->n; P.E = h->E; P.n_levels = h->layered_levels; P.S = S;
+    P.row_ptr = h->d_row_ptr.p; P.col_idx = h->d_col_idx.p;
+    P.order = h->d_layered_order.p; P.level_ptr = h->d_layered_level_ptr.p;
+    P.prior = c.prior; P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    P.max_iter = c.max_iter; P.flags = (c.flags & QBP_FLAG_FORCE_FULL) ? qbp::LAYERED_FORCE_FULL : 0u;
+    P.alpha = c.alpha; P.clip_llr = c.clip_llr; P.B = c.B;
+    P.syndromes = c.syndromes; P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr;
+    if (c.mc) {
+        P.errors_in = c.mc->errors_in; P.lx_cols = c.mc->lx_cols; P.half_distance = c.mc->half_distance;
+        P.counters = c.mc->counters;
+        P.fail_list = c.mc->fail_list; P.fail_count = c.mc->fail_count; P.fail_syn = c.mc->fail_syn;
+        P.fail_hard = c.mc->fail_hard; P.fail_err = c.mc->fail_err; P.fail_llr = c.mc->fail_llr;
+    }
+    h->last_threads = qbp::LAYERED_THREADS; h->last_lds = (int)lds; h->last_grid = grid;
+    HIP_TRY(qbp::launch_layered(c.mc != nullptr, c.variant, P, grid, lds, s));
+    return QBP_OK;
+}
+
+int qbp_layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* order_in,
+                     int32_t* order_out, int32_t* level_ptr, int32_t* n_levels)
+try {
+    int rc = check_csr(row_ptr, col_idx, m, n);
+    if (rc) return rc;
+    if (!order_out || !level_ptr || !n_levels) return fail(QBP_E_INVALID, "null output pointer");
+    std::vector<int32_t> order, lptr;
+    if ((rc = layered_plan(row_ptr, col_idx, m, n, order_in, order, lptr)) != QBP_OK) return rc;
+    std::copy(order.begin(), order.end(), order_out);
+    std::fill(level_ptr, level_ptr + m + 1, (int32_t)m);
+    std::copy(lptr.begin(), lptr.end(), level_ptr);
+    *n_levels = (int32_t)lptr.size() - 1;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_layered_configure(qbp_handle* h, const int32_t* order)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    int rc = layered_supported(h);
+    if (rc) return rc;
+    std::vector<int32_t> ord, lptr;
+    if ((rc = layered_plan(h->row_ptr.data(), h->col_idx.data(), h->m, h->n, order, ord, lptr)) != QBP_OK) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    HIP_TRY(hipStreamSynchronize(h->stream));       // (a launch of this handle's stream may still read the old tables)
+    h->layered_ready = false;
+    HIP_TRY(h->d_layered_order.upload(ord));
+    HIP_TRY(h->d_layered_level_ptr.upload(lptr));
+    h->layered_levels = (int)lptr.size() - 1;
+    h->layered_max_width = 1;
+    for (size_t l = 0; l + 1 < lptr.size(); ++l) h->layered_max_width = std::max(h->layered_max_width, lptr[l + 1] - lptr[l]);
+    h->layered_ready = true;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 // ---- Relay-BP (qbp_relay.hpp) ------------------------------------------------------------------------------------
 // The kernel keeps a record's whole state in LDS: matrices beyond that are QBP_E_UNSUPPORTED.
 static int relay_supported(const qbp_handle* h, bool records)
@@ -1952,6 +2165,7 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
                        int32_t n_budgets = 0, int64_t* d_spectrum = nullptr, int64_t* d_iter_hist = nullptr)
 {
     const int64_t T = trial_end - trial_begin;
+    const uint32_t flags_in = flags;
     const size_t rows = budgets ? (size_t)n_budgets : 1;       // counter rows = failure-record planes
     if (budgets) max_iter = budgets[n_budgets - 1];
     int rc = check_decode_args(h, T, max_iter, variant);
@@ -1960,6 +2174,9 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     const bool relay = (flags & QBP_FLAG_RELAY) != 0;
     if ((rc = check_relay_flags(h, flags, budgets != nullptr || d_spectrum != nullptr)) != QBP_OK) return rc;
     flags &= ~(uint32_t)QBP_FLAG_RELAY;
+    // the layered schedule as the first stage: its kernel decodes stored errors only
+    const bool layered = (flags & QBP_FLAG_LAYERED) != 0;
+    if ((rc = check_layered_flags(h, flags, variant, budgets != nullptr || d_spectrum != nullptr)) != QBP_OK) return rc;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
     int osd_method = 0, osd_order = 0;
     rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order);
@@ -1977,6 +2194,23 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     rc = mc_prepare(h, Lx_host, k, s);
     if (rc) return rc;
     if (probs && (rc = mc_prepare_thr(h, probs, s)) != QBP_OK) return rc;
+    if (layered && !d_errors_in) {
+        // sampled trials: the errors qbp_mc_sample_errors[_probs] returns, drawn chunk by chunk into the handle's
+        // buffer and run as stored errors (as qbp_mc_run_weight does; the pipeline indexes a chunk's trials from 0)
+        const size_t n = (size_t)h->n;
+        const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)n));
+        const long long chunk = std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
+        HIP_TRY(h->d_weight_err.reserve((size_t)chunk * n));
+        for (int64_t a = trial_begin; a < trial_end; a += chunk) {
+            const long long t = std::min<long long>(chunk, trial_end - a);
+            if (probs) HIP_TRY(qbp::launch_mc_sample_cols(h->d_weight_err.p, h->n, t, a, draws, seed, h->d_mc_thr.p, s));
+            else HIP_TRY(qbp::launch_mc_sample(h->d_weight_err.p, h->n, t, a, draws, seed, mc_threshold(p), s));
+            rc = mc_run_impl(h, Lx_host, k, distance, 0.0, nullptr, 1, 0, 0, t, h->d_weight_err.p, d_prior, max_iter,
+                             variant, alpha, damping, clip_llr, flags_in, d_counters, s);
+            if (rc) return rc;
+        }
+        return QBP_OK;
+    }
     const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay;
     if (osd) {
         // per-trial records of the trials BP leaves unconverged (read by the OSD kernel, or the Relay-BP one)
@@ -2015,7 +2249,11 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
     // (likewise the iteration histogram of qbp_mc_run_spectrum)
     const bool hist_fits = !d_spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false, qbp::NUM_COUNTERS,
                                                           max_iter + 1) <= 160 * 1024;
-    if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits || !hist_fits) {
+    if (layered) {
+        c.flags = 0;                 // (forced iterations cannot change a count: the kernel's Monte-Carlo build exits early)
+        h->last_kernel = 4;
+        rc = layered_launch(h, c, s);
+    } else if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits || !hist_fits) {
         h->last_kernel = 2;
         rc = generic_launch(h, c, s);
     } else {
@@ -2069,6 +2307,10 @@ try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (!errors || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
     if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    if (flags & QBP_FLAG_LAYERED) {
+        const int rcl = check_finite_prior(h, prior);
+        if (rcl) return rcl;
+    }
     for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] = 0;
     if (T == 0) return QBP_OK;
     DeviceScope on_device(h->device);
@@ -2099,6 +2341,10 @@ int qbp_mc_run(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, do
 try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    if (flags & QBP_FLAG_LAYERED) {
+        const int rcl = check_finite_prior(h, prior);
+        if (rcl) return rcl;
+    }
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     hipStream_t s = h->stream;
@@ -2164,6 +2410,7 @@ try {
     if ((rc = check_decode_args(h, T, max_iter, variant)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
     if ((rc = check_relay_flags(h, flags, false)) != QBP_OK) return rc;
+    if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
     if ((rc = parse_osd_flags(h, flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order)) != QBP_OK) return rc;
     if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
     if (k > 0 && !Lx_host) return fail(QBP_E_INVALID, "Lx is null");
@@ -2195,6 +2442,10 @@ int qbp_mc_run_weight(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t dista
 try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    if (flags & QBP_FLAG_LAYERED) {
+        const int rcl = check_finite_prior(h, prior);
+        if (rcl) return rcl;
+    }
     int rc = check_weight(h, weight, trial_begin);
     if (rc) return rc;
     DeviceScope on_device(h->device);
@@ -2259,6 +2510,10 @@ int qbp_mc_run_probs(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distan
 try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
+    if (flags & QBP_FLAG_LAYERED) {
+        const int rcl = check_finite_prior(h, prior);
+        if (rcl) return rcl;
+    }
     int rc = check_probs(h, probs);
     if (rc) return rc;
     DeviceScope on_device(h->device);
@@ -2475,6 +2730,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if (!Lx || !det_bits || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
     if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k = %d observables (need 1..64)", k);
     if ((rc = check_relay_flags(h, flags, true)) != QBP_OK) return rc;
+    if ((rc = check_layered_flags(h, flags, 0, true)) != QBP_OK) return rc;
     if (host_prior)
         for (int v = 0; v < h->n; ++v)
             if (host_prior[v] != host_prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
@@ -2655,6 +2911,9 @@ try {
         case QBP_OPT_MC_WEIGHT_CHUNK:
             if (value < 0 || value > (1 << 20)) return fail(QBP_E_INVALID, "trials per chunk out of [0, 2^20]");
             h->opt_weight_chunk = value; return QBP_OK;
+        case QBP_OPT_LAYERED_SLOTS:
+            if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
+            h->opt_layered_slots = (int)value; return QBP_OK;
         case QBP_OPT_GENERAL_THREADS:
             if (value < 0 || value > 1024) return fail(QBP_E_INVALID, "threads per workgroup out of range");
             h->opt_threads = (int)value; return QBP_OK;

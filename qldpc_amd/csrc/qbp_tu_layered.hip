@@ -1,0 +1,40 @@
+// libqbp.so, translation unit of the layered BP kernel (qbp_layered.hpp): sum-product and min-sum, the batch build and
+// the Monte-Carlo build.
+#include <hip/hip_runtime.h>
+
+#include "../../include/qbp.h"
+#include "qbp_layered.hpp"
+#include "qbp_launch.hpp"
+
+namespace qbp {
+namespace {
+
+template <int VARIANT, bool MC>
+hipError_t layered_launch_k(const LayeredParams& P, int grid, size_t lds, hipStream_t s)
+{
+    auto kern = bp_layered_kernel<VARIANT, MC>;
+    static thread_local size_t lds_set[64] = {0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(LAYERED_THREADS), lds, s, P);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s)
+{
+    if (variant == QBP_MIN_SUM)
+        return mc ? layered_launch_k<2, true>(P, grid, lds, s) : layered_launch_k<2, false>(P, grid, lds, s);
+    if (variant == QBP_SUM_PRODUCT)
+        return mc ? layered_launch_k<0, true>(P, grid, lds, s) : layered_launch_k<0, false>(P, grid, lds, s);
+    return hipErrorInvalidValue;
+}
+
+}  // namespace qbp

@@ -86,10 +86,28 @@ def _configure_relay(dec, relay):
         dec.relay_configure(relay_mod.as_config(relay, dec.n))
 
 
+def layered_run_flags(flags, layered, variant) -> int:
+    """``flags`` of a sweep with ``layered`` (False / None, True = the default order, or a permutation of the checks):
+    | FLAG_LAYERED, BP runs the layered schedule.  ValueError with the damped variant, which has no layered form."""
+    if layered is None or layered is False:
+        return flags
+    if int(variant) == _lib.DAMPED_SP:
+        raise ValueError("layered=True needs variant sum-product or min-sum: there is no damped layered schedule")
+    return flags | _lib.FLAG_LAYERED
+
+
+def _configure_layered(dec, layered):
+    if layered is not None and layered is not False:
+        dec.layered_configure(None if layered is True else layered)
+
+
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
-              world=1, device=0, runner=None, all_reduce=None, relay=None):
+              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
+
+    ``layered``: True -- BP runs the layered (check-serial) schedule in its default order (FLAG_LAYERED); an array -- in
+    that order of the checks.  OSD and Relay act on what it leaves unconverged.
 
     ``relay``: a ``relay.RelayConfig`` or its dict form -- Relay-BP instead of OSD on the trials BP does not converge
     on (FLAG_RELAY; not together with ``osd``).
@@ -99,6 +117,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
+    flags = layered_run_flags(flags, layered, variant)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -107,6 +126,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
+        _configure_layered(dec, layered)
         dev = torch.device("cuda", device)
         d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev)
@@ -140,7 +160,8 @@ def dem_prior(probs) -> np.ndarray:
 
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
-            osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None):
+            osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
+            layered=False):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -150,8 +171,9 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     ``distance``: the "BPs_miscorrected" / "incorrectable" split compares the error weight with distance // 2;
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
-    tests; by default the HIP library and torch.distributed.  ``relay``: as in ``run_sweep``."""
+    tests; by default the HIP library and torch.distributed.  ``relay``, ``layered``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
+    flags = layered_run_flags(flags, layered, variant)
     L = np.ascontiguousarray(L, np.uint8)
     probs = np.ascontiguousarray(probs, np.float64)
     n = H.shape[1]
@@ -171,6 +193,7 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         from . import bp
         dec = bp.decoder_for(H, device=device)
         _configure_relay(dec, relay)
+        _configure_layered(dec, layered)
         dev = torch.device("cuda", device)
         d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
         stream = torch.cuda.current_stream(dev)
@@ -508,15 +531,16 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
-                device=0, runner=None, all_reduce=None, relay=None):
+                device=0, runner=None, all_reduce=None, relay=None, layered=False):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed.  ``relay``: as in ``run_sweep``."""
+    the HIP library and torch.distributed.  ``relay``, ``layered``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
+    flags = layered_run_flags(flags, layered, variant)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
@@ -524,6 +548,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
+        _configure_layered(dec, layered)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
@@ -722,6 +747,9 @@ def main(argv=None):
     ap.add_argument("--relay-gamma0", type=float, default=0.125, help="memory strength of leg 0, every variable")
     ap.add_argument("--relay-interval", type=float, nargs=2, default=(-0.24, 0.66), metavar=("LO", "HI"),
                     help="later legs draw a strength per variable uniformly from [LO, HI] (seeded by --seed)")
+    ap.add_argument("--layered", action="store_true",
+                    help="BP runs the layered (check-serial) schedule in its default order instead of flooding "
+                         "(sum-product or min-sum; not with --budgets, --spectrum, --shots)")
     ap.add_argument("--relay-stop", type=int, default=1, metavar="S", help="stop after S solutions, keep the lightest")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
@@ -747,6 +775,11 @@ def main(argv=None):
             relay_mod.as_config(relay, 1)
         except (ValueError, TypeError) as e:
             ap.error(f"--relay: {e}")
+    if args.layered:
+        if args.budgets is not None or args.spectrum is not None or args.shots is not None:
+            ap.error("--layered does not combine with --budgets, --spectrum or --shots")
+        if args.variant == "damped":
+            ap.error("--layered needs --variant sum-product or min-sum")
     if args.budgets is not None:
         try:
             _lib.check_budgets(args.budgets)
@@ -889,18 +922,19 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               **common)
+                               layered=args.layered, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
-            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, **common)
+            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered,
+                             **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
-                           **common)[None, :]
+                           layered=args.layered, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

@@ -32,6 +32,8 @@ UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SHOTS_TU"])] +
 UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
 # Relay-BP (qbp_relay_decode_batch, QBP_FLAG_RELAY): bp_relay_kernel, batch and records builds
 UNITS += [("qbp_tu_relay.hip", [])]
+# Layered BP (QBP_FLAG_LAYERED): bp_layered_kernel<variant, mc>
+UNITS += [("qbp_tu_layered.hip", [])]
 
 
 def demangle(sym):
