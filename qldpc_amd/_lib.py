@@ -384,45 +384,60 @@ class Decoder:
         """Trials one qbp_mc_run call may cover with FLAG_OSD0 or FLAG_RELAY (per-trial records: m + 10 n bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
-    @_locked
-    def mc_run(self, Lx, distance, p, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
-               variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+    def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None):
+        """The host form ``fn`` of a sampled Monte-Carlo entry over [trial_begin, trial_end): ``source`` are its
+        arguments between distance and the range, ``limit`` those between the prior and the variant, ``decoder`` is
+        (variant, alpha, damping, clip_llr, flags) and ``outputs`` the int64 arrays it adds to, which are returned."""
         Lx = np.ascontiguousarray(Lx, np.uint8)
         pr = np.ascontiguousarray(prior, np.float64)
         if Lx.ndim != 2 or Lx.shape[1] != self.n:
             raise ValueError(f"Lx must have shape (k, {self.n})")
         if pr.shape != (self.n,):
             raise ValueError(f"prior must have shape ({self.n},)")
-        counters = np.zeros(NUM_COUNTERS, np.int64)
+        variant, alpha, damping, clip_llr, flags = decoder
+        begin, end = int(trial_begin), int(trial_end)
         # with OSD a call keeps per-trial records on the device: split long ranges
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
-        for a in range(int(trial_begin), int(trial_end), step):
-            _check(load().qbp_mc_run(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), float(p),
-                                     int(draws), int(seed), a, min(a + step, int(trial_end)),
-                                     pr.ctypes.data, int(max_iter), int(variant), float(alpha),
-                                     float(damping), float(clip_llr), int(flags), counters.ctypes.data))
-        return counters
+        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(end - begin, 1)
+        for a in range(begin, end, step):
+            _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), *source, a, min(a + step, end),
+                                       pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
+                                       float(clip_llr), int(flags), *(o.ctypes.data for o in outputs)))
+        return outputs
+
+    def _mc_stored(self, fn, Lx, distance, errors, prior, max_iter, decoder, tables=()):
+        """The host form ``fn`` of a stored-error entry on error patterns uint8[T, n]: the counters, summed over the
+        parts of a long list (a call SETS its counters); ``tables`` are added to by every part."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        err = np.ascontiguousarray(errors, np.uint8)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
+            raise ValueError("bad shapes")
+        variant, alpha, damping, clip_llr, flags = decoder
+        total = np.zeros(NUM_COUNTERS, np.int64)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
+        for a in range(0, len(err), step):
+            part = np.zeros(NUM_COUNTERS, np.int64)
+            chunk = err[a:a + step]
+            _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), chunk.ctypes.data, len(chunk),
+                                       pr.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping),
+                                       float(clip_llr), int(flags), part.ctypes.data, *(t.ctypes.data for t in tables)))
+            total += part
+        return total
+
+    @_locked
+    def mc_run(self, Lx, distance, p, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
+               variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        return self._mc_sampled("qbp_mc_run", Lx, distance, (float(p), int(draws), int(seed)), trial_begin, trial_end,
+                                prior, (int(max_iter),), (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros(NUM_COUNTERS, np.int64)])[0]
 
     @_locked
     def mc_run_errors(self, Lx, distance, errors, prior, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
                       clip_llr=20.0, flags=0):
         """Counters int64[12] of the device pipeline (syndrome = H e, BP, [OSD-0,] classification) on GIVEN
         error patterns uint8[T, n] instead of sampled ones (qbp_mc_run_errors)."""
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
-        err = np.ascontiguousarray(errors, np.uint8)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
-            raise ValueError("bad shapes")
-        total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
-        for a in range(0, len(err), step):
-            part = np.zeros(NUM_COUNTERS, np.int64)
-            chunk = err[a:a + step]
-            _check(load().qbp_mc_run_errors(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), chunk.ctypes.data,
-                                            len(chunk), pr.ctypes.data, int(max_iter), int(variant), float(alpha),
-                                            float(damping), float(clip_llr), int(flags), part.ctypes.data))
-            total += part
-        return total
+        return self._mc_stored("qbp_mc_run_errors", Lx, distance, errors, prior, max_iter,
+                               (variant, alpha, damping, clip_llr, flags))
 
     def mc_run_device(self, Lx, distance, p, d_prior, trial_begin, trial_end, d_counters, draws=1,
                       seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -443,21 +458,10 @@ class Decoder:
     def mc_run_probs(self, Lx, distance, probs, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
                      variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
         """``mc_run`` with a probability per column (detector error models: qbp_mc_run_probs)."""
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
         probs = self._probs(probs)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n:
-            raise ValueError(f"Lx must have shape (k, {self.n})")
-        if pr.shape != (self.n,):
-            raise ValueError(f"prior must have shape ({self.n},)")
-        counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
-        for a in range(int(trial_begin), int(trial_end), step):
-            _check(load().qbp_mc_run_probs(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
-                                           int(draws), int(seed), a, min(a + step, int(trial_end)),
-                                           pr.ctypes.data, int(max_iter), int(variant), float(alpha),
-                                           float(damping), float(clip_llr), int(flags), counters.ctypes.data))
-        return counters
+        return self._mc_sampled("qbp_mc_run_probs", Lx, distance, (probs.ctypes.data, int(draws), int(seed)), trial_begin,
+                                trial_end, prior, (int(max_iter),), (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros(NUM_COUNTERS, np.int64)])[0]
 
     def mc_run_probs_device(self, Lx, distance, probs, d_prior, trial_begin, trial_end, d_counters, draws=1,
                             seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -476,20 +480,9 @@ class Decoder:
                       variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
         """``mc_run`` on errors of exactly ``weight`` ones, uniform among the C(n, weight) patterns
         (qbp_mc_run_weight): counters int64[12] of trials [trial_begin, trial_end)."""
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n:
-            raise ValueError(f"Lx must have shape (k, {self.n})")
-        if pr.shape != (self.n,):
-            raise ValueError(f"prior must have shape ({self.n},)")
-        counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
-        for a in range(int(trial_begin), int(trial_end), step):
-            _check(load().qbp_mc_run_weight(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight),
-                                            int(seed), a, min(a + step, int(trial_end)), pr.ctypes.data,
-                                            int(max_iter), int(variant), float(alpha), float(damping),
-                                            float(clip_llr), int(flags), counters.ctypes.data))
-        return counters
+        return self._mc_sampled("qbp_mc_run_weight", Lx, distance, (int(weight), int(seed)), trial_begin, trial_end,
+                                prior, (int(max_iter),), (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros(NUM_COUNTERS, np.int64)])[0]
 
     def mc_run_weight_device(self, Lx, distance, weight, d_prior, trial_begin, trial_end, d_counters, seed=0,
                              max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
@@ -525,23 +518,12 @@ class Decoder:
         weights of rework/main.py's list r (weights_found_BP, _OSD, _BP_error, _OSD_error); bin k of ``iter_hist``
         counts the trials first satisfied in iteration k, bin max_iter those BP did not converge on.  ``probs``: one
         probability per column, or a scalar p.  Given ``spectrum`` / ``iter_hist`` arrays are added to."""
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
         probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n:
-            raise ValueError(f"Lx must have shape (k, {self.n})")
-        if pr.shape != (self.n,):
-            raise ValueError(f"prior must have shape ({self.n},)")
         spectrum, iter_hist = self._spectrum_tables(max_iter, spectrum, iter_hist)
-        counters = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
-        for a in range(int(trial_begin), int(trial_end), step):
-            _check(load().qbp_mc_run_spectrum(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
-                                              int(draws), int(seed), a, min(a + step, int(trial_end)),
-                                              pr.ctypes.data, int(max_iter), int(variant), float(alpha),
-                                              float(damping), float(clip_llr), int(flags), counters.ctypes.data,
-                                              spectrum.ctypes.data, iter_hist.ctypes.data))
-        return counters, spectrum, iter_hist
+        return tuple(self._mc_sampled("qbp_mc_run_spectrum", Lx, distance, (probs.ctypes.data, int(draws), int(seed)),
+                                      trial_begin, trial_end, prior, (int(max_iter),),
+                                      (variant, alpha, damping, clip_llr, flags),
+                                      [np.zeros(NUM_COUNTERS, np.int64), spectrum, iter_hist]))
 
     def mc_run_spectrum_device(self, Lx, distance, probs, d_prior, trial_begin, trial_end, d_counters, d_spectrum,
                                d_iter_hist=0, draws=1, seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0,
@@ -562,22 +544,9 @@ class Decoder:
                                damping=1.0, clip_llr=20.0, flags=0):
         """``mc_run_errors`` plus the two tables of ``mc_run_spectrum`` on GIVEN error patterns uint8[T, n]
         (qbp_mc_run_errors_spectrum): ``(counters, spectrum, iter_hist)``."""
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
-        err = np.ascontiguousarray(errors, np.uint8)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
-            raise ValueError("bad shapes")
         spectrum, iter_hist = self._spectrum_tables(max_iter, None, None)
-        total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
-        for a in range(0, len(err), step):
-            part = np.zeros(NUM_COUNTERS, np.int64)
-            chunk = err[a:a + step]
-            _check(load().qbp_mc_run_errors_spectrum(
-                self._h, Lx.ctypes.data, Lx.shape[0], int(distance), chunk.ctypes.data, len(chunk), pr.ctypes.data,
-                int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags),
-                part.ctypes.data, spectrum.ctypes.data, iter_hist.ctypes.data))
-            total += part
+        total = self._mc_stored("qbp_mc_run_errors_spectrum", Lx, distance, errors, prior, max_iter,
+                                (variant, alpha, damping, clip_llr, flags), (spectrum, iter_hist))
         return total, spectrum, iter_hist
 
     @_locked
@@ -641,21 +610,11 @@ class Decoder:
         """Counters int64[K, 12] of ONE pass over the trials: row j is ``mc_run_probs(..., max_iter=budgets[j])``
         (qbp_mc_run_budgets; ``probs``: one probability per column, or a scalar p for all of them)."""
         bud = check_budgets(budgets)
-        Lx = np.ascontiguousarray(Lx, np.uint8)
-        pr = np.ascontiguousarray(prior, np.float64)
         probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
-        if Lx.ndim != 2 or Lx.shape[1] != self.n:
-            raise ValueError(f"Lx must have shape (k, {self.n})")
-        if pr.shape != (self.n,):
-            raise ValueError(f"prior must have shape ({self.n},)")
-        counters = np.zeros((len(bud), NUM_COUNTERS), np.int64)
-        step = self.mc_budgets_step(len(bud)) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(int(trial_end) - int(trial_begin), 1)
-        for a in range(int(trial_begin), int(trial_end), step):
-            _check(load().qbp_mc_run_budgets(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data,
-                                             int(draws), int(seed), a, min(a + step, int(trial_end)),
-                                             pr.ctypes.data, bud.ctypes.data, len(bud), int(variant), float(alpha),
-                                             float(damping), float(clip_llr), int(flags), counters.ctypes.data))
-        return counters
+        return self._mc_sampled("qbp_mc_run_budgets", Lx, distance, (probs.ctypes.data, int(draws), int(seed)),
+                                trial_begin, trial_end, prior, (bud.ctypes.data, len(bud)),
+                                (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros((len(bud), NUM_COUNTERS), np.int64)], step=self.mc_budgets_step(len(bud)))[0]
 
     def mc_run_budgets_device(self, Lx, distance, probs, d_prior, budgets, trial_begin, trial_end, d_counters,
                               draws=1, seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,

@@ -2152,122 +2152,187 @@ try {
 }
 QBP_ABI_CATCH
 
-// probs: host per-column probabilities (qbp_mc_run_probs; p unused), else null.
-// budgets (checked by the caller; needs probs): qbp_mc_run_budgets -- max_iter is unused, d_counters is
-// [n_budgets][QBP_NUM_COUNTERS]; else null / 0.
-// d_spectrum (not with budgets): qbp_mc_run_spectrum -- [QBP_SPECTRUM_ROWS][n + 1] and d_iter_hist [max_iter + 1] (may
-// be null), device, added to; with d_errors_in too (qbp_mc_run_errors_spectrum); else null.
-static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
-                       double p, const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
-                       int64_t trial_end, const uint8_t* d_errors_in, const double* d_prior, int32_t max_iter,
-                       int32_t variant, double alpha, double damping, double clip_llr,
-                       uint32_t flags, int64_t* d_counters, void* stream, const int32_t* budgets = nullptr,
-                       int32_t n_budgets = 0, int64_t* d_spectrum = nullptr, int64_t* d_iter_hist = nullptr)
+// ---- Monte-Carlo (include/qbp.h: qbp_mc_run*) --------------------------------------------------------------------
+
+// Where the errors of a Monte-Carlo call come from; only the fields of `kind` are read.
+struct McErrors {
+    enum Kind { P, PROBS, WEIGHT, STORED } kind = P;
+    int32_t draws = 1;                       // P, PROBS
+    uint64_t seed = 0;                       // all but STORED
+    double p = 0.0;                          // P: every column fails with p
+    const double* probs = nullptr;           // PROBS: a probability per column, host [n]
+    int32_t weight = 0;                      // WEIGHT: exactly this many ones, uniform among the patterns
+    const uint8_t* d_errors = nullptr;       // STORED: device [trials, n]; the trial range starts at 0
+};
+
+struct McDecoder {
+    int32_t max_iter = 0;                    // (McCall::LADDER: the last budget instead)
+    int32_t variant = 0;
+    double alpha = 1.0, damping = 1.0, clip_llr = 0.0;
+    uint32_t flags = 0;
+};
+
+// One Monte-Carlo call, whichever entry it came through (device pointers but Lx, errors.probs and budgets).
+struct McCall {
+    McErrors errors;
+    int64_t trial_begin = 0, trial_end = 0;
+    const uint8_t* Lx = nullptr;             // host [k, n]
+    int32_t k = 0, distance = 0;
+    McDecoder dec;
+    const double* d_prior = nullptr;
+    // the outputs, all added to
+    enum Out { COUNTERS, LADDER, SPECTRUM } out = COUNTERS;   // qbp_mc_run_budgets*: LADDER, qbp_mc_run*_spectrum*: SPECTRUM
+    int64_t* d_counters = nullptr;           // [rows()][QBP_NUM_COUNTERS]
+    const int32_t* budgets = nullptr;        // LADDER: host [n_budgets], a counter row each
+    int32_t n_budgets = 0;
+    int64_t* d_spectrum = nullptr;           // SPECTRUM: [QBP_SPECTRUM_ROWS][n + 1]
+    int64_t* d_iter_hist = nullptr;          // SPECTRUM: [max_iter + 1], may be null
+
+    int64_t trials() const { return trial_end - trial_begin; }
+    size_t rows() const { return out == LADDER ? (size_t)n_budgets : 1; }     // counter rows = failure-record planes
+    int32_t last_iter() const { return out == LADDER ? budgets[n_budgets - 1] : dec.max_iter; }
+    // sampled trials that no BP kernel draws itself: fixed weight, and the layered kernel, which decodes stored errors only
+    bool chunked() const
+    {
+        return errors.kind == McErrors::WEIGHT || (errors.kind != McErrors::STORED && (dec.flags & QBP_FLAG_LAYERED));
+    }
+};
+
+// Trials sampled into the handle's buffer and decoded per chunk of a chunked() call of T trials
+static long long mc_chunk_trials(const qbp_handle* h, int64_t T)
 {
-    const int64_t T = trial_end - trial_begin;
-    const uint32_t flags_in = flags;
-    const size_t rows = budgets ? (size_t)n_budgets : 1;       // counter rows = failure-record planes
-    if (budgets) max_iter = budgets[n_budgets - 1];
-    int rc = check_decode_args(h, T, max_iter, variant);
-    if (rc) return rc;
+    const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)h->n));
+    return std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
+}
+
+static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial_begin)
+{
+    if (e.kind == McErrors::STORED) return e.d_errors ? QBP_OK : fail(QBP_E_INVALID, "null pointer");
+    if (e.kind == McErrors::WEIGHT) {
+        if (e.weight < 0 || e.weight > h->n)
+            return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", e.weight, h->n);
+    } else {
+        if (e.draws != 1 && e.draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", e.draws);
+        if (e.kind == McErrors::P && !(e.p >= 0.0 && e.p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", e.p);
+        const int rc = e.kind == McErrors::PROBS ? check_probs(h, e.probs) : QBP_OK;
+        if (rc) return rc;
+    }
+    if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
+    return QBP_OK;
+}
+
+// Everything a Monte-Carlo call refuses: host only, once per public call, for the whole range and before any GPU work.
+// `host_prior`: the priors when they are a host array (the layered schedule's finite check), else null.
+static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prior)
+{
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!c.d_prior || !c.d_counters) return fail(QBP_E_INVALID, "null pointer");
+    int rc = QBP_OK;
+    if (c.out == McCall::SPECTRUM) {
+        if (!c.d_spectrum) return fail(QBP_E_INVALID, "spectrum is null");
+        if (c.dec.max_iter > QBP_MC_SPECTRUM_MAX_ITER)
+            return fail(QBP_E_INVALID, "max_iter = %d beyond QBP_MC_SPECTRUM_MAX_ITER = %d", c.dec.max_iter,
+                        QBP_MC_SPECTRUM_MAX_ITER);
+    }
+    if (c.out == McCall::LADDER && (rc = check_budgets(c.budgets, c.n_budgets)) != QBP_OK) return rc;
+    if ((rc = check_mc_errors(h, c.errors, c.trial_begin)) != QBP_OK) return rc;
+    if ((rc = check_decode_args(h, c.trials(), c.last_iter(), c.dec.variant)) != QBP_OK) return rc;
+    // ladders and spectra have neither a Relay stage nor a layered build
+    if ((rc = check_relay_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
+    if ((rc = check_layered_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
+    if (host_prior && (c.dec.flags & QBP_FLAG_LAYERED) && (rc = check_finite_prior(h, host_prior)) != QBP_OK) return rc;
+    int osd_method = 0, osd_order = 0;
+    if ((rc = parse_osd_flags(h, c.dec.flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order)) != QBP_OK) return rc;
+    if (c.k < 0 || c.k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", c.k);
+    if (c.k > 0 && !c.Lx) return fail(QBP_E_INVALID, "Lx is null");
+    if (c.dec.flags & (QBP_FLAG_OSD0 | QBP_FLAG_RELAY)) {
+        // QBP_MC_OSD_MAX_TRIALS bounds the records of one launch.  That is the whole call -- a fixed-weight call too,
+        // although it launches chunk by chunk -- except for layered sampled calls, which have always been held to it
+        // per chunk only: a longer range of those goes through.
+        const bool per_chunk = c.chunked() && c.errors.kind != McErrors::WEIGHT;
+        rc = check_mc_osd_trials(h, per_chunk ? mc_chunk_trials(h, c.trials()) : c.trials(), c.rows());
+    }
+    return rc;
+}
+
+// Per-trial records of the trials the BP launch leaves unconverged, read by the second kernel (OSD or Relay-BP):
+// room for `t` trials in each of `rows` planes, the planes' counts zeroed, all of it named in `mc`.  `error_rows`:
+// the trial's error as well (recorded shots have none).
+static int mc_fail_records(qbp_handle* h, McArgs& mc, size_t rows, size_t t, bool error_rows, hipStream_t s)
+{
+    const size_t m = h->m, n = h->n;
+    t *= rows;
+    HIP_TRY(h->d_fail_count.reserve(rows));
+    HIP_TRY(h->d_fail_list.reserve(t));
+    HIP_TRY(h->d_fail_syn.reserve(t * m));
+    HIP_TRY(h->d_fail_llr.reserve(t * n));
+    HIP_TRY(h->d_fail_hard.reserve(t * n));
+    if (error_rows) HIP_TRY(h->d_fail_err.reserve(t * n));
+    HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, rows * sizeof(unsigned long long), s));
+    mc.fail_list = h->d_fail_list.p; mc.fail_count = h->d_fail_count.p;
+    mc.fail_syn = h->d_fail_syn.p; mc.fail_llr = h->d_fail_llr.p; mc.fail_hard = h->d_fail_hard.p;
+    if (error_rows) mc.fail_err = h->d_fail_err.p;
+    return QBP_OK;
+}
+
+// The launches of a checked call whose BP kernel draws the errors itself, or reads stored ones: BP and
+// classification, then the second stage on the trials BP left unconverged.  The Lx columns (mc_prepare) and the
+// thresholds of errors.probs (mc_prepare_thr) are on the device.
+static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
+{
+    const int64_t T = c.trials();
+    const size_t rows = c.rows();
+    const bool ladder = c.out == McCall::LADDER, spectrum = c.out == McCall::SPECTRUM;
+    const int32_t max_iter = c.last_iter();
     // Relay-BP instead of OSD on the trials the first stage leaves unconverged: its bit goes to no BP launch
-    const bool relay = (flags & QBP_FLAG_RELAY) != 0;
-    if ((rc = check_relay_flags(h, flags, budgets != nullptr || d_spectrum != nullptr)) != QBP_OK) return rc;
-    flags &= ~(uint32_t)QBP_FLAG_RELAY;
-    // the layered schedule as the first stage: its kernel decodes stored errors only
-    const bool layered = (flags & QBP_FLAG_LAYERED) != 0;
-    if ((rc = check_layered_flags(h, flags, variant, budgets != nullptr || d_spectrum != nullptr)) != QBP_OK) return rc;
+    const bool relay = (c.dec.flags & QBP_FLAG_RELAY) != 0;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
     int osd_method = 0, osd_order = 0;
-    rc = parse_osd_flags(h, flags, true, &osd_method, &osd_order);
+    int rc = parse_osd_flags(h, c.dec.flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order);
     if (rc) return rc;
-    flags &= ~OSD_ALL_BITS;
-    if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
-    if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", draws);
-    if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", p);
-    if (!d_prior || !d_counters) return fail(QBP_E_INVALID, "null pointer");
-    if (probs && (rc = check_probs(h, probs)) != QBP_OK) return rc;
-    if (T == 0) return QBP_OK;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = mc_prepare(h, Lx_host, k, s);
-    if (rc) return rc;
-    if (probs && (rc = mc_prepare_thr(h, probs, s)) != QBP_OK) return rc;
-    if (layered && !d_errors_in) {
-        // sampled trials: the errors qbp_mc_sample_errors[_probs] returns, drawn chunk by chunk into the handle's
-        // buffer and run as stored errors (as qbp_mc_run_weight does; the pipeline indexes a chunk's trials from 0)
-        const size_t n = (size_t)h->n;
-        const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)n));
-        const long long chunk = std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
-        HIP_TRY(h->d_weight_err.reserve((size_t)chunk * n));
-        for (int64_t a = trial_begin; a < trial_end; a += chunk) {
-            const long long t = std::min<long long>(chunk, trial_end - a);
-            if (probs) HIP_TRY(qbp::launch_mc_sample_cols(h->d_weight_err.p, h->n, t, a, draws, seed, h->d_mc_thr.p, s));
-            else HIP_TRY(qbp::launch_mc_sample(h->d_weight_err.p, h->n, t, a, draws, seed, mc_threshold(p), s));
-            rc = mc_run_impl(h, Lx_host, k, distance, 0.0, nullptr, 1, 0, 0, t, h->d_weight_err.p, d_prior, max_iter,
-                             variant, alpha, damping, clip_llr, flags_in, d_counters, s);
-            if (rc) return rc;
-        }
-        return QBP_OK;
-    }
+    const uint32_t flags = c.dec.flags & ~((uint32_t)QBP_FLAG_RELAY | OSD_ALL_BITS);
+    const bool layered = (flags & QBP_FLAG_LAYERED) != 0;
     const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay;
-    if (osd) {
-        // per-trial records of the trials BP leaves unconverged (read by the OSD kernel, or the Relay-BP one)
-        // (qbp_mc_run_budgets: a record per trial and budget)
-        const size_t t = (size_t)T * rows, m = h->m, n = h->n;
-        if ((rc = check_mc_osd_trials(h, T, rows)) != QBP_OK) return rc;
-        HIP_TRY(h->d_fail_count.reserve(rows));
-        HIP_TRY(h->d_fail_list.reserve(t));
-        HIP_TRY(h->d_fail_syn.reserve(t * m));
-        HIP_TRY(h->d_fail_llr.reserve(t * n));
-        HIP_TRY(h->d_fail_hard.reserve(t * n));
-        HIP_TRY(h->d_fail_err.reserve(t * n));
-        HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, rows * sizeof(unsigned long long), s));
-    }
     McArgs mc{};
-    mc.n_budgets = budgets ? n_budgets : 0; mc.budgets = budgets;
-    mc.spectrum = reinterpret_cast<long long*>(d_spectrum); mc.iter_hist = reinterpret_cast<long long*>(d_iter_hist);
-    mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = trial_begin; mc.seed = seed;
-    mc.threshold = mc_threshold(p); mc.draws = draws; mc.half_distance = distance / 2;
-    mc.thr_cols = probs ? h->d_mc_thr.p : nullptr;
-    mc.counters = reinterpret_cast<long long*>(d_counters);
-    mc.errors_in = d_errors_in;
-    if (osd) {
-        mc.fail_list = h->d_fail_list.p; mc.fail_count = h->d_fail_count.p;
-        mc.fail_syn = h->d_fail_syn.p; mc.fail_llr = h->d_fail_llr.p;
-        mc.fail_hard = h->d_fail_hard.p; mc.fail_err = h->d_fail_err.p;
-    }
-    BpCall c;
-    c.prior = d_prior; c.B = T; c.max_iter = max_iter; c.variant = variant;
-    c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
-    c.mc = &mc;
+    // (qbp_mc_run_budgets: a record per trial and budget)
+    if (osd && (rc = mc_fail_records(h, mc, rows, (size_t)T, true, s)) != QBP_OK) return rc;
+    mc.n_budgets = ladder ? c.n_budgets : 0; mc.budgets = ladder ? c.budgets : nullptr;
+    mc.spectrum = reinterpret_cast<long long*>(c.d_spectrum); mc.iter_hist = reinterpret_cast<long long*>(c.d_iter_hist);
+    mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = c.trial_begin; mc.seed = c.errors.seed;
+    mc.threshold = mc_threshold(c.errors.p); mc.draws = c.errors.draws; mc.half_distance = c.distance / 2;
+    mc.thr_cols = c.errors.kind == McErrors::PROBS ? h->d_mc_thr.p : nullptr;
+    mc.counters = reinterpret_cast<long long*>(c.d_counters);
+    mc.errors_in = c.errors.d_errors;
+    BpCall b;
+    b.prior = c.d_prior; b.B = T; b.max_iter = max_iter; b.variant = c.dec.variant;
+    b.alpha = c.dec.alpha; b.damping = c.dec.damping; b.clip_llr = c.dec.clip_llr; b.flags = flags;
+    b.mc = &mc;
     // (a ladder's counter rows need LDS of their own: a matrix that fills the on-chip kernel's to the last
     // kilobyte goes to the general-H kernel)
-    const bool ladder_fits = !budgets || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false,
-                                                         2 * n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
+    const bool ladder_fits = !ladder || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false,
+                                                        2 * c.n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
     // (likewise the iteration histogram of qbp_mc_run_spectrum)
-    const bool hist_fits = !d_spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false, qbp::NUM_COUNTERS,
-                                                          max_iter + 1) <= 160 * 1024;
+    const bool hist_fits = !spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false, qbp::NUM_COUNTERS,
+                                                        max_iter + 1) <= 160 * 1024;
     if (layered) {
-        c.flags = 0;                 // (forced iterations cannot change a count: the kernel's Monte-Carlo build exits early)
+        b.flags = 0;                 // (forced iterations cannot change a count: the kernel's Monte-Carlo build exits early)
         h->last_kernel = 4;
-        rc = layered_launch(h, c, s);
+        rc = layered_launch(h, b, s);
     } else if (bp_kernel(h, T, flags, 0, true) == 2 || !ladder_fits || !hist_fits) {
         h->last_kernel = 2;
-        rc = generic_launch(h, c, s);
+        rc = generic_launch(h, b, s);
     } else {
-        rc = fused_launch(h, c, s);
+        rc = fused_launch(h, b, s);
         if (rc == QBP_OK) h->last_kernel = 1;
     }
     if (rc || !osd) return rc;
     if (relay) {
         // second kernel: Relay-BP + classification of the trials the first stage left unconverged
         RelayCall r;
-        r.prior = d_prior; r.max_items = T;
+        r.prior = c.d_prior; r.max_items = T;
         r.fail_count = h->d_fail_count.p; r.fail_list = h->d_fail_list.p;
         r.fail_syn = h->d_fail_syn.p; r.fail_err = h->d_fail_err.p;
-        r.half_distance = distance / 2; r.counters = reinterpret_cast<long long*>(d_counters);
+        r.half_distance = c.distance / 2; r.counters = reinterpret_cast<long long*>(c.d_counters);
         return relay_launch(h, r, true, s);
     }
     // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
@@ -2280,13 +2345,135 @@ static int mc_run_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t
         O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p + j);
         O.list = h->d_fail_list.p + r0;
         O.syndromes = h->d_fail_syn.p + r0 * m; O.llr = h->d_fail_llr.p + r0 * n; O.hard = h->d_fail_hard.p + r0 * n;
-        O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->d_lx_cols.p; O.half_distance = distance / 2;
-        O.counters = reinterpret_cast<long long*>(d_counters) + j * qbp::NUM_COUNTERS;
-        O.spectrum = reinterpret_cast<long long*>(d_spectrum);
+        O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->d_lx_cols.p; O.half_distance = c.distance / 2;
+        O.counters = reinterpret_cast<long long*>(c.d_counters) + j * qbp::NUM_COUNTERS;
+        O.spectrum = reinterpret_cast<long long*>(c.d_spectrum);
         rc = osd_launch(h, O, T, s, false, osd_method, osd_order);
         if (rc) return rc;
     }
     return QBP_OK;
+}
+
+static hipError_t mc_sample(qbp_handle* h, const McErrors& e, uint8_t* errors, long long t, int64_t trial_begin,
+                            hipStream_t s)
+{
+    // (the samplers do not depend on H: any matrix, whichever kernel decodes it)
+    if (e.kind == McErrors::WEIGHT) return qbp::launch_mc_sample_weight(errors, h->n, e.weight, t, trial_begin, e.seed, s);
+    if (e.kind == McErrors::PROBS)
+        return qbp::launch_mc_sample_cols(errors, h->n, t, trial_begin, e.draws, e.seed, h->d_mc_thr.p, s);
+    return qbp::launch_mc_sample(errors, h->n, t, trial_begin, e.draws, e.seed, mc_threshold(e.p), s);
+}
+
+// A checked call (check_mc_call) on the stream.
+static int mc_run(qbp_handle* h, const McCall& c, hipStream_t s)
+{
+    if (c.trials() == 0) return QBP_OK;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    int rc = mc_prepare(h, c.Lx, c.k, s);
+    if (rc) return rc;
+    if (c.errors.kind == McErrors::PROBS && (rc = mc_prepare_thr(h, c.errors.probs, s)) != QBP_OK) return rc;
+    if (!c.chunked()) return mc_launch(h, c, s);
+    // the errors qbp_mc_sample_errors* returns, drawn chunk by chunk into the handle's buffer and run as stored errors:
+    // the global trial index lives in the sampler only, the pipeline indexes a chunk's trials from 0
+    const long long chunk = mc_chunk_trials(h, c.trials());
+    HIP_TRY(h->d_weight_err.reserve((size_t)chunk * (size_t)h->n));
+    McCall part = c;
+    part.errors = {McErrors::STORED};
+    part.errors.d_errors = h->d_weight_err.p;
+    part.trial_begin = 0;
+    for (int64_t a = c.trial_begin; a < c.trial_end; a += chunk) {
+        part.trial_end = std::min<long long>(chunk, c.trial_end - a);
+        HIP_TRY(mc_sample(h, c.errors, h->d_weight_err.p, part.trial_end, a, s));
+        if ((rc = mc_launch(h, part, s)) != QBP_OK) return rc;
+    }
+    return QBP_OK;
+}
+
+// Every _device entry: the check, then the launches.
+static int mc_run_device(qbp_handle* h, const McCall& c, void* stream)
+{
+    const int rc = check_mc_call(h, c, nullptr);
+    return rc ? rc : mc_run(h, c, static_cast<hipStream_t>(stream));
+}
+
+// Every host-array entry: the check, the prior (and stored errors) uploaded, counters (and spectrum tables) zeroed on
+// the device, the launches, and the results copied back and ADDED to the caller's arrays.  Stored-error entries SET the
+// counters: the caller's are zeroed first, also when there is no pattern.  A failed run synchronises, then returns.
+static int mc_run_host(qbp_handle* h, McCall c, const double* prior, const uint8_t* errors, int64_t* counters,
+                       int64_t* spectrum, int64_t* iter_hist)
+{
+    // (the check asks of these only whether they are null: the handle's buffers take their place below)
+    c.d_prior = prior; c.d_counters = counters; c.d_spectrum = spectrum; c.errors.d_errors = errors;
+    int rc = check_mc_call(h, c, prior);
+    if (rc) return rc;
+    const bool stored = c.errors.kind == McErrors::STORED, tables = c.out == McCall::SPECTRUM;
+    const size_t n = (size_t)h->n, T = (size_t)c.trials(), cells = c.rows() * qbp::NUM_COUNTERS;
+    const size_t spec_cells = tables ? (size_t)QBP_SPECTRUM_ROWS * (n + 1) : 0, hist_cells = tables ? (size_t)c.dec.max_iter + 1 : 0;
+    if (stored) std::fill(counters, counters + cells, (int64_t)0);
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    HIP_TRY(h->d_prior.reserve(n));
+    HIP_TRY(h->d_counters.reserve(cells));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, cells * sizeof(long long), s));
+    c.d_prior = h->d_prior.p; c.d_counters = reinterpret_cast<int64_t*>(h->d_counters.p);
+    if (stored) {
+        HIP_TRY(h->d_hard.reserve(T * n));                // (scratch of the host-pointer entries: the errors)
+        HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, T * n, hipMemcpyHostToDevice, s));
+        c.errors.d_errors = h->d_hard.p;
+    }
+    if (tables) {
+        HIP_TRY(h->d_spectrum.reserve(spec_cells + hist_cells));
+        HIP_TRY(hipMemsetAsync(h->d_spectrum.p, 0, (spec_cells + hist_cells) * sizeof(long long), s));
+        c.d_spectrum = reinterpret_cast<int64_t*>(h->d_spectrum.p);
+        c.d_iter_hist = iter_hist ? c.d_spectrum + spec_cells : nullptr;
+    }
+    if ((rc = mc_run(h, c, s)) != QBP_OK) { (void)hipStreamSynchronize(s); return rc; }
+    long long tmp[QBP_MC_MAX_BUDGETS * qbp::NUM_COUNTERS];
+    std::vector<long long> tab(spec_cells + hist_cells);
+    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, cells * sizeof(long long), hipMemcpyDeviceToHost, s));
+    if (tables) HIP_TRY(hipMemcpyAsync(tab.data(), h->d_spectrum.p, tab.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < cells; ++i) counters[i] += tmp[i];
+    for (size_t i = 0; i < spec_cells; ++i) spectrum[i] += tab[i];
+    if (iter_hist)
+        for (size_t i = 0; i < hist_cells; ++i) iter_hist[i] += tab[spec_cells + i];
+    return QBP_OK;
+}
+
+// The three qbp_mc_sample_errors* entries: errors [T, n] of trials trial_begin .. + T, as the runs draw them.
+static int mc_sample_host(qbp_handle* h, const McErrors& e, int64_t trial_begin, int64_t T, uint8_t* errors)
+{
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    if (!errors) return fail(QBP_E_INVALID, "errors is null");
+    int rc = check_mc_errors(h, e, trial_begin);
+    if (rc) return rc;
+    if (T == 0) return QBP_OK;
+    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    if (e.kind == McErrors::PROBS && (rc = mc_prepare_thr(h, e.probs, s)) != QBP_OK) return rc;
+    HIP_TRY(h->d_hard.reserve((size_t)T * (size_t)h->n));
+    HIP_TRY(mc_sample(h, e, h->d_hard.p, T, trial_begin, s));
+    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * (size_t)h->n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+
+// The arguments every qbp_mc_run* entry has, in the order of their parameter lists
+static McCall mc_call(const uint8_t* Lx, int32_t k, int32_t distance, const McErrors& errors, int64_t trial_begin,
+                      int64_t trial_end, const McDecoder& dec, const double* d_prior = nullptr,
+                      int64_t* d_counters = nullptr)
+{
+    McCall c;
+    c.Lx = Lx; c.k = k; c.distance = distance; c.errors = errors; c.trial_begin = trial_begin; c.trial_end = trial_end;
+    c.dec = dec; c.d_prior = d_prior; c.d_counters = d_counters;
+    return c;
 }
 
 int qbp_mc_run_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
@@ -2295,42 +2482,8 @@ int qbp_mc_run_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t 
                       int32_t variant, double alpha, double damping, double clip_llr,
                       uint32_t flags, int64_t* d_counters, void* stream)
 try {
-    return mc_run_impl(h, Lx_host, k, distance, p, nullptr, draws, seed, trial_begin, trial_end, nullptr, d_prior,
-                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream);
-}
-QBP_ABI_CATCH
-
-int qbp_mc_run_errors(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
-                      int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
-                      double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
-try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!errors || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
-    if (flags & QBP_FLAG_LAYERED) {
-        const int rcl = check_finite_prior(h, prior);
-        if (rcl) return rcl;
-    }
-    for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] = 0;
-    if (T == 0) return QBP_OK;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    const size_t n = (size_t)h->n;
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_counters.reserve(QBP_NUM_COUNTERS));
-    HIP_TRY(h->d_hard.reserve((size_t)T * n));            // (scratch of the host-pointer entries: the errors)
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, (size_t)T * n, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, QBP_NUM_COUNTERS * sizeof(long long), s));
-    // (p, draws, seed are unused with stored errors)
-    const int rc = mc_run_impl(h, Lx, k, distance, 0.0, nullptr, 1, 0, 0, T, h->d_hard.p, h->d_prior.p, max_iter,
-                               variant, alpha, damping, clip_llr, flags, reinterpret_cast<int64_t*>(h->d_counters.p),
-                               s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    HIP_TRY(hipMemcpyAsync(counters, h->d_counters.p, QBP_NUM_COUNTERS * sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    return mc_run_device(h, mc_call(Lx_host, k, distance, {McErrors::P, draws, seed, p}, trial_begin, trial_end,
+                                    {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters), stream);
 }
 QBP_ABI_CATCH
 
@@ -2339,99 +2492,38 @@ int qbp_mc_run(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, do
                const double* prior, int32_t max_iter, int32_t variant, double alpha,
                double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    if (flags & QBP_FLAG_LAYERED) {
-        const int rcl = check_finite_prior(h, prior);
-        if (rcl) return rcl;
-    }
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    HIP_TRY(h->d_prior.reserve(h->n));
-    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
-    int rc = qbp_mc_run_device(h, Lx, k, distance, p, draws, seed, trial_begin, trial_end,
-                               h->d_prior.p, max_iter, variant, alpha, damping, clip_llr, flags,
-                               reinterpret_cast<int64_t*>(h->d_counters.p), s);
-    if (rc) return rc;
-    long long tmp[qbp::NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    return mc_run_host(h, mc_call(Lx, k, distance, {McErrors::P, draws, seed, p}, trial_begin, trial_end,
+                                  {max_iter, variant, alpha, damping, clip_llr, flags}), prior, nullptr, counters,
+                       nullptr, nullptr);
+}
+QBP_ABI_CATCH
+
+// (T patterns instead of a sampler: counters SET, not added to)
+int qbp_mc_run_errors(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                      int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                      double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
+try {
+    return mc_run_host(h, mc_call(Lx, k, distance, {McErrors::STORED}, 0, T,
+                                  {max_iter, variant, alpha, damping, clip_llr, flags}), prior, errors, counters,
+                       nullptr, nullptr);
 }
 QBP_ABI_CATCH
 
 int qbp_mc_sample_errors(qbp_handle* h, double p, int32_t draws, uint64_t seed,
                          int64_t trial_begin, int64_t T, uint8_t* errors)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (T < 0 || trial_begin < 0) return fail(QBP_E_INVALID, "T and trial_begin must be >= 0");
-    if (!errors) return fail(QBP_E_INVALID, "errors is null");
-    if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2");
-    if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", p);
-    if (T == 0) return QBP_OK;
-    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    const size_t n = h->n;
-    // (the sampler does not depend on H: any matrix, whichever kernel decodes it)
-    HIP_TRY(h->d_hard.reserve((size_t)T * n));
-    HIP_TRY(qbp::launch_mc_sample(h->d_hard.p, h->n, T, trial_begin, draws, seed, mc_threshold(p), s));
-    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    return mc_sample_host(h, {McErrors::P, draws, seed, p}, trial_begin, T, errors);
 }
 QBP_ABI_CATCH
-
-// What the fixed-weight calls refuse beyond qbp_mc_run's own checks (host only, before any GPU work)
-static int check_weight(const qbp_handle* h, int32_t weight, int64_t trial_begin)
-{
-    if (weight < 0 || weight > h->n)
-        return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", weight, h->n);
-    if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
-    return QBP_OK;
-}
 
 int qbp_mc_run_weight_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, int32_t weight,
                              uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* d_prior,
                              int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
                              uint32_t flags, int64_t* d_counters, void* stream)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!d_prior || !d_counters) return fail(QBP_E_INVALID, "null pointer");
-    int rc = check_weight(h, weight, trial_begin);
-    if (rc) return rc;
-    // everything mc_run_impl refuses, for the WHOLE range and before the first chunk is sampled
-    const int64_t T = trial_end - trial_begin;
-    if ((rc = check_decode_args(h, T, max_iter, variant)) != QBP_OK) return rc;
-    int osd_method = 0, osd_order = 0;
-    if ((rc = check_relay_flags(h, flags, false)) != QBP_OK) return rc;
-    if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
-    if ((rc = parse_osd_flags(h, flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order)) != QBP_OK) return rc;
-    if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
-    if (k > 0 && !Lx_host) return fail(QBP_E_INVALID, "Lx is null");
-    if ((flags & (QBP_FLAG_OSD0 | QBP_FLAG_RELAY)) && (rc = check_mc_osd_trials(h, T, 1)) != QBP_OK) return rc;
-    if (T == 0) return QBP_OK;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t n = (size_t)h->n;
-    const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)n));
-    const long long chunk = std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
-    HIP_TRY(h->d_weight_err.reserve((size_t)chunk * n));
-    for (int64_t a = trial_begin; a < trial_end; a += chunk) {
-        const long long t = std::min<long long>(chunk, trial_end - a);
-        // the global trial index lives in the sampler only: the pipeline indexes its stored errors from 0
-        HIP_TRY(qbp::launch_mc_sample_weight(h->d_weight_err.p, h->n, weight, t, a, seed, s));
-        rc = mc_run_impl(h, Lx_host, k, distance, 0.0, nullptr, 1, 0, 0, t, h->d_weight_err.p, d_prior, max_iter,
-                         variant, alpha, damping, clip_llr, flags, d_counters, s);
-        if (rc) return rc;
-    }
-    return QBP_OK;
+    return mc_run_device(h, mc_call(Lx_host, k, distance, {McErrors::WEIGHT, 1, seed, 0.0, nullptr, weight}, trial_begin,
+                                    trial_end, {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters),
+                         stream);
 }
 QBP_ABI_CATCH
 
@@ -2440,52 +2532,16 @@ int qbp_mc_run_weight(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t dista
                       int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
                       int64_t counters[QBP_NUM_COUNTERS])
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    if (flags & QBP_FLAG_LAYERED) {
-        const int rcl = check_finite_prior(h, prior);
-        if (rcl) return rcl;
-    }
-    int rc = check_weight(h, weight, trial_begin);
-    if (rc) return rc;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    HIP_TRY(h->d_prior.reserve(h->n));
-    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
-    rc = qbp_mc_run_weight_device(h, Lx, k, distance, weight, seed, trial_begin, trial_end, h->d_prior.p, max_iter,
-                                  variant, alpha, damping, clip_llr, flags,
-                                  reinterpret_cast<int64_t*>(h->d_counters.p), s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    long long tmp[qbp::NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    return mc_run_host(h, mc_call(Lx, k, distance, {McErrors::WEIGHT, 1, seed, 0.0, nullptr, weight}, trial_begin,
+                                  trial_end, {max_iter, variant, alpha, damping, clip_llr, flags}), prior, nullptr,
+                       counters, nullptr, nullptr);
 }
 QBP_ABI_CATCH
 
 int qbp_mc_sample_errors_weight(qbp_handle* h, int32_t weight, uint64_t seed, int64_t trial_begin, int64_t T,
                                 uint8_t* errors)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
-    if (!errors) return fail(QBP_E_INVALID, "errors is null");
-    const int rc = check_weight(h, weight, trial_begin);
-    if (rc) return rc;
-    if (T == 0) return QBP_OK;
-    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    const size_t n = h->n;
-    HIP_TRY(h->d_hard.reserve((size_t)T * n));
-    HIP_TRY(qbp::launch_mc_sample_weight(h->d_hard.p, h->n, weight, T, trial_begin, seed, s));
-    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    return mc_sample_host(h, {McErrors::WEIGHT, 1, seed, 0.0, nullptr, weight}, trial_begin, T, errors);
 }
 QBP_ABI_CATCH
 
@@ -2495,11 +2551,9 @@ int qbp_mc_run_probs_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, in
                             int32_t variant, double alpha, double damping, double clip_llr,
                             uint32_t flags, int64_t* d_counters, void* stream)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    const int rc = check_probs(h, probs);
-    if (rc) return rc;
-    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
-                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream);
+    return mc_run_device(h, mc_call(Lx_host, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin,
+                                    trial_end, {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters),
+                         stream);
 }
 QBP_ABI_CATCH
 
@@ -2508,30 +2562,9 @@ int qbp_mc_run_probs(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distan
                      const double* prior, int32_t max_iter, int32_t variant, double alpha,
                      double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    if (flags & QBP_FLAG_LAYERED) {
-        const int rcl = check_finite_prior(h, prior);
-        if (rcl) return rcl;
-    }
-    int rc = check_probs(h, probs);
-    if (rc) return rc;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    HIP_TRY(h->d_prior.reserve(h->n));
-    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
-    rc = qbp_mc_run_probs_device(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end,
-                                 h->d_prior.p, max_iter, variant, alpha, damping, clip_llr, flags,
-                                 reinterpret_cast<int64_t*>(h->d_counters.p), s);
-    if (rc) return rc;
-    long long tmp[qbp::NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    return mc_run_host(h, mc_call(Lx, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, trial_end,
+                                  {max_iter, variant, alpha, damping, clip_llr, flags}), prior, nullptr, counters,
+                       nullptr, nullptr);
 }
 QBP_ABI_CATCH
 
@@ -2541,13 +2574,10 @@ int qbp_mc_run_budgets_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, 
                               int32_t variant, double alpha, double damping, double clip_llr,
                               uint32_t flags, int64_t* d_counters, void* stream)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    int rc = check_budgets(budgets, n_budgets);
-    if (rc) return rc;
-    rc = check_probs(h, probs);
-    if (rc) return rc;
-    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
-                       0, variant, alpha, damping, clip_llr, flags, d_counters, stream, budgets, n_budgets);
+    McCall c = mc_call(Lx_host, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, trial_end,
+                       {0, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters);
+    c.out = McCall::LADDER; c.budgets = budgets; c.n_budgets = n_budgets;
+    return mc_run_device(h, c, stream);
 }
 QBP_ABI_CATCH
 
@@ -2556,43 +2586,12 @@ int qbp_mc_run_budgets(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t dist
                        const double* prior, const int32_t* budgets, int32_t n_budgets, int32_t variant,
                        double alpha, double damping, double clip_llr, uint32_t flags, int64_t* counters)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    int rc = check_budgets(budgets, n_budgets);
-    if (rc) return rc;
-    rc = check_probs(h, probs);
-    if (rc) return rc;
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    const size_t cells = (size_t)n_budgets * qbp::NUM_COUNTERS;
-    HIP_TRY(h->d_prior.reserve(h->n));
-    HIP_TRY(h->d_counters.reserve(cells));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, h->n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, cells * sizeof(long long), s));
-    rc = qbp_mc_run_budgets_device(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end, h->d_prior.p,
-                                   budgets, n_budgets, variant, alpha, damping, clip_llr, flags,
-                                   reinterpret_cast<int64_t*>(h->d_counters.p), s);
-    if (rc) return rc;
-    long long tmp[QBP_MC_MAX_BUDGETS * qbp::NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, cells * sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < cells; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    McCall c = mc_call(Lx, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, trial_end,
+                       {0, variant, alpha, damping, clip_llr, flags});
+    c.out = McCall::LADDER; c.budgets = budgets; c.n_budgets = n_budgets;
+    return mc_run_host(h, c, prior, nullptr, counters, nullptr, nullptr);
 }
 QBP_ABI_CATCH
-
-// Arguments qbp_mc_run_spectrum* refuse on top of qbp_mc_run_probs (host only, before any GPU work)
-static int check_spectrum(qbp_handle* h, const int64_t* spectrum, int32_t max_iter, uint32_t flags)
-{
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (!spectrum) return fail(QBP_E_INVALID, "spectrum is null");
-    if (max_iter > QBP_MC_SPECTRUM_MAX_ITER)
-        return fail(QBP_E_INVALID, "max_iter = %d beyond QBP_MC_SPECTRUM_MAX_ITER = %d", max_iter,
-                    QBP_MC_SPECTRUM_MAX_ITER);
-    int method = 0, order = 0;
-    return parse_osd_flags(h, flags, true, &method, &order);
-}
 
 int qbp_mc_run_spectrum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance,
                                const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
@@ -2601,57 +2600,12 @@ int qbp_mc_run_spectrum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k,
                                uint32_t flags, int64_t* d_counters, int64_t* d_spectrum, int64_t* d_iter_hist,
                                void* stream)
 try {
-    int rc = check_spectrum(h, d_spectrum, max_iter, flags);
-    if (rc) return rc;
-    rc = check_probs(h, probs);
-    if (rc) return rc;
-    return mc_run_impl(h, Lx_host, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end, nullptr, d_prior,
-                       max_iter, variant, alpha, damping, clip_llr, flags, d_counters, stream, nullptr, 0, d_spectrum,
-                       d_iter_hist);
+    McCall c = mc_call(Lx_host, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, trial_end,
+                       {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters);
+    c.out = McCall::SPECTRUM; c.d_spectrum = d_spectrum; c.d_iter_hist = d_iter_hist;
+    return mc_run_device(h, c, stream);
 }
 QBP_ABI_CATCH
-
-// Host-array forms of the two spectrum entries: tables zeroed on the device, the run, then counters and tables
-// copied back.  errors != null: qbp_mc_run_errors_spectrum (T patterns; counters set), else sampled trials
-// (counters added to).
-static int mc_run_spectrum_host(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
-                                int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
-                                const uint8_t* errors, const double* prior, int32_t max_iter, int32_t variant,
-                                double alpha, double damping, double clip_llr, uint32_t flags, int64_t* counters,
-                                int64_t* spectrum, int64_t* iter_hist)
-{
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    const size_t n = (size_t)h->n, T = (size_t)(trial_end - trial_begin);
-    const size_t spec_cells = (size_t)QBP_SPECTRUM_ROWS * (n + 1), hist_cells = (size_t)std::max(max_iter, 0) + 1;
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
-    HIP_TRY(h->d_spectrum.reserve(spec_cells + hist_cells));
-    if (errors) {
-        HIP_TRY(h->d_hard.reserve(T * n));                // (scratch of the host-pointer entries: the errors)
-        HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, T * n, hipMemcpyHostToDevice, s));
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
-    HIP_TRY(hipMemsetAsync(h->d_spectrum.p, 0, (spec_cells + hist_cells) * sizeof(long long), s));
-    int64_t* const d_spec = reinterpret_cast<int64_t*>(h->d_spectrum.p);
-    const int rc = mc_run_impl(h, Lx, k, distance, 0.0, probs, draws, seed, trial_begin, trial_end,
-                               errors ? h->d_hard.p : nullptr, h->d_prior.p, max_iter, variant, alpha, damping, clip_llr,
-                               flags, reinterpret_cast<int64_t*>(h->d_counters.p), s, nullptr, 0, d_spec,
-                               iter_hist ? d_spec + spec_cells : nullptr);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    long long tmp[qbp::NUM_COUNTERS];
-    std::vector<long long> tab(spec_cells + hist_cells);
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(tab.data(), h->d_spectrum.p, tab.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] = errors ? tmp[i] : counters[i] + tmp[i];
-    for (size_t i = 0; i < spec_cells; ++i) spectrum[i] += tab[i];
-    if (iter_hist)
-        for (size_t i = 0; i < hist_cells; ++i) iter_hist[i] += tab[spec_cells + i];
-    return QBP_OK;
-}
 
 int qbp_mc_run_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
                         int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
@@ -2659,15 +2613,10 @@ int qbp_mc_run_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t dis
                         double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
                         int64_t* spectrum, int64_t* iter_hist)
 try {
-    int rc = check_spectrum(h, spectrum, max_iter, flags);
-    if (rc) return rc;
-    if (!prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    rc = check_probs(h, probs);
-    if (rc) return rc;
-    rc = check_decode_args(h, trial_end - trial_begin, max_iter, variant);
-    if (rc) return rc;
-    return mc_run_spectrum_host(h, Lx, k, distance, probs, draws, seed, trial_begin, trial_end, nullptr, prior, max_iter,
-                                variant, alpha, damping, clip_llr, flags, counters, spectrum, iter_hist);
+    McCall c = mc_call(Lx, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, trial_end,
+                       {max_iter, variant, alpha, damping, clip_llr, flags});
+    c.out = McCall::SPECTRUM;
+    return mc_run_host(h, c, prior, nullptr, counters, spectrum, iter_hist);
 }
 QBP_ABI_CATCH
 
@@ -2676,44 +2625,16 @@ int qbp_mc_run_errors_spectrum(qbp_handle* h, const uint8_t* Lx, int32_t k, int3
                                double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS],
                                int64_t* spectrum, int64_t* iter_hist)
 try {
-    int rc = check_spectrum(h, spectrum, max_iter, flags);
-    if (rc) return rc;
-    if (!errors || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
-    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
-    rc = check_decode_args(h, T, max_iter, variant);
-    if (rc) return rc;
-    if (T == 0) {
-        for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] = 0;
-        return QBP_OK;
-    }
-    // (probs, draws, seed are unused with stored errors)
-    return mc_run_spectrum_host(h, Lx, k, distance, nullptr, 1, 0, 0, T, errors, prior, max_iter, variant, alpha, damping,
-                                clip_llr, flags, counters, spectrum, iter_hist);
+    McCall c = mc_call(Lx, k, distance, {McErrors::STORED}, 0, T, {max_iter, variant, alpha, damping, clip_llr, flags});
+    c.out = McCall::SPECTRUM;
+    return mc_run_host(h, c, prior, errors, counters, spectrum, iter_hist);
 }
 QBP_ABI_CATCH
 
 int qbp_mc_sample_errors_probs(qbp_handle* h, const double* probs, int32_t draws, uint64_t seed,
                                int64_t trial_begin, int64_t T, uint8_t* errors)
 try {
-    if (!h) return fail(QBP_E_INVALID, "null handle");
-    if (T < 0 || trial_begin < 0) return fail(QBP_E_INVALID, "T and trial_begin must be >= 0");
-    if (!errors) return fail(QBP_E_INVALID, "errors is null");
-    if (draws != 1 && draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2");
-    int rc = check_probs(h, probs);
-    if (rc) return rc;
-    if (T == 0) return QBP_OK;
-    if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    const size_t n = h->n;
-    rc = mc_prepare_thr(h, probs, s);
-    if (rc) return rc;
-    HIP_TRY(h->d_hard.reserve((size_t)T * n));
-    HIP_TRY(qbp::launch_mc_sample_cols(h->d_hard.p, h->n, T, trial_begin, draws, seed, h->d_mc_thr.p, s));
-    HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    return mc_sample_host(h, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin, T, errors);
 }
 QBP_ABI_CATCH
 
@@ -2761,25 +2682,13 @@ static int decode_shots_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, c
     rc = mc_prepare(h, Lx_host, k, s);
     if (rc) return rc;
     const bool osd = (flags & QBP_FLAG_OSD0) != 0;
-    const size_t t = (size_t)T, m = h->m, n = h->n;
-    if (osd) {
-        HIP_TRY(h->d_fail_count.reserve(1));
-        HIP_TRY(h->d_fail_list.reserve(t));
-        HIP_TRY(h->d_fail_syn.reserve(t * m));
-        HIP_TRY(h->d_fail_llr.reserve(t * n));
-        HIP_TRY(h->d_fail_hard.reserve(t * n));
-        HIP_TRY(hipMemsetAsync(h->d_fail_count.p, 0, sizeof(unsigned long long), s));
-    }
     McArgs mc{};
+    if (osd && (rc = mc_fail_records(h, mc, 1, (size_t)T, false, s)) != QBP_OK) return rc;
     mc.lx_cols = h->d_lx_cols.p;
     mc.counters = reinterpret_cast<long long*>(d_counters);
     mc.det_bits = d_det_bits; mc.det_row_bytes = (h->m + 7) / 8;
     mc.actual = reinterpret_cast<const unsigned long long*>(d_actual);
     mc.predictions = reinterpret_cast<unsigned long long*>(d_predictions);
-    if (osd) {
-        mc.fail_list = h->d_fail_list.p; mc.fail_count = h->d_fail_count.p;
-        mc.fail_syn = h->d_fail_syn.p; mc.fail_llr = h->d_fail_llr.p; mc.fail_hard = h->d_fail_hard.p;
-    }
     c.prior = d_prior; c.B = T; c.max_iter = max_iter; c.variant = variant;
     c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr; c.flags = flags;
     c.converged = d_converged;

@@ -101,6 +101,30 @@ def _configure_layered(dec, layered):
         dec.layered_configure(None if layered is True else layered)
 
 
+def _on_device(shape, priors, begin, end, step, launch, world, device):
+    """One rank's slice [begin, end) of a run on the device, then the ONE all-reduce of its int64 table of ``shape``
+    (zeroed here; returned as a numpy array).  A point per entry of ``priors``, each owning an equal share of the
+    table: ``launch(i, d_prior, a, b, d_out, stream)`` enqueues trials [a, b) of point i, which add to the share at
+    address ``d_out``; ``step`` trials at the most per launch."""
+    import torch
+    dev = torch.device("cuda", device)
+    d_table = torch.zeros(shape, dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    d_priors = [torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev) for prior in priors]
+    shares = d_table.view(len(priors), d_table.numel() // max(len(priors), 1))
+    for i, (d_prior, d_out) in enumerate(zip(d_priors, shares)):
+        for a in range(begin, end, step):
+            launch(i, d_prior.data_ptr(), a, min(a + step, end), d_out.data_ptr(), stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(d_table)                     # the one RCCL collective of the run
+    torch.cuda.synchronize(dev)
+    return d_table.cpu().numpy()
+
+
+NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial records: one launch per point
+
+
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
               world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False):
@@ -121,30 +145,18 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
-        import torch
-
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
         _configure_layered(dec, layered)
-        dev = torch.device("cuda", device)
-        d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        priors = [torch.from_numpy(prior_of(p, code.n)).to(dev) for p in ps]
-        step = dec.mc_osd_step() if osd or relay is not None else 1 << 40         # OSD and Relay keep per-trial records
-        for i, p in enumerate(ps):
-            begin, end = shard_range(trials, rank, world)
-            for a in range(begin, end, step):
-                dec.mc_run_device(code.Lx, code.distance, p, priors[i].data_ptr(), a,
-                                  min(a + step, end), d_table[i].data_ptr(), draws=draws,
-                                  seed=seed, max_iter=max_iter, variant=variant, alpha=alpha,
-                                  damping=damping, clip_llr=clip_llr, flags=flags,
-                                  stream=stream.cuda_stream)
-        if world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(d_table)                 # the one RCCL collective of the sweep
-        torch.cuda.synchronize(dev)
-        return d_table.cpu().numpy()
+        step = dec.mc_osd_step() if osd or relay is not None else NO_STEP         # OSD and Relay keep per-trial records
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_device(code.Lx, code.distance, ps[i], d_prior, a, b, d_out, draws=draws, seed=seed,
+                              max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                              flags=flags, stream=stream)
+        return _on_device((len(ps), NUM_COUNTERS), [prior_of(p, code.n) for p in ps], *shard_range(trials, rank, world),
+                          step, launch, world, device)
     for i, p in enumerate(ps):
         begin, end = shard_range(trials, rank, world)
         table[i] = runner(code, p, begin, end)
@@ -156,6 +168,26 @@ def dem_prior(probs) -> np.ndarray:
     (studies/studyComplete.py:85-86)."""
     p = np.clip(np.asarray(probs, np.float64), 1e-15, 1 - 1e-15)
     return np.log((1 - p) / p)
+
+
+def _dem_args(H, L, probs, prior):
+    """The arguments of a run on a matrix H [m, n], as ``(L uint8[k, n], probs float64[n], prior float64[n], n)``: at
+    most 64 observables; ``probs`` None for a run without them; ``prior`` None: ``dem_prior(probs)``.  ValueError
+    for any other shape."""
+    L = np.ascontiguousarray(L, np.uint8)
+    n = H.shape[1]
+    if L.ndim != 2 or L.shape[1] != n:
+        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
+    if L.shape[0] > 64:
+        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
+    if probs is not None:
+        probs = np.ascontiguousarray(probs, np.float64)
+        if probs.shape != (n,):
+            raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
+    prior = dem_prior(probs) if prior is None and probs is not None else np.ascontiguousarray(prior, np.float64)
+    if prior.shape != (n,):
+        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    return L, probs, prior, n
 
 
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
@@ -174,40 +206,20 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     tests; by default the HIP library and torch.distributed.  ``relay``, ``layered``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
     flags = layered_run_flags(flags, layered, variant)
-    L = np.ascontiguousarray(L, np.uint8)
-    probs = np.ascontiguousarray(probs, np.float64)
-    n = H.shape[1]
-    if L.ndim != 2 or L.shape[1] != n:
-        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
-    if L.shape[0] > 64:
-        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
-    if probs.shape != (n,):
-        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
-    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
-    if prior.shape != (n,):
-        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
-        import torch
-
         from . import bp
         dec = bp.decoder_for(H, device=device)
         _configure_relay(dec, relay)
         _configure_layered(dec, layered)
-        dev = torch.device("cuda", device)
-        d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
-        stream = torch.cuda.current_stream(dev)
-        d_prior = torch.from_numpy(prior).to(dev)
-        step = dec.mc_osd_step() if osd or relay is not None else 1 << 40          # OSD and Relay keep per-trial records
-        for a in range(begin, end, step):
-            dec.mc_run_probs_device(L, distance, probs, d_prior.data_ptr(), a, min(a + step, end), d_cnt.data_ptr(),
-                                    draws=draws, seed=seed, max_iter=max_iter, variant=variant, alpha=alpha,
-                                    damping=damping, clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
-        if world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(d_cnt)
-        torch.cuda.synchronize(dev)
-        return d_cnt.cpu().numpy()
+        step = dec.mc_osd_step() if osd or relay is not None else NO_STEP          # OSD and Relay keep per-trial records
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed, max_iter=max_iter,
+                                    variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
+                                    stream=stream)
+        return _on_device((NUM_COUNTERS,), [prior], begin, end, step, launch, world, device)
     cnt = np.asarray(runner(H, L, probs, prior, begin, end), np.int64)
     return all_reduce(cnt) if all_reduce is not None else cnt
 
@@ -302,21 +314,12 @@ def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant
 def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, draws, seed, variant, alpha, damping,
                       clip_llr, osd, flags, world, device):
     """One rank's slice of a ladder on the device, then the one all-reduce of the [K, 12] table."""
-    import torch
-    dev = torch.device("cuda", device)
-    d_table = torch.zeros((len(budgets), NUM_COUNTERS), dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
-    step = dec.mc_budgets_step(len(budgets)) if osd else 1 << 40      # OSD keeps records per trial and budget
-    for a in range(begin, end, step):
-        dec.mc_run_budgets_device(L, distance, probs, d_prior.data_ptr(), budgets, a, min(a + step, end),
-                                  d_table.data_ptr(), draws=draws, seed=seed, variant=variant, alpha=alpha,
-                                  damping=damping, clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
-    if world > 1:
-        import torch.distributed as dist
-        dist.all_reduce(d_table)
-    torch.cuda.synchronize(dev)
-    return d_table.cpu().numpy()
+    def launch(i, d_prior, a, b, d_out, stream):
+        dec.mc_run_budgets_device(L, distance, probs, d_prior, budgets, a, b, d_out, draws=draws, seed=seed,
+                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
+                                  stream=stream)
+    step = dec.mc_budgets_step(len(budgets)) if osd else NO_STEP      # OSD keeps records per trial and budget
+    return _on_device((len(budgets), NUM_COUNTERS), [prior], begin, end, step, launch, world, device)
 
 
 def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -351,18 +354,7 @@ def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, dra
     ``runner(H, L, probs, prior, budgets, begin, end) -> int64[K, 12]``."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     budgets = _lib.check_budgets(budgets)
-    L = np.ascontiguousarray(L, np.uint8)
-    probs = np.ascontiguousarray(probs, np.float64)
-    n = H.shape[1]
-    if L.ndim != 2 or L.shape[1] != n:
-        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
-    if L.shape[0] > 64:
-        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
-    if probs.shape != (n,):
-        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
-    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
-    if prior.shape != (n,):
-        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
@@ -405,27 +397,16 @@ def _spectrum_on_device(dec, L, distance, probs_list, priors, begin, end, *, dra
                         damping, clip_llr, osd, flags, world, device):
     """One rank's slice of every point on the device -- counters, weights and iterations of a point side by side in
     one int64 row -- then the one all-reduce of the whole table."""
-    import torch
     n = dec.n
-    dev = torch.device("cuda", device)
     width = NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1) + max_iter + 1
-    d_all = torch.zeros((len(probs_list), width), dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    step = dec.mc_osd_step() if osd else 1 << 40          # OSD keeps per-trial records
-    for i, (probs, prior) in enumerate(zip(probs_list, priors)):
-        d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
-        base = d_all[i].data_ptr()
-        for a in range(begin, end, step):
-            dec.mc_run_spectrum_device(L, distance, probs, d_prior.data_ptr(), a, min(a + step, end), base,
-                                       base + 8 * NUM_COUNTERS,
-                                       base + 8 * (NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)), draws=draws,
-                                       seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                       clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
-    if world > 1:
-        import torch.distributed as dist
-        dist.all_reduce(d_all)                       # counters and both tables: one collective
-    torch.cuda.synchronize(dev)
-    return d_all.cpu().numpy()
+
+    def launch(i, d_prior, a, b, d_out, stream):
+        dec.mc_run_spectrum_device(L, distance, probs_list[i], d_prior, a, b, d_out, d_out + 8 * NUM_COUNTERS,
+                                   d_out + 8 * (NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)), draws=draws, seed=seed,
+                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                                   flags=flags, stream=stream)
+    step = dec.mc_osd_step() if osd else NO_STEP          # OSD keeps per-trial records
+    return _on_device((len(probs_list), width), priors, begin, end, step, launch, world, device)
 
 
 def _check_spectrum_max_iter(max_iter):
@@ -472,18 +453,7 @@ def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, se
     ``run_dem``; ``runner(H, L, probs, prior, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])``."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     max_iter = _check_spectrum_max_iter(max_iter)
-    L = np.ascontiguousarray(L, np.uint8)
-    probs = np.ascontiguousarray(probs, np.float64)
-    n = H.shape[1]
-    if L.ndim != 2 or L.shape[1] != n:
-        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
-    if L.shape[0] > 64:
-        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
-    if probs.shape != (n,):
-        raise ValueError(f"probs must have shape ({n},), got {probs.shape}")
-    prior = dem_prior(probs) if prior is None else np.ascontiguousarray(prior, np.float64)
-    if prior.shape != (n,):
-        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
@@ -511,22 +481,12 @@ def check_weights(weights, n):
 def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, max_iter, variant, alpha, damping,
                        clip_llr, osd, flags, world, device):
     """One rank's slice of every weight on the device, then the one all-reduce of the [len(weights), 12] table."""
-    import torch
-    dev = torch.device("cuda", device)
-    d_table = torch.zeros((len(weights), NUM_COUNTERS), dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev)
-    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
-    step = dec.mc_osd_step() if osd or (flags & _lib.FLAG_RELAY) else 1 << 40          # OSD and Relay keep per-trial records
-    for i, w in enumerate(weights):
-        for a in range(begin, end, step):
-            dec.mc_run_weight_device(L, distance, w, d_prior.data_ptr(), a, min(a + step, end), d_table[i].data_ptr(),
-                                     seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                     clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
-    if world > 1:
-        import torch.distributed as dist
-        dist.all_reduce(d_table)
-    torch.cuda.synchronize(dev)
-    return d_table.cpu().numpy()
+    def launch(i, d_prior, a, b, d_out, stream):
+        dec.mc_run_weight_device(L, distance, weights[i], d_prior, a, b, d_out, seed=seed, max_iter=max_iter,
+                                 variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
+                                 stream=stream)
+    step = dec.mc_osd_step() if osd or (flags & _lib.FLAG_RELAY) else NO_STEP    # OSD and Relay keep per-trial records
+    return _on_device((len(weights), NUM_COUNTERS), [prior] * len(weights), begin, end, step, launch, world, device)
 
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
@@ -566,15 +526,7 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
     same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
     does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
-    L = np.ascontiguousarray(L, np.uint8)
-    n = H.shape[1]
-    if L.ndim != 2 or L.shape[1] != n:
-        raise ValueError(f"L must have shape (k, {n}), got {L.shape}")
-    if L.shape[0] > 64:
-        raise ValueError(f"at most 64 observables (got {L.shape[0]})")
-    prior = np.ascontiguousarray(prior, np.float64)
-    if prior.shape != (n,):
-        raise ValueError(f"prior must have shape ({n},), got {prior.shape}")
+    L, _, prior, n = _dem_args(H, L, None, prior)
     weights = check_weights(weights, n)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
