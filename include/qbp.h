@@ -98,9 +98,13 @@ enum {
     QBP_FLAG_RELAY = 512u,    /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first-stage
                                  BP (any variant) does not converge on go through Relay-BP (qbp_relay_decode_batch, as
                                  configured by qbp_relay_configure) instead of OSD, then to classification */
-    QBP_FLAG_LAYERED = 1024u  /* the layered (check-serial) schedule instead of flooding: qbp_layered_configure below.
+    QBP_FLAG_LAYERED = 1024u, /* the layered (check-serial) schedule instead of flooding: qbp_layered_configure below.
                                  Honoured by qbp_decode_batch(_device), qbp_mc_run(_device), qbp_mc_run_errors,
                                  qbp_mc_run_probs(_device), qbp_mc_run_weight(_device) */
+    QBP_FLAG_GD = 2048u       /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first
+                                 stage (any variant, flooding or QBP_FLAG_LAYERED) does not converge on go through BP
+                                 guided decimation (qbp_gd_decode_batch, as configured by qbp_gd_configure), then to
+                                 classification */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -404,6 +408,63 @@ int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, con
 int qbp_layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* order_in,
                      int32_t* order_out, int32_t* level_ptr, int32_t* n_levels);
 int qbp_layered_configure(qbp_handle* h, const int32_t* order);
+
+/*
+ * BP guided decimation (BPGD; Yao, Gokduman, Pfister, "Belief propagation decoding of quantum LDPC codes with guided
+ * decimation"): flooding BP in rounds of a few iterations; a round that ends without a solution freezes the most
+ * reliable variable by overwriting its prior with +-decim_llr, and the next round continues on the same messages.  No
+ * elimination and no tables.  The reference has no such decoder; the rules below are this build's specification
+ * (tests/gd_oracle.py states them in numpy, and the kernel reproduces that statement bit for bit).  With max_rounds = 0
+ * the outputs are those of qbp_decode_batch(max_iter = iters_per_round) -- the plain variant for QBP_SUM_PRODUCT,
+ * damping = 1.0 for QBP_MIN_SUM -- `iters` being that call's iters + 1 on converged records and iters_per_round
+ * otherwise.
+ *
+ * qbp_gd_configure stores the configuration in the handle:
+ *   iters_per_round T >= 1, max_rounds >= 0, decim_llr > 0 and finite, variant QBP_SUM_PRODUCT or QBP_MIN_SUM, alpha
+ *   and clip_llr finite (used by QBP_MIN_SUM only, as in rework/decoding.py).
+ * QBP_E_INVALID: a value out of range or not finite, QBP_DAMPED_SP.  QBP_E_UNSUPPORTED: a matrix whose per-record
+ * state -- E messages, two rows of n doubles, and numpy's function tables for sum-product -- does not fit the 160 KiB of
+ * LDS of one workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not).
+ *
+ * One record (syndrome s, prior P [n] finite):
+ *   1. W = P (the working prior), Q = P on the edges, V = P, D = {} (the decimated set), total = 0, rounds = 0;
+ *   2. one round, for t = 0 .. T - 1:
+ *      1. check step on Q.  QBP_MIN_SUM: rule 2a of Relay-BP above (signs with 0 -> +1, first minimum by lowest column,
+ *         R = alpha * syndrome_sign * r_signs * magnitude).  QBP_SUM_PRODUCT: the exact row update of
+ *         beliefPropagation.py:114-126 (numpy's tanh, the sequential product in ascending column order, t_safe, the
+ *         division, the syndrome sign, the clip at +-0.9999999, 2 arctanh), as flooding and layered BP use it;
+ *      2. Vn = colsum(R) + W, the column sum in ascending check order, left to right from the first entry, + W last;
+ *      3. on the edges Q = clip(Vn - R, -clip_llr, clip_llr) for QBP_MIN_SUM, Q = Vn - R for QBP_SUM_PRODUCT (no damping
+ *         term);
+ *      4. V = Vn, total += 1;
+ *      5. hard = V < 0; if H hard == s the record has converged and stops;
+ *   3. after a round without a solution: stop if rounds == max_rounds.  Otherwise v* is, among the variables not in D,
+ *      of column weight >= 1 and with V[v] not NaN, the one with the largest |V[v]|, equal values going to the lowest
+ *      variable index; stop if there is none.  W[v*] = -decim_llr if V[v*] < 0, else +decim_llr; v* joins D;
+ *      rounds += 1; go to 2 -- Q and V carry over unchanged;
+ *   4. hard and llr (= V) are those of the last iteration executed; converged; iters = total; rounds.  Isolated
+ *      variables keep V = W = P.
+ *   Every floating-point operation is rounded on its own; nothing is fused or reordered.
+ * qbp_gd_decode_batch: syndromes [B][m], prior [n] (host entry: a value that is not finite is QBP_E_INVALID) ->
+ * hard [B][n], converged [B], iters [B], llr [B][n], rounds [B]; any output may be NULL.  QBP_E_INVALID without a
+ * configuration.  One workgroup per record, all of its state in LDS (bp_gd_kernel).
+ *
+ * QBP_FLAG_GD in a Monte-Carlo call: the first stage is the call's BP as without the flag (any variant, flooding or
+ * QBP_FLAG_LAYERED); every trial it leaves unconverged is decoded by the rules above from its syndrome and the call's
+ * prior (first-stage messages are not carried over) and classified on the result like an OSD output.  counters[10]
+ * counts the records BPGD leaves unsolved (their hard decision misses the syndrome); [0], [6], [7] are the first
+ * stage's.  The record limits of QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with
+ * QBP_FLAG_OSD0, any OSD bit or QBP_FLAG_RELAY, or without a configuration.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets,
+ * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum and qbp_decode_shots.
+ */
+int qbp_gd_configure(qbp_handle* h, int32_t iters_per_round, int32_t max_rounds, double decim_llr, int32_t variant,
+                     double alpha, double clip_llr);
+int qbp_gd_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, uint8_t* hard,
+                        uint8_t* converged, int32_t* iters, double* llr, int32_t* rounds);
+/* Same, all pointers are DEVICE pointers, enqueued on `stream` (may be NULL), asynchronous. */
+int qbp_gd_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                               uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr, int32_t* d_rounds,
+                               void* stream);
 
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */

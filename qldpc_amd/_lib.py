@@ -29,6 +29,7 @@ FLAG_OSD_E = 128             # order-w OSD, exhaustive over the w least reliable
 FLAG_OSD_LARGE = 256         # order-w OSD also on matrices beyond the one-wavefront kernel (up to 8192 rows)
 FLAG_RELAY = 512             # Monte-Carlo calls: Relay-BP (qbp_relay_configure) instead of OSD on the trials BP leaves
 FLAG_LAYERED = 1024          # the layered (check-serial) schedule instead of flooding (qbp_layered_configure)
+FLAG_GD = 2048               # Monte-Carlo calls: BP guided decimation (qbp_gd_configure) on the trials BP leaves
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -116,6 +117,9 @@ SIGNATURES = {
     "qbp_relay_configure": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_double, C.c_double]),
     "qbp_relay_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "qbp_relay_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_gd_configure": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double]),
+    "qbp_gd_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_gd_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
@@ -380,8 +384,42 @@ class Decoder:
                                                     d_converged or None, d_iters or None, d_llr or None, d_legs or None,
                                                     d_solutions or None, stream or None))
 
+    @_locked
+    def gd_configure(self, cfg):
+        """Store a BP guided decimation configuration (``gd.GDConfig``) in the handle: qbp_gd_configure."""
+        _check(load().qbp_gd_configure(self._h, cfg.iters_per_round, cfg.max_rounds, cfg.decim_llr, cfg.variant,
+                                       cfg.alpha, cfg.clip_llr))
+
+    @_locked
+    def gd_decode(self, syndromes, prior, cfg=None, want_llr=True):
+        """BP guided decimation of B syndromes (qbp_gd_decode_batch) -> ``(hard, converged, iters, llr, rounds)``;
+        ``cfg``: configure first (None: the handle's configuration)."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},), got {pr.shape}")
+        if cfg is not None:
+            self.gd_configure(cfg)
+        B = syn.shape[0]
+        hard = np.empty((B, self.n), np.uint8)
+        conv = np.empty(B, np.uint8)
+        iters, rounds = (np.empty(B, np.int32) for _ in range(2))
+        llr = np.empty((B, self.n), np.float64) if want_llr else None
+        _check(load().qbp_gd_decode_batch(self._h, syn.ctypes.data, pr.ctypes.data, B, hard.ctypes.data,
+                                          conv.ctypes.data, iters.ctypes.data, _ptr(llr), rounds.ctypes.data))
+        return hard, conv.astype(bool), iters, llr, rounds
+
+    def gd_decode_device(self, d_syndromes, d_prior, B, d_hard, d_converged, d_iters, d_llr, d_rounds, stream=0):
+        """``gd_decode`` on device buffers (pointers as ints; outputs may be 0), enqueued on `stream`."""
+        _check(load().qbp_gd_decode_batch_device(self._h, d_syndromes, d_prior, int(B), d_hard or None,
+                                                 d_converged or None, d_iters or None, d_llr or None, d_rounds or None,
+                                                 stream or None))
+
     def mc_osd_step(self):
-        """Trials one qbp_mc_run call may cover with FLAG_OSD0 or FLAG_RELAY (per-trial records: m + 10 n bytes)."""
+        """Trials one qbp_mc_run call may cover with FLAG_OSD0, FLAG_RELAY or FLAG_GD (per-trial records: m + 10 n
+        bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
     def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None):
@@ -397,7 +435,7 @@ class Decoder:
         variant, alpha, damping, clip_llr, flags = decoder
         begin, end = int(trial_begin), int(trial_end)
         # with OSD a call keeps per-trial records on the device: split long ranges
-        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(end - begin, 1)
+        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(end - begin, 1)
         for a in range(begin, end, step):
             _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), *source, a, min(a + step, end),
                                        pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
@@ -414,7 +452,7 @@ class Decoder:
             raise ValueError("bad shapes")
         variant, alpha, damping, clip_llr, flags = decoder
         total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(len(err), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(len(err), 1)
         for a in range(0, len(err), step):
             part = np.zeros(NUM_COUNTERS, np.int64)
             chunk = err[a:a + step]
@@ -581,7 +619,7 @@ class Decoder:
             raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
         pred = np.zeros(T, np.uint64)
         conv = np.zeros(T, np.uint8)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY)) else max(T, 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(T, 1)
         for a in range(0, T, step):
             b = min(a + step, T)
             _check(load().qbp_decode_shots(

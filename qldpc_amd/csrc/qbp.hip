@@ -21,6 +21,7 @@
 #include "qbp_stream.hpp"
 #include "qbp_hist.hpp"
 #include "qbp_relay.hpp"
+#include "qbp_gd.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_launch.hpp"
 
@@ -210,6 +211,11 @@ struct qbp_handle {
     double relay_alpha = 1.0, relay_clip = 0.0;
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
+    // BP guided decimation (qbp_gd_configure); scratch of the host-pointer entry
+    bool gd_ready = false;
+    int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
+    double gd_llr = 0.0, gd_alpha = 1.0, gd_clip = 0.0;
+    DevBuf<int32_t> d_gd_rounds;
     // layered BP (qbp_layered_configure): the checks level after level, the level boundaries
     bool layered_ready = false;
     int layered_levels = 0, layered_max_width = 0;
@@ -2152,6 +2158,169 @@ try {
 }
 QBP_ABI_CATCH
 
+// ---- BP guided decimation (qbp_gd.hpp) ---------------------------------------------------------------------------
+// The kernel keeps a record's whole state in LDS: matrices beyond that are QBP_E_UNSUPPORTED.
+static int gd_supported(const qbp_handle* h, int variant)
+{
+    const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT);
+    if (lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "BP guided decimation keeps the messages and two rows of n doubles in LDS: %d x %d "
+                                       "with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
+    return QBP_OK;
+}
+
+// QBP_FLAG_GD of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and shots
+// entries, which have no such stage.
+static int check_gd_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
+{
+    if (!(flags & QBP_FLAG_GD)) return QBP_OK;
+    if (flags & (QBP_FLAG_OSD0 | OSD_ALL_BITS | QBP_FLAG_RELAY))
+        return fail(QBP_E_INVALID, "QBP_FLAG_GD together with an OSD bit or QBP_FLAG_RELAY: one second stage per call");
+    if (other_entry)
+        return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_GD is not available with iteration budgets, spectra or recorded shots");
+    if (!h->gd_ready) return fail(QBP_E_INVALID, "QBP_FLAG_GD without qbp_gd_configure");
+    return QBP_OK;                      // (qbp_gd_configure has checked the LDS)
+}
+
+// One launch of bp_gd_kernel (device pointers): a batch of syndromes, or the failure records of a Monte-Carlo launch
+struct GdCall {
+    const double* prior = nullptr;
+    long long max_items = 0;            // B, or the most records the list can hold
+    const uint8_t* syndromes = nullptr;
+    uint8_t* hard = nullptr;
+    uint8_t* converged = nullptr;
+    int32_t* iters = nullptr;
+    double* llr = nullptr;
+    int32_t* rounds = nullptr;
+    const unsigned long long* fail_count = nullptr;
+    const long long* fail_list = nullptr;
+    const uint8_t* fail_syn = nullptr;
+    const uint8_t* fail_err = nullptr;
+    int half_distance = 0;
+    long long* counters = nullptr;
+};
+
+static int gd_launch(qbp_handle* h, const GdCall& c, bool records, hipStream_t s)
+{
+    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
+    constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
+    if (c.max_items > MAX_LAUNCH)
+        return fail(QBP_E_UNSUPPORTED, "BP guided decimation decodes at most 2^30 syndromes per call (got %lld)", c.max_items);
+    const size_t n = (size_t)h->n;
+    const bool sp = h->gd_variant == QBP_SUM_PRODUCT;
+    const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
+    const int threads = qbp::gd_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1]);
+    // resident workgroups per CU: the wavefronts a CU holds at the kernel's registers (min-sum 7 per SIMD, sum-product
+    // 5), and the LDS; QBP_OPT_BLOCKS_PER_CU overrides
+    const int waves = sp ? 20 : 28;
+    int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)(waves / (threads / 64)), ((size_t)160 * 1024) / lds));
+    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
+    const int grid = (int)std::max<long long>(1, std::min<long long>(c.max_items, (long long)h->num_cu * per_cu));
+    const size_t n_long = (size_t)(h->row_off[RC + 2] - h->row_off[RC + 1]);
+    HIP_TRY(h->d_wsL.reserve((size_t)grid * 3 * std::max<size_t>(n_long, 1)));
+    HIP_TRY(h->d_prior_sorted.reserve(n));
+    HIP_TRY(qbp::launch_permute_prior(c.prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
+    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    qbp::GdParams P{};
+    P.m = h->m; P.n = h->n; P.E = h->E;
+    P.srow = h->d_srow.p; P.srow_e0 = h->d_srow_e0.p; P.srow_deg = h->d_srow_deg.p; P.epos = h->d_epos.p;
+    P.long_edge_row = h->d_long_edge_row.p; P.svar = h->d_svar.p; P.vpos = h->d_vpos.p; P.vrow = h->d_vrow.p;
+    P.lcol_ptr = h->d_lcol_ptr.p;
+    std::copy(std::begin(h->row_off), std::end(h->row_off), P.row_off);
+    std::copy(std::begin(h->row_base), std::end(h->row_base), P.row_base);
+    std::copy(std::begin(h->rpad_off), std::end(h->rpad_off), P.rpad_off);
+    std::copy(std::begin(h->col_off), std::end(h->col_off), P.col_off);
+    std::copy(std::begin(h->gcol_base), std::end(h->gcol_base), P.col_base);
+    std::copy(std::begin(h->cpad_off), std::end(h->cpad_off), P.cpad_off);
+    P.prior_sorted = h->d_prior_sorted.p; P.wsL = h->d_wsL.p;
+    P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    P.iters_per_round = h->gd_iters; P.max_rounds = h->gd_max_rounds; P.decim_llr = h->gd_llr;
+    P.alpha = h->gd_alpha; P.clip_llr = h->gd_clip;
+    P.syndromes = c.syndromes; P.B = records ? 0 : c.max_items;
+    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr; P.rounds = c.rounds;
+    P.fail_count = c.fail_count; P.fail_list = c.fail_list; P.fail_syn = c.fail_syn; P.fail_err = c.fail_err;
+    P.lx_cols = h->d_lx_cols.p; P.half_distance = c.half_distance; P.counters = c.counters;
+    h->last_threads = threads; h->last_lds = (int)lds; h->last_grid = grid;
+    HIP_TRY(qbp::launch_gd(records, h->gd_variant, P, grid, threads, lds, s));
+    return QBP_OK;
+}
+
+int qbp_gd_configure(qbp_handle* h, int32_t iters_per_round, int32_t max_rounds, double decim_llr, int32_t variant,
+                     double alpha, double clip_llr)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (iters_per_round < 1) return fail(QBP_E_INVALID, "iters_per_round = %d (need >= 1)", iters_per_round);
+    if (max_rounds < 0) return fail(QBP_E_INVALID, "max_rounds = %d (need >= 0)", max_rounds);
+    if (!(decim_llr > 0.0) || !std::isfinite(decim_llr))
+        return fail(QBP_E_INVALID, "decim_llr = %g (need > 0 and finite)", decim_llr);
+    if (variant != QBP_SUM_PRODUCT && variant != QBP_MIN_SUM)
+        return fail(QBP_E_INVALID, "variant = %d: BP guided decimation runs QBP_SUM_PRODUCT or QBP_MIN_SUM", variant);
+    if (!std::isfinite(alpha) || !std::isfinite(clip_llr))
+        return fail(QBP_E_INVALID, "alpha = %g, clip_llr = %g: both must be finite", alpha, clip_llr);
+    const int rc = gd_supported(h, variant);
+    if (rc) return rc;
+    h->gd_iters = iters_per_round; h->gd_max_rounds = max_rounds; h->gd_llr = decim_llr; h->gd_variant = variant;
+    h->gd_alpha = alpha; h->gd_clip = clip_llr;
+    h->gd_ready = true;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_gd_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                               uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr, int32_t* d_rounds,
+                               void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->gd_ready) return fail(QBP_E_INVALID, "qbp_gd_decode_batch without qbp_gd_configure");
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    GdCall c;
+    c.prior = d_prior; c.max_items = B; c.syndromes = d_syndromes;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr; c.rounds = d_rounds;
+    return gd_launch(h, c, false, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_gd_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, uint8_t* hard,
+                        uint8_t* converged, int32_t* iters, double* llr, int32_t* rounds)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->gd_ready) return fail(QBP_E_INVALID, "qbp_gd_decode_batch without qbp_gd_configure");
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
+    for (int v = 0; v < h->n; ++v)
+        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_prior.reserve(n));
+    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
+    if (converged) HIP_TRY(h->d_conv.reserve(b));
+    if (iters) HIP_TRY(h->d_iters.reserve(b));
+    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
+    if (rounds) HIP_TRY(h->d_gd_rounds.reserve(b));
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    int rc = qbp_gd_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, hard ? h->d_hard.p : nullptr,
+                                        converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
+                                        llr ? h->d_llr.p : nullptr, rounds ? h->d_gd_rounds.p : nullptr, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
+    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
+    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
+    if (rounds) HIP_TRY(hipMemcpyAsync(rounds, h->d_gd_rounds.p, b * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 // ---- Monte-Carlo (include/qbp.h: qbp_mc_run*) --------------------------------------------------------------------
 
 // Where the errors of a Monte-Carlo call come from; only the fields of `kind` are read.
@@ -2221,6 +2390,8 @@ static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial
     return QBP_OK;
 }
 
+constexpr uint32_t SECOND_BP_BITS = QBP_FLAG_RELAY | QBP_FLAG_GD;    // second stages that are no OSD: never a BP launch's bit
+
 // Everything a Monte-Carlo call refuses: host only, once per public call, for the whole range and before any GPU work.
 // `host_prior`: the priors when they are a host array (the layered schedule's finite check), else null.
 static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prior)
@@ -2237,15 +2408,16 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
     if (c.out == McCall::LADDER && (rc = check_budgets(c.budgets, c.n_budgets)) != QBP_OK) return rc;
     if ((rc = check_mc_errors(h, c.errors, c.trial_begin)) != QBP_OK) return rc;
     if ((rc = check_decode_args(h, c.trials(), c.last_iter(), c.dec.variant)) != QBP_OK) return rc;
-    // ladders and spectra have neither a Relay stage nor a layered build
+    // ladders and spectra have neither a Relay or guided-decimation stage nor a layered build
     if ((rc = check_relay_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
+    if ((rc = check_gd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if (host_prior && (c.dec.flags & QBP_FLAG_LAYERED) && (rc = check_finite_prior(h, host_prior)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
-    if ((rc = parse_osd_flags(h, c.dec.flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order)) != QBP_OK) return rc;
+    if ((rc = parse_osd_flags(h, c.dec.flags & ~SECOND_BP_BITS, true, &osd_method, &osd_order)) != QBP_OK) return rc;
     if (c.k < 0 || c.k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", c.k);
     if (c.k > 0 && !c.Lx) return fail(QBP_E_INVALID, "Lx is null");
-    if (c.dec.flags & (QBP_FLAG_OSD0 | QBP_FLAG_RELAY)) {
+    if (c.dec.flags & (QBP_FLAG_OSD0 | SECOND_BP_BITS)) {
         // QBP_MC_OSD_MAX_TRIALS bounds the records of one launch.  That is the whole call -- a fixed-weight call too,
         // although it launches chunk by chunk -- except for layered sampled calls, which have always been held to it
         // per chunk only: a longer range of those goes through.
@@ -2286,13 +2458,15 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     const int32_t max_iter = c.last_iter();
     // Relay-BP instead of OSD on the trials the first stage leaves unconverged: its bit goes to no BP launch
     const bool relay = (c.dec.flags & QBP_FLAG_RELAY) != 0;
+    // likewise BP guided decimation
+    const bool gd = (c.dec.flags & QBP_FLAG_GD) != 0;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
     int osd_method = 0, osd_order = 0;
-    int rc = parse_osd_flags(h, c.dec.flags & ~(uint32_t)QBP_FLAG_RELAY, true, &osd_method, &osd_order);
+    int rc = parse_osd_flags(h, c.dec.flags & ~SECOND_BP_BITS, true, &osd_method, &osd_order);
     if (rc) return rc;
-    const uint32_t flags = c.dec.flags & ~((uint32_t)QBP_FLAG_RELAY | OSD_ALL_BITS);
+    const uint32_t flags = c.dec.flags & ~(SECOND_BP_BITS | OSD_ALL_BITS);
     const bool layered = (flags & QBP_FLAG_LAYERED) != 0;
-    const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay;
+    const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay || gd;
     McArgs mc{};
     // (qbp_mc_run_budgets: a record per trial and budget)
     if (osd && (rc = mc_fail_records(h, mc, rows, (size_t)T, true, s)) != QBP_OK) return rc;
@@ -2334,6 +2508,15 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
         r.fail_syn = h->d_fail_syn.p; r.fail_err = h->d_fail_err.p;
         r.half_distance = c.distance / 2; r.counters = reinterpret_cast<long long*>(c.d_counters);
         return relay_launch(h, r, true, s);
+    }
+    if (gd) {
+        // second kernel: BP guided decimation + classification of the same records
+        GdCall g;
+        g.prior = c.d_prior; g.max_items = T;
+        g.fail_count = h->d_fail_count.p; g.fail_list = h->d_fail_list.p;
+        g.fail_syn = h->d_fail_syn.p; g.fail_err = h->d_fail_err.p;
+        g.half_distance = c.distance / 2; g.counters = reinterpret_cast<long long*>(c.d_counters);
+        return gd_launch(h, g, true, s);
     }
     // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
     // read from device memory by the kernel itself (no host round trip)
@@ -2651,6 +2834,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if (!Lx || !det_bits || !prior || !counters) return fail(QBP_E_INVALID, "null pointer");
     if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k = %d observables (need 1..64)", k);
     if ((rc = check_relay_flags(h, flags, true)) != QBP_OK) return rc;
+    if ((rc = check_gd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, flags, 0, true)) != QBP_OK) return rc;
     if (host_prior)
         for (int v = 0; v < h->n; ++v)

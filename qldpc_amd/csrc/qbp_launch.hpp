@@ -18,6 +18,7 @@ struct OsdBigWorkspace;
 struct OsdOrderBigArgs;
 struct RelayParams;
 struct LayeredParams;
+struct GdParams;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -125,6 +126,8 @@ hipError_t launch_osd_order_blocked_ordered(int rows_per_thread, unsigned grid, 
 hipError_t launch_relay(bool records, const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s);
 // qbp_tu_layered.hip: bp_layered_kernel<variant, mc> (sum-product or min-sum; batch or Monte-Carlo build)
 hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
+// qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
+hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

@@ -1,0 +1,38 @@
+// libqbp.so, translation unit of the BP guided decimation kernel (qbp_gd.hpp): sum-product and min-sum, the batch
+// build and the records build.
+#include <hip/hip_runtime.h>
+
+#include "../../include/qbp.h"
+#include "qbp_gd.hpp"
+#include "qbp_launch.hpp"
+
+namespace qbp {
+namespace {
+
+template <int VARIANT, bool RECORDS>
+hipError_t gd_launch_k(const GdParams& P, int grid, int threads, size_t lds, hipStream_t s)
+{
+    auto kern = bp_gd_kernel<VARIANT, RECORDS>;
+    static thread_local size_t lds_set[64] = {0};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, P);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s)
+{
+    if (variant == QBP_MIN_SUM)
+        return records ? gd_launch_k<2, true>(P, grid, threads, lds, s) : gd_launch_k<2, false>(P, grid, threads, lds, s);
+    return records ? gd_launch_k<0, true>(P, grid, threads, lds, s) : gd_launch_k<0, false>(P, grid, threads, lds, s);
+}
+
+}  // namespace qbp

@@ -80,6 +80,24 @@ def relay_run_flags(flags, relay) -> int:
     return flags | _lib.FLAG_RELAY
 
 
+def gd_run_flags(flags, gd) -> int:
+    """``flags`` of a sweep with ``gd`` (None, a ``gd.GDConfig`` or its dict form): | FLAG_GD, the trials BP leaves
+    unconverged go to BP guided decimation.  ValueError together with OSD or Relay-BP: one second stage per run."""
+    if gd is None:
+        return flags
+    if flags & (_lib.FLAG_OSD0 | _lib.FLAG_OSD_CS | _lib.FLAG_OSD_E | _lib.FLAG_OSD_LARGE | _lib.FLAG_RELAY):
+        raise ValueError("gd= excludes osd=True and relay=: one second stage per run")
+    from . import gd as gd_mod
+    gd_mod.as_config(gd)                # (a bad configuration raises here, before any GPU work)
+    return flags | _lib.FLAG_GD
+
+
+def _configure_gd(dec, gd):
+    if gd is not None:
+        from . import gd as gd_mod
+        dec.gd_configure(gd_mod.as_config(gd))
+
+
 def _configure_relay(dec, relay):
     if relay is not None:
         from . import relay as relay_mod
@@ -127,8 +145,11 @@ NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial record
 
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
-              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False):
+              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
+
+    ``gd``: a ``gd.GDConfig`` or its dict form -- BP guided decimation on the trials BP does not converge on (FLAG_GD;
+    not together with ``osd`` or ``relay``).
 
     ``layered``: True -- BP runs the layered (check-serial) schedule in its default order (FLAG_LAYERED); an array -- in
     that order of the checks.  OSD and Relay act on what it leaves unconverged.
@@ -141,15 +162,16 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(flags, layered, variant)
+    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
+        _configure_gd(dec, gd)
         _configure_layered(dec, layered)
-        step = dec.mc_osd_step() if osd or relay is not None else NO_STEP         # OSD and Relay keep per-trial records
+        step = dec.mc_osd_step() if osd or relay is not None or gd is not None else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_device(code.Lx, code.distance, ps[i], d_prior, a, b, d_out, draws=draws, seed=seed,
@@ -193,7 +215,7 @@ def _dem_args(H, L, probs, prior):
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
-            layered=False):
+            layered=False, gd=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -203,17 +225,18 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     ``distance``: the "BPs_miscorrected" / "incorrectable" split compares the error weight with distance // 2;
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
-    tests; by default the HIP library and torch.distributed.  ``relay``, ``layered``: as in ``run_sweep``."""
+    tests; by default the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
-    flags = layered_run_flags(flags, layered, variant)
+    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
         dec = bp.decoder_for(H, device=device)
         _configure_relay(dec, relay)
+        _configure_gd(dec, gd)
         _configure_layered(dec, layered)
-        step = dec.mc_osd_step() if osd or relay is not None else NO_STEP          # OSD and Relay keep per-trial records
+        step = dec.mc_osd_step() if osd or relay is not None or gd is not None else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed, max_iter=max_iter,
@@ -485,22 +508,22 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
         dec.mc_run_weight_device(L, distance, weights[i], d_prior, a, b, d_out, seed=seed, max_iter=max_iter,
                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
                                  stream=stream)
-    step = dec.mc_osd_step() if osd or (flags & _lib.FLAG_RELAY) else NO_STEP    # OSD and Relay keep per-trial records
+    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD)) else NO_STEP    # (per-trial records)
     return _on_device((len(weights), NUM_COUNTERS), [prior] * len(weights), begin, end, step, launch, world, device)
 
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
-                device=0, runner=None, all_reduce=None, relay=None, layered=False):
+                device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed.  ``relay``, ``layered``: as in ``run_sweep``."""
+    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(flags, layered, variant)
+    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
@@ -508,6 +531,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
+        _configure_gd(dec, gd)
         _configure_layered(dec, layered)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
@@ -699,6 +723,13 @@ def main(argv=None):
     ap.add_argument("--relay-gamma0", type=float, default=0.125, help="memory strength of leg 0, every variable")
     ap.add_argument("--relay-interval", type=float, nargs=2, default=(-0.24, 0.66), metavar=("LO", "HI"),
                     help="later legs draw a strength per variable uniformly from [LO, HI] (seeded by --seed)")
+    ap.add_argument("--gd", type=int, nargs=2, default=None, metavar=("T", "ROUNDS"),
+                    help="BP guided decimation on the trials BP does not converge on: rounds of T iterations, at most "
+                         "ROUNDS variables decimated (with --alpha and --clip-llr; not with --osd, --relay, --budgets, "
+                         "--spectrum, --shots)")
+    ap.add_argument("--gd-llr", type=float, default=25.0, metavar="X", help="the prior a decimated variable gets is +-X")
+    ap.add_argument("--gd-variant", choices=("sum-product", "min-sum"), default="min-sum",
+                    help="the BP that --gd runs between decimations")
     ap.add_argument("--layered", action="store_true",
                     help="BP runs the layered (check-serial) schedule in its default order instead of flooding "
                          "(sum-product or min-sum; not with --budgets, --spectrum, --shots)")
@@ -727,6 +758,20 @@ def main(argv=None):
             relay_mod.as_config(relay, 1)
         except (ValueError, TypeError) as e:
             ap.error(f"--relay: {e}")
+    gd = None
+    if args.gd is not None:
+        if args.osd or args.relay is not None:
+            ap.error("--gd excludes --osd and --relay")
+        if args.budgets is not None or args.spectrum is not None or args.shots is not None:
+            ap.error("--gd does not combine with --budgets, --spectrum or --shots")
+        gd = dict(iters_per_round=args.gd[0], max_rounds=args.gd[1], decim_llr=args.gd_llr,
+                  variant=_lib.MIN_SUM if args.gd_variant == "min-sum" else _lib.SUM_PRODUCT, alpha=args.alpha,
+                  clip_llr=args.clip_llr)
+        try:
+            from . import gd as gd_mod
+            gd_mod.as_config(gd)
+        except (ValueError, TypeError) as e:
+            ap.error(f"--gd: {e}")
     if args.layered:
         if args.budgets is not None or args.spectrum is not None or args.shots is not None:
             ap.error("--layered does not combine with --budgets, --spectrum or --shots")
@@ -874,19 +919,19 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               layered=args.layered, **common)
+                               layered=args.layered, gd=gd, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
-            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered,
+            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered, gd=gd,
                              **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
-                           layered=args.layered, **common)[None, :]
+                           layered=args.layered, gd=gd, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

@@ -34,6 +34,8 @@ UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
 UNITS += [("qbp_tu_relay.hip", [])]
 # Layered BP (QBP_FLAG_LAYERED): bp_layered_kernel<variant, mc>
 UNITS += [("qbp_tu_layered.hip", [])]
+# BP guided decimation (qbp_gd_decode_batch, QBP_FLAG_GD): bp_gd_kernel<variant, records>
+UNITS += [("qbp_tu_gd.hip", [])]
 
 
 def demangle(sym):
