@@ -646,6 +646,107 @@ int qbp_decode_shots_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, co
                             int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
                             uint64_t* d_predictions, uint8_t* d_converged, int64_t* d_counters, void* stream);
 
+/*
+ * Sliding-window decoding of a multi-round matrix (space-time matrices in the style of spaceTime.py, detector error
+ * models): instead of one decode of the whole history, overlapping windows of W rounds are decoded one after another,
+ * each commits its first F rounds, and the committed correction is folded into the syndrome the later windows see.  The
+ * 2592 x 7776 phenomenological matrix of [[288,12,18]] over 18 rounds becomes five 864 x 2592 problems at (W, F) = (6, 3),
+ * which the on-chip BP kernel and the one-launch OSD kernels take.  The reference has no such decoder; the rules below are
+ * this build's specification (tests/window_oracle.py states them in numpy, and the device path reproduces that statement
+ * composed from qbp_decode_batch and qbp_osd_batch bit for bit).
+ *
+ * Inputs: H [m][n] in CSR form; check_round [m], integers in [0, R) with R = 1 + the largest of them, in any order, not
+ * necessarily contiguous, a round may have no check; the window size W >= 1 and the commit size 1 <= F <= W.
+ *   var_round[v] = the smallest check_round over column v, 0 for an empty column.
+ *   Window k covers rounds [kF, min(kF + W, R)).  The last window is the first k with kF + W >= R (window 0 when
+ *   W >= R); there are K = k_last + 1 windows.  For window k:
+ *     C_k = the checks whose round lies in the window, ascending;  U_k = the variables whose var_round does, ascending;
+ *     H_k = H[C_k, U_k] (column entries in later rounds are cut off);
+ *     M_k = {v in U_k : var_round[v] < kF + F}, in the last window all of U_k.  Every variable is in exactly one M_k.
+ * One record (syndrome s, prior [n]; only bit 0 of a syndrome byte counts): r = s & 1, x = 0, iters = 0,
+ * window_fails = 0; for k = 0 .. K - 1
+ *   0. a window without a check or without a variable (a round may have no check) is skipped: nothing is decoded or
+ *      counted; for v in M_k -- columns no check touches, the only variables such a window can hold -- x[v] = 0 and
+ *      llr_out[v] = prior[v];
+ *   1. (hard, conv, it, llr) = qbp_decode_batch(H_k, r[C_k], prior[U_k], max_iter, variant, alpha, damping, clip_llr):
+ *      flooding BP, any of the three variants, the default column-sum order;
+ *   2. if !conv and OSD bits are set: hard = qbp_osd_batch(H_k, OSD bits)(r[C_k], llr, hard);
+ *   3. for v in M_k: x[v] = hard[v], llr_out[v] = llr[v];
+ *   4. for every check c of H (also beyond the window): r[c] ^= XOR of x[v] over v in M_k and row c;
+ *   5. iters += it, window_fails += !conv.
+ * Outputs (any may be NULL): correction [B][n], converged [B] (1 when r == 0 at the end, i.e. H x == s), iters [B],
+ * llr [B][n], window_fails [B].  With W >= R and no OSD bits correction, iters and llr are those of qbp_decode_batch on
+ * H, bit for bit, and converged is its flag.
+ *
+ * qbp_window_plan (host only, no device): sizes[3] = {K, sum of |C_k|, sum of |U_k|}; the other outputs may be NULL (call
+ * once for the sizes; K <= R, and a check or a variable is in at most ceil(W / F) windows): win_check_ptr [K + 1] into
+ * win_checks, win_var_ptr [K + 1] into win_vars, win_commit (0/1 per entry of win_vars), win_class [K] -- windows whose
+ * local CSR (H_k in the indices of C_k and U_k) is identical share a class id, numbered in order of first appearance;
+ * a skipped window (rule 0) has class -1.
+ * QBP_E_INVALID: a null row_ptr, col_idx, check_round or sizes, a malformed CSR, a negative round, W < 1, F outside 1..W,
+ * a round of 2^20 or more (rounds need not be contiguous, but K grows with the largest), and windows that hold more than
+ * 2^28 checks or variables in all.
+ *
+ * qbp_window_create builds the decoder: one ordinary qbp_handle per window class (one on a phenomenological matrix, a
+ * second if the last window is shorter), the window tables and the rows of H restricted to each M_k on the device, and
+ * its batch workspaces.  It is bound to one device and has the thread and stream rules of a handle.  QBP_E_INVALID as
+ * qbp_window_plan.
+ *
+ * qbp_window_decode_batch (host pointers; a NaN prior is QBP_E_INVALID) and qbp_window_decode_batch_device (device
+ * pointers, enqueued on `stream`, asynchronous): one call enqueues the whole chain of launches -- per window a gather
+ * of the syndrome rows (window_gather_kernel), the sub-handle's BP launch, with OSD bits the list of its failures
+ * (window_fail_list_kernel) and the sub-handle's OSD launch on those records only, and the commit of rules 3-5
+ * (window_commit_kernel) -- and nothing returns to the host in between.  flags: QBP_FLAG_FORCE_FULL, and the OSD bits as
+ * qbp_osd_batch reads them (QBP_FLAG_OSD0 alone: OSD-0; QBP_FLAG_OSD_CS / _E with QBP_OSD_ORDER_FLAGS(w), QBP_FLAG_OSD_LARGE);
+ * any other bit is QBP_E_INVALID.  What a sub-handle would refuse (an OSD order its matrix does not take:
+ * QBP_E_UNSUPPORTED) is refused before any GPU work, with every output untouched.
+ *
+ * qbp_window_mc_run_probs(_device): trials [trial_begin, trial_end) drawn by the sampler of qbp_mc_run_probs (the rows of
+ * qbp_mc_sample_errors_probs), syndrome = H e (window_syndrome_kernel), the window decoder, classification on the device
+ * (window_classify_kernel); chunk by chunk (QBP_OPT_MC_WEIGHT_CHUNK through qbp_window_set_option; default 2^28 / n
+ * trials, at most 2^20): counters do not depend on the chunk or on how the range is split.  counters[QBP_NUM_COUNTERS]
+ * are ADDED to and mean what qbp_mc_run's mean with detection = correction and "converged" = (window_fails == 0):
+ * [6] trials with a window BP did not converge on, [7] the sum of iters, [5] asks H x == s itself, and [10] counts the
+ * trials whose correction misses the syndrome.  qbp_window_mc_run_errors: the same pipeline on T stored error patterns
+ * (host), counters SET.
+ *
+ * Out of scope: Relay-BP, BPGD and the layered schedule inside a window (they need per-window configuration), the
+ * column-sum order flags, QBP_FLAG_FAST_MATH, budget ladders and spectra, bit-packed shot files (unpack them to bytes),
+ * and reading rounds out of a detector error model's coordinates -- the caller supplies check_round.
+ */
+typedef struct qbp_window qbp_window;
+int qbp_window_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* check_round,
+                    int32_t W, int32_t F, int32_t sizes[3], int32_t* win_check_ptr, int32_t* win_checks,
+                    int32_t* win_var_ptr, int32_t* win_vars, uint8_t* win_commit, int32_t* win_class);
+int qbp_window_create(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* check_round,
+                      int32_t W, int32_t F, int32_t device, qbp_window** out);
+void qbp_window_destroy(qbp_window* w);
+int qbp_window_decode_batch(qbp_window* w, const uint8_t* syndromes, const double* prior, int64_t B, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            uint8_t* correction, uint8_t* converged, int32_t* iters, double* llr, int32_t* window_fails);
+int qbp_window_decode_batch_device(qbp_window* w, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                   int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                                   uint32_t flags, uint8_t* d_correction, uint8_t* d_converged, int32_t* d_iters,
+                                   double* d_llr, int32_t* d_window_fails, void* stream);
+int qbp_window_mc_run_probs(qbp_window* w, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                            int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* prior,
+                            int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                            uint32_t flags, int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form: d_prior and d_counters (ADDED to) are device pointers; Lx and probs stay host pointers. */
+int qbp_window_mc_run_probs_device(qbp_window* w, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                                   const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                                   int64_t trial_end, const double* d_prior, int32_t max_iter, int32_t variant,
+                                   double alpha, double damping, double clip_llr, uint32_t flags, int64_t* d_counters,
+                                   void* stream);
+int qbp_window_mc_run_errors(qbp_window* w, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                             int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS]);
+/* what: QBP_WINDOW_INFO_* below, or a QBP_INFO_* of the sub-handle of window class `index`; -1 if unknown. */
+enum { QBP_WINDOW_INFO_WINDOWS = 1, QBP_WINDOW_INFO_CLASSES = 2, QBP_WINDOW_INFO_ROUNDS = 3 };
+int64_t qbp_window_get_info(qbp_window* w, int32_t what, int32_t index);
+/* QBP_OPT_MC_WEIGHT_CHUNK: trials per chunk of qbp_window_mc_run_* (0 = default); any other option goes to every sub-handle. */
+int qbp_window_set_option(qbp_window* w, int32_t option, int64_t value);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

@@ -15,7 +15,8 @@ import threading
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("QBP_LIB_PATH") or os.path.join(_HERE, "csrc", "libqbp.so")   # override: experiments
+_DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libqbp.so")
+LIB_PATH = os.environ.get("QBP_LIB_PATH") or _DEFAULT_LIB_PATH   # override: experiments
 
 SUM_PRODUCT, DAMPED_SP, MIN_SUM = 0, 1, 2
 FLAG_FORCE_FULL = 1
@@ -122,6 +123,25 @@ SIGNATURES = {
     "qbp_gd_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
+    "qbp_window_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
+                                  _VP]),
+    "qbp_window_create": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(_VP)]),
+    "qbp_window_destroy": (None, [_VP]),
+    "qbp_window_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                          C.c_double, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_window_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                 C.c_double, C.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_window_mc_run_probs": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64, C.c_int64,
+                                          C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                          C.c_uint32, _VP]),
+    "qbp_window_mc_run_probs_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64, C.c_int64,
+                                                 C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                 C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_window_mc_run_errors": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, C.c_int32, C.c_int32,
+                                           C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_window_get_info": (C.c_int64, [_VP, C.c_int32, C.c_int32]),
+    "qbp_window_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
@@ -198,6 +218,12 @@ def _preload_hip_runtime():
             pass
 
 
+def _missing(name):
+    def fn(*args):
+        raise QbpError(f"{LIB_PATH} has no {name} (a build without sliding-window decoding)")
+    return fn
+
+
 def load():
     """Load libqbp.so (built by ``__graft_entry__.build()`` / ``make -C qldpc_amd/csrc``)."""
     global _lib
@@ -208,7 +234,14 @@ def load():
         _preload_hip_runtime()
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
+            fn = getattr(lib, name, None)
+            if fn is None and name.startswith("qbp_window_") and LIB_PATH != _DEFAULT_LIB_PATH:
+                # a QBP_LIB_PATH build from before sliding-window decoding (tools/bench_window.py times its
+                # whole-matrix path): everything else works, a window call raises QbpError
+                setattr(lib, name, _missing(name))
+                continue
+            if fn is None:
+                raise AttributeError(f"{LIB_PATH} has no {name}: rebuild it")
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
@@ -256,6 +289,151 @@ def _locked(method):
         with self._lock:
             return method(self, *args, **kwargs)
     return wrapper
+
+
+WINDOW_INFO = dict(windows=1, classes=2, rounds=3)     # QBP_WINDOW_INFO_*
+
+
+def _window_args(row_ptr, col_idx, m, n, check_round):
+    rp = np.ascontiguousarray(row_ptr, np.int32)
+    ci = np.ascontiguousarray(col_idx, np.int32)
+    if rp.shape != (int(m) + 1,):
+        raise ValueError(f"row_ptr must have shape ({int(m) + 1},)")
+    cr = np.ascontiguousarray(check_round, np.int32)
+    if cr.shape != (int(m),):
+        raise ValueError(f"check_round must have shape ({int(m)},), got {cr.shape}")
+    return rp, ci, cr
+
+
+def window_plan(row_ptr, col_idx, m, n, check_round, W, F):
+    """Host-only: the partition of sliding-window decoding (qbp_window_plan) as a dict -- ``K`` windows;
+    ``check_ptr`` int32[K + 1] into ``checks``; ``var_ptr`` int32[K + 1] into ``vars``; ``commit`` uint8 per entry of
+    ``vars``; ``cls`` int32[K], the class of identical local CSR of every window."""
+    rp, ci, cr = _window_args(row_ptr, col_idx, m, n, check_round)
+    lib = load()
+    sizes = np.zeros(3, np.int32)
+    head = (rp.ctypes.data, _ptr(ci), int(m), int(n), cr.ctypes.data, int(W), int(F), sizes.ctypes.data)
+    _check(lib.qbp_window_plan(*head, None, None, None, None, None, None))
+    K, nc, nv = (int(x) for x in sizes)
+    out = dict(K=K, check_ptr=np.zeros(K + 1, np.int32), checks=np.zeros(nc, np.int32), var_ptr=np.zeros(K + 1, np.int32),
+               vars=np.zeros(nv, np.int32), commit=np.zeros(nv, np.uint8), cls=np.zeros(K, np.int32))
+    _check(lib.qbp_window_plan(*head, *(out[k].ctypes.data for k in ("check_ptr", "checks", "var_ptr", "vars", "commit",
+                                                                      "cls"))))
+    return out
+
+
+class WindowDecoder:
+    """Sliding-window decoder of one multi-round matrix on one GPU (wraps a ``qbp_window``; include/qbp.h states the
+    rule).  Methods taking host arrays are serialised per object; the ``*_device`` methods only enqueue work."""
+
+    def __init__(self, row_ptr, col_idx, m, n, check_round, W, F, device=0):
+        self.row_ptr, self.col_idx, self.check_round = _window_args(row_ptr, col_idx, m, n, check_round)
+        self.m, self.n, self.W, self.F = int(m), int(n), int(W), int(F)
+        h = _VP()
+        _check(load().qbp_window_create(self.row_ptr.ctypes.data, _ptr(self.col_idx), self.m, self.n,
+                                        self.check_round.ctypes.data, self.W, self.F, int(device), C.byref(h)))
+        self._h = h
+        self.device = int(device)
+        self._lock = threading.RLock()
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.qbp_window_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self, what, index=0):
+        """``what``: "windows", "classes", "rounds", or a key of ``INFO`` for the sub-handle of class ``index``."""
+        code = WINDOW_INFO[what] if what in WINDOW_INFO else INFO[what]
+        return int(load().qbp_window_get_info(self._h, code, int(index)))
+
+    @_locked
+    def set_option(self, option, value):
+        _check(load().qbp_window_set_option(self._h, int(option), int(value)))
+
+    @_locked
+    def decode(self, syndromes, prior, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
+               want_llr=True):
+        """-> (correction uint8[B, n], converged bool[B], iters int32[B], llr float64[B, n] or None,
+        window_fails int32[B]).  ``flags``: FLAG_FORCE_FULL and the OSD bits (``osd_flags``)."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},), got {pr.shape}")
+        B = syn.shape[0]
+        x = np.empty((B, self.n), np.uint8)
+        conv = np.empty(B, np.uint8)
+        iters = np.empty(B, np.int32)
+        llr = np.empty((B, self.n), np.float64) if want_llr else None
+        fails = np.empty(B, np.int32)
+        _check(load().qbp_window_decode_batch(self._h, syn.ctypes.data, pr.ctypes.data, B, int(max_iter), int(variant),
+                                              float(alpha), float(damping), float(clip_llr), int(flags), x.ctypes.data,
+                                              conv.ctypes.data, iters.ctypes.data, _ptr(llr), fails.ctypes.data))
+        return x, conv.astype(bool), iters, llr, fails
+
+    def decode_device(self, d_syndromes, d_prior, B, max_iter, variant, alpha, damping, clip_llr, flags, d_correction,
+                      d_converged, d_iters, d_llr, d_window_fails, stream=0):
+        _check(load().qbp_window_decode_batch_device(
+            self._h, d_syndromes, d_prior, int(B), int(max_iter), int(variant), float(alpha), float(damping),
+            float(clip_llr), int(flags), d_correction or None, d_converged or None, d_iters or None, d_llr or None,
+            d_window_fails or None, stream or None))
+
+    def _lx(self, Lx):
+        L = np.ascontiguousarray(Lx, np.uint8)
+        if L.ndim != 2 or L.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n}), got {L.shape}")
+        return L
+
+    @_locked
+    def mc_run_probs(self, Lx, distance, probs, prior, trial_begin, trial_end, draws=1, seed=0, max_iter=50,
+                     variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, counters=None):
+        """qbp_window_mc_run_probs -> int64[12], ADDED to ``counters`` if given."""
+        L = self._lx(Lx)
+        pb = np.ascontiguousarray(probs, np.float64)
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pb.shape != (self.n,) or pr.shape != (self.n,):
+            raise ValueError(f"probs and prior must have shape ({self.n},)")
+        cnt = np.zeros(NUM_COUNTERS, np.int64) if counters is None else counters
+        _check(load().qbp_window_mc_run_probs(self._h, L.ctypes.data, L.shape[0], int(distance), pb.ctypes.data, int(draws),
+                                              int(seed), int(trial_begin), int(trial_end), pr.ctypes.data, int(max_iter),
+                                              int(variant), float(alpha), float(damping), float(clip_llr), int(flags),
+                                              cnt.ctypes.data))
+        return cnt
+
+    def mc_run_probs_device(self, Lx, distance, probs, d_prior, trial_begin, trial_end, d_counters, draws=1, seed=0,
+                            max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, stream=0):
+        L = self._lx(Lx)
+        pb = np.ascontiguousarray(probs, np.float64)
+        if pb.shape != (self.n,):
+            raise ValueError(f"probs must have shape ({self.n},)")
+        _check(load().qbp_window_mc_run_probs_device(
+            self._h, L.ctypes.data, L.shape[0], int(distance), pb.ctypes.data, int(draws), int(seed), int(trial_begin),
+            int(trial_end), d_prior, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr),
+            int(flags), d_counters, stream or None))
+
+    @_locked
+    def mc_run_errors(self, Lx, distance, errors, prior, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
+                      clip_llr=20.0, flags=0):
+        """qbp_window_mc_run_errors -> int64[12] (SET)."""
+        L = self._lx(Lx)
+        err = np.ascontiguousarray(errors, np.uint8)
+        if err.ndim != 2 or err.shape[1] != self.n:
+            raise ValueError(f"errors must have shape (T, {self.n}), got {err.shape}")
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},), got {pr.shape}")
+        cnt = np.zeros(NUM_COUNTERS, np.int64)
+        _check(load().qbp_window_mc_run_errors(self._h, L.ctypes.data, L.shape[0], int(distance), err.ctypes.data,
+                                               err.shape[0], pr.ctypes.data, int(max_iter), int(variant), float(alpha),
+                                               float(damping), float(clip_llr), int(flags), cnt.ctypes.data))
+        return cnt
 
 
 class Decoder:

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <map>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -23,6 +24,7 @@
 #include "qbp_relay.hpp"
 #include "qbp_gd.hpp"
 #include "qbp_layered.hpp"
+#include "qbp_window.hpp"
 #include "qbp_launch.hpp"
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
@@ -3055,5 +3057,570 @@ try {
     return QBP_OK;
 }
 QBP_ABI_CATCH
+
+// ---- sliding-window decoding (include/qbp.h, qbp_window_*; glue kernels: qbp_window.hpp) ---------------------------
+// The partition of rule 1, host only: windows, their checks C_k and variables U_k, the commit flags, and the classes of
+// identical local CSR (the first window of a class keeps it for qbp_create).
+struct WindowPlan {
+    int R = 0, K = 0;
+    std::vector<int32_t> check_ptr, checks, var_ptr, vars, cls;      // cls[k] = -1: window k is skipped (rule 0)
+    std::vector<uint8_t> commit;
+    std::vector<std::vector<int32_t>> cls_row_ptr, cls_col_idx;
+    std::vector<int> cls_n;
+};
+
+// Bounds of a plan: rounds need not be contiguous, so one large round number must not turn into hours of empty windows
+// or tables beyond int32 (QBP_E_INVALID beyond these).
+constexpr int WINDOW_MAX_ROUNDS = 1 << 20;
+constexpr long long WINDOW_MAX_ENTRIES = (long long)1 << 28;      // sum of |C_k|, and of |U_k|
+
+static int window_plan(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, const int32_t* check_round, int W,
+                       int F, WindowPlan& P)
+{
+    const int rc = check_csr(row_ptr, col_idx, m, n);
+    if (rc) return rc;
+    if (!check_round) return fail(QBP_E_INVALID, "check_round is null");
+    if (W < 1) return fail(QBP_E_INVALID, "window size W = %d (need >= 1)", W);
+    if (F < 1 || F > W) return fail(QBP_E_INVALID, "commit size F = %d outside [1, W = %d]", F, W);
+    for (int c = 0; c < m; ++c) {
+        if (check_round[c] < 0) return fail(QBP_E_INVALID, "check_round[%d] = %d is negative", c, check_round[c]);
+        if (check_round[c] >= WINDOW_MAX_ROUNDS)
+            return fail(QBP_E_INVALID, "check_round[%d] = %d: rounds must be below %d", c, check_round[c], WINDOW_MAX_ROUNDS);
+        P.R = std::max(P.R, check_round[c] + 1);
+    }
+    std::vector<int32_t> var_round((size_t)n, INT32_MAX);
+    for (int c = 0; c < m; ++c)
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e)
+            var_round[col_idx[e]] = std::min(var_round[col_idx[e]], check_round[c]);
+    for (int v = 0; v < n; ++v)
+        if (var_round[v] == INT32_MAX) var_round[v] = 0;
+    long long k_last = 0;
+    while (k_last * F + W < P.R) ++k_last;
+    P.K = (int)k_last + 1;
+    // checks and variables sorted by round (ties by index): a window is a range of each, whatever R is
+    std::vector<int32_t> by_check((size_t)m), by_var((size_t)n);
+    for (int c = 0; c < m; ++c) by_check[c] = c;
+    for (int v = 0; v < n; ++v) by_var[v] = v;
+    std::stable_sort(by_check.begin(), by_check.end(), [&](int a, int b) { return check_round[a] < check_round[b]; });
+    std::stable_sort(by_var.begin(), by_var.end(), [&](int a, int b) { return var_round[a] < var_round[b]; });
+    auto range = [](const std::vector<int32_t>& by, const int32_t* round, long long lo, long long hi, std::vector<int32_t>& out) {
+        auto first = std::lower_bound(by.begin(), by.end(), lo, [&](int a, long long x) { return round[a] < x; });
+        auto last = std::lower_bound(first, by.end(), hi, [&](int a, long long x) { return round[a] < x; });
+        out.assign(first, last);
+        std::sort(out.begin(), out.end());
+    };
+    P.check_ptr.assign(1, 0);
+    P.var_ptr.assign(1, 0);
+    std::vector<int32_t> loc((size_t)n, -1), C, U;
+    std::map<std::pair<std::vector<int32_t>, std::vector<int32_t>>, int> seen;   // (row_ptr + [n_k], col_idx) -> class
+    for (int k = 0; k < P.K; ++k) {
+        const long long lo = (long long)k * F, hi = std::min<long long>(lo + W, P.R);
+        const long long commit_hi = k == P.K - 1 ? hi : lo + F;
+        range(by_check, check_round, lo, hi, C);
+        range(by_var, var_round.data(), lo, hi, U);
+        if ((long long)P.checks.size() + (long long)C.size() > WINDOW_MAX_ENTRIES ||
+            (long long)P.vars.size() + (long long)U.size() > WINDOW_MAX_ENTRIES)
+            return fail(QBP_E_INVALID, "the windows hold more than 2^28 checks or variables in all (W = %d, F = %d)", W, F);
+        P.checks.insert(P.checks.end(), C.begin(), C.end());
+        P.check_ptr.push_back((int32_t)P.checks.size());
+        for (size_t j = 0; j < U.size(); ++j) {
+            P.vars.push_back(U[j]);
+            P.commit.push_back(var_round[U[j]] < commit_hi ? 1 : 0);
+        }
+        P.var_ptr.push_back((int32_t)P.vars.size());
+        if (C.empty() || U.empty()) { P.cls.push_back(-1); continue; }
+        for (size_t j = 0; j < U.size(); ++j) loc[U[j]] = (int32_t)j;
+        std::vector<int32_t> rp(1, 0), ci;
+        for (int c : C) {
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e)
+                if (loc[col_idx[e]] >= 0) ci.push_back(loc[col_idx[e]]);
+            rp.push_back((int32_t)ci.size());
+        }
+        for (int v : U) loc[v] = -1;
+        std::vector<int32_t> key_rp = rp;
+        key_rp.push_back((int32_t)U.size());
+        auto ins = seen.emplace(std::make_pair(std::move(key_rp), ci), (int)P.cls_n.size());
+        if (ins.second) {
+            P.cls_n.push_back((int)U.size());
+            P.cls_row_ptr.push_back(std::move(rp));
+            P.cls_col_idx.push_back(std::move(ci));
+        }
+        P.cls.push_back(ins.first->second);
+    }
+    return QBP_OK;
+}
+
+int qbp_window_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* check_round,
+                    int32_t W, int32_t F, int32_t sizes[3], int32_t* win_check_ptr, int32_t* win_checks,
+                    int32_t* win_var_ptr, int32_t* win_vars, uint8_t* win_commit, int32_t* win_class)
+try {
+    if (!sizes) return fail(QBP_E_INVALID, "sizes is null");
+    WindowPlan P;
+    const int rc = window_plan(row_ptr, col_idx, m, n, check_round, W, F, P);
+    if (rc) return rc;
+    sizes[0] = P.K; sizes[1] = (int32_t)P.checks.size(); sizes[2] = (int32_t)P.vars.size();
+    if (win_check_ptr) std::copy(P.check_ptr.begin(), P.check_ptr.end(), win_check_ptr);
+    if (win_checks) std::copy(P.checks.begin(), P.checks.end(), win_checks);
+    if (win_var_ptr) std::copy(P.var_ptr.begin(), P.var_ptr.end(), win_var_ptr);
+    if (win_vars) std::copy(P.vars.begin(), P.vars.end(), win_vars);
+    if (win_commit) std::copy(P.commit.begin(), P.commit.end(), win_commit);
+    if (win_class) std::copy(P.cls.begin(), P.cls.end(), win_class);
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+struct qbp_window {
+    int device = 0, m = 0, n = 0;
+    WindowPlan plan;
+    std::vector<qbp_handle*> sub;           // one ordinary handle per window class
+    // one window: its class handle, sizes, and where its tables start in the device arrays below
+    struct Win { qbp_handle* h; int mk, nk, check_off, var_off, n_upd, upd_off, upd_ptr_off, ent_off, n_commit, commit_off; };
+    std::vector<Win> win;
+    int max_mk = 0, max_nk = 0;
+    DevBuf<int32_t> d_checks, d_vars;                       // C_k and U_k, window after window
+    DevBuf<int32_t> d_upd_check, d_upd_ptr, d_upd_local;    // the rows of H restricted to M_k (checks with an entry there)
+    DevBuf<int32_t> d_commit_local, d_commit_var;           // M_k as positions in U_k and as columns of H
+    DevBuf<int32_t> d_row_ptr, d_col_idx;                   // H itself (syndromes of the Monte-Carlo entries)
+    // batch workspaces: the running syndrome, one window's inputs and outputs, the failure list and a count per window
+    DevBuf<uint8_t> d_r, d_syn, d_hard, d_conv, d_sol;
+    DevBuf<int32_t> d_it;
+    DevBuf<double> d_llr, d_prior_w;
+    DevBuf<long long> d_fail_list;
+    DevBuf<unsigned long long> d_fail_count;
+    // host-pointer entries and Monte-Carlo
+    hipStream_t stream = nullptr;
+    DevBuf<uint8_t> d_in_syn, d_x, d_conv_out, d_err;
+    DevBuf<double> d_in_prior, d_llr_out;
+    DevBuf<int32_t> d_iters, d_fails;
+    DevBuf<long long> d_counters;
+    DevBuf<unsigned long long> d_lx_cols;
+    std::vector<uint8_t> lx_cache;
+    int lx_cache_k = -1;
+    DevBuf<uint32_t> d_thr;
+    std::vector<uint32_t> thr_cache;
+    long long opt_chunk = 0;
+};
+
+void qbp_window_destroy(qbp_window* w)
+try {
+    if (!w) return;
+    DeviceScope on_device(w->device);
+    for (qbp_handle* h : w->sub) qbp_destroy(h);
+    if (w->stream) (void)hipStreamDestroy(w->stream);
+    delete w;
+}
+catch (...) {
+}
+
+int qbp_window_create(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* check_round,
+                      int32_t W, int32_t F, int32_t device, qbp_window** out)
+try {
+    if (!out) return fail(QBP_E_INVALID, "out is null");
+    *out = nullptr;
+    struct Guard {
+        qbp_window* w;
+        ~Guard() { if (w) qbp_window_destroy(w); }
+    } guard{new qbp_window()};
+    qbp_window* w = guard.w;
+    WindowPlan& P = w->plan;
+    int rc = window_plan(row_ptr, col_idx, m, n, check_round, W, F, P);
+    if (rc) return rc;
+    w->device = device; w->m = m; w->n = n;
+    for (size_t c = 0; c < P.cls_n.size(); ++c) {
+        qbp_handle* h = nullptr;
+        rc = qbp_create(P.cls_row_ptr[c].data(), P.cls_col_idx[c].data(), (int32_t)P.cls_row_ptr[c].size() - 1, P.cls_n[c],
+                        device, &h);
+        if (rc) return rc;
+        w->sub.push_back(h);
+    }
+    // the rows of H restricted to each commit set, and the commit sets themselves
+    std::vector<int32_t> upd_check, upd_ptr, upd_local, commit_local, commit_var, loc((size_t)n, -1);
+    for (int k = 0; k < P.K; ++k) {
+        qbp_window::Win x{};
+        x.h = P.cls[k] >= 0 ? w->sub[P.cls[k]] : nullptr;     // (null: a skipped window)
+        x.check_off = P.check_ptr[k]; x.mk = P.check_ptr[k + 1] - x.check_off;
+        x.var_off = P.var_ptr[k]; x.nk = P.var_ptr[k + 1] - x.var_off;
+        x.upd_off = (int)upd_check.size(); x.upd_ptr_off = (int)upd_ptr.size(); x.ent_off = (int)upd_local.size();
+        x.commit_off = (int)commit_local.size();
+        for (int j = 0; j < x.nk; ++j)
+            if (P.commit[x.var_off + j]) {
+                loc[P.vars[x.var_off + j]] = j;
+                commit_local.push_back(j);
+                commit_var.push_back(P.vars[x.var_off + j]);
+            }
+        upd_ptr.push_back(0);
+        // (a skipped window commits empty columns only, and a window that commits nothing updates nothing)
+        for (int c = 0; x.h && (int)commit_local.size() > x.commit_off && c < m; ++c) {
+            const size_t before = upd_local.size();
+            for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e)
+                if (loc[col_idx[e]] >= 0) upd_local.push_back(loc[col_idx[e]]);
+            if (upd_local.size() == before) continue;
+            upd_check.push_back(c);
+            upd_ptr.push_back((int32_t)(upd_local.size() - x.ent_off));
+        }
+        x.n_upd = (int)upd_check.size() - x.upd_off;
+        x.n_commit = (int)commit_local.size() - x.commit_off;
+        for (int j = x.commit_off; j < (int)commit_var.size(); ++j) loc[commit_var[j]] = -1;
+        w->max_mk = std::max(w->max_mk, x.mk);
+        w->max_nk = std::max(w->max_nk, x.nk);
+        w->win.push_back(x);
+    }
+    DeviceScope on_device(device);
+    HIP_TRY(on_device.err);
+    HIP_TRY(w->d_checks.upload(P.checks));
+    HIP_TRY(w->d_vars.upload(P.vars));
+    HIP_TRY(w->d_upd_check.upload(upd_check));
+    HIP_TRY(w->d_upd_ptr.upload(upd_ptr));
+    HIP_TRY(w->d_upd_local.upload(upd_local));
+    HIP_TRY(w->d_commit_local.upload(commit_local));
+    HIP_TRY(w->d_commit_var.upload(commit_var));
+    HIP_TRY(w->d_row_ptr.upload(std::vector<int32_t>(row_ptr, row_ptr + m + 1)));
+    HIP_TRY(w->d_col_idx.upload(std::vector<int32_t>(col_idx, col_idx + row_ptr[m])));
+    HIP_TRY(w->d_fail_count.reserve((size_t)P.K));
+    HIP_TRY(hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    guard.w = nullptr;
+    *out = w;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// Everything a window call refuses, host only and before any GPU work: the flags, and what a sub-handle would refuse.
+static int window_check_call(qbp_window* w, int64_t B, int32_t max_iter, int32_t variant, uint32_t flags, int* method,
+                             int* order)
+{
+    if (!w) return fail(QBP_E_INVALID, "null window decoder");
+    if (flags & ~(QBP_FLAG_FORCE_FULL | QBP_FLAG_OSD0 | OSD_ALL_BITS))
+        return fail(QBP_E_INVALID, "flags 0x%x: a window call takes QBP_FLAG_FORCE_FULL and the OSD bits only", flags);
+    for (qbp_handle* h : w->sub) {
+        int rc = check_decode_args(h, B, max_iter, variant);
+        if (rc) return rc;
+        if ((rc = parse_osd_flags(h, flags & ~QBP_FLAG_FORCE_FULL, false, method, order)) != QBP_OK) return rc;
+        if (bp_kernel(h, B, 0, 0, false) < 0) return fail(QBP_E_UNSUPPORTED, "a window's matrix does not fit the forced kernel");
+    }
+    return QBP_OK;
+}
+
+// One checked call on the stream (device pointers; any output may be null): the chain of launches of all windows.
+static int window_run(qbp_window* w, const uint8_t* d_syndromes, const double* d_prior, int64_t B, int32_t max_iter,
+                      int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags, int method, int order,
+                      uint8_t* d_x, uint8_t* d_converged, int32_t* d_iters, double* d_llr, int32_t* d_fails, hipStream_t s,
+                      bool gather_prior = true)
+{
+    const size_t b = (size_t)B, m = w->m;
+    const bool osd = (flags & (QBP_FLAG_OSD0 | OSD_METHOD_BITS)) != 0;
+    const int K = w->plan.K;
+    HIP_TRY(w->d_r.reserve(b * m));
+    HIP_TRY(w->d_syn.reserve(b * w->max_mk));
+    HIP_TRY(w->d_hard.reserve(b * w->max_nk));
+    HIP_TRY(w->d_llr.reserve(b * w->max_nk));
+    HIP_TRY(w->d_conv.reserve(b));
+    HIP_TRY(w->d_it.reserve(b));
+    HIP_TRY(w->d_prior_w.reserve(w->plan.vars.size()));
+    if (osd) {
+        HIP_TRY(w->d_sol.reserve(b * w->max_nk));
+        HIP_TRY(w->d_fail_list.reserve(b));
+        HIP_TRY(hipMemsetAsync(w->d_fail_count.p, 0, (size_t)K * sizeof(unsigned long long), s));
+    }
+    HIP_TRY(hipMemcpyAsync(w->d_r.p, d_syndromes, b * m, hipMemcpyDeviceToDevice, s));
+    if (d_iters) HIP_TRY(hipMemsetAsync(d_iters, 0, b * sizeof(int32_t), s));
+    if (d_fails) HIP_TRY(hipMemsetAsync(d_fails, 0, b * sizeof(int32_t), s));
+    // (the priors of all windows: once per call -- the Monte-Carlo entries pass false from their second chunk on)
+    if (gather_prior)
+        HIP_TRY(qbp::launch_window_gather_prior(d_prior, w->d_vars.p, (int)w->plan.vars.size(), w->d_prior_w.p, s));
+    for (int k = 0; k < K; ++k) {
+        const qbp_window::Win& x = w->win[k];
+        if (!x.h) {
+            // rule 0: nothing is decoded or counted; the variables of such a window (empty columns) get 0 and their prior
+            if (x.n_commit && (d_x || d_llr)) {
+                qbp::WindowCommit C{};
+                C.B = B; C.m = w->m; C.n = w->n; C.nk = x.nk; C.llr = w->d_prior_w.p + x.var_off;
+                C.n_commit = x.n_commit;
+                C.commit_local = w->d_commit_local.p + x.commit_off; C.commit_var = w->d_commit_var.p + x.commit_off;
+                C.x = d_x; C.llr_out = d_llr;
+                HIP_TRY(qbp::launch_window_commit(C, false, s));
+            }
+            continue;
+        }
+        HIP_TRY(qbp::launch_window_gather(w->d_r.p, B, w->m, w->d_checks.p + x.check_off, x.mk, w->d_syn.p, s));
+        int rc = qbp_decode_batch_device(x.h, w->d_syn.p, w->d_prior_w.p + x.var_off, B, max_iter, variant, alpha, damping,
+                                         clip_llr, flags & QBP_FLAG_FORCE_FULL, w->d_hard.p, w->d_conv.p, w->d_it.p,
+                                         w->d_llr.p, s);
+        if (rc) return rc;
+        if (osd) {
+            // OSD on the failures only: their list and its device-side count feed the sub-handle's ordinary launch (a
+            // window's syndrome need not lie in the column space of H_k: the redo pass follows the reference there)
+            HIP_TRY(qbp::launch_window_fail_list(w->d_conv.p, B, w->d_fail_list.p, w->d_fail_count.p + k, s));
+            qbp::OsdParams O{};
+            O.count = B; O.count_ptr = reinterpret_cast<const long long*>(w->d_fail_count.p + k); O.list = w->d_fail_list.p;
+            O.syndromes = w->d_syn.p; O.llr = w->d_llr.p; O.hard = w->d_hard.p; O.solution = w->d_sol.p;
+            if ((rc = osd_launch(x.h, O, B, s, true, method, order)) != QBP_OK) return rc;
+        }
+        qbp::WindowCommit C{};
+        C.B = B; C.m = w->m; C.n = w->n; C.nk = x.nk;
+        C.hard = w->d_hard.p; C.sol = osd ? w->d_sol.p : nullptr; C.conv = w->d_conv.p; C.it = w->d_it.p; C.llr = w->d_llr.p;
+        C.n_upd = x.n_upd; C.n_commit = x.n_commit;
+        C.upd_check = w->d_upd_check.p + x.upd_off; C.upd_ptr = w->d_upd_ptr.p + x.upd_ptr_off;
+        C.upd_local = w->d_upd_local.p + x.ent_off;
+        C.commit_local = w->d_commit_local.p + x.commit_off; C.commit_var = w->d_commit_var.p + x.commit_off;
+        C.r = w->d_r.p; C.x = d_x; C.llr_out = d_llr; C.iters = d_iters; C.fails = d_fails; C.converged = d_converged;
+        HIP_TRY(qbp::launch_window_commit(C, false, s));
+    }
+    if (d_converged) {
+        qbp::WindowCommit C{};
+        C.B = B; C.m = w->m; C.r = w->d_r.p; C.converged = d_converged;
+        HIP_TRY(qbp::launch_window_commit(C, true, s));
+    }
+    return QBP_OK;
+}
+
+int qbp_window_decode_batch_device(qbp_window* w, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                   int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                                   uint32_t flags, uint8_t* d_correction, uint8_t* d_converged, int32_t* d_iters,
+                                   double* d_llr, int32_t* d_window_fails, void* stream)
+try {
+    int method = 0, order = 0;
+    const int rc = window_check_call(w, B, max_iter, variant, flags, &method, &order);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
+    if (B > (int64_t)1 << 40) return fail(QBP_E_INVALID, "B too large");
+    DeviceScope on_device(w->device);
+    HIP_TRY(on_device.err);
+    return window_run(w, d_syndromes, d_prior, B, max_iter, variant, alpha, damping, clip_llr, flags, method, order,
+                      d_correction, d_converged, d_iters, d_llr, d_window_fails, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_window_decode_batch(qbp_window* w, const uint8_t* syndromes, const double* prior, int64_t B, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            uint8_t* correction, uint8_t* converged, int32_t* iters, double* llr, int32_t* window_fails)
+try {
+    int method = 0, order = 0;
+    int rc = window_check_call(w, B, max_iter, variant, flags, &method, &order);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
+    if (B > (int64_t)1 << 40) return fail(QBP_E_INVALID, "B too large");
+    for (int v = 0; v < w->n; ++v)
+        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    DeviceScope on_device(w->device);
+    HIP_TRY(on_device.err);
+    const size_t b = (size_t)B, m = w->m, n = w->n;
+    hipStream_t s = w->stream;
+    HIP_TRY(w->d_in_syn.reserve(b * m));
+    HIP_TRY(w->d_in_prior.reserve(n));
+    if (correction) HIP_TRY(w->d_x.reserve(b * n));
+    if (converged) HIP_TRY(w->d_conv_out.reserve(b));
+    if (iters) HIP_TRY(w->d_iters.reserve(b));
+    if (llr) HIP_TRY(w->d_llr_out.reserve(b * n));
+    if (window_fails) HIP_TRY(w->d_fails.reserve(b));
+    HIP_TRY(hipMemcpyAsync(w->d_in_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w->d_in_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    rc = window_run(w, w->d_in_syn.p, w->d_in_prior.p, B, max_iter, variant, alpha, damping, clip_llr, flags, method, order,
+                    correction ? w->d_x.p : nullptr, converged ? w->d_conv_out.p : nullptr, iters ? w->d_iters.p : nullptr,
+                    llr ? w->d_llr_out.p : nullptr, window_fails ? w->d_fails.p : nullptr, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (correction) HIP_TRY(hipMemcpyAsync(correction, w->d_x.p, b * n, hipMemcpyDeviceToHost, s));
+    if (converged) HIP_TRY(hipMemcpyAsync(converged, w->d_conv_out.p, b, hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, w->d_iters.p, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (llr) HIP_TRY(hipMemcpyAsync(llr, w->d_llr_out.p, b * n * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (window_fails) HIP_TRY(hipMemcpyAsync(window_fails, w->d_fails.p, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// One Monte-Carlo call of the window decoder (device prior and counters; Lx and probs host): `d_errors` the stored
+// patterns of trials trial_begin.., or null to draw them.
+struct WindowMcCall {
+    const uint8_t* Lx; int32_t k, distance;
+    const double* probs; int32_t draws; uint64_t seed;
+    const uint8_t* d_errors;
+    int64_t trial_begin, trial_end;
+    const double* d_prior;
+    int32_t max_iter, variant; double alpha, damping, clip_llr; uint32_t flags;
+    int64_t* d_counters;
+};
+
+static int window_mc_check(qbp_window* w, const WindowMcCall& c, bool stored, int* method, int* order)
+{
+    if (!w) return fail(QBP_E_INVALID, "null window decoder");
+    if (!c.d_prior || !c.d_counters) return fail(QBP_E_INVALID, "null pointer");
+    if (c.trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
+    if (c.trial_end < c.trial_begin) return fail(QBP_E_INVALID, "trial_end before trial_begin");
+    if (c.k < 0 || c.k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", c.k);
+    if (c.k > 0 && !c.Lx) return fail(QBP_E_INVALID, "Lx is null");
+    if (stored) {
+        if (!c.d_errors) return fail(QBP_E_INVALID, "errors is null");
+    } else {
+        if (c.draws != 1 && c.draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", c.draws);
+        if (!c.probs) return fail(QBP_E_INVALID, "probs is null");
+        for (int v = 0; v < w->n; ++v)
+            if (!(c.probs[v] >= 0.0 && c.probs[v] <= 1.0))
+                return fail(QBP_E_INVALID, "probs[%d] = %g out of [0, 1]", v, c.probs[v]);
+    }
+    return window_check_call(w, c.trial_end - c.trial_begin, c.max_iter, c.variant, c.flags, method, order);
+}
+
+static long long window_chunk_trials(const qbp_window* w, int64_t T)
+{
+    const long long dflt = std::max<long long>(1, std::min<long long>(1 << 20, ((long long)1 << 28) / (long long)w->n));
+    return std::min<long long>(w->opt_chunk > 0 ? w->opt_chunk : dflt, T);
+}
+
+// A checked call on the stream, chunk by chunk: [sample,] syndrome, the window chain, classification.
+static int window_mc_run(qbp_window* w, const WindowMcCall& c, int method, int order, hipStream_t s)
+{
+    const int64_t T = c.trial_end - c.trial_begin;
+    if (T == 0) return QBP_OK;
+    const size_t n = w->n, m = w->m;
+    // the Lx columns and the sampler thresholds, uploaded when they change (as mc_prepare / mc_prepare_thr do)
+    if (!(w->lx_cache_k == c.k && w->lx_cache.size() == (size_t)c.k * n &&
+          (c.k == 0 || std::memcmp(w->lx_cache.data(), c.Lx, (size_t)c.k * n) == 0))) {
+        std::vector<unsigned long long> cols(n, 0ull);
+        for (int l = 0; l < c.k; ++l)
+            for (size_t v = 0; v < n; ++v)
+                if (c.Lx[(size_t)l * n + v] & 1) cols[v] |= 1ull << l;
+        w->lx_cache_k = -1;
+        HIP_TRY(hipStreamSynchronize(s));   // (an earlier call on the stream may still read the columns)
+        HIP_TRY(w->d_lx_cols.upload(cols));
+        w->lx_cache.assign(c.Lx, c.Lx + (size_t)c.k * n);
+        w->lx_cache_k = c.k;
+    }
+    if (!c.d_errors) {
+        const size_t n4 = (n + 3) / 4 * 4;
+        std::vector<uint32_t> thr(n4, 0u);
+        for (size_t v = 0; v < n; ++v) thr[v] = mc_threshold(c.probs[v]);
+        if (w->thr_cache != thr) {
+            w->thr_cache.clear();
+            HIP_TRY(hipStreamSynchronize(s));
+            HIP_TRY(w->d_thr.upload(thr));
+            w->thr_cache.swap(thr);
+        }
+    }
+    const long long chunk = window_chunk_trials(w, T);
+    if (!c.d_errors) HIP_TRY(w->d_err.reserve((size_t)chunk * n));
+    HIP_TRY(w->d_in_syn.reserve((size_t)chunk * m));
+    HIP_TRY(w->d_x.reserve((size_t)chunk * n));
+    HIP_TRY(w->d_conv_out.reserve((size_t)chunk));
+    HIP_TRY(w->d_iters.reserve((size_t)chunk));
+    HIP_TRY(w->d_fails.reserve((size_t)chunk));
+    for (int64_t a = c.trial_begin; a < c.trial_end; a += chunk) {
+        const long long t = std::min<long long>(chunk, c.trial_end - a);
+        const uint8_t* err = c.d_errors ? c.d_errors + (size_t)(a - c.trial_begin) * n : w->d_err.p;
+        if (!c.d_errors) HIP_TRY(qbp::launch_mc_sample_cols(w->d_err.p, w->n, t, a, c.draws, c.seed, w->d_thr.p, s));
+        HIP_TRY(qbp::launch_window_syndrome(err, t, w->m, w->n, w->d_row_ptr.p, w->d_col_idx.p, w->d_in_syn.p, s));
+        const int rc = window_run(w, w->d_in_syn.p, c.d_prior, t, c.max_iter, c.variant, c.alpha, c.damping, c.clip_llr,
+                                  c.flags, method, order, w->d_x.p, w->d_conv_out.p, w->d_iters.p, nullptr, w->d_fails.p, s,
+                                  a == c.trial_begin);
+        if (rc) return rc;
+        HIP_TRY(qbp::launch_window_classify(err, w->d_x.p, w->d_conv_out.p, w->d_iters.p, w->d_fails.p, t, w->n,
+                                            w->d_lx_cols.p, c.distance / 2, reinterpret_cast<long long*>(c.d_counters), s));
+    }
+    return QBP_OK;
+}
+
+int qbp_window_mc_run_probs_device(qbp_window* w, const uint8_t* Lx_host, int32_t k, int32_t distance,
+                                   const double* probs, int32_t draws, uint64_t seed, int64_t trial_begin,
+                                   int64_t trial_end, const double* d_prior, int32_t max_iter, int32_t variant,
+                                   double alpha, double damping, double clip_llr, uint32_t flags, int64_t* d_counters,
+                                   void* stream)
+try {
+    const WindowMcCall c{Lx_host, k, distance, probs, draws, seed, nullptr, trial_begin, trial_end, d_prior,
+                         max_iter, variant, alpha, damping, clip_llr, flags, d_counters};
+    int method = 0, order = 0;
+    const int rc = window_mc_check(w, c, false, &method, &order);
+    if (rc) return rc;
+    DeviceScope on_device(w->device);
+    HIP_TRY(on_device.err);
+    return window_mc_run(w, c, method, order, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+// The two host-array entries: the prior (and stored errors) uploaded, counters zeroed on the device, the launches, the
+// result ADDED to the caller's counters (stored errors: SET).
+static int window_mc_host(qbp_window* w, WindowMcCall c, const double* prior, const uint8_t* errors, int64_t* counters)
+{
+    const bool stored = errors != nullptr || c.probs == nullptr;
+    c.d_prior = prior; c.d_counters = counters; c.d_errors = errors;
+    int method = 0, order = 0;
+    int rc = window_mc_check(w, c, stored, &method, &order);
+    if (rc) return rc;
+    for (int v = 0; v < w->n; ++v)
+        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if (stored) std::fill(counters, counters + QBP_NUM_COUNTERS, (int64_t)0);
+    const size_t T = (size_t)(c.trial_end - c.trial_begin), n = w->n;
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(w->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = w->stream;
+    HIP_TRY(w->d_in_prior.reserve(n));
+    HIP_TRY(w->d_counters.reserve(QBP_NUM_COUNTERS));
+    HIP_TRY(hipMemcpyAsync(w->d_in_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(w->d_counters.p, 0, QBP_NUM_COUNTERS * sizeof(long long), s));
+    c.d_prior = w->d_in_prior.p; c.d_counters = reinterpret_cast<int64_t*>(w->d_counters.p);
+    if (stored) {
+        HIP_TRY(w->d_err.reserve(T * n));
+        HIP_TRY(hipMemcpyAsync(w->d_err.p, errors, T * n, hipMemcpyHostToDevice, s));
+        c.d_errors = w->d_err.p;
+    }
+    if ((rc = window_mc_run(w, c, method, order, s)) != QBP_OK) { (void)hipStreamSynchronize(s); return rc; }
+    long long tmp[QBP_NUM_COUNTERS];
+    HIP_TRY(hipMemcpyAsync(tmp, w->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] += tmp[i];
+    return QBP_OK;
+}
+
+int qbp_window_mc_run_probs(qbp_window* w, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                            int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* prior,
+                            int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                            uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
+try {
+    if (!probs) return fail(QBP_E_INVALID, "probs is null");
+    return window_mc_host(w, WindowMcCall{Lx, k, distance, probs, draws, seed, nullptr, trial_begin, trial_end, nullptr,
+                                          max_iter, variant, alpha, damping, clip_llr, flags, nullptr},
+                          prior, nullptr, counters);
+}
+QBP_ABI_CATCH
+
+int qbp_window_mc_run_errors(qbp_window* w, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                             int64_t T, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
+try {
+    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    return window_mc_host(w, WindowMcCall{Lx, k, distance, nullptr, 1, 0, nullptr, 0, T, nullptr, max_iter, variant,
+                                          alpha, damping, clip_llr, flags, nullptr},
+                          prior, errors, counters);
+}
+QBP_ABI_CATCH
+
+int64_t qbp_window_get_info(qbp_window* w, int32_t what, int32_t index)
+try {
+    if (!w) return -1;
+    if (what == QBP_WINDOW_INFO_WINDOWS) return w->plan.K;
+    if (what == QBP_WINDOW_INFO_CLASSES) return (int64_t)w->sub.size();
+    if (what == QBP_WINDOW_INFO_ROUNDS) return w->plan.R;
+    if (index < 0 || index >= (int32_t)w->sub.size()) return -1;
+    return qbp_get_info(w->sub[index], what);
+}
+catch (...) { return -1; }
+
+int qbp_window_set_option(qbp_window* w, int32_t option, int64_t value)
+try {
+    if (!w) return fail(QBP_E_INVALID, "null window decoder");
+    if (option == QBP_OPT_MC_WEIGHT_CHUNK) {
+        if (value < 0 || value > (1 << 20)) return fail(QBP_E_INVALID, "trials per chunk out of [0, 2^20]");
+        w->opt_chunk = value;
+        return QBP_OK;
+    }
+    for (qbp_handle* h : w->sub) {
+        const int rc = qbp_set_option(h, option, value);
+        if (rc) return rc;
+    }
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 
 }  // extern "C"

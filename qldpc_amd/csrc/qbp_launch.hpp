@@ -19,6 +19,7 @@ struct OsdOrderBigArgs;
 struct RelayParams;
 struct LayeredParams;
 struct GdParams;
+struct WindowCommit;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -128,6 +129,19 @@ hipError_t launch_relay(bool records, const RelayParams& P, int grid, int thread
 hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
 hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
+// qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)
+hipError_t launch_window_gather(const uint8_t* r, long long B, int m, const int32_t* checks, int mk, uint8_t* syn,
+                                hipStream_t s);
+hipError_t launch_window_gather_prior(const double* prior, const int32_t* vars, int total, double* out, hipStream_t s);
+hipError_t launch_window_fail_list(const uint8_t* conv, long long B, long long* list, unsigned long long* count,
+                                   hipStream_t s);
+// final_pass: converged [B] from the running syndrome, after the last window's commit
+hipError_t launch_window_commit(const WindowCommit& P, bool final_pass, hipStream_t s);
+hipError_t launch_window_syndrome(const uint8_t* errors, long long T, int m, int n, const int32_t* row_ptr,
+                                  const int32_t* col_idx, uint8_t* syn, hipStream_t s);
+hipError_t launch_window_classify(const uint8_t* errors, const uint8_t* x, const uint8_t* valid, const int32_t* iters,
+                                  const int32_t* fails, long long T, int n, const unsigned long long* lx_cols,
+                                  int half_distance, long long* counters, hipStream_t s);
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s);
 hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_t* errors, const int32_t* col_idx,
                            long long B, int E, int n, const double* edges, int bins, unsigned long long* hist,

@@ -215,7 +215,7 @@ def _dem_args(H, L, probs, prior):
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
-            layered=False, gd=None):
+            layered=False, gd=None, window=None, check_round=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -225,11 +225,33 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     ``distance``: the "BPs_miscorrected" / "incorrectable" split compares the error weight with distance // 2;
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
-    tests; by default the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``."""
+    tests (with ``window`` the runner is also passed ``window=(W, F), check_round=``); by default the HIP library and
+    torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``.
+
+    ``window``: ``(W, F)`` -- the sliding-window decoder (qbp_window_mc_run_probs; ``window.py``) with the round of
+    every check in ``check_round``; "not_converged" then counts the trials with a window BP did not converge on.  Not
+    together with ``relay``, ``layered`` or ``gd``.  Sharded and reduced exactly like the plain path."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
     flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
+    if window is not None:
+        if relay is not None or gd is not None or (layered is not None and layered is not False):
+            raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with relay, layered or gd")
+        if check_round is None:
+            raise ValueError("window= needs check_round, the round of every check of H")
+        W, F = (int(x) for x in window)
+        if runner is None:
+            from . import window as window_mod
+            wdec = window_mod.decoder_for(H, check_round, W, F, device=device)
+
+            def launch(i, d_prior, a, b, d_out, stream):
+                wdec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed,
+                                         max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                                         clip_llr=clip_llr, flags=flags, stream=stream)
+            return _on_device((NUM_COUNTERS,), [prior], begin, end, NO_STEP, launch, world, device)
+        cnt = np.asarray(runner(H, L, probs, prior, begin, end, window=(W, F), check_round=check_round), np.int64)
+        return all_reduce(cnt) if all_reduce is not None else cnt
     if runner is None:
         from . import bp
         dec = bp.decoder_for(H, device=device)
@@ -673,6 +695,14 @@ def main(argv=None):
     ap.add_argument("--code", default="[[288, 12, 18]]")
     ap.add_argument("--dem", default=None,
                     help="detector error model file (stim's text format) instead of --code / --p: run_dem")
+    ap.add_argument("--phenomenological", nargs=2, default=None, metavar=("CODE", "ROUNDS"),
+                    help="the phenomenological space-time model of CODE over ROUNDS rounds (dem.phenomenological) at the "
+                         "one --p, data and measurement errors alike, instead of --code or --dem: run_dem; --distance "
+                         "defaults to the code's")
+    ap.add_argument("--window", type=int, nargs=2, default=None, metavar=("W", "F"),
+                    help="with --phenomenological: the sliding-window decoder -- windows of W rounds, each commits F "
+                         "(flooding BP [+ --osd]; not with --relay, --gd, --layered, --budgets, --spectrum, --weights, "
+                         "--shots)")
     ap.add_argument("--distance", type=int, default=0,
                     help="with --dem: the distance of the miscorrected / incorrectable split (0: all incorrectable)")
     ap.add_argument("--p", type=float, nargs="+",
@@ -816,6 +846,33 @@ def main(argv=None):
         if dem_model[1].shape[0] > 64:
             ap.error(f"--dem {args.dem}: {dem_model[1].shape[0]} observables (at most 64)")
 
+    check_round, model_name = None, args.dem
+    if args.phenomenological is not None:
+        from . import dem, window as window_mod
+        if args.dem is not None or args.shots is not None or args.weights is not None:
+            ap.error("--phenomenological does not combine with --dem, --shots or --weights")
+        if len(args.p) != 1:
+            ap.error("--phenomenological takes one --p")
+        code_name, rounds = args.phenomenological
+        try:
+            rounds = int(rounds)
+            code = codes.load_code(code_name)
+            dem_model = dem.phenomenological(code, rounds, args.p[0])
+            check_round = window_mod.phenomenological_rounds(code, rounds)
+        except (ValueError, KeyError, OSError) as e:
+            ap.error(f"--phenomenological {code_name} {rounds}: {e}")
+        if args.distance == 0 and code.distance:
+            args.distance = int(code.distance)
+        model_name = f"phenomenological {code_name} x {rounds}, p={args.p[0]}"
+    if args.window is not None:
+        if check_round is None:
+            ap.error("--window needs --phenomenological (a detector error model file does not say its rounds)")
+        if (relay is not None or gd is not None or args.layered or args.budgets is not None or args.spectrum is not None
+                or args.weights is not None or args.shots is not None):
+            ap.error("--window does not combine with --relay, --gd, --layered, --budgets, --spectrum, --weights or --shots")
+        if args.window[0] < 1 or not 1 <= args.window[1] <= args.window[0]:
+            ap.error("--window W F needs W >= 1 and 1 <= F <= W")
+
     shot_data = None
     if args.shots is not None:
         from . import shots as shots_mod
@@ -931,7 +988,7 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
-                           layered=args.layered, gd=gd, **common)[None, :]
+                           layered=args.layered, gd=gd, window=args.window, check_round=check_round, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()
@@ -953,8 +1010,8 @@ def main(argv=None):
                     s["p"] = args.p[0]
                     label = f"p={args.p[0]}, max_iter={p}"
                 else:
-                    s.update(dem=args.dem)
-                    label = f"dem={args.dem}, max_iter={p}"
+                    s.update(dem=model_name)
+                    label = f"dem={model_name}, max_iter={p}"
             elif args.weights is not None:
                 s.update(weight=p, prior_p=args.prior_p)
                 label = f"weight={p}"
@@ -963,8 +1020,10 @@ def main(argv=None):
                 label = f"p={p}"
             else:
                 H, L, probs = dem_model
-                s.update(dem=args.dem, m=int(H.shape[0]), n=int(H.shape[1]), k=int(L.shape[0]))
-                label = f"dem={args.dem} ({H.shape[0]} x {H.shape[1]}, k={L.shape[0]})"
+                s.update(dem=model_name, m=int(H.shape[0]), n=int(H.shape[1]), k=int(L.shape[0]))
+                if args.window is not None:
+                    s.update(window=list(args.window))
+                label = f"dem={model_name} ({H.shape[0]} x {H.shape[1]}, k={L.shape[0]})"
             rows.append(s)
             print(f"  {label}: LER={s['ler']:.6f}, BP-only LER={s['ler_bp_only']:.6f}, "
                   f"degeneracies={s['degenerateErrors']}, not converged={s['not_converged']}, "
@@ -989,7 +1048,9 @@ def main(argv=None):
                   f"iterations {tables['iterations'].shape}")
         if args.out:
             with open(args.out, "w") as f:
-                model = {"code": args.code} if dem_model is None else {"dem": args.dem, "distance": args.distance}
+                model = {"code": args.code} if dem_model is None else {"dem": model_name, "distance": args.distance}
+                if args.window is not None:
+                    model["window"] = list(args.window)
                 if args.budgets is not None:
                     model["budgets"] = points
                 if args.weights is not None:

@@ -36,6 +36,8 @@ UNITS += [("qbp_tu_relay.hip", [])]
 UNITS += [("qbp_tu_layered.hip", [])]
 # BP guided decimation (qbp_gd_decode_batch, QBP_FLAG_GD): bp_gd_kernel<variant, records>
 UNITS += [("qbp_tu_gd.hip", [])]
+# Sliding-window decoding (qbp_window_*): window_*_kernel, the glue between the windows of one call
+UNITS += [("qbp_tu_window.hip", [])]
 
 
 def demangle(sym):
