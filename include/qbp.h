@@ -101,10 +101,13 @@ enum {
     QBP_FLAG_LAYERED = 1024u, /* the layered (check-serial) schedule instead of flooding: qbp_layered_configure below.
                                  Honoured by qbp_decode_batch(_device), qbp_mc_run(_device), qbp_mc_run_errors,
                                  qbp_mc_run_probs(_device), qbp_mc_run_weight(_device) */
-    QBP_FLAG_GD = 2048u       /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first
+    QBP_FLAG_GD = 2048u,      /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: trials the first
                                  stage (any variant, flooding or QBP_FLAG_LAYERED) does not converge on go through BP
                                  guided decimation (qbp_gd_decode_batch, as configured by qbp_gd_configure), then to
                                  classification */
+    QBP_FLAG_LSD = 4096u      /* the same entries only: those trials go through localized statistics decoding
+                                 (qbp_lsd_batch, as configured by qbp_lsd_configure) on the first stage's posterior and
+                                 hard decision, then to classification */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -465,6 +468,61 @@ int qbp_gd_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* p
 int qbp_gd_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
                                uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters, double* d_llr, int32_t* d_rounds,
                                void* stream);
+
+/*
+ * Localized statistics decoding (BP+LSD; Hillmann, Berent, Di Matteo, Eisert, Wille, Roffe, "Localized statistics
+ * decoding: a parallel decoding algorithm for quantum low-density parity-check codes", 2024): a drop-in alternative to
+ * OSD-0 with the inputs of qbp_osd_batch.  Clusters grow around the unsatisfied checks in the order of BP's
+ * reliabilities; only the small systems inside the clusters are solved, and growth stops as soon as every cluster
+ * explains its own syndrome.  The reference has no such decoder; the rules below are this build's specification
+ * (tests/lsd_oracle.py states them in numpy, and lsd_kernel reproduces that statement bit for bit).
+ *
+ * qbp_lsd_configure stores bits_per_step = g >= 0 in the handle (QBP_E_INVALID otherwise).  QBP_E_UNSUPPORTED: a matrix
+ * of more than 2048 rows or 65535 columns, or whose per-record state -- the bit-packed rows of [H | syndrome] and the
+ * cluster tables -- exceeds the 160 KiB of LDS of one workgroup (the codes of codes/ and 432 x 1296 fit; 864 x 2592
+ * does not).
+ *
+ * One record (syndrome s [m], posterior llr [n], hard decision hard [n]):
+ *   1. rank[v] = position of column v in the ascending order of (|llr[v]| by bit pattern, NaN last, v): OSD-0's order;
+ *   2. r = s ^ (H hard mod 2); the rows are A = [H | r], all m rows and n columns; no row is a pivot row, no column
+ *      is active;
+ *   3. every check c with r[c] = 1 is active (a seed);
+ *   4. at any time the active checks are the seeds and every check adjacent to an active variable; the clusters are the
+ *      connected components of the Tanner graph induced on the active checks and variables (a seed without active
+ *      neighbour is a cluster of one check).  A cluster is invalid when it holds a row that is no pivot row and whose
+ *      reduced syndrome bit is 1;
+ *   5. round t = 1, 2, ... (clusters and validity as at its start): the candidates of an invalid cluster are the
+ *      inactive variables adjacent to one of its checks; g = 0: all of them become active; g >= 1: its g candidates of
+ *      lowest rank (all, if fewer).  A variable two clusters claim is activated once (the clusters merge); valid
+ *      clusters add nothing; a round that activates nothing ends the loop;
+ *   6. the columns activated in the round are eliminated in ascending rank, on the same rows: the pivot of column c is
+ *      the lowest row that is no pivot row yet and has a 1 in c; without one the column is skipped (it stays active);
+ *      otherwise the pivot row is XORed, over the full width and the syndrome bit, into every other row with a 1 in c,
+ *      and pivcol[row] = c.  Every activated column is processed;
+ *   7. the loop ends when every cluster is valid or nothing more can be activated (at most n rounds);
+ *   8. e[pivcol[row]] = reduced syndrome bit of every pivot row, 0 elsewhere; solution = hard ^ e;
+ *      stats = {rounds that activated something, active variables, clusters at the end, valid}, valid = 1 iff no cluster
+ *      is invalid -- the solution then satisfies s.  With valid = 0 the solution is still the readout above.
+ * Row operations never cross clusters, so diag(H1, H2) decodes to the concatenation of the separate solutions; a record
+ * with r = 0 returns hard with stats {0, 0, 0, 1}.
+ *
+ * qbp_lsd_batch: syndromes [B][m], llr [B][n], hard [B][n] -> solution [B][n], stats [B][4] (may be NULL).
+ * QBP_E_INVALID without a configuration.  One wavefront per record, all of its state in LDS (lsd_kernel).
+ *
+ * QBP_FLAG_LSD in a Monte-Carlo call: the first stage is the call's BP as without the flag (any variant, flooding or
+ * QBP_FLAG_LAYERED); every trial it leaves unconverged is decoded by the rules above from its syndrome and the first
+ * stage's posterior and hard decision, and classified on the result like an OSD output: the counters OSD-0 fills.
+ * counters[10] counts the records with valid = 0 (their solution misses the syndrome); [0], [6], [7] are the first
+ * stage's.  The record limits of QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with
+ * QBP_FLAG_OSD0, any OSD bit, QBP_FLAG_RELAY or QBP_FLAG_GD, or without a configuration.  QBP_E_UNSUPPORTED: in
+ * qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and the window entries.
+ */
+int qbp_lsd_configure(qbp_handle* h, int32_t bits_per_step);
+int qbp_lsd_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, const uint8_t* hard, int64_t B,
+                  uint8_t* solution, int32_t* stats);
+/* Same, all pointers are DEVICE pointers, enqueued on `stream` (may be NULL), asynchronous. */
+int qbp_lsd_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_llr, const uint8_t* d_hard,
+                         int64_t B, uint8_t* d_solution, int32_t* d_stats, void* stream);
 
 /* Errors the sampler of qbp_mc_run draws for trials [trial_begin, trial_begin + T):
  * errors [T][n] host bytes.  For tests (compared bit for bit with the oracle's restatement). */

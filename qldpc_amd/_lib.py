@@ -31,6 +31,7 @@ FLAG_OSD_LARGE = 256         # order-w OSD also on matrices beyond the one-wavef
 FLAG_RELAY = 512             # Monte-Carlo calls: Relay-BP (qbp_relay_configure) instead of OSD on the trials BP leaves
 FLAG_LAYERED = 1024          # the layered (check-serial) schedule instead of flooding (qbp_layered_configure)
 FLAG_GD = 2048               # Monte-Carlo calls: BP guided decimation (qbp_gd_configure) on the trials BP leaves
+FLAG_LSD = 4096              # Monte-Carlo calls: localized statistics decoding (qbp_lsd_configure) on those trials
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -121,6 +122,9 @@ SIGNATURES = {
     "qbp_gd_configure": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_double, C.c_double]),
     "qbp_gd_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "qbp_gd_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_lsd_configure": (C.c_int, [_VP, C.c_int32]),
+    "qbp_lsd_batch": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
+    "qbp_lsd_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
     "qbp_window_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
@@ -595,9 +599,38 @@ class Decoder:
                                                  d_converged or None, d_iters or None, d_llr or None, d_rounds or None,
                                                  stream or None))
 
+    @_locked
+    def lsd_configure(self, bits_per_step):
+        """Store the bits_per_step of localized statistics decoding in the handle: qbp_lsd_configure."""
+        _check(load().qbp_lsd_configure(self._h, int(bits_per_step)))
+
+    @_locked
+    def lsd(self, syndromes, llr, hard, bits_per_step=None, want_stats=True):
+        """Localized statistics decoding of B decoder outputs (host arrays; qbp_lsd_batch) -> ``(solution uint8[B, n],
+        stats int32[B, 4])``; ``bits_per_step``: configure first (None: the handle's configuration)."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        l = np.ascontiguousarray(llr, np.float64)
+        hd = np.ascontiguousarray(hard, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m})")
+        if l.shape != (syn.shape[0], self.n) or hd.shape != l.shape:
+            raise ValueError(f"llr and hard must have shape ({syn.shape[0]}, {self.n})")
+        if bits_per_step is not None:
+            self.lsd_configure(bits_per_step)
+        sol = np.empty_like(hd)
+        stats = np.empty((syn.shape[0], 4), np.int32) if want_stats else None
+        _check(load().qbp_lsd_batch(self._h, syn.ctypes.data, l.ctypes.data, hd.ctypes.data, syn.shape[0],
+                                    sol.ctypes.data, _ptr(stats)))
+        return sol, stats
+
+    def lsd_device(self, d_syndromes, d_llr, d_hard, B, d_solution, d_stats=0, stream=0):
+        """``lsd`` on device buffers (pointers as ints; d_stats may be 0), enqueued on `stream`."""
+        _check(load().qbp_lsd_batch_device(self._h, d_syndromes, d_llr, d_hard, int(B), d_solution, d_stats or None,
+                                           stream or None))
+
     def mc_osd_step(self):
-        """Trials one qbp_mc_run call may cover with FLAG_OSD0, FLAG_RELAY or FLAG_GD (per-trial records: m + 10 n
-        bytes)."""
+        """Trials one qbp_mc_run call may cover with FLAG_OSD0, FLAG_RELAY, FLAG_GD or FLAG_LSD (per-trial records:
+        m + 10 n bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
     def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None):
@@ -613,7 +646,7 @@ class Decoder:
         variant, alpha, damping, clip_llr, flags = decoder
         begin, end = int(trial_begin), int(trial_end)
         # with OSD a call keeps per-trial records on the device: split long ranges
-        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(end - begin, 1)
+        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(end - begin, 1)
         for a in range(begin, end, step):
             _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), *source, a, min(a + step, end),
                                        pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
@@ -630,7 +663,7 @@ class Decoder:
             raise ValueError("bad shapes")
         variant, alpha, damping, clip_llr, flags = decoder
         total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(len(err), 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(len(err), 1)
         for a in range(0, len(err), step):
             part = np.zeros(NUM_COUNTERS, np.int64)
             chunk = err[a:a + step]
@@ -797,7 +830,7 @@ class Decoder:
             raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
         pred = np.zeros(T, np.uint64)
         conv = np.zeros(T, np.uint8)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD)) else max(T, 1)
+        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(T, 1)
         for a in range(0, T, step):
             b = min(a + step, T)
             _check(load().qbp_decode_shots(

@@ -23,6 +23,7 @@
 #include "qbp_hist.hpp"
 #include "qbp_relay.hpp"
 #include "qbp_gd.hpp"
+#include "qbp_lsd.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_window.hpp"
 #include "qbp_launch.hpp"
@@ -218,6 +219,11 @@ struct qbp_handle {
     int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
     double gd_llr = 0.0, gd_alpha = 1.0, gd_clip = 0.0;
     DevBuf<int32_t> d_gd_rounds;
+    // localized statistics decoding (qbp_lsd_configure): bits_per_step, the checks of every column (CSC, beside
+    // d_col_ptr); scratch of the host-pointer entry
+    bool lsd_ready = false;
+    int lsd_bits = 0;
+    DevBuf<int32_t> d_lsd_col_row, d_lsd_stats;
     // layered BP (qbp_layered_configure): the checks level after level, the level boundaries
     bool layered_ready = false;
     int layered_levels = 0, layered_max_width = 0;
@@ -2323,6 +2329,122 @@ try {
 }
 QBP_ABI_CATCH
 
+// ---- Localized statistics decoding (qbp_lsd.hpp) ------------------------------------------------------------------
+// The kernel keeps a record's rows of [H | syndrome] and its cluster tables in LDS, a lane tracks its rows in a 32-bit
+// mask, and columns are 16-bit: matrices beyond that are QBP_E_UNSUPPORTED.
+static int lsd_supported(const qbp_handle* h)
+{
+    const size_t lds = qbp::lsd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP);
+    if (lds > (size_t)160 * 1024 || h->m > 64 * 32 || h->n > 65535)
+        return fail(QBP_E_UNSUPPORTED, "localized statistics decoding keeps the bit-packed rows of H and its cluster tables "
+                                       "in LDS: %d x %d needs %zu B (limits: 160 KiB, 2048 rows, 65535 columns)",
+                    h->m, h->n, lds);
+    return QBP_OK;
+}
+
+// QBP_FLAG_LSD of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and shots
+// entries, which have no such stage.
+static int check_lsd_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
+{
+    if (!(flags & QBP_FLAG_LSD)) return QBP_OK;
+    if (flags & (QBP_FLAG_OSD0 | OSD_ALL_BITS | QBP_FLAG_RELAY | QBP_FLAG_GD))
+        return fail(QBP_E_INVALID, "QBP_FLAG_LSD together with an OSD bit, QBP_FLAG_RELAY or QBP_FLAG_GD: one second stage "
+                                   "per call");
+    if (other_entry)
+        return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_LSD is not available with iteration budgets, spectra or recorded shots");
+    if (!h->lsd_ready) return fail(QBP_E_INVALID, "QBP_FLAG_LSD without qbp_lsd_configure");
+    return QBP_OK;                      // (qbp_lsd_configure has checked the limits)
+}
+
+// One launch of lsd_kernel (device pointers in P: a batch, or the failure records of a Monte-Carlo launch)
+static int lsd_launch(qbp_handle* h, qbp::LsdParams& P, long long max_items, bool records, hipStream_t s)
+{
+    const int rc = osd_prepare(h);      // (the bit-packed rows of H)
+    if (rc) return rc;
+    P.m = h->m; P.n = h->n; P.W = h->osd_W; P.NP = h->osd_NP;
+    P.hbits = h->d_hbits.p; P.row_ptr = h->d_row_ptr.p; P.col_idx = h->d_col_idx.p;
+    P.col_ptr = h->d_col_ptr.p; P.col_row = h->d_lsd_col_row.p;
+    P.bits_per_step = h->lsd_bits;
+    const size_t lds = (qbp::lsd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
+    // one wavefront per workgroup: as many per CU as the LDS holds, up to osd0_kernel's 32; QBP_OPT_BLOCKS_PER_CU overrides
+    long long per_cu = std::max<long long>(1, std::min<long long>(32, (long long)(((size_t)160 * 1024) / lds)));
+    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
+    const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * per_cu));
+    h->last_threads = 64; h->last_lds = (int)lds; h->last_grid = (int)grid;
+    HIP_TRY(qbp::launch_lsd(records, P, (unsigned)grid, lds, s));
+    return QBP_OK;
+}
+
+int qbp_lsd_configure(qbp_handle* h, int32_t bits_per_step)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (bits_per_step < 0) return fail(QBP_E_INVALID, "bits_per_step = %d (need >= 0)", bits_per_step);
+    int rc = lsd_supported(h);
+    if (rc) return rc;
+    if (!h->d_lsd_col_row.p) {
+        // the checks of every column in ascending order, at the offsets of d_col_ptr
+        DeviceScope on_device(h->device);
+        HIP_TRY(on_device.err);
+        std::vector<int32_t> at((size_t)h->n + 1, 0), col_row((size_t)std::max(h->E, 1), 0);
+        for (int e = 0; e < h->E; ++e) ++at[(size_t)h->col_idx[e] + 1];
+        for (int v = 0; v < h->n; ++v) at[(size_t)v + 1] += at[v];
+        for (int c = 0; c < h->m; ++c)
+            for (int e = h->row_ptr[c]; e < h->row_ptr[c + 1]; ++e) col_row[(size_t)at[h->col_idx[e]]++] = c;
+        HIP_TRY(h->d_lsd_col_row.upload(col_row));
+        if ((rc = osd_prepare(h)) != QBP_OK) return rc;
+    }
+    h->lsd_bits = bits_per_step;
+    h->lsd_ready = true;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_lsd_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_llr, const uint8_t* d_hard,
+                         int64_t B, uint8_t* d_solution, int32_t* d_stats, void* stream)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->lsd_ready) return fail(QBP_E_INVALID, "qbp_lsd_batch without qbp_lsd_configure");
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_llr || !d_hard || !d_solution) return fail(QBP_E_INVALID, "null pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    qbp::LsdParams P{};
+    P.count = B; P.syndromes = d_syndromes; P.llr = d_llr; P.hard = d_hard; P.solution = d_solution; P.stats = d_stats;
+    return lsd_launch(h, P, B, false, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_lsd_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, const uint8_t* hard, int64_t B,
+                  uint8_t* solution, int32_t* stats)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (B < 0) return fail(QBP_E_INVALID, "B must be >= 0 (got %lld)", (long long)B);
+    if (!h->lsd_ready) return fail(QBP_E_INVALID, "qbp_lsd_batch without qbp_lsd_configure");
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_llr.reserve(b * n));
+    HIP_TRY(h->d_hard.reserve(b * n));
+    HIP_TRY(h->d_sol.reserve(b * n));
+    if (stats) HIP_TRY(h->d_lsd_stats.reserve(b * 4));
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
+    const int rc = qbp_lsd_batch_device(h, h->d_syn.p, h->d_llr.p, h->d_hard.p, B, h->d_sol.p,
+                                        stats ? h->d_lsd_stats.p : nullptr, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, h->d_lsd_stats.p, b * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
 // ---- Monte-Carlo (include/qbp.h: qbp_mc_run*) --------------------------------------------------------------------
 
 // Where the errors of a Monte-Carlo call come from; only the fields of `kind` are read.
@@ -2392,7 +2514,8 @@ static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial
     return QBP_OK;
 }
 
-constexpr uint32_t SECOND_BP_BITS = QBP_FLAG_RELAY | QBP_FLAG_GD;    // second stages that are no OSD: never a BP launch's bit
+// second stages that are no OSD: never a BP launch's bit
+constexpr uint32_t SECOND_BP_BITS = QBP_FLAG_RELAY | QBP_FLAG_GD | QBP_FLAG_LSD;
 
 // Everything a Monte-Carlo call refuses: host only, once per public call, for the whole range and before any GPU work.
 // `host_prior`: the priors when they are a host array (the layered schedule's finite check), else null.
@@ -2413,6 +2536,7 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
     // ladders and spectra have neither a Relay or guided-decimation stage nor a layered build
     if ((rc = check_relay_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_gd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
+    if ((rc = check_lsd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if (host_prior && (c.dec.flags & QBP_FLAG_LAYERED) && (rc = check_finite_prior(h, host_prior)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
@@ -2462,13 +2586,15 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     const bool relay = (c.dec.flags & QBP_FLAG_RELAY) != 0;
     // likewise BP guided decimation
     const bool gd = (c.dec.flags & QBP_FLAG_GD) != 0;
+    // and localized statistics decoding, which reads the records OSD-0 reads
+    const bool lsd = (c.dec.flags & QBP_FLAG_LSD) != 0;
     // order-w OSD: its bits go to the OSD launch only, never to the decoder's launch or column-order logic
     int osd_method = 0, osd_order = 0;
     int rc = parse_osd_flags(h, c.dec.flags & ~SECOND_BP_BITS, true, &osd_method, &osd_order);
     if (rc) return rc;
     const uint32_t flags = c.dec.flags & ~(SECOND_BP_BITS | OSD_ALL_BITS);
     const bool layered = (flags & QBP_FLAG_LAYERED) != 0;
-    const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay || gd;
+    const bool osd = (flags & QBP_FLAG_OSD0) != 0 || relay || gd || lsd;
     McArgs mc{};
     // (qbp_mc_run_budgets: a record per trial and budget)
     if (osd && (rc = mc_fail_records(h, mc, rows, (size_t)T, true, s)) != QBP_OK) return rc;
@@ -2519,6 +2645,15 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
         g.fail_syn = h->d_fail_syn.p; g.fail_err = h->d_fail_err.p;
         g.half_distance = c.distance / 2; g.counters = reinterpret_cast<long long*>(c.d_counters);
         return gd_launch(h, g, true, s);
+    }
+    if (lsd) {
+        // second kernel: localized statistics decoding + classification of the same records
+        qbp::LsdParams P{};
+        P.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p); P.list = h->d_fail_list.p;
+        P.syndromes = h->d_fail_syn.p; P.llr = h->d_fail_llr.p; P.hard = h->d_fail_hard.p;
+        P.errors = h->d_fail_err.p; P.lx_cols = h->d_lx_cols.p; P.half_distance = c.distance / 2;
+        P.counters = reinterpret_cast<long long*>(c.d_counters);
+        return lsd_launch(h, P, T, true, s);
     }
     // second kernel: OSD-0 + classification of the trials BP left unconverged; their number is
     // read from device memory by the kernel itself (no host round trip)
@@ -2837,6 +2972,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k = %d observables (need 1..64)", k);
     if ((rc = check_relay_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_gd_flags(h, flags, true)) != QBP_OK) return rc;
+    if ((rc = check_lsd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, flags, 0, true)) != QBP_OK) return rc;
     if (host_prior)
         for (int v = 0; v < h->n; ++v)
@@ -3289,6 +3425,7 @@ static int window_check_call(qbp_window* w, int64_t B, int32_t max_iter, int32_t
                              int* order)
 {
     if (!w) return fail(QBP_E_INVALID, "null window decoder");
+    if (flags & QBP_FLAG_LSD) return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_LSD is not available in a window call");
     if (flags & ~(QBP_FLAG_FORCE_FULL | QBP_FLAG_OSD0 | OSD_ALL_BITS))
         return fail(QBP_E_INVALID, "flags 0x%x: a window call takes QBP_FLAG_FORCE_FULL and the OSD bits only", flags);
     for (qbp_handle* h : w->sub) {

@@ -19,6 +19,7 @@ struct OsdOrderBigArgs;
 struct RelayParams;
 struct LayeredParams;
 struct GdParams;
+struct LsdParams;
 struct WindowCommit;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
@@ -129,6 +130,8 @@ hipError_t launch_relay(bool records, const RelayParams& P, int grid, int thread
 hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
 hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
+// qbp_tu_lsd.hip: lsd_kernel<records> (batch build or Monte-Carlo failure records), one wavefront per record
+hipError_t launch_lsd(bool records, const LsdParams& P, unsigned grid, size_t lds, hipStream_t s);
 // qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)
 hipError_t launch_window_gather(const uint8_t* r, long long B, int m, const int32_t* checks, int mk, uint8_t* syn,
                                 hipStream_t s);

@@ -92,6 +92,23 @@ def gd_run_flags(flags, gd) -> int:
     return flags | _lib.FLAG_GD
 
 
+def lsd_run_flags(flags, lsd) -> int:
+    """``flags`` of a sweep with ``lsd`` (None, or the bits_per_step of localized statistics decoding): | FLAG_LSD, the
+    trials BP leaves unconverged go to LSD.  ValueError together with OSD, Relay-BP or BPGD: one second stage per run."""
+    if lsd is None:
+        return flags
+    if flags & (_lib.FLAG_OSD0 | _lib.FLAG_OSD_CS | _lib.FLAG_OSD_E | _lib.FLAG_OSD_LARGE | _lib.FLAG_RELAY | _lib.FLAG_GD):
+        raise ValueError("lsd= excludes osd=True, relay= and gd=: one second stage per run")
+    from . import lsd as lsd_mod
+    lsd_mod.check_bits_per_step(lsd)    # (a bad value raises here, before any GPU work)
+    return flags | _lib.FLAG_LSD
+
+
+def _configure_lsd(dec, lsd):
+    if lsd is not None:
+        dec.lsd_configure(lsd)
+
+
 def _configure_gd(dec, gd):
     if gd is not None:
         from . import gd as gd_mod
@@ -145,8 +162,11 @@ NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial record
 
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
-              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None):
+              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
+
+    ``lsd``: the bits_per_step (>= 0) of localized statistics decoding on the trials BP does not converge on (FLAG_LSD;
+    not together with ``osd``, ``relay`` or ``gd``).
 
     ``gd``: a ``gd.GDConfig`` or its dict form -- BP guided decimation on the trials BP does not converge on (FLAG_GD;
     not together with ``osd`` or ``relay``).
@@ -162,7 +182,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -170,8 +190,9 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
+        _configure_lsd(dec, lsd)
         _configure_layered(dec, layered)
-        step = dec.mc_osd_step() if osd or relay is not None or gd is not None else NO_STEP   # (per-trial records)
+        step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_device(code.Lx, code.distance, ps[i], d_prior, a, b, d_out, draws=draws, seed=seed,
@@ -215,7 +236,7 @@ def _dem_args(H, L, probs, prior):
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
-            layered=False, gd=None, window=None, check_round=None):
+            layered=False, gd=None, window=None, check_round=None, lsd=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -226,18 +247,20 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
     tests (with ``window`` the runner is also passed ``window=(W, F), check_round=``); by default the HIP library and
-    torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``.
+    torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``: as in ``run_sweep``.
 
     ``window``: ``(W, F)`` -- the sliding-window decoder (qbp_window_mc_run_probs; ``window.py``) with the round of
     every check in ``check_round``; "not_converged" then counts the trials with a window BP did not converge on.  Not
-    together with ``relay``, ``layered`` or ``gd``.  Sharded and reduced exactly like the plain path."""
+    together with ``relay``, ``layered``, ``gd`` or ``lsd``.  Sharded and reduced exactly like the plain path."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
-    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if window is not None:
         if relay is not None or gd is not None or (layered is not None and layered is not False):
             raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with relay, layered or gd")
+        if lsd is not None:
+            raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with lsd")
         if check_round is None:
             raise ValueError("window= needs check_round, the round of every check of H")
         W, F = (int(x) for x in window)
@@ -257,8 +280,9 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         dec = bp.decoder_for(H, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
+        _configure_lsd(dec, lsd)
         _configure_layered(dec, layered)
-        step = dec.mc_osd_step() if osd or relay is not None or gd is not None else NO_STEP   # (per-trial records)
+        step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed, max_iter=max_iter,
@@ -530,22 +554,22 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
         dec.mc_run_weight_device(L, distance, weights[i], d_prior, a, b, d_out, seed=seed, max_iter=max_iter,
                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
                                  stream=stream)
-    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD)) else NO_STEP    # (per-trial records)
+    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD | _lib.FLAG_LSD)) else NO_STEP    # (per-trial records)
     return _on_device((len(weights), NUM_COUNTERS), [prior] * len(weights), begin, end, step, launch, world, device)
 
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
-                device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None):
+                device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``: as in ``run_sweep``."""
+    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(gd_run_flags(flags, gd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
@@ -554,6 +578,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
+        _configure_lsd(dec, lsd)
         _configure_layered(dec, layered)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
@@ -760,6 +785,10 @@ def main(argv=None):
     ap.add_argument("--gd-llr", type=float, default=25.0, metavar="X", help="the prior a decimated variable gets is +-X")
     ap.add_argument("--gd-variant", choices=("sum-product", "min-sum"), default="min-sum",
                     help="the BP that --gd runs between decimations")
+    ap.add_argument("--lsd", type=int, default=None, metavar="G",
+                    help="localized statistics decoding on the trials BP does not converge on: every invalid cluster "
+                         "activates its G least reliable neighbours per round, 0: all of them (not with --osd, --relay, "
+                         "--gd, --budgets, --spectrum, --shots, --window)")
     ap.add_argument("--layered", action="store_true",
                     help="BP runs the layered (check-serial) schedule in its default order instead of flooding "
                          "(sum-product or min-sum; not with --budgets, --spectrum, --shots)")
@@ -802,6 +831,18 @@ def main(argv=None):
             gd_mod.as_config(gd)
         except (ValueError, TypeError) as e:
             ap.error(f"--gd: {e}")
+    lsd = None
+    if args.lsd is not None:
+        if args.osd or args.relay is not None or args.gd is not None:
+            ap.error("--lsd excludes --osd, --relay and --gd")
+        if (args.budgets is not None or args.spectrum is not None or args.shots is not None
+                or getattr(args, "window", None) is not None):
+            ap.error("--lsd does not combine with --budgets, --spectrum, --shots or --window")
+        try:
+            from . import lsd as lsd_mod
+            lsd = lsd_mod.check_bits_per_step(args.lsd)
+        except ValueError as e:
+            ap.error(f"--lsd: {e}")
     if args.layered:
         if args.budgets is not None or args.spectrum is not None or args.shots is not None:
             ap.error("--layered does not combine with --budgets, --spectrum or --shots")
@@ -976,19 +1017,20 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               layered=args.layered, gd=gd, **common)
+                               layered=args.layered, gd=gd, lsd=lsd, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
             return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered, gd=gd,
-                             **common)
+                             lsd=lsd, **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
-                           layered=args.layered, gd=gd, window=args.window, check_round=check_round, **common)[None, :]
+                           layered=args.layered, gd=gd, window=args.window, check_round=check_round, lsd=lsd,
+                           **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

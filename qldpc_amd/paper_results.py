@@ -69,8 +69,11 @@ def main(argv=None):
     ap.add_argument("--trials", type=int, default=10000)                       # :36
     ap.add_argument("--max-iter", type=int, default=150)                       # :109
     ap.add_argument("--draws", type=int, default=2, choices=(1, 2))            # :96-105
-    ap.add_argument("--osd", type=int, default=0, choices=(-1, 0),
-                    help="0: OSD on BP failures (OSD-0 as paperResults.py:77 unless --osd-order); -1: BP only")
+    ap.add_argument("--osd", type=int, default=None, choices=(-1, 0),
+                    help="0 (default): OSD on BP failures (OSD-0 as paperResults.py:77 unless --osd-order); -1: BP only")
+    ap.add_argument("--lsd", type=int, default=None, metavar="G",
+                    help="localized statistics decoding instead of OSD on BP failures: G variables per cluster and round, "
+                         "0: all neighbours (not with --osd 0 or --osd-order)")
     ap.add_argument("--osd-method", choices=("cs", "e"), default="cs",
                     help="with --osd-order W >= 1: combination sweep or exhaustive search")
     ap.add_argument("--osd-order", type=int, default=0,
@@ -83,11 +86,15 @@ def main(argv=None):
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL; gloo only for rehearsals")
     ap.add_argument("--share-device", action="store_true", help="rehearsal: every rank on cuda:0")
     args = ap.parse_args(argv)
+    if args.lsd is not None and (args.osd == 0 or args.osd_order):
+        ap.error("--lsd excludes --osd 0 and --osd-order")
+    if args.osd is None:
+        args.osd = -1 if args.lsd is not None else 0
     try:
-        mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order)
+        mc.lsd_run_flags(mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order), args.lsd)
     except ValueError as e:
         ap.error(str(e))
-    osd_name = ("no OSD" if args.osd != 0 else "OSD-0" if args.osd_order == 0
+    osd_name = (f"LSD-{args.lsd}" if args.lsd is not None else "no OSD" if args.osd != 0 else "OSD-0" if args.osd_order == 0
                 else f"OSD-{args.osd_method.upper()}-{args.osd_order}")
 
     import sys
@@ -123,7 +130,7 @@ def main(argv=None):
         t0 = time.time()
         tables[name] = mc.run_sweep(name, args.p, args.trials, draws=args.draws, seed=args.seed,
                                     max_iter=args.max_iter, osd=args.osd == 0, osd_method=args.osd_method,
-                                    osd_order=args.osd_order, rank=rank, world=world, device=local)
+                                    osd_order=args.osd_order, rank=rank, world=world, device=local, lsd=args.lsd)
         if rank == 0:
             dt = time.time() - t0
             for p, row in zip(args.p, tables[name]):
@@ -134,7 +141,7 @@ def main(argv=None):
         print(f"\n{'=' * 60}\nTotal time: {total:.1f}s ({total / 60:.1f} min)")
         meta = dict(physicalErrorRates=args.p, trials=args.trials, maxIter=args.max_iter,
                     draws=args.draws, osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
-                    osd_decoder=osd_name, seed=args.seed, world_size=world,
+                    osd_decoder=osd_name, lsd=args.lsd, seed=args.seed, world_size=world,
                     noise="XOR of two Bernoulli(p) draws" if args.draws == 2 else "Bernoulli(p)",
                     decoder="sum-product BP (libqbp, MI355X)", seconds=total,
                     counters={n: tables[n].tolist() for n in tables},

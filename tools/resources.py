@@ -38,6 +38,8 @@ UNITS += [("qbp_tu_layered.hip", [])]
 UNITS += [("qbp_tu_gd.hip", [])]
 # Sliding-window decoding (qbp_window_*): window_*_kernel, the glue between the windows of one call
 UNITS += [("qbp_tu_window.hip", [])]
+# Localized statistics decoding (qbp_lsd_batch, QBP_FLAG_LSD): lsd_kernel<records>
+UNITS += [("qbp_tu_lsd.hip", [])]
 
 
 def demangle(sym):
