@@ -2007,8 +2007,9 @@ static int check_relay_flags(const qbp_handle* h, uint32_t flags, bool other_ent
     return relay_supported(h, true);
 }
 
-// One launch of bp_relay_kernel (device pointers): a batch of syndromes, or the failure records of a Monte-Carlo launch
-struct RelayCall {
+// One launch of bp_relay_kernel or bp_gd_kernel (device pointers): a batch of syndromes, or the failure records of a
+// Monte-Carlo launch
+struct RecordCall {
     const double* prior = nullptr;
     long long max_items = 0;            // B, or the most records the list can hold
     const uint8_t* syndromes = nullptr;
@@ -2016,8 +2017,7 @@ struct RelayCall {
     uint8_t* converged = nullptr;
     int32_t* iters = nullptr;
     double* llr = nullptr;
-    int32_t* legs = nullptr;
-    int32_t* solutions = nullptr;
+    int32_t* extra[2] = {nullptr, nullptr};     // Relay-BP: legs, solutions; BP guided decimation: rounds
     const unsigned long long* fail_count = nullptr;
     const long long* fail_list = nullptr;
     const uint8_t* fail_syn = nullptr;
@@ -2026,24 +2026,32 @@ struct RelayCall {
     long long* counters = nullptr;
 };
 
-static int relay_launch(qbp_handle* h, const RelayCall& c, bool records, hipStream_t s)
+// What the launches of the two kernels share: the limit of a call, the grid -- resident workgroups per CU: `waves`
+// wavefronts at the kernel's registers, and the LDS; QBP_OPT_BLOCKS_PER_CU overrides where the decoder honours it --,
+// the workspace, the sorted prior, the work counter, the tables of the general-H kernel (P) and the inputs and outputs of
+// the call (io).  *grid: the workgroups to launch.
+struct RecordGeometry {
+    const char* name;           // of the decoder, for messages
+    size_t lds;
+    int threads, waves;
+    bool honours_blocks_per_cu;
+};
+static int record_launch_setup(qbp_handle* h, const RecordCall& c, bool records, const RecordGeometry& g, hipStream_t s,
+                               qbp::RecordTables& P, qbp::RecordIo& io, int* grid_out)
 {
-    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
+    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS;
     constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
     if (c.max_items > MAX_LAUNCH)
-        return fail(QBP_E_UNSUPPORTED, "Relay-BP decodes at most 2^30 syndromes per call (got %lld)", c.max_items);
+        return fail(QBP_E_UNSUPPORTED, "%s decodes at most 2^30 syndromes per call (got %lld)", g.name, c.max_items);
     const size_t n = (size_t)h->n;
-    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
-    const int threads = qbp::relay_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1]);
-    // resident workgroups per CU: 28 wavefronts at the kernel's registers, and the LDS
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)(28 / (threads / 64)), ((size_t)160 * 1024) / lds));
+    int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)(g.waves / (g.threads / 64)), ((size_t)160 * 1024) / g.lds));
+    if (g.honours_blocks_per_cu && h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
     const int grid = (int)std::max<long long>(1, std::min<long long>(c.max_items, (long long)h->num_cu * per_cu));
     const size_t n_long = (size_t)(h->row_off[RC + 2] - h->row_off[RC + 1]);
     HIP_TRY(h->d_wsL.reserve((size_t)grid * 3 * std::max<size_t>(n_long, 1)));
     HIP_TRY(h->d_prior_sorted.reserve(n));
     HIP_TRY(qbp::launch_permute_prior(c.prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
     HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
-    qbp::RelayParams P{};
     P.m = h->m; P.n = h->n; P.E = h->E;
     P.srow = h->d_srow.p; P.srow_e0 = h->d_srow_e0.p; P.srow_deg = h->d_srow_deg.p; P.epos = h->d_epos.p;
     P.long_edge_row = h->d_long_edge_row.p; P.svar = h->d_svar.p; P.vpos = h->d_vpos.p; P.vrow = h->d_vrow.p;
@@ -2054,15 +2062,71 @@ static int relay_launch(qbp_handle* h, const RelayCall& c, bool records, hipStre
     std::copy(std::begin(h->col_off), std::end(h->col_off), P.col_off);
     std::copy(std::begin(h->gcol_base), std::end(h->gcol_base), P.col_base);
     std::copy(std::begin(h->cpad_off), std::end(h->cpad_off), P.cpad_off);
-    P.vinv = h->d_relay_vinv.p; P.prior = c.prior; P.prior_sorted = h->d_prior_sorted.p; P.wsL = h->d_wsL.p;
+    P.prior_sorted = h->d_prior_sorted.p; P.wsL = h->d_wsL.p;
     P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    io.syndromes = c.syndromes; io.B = records ? 0 : c.max_items;
+    io.hard = c.hard; io.converged = c.converged; io.iters = c.iters; io.llr = c.llr;
+    io.fail_count = c.fail_count; io.fail_list = c.fail_list; io.fail_syn = c.fail_syn; io.fail_err = c.fail_err;
+    io.lx_cols = h->d_lx_cols.p; io.half_distance = c.half_distance; io.counters = c.counters;
+    h->last_threads = g.threads; h->last_lds = (int)g.lds; h->last_grid = grid;
+    *grid_out = grid;
+    return QBP_OK;
+}
+
+extern "C++" {       // (a template: not in the C linkage of the entry points around it)
+// The host-pointer entry of both decoders after its argument checks: finite prior, staging, the device entry
+// (entry(d_hard, d_converged, d_iters, d_llr, d_extra0, d_extra1, stream)), download.  extra / d_extra: the decoder's
+// own int32 columns and their scratch (a slot it does not have is null).
+template <class Entry>
+static int record_decode_batch_host(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, uint8_t* hard,
+                                    uint8_t* converged, int32_t* iters, double* llr, int32_t* const (&extra)[2],
+                                    DevBuf<int32_t>* const (&d_extra)[2], const Entry& entry)
+{
+    for (int v = 0; v < h->n; ++v)
+        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HIP_TRY(h->d_syn.reserve(b * m));
+    HIP_TRY(h->d_prior.reserve(n));
+    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
+    if (converged) HIP_TRY(h->d_conv.reserve(b));
+    if (iters) HIP_TRY(h->d_iters.reserve(b));
+    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
+    for (int k = 0; k < 2; ++k)
+        if (extra[k]) HIP_TRY(d_extra[k]->reserve(b));
+    hipStream_t s = h->stream;
+    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
+    int rc = entry(hard ? h->d_hard.p : nullptr, converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
+                   llr ? h->d_llr.p : nullptr, extra[0] ? d_extra[0]->p : nullptr, extra[1] ? d_extra[1]->p : nullptr, s);
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }
+    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
+    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
+    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
+    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < 2; ++k)
+        if (extra[k]) HIP_TRY(hipMemcpyAsync(extra[k], d_extra[k]->p, b * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return QBP_OK;
+}
+
+}  // extern "C++"
+
+static int relay_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream_t s)
+{
+    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
+    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
+    const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::RELAY_MAX_THREADS);
+    qbp::RelayParams P{};
+    int grid = 0;
+    // 28 wavefronts per CU at the kernel's registers; QBP_OPT_BLOCKS_PER_CU is not honoured
+    const int rc = record_launch_setup(h, c, records, {"Relay-BP", lds, threads, 28, false}, s, P.tab, P.io, &grid);
+    if (rc) return rc;
+    P.vinv = h->d_relay_vinv.p; P.prior = c.prior;
     P.gammas_sorted = h->d_relay_gammas.p; P.leg_iters = h->d_relay_iters.p;
     P.L = h->relay_L; P.stop_after = h->relay_stop_after; P.alpha = h->relay_alpha; P.clip_llr = h->relay_clip;
-    P.syndromes = c.syndromes; P.B = records ? 0 : c.max_items;
-    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr; P.legs = c.legs; P.solutions = c.solutions;
-    P.fail_count = c.fail_count; P.fail_list = c.fail_list; P.fail_syn = c.fail_syn; P.fail_err = c.fail_err;
-    P.lx_cols = h->d_lx_cols.p; P.half_distance = c.half_distance; P.counters = c.counters;
-    h->last_threads = threads; h->last_lds = (int)lds; h->last_grid = grid;
+    P.legs = c.extra[0]; P.solutions = c.extra[1];
     HIP_TRY(qbp::launch_relay(records, P, grid, threads, lds, s));
     return QBP_OK;
 }
@@ -2119,9 +2183,10 @@ try {
     if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    RelayCall c;
+    RecordCall c;
     c.prior = d_prior; c.max_items = B; c.syndromes = d_syndromes;
-    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr; c.legs = d_legs; c.solutions = d_solutions;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr;
+    c.extra[0] = d_legs; c.extra[1] = d_solutions;
     return relay_launch(h, c, false, static_cast<hipStream_t>(stream));
 }
 QBP_ABI_CATCH
@@ -2134,35 +2199,14 @@ try {
     if (!h->relay_ready) return fail(QBP_E_INVALID, "qbp_relay_decode_batch without qbp_relay_configure");
     if (B == 0) return QBP_OK;
     if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
-    for (int v = 0; v < h->n; ++v)
-        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
-    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
-    if (converged) HIP_TRY(h->d_conv.reserve(b));
-    if (iters) HIP_TRY(h->d_iters.reserve(b));
-    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
-    if (legs) HIP_TRY(h->d_relay_legs.reserve(b));
-    if (solutions) HIP_TRY(h->d_relay_sol.reserve(b));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    int rc = qbp_relay_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, hard ? h->d_hard.p : nullptr,
-                                           converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
-                                           llr ? h->d_llr.p : nullptr, legs ? h->d_relay_legs.p : nullptr,
-                                           solutions ? h->d_relay_sol.p : nullptr, s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
-    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
-    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
-    if (legs) HIP_TRY(hipMemcpyAsync(legs, h->d_relay_legs.p, b * 4, hipMemcpyDeviceToHost, s));
-    if (solutions) HIP_TRY(hipMemcpyAsync(solutions, h->d_relay_sol.p, b * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    int32_t* const extra[2] = {legs, solutions};
+    DevBuf<int32_t>* const d_extra[2] = {&h->d_relay_legs, &h->d_relay_sol};
+    return record_decode_batch_host(h, syndromes, prior, B, hard, converged, iters, llr, extra, d_extra,
+                                    [&](uint8_t* d_hard, uint8_t* d_conv, int32_t* d_iters, double* d_llr, int32_t* d_legs,
+                                        int32_t* d_sol, hipStream_t s) {
+                                        return qbp_relay_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, d_hard, d_conv,
+                                                                             d_iters, d_llr, d_legs, d_sol, s);
+                                    });
 }
 QBP_ABI_CATCH
 
@@ -2190,65 +2234,22 @@ static int check_gd_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
     return QBP_OK;                      // (qbp_gd_configure has checked the LDS)
 }
 
-// One launch of bp_gd_kernel (device pointers): a batch of syndromes, or the failure records of a Monte-Carlo launch
-struct GdCall {
-    const double* prior = nullptr;
-    long long max_items = 0;            // B, or the most records the list can hold
-    const uint8_t* syndromes = nullptr;
-    uint8_t* hard = nullptr;
-    uint8_t* converged = nullptr;
-    int32_t* iters = nullptr;
-    double* llr = nullptr;
-    int32_t* rounds = nullptr;
-    const unsigned long long* fail_count = nullptr;
-    const long long* fail_list = nullptr;
-    const uint8_t* fail_syn = nullptr;
-    const uint8_t* fail_err = nullptr;
-    int half_distance = 0;
-    long long* counters = nullptr;
-};
-
-static int gd_launch(qbp_handle* h, const GdCall& c, bool records, hipStream_t s)
+static int gd_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream_t s)
 {
     constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
-    constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
-    if (c.max_items > MAX_LAUNCH)
-        return fail(QBP_E_UNSUPPORTED, "BP guided decimation decodes at most 2^30 syndromes per call (got %lld)", c.max_items);
-    const size_t n = (size_t)h->n;
     const bool sp = h->gd_variant == QBP_SUM_PRODUCT;
     const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
-    const int threads = qbp::gd_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1]);
-    // resident workgroups per CU: the wavefronts a CU holds at the kernel's registers (min-sum 7 per SIMD, sum-product
-    // 5), and the LDS; QBP_OPT_BLOCKS_PER_CU overrides
-    const int waves = sp ? 20 : 28;
-    int per_cu = (int)std::max<size_t>(1, std::min<size_t>((size_t)(waves / (threads / 64)), ((size_t)160 * 1024) / lds));
-    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
-    const int grid = (int)std::max<long long>(1, std::min<long long>(c.max_items, (long long)h->num_cu * per_cu));
-    const size_t n_long = (size_t)(h->row_off[RC + 2] - h->row_off[RC + 1]);
-    HIP_TRY(h->d_wsL.reserve((size_t)grid * 3 * std::max<size_t>(n_long, 1)));
-    HIP_TRY(h->d_prior_sorted.reserve(n));
-    HIP_TRY(qbp::launch_permute_prior(c.prior, h->d_svar.p, h->d_prior_sorted.p, (int)n, s));
-    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::GD_MAX_THREADS);
     qbp::GdParams P{};
-    P.m = h->m; P.n = h->n; P.E = h->E;
-    P.srow = h->d_srow.p; P.srow_e0 = h->d_srow_e0.p; P.srow_deg = h->d_srow_deg.p; P.epos = h->d_epos.p;
-    P.long_edge_row = h->d_long_edge_row.p; P.svar = h->d_svar.p; P.vpos = h->d_vpos.p; P.vrow = h->d_vrow.p;
-    P.lcol_ptr = h->d_lcol_ptr.p;
-    std::copy(std::begin(h->row_off), std::end(h->row_off), P.row_off);
-    std::copy(std::begin(h->row_base), std::end(h->row_base), P.row_base);
-    std::copy(std::begin(h->rpad_off), std::end(h->rpad_off), P.rpad_off);
-    std::copy(std::begin(h->col_off), std::end(h->col_off), P.col_off);
-    std::copy(std::begin(h->gcol_base), std::end(h->gcol_base), P.col_base);
-    std::copy(std::begin(h->cpad_off), std::end(h->cpad_off), P.cpad_off);
-    P.prior_sorted = h->d_prior_sorted.p; P.wsL = h->d_wsL.p;
-    P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    int grid = 0;
+    // the wavefronts a CU holds at the kernel's registers: min-sum 7 per SIMD, sum-product 5; QBP_OPT_BLOCKS_PER_CU
+    // overrides
+    const int rc = record_launch_setup(h, c, records, {"BP guided decimation", lds, threads, sp ? 20 : 28, true}, s, P.tab, P.io,
+                                       &grid);
+    if (rc) return rc;
     P.iters_per_round = h->gd_iters; P.max_rounds = h->gd_max_rounds; P.decim_llr = h->gd_llr;
     P.alpha = h->gd_alpha; P.clip_llr = h->gd_clip;
-    P.syndromes = c.syndromes; P.B = records ? 0 : c.max_items;
-    P.hard = c.hard; P.converged = c.converged; P.iters = c.iters; P.llr = c.llr; P.rounds = c.rounds;
-    P.fail_count = c.fail_count; P.fail_list = c.fail_list; P.fail_syn = c.fail_syn; P.fail_err = c.fail_err;
-    P.lx_cols = h->d_lx_cols.p; P.half_distance = c.half_distance; P.counters = c.counters;
-    h->last_threads = threads; h->last_lds = (int)lds; h->last_grid = grid;
+    P.rounds = c.extra[0];
     HIP_TRY(qbp::launch_gd(records, h->gd_variant, P, grid, threads, lds, s));
     return QBP_OK;
 }
@@ -2285,9 +2286,9 @@ try {
     if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    GdCall c;
+    RecordCall c;
     c.prior = d_prior; c.max_items = B; c.syndromes = d_syndromes;
-    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr; c.rounds = d_rounds;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr; c.extra[0] = d_rounds;
     return gd_launch(h, c, false, static_cast<hipStream_t>(stream));
 }
 QBP_ABI_CATCH
@@ -2300,32 +2301,14 @@ try {
     if (!h->gd_ready) return fail(QBP_E_INVALID, "qbp_gd_decode_batch without qbp_gd_configure");
     if (B == 0) return QBP_OK;
     if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
-    for (int v = 0; v < h->n; ++v)
-        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
-    DeviceScope on_device(h->device);
-    HIP_TRY(on_device.err);
-    const size_t m = h->m, n = h->n, b = (size_t)B;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
-    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
-    if (converged) HIP_TRY(h->d_conv.reserve(b));
-    if (iters) HIP_TRY(h->d_iters.reserve(b));
-    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
-    if (rounds) HIP_TRY(h->d_gd_rounds.reserve(b));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    int rc = qbp_gd_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, hard ? h->d_hard.p : nullptr,
-                                        converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
-                                        llr ? h->d_llr.p : nullptr, rounds ? h->d_gd_rounds.p : nullptr, s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
-    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
-    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
-    if (rounds) HIP_TRY(hipMemcpyAsync(rounds, h->d_gd_rounds.p, b * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    int32_t* const extra[2] = {rounds, nullptr};
+    DevBuf<int32_t>* const d_extra[2] = {&h->d_gd_rounds, nullptr};
+    return record_decode_batch_host(h, syndromes, prior, B, hard, converged, iters, llr, extra, d_extra,
+                                    [&](uint8_t* d_hard, uint8_t* d_conv, int32_t* d_iters, double* d_llr, int32_t* d_rounds,
+                                        int32_t*, hipStream_t s) {
+                                        return qbp_gd_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, d_hard, d_conv,
+                                                                          d_iters, d_llr, d_rounds, s);
+                                    });
 }
 QBP_ABI_CATCH
 
@@ -2628,23 +2611,14 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
         if (rc == QBP_OK) h->last_kernel = 1;
     }
     if (rc || !osd) return rc;
-    if (relay) {
-        // second kernel: Relay-BP + classification of the trials the first stage left unconverged
-        RelayCall r;
+    if (relay || gd) {
+        // second kernel: Relay-BP or BP guided decimation + classification of the trials the first stage left unconverged
+        RecordCall r;
         r.prior = c.d_prior; r.max_items = T;
         r.fail_count = h->d_fail_count.p; r.fail_list = h->d_fail_list.p;
         r.fail_syn = h->d_fail_syn.p; r.fail_err = h->d_fail_err.p;
         r.half_distance = c.distance / 2; r.counters = reinterpret_cast<long long*>(c.d_counters);
-        return relay_launch(h, r, true, s);
-    }
-    if (gd) {
-        // second kernel: BP guided decimation + classification of the same records
-        GdCall g;
-        g.prior = c.d_prior; g.max_items = T;
-        g.fail_count = h->d_fail_count.p; g.fail_list = h->d_fail_list.p;
-        g.fail_syn = h->d_fail_syn.p; g.fail_err = h->d_fail_err.p;
-        g.half_distance = c.distance / 2; g.counters = reinterpret_cast<long long*>(c.d_counters);
-        return gd_launch(h, g, true, s);
+        return relay ? relay_launch(h, r, true, s) : gd_launch(h, r, true, s);
     }
     if (lsd) {
         // second kernel: localized statistics decoding + classification of the same records

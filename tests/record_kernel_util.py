@@ -1,8 +1,9 @@
 """Helpers of tests/test_gpu_record_kernel_sizes.py: the launch arithmetic of the three per-record decoders restated in
-Python (gd_threads / gd_lds_bytes of qbp_gd.hpp, relay_threads / relay_lds_bytes of qbp_relay.hpp, layered_lds_bytes of
-qbp_layered.hpp, the grids of gd_launch / relay_launch / layered_launch and layered_slots of qbp.hip -- usable without
-a GPU), the matrices large enough that a workgroup walks its strided loops more than once, and launches of the device
-entries into poisoned buffers (geometry_util.Outputs plus the decoders' extra int32 outputs).
+Python (record_threads of qbp_record_bp.hpp, gd_lds_bytes of qbp_gd.hpp, relay_lds_bytes of qbp_relay.hpp,
+layered_lds_bytes of qbp_layered.hpp, the grids of gd_launch / relay_launch / layered_launch and layered_slots of
+qbp.hip -- usable without a GPU), the matrices large enough that a workgroup walks its strided loops more than once,
+and launches of the device entries into poisoned buffers (geometry_util.Outputs plus the decoders' extra int32
+outputs).
 
 Work items: the general-H tables pad every weight class to whole wavefronts, so the check step has
 sum_{k=1..8} pad64(#rows of weight k) items and the variable step sum_{k=1..4} pad64(#columns of weight k); rows beyond

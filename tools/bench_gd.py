@@ -12,6 +12,10 @@ four pipelines timed alternately inside each repetition:
 and per pipeline the LER, the fraction of trials left unsolved and trials/s from the counters of the timed runs (same
 trials: one seed).  Then the batch kernel alone: qbp_gd_decode_batch_device on 65 536 BP failures of [[144,12,12]] at
 p = 0.05 against qbp_osd_batch_device (OSD-0) on the same records.  Nobody set a threshold: figures are reported.
+With --baseline-lib the BPGD pipeline and the batch kernel (min-sum and sum-product) of that library run too (gd_parent,
+gd_batch_parent, gd_sp_batch_parent), alternately with this build's, and "vs_parent" has per item the parent's
+run-to-run spread (max - min) / min, the ratio of the best times (this build / parent) and whether the ratio stays
+within 1 + spread.
 
     make -C qldpc_amd/csrc OBJ=/tmp/obj_parent OUT=/tmp/libqbp_parent.so      (in a checkout of the parent commit)
     python tools/bench_gd.py --baseline-lib /tmp/libqbp_parent.so --out profiles/r14_gd.json
@@ -40,7 +44,8 @@ class BaselineDecoder:
 
     def __init__(self, path, H, device=0):
         self.lib = C.CDLL(path)
-        for name in ("qbp_create", "qbp_destroy", "qbp_mc_run_device", "qbp_relay_configure", "qbp_last_error"):
+        for name in ("qbp_create", "qbp_destroy", "qbp_mc_run_device", "qbp_relay_configure", "qbp_gd_configure",
+                     "qbp_gd_decode_batch_device", "qbp_last_error"):
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = _lib.SIGNATURES[name]
         self.row_ptr, self.col_idx, self.m, self.n = bp.csr_from_H(H)
@@ -63,8 +68,28 @@ class BaselineDecoder:
         if rc:
             raise RuntimeError(f"baseline qbp_relay_configure: {rc} {self.lib.qbp_last_error().decode()}")
 
+    def gd_configure(self, cfg):
+        rc = self.lib.qbp_gd_configure(self.h, cfg.iters_per_round, cfg.max_rounds, cfg.decim_llr, cfg.variant, cfg.alpha,
+                                       cfg.clip_llr)
+        if rc:
+            raise RuntimeError(f"baseline qbp_gd_configure: {rc} {self.lib.qbp_last_error().decode()}")
+
+    def gd_decode_device(self, d_syn, d_prior, B, d_hard, d_conv, d_iters, d_llr, d_rounds, stream=0):
+        rc = self.lib.qbp_gd_decode_batch_device(self.h, d_syn, d_prior, int(B), d_hard or None, d_conv or None,
+                                                 d_iters or None, d_llr or None, d_rounds or None, stream or None)
+        if rc:
+            raise RuntimeError(f"baseline qbp_gd_decode_batch_device: {rc} {self.lib.qbp_last_error().decode()}")
+
     def close(self):
         self.lib.qbp_destroy(self.h)
+
+
+def vs_parent(new, parent):
+    """The parent's spread over its repetitions, the ratio of the best times, and the verdict of the two."""
+    spread = (max(parent) - min(parent)) / min(parent)
+    ratio = min(new) / min(parent)
+    return {"new_seconds": new, "parent_seconds": parent, "parent_spread": spread, "ratio_best": ratio,
+            "within_spread": ratio <= 1.0 + spread}
 
 
 def timed_mc(torch, dec, code, p, trials, flags):
@@ -106,17 +131,23 @@ def main():
                                                STOP, ALPHA))
         runs = {"gd": (dec, _lib.FLAG_GD), "osd0": (base, _lib.FLAG_OSD0), "cs7": (base, _lib.osd_flags("cs", 7)),
                 "relay": (base, _lib.FLAG_RELAY)}
+        if base is not dec:
+            base.gd_configure(gd.GDConfig(GD_T, code.n, GD_LLR, gd.MIN_SUM, ALPHA))
+            runs["gd_parent"] = (base, _lib.FLAG_GD)
         for p in (0.03, 0.05):
             for d, fl in runs.values():                                   # warm-up
                 timed_mc(torch, d, code, p, min(args.trials, 65536), fl)
-            best, cnt = {}, {}
+            best, cnt, raw = {}, {}, {key: [] for key in runs}
             for _ in range(args.reps):
                 for key, (d, fl) in runs.items():
                     t, c = timed_mc(torch, d, code, p, args.trials, fl)
+                    raw[key].append(t)
                     if key not in best or t < best[key]:
                         best[key] = t
                     cnt[key] = c
             row = {"code": name, "p": p}
+            if "gd_parent" in runs:
+                row["vs_parent"] = vs_parent(raw["gd"], raw["gd_parent"])
             for key in runs:
                 row[key] = {"seconds": best[key], "trials_per_s": args.trials / best[key], "ler": cnt[key][1] / cnt[key][0],
                             "not_converged": int(cnt[key][6]), "unsolved_fraction": int(cnt[key][10]) / int(cnt[key][0])}
@@ -147,21 +178,41 @@ def main():
     stream = torch.cuda.current_stream(dev).cuda_stream
     dec.gd_configure(gd.GDConfig(GD_T, code.n, GD_LLR, gd.MIN_SUM, ALPHA))
     times = {"gd_batch": [], "osd0_batch": []}
+    batch = {"gd_batch": dec}
+    solved = 0
+    if args.baseline_lib:
+        # (a handle has one configuration: the sum-product kernel runs on handles of its own)
+        sp = gd.GDConfig(GD_T, code.n, GD_LLR, gd.SUM_PRODUCT, 1.0)
+        batch["gd_sp_batch"] = _lib.Decoder(*bp.csr_from_H(code.Hx))
+        batch["gd_batch_parent"] = BaselineDecoder(args.baseline_lib, code.Hx)
+        batch["gd_sp_batch_parent"] = BaselineDecoder(args.baseline_lib, code.Hx)
+        batch["gd_sp_batch"].gd_configure(sp)
+        batch["gd_batch_parent"].gd_configure(gd.GDConfig(GD_T, code.n, GD_LLR, gd.MIN_SUM, ALPHA))
+        batch["gd_sp_batch_parent"].gd_configure(sp)
+        times.update({key: [] for key in batch})
     for rep in range(args.reps + 1):
         for key in times:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            if key == "gd_batch":
-                dec.gd_decode_device(d_syn.data_ptr(), d_prior.data_ptr(), len(syn), d_out.data_ptr(), d_conv.data_ptr(),
-                                     0, 0, 0, stream=stream)
+            if key in batch:
+                batch[key].gd_decode_device(d_syn.data_ptr(), d_prior.data_ptr(), len(syn), d_out.data_ptr(),
+                                            d_conv.data_ptr(), 0, 0, 0, stream=stream)
+                if key == "gd_batch":
+                    solved = int(d_conv.sum().item())
             else:
                 dec.osd0_device(d_syn.data_ptr(), d_llr.data_ptr(), d_hard.data_ptr(), len(syn), d_out.data_ptr(),
                                 stream=stream)
             torch.cuda.synchronize(dev)
             if rep:
                 times[key].append(time.perf_counter() - t0)
-    result["batch"] = {"code": "[[144, 12, 12]]", "p": p, "records": len(syn), "solved_by_gd": int(d_conv.sum().item()),
+    result["batch"] = {"code": "[[144, 12, 12]]", "p": p, "records": len(syn), "solved_by_gd": solved,
                        **{k: {"seconds": min(v), "records_per_s": len(syn) / min(v)} for k, v in times.items()}}
+    if args.baseline_lib:
+        result["batch"]["vs_parent"] = {"gd_batch": vs_parent(times["gd_batch"], times["gd_batch_parent"]),
+                                        "gd_sp_batch": vs_parent(times["gd_sp_batch"], times["gd_sp_batch_parent"])}
+        batch["gd_batch_parent"].close()
+        batch["gd_sp_batch_parent"].close()
+        batch["gd_sp_batch"].close()
     print(json.dumps(result["batch"]))
     if args.out:
         with open(args.out, "w") as f:

@@ -10,6 +10,9 @@ three pipelines timed alternately inside each repetition:
 and their LERs from the counters of the timed runs (same trials: one seed).  Then the batch kernel alone:
 qbp_relay_decode_batch_device on 65 536 BP failures of [[144,12,12]] at p = 0.05 against qbp_osd_batch_device (OSD-0)
 on the same records.  Nobody set a threshold: times and LERs are reported.
+With --baseline-lib the Relay pipeline and the batch kernel of that library run too (relay_parent, relay_batch_parent),
+alternately with this build's, and "vs_parent" has per item the parent's run-to-run spread (max - min) / min, the ratio
+of the best times (this build / parent) and whether the ratio stays within 1 + spread.
 
     make -C qldpc_amd/csrc OBJ=/tmp/obj_parent OUT=/tmp/libqbp_parent.so      (in a checkout of the parent commit)
     python tools/bench_relay.py --baseline-lib /tmp/libqbp_parent.so --out profiles/r12_relay.json
@@ -37,7 +40,8 @@ class BaselineDecoder:
 
     def __init__(self, path, H, device=0):
         self.lib = C.CDLL(path)
-        for name in ("qbp_create", "qbp_destroy", "qbp_mc_run_device", "qbp_last_error"):
+        for name in ("qbp_create", "qbp_destroy", "qbp_mc_run_device", "qbp_relay_configure",
+                     "qbp_relay_decode_batch_device", "qbp_last_error"):
             fn = getattr(self.lib, name)
             fn.restype, fn.argtypes = _lib.SIGNATURES[name]
         self.row_ptr, self.col_idx, self.m, self.n = bp.csr_from_H(H)
@@ -54,8 +58,29 @@ class BaselineDecoder:
         if rc:
             raise RuntimeError(f"baseline qbp_mc_run_device: {rc} {self.lib.qbp_last_error().decode()}")
 
+    def relay_configure(self, cfg):
+        rc = self.lib.qbp_relay_configure(self.h, cfg.gammas.ctypes.data, cfg.gammas.shape[0], cfg.leg_iters.ctypes.data,
+                                          cfg.stop_after, cfg.alpha, cfg.clip_llr)
+        if rc:
+            raise RuntimeError(f"baseline qbp_relay_configure: {rc} {self.lib.qbp_last_error().decode()}")
+
+    def relay_decode_device(self, d_syn, d_prior, B, d_hard, d_conv, d_iters, d_llr, d_legs, d_sol, stream=0):
+        rc = self.lib.qbp_relay_decode_batch_device(self.h, d_syn, d_prior, int(B), d_hard or None, d_conv or None,
+                                                    d_iters or None, d_llr or None, d_legs or None, d_sol or None,
+                                                    stream or None)
+        if rc:
+            raise RuntimeError(f"baseline qbp_relay_decode_batch_device: {rc} {self.lib.qbp_last_error().decode()}")
+
     def close(self):
         self.lib.qbp_destroy(self.h)
+
+
+def vs_parent(new, parent):
+    """The parent's spread over its repetitions, the ratio of the best times, and the verdict of the two."""
+    spread = (max(parent) - min(parent)) / min(parent)
+    ratio = min(new) / min(parent)
+    return {"new_seconds": new, "parent_seconds": parent, "parent_spread": spread, "ratio_best": ratio,
+            "within_spread": ratio <= 1.0 + spread}
 
 
 def timed_mc(torch, dec, code, p, trials, flags):
@@ -89,21 +114,27 @@ def main():
     for name in ("[[144, 12, 12]]", "[[288, 12, 18]]"):
         code = codes.load_code(name)
         dec = bp.decoder_for(code.Hx)
-        dec.relay_configure(relay.RelayConfig(relay.relay_gammas(code.n, LEGS, GAMMA0, INTERVAL, SEED), [ITERS] * LEGS,
-                                              STOP, ALPHA))
+        cfg = relay.RelayConfig(relay.relay_gammas(code.n, LEGS, GAMMA0, INTERVAL, SEED), [ITERS] * LEGS, STOP, ALPHA)
+        dec.relay_configure(cfg)
         base = BaselineDecoder(args.baseline_lib, code.Hx) if args.baseline_lib else dec
         runs = {"relay": (dec, _lib.FLAG_RELAY), "osd0": (base, _lib.FLAG_OSD0), "cs7": (base, _lib.osd_flags("cs", 7))}
+        if base is not dec:
+            base.relay_configure(cfg)
+            runs["relay_parent"] = (base, _lib.FLAG_RELAY)
         for p in (0.03, 0.05):
             for d, fl in runs.values():                                   # warm-up
                 timed_mc(torch, d, code, p, min(args.trials, 65536), fl)
-            best, cnt = {}, {}
+            best, cnt, raw = {}, {}, {key: [] for key in runs}
             for _ in range(args.reps):
                 for key, (d, fl) in runs.items():
                     t, c = timed_mc(torch, d, code, p, args.trials, fl)
+                    raw[key].append(t)
                     if key not in best or t < best[key]:
                         best[key] = t
                     cnt[key] = c
             row = {"code": name, "p": p}
+            if "relay_parent" in runs:
+                row["vs_parent"] = vs_parent(raw["relay"], raw["relay_parent"])
             for key in runs:
                 row[key] = {"seconds": best[key], "trials_per_s": args.trials / best[key], "ler": cnt[key][1] / cnt[key][0],
                             "not_converged": int(cnt[key][6]), "without_solution": int(cnt[key][10])}
@@ -133,13 +164,18 @@ def main():
     d_conv = torch.zeros(len(syn), dtype=torch.uint8, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     times = {"relay_batch": [], "osd0_batch": []}
+    batch = {"relay_batch": dec}
+    if args.baseline_lib:
+        batch["relay_batch_parent"] = BaselineDecoder(args.baseline_lib, code.Hx)
+        batch["relay_batch_parent"].relay_configure(cfg)
+        times["relay_batch_parent"] = []
     for rep in range(args.reps + 1):
         for key in times:
             torch.cuda.synchronize(dev)
             t0 = time.perf_counter()
-            if key == "relay_batch":
-                dec.relay_decode_device(d_syn.data_ptr(), d_prior.data_ptr(), len(syn), d_out.data_ptr(), d_conv.data_ptr(),
-                                        0, 0, 0, 0, stream=stream)
+            if key in batch:
+                batch[key].relay_decode_device(d_syn.data_ptr(), d_prior.data_ptr(), len(syn), d_out.data_ptr(),
+                                               d_conv.data_ptr(), 0, 0, 0, 0, stream=stream)
             else:
                 dec.osd0_device(d_syn.data_ptr(), d_llr.data_ptr(), d_hard.data_ptr(), len(syn), d_out.data_ptr(),
                                 stream=stream)
@@ -148,6 +184,9 @@ def main():
                 times[key].append(time.perf_counter() - t0)
     result["batch"] = {"code": "[[144, 12, 12]]", "p": p, "records": len(syn), "solved_by_relay": int(d_conv.sum().item()),
                        **{k: {"seconds": min(v), "records_per_s": len(syn) / min(v)} for k, v in times.items()}}
+    if args.baseline_lib:
+        result["batch"]["vs_parent"] = vs_parent(times["relay_batch"], times["relay_batch_parent"])
+        batch["relay_batch_parent"].close()
     print(json.dumps(result["batch"]))
     if args.out:
         with open(args.out, "w") as f:
