@@ -61,7 +61,9 @@ def clusters_of(H, seeds, active):
 
 def lsd_decode(H, syndrome, llr, hard, bits_per_step=1):
     """One record -> dict(solution uint8[n], stats int32[4] = {rounds, active variables, clusters, valid},
-    e uint8[n], active bool[n], merged bool, skipped int (columns without a pivot), max_clusters int)."""
+    e uint8[n], active bool[n], merged bool, skipped int (columns without a pivot), max_clusters int,
+    pivot_rows int64[*] (the rows that serve as a pivot, ascending), cluster_lows int64[clusters] (the lowest check of
+    every cluster at the end))."""
     H = np.asarray(H, np.uint8) & 1
     m, n = H.shape
     g = int(bits_per_step)
@@ -115,17 +117,21 @@ def lsd_decode(H, syndrome, llr, hard, bits_per_step=1):
     valid = not any(invalid(c) for c in cl)
     stats = np.array([rounds, int(active.sum()), len(cl), int(valid)], np.int32)
     return dict(solution=hard ^ e, stats=stats, e=e, active=active, merged=merged, skipped=skipped,
-                max_clusters=max_clusters)
+                max_clusters=max_clusters, pivot_rows=np.flatnonzero(is_pivot),
+                cluster_lows=np.array([c[0][0] for c in cl], np.int64))
 
 
 def lsd_decode_batch(H, syndromes, llr, hard, bits_per_step=1):
-    """B records -> dict(solution uint8[B, n], stats int32[B, 4], e, active, merged bool[B], skipped int[B])."""
+    """B records -> dict(solution uint8[B, n], stats int32[B, 4], e, active, merged bool[B], skipped int[B], and the
+    lists pivot_rows and cluster_lows of one array per record)."""
     recs = [lsd_decode(H, syndromes[b], llr[b], hard[b], bits_per_step) for b in range(len(syndromes))]
     n = np.asarray(H).shape[1]
     out = {}
     for k, dt, shape in (("solution", np.uint8, (0, n)), ("stats", np.int32, (0, 4)), ("e", np.uint8, (0, n)),
                          ("active", bool, (0, n)), ("merged", bool, (0,)), ("skipped", np.int64, (0,))):
         out[k] = np.array([x[k] for x in recs], dt) if recs else np.zeros(shape, dt)
+    for k in ("pivot_rows", "cluster_lows"):
+        out[k] = [x[k] for x in recs]
     return out
 
 

@@ -1,5 +1,6 @@
-"""Inputs shared by tests/test_lsd_cpu.py and tests/test_gpu_lsd.py: the matrices, and BP outputs to post-process
-(computed by the CPU oracle, so the inputs are the same with and without a device)."""
+"""Inputs shared by tests/test_lsd_cpu.py, tests/test_gpu_lsd.py and tests/test_gpu_lsd_sizes.py: the matrices, BP
+outputs to post-process (computed by the CPU oracle, so the inputs are the same with and without a device), and the
+launch arithmetic of lsd_kernel restated in Python (lsd_lds_bytes of qbp_lsd.hpp, the grid of lsd_launch in qbp.hip)."""
 import numpy as np
 
 from oracle import oracle
@@ -35,6 +36,63 @@ def matrix(name):
         H = np.asarray(codes.load_code(NAMES["72"]).Hx, np.uint8)
         return np.concatenate([H, np.zeros((H.shape[0], 2), np.uint8)], axis=1)
     return np.asarray(codes.load_code(NAMES[name]).Hx, np.uint8)
+
+
+def rows2048(extra_row=False):
+    """2048 x 384 (one row more: 2049 x 384), every row of weight 3, no empty column: as many rows as the kernel's 32-bit
+    per-lane row masks hold.  Rows 0 .. 63 live on columns 0 .. 31 and rows 1984 .. 2047 on columns 352 .. 383, which no
+    other row touches: a column of the upper block finds its pivot in the last 64-row pass (bit 31 of the masks), and
+    the two blocks are clusters of their own.  The rows between, and the extra row, are random on columns 32 .. 351."""
+    rng = np.random.default_rng(2048)
+    m = 2049 if extra_row else 2048
+    H = np.zeros((m, 384), np.uint8)
+    for r in range(2048):
+        lo, width = (0, 32) if r < 64 else (352, 32) if r >= 1984 else (32, 320)
+        H[r, lo + rng.choice(width, 3, replace=False)] = 1
+    if extra_row:
+        H[2048, 32 + rng.choice(320, 3, replace=False)] = 1
+    assert H.sum(1).tolist() == [3] * m and H.sum(0).min() > 0
+    return H
+
+
+def sort_edge(n):
+    """An irregular 100 x n matrix in the style of irregular37 (row weights 2 .. 21, no empty column): n = 256 is a
+    power of two (the bitonic sort runs without a padding key), n = 257 pads to 512 (255 padding keys)."""
+    rng = np.random.default_rng(n)
+    H = (rng.random((100, n)) < rng.uniform(0.01, 0.05, size=(100, 1))).astype(np.uint8)
+    H[np.arange(100), rng.integers(0, n, 100)] = 1
+    H[rng.integers(0, 100, n), np.arange(n)] = 1
+    return H
+
+
+# ---- the launch arithmetic of lsd_kernel (no GPU) ------------------------------------------------------------------------
+LDS_LIMIT = 160 * 1024
+MAX_ROWS, MAX_COLS = 64 * 32, 65535
+
+
+def lsd_lds_bytes(m, n):
+    """lsd_lds_bytes of qbp_lsd.hpp: osd_region0_bytes { u64 keys[NP] | u32 A[m][W + 1] }, then int pivcol / label and
+    u32 pick / prev [m], u16 idx[NP] and rank[n], u8 sol / act [n], u8 bad[m], and 16 spare bytes."""
+    W = -(-n // 32)
+    NP = 1
+    while NP < n:
+        NP <<= 1
+    region0 = -(-max(8 * NP, 4 * m * (W + 1)) // 8) * 8
+    return region0 + 16 * m + 2 * NP + 4 * n + m + 16
+
+
+def lsd_lds16(m, n):
+    """What the launch asks for: the size rounded up to 16."""
+    return -(-lsd_lds_bytes(m, n) // 16) * 16
+
+
+def lsd_grid(m, n, B, num_cu, blocks_per_cu=0):
+    """The grid of lsd_launch: one wavefront per workgroup, as many per CU as the LDS holds, at most 32;
+    QBP_OPT_BLOCKS_PER_CU overrides the count."""
+    per_cu = max(1, min(32, LDS_LIMIT // lsd_lds16(m, n)))
+    if blocks_per_cu > 0:
+        per_cu = blocks_per_cu
+    return max(1, min(B, num_cu * per_cu))
 
 
 def diag(H1, H2):
