@@ -192,6 +192,9 @@ int qbp_check_messages(qbp_handle* h, const uint8_t* syndromes, const double* pr
  * with np.histogram's rules (:46-47).  Outputs: edges [bins + 1] (= np.linspace(min, max, bins + 1)),
  * hist0 / hist1 [bins] raw counts.  The density normalisation and the one-parameter fit (:49-62)
  * are a few flops on 2 * bins numbers and stay with the caller (qldpc_amd/alvarado.py).
+ * QBP_E_INVALID, with edges, hist0 and hist1 untouched: a null pointer, B = 0, a matrix without edges, bins outside
+ * 1 .. 4096, or a message range that is not finite -- ANY message NaN or infinite (a NaN prior entry; min-sum on a
+ * check of weight 1): np.histogram raises on that range, no histogram of the remaining messages is returned.
  */
 int qbp_message_histograms(qbp_handle* h, const uint8_t* syndromes, const uint8_t* errors,
                            const double* prior, int64_t B, int32_t variant, double alpha,

@@ -1391,7 +1391,10 @@ try {
     HIP_TRY(hipMemcpyAsync(part.data(), h->d_part.p, part.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     double lo = __builtin_inf(), hi = -__builtin_inf();
-    for (int i = 0; i < grid; ++i) { lo = std::min(lo, part[2 * i]); hi = std::max(hi, part[2 * i + 1]); }
+    for (int i = 0; i < grid; ++i) {                 // (a NaN part stays: std::min / std::max would drop it)
+        lo = (std::isnan(part[2 * i]) || part[2 * i] < lo) ? part[2 * i] : lo;
+        hi = (std::isnan(part[2 * i + 1]) || part[2 * i + 1] > hi) ? part[2 * i + 1] : hi;
+    }
     if (!(lo <= hi) || std::isinf(lo) || std::isinf(hi))
         return fail(QBP_E_INVALID, "message range [%g, %g] is not finite (np.histogram raises there too)", lo, hi);
     if (lo == hi) { lo -= 0.5; hi += 0.5; }          // np.histogram's rule for a degenerate range

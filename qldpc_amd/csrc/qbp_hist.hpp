@@ -16,22 +16,27 @@
 namespace qbp {
 
 #ifdef QBP_DEFINE_KERNELS   /* non-template kernels: defined in their translation unit only */
-// per-block minimum / maximum of x[0 .. count)
+// min / max that keep a NaN, as np.min / np.max do (a plain comparison drops it)
+__device__ inline double hist_min(double a, double b) { return (a != a || a < b) ? a : b; }
+__device__ inline double hist_max(double a, double b) { return (a != a || a > b) ? a : b; }
+
+// per-block minimum / maximum of x[0 .. count); NaN if any value is NaN (the caller refuses that range,
+// where np.histogram raises)
 __global__ __launch_bounds__(256) void hist_minmax_kernel(const double* x, long long count, double* part /*[2 * grid]*/)
 {
     __shared__ double smin[256], smax[256];
     double lo = __builtin_inf(), hi = -__builtin_inf();
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
         const double v = x[i];
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
+        lo = hist_min(v, lo);
+        hi = hist_max(v, hi);
     }
     smin[threadIdx.x] = lo; smax[threadIdx.x] = hi;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) {
-            smin[threadIdx.x] = smin[threadIdx.x + s] < smin[threadIdx.x] ? smin[threadIdx.x + s] : smin[threadIdx.x];
-            smax[threadIdx.x] = smax[threadIdx.x + s] > smax[threadIdx.x] ? smax[threadIdx.x + s] : smax[threadIdx.x];
+            smin[threadIdx.x] = hist_min(smin[threadIdx.x + s], smin[threadIdx.x]);
+            smax[threadIdx.x] = hist_max(smax[threadIdx.x + s], smax[threadIdx.x]);
         }
         __syncthreads();
     }
