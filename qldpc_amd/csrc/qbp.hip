@@ -105,6 +105,157 @@ struct DevBuf {
     }
 };
 
+// The host-array side of one call on `s`: every host entry point stages through one of these.
+//   in     a host array uploaded into a DevBuf; the device pointer
+//   out    null for a null host array; else the DevBuf reserved and its download recorded; the device pointer
+//   zeroed a DevBuf of accumulators reserved and set to zero; add: the sum into a host array recorded (null: none)
+//   finish rc != 0 (the device entry refused, g_err is its message): synchronise and return rc; else enqueue what
+//          out and add recorded, synchronise, add up and return QBP_OK -- or the first HIP error of any step
+// Whatever way a call leaves -- finish, an early return, an exception -- the destructor has synchronised the stream
+// if finish has not: copies of a refused call may still be in flight, and the next call on the handle, which reserves
+// the same DevBufs again, must not find them so.  After a HIP error in / out / zeroed return null and enqueue nothing:
+// the caller returns error() instead of making the device call.
+class HostStage {
+    struct Copy { void* host; const void* dev; size_t bytes; };
+    struct Sum { int64_t* host; const long long* dev; size_t count; };
+    hipStream_t s;
+    hipError_t err = hipSuccess;
+    const char* what = "";
+    int line = 0;
+    bool finished = false;
+    std::vector<Copy> downloads;
+    std::vector<Sum> sums;
+    bool step(hipError_t e, const char* expr, int at)
+    {
+        if (err == hipSuccess && e != hipSuccess) { err = e; what = expr; line = at; }
+        return err == hipSuccess;
+    }
+// (the message of HIP_TRY: the expression, the HIP error, where)
+#define QBP_STAGE_STEP(expr) step((expr), #expr, __LINE__)
+
+public:
+    explicit HostStage(hipStream_t stream) : s(stream) {}
+    HostStage(const HostStage&) = delete;
+    HostStage& operator=(const HostStage&) = delete;
+    ~HostStage() { if (!finished) (void)hipStreamSynchronize(s); }
+    bool failed() const { return err != hipSuccess; }
+
+    template <typename T>
+    T* in(DevBuf<T>& buf, const T* host, size_t count)
+    {
+        if (failed() || !QBP_STAGE_STEP(buf.reserve(count))) return nullptr;
+        QBP_STAGE_STEP(hipMemcpyAsync(buf.p, host, count * sizeof(T), hipMemcpyHostToDevice, s));
+        return failed() ? nullptr : buf.p;
+    }
+    template <typename T>
+    T* out(DevBuf<T>& buf, T* host, size_t count)
+    {
+        if (!host || failed() || !QBP_STAGE_STEP(buf.reserve(count))) return nullptr;
+        downloads.push_back({host, buf.p, count * sizeof(T)});
+        return buf.p;
+    }
+    long long* zeroed(DevBuf<long long>& buf, size_t count)
+    {
+        if (failed() || !QBP_STAGE_STEP(buf.reserve(count))) return nullptr;
+        QBP_STAGE_STEP(hipMemsetAsync(buf.p, 0, count * sizeof(long long), s));
+        return failed() ? nullptr : buf.p;
+    }
+    void add(int64_t* host, const long long* dev, size_t count)
+    {
+        if (host && !failed()) sums.push_back({host, dev, count});
+    }
+    int error() const
+    {
+        return fail(QBP_E_HIP, "%s failed: %s (%s:%d)", what, hipGetErrorString(err), __FILE__, line);
+    }
+    int finish(int rc)
+    {
+        if (rc || failed()) return rc ? rc : error();      // (the destructor synchronises)
+        size_t cells = 0;
+        for (const Sum& a : sums) cells += a.count;
+        std::vector<long long> tmp(cells);
+        for (const Copy& c : downloads)
+            if (c.bytes) QBP_STAGE_STEP(hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, s));
+        long long* t = tmp.data();
+        for (const Sum& a : sums) {
+            QBP_STAGE_STEP(hipMemcpyAsync(t, a.dev, a.count * sizeof(long long), hipMemcpyDeviceToHost, s));
+            t += a.count;
+        }
+        finished = true;
+        if (!QBP_STAGE_STEP(hipStreamSynchronize(s))) return error();
+        t = tmp.data();
+        for (const Sum& a : sums)
+            for (size_t i = 0; i < a.count; ++i) a.host[i] += *t++;
+        return QBP_OK;
+    }
+#undef QBP_STAGE_STEP
+};
+
+// "prior has no NaN" (+-inf are legal: a column known to be 0 or 1), or "prior is finite" where the decoder needs it
+// (host only, before any GPU work).  Two loops, each the one the entries had inline: the NaN one runs in every
+// one-syndrome qbp_decode_batch call.
+inline int check_prior(int n, const double* prior, bool must_be_finite)
+{
+    if (must_be_finite) {
+        for (int v = 0; v < n; ++v)
+            if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
+        return QBP_OK;
+    }
+    for (int v = 0; v < n; ++v)
+        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    return QBP_OK;
+}
+
+unsigned mc_threshold(double p)
+{
+    double t = std::floor(p * 4294967296.0);
+    if (!(t > 0.0)) t = 0.0;
+    if (t > 4294967295.0) t = 4294967295.0;
+    return (unsigned)t;
+}
+
+// The input tables of a Monte-Carlo call on the device, with host copies of what was uploaded last: a call uploads
+// only what changed.  The copy goes on the call's stream, behind any earlier launch there that still reads the table,
+// and is waited for because its source is a local.  A failed upload leaves the cache empty.
+struct McInputs {
+    DevBuf<unsigned long long> d_lx_cols;    // per column, bit l: Lx[l] has it
+    std::vector<uint8_t> lx_cache;
+    int lx_cache_k = -1;
+    DevBuf<uint32_t> d_thr;                  // a sampler threshold per column, [n rounded up to 4] (zero in the padding)
+    std::vector<uint32_t> thr_cache;
+
+    int prepare_lx(size_t n, const uint8_t* Lx, int32_t k, hipStream_t s)
+    {
+        if (lx_cache_k == k && lx_cache.size() == (size_t)k * n &&
+            (k == 0 || std::memcmp(lx_cache.data(), Lx, (size_t)k * n) == 0))
+            return QBP_OK;
+        std::vector<unsigned long long> cols(n, 0ull);
+        for (int l = 0; l < k; ++l)
+            for (size_t v = 0; v < n; ++v)
+                if (Lx[(size_t)l * n + v] & 1) cols[v] |= 1ull << l;
+        lx_cache_k = -1;
+        HIP_TRY(d_lx_cols.reserve(n));
+        HIP_TRY(hipMemcpyAsync(d_lx_cols.p, cols.data(), n * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        lx_cache.assign(Lx, Lx + (size_t)k * n);
+        lx_cache_k = k;
+        return QBP_OK;
+    }
+    int prepare_thr(size_t n, const double* probs, hipStream_t s)
+    {
+        const size_t n4 = (n + 3) / 4 * 4;
+        std::vector<uint32_t> thr(n4, 0u);
+        for (size_t v = 0; v < n; ++v) thr[v] = mc_threshold(probs[v]);
+        if (thr_cache == thr) return QBP_OK;
+        thr_cache.clear();
+        HIP_TRY(d_thr.reserve(n4));
+        HIP_TRY(hipMemcpyAsync(d_thr.p, thr.data(), n4 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        thr_cache.swap(thr);
+        return QBP_OK;
+    }
+};
+
 }  // namespace
 
 struct qbp_handle {
@@ -133,13 +284,9 @@ struct qbp_handle {
     DevBuf<int32_t> d_iters;
     DevBuf<double> d_llr, d_prior, d_mathx, d_mathy, d_part, d_edges;
     DevBuf<unsigned long long> d_hist;
-    DevBuf<unsigned long long> d_lx_cols;
+    McInputs mc_in;                  // the Lx columns, and the sampler thresholds of qbp_mc_run_probs
     DevBuf<long long> d_counters;
     DevBuf<long long> d_spectrum;    // qbp_mc_run_spectrum: [QBP_SPECTRUM_ROWS][n + 1], then iter_hist [max_iter + 1]
-    std::vector<uint8_t> lx_cache;   // last uploaded Lx (host copy) to skip re-uploads
-    int lx_cache_k = -1;
-    DevBuf<uint32_t> d_mc_thr;       // qbp_mc_run_probs: a sampler threshold per column, [n rounded up to 4]
-    std::vector<uint32_t> thr_cache; // last uploaded thresholds (host copy) to skip re-uploads
     // general-H kernel
     DevBuf<int32_t> d_col_ptr, d_col_edge;
     DevBuf<double> d_wsQ, d_wsR, d_wsV;
@@ -1113,7 +1260,6 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 
 // (layered BP, defined with its configuration further down)
 static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry);
-static int check_finite_prior(const qbp_handle* h, const double* prior);
 static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s);
 
 int qbp_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior,
@@ -1154,6 +1300,75 @@ try {
 }
 QBP_ABI_CATCH
 
+// The outputs of a large qbp_decode_batch call, b records in the handle's scratch: device -> pinned staging (DMA at
+// PCIe rate) -> the caller's arrays (memcpy), in chunks of up to 32 MiB, the host copy of one chunk overlapping the
+// DMA of the next.  (A direct copy into pageable memory goes through the runtime's own small staging buffers at a
+// fraction of that rate.)  The two staging buffers are as large as the largest chunk any call of this handle has
+// needed, never more than 32 MiB each (they used to be 32 MiB from the first 256 KiB call on).  The one
+// download that is not "enqueue all, synchronise once": it does not go through HostStage, whose finish ends the call.
+static int decode_copy_out(qbp_handle* h, size_t b, uint8_t* hard, uint8_t* converged, int32_t* iters, double* llr,
+                           hipStream_t s)
+{
+    const size_t n = h->n;
+    const size_t per = (hard ? n : 0) + (converged ? 1 : 0) + (iters ? 4 : 0) + (llr ? 8 * n : 0);
+    constexpr size_t STAGE = (size_t)32 << 20;
+    if (per == 0) return QBP_OK;
+    // (pieces of at least 1 MiB, at least four of them above 4 MiB: the reference driver's 13 MB per
+    // batch then overlap their DMA with the copy-out instead of running one after the other)
+    const size_t quarter = std::max<size_t>((b + 3) / 4, ((size_t)1 << 20) / per + 1);
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>({b, STAGE / (per + 8), quarter}));
+    const size_t need = std::min<size_t>(STAGE, chunk * (per + 8) + 64);
+    if (h->stage_bytes < need) {
+        for (int i = 0; i < 2; ++i) {
+            if (h->stage[i]) (void)hipHostFree(h->stage[i]);
+            h->stage[i] = nullptr;
+        }
+        h->stage_bytes = 0;
+        const size_t want = std::min<size_t>(STAGE, std::max<size_t>(need, (size_t)1 << 20));
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(hipHostMalloc(&h->stage[i], want + 64, hipHostMallocDefault));
+            if (!h->stage_ev[i]) HIP_TRY(hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
+        }
+        h->stage_bytes = want;
+    }
+    struct Piece { size_t b0, cnt; };
+    Piece prev{0, 0};
+    auto offsets = [&](size_t cnt, size_t& o_llr, size_t& o_it, size_t& o_hard, size_t& o_conv) {
+        o_llr = 0;
+        o_it = o_llr + (llr ? cnt * n * 8 : 0);
+        o_hard = o_it + (iters ? ((cnt * 4 + 7) & ~(size_t)7) : 0);
+        o_conv = o_hard + (hard ? cnt * n : 0);
+    };
+    auto drain = [&](const Piece& pc, int slot) -> int {
+        if (pc.cnt == 0) return QBP_OK;
+        HIP_TRY(hipEventSynchronize(h->stage_ev[slot]));
+        const uint8_t* st = static_cast<const uint8_t*>(h->stage[slot]);
+        size_t o_llr, o_it, o_hard, o_conv;
+        offsets(pc.cnt, o_llr, o_it, o_hard, o_conv);
+        if (llr) std::memcpy(llr + pc.b0 * n, st + o_llr, pc.cnt * n * 8);
+        if (iters) std::memcpy(iters + pc.b0, st + o_it, pc.cnt * 4);
+        if (hard) std::memcpy(hard + pc.b0 * n, st + o_hard, pc.cnt * n);
+        if (converged) std::memcpy(converged + pc.b0, st + o_conv, pc.cnt);
+        return QBP_OK;
+    };
+    int slot = 0;
+    for (size_t b0 = 0; b0 < b; b0 += chunk, slot ^= 1) {
+        const size_t cnt = std::min(chunk, b - b0);
+        uint8_t* st = static_cast<uint8_t*>(h->stage[slot]);
+        size_t o_llr, o_it, o_hard, o_conv;
+        offsets(cnt, o_llr, o_it, o_hard, o_conv);
+        if (llr) HIP_TRY(hipMemcpyAsync(st + o_llr, h->d_llr.p + b0 * n, cnt * n * 8, hipMemcpyDeviceToHost, s));
+        if (iters) HIP_TRY(hipMemcpyAsync(st + o_it, h->d_iters.p + b0, cnt * 4, hipMemcpyDeviceToHost, s));
+        if (hard) HIP_TRY(hipMemcpyAsync(st + o_hard, h->d_hard.p + b0 * n, cnt * n, hipMemcpyDeviceToHost, s));
+        if (converged) HIP_TRY(hipMemcpyAsync(st + o_conv, h->d_conv.p + b0, cnt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipEventRecord(h->stage_ev[slot], s));
+        const int rc2 = drain(prev, slot ^ 1);          // the previous chunk, while this one is in flight
+        if (rc2) return rc2;
+        prev = Piece{b0, cnt};
+    }
+    return drain(prev, slot ^ 1);
+}
+
 int qbp_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B,
                      int32_t max_iter, int32_t variant, double alpha, double damping,
                      double clip_llr, uint32_t flags, uint8_t* hard, uint8_t* converged,
@@ -1163,11 +1378,10 @@ try {
     if (rc) return rc;
     if (B == 0) return QBP_OK;
     if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
-    for (int v = 0; v < h->n; ++v)
-        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if ((rc = check_prior(h->n, prior, false)) != QBP_OK) return rc;
     if (flags & QBP_FLAG_LAYERED) {
         if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
-        if ((rc = check_finite_prior(h, prior)) != QBP_OK) return rc;
+        if ((rc = check_prior(h->n, prior, true)) != QBP_OK) return rc;
     }
     if (flags & QBP_FLAG_DENSE_F_COLSUM_ITER0) {     // (the shortcut is judged on the host copy of the priors)
         int mode = 0;
@@ -1218,100 +1432,29 @@ try {
             return QBP_OK;
         }
     }
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
+    // (the outputs leave through decode_copy_out, not through the stage's downloads: reserved only)
     if (hard) HIP_TRY(h->d_hard.reserve(b * n));
     if (converged) HIP_TRY(h->d_conv.reserve(b));
     if (iters) HIP_TRY(h->d_iters.reserve(b));
     if (llr) HIP_TRY(h->d_llr.reserve(b * n));
     hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = qbp_decode_batch_device(h, h->d_syn.p, h->d_prior.p, B, max_iter, variant, alpha, damping,
-                                 clip_llr, flags, hard ? h->d_hard.p : nullptr,
-                                 converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
-                                 llr ? h->d_llr.p : nullptr, s);
-    if (rc) return rc;
-    // Outputs: device -> pinned staging (DMA at PCIe rate) -> the caller's arrays (memcpy), in chunks
-    // of up to 32 MiB, the host copy of one chunk overlapping the DMA of the next.  (A direct copy
-    // into pageable memory goes through the runtime's own small staging buffers at a fraction of
-    // that rate.)  The two staging buffers are as large as the largest chunk any call of this handle has
-    // needed, never more than 32 MiB each (they used to be 32 MiB from the first 256 KiB call on).
-    auto copy_out = [&]() -> int {
-        const size_t per = (hard ? n : 0) + (converged ? 1 : 0) + (iters ? 4 : 0) + (llr ? 8 * n : 0);
-        constexpr size_t STAGE = (size_t)32 << 20;
-        if (per == 0) return QBP_OK;
-        // (pieces of at least 1 MiB, at least four of them above 4 MiB: the reference driver's 13 MB per
-        // batch then overlap their DMA with the copy-out instead of running one after the other)
-        const size_t quarter = std::max<size_t>((b + 3) / 4, ((size_t)1 << 20) / per + 1);
-        const size_t chunk = std::max<size_t>(1, std::min<size_t>({b, STAGE / (per + 8), quarter}));
-        const size_t need = std::min<size_t>(STAGE, chunk * (per + 8) + 64);
-        if (h->stage_bytes < need) {
-            for (int i = 0; i < 2; ++i) {
-                if (h->stage[i]) (void)hipHostFree(h->stage[i]);
-                h->stage[i] = nullptr;
-            }
-            h->stage_bytes = 0;
-            const size_t want = std::min<size_t>(STAGE, std::max<size_t>(need, (size_t)1 << 20));
-            for (int i = 0; i < 2; ++i) {
-                HIP_TRY(hipHostMalloc(&h->stage[i], want + 64, hipHostMallocDefault));
-                if (!h->stage_ev[i]) HIP_TRY(hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
-            }
-            h->stage_bytes = want;
-        }
-        struct Piece { size_t b0, cnt; };
-        Piece prev{0, 0};
-        auto offsets = [&](size_t cnt, size_t& o_llr, size_t& o_it, size_t& o_hard, size_t& o_conv) {
-            o_llr = 0;
-            o_it = o_llr + (llr ? cnt * n * 8 : 0);
-            o_hard = o_it + (iters ? ((cnt * 4 + 7) & ~(size_t)7) : 0);
-            o_conv = o_hard + (hard ? cnt * n : 0);
-        };
-        auto drain = [&](const Piece& pc, int slot) -> int {
-            if (pc.cnt == 0) return QBP_OK;
-            HIP_TRY(hipEventSynchronize(h->stage_ev[slot]));
-            const uint8_t* st = static_cast<const uint8_t*>(h->stage[slot]);
-            size_t o_llr, o_it, o_hard, o_conv;
-            offsets(pc.cnt, o_llr, o_it, o_hard, o_conv);
-            if (llr) std::memcpy(llr + pc.b0 * n, st + o_llr, pc.cnt * n * 8);
-            if (iters) std::memcpy(iters + pc.b0, st + o_it, pc.cnt * 4);
-            if (hard) std::memcpy(hard + pc.b0 * n, st + o_hard, pc.cnt * n);
-            if (converged) std::memcpy(converged + pc.b0, st + o_conv, pc.cnt);
-            return QBP_OK;
-        };
-        int slot = 0;
-        for (size_t b0 = 0; b0 < b; b0 += chunk, slot ^= 1) {
-            const size_t cnt = std::min(chunk, b - b0);
-            uint8_t* st = static_cast<uint8_t*>(h->stage[slot]);
-            size_t o_llr, o_it, o_hard, o_conv;
-            offsets(cnt, o_llr, o_it, o_hard, o_conv);
-            if (llr) HIP_TRY(hipMemcpyAsync(st + o_llr, h->d_llr.p + b0 * n, cnt * n * 8, hipMemcpyDeviceToHost, s));
-            if (iters) HIP_TRY(hipMemcpyAsync(st + o_it, h->d_iters.p + b0, cnt * 4, hipMemcpyDeviceToHost, s));
-            if (hard) HIP_TRY(hipMemcpyAsync(st + o_hard, h->d_hard.p + b0 * n, cnt * n, hipMemcpyDeviceToHost, s));
-            if (converged) HIP_TRY(hipMemcpyAsync(st + o_conv, h->d_conv.p + b0, cnt, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipEventRecord(h->stage_ev[slot], s));
-            const int rc2 = drain(prev, slot ^ 1);          // the previous chunk, while this one is in flight
-            if (rc2) return rc2;
-            prev = Piece{b0, cnt};
-        }
-        return drain(prev, slot ^ 1);
-    };
-    rc = copy_out();
-    if (rc) {
-        // (copies into the staging buffers may still be in flight: the next call must not find them so)
-        (void)hipStreamSynchronize(s);
-        return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    HostStage st(s);
+    const uint8_t* d_syn = st.in(h->d_syn, syndromes, b * m);
+    const double* d_prior = st.in(h->d_prior, prior, n);
+    if (st.failed()) return st.error();
+    rc = qbp_decode_batch_device(h, d_syn, d_prior, B, max_iter, variant, alpha, damping, clip_llr, flags,
+                                 hard ? h->d_hard.p : nullptr, converged ? h->d_conv.p : nullptr,
+                                 iters ? h->d_iters.p : nullptr, llr ? h->d_llr.p : nullptr, s);
+    if (rc == QBP_OK) rc = decode_copy_out(h, b, hard, converged, iters, llr, s);
+    return st.finish(rc);
 }
 QBP_ABI_CATCH
 
 // The messages of iteration `iteration` of a B-syndrome decode (host inputs), [B][E] in h->d_llr: the work of
 // qbp_check_messages and qbp_message_histograms after their argument checks.
-static int dump_messages(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, int variant,
-                         double alpha, double damping, double clip_llr, int iteration, uint32_t flags, int col_mode,
-                         hipStream_t s)
+static int dump_messages(qbp_handle* h, HostStage& st, const uint8_t* syndromes, const double* prior, int64_t B,
+                         int variant, double alpha, double damping, double clip_llr, int iteration, uint32_t flags,
+                         int col_mode, hipStream_t s)
 {
     if (variant == QBP_SUM_PRODUCT) {
         // plain sum-product = the damped update with alpha = damping = 1 and no LLR clip: the
@@ -1320,13 +1463,12 @@ static int dump_messages(qbp_handle* h, const uint8_t* syndromes, const double* 
         alpha = 1.0; damping = 1.0; clip_llr = __builtin_inf();
     }
     const size_t m = h->m, n = h->n, b = (size_t)B, E = (size_t)std::max(h->E, 1);
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
     HIP_TRY(h->d_llr.reserve(b * E));
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
     BpCall c;
-    c.syndromes = h->d_syn.p; c.prior = h->d_prior.p; c.B = B; c.max_iter = iteration + 1; c.variant = variant;
+    c.syndromes = st.in(h->d_syn, syndromes, b * m);
+    c.prior = st.in(h->d_prior, prior, n);
+    if (st.failed()) return st.error();
+    c.B = B; c.max_iter = iteration + 1; c.variant = variant;
     c.alpha = alpha; c.damping = damping; c.clip_llr = clip_llr;
     c.flags = flags | QBP_FLAG_FORCE_FULL;   // (no early exit before the dump iteration)
     c.dump = h->d_llr.p; c.dump_iter = iteration;
@@ -1351,13 +1493,11 @@ try {
     if (!syndromes || !prior || !messages) return fail(QBP_E_INVALID, "null pointer");
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    const size_t b = (size_t)B;
     hipStream_t s = h->stream;
-    rc = dump_messages(h, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(messages, h->d_llr.p, b * (size_t)h->E * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    HostStage st(s);
+    rc = dump_messages(h, st, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
+    if (rc == QBP_OK) st.out(h->d_llr, messages, (size_t)B * (size_t)h->E);     // (reserved by dump_messages: the download alone)
+    return st.finish(rc);
 }
 QBP_ABI_CATCH
 
@@ -1379,9 +1519,10 @@ try {
     HIP_TRY(on_device.err);
     const size_t n = h->n, b = (size_t)B, E = (size_t)h->E;
     hipStream_t s = h->stream;
-    HIP_TRY(h->d_hard.reserve(b * n));               // the true error bits
-    HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, b * n, hipMemcpyHostToDevice, s));
-    rc = dump_messages(h, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
+    HostStage st(s);                                 // (every return below leaves the stream idle)
+    const uint8_t* d_errors = st.in(h->d_hard, errors, b * n);      // the true error bits
+    if (st.failed()) return st.error();
+    rc = dump_messages(h, st, syndromes, prior, B, variant, alpha, damping, clip_llr, iteration, flags, col_mode, s);
     if (rc) return rc;
     // range of all messages (rework/Alvarado.py:41-44: the two classes share one range)
     const int grid = (int)std::min<size_t>(1024, (b * E + 255) / 256);
@@ -1402,16 +1543,15 @@ try {
     const double step = (hi - lo) / (double)bins;
     for (int i = 0; i < bins; ++i) edges[i] = (double)i * step + lo;
     edges[bins] = hi;
-    HIP_TRY(h->d_edges.reserve((size_t)bins + 1));
-    HIP_TRY(h->d_hist.reserve((size_t)2 * bins));
-    HIP_TRY(hipMemcpyAsync(h->d_edges.p, edges, ((size_t)bins + 1) * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_hist.p, 0, (size_t)2 * bins * sizeof(unsigned long long), s));
-    const size_t lds = (((size_t)2 * bins + 1) & ~(size_t)1) * 4 + ((size_t)bins + 1) * 8;
-    HIP_TRY(qbp::launch_hist_bin(grid, lds, h->d_llr.p, h->d_hard.p, h->d_col_idx.p, (long long)B, (int)E, (int)n,
-                                 h->d_edges.p, bins, h->d_hist.p, s));
     std::vector<unsigned long long> hist((size_t)2 * bins);
-    HIP_TRY(hipMemcpyAsync(hist.data(), h->d_hist.p, hist.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    const double* d_edges = st.in(h->d_edges, edges, (size_t)bins + 1);
+    unsigned long long* d_hist = st.out(h->d_hist, hist.data(), hist.size());
+    if (st.failed()) return st.error();
+    HIP_TRY(hipMemsetAsync(d_hist, 0, hist.size() * sizeof(unsigned long long), s));
+    const size_t lds = (((size_t)2 * bins + 1) & ~(size_t)1) * 4 + ((size_t)bins + 1) * 8;
+    HIP_TRY(qbp::launch_hist_bin(grid, lds, h->d_llr.p, d_errors, h->d_col_idx.p, (long long)B, (int)E, (int)n,
+                                 d_edges, bins, d_hist, s));
+    if ((rc = st.finish(QBP_OK)) != QBP_OK) return rc;
     for (int i = 0; i < bins; ++i) { hist0[i] = (int64_t)hist[i]; hist1[i] = (int64_t)hist[bins + i]; }
     return QBP_OK;
 }
@@ -1421,29 +1561,7 @@ static int mc_prepare(qbp_handle* h, const uint8_t* Lx, int32_t k, hipStream_t s
 {
     if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
     if (k > 0 && !Lx) return fail(QBP_E_INVALID, "Lx is null");
-    const size_t n = h->n;
-    if (h->lx_cache_k == k && h->lx_cache.size() == (size_t)k * n &&
-        (k == 0 || std::memcmp(h->lx_cache.data(), Lx, (size_t)k * n) == 0))
-        return QBP_OK;
-    std::vector<unsigned long long> cols(n, 0ull);
-    for (int l = 0; l < k; ++l)
-        for (size_t v = 0; v < n; ++v)
-            if (Lx[(size_t)l * n + v] & 1) cols[v] |= 1ull << l;
-    HIP_TRY(h->d_lx_cols.reserve(n));
-    HIP_TRY(hipMemcpyAsync(h->d_lx_cols.p, cols.data(), n * sizeof(unsigned long long),
-                           hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // cols is a local
-    h->lx_cache.assign(Lx, Lx + (size_t)k * n);
-    h->lx_cache_k = k;
-    return QBP_OK;
-}
-
-static unsigned mc_threshold(double p)
-{
-    double t = std::floor(p * 4294967296.0);
-    if (!(t > 0.0)) t = 0.0;
-    if (t > 4294967295.0) t = 4294967295.0;
-    return (unsigned)t;
+    return h->mc_in.prepare_lx((size_t)h->n, Lx, k, s);
 }
 
 // probs [n] of qbp_mc_run_probs: every value in [0, 1] (host only, before any GPU work)
@@ -1453,22 +1571,6 @@ static int check_probs(const qbp_handle* h, const double* probs)
     for (int v = 0; v < h->n; ++v)
         if (!(probs[v] >= 0.0 && probs[v] <= 1.0))
             return fail(QBP_E_INVALID, "probs[%d] = %g out of [0, 1]", v, probs[v]);
-    return QBP_OK;
-}
-
-// Sampler thresholds of probs on the device, [n rounded up to 4] (zero in the padding: those bytes are never
-// set), uploaded once and again only when they change, like the Lx columns of mc_prepare.
-static int mc_prepare_thr(qbp_handle* h, const double* probs, hipStream_t s)
-{
-    const size_t n4 = ((size_t)h->n + 3) / 4 * 4;
-    std::vector<uint32_t> thr(n4, 0u);
-    for (int v = 0; v < h->n; ++v) thr[v] = mc_threshold(probs[v]);
-    if (h->thr_cache == thr) return QBP_OK;
-    h->thr_cache.clear();
-    HIP_TRY(h->d_mc_thr.reserve(n4));
-    HIP_TRY(hipMemcpyAsync(h->d_mc_thr.p, thr.data(), n4 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));   // thr is a local
-    h->thr_cache.swap(thr);
     return QBP_OK;
 }
 
@@ -1724,22 +1826,14 @@ static int osd_batch_host(qbp_handle* h, uint32_t osd_flags, const uint8_t* synd
     }
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_llr.reserve(b * n));
-    HIP_TRY(h->d_hard.reserve(b * n));
-    HIP_TRY(h->d_sol.reserve(b * n));
-    if (ordered) HIP_TRY(h->d_osd_order.reserve(b * n));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
-    if (ordered) HIP_TRY(hipMemcpyAsync(h->d_osd_order.p, col_order, b * n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    rc = osd_batch_device(h, osd_flags, h->d_syn.p, h->d_llr.p, h->d_hard.p, ordered ? h->d_osd_order.p : nullptr, B,
-                          h->d_sol.p, s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    HostStage st(h->stream);
+    const uint8_t* d_syn = st.in(h->d_syn, syndromes, b * m);
+    const double* d_llr = st.in(h->d_llr, llr, b * n);
+    const uint8_t* d_hard = st.in(h->d_hard, hard, b * n);
+    const int32_t* d_order = ordered ? st.in(h->d_osd_order, col_order, b * n) : nullptr;
+    uint8_t* d_sol = st.out(h->d_sol, solution, b * n);
+    if (st.failed()) return st.error();
+    return st.finish(osd_batch_device(h, osd_flags, d_syn, d_llr, d_hard, d_order, B, d_sol, h->stream));
 }
 
 int qbp_osd_batch(qbp_handle* h, uint32_t osd_flags, const uint8_t* syndromes, const double* llr, const uint8_t* hard,
@@ -1908,13 +2002,6 @@ static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant,
     return QBP_OK;
 }
 
-static int check_finite_prior(const qbp_handle* h, const double* prior)
-{
-    for (int v = 0; v < h->n; ++v)
-        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite (QBP_FLAG_LAYERED)", v);
-    return QBP_OK;
-}
-
 // One launch of bp_layered_kernel (device pointers): the batch build, or (c.mc) the Monte-Carlo build on stored errors
 static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 {
@@ -2070,7 +2157,7 @@ static int record_launch_setup(qbp_handle* h, const RecordCall& c, bool records,
     io.syndromes = c.syndromes; io.B = records ? 0 : c.max_items;
     io.hard = c.hard; io.converged = c.converged; io.iters = c.iters; io.llr = c.llr;
     io.fail_count = c.fail_count; io.fail_list = c.fail_list; io.fail_syn = c.fail_syn; io.fail_err = c.fail_err;
-    io.lx_cols = h->d_lx_cols.p; io.half_distance = c.half_distance; io.counters = c.counters;
+    io.lx_cols = h->mc_in.d_lx_cols.p; io.half_distance = c.half_distance; io.counters = c.counters;
     h->last_threads = g.threads; h->last_lds = (int)g.lds; h->last_grid = grid;
     *grid_out = grid;
     return QBP_OK;
@@ -2085,33 +2172,23 @@ static int record_decode_batch_host(qbp_handle* h, const uint8_t* syndromes, con
                                     uint8_t* converged, int32_t* iters, double* llr, int32_t* const (&extra)[2],
                                     DevBuf<int32_t>* const (&d_extra)[2], const Entry& entry)
 {
-    for (int v = 0; v < h->n; ++v)
-        if (!std::isfinite(prior[v])) return fail(QBP_E_INVALID, "prior[%d] is not finite", v);
+    const int rc = check_prior(h->n, prior, true);
+    if (rc) return rc;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     const size_t m = h->m, n = h->n, b = (size_t)B;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_prior.reserve(n));
-    if (hard) HIP_TRY(h->d_hard.reserve(b * n));
-    if (converged) HIP_TRY(h->d_conv.reserve(b));
-    if (iters) HIP_TRY(h->d_iters.reserve(b));
-    if (llr) HIP_TRY(h->d_llr.reserve(b * n));
+    HostStage st(h->stream);
+    st.in(h->d_syn, syndromes, b * m);          // (the entries read h->d_syn.p and h->d_prior.p)
+    st.in(h->d_prior, prior, n);
+    uint8_t* d_hard = st.out(h->d_hard, hard, b * n);
+    uint8_t* d_conv = st.out(h->d_conv, converged, b);
+    int32_t* d_iters = st.out(h->d_iters, iters, b);
+    double* d_llr = st.out(h->d_llr, llr, b * n);
+    int32_t* d_x[2] = {nullptr, nullptr};
     for (int k = 0; k < 2; ++k)
-        if (extra[k]) HIP_TRY(d_extra[k]->reserve(b));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    int rc = entry(hard ? h->d_hard.p : nullptr, converged ? h->d_conv.p : nullptr, iters ? h->d_iters.p : nullptr,
-                   llr ? h->d_llr.p : nullptr, extra[0] ? d_extra[0]->p : nullptr, extra[1] ? d_extra[1]->p : nullptr, s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (hard) HIP_TRY(hipMemcpyAsync(hard, h->d_hard.p, b * n, hipMemcpyDeviceToHost, s));
-    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, b, hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, h->d_iters.p, b * 4, hipMemcpyDeviceToHost, s));
-    if (llr) HIP_TRY(hipMemcpyAsync(llr, h->d_llr.p, b * n * 8, hipMemcpyDeviceToHost, s));
-    for (int k = 0; k < 2; ++k)
-        if (extra[k]) HIP_TRY(hipMemcpyAsync(extra[k], d_extra[k]->p, b * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+        if (d_extra[k]) d_x[k] = st.out(*d_extra[k], extra[k], b);
+    if (st.failed()) return st.error();
+    return st.finish(entry(d_hard, d_conv, d_iters, d_llr, d_x[0], d_x[1], h->stream));
 }
 
 }  // extern "C++"
@@ -2412,22 +2489,14 @@ try {
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     const size_t m = h->m, n = h->n, b = (size_t)B;
-    HIP_TRY(h->d_syn.reserve(b * m));
-    HIP_TRY(h->d_llr.reserve(b * n));
-    HIP_TRY(h->d_hard.reserve(b * n));
-    HIP_TRY(h->d_sol.reserve(b * n));
-    if (stats) HIP_TRY(h->d_lsd_stats.reserve(b * 4));
-    hipStream_t s = h->stream;
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_llr.p, llr, b * n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_hard.p, hard, b * n, hipMemcpyHostToDevice, s));
-    const int rc = qbp_lsd_batch_device(h, h->d_syn.p, h->d_llr.p, h->d_hard.p, B, h->d_sol.p,
-                                        stats ? h->d_lsd_stats.p : nullptr, s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    HIP_TRY(hipMemcpyAsync(solution, h->d_sol.p, b * n, hipMemcpyDeviceToHost, s));
-    if (stats) HIP_TRY(hipMemcpyAsync(stats, h->d_lsd_stats.p, b * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    HostStage st(h->stream);
+    const uint8_t* d_syn = st.in(h->d_syn, syndromes, b * m);
+    const double* d_llr = st.in(h->d_llr, llr, b * n);
+    const uint8_t* d_hard = st.in(h->d_hard, hard, b * n);
+    uint8_t* d_sol = st.out(h->d_sol, solution, b * n);
+    int32_t* d_stats = st.out(h->d_lsd_stats, stats, b * 4);
+    if (st.failed()) return st.error();
+    return st.finish(qbp_lsd_batch_device(h, d_syn, d_llr, d_hard, B, d_sol, d_stats, h->stream));
 }
 QBP_ABI_CATCH
 
@@ -2504,7 +2573,7 @@ static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial
 constexpr uint32_t SECOND_BP_BITS = QBP_FLAG_RELAY | QBP_FLAG_GD | QBP_FLAG_LSD;
 
 // Everything a Monte-Carlo call refuses: host only, once per public call, for the whole range and before any GPU work.
-// `host_prior`: the priors when they are a host array (the layered schedule's finite check), else null.
+// `host_prior`: the priors when they are a host array (no NaN; finite for the layered schedule), else null.
 static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prior)
 {
     if (!h) return fail(QBP_E_INVALID, "null handle");
@@ -2524,7 +2593,7 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
     if ((rc = check_gd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_lsd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
-    if (host_prior && (c.dec.flags & QBP_FLAG_LAYERED) && (rc = check_finite_prior(h, host_prior)) != QBP_OK) return rc;
+    if (host_prior && (rc = check_prior(h->n, host_prior, (c.dec.flags & QBP_FLAG_LAYERED) != 0)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
     if ((rc = parse_osd_flags(h, c.dec.flags & ~SECOND_BP_BITS, true, &osd_method, &osd_order)) != QBP_OK) return rc;
     if (c.k < 0 || c.k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", c.k);
@@ -2586,9 +2655,9 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     if (osd && (rc = mc_fail_records(h, mc, rows, (size_t)T, true, s)) != QBP_OK) return rc;
     mc.n_budgets = ladder ? c.n_budgets : 0; mc.budgets = ladder ? c.budgets : nullptr;
     mc.spectrum = reinterpret_cast<long long*>(c.d_spectrum); mc.iter_hist = reinterpret_cast<long long*>(c.d_iter_hist);
-    mc.lx_cols = h->d_lx_cols.p; mc.trial_begin = c.trial_begin; mc.seed = c.errors.seed;
+    mc.lx_cols = h->mc_in.d_lx_cols.p; mc.trial_begin = c.trial_begin; mc.seed = c.errors.seed;
     mc.threshold = mc_threshold(c.errors.p); mc.draws = c.errors.draws; mc.half_distance = c.distance / 2;
-    mc.thr_cols = c.errors.kind == McErrors::PROBS ? h->d_mc_thr.p : nullptr;
+    mc.thr_cols = c.errors.kind == McErrors::PROBS ? h->mc_in.d_thr.p : nullptr;
     mc.counters = reinterpret_cast<long long*>(c.d_counters);
     mc.errors_in = c.errors.d_errors;
     BpCall b;
@@ -2628,7 +2697,7 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
         qbp::LsdParams P{};
         P.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p); P.list = h->d_fail_list.p;
         P.syndromes = h->d_fail_syn.p; P.llr = h->d_fail_llr.p; P.hard = h->d_fail_hard.p;
-        P.errors = h->d_fail_err.p; P.lx_cols = h->d_lx_cols.p; P.half_distance = c.distance / 2;
+        P.errors = h->d_fail_err.p; P.lx_cols = h->mc_in.d_lx_cols.p; P.half_distance = c.distance / 2;
         P.counters = reinterpret_cast<long long*>(c.d_counters);
         return lsd_launch(h, P, T, true, s);
     }
@@ -2642,7 +2711,7 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
         O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p + j);
         O.list = h->d_fail_list.p + r0;
         O.syndromes = h->d_fail_syn.p + r0 * m; O.llr = h->d_fail_llr.p + r0 * n; O.hard = h->d_fail_hard.p + r0 * n;
-        O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->d_lx_cols.p; O.half_distance = c.distance / 2;
+        O.errors = h->d_fail_err.p + r0 * n; O.lx_cols = h->mc_in.d_lx_cols.p; O.half_distance = c.distance / 2;
         O.counters = reinterpret_cast<long long*>(c.d_counters) + j * qbp::NUM_COUNTERS;
         O.spectrum = reinterpret_cast<long long*>(c.d_spectrum);
         rc = osd_launch(h, O, T, s, false, osd_method, osd_order);
@@ -2657,7 +2726,7 @@ static hipError_t mc_sample(qbp_handle* h, const McErrors& e, uint8_t* errors, l
     // (the samplers do not depend on H: any matrix, whichever kernel decodes it)
     if (e.kind == McErrors::WEIGHT) return qbp::launch_mc_sample_weight(errors, h->n, e.weight, t, trial_begin, e.seed, s);
     if (e.kind == McErrors::PROBS)
-        return qbp::launch_mc_sample_cols(errors, h->n, t, trial_begin, e.draws, e.seed, h->d_mc_thr.p, s);
+        return qbp::launch_mc_sample_cols(errors, h->n, t, trial_begin, e.draws, e.seed, h->mc_in.d_thr.p, s);
     return qbp::launch_mc_sample(errors, h->n, t, trial_begin, e.draws, e.seed, mc_threshold(e.p), s);
 }
 
@@ -2669,7 +2738,7 @@ static int mc_run(qbp_handle* h, const McCall& c, hipStream_t s)
     HIP_TRY(on_device.err);
     int rc = mc_prepare(h, c.Lx, c.k, s);
     if (rc) return rc;
-    if (c.errors.kind == McErrors::PROBS && (rc = mc_prepare_thr(h, c.errors.probs, s)) != QBP_OK) return rc;
+    if (c.errors.kind == McErrors::PROBS && (rc = h->mc_in.prepare_thr((size_t)h->n, c.errors.probs, s)) != QBP_OK) return rc;
     if (!c.chunked()) return mc_launch(h, c, s);
     // the errors qbp_mc_sample_errors* returns, drawn chunk by chunk into the handle's buffer and run as stored errors:
     // the global trial index lives in the sampler only, the pipeline indexes a chunk's trials from 0
@@ -2711,34 +2780,21 @@ static int mc_run_host(qbp_handle* h, McCall c, const double* prior, const uint8
     if (T == 0) return QBP_OK;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    hipStream_t s = h->stream;
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_counters.reserve(cells));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, cells * sizeof(long long), s));
-    c.d_prior = h->d_prior.p; c.d_counters = reinterpret_cast<int64_t*>(h->d_counters.p);
-    if (stored) {
-        HIP_TRY(h->d_hard.reserve(T * n));                // (scratch of the host-pointer entries: the errors)
-        HIP_TRY(hipMemcpyAsync(h->d_hard.p, errors, T * n, hipMemcpyHostToDevice, s));
-        c.errors.d_errors = h->d_hard.p;
-    }
+    HostStage st(h->stream);
+    c.d_prior = st.in(h->d_prior, prior, n);
+    long long* d_cnt = st.zeroed(h->d_counters, cells);
+    st.add(counters, d_cnt, cells);
+    c.d_counters = reinterpret_cast<int64_t*>(d_cnt);
+    if (stored) c.errors.d_errors = st.in(h->d_hard, errors, T * n);     // (scratch of the host-pointer entries)
     if (tables) {
-        HIP_TRY(h->d_spectrum.reserve(spec_cells + hist_cells));
-        HIP_TRY(hipMemsetAsync(h->d_spectrum.p, 0, (spec_cells + hist_cells) * sizeof(long long), s));
-        c.d_spectrum = reinterpret_cast<int64_t*>(h->d_spectrum.p);
+        long long* d_tab = st.zeroed(h->d_spectrum, spec_cells + hist_cells);
+        st.add(spectrum, d_tab, spec_cells);
+        st.add(iter_hist, d_tab + spec_cells, hist_cells);
+        c.d_spectrum = reinterpret_cast<int64_t*>(d_tab);
         c.d_iter_hist = iter_hist ? c.d_spectrum + spec_cells : nullptr;
     }
-    if ((rc = mc_run(h, c, s)) != QBP_OK) { (void)hipStreamSynchronize(s); return rc; }
-    long long tmp[QBP_MC_MAX_BUDGETS * qbp::NUM_COUNTERS];
-    std::vector<long long> tab(spec_cells + hist_cells);
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, cells * sizeof(long long), hipMemcpyDeviceToHost, s));
-    if (tables) HIP_TRY(hipMemcpyAsync(tab.data(), h->d_spectrum.p, tab.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < cells; ++i) counters[i] += tmp[i];
-    for (size_t i = 0; i < spec_cells; ++i) spectrum[i] += tab[i];
-    if (iter_hist)
-        for (size_t i = 0; i < hist_cells; ++i) iter_hist[i] += tab[spec_cells + i];
-    return QBP_OK;
+    if (st.failed()) return st.error();
+    return st.finish(mc_run(h, c, h->stream));
 }
 
 // The three qbp_mc_sample_errors* entries: errors [T, n] of trials trial_begin .. + T, as the runs draw them.
@@ -2754,7 +2810,7 @@ static int mc_sample_host(qbp_handle* h, const McErrors& e, int64_t trial_begin,
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     hipStream_t s = h->stream;
-    if (e.kind == McErrors::PROBS && (rc = mc_prepare_thr(h, e.probs, s)) != QBP_OK) return rc;
+    if (e.kind == McErrors::PROBS && (rc = h->mc_in.prepare_thr((size_t)h->n, e.probs, s)) != QBP_OK) return rc;
     HIP_TRY(h->d_hard.reserve((size_t)T * (size_t)h->n));
     HIP_TRY(mc_sample(h, e, h->d_hard.p, T, trial_begin, s));
     HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * (size_t)h->n, hipMemcpyDeviceToHost, s));
@@ -2951,9 +3007,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if ((rc = check_gd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_lsd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, flags, 0, true)) != QBP_OK) return rc;
-    if (host_prior)
-        for (int v = 0; v < h->n; ++v)
-            if (host_prior[v] != host_prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if (host_prior && (rc = check_prior(h->n, host_prior, false)) != QBP_OK) return rc;
     rc = parse_osd_flags(h, flags, true, osd_method, osd_order);
     if (rc) return rc;
     if (flags & QBP_FLAG_OSD0) {
@@ -2983,7 +3037,7 @@ static int decode_shots_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, c
     const bool osd = (flags & QBP_FLAG_OSD0) != 0;
     McArgs mc{};
     if (osd && (rc = mc_fail_records(h, mc, 1, (size_t)T, false, s)) != QBP_OK) return rc;
-    mc.lx_cols = h->d_lx_cols.p;
+    mc.lx_cols = h->mc_in.d_lx_cols.p;
     mc.counters = reinterpret_cast<long long*>(d_counters);
     mc.det_bits = d_det_bits; mc.det_row_bytes = (h->m + 7) / 8;
     mc.actual = reinterpret_cast<const unsigned long long*>(d_actual);
@@ -3007,7 +3061,7 @@ static int decode_shots_impl(qbp_handle* h, const uint8_t* Lx_host, int32_t k, c
     O.count_ptr = reinterpret_cast<const long long*>(h->d_fail_count.p);
     O.list = h->d_fail_list.p;
     O.syndromes = h->d_fail_syn.p; O.llr = h->d_fail_llr.p; O.hard = h->d_fail_hard.p;
-    O.lx_cols = h->d_lx_cols.p;
+    O.lx_cols = h->mc_in.d_lx_cols.p;
     O.counters = reinterpret_cast<long long*>(d_counters);
     O.shots = 1; O.actual = mc.actual; O.predictions = mc.predictions;
     return osd_launch(h, O, T, s, true, osd_method, osd_order);
@@ -3051,29 +3105,20 @@ try {
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     const size_t n = h->n, t = (size_t)T, rb = ((size_t)h->m + 7) / 8;
-    hipStream_t s = h->stream;
-    HIP_TRY(h->d_syn.reserve(t * rb));
-    HIP_TRY(h->d_prior.reserve(n));
-    HIP_TRY(h->d_counters.reserve(qbp::NUM_COUNTERS));
-    if (actual) HIP_TRY(h->d_shot_actual.reserve(t));
-    if (predictions) HIP_TRY(h->d_shot_pred.reserve(t));
-    if (converged) HIP_TRY(h->d_conv.reserve(t));
-    HIP_TRY(hipMemcpyAsync(h->d_syn.p, det_bits, t * rb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->d_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    if (actual) HIP_TRY(hipMemcpyAsync(h->d_shot_actual.p, actual, t * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(h->d_counters.p, 0, qbp::NUM_COUNTERS * sizeof(long long), s));
-    rc = decode_shots_impl(h, Lx, k, h->d_syn.p, actual ? reinterpret_cast<const uint64_t*>(h->d_shot_actual.p) : nullptr,
-                           T, h->d_prior.p, max_iter, variant, alpha, damping, clip_llr, flags, osd_method, osd_order,
-                           predictions ? reinterpret_cast<uint64_t*>(h->d_shot_pred.p) : nullptr,
-                           converged ? h->d_conv.p : nullptr, reinterpret_cast<int64_t*>(h->d_counters.p), s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    long long tmp[qbp::NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, h->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    if (predictions) HIP_TRY(hipMemcpyAsync(predictions, h->d_shot_pred.p, t * 8, hipMemcpyDeviceToHost, s));
-    if (converged) HIP_TRY(hipMemcpyAsync(converged, h->d_conv.p, t, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < qbp::NUM_COUNTERS; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    HostStage st(h->stream);
+    const uint8_t* d_det = st.in(h->d_syn, det_bits, t * rb);
+    const double* d_prior = st.in(h->d_prior, prior, n);
+    const unsigned long long* d_actual =
+        actual ? st.in(h->d_shot_actual, reinterpret_cast<const unsigned long long*>(actual), t) : nullptr;
+    unsigned long long* d_pred = st.out(h->d_shot_pred, reinterpret_cast<unsigned long long*>(predictions), t);
+    uint8_t* d_conv = st.out(h->d_conv, converged, t);
+    long long* d_cnt = st.zeroed(h->d_counters, qbp::NUM_COUNTERS);
+    st.add(counters, d_cnt, qbp::NUM_COUNTERS);           // (ADDED to the caller's)
+    if (st.failed()) return st.error();
+    return st.finish(decode_shots_impl(h, Lx, k, d_det, reinterpret_cast<const uint64_t*>(d_actual), T, d_prior, max_iter,
+                                       variant, alpha, damping, clip_llr, flags, osd_method, osd_order,
+                                       reinterpret_cast<uint64_t*>(d_pred), d_conv, reinterpret_cast<int64_t*>(d_cnt),
+                                       h->stream));
 }
 QBP_ABI_CATCH
 
@@ -3306,11 +3351,7 @@ struct qbp_window {
     DevBuf<double> d_in_prior, d_llr_out;
     DevBuf<int32_t> d_iters, d_fails;
     DevBuf<long long> d_counters;
-    DevBuf<unsigned long long> d_lx_cols;
-    std::vector<uint8_t> lx_cache;
-    int lx_cache_k = -1;
-    DevBuf<uint32_t> d_thr;
-    std::vector<uint32_t> thr_cache;
+    McInputs mc_in;
     long long opt_chunk = 0;
 };
 
@@ -3515,32 +3556,21 @@ try {
     if (B == 0) return QBP_OK;
     if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
     if (B > (int64_t)1 << 40) return fail(QBP_E_INVALID, "B too large");
-    for (int v = 0; v < w->n; ++v)
-        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if ((rc = check_prior(w->n, prior, false)) != QBP_OK) return rc;
     DeviceScope on_device(w->device);
     HIP_TRY(on_device.err);
     const size_t b = (size_t)B, m = w->m, n = w->n;
-    hipStream_t s = w->stream;
-    HIP_TRY(w->d_in_syn.reserve(b * m));
-    HIP_TRY(w->d_in_prior.reserve(n));
-    if (correction) HIP_TRY(w->d_x.reserve(b * n));
-    if (converged) HIP_TRY(w->d_conv_out.reserve(b));
-    if (iters) HIP_TRY(w->d_iters.reserve(b));
-    if (llr) HIP_TRY(w->d_llr_out.reserve(b * n));
-    if (window_fails) HIP_TRY(w->d_fails.reserve(b));
-    HIP_TRY(hipMemcpyAsync(w->d_in_syn.p, syndromes, b * m, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(w->d_in_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = window_run(w, w->d_in_syn.p, w->d_in_prior.p, B, max_iter, variant, alpha, damping, clip_llr, flags, method, order,
-                    correction ? w->d_x.p : nullptr, converged ? w->d_conv_out.p : nullptr, iters ? w->d_iters.p : nullptr,
-                    llr ? w->d_llr_out.p : nullptr, window_fails ? w->d_fails.p : nullptr, s);
-    if (rc) { (void)hipStreamSynchronize(s); return rc; }
-    if (correction) HIP_TRY(hipMemcpyAsync(correction, w->d_x.p, b * n, hipMemcpyDeviceToHost, s));
-    if (converged) HIP_TRY(hipMemcpyAsync(converged, w->d_conv_out.p, b, hipMemcpyDeviceToHost, s));
-    if (iters) HIP_TRY(hipMemcpyAsync(iters, w->d_iters.p, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (llr) HIP_TRY(hipMemcpyAsync(llr, w->d_llr_out.p, b * n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (window_fails) HIP_TRY(hipMemcpyAsync(window_fails, w->d_fails.p, b * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return QBP_OK;
+    HostStage st(w->stream);
+    const uint8_t* d_syn = st.in(w->d_in_syn, syndromes, b * m);
+    const double* d_prior = st.in(w->d_in_prior, prior, n);
+    uint8_t* d_x = st.out(w->d_x, correction, b * n);
+    uint8_t* d_conv = st.out(w->d_conv_out, converged, b);
+    int32_t* d_iters = st.out(w->d_iters, iters, b);
+    double* d_llr = st.out(w->d_llr_out, llr, b * n);
+    int32_t* d_fails = st.out(w->d_fails, window_fails, b);
+    if (st.failed()) return st.error();
+    return st.finish(window_run(w, d_syn, d_prior, B, max_iter, variant, alpha, damping, clip_llr, flags, method, order, d_x,
+                                d_conv, d_iters, d_llr, d_fails, w->stream));
 }
 QBP_ABI_CATCH
 
@@ -3588,30 +3618,9 @@ static int window_mc_run(qbp_window* w, const WindowMcCall& c, int method, int o
     const int64_t T = c.trial_end - c.trial_begin;
     if (T == 0) return QBP_OK;
     const size_t n = w->n, m = w->m;
-    // the Lx columns and the sampler thresholds, uploaded when they change (as mc_prepare / mc_prepare_thr do)
-    if (!(w->lx_cache_k == c.k && w->lx_cache.size() == (size_t)c.k * n &&
-          (c.k == 0 || std::memcmp(w->lx_cache.data(), c.Lx, (size_t)c.k * n) == 0))) {
-        std::vector<unsigned long long> cols(n, 0ull);
-        for (int l = 0; l < c.k; ++l)
-            for (size_t v = 0; v < n; ++v)
-                if (c.Lx[(size_t)l * n + v] & 1) cols[v] |= 1ull << l;
-        w->lx_cache_k = -1;
-        HIP_TRY(hipStreamSynchronize(s));   // (an earlier call on the stream may still read the columns)
-        HIP_TRY(w->d_lx_cols.upload(cols));
-        w->lx_cache.assign(c.Lx, c.Lx + (size_t)c.k * n);
-        w->lx_cache_k = c.k;
-    }
-    if (!c.d_errors) {
-        const size_t n4 = (n + 3) / 4 * 4;
-        std::vector<uint32_t> thr(n4, 0u);
-        for (size_t v = 0; v < n; ++v) thr[v] = mc_threshold(c.probs[v]);
-        if (w->thr_cache != thr) {
-            w->thr_cache.clear();
-            HIP_TRY(hipStreamSynchronize(s));
-            HIP_TRY(w->d_thr.upload(thr));
-            w->thr_cache.swap(thr);
-        }
-    }
+    int rc = w->mc_in.prepare_lx(n, c.Lx, c.k, s);
+    if (rc == QBP_OK && !c.d_errors) rc = w->mc_in.prepare_thr(n, c.probs, s);
+    if (rc) return rc;
     const long long chunk = window_chunk_trials(w, T);
     if (!c.d_errors) HIP_TRY(w->d_err.reserve((size_t)chunk * n));
     HIP_TRY(w->d_in_syn.reserve((size_t)chunk * m));
@@ -3622,14 +3631,14 @@ static int window_mc_run(qbp_window* w, const WindowMcCall& c, int method, int o
     for (int64_t a = c.trial_begin; a < c.trial_end; a += chunk) {
         const long long t = std::min<long long>(chunk, c.trial_end - a);
         const uint8_t* err = c.d_errors ? c.d_errors + (size_t)(a - c.trial_begin) * n : w->d_err.p;
-        if (!c.d_errors) HIP_TRY(qbp::launch_mc_sample_cols(w->d_err.p, w->n, t, a, c.draws, c.seed, w->d_thr.p, s));
+        if (!c.d_errors) HIP_TRY(qbp::launch_mc_sample_cols(w->d_err.p, w->n, t, a, c.draws, c.seed, w->mc_in.d_thr.p, s));
         HIP_TRY(qbp::launch_window_syndrome(err, t, w->m, w->n, w->d_row_ptr.p, w->d_col_idx.p, w->d_in_syn.p, s));
-        const int rc = window_run(w, w->d_in_syn.p, c.d_prior, t, c.max_iter, c.variant, c.alpha, c.damping, c.clip_llr,
+        rc = window_run(w, w->d_in_syn.p, c.d_prior, t, c.max_iter, c.variant, c.alpha, c.damping, c.clip_llr,
                                   c.flags, method, order, w->d_x.p, w->d_conv_out.p, w->d_iters.p, nullptr, w->d_fails.p, s,
                                   a == c.trial_begin);
         if (rc) return rc;
         HIP_TRY(qbp::launch_window_classify(err, w->d_x.p, w->d_conv_out.p, w->d_iters.p, w->d_fails.p, t, w->n,
-                                            w->d_lx_cols.p, c.distance / 2, reinterpret_cast<long long*>(c.d_counters), s));
+                                            w->mc_in.d_lx_cols.p, c.distance / 2, reinterpret_cast<long long*>(c.d_counters), s));
     }
     return QBP_OK;
 }
@@ -3660,30 +3669,20 @@ static int window_mc_host(qbp_window* w, WindowMcCall c, const double* prior, co
     int method = 0, order = 0;
     int rc = window_mc_check(w, c, stored, &method, &order);
     if (rc) return rc;
-    for (int v = 0; v < w->n; ++v)
-        if (prior[v] != prior[v]) return fail(QBP_E_INVALID, "prior[%d] is NaN (+-inf are legal)", v);
+    if ((rc = check_prior(w->n, prior, false)) != QBP_OK) return rc;
     if (stored) std::fill(counters, counters + QBP_NUM_COUNTERS, (int64_t)0);
     const size_t T = (size_t)(c.trial_end - c.trial_begin), n = w->n;
     if (T == 0) return QBP_OK;
     DeviceScope on_device(w->device);
     HIP_TRY(on_device.err);
-    hipStream_t s = w->stream;
-    HIP_TRY(w->d_in_prior.reserve(n));
-    HIP_TRY(w->d_counters.reserve(QBP_NUM_COUNTERS));
-    HIP_TRY(hipMemcpyAsync(w->d_in_prior.p, prior, n * sizeof(double), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(w->d_counters.p, 0, QBP_NUM_COUNTERS * sizeof(long long), s));
-    c.d_prior = w->d_in_prior.p; c.d_counters = reinterpret_cast<int64_t*>(w->d_counters.p);
-    if (stored) {
-        HIP_TRY(w->d_err.reserve(T * n));
-        HIP_TRY(hipMemcpyAsync(w->d_err.p, errors, T * n, hipMemcpyHostToDevice, s));
-        c.d_errors = w->d_err.p;
-    }
-    if ((rc = window_mc_run(w, c, method, order, s)) != QBP_OK) { (void)hipStreamSynchronize(s); return rc; }
-    long long tmp[QBP_NUM_COUNTERS];
-    HIP_TRY(hipMemcpyAsync(tmp, w->d_counters.p, sizeof(tmp), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    for (int i = 0; i < QBP_NUM_COUNTERS; ++i) counters[i] += tmp[i];
-    return QBP_OK;
+    HostStage st(w->stream);
+    c.d_prior = st.in(w->d_in_prior, prior, n);
+    long long* d_cnt = st.zeroed(w->d_counters, QBP_NUM_COUNTERS);
+    st.add(counters, d_cnt, QBP_NUM_COUNTERS);
+    c.d_counters = reinterpret_cast<int64_t*>(d_cnt);
+    if (stored) c.d_errors = st.in(w->d_err, errors, T * n);
+    if (st.failed()) return st.error();
+    return st.finish(window_mc_run(w, c, method, order, w->stream));
 }
 
 int qbp_window_mc_run_probs(qbp_window* w, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
