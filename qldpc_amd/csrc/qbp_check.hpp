@@ -83,12 +83,15 @@ QBP_HD double minsum_message(double x, const MinSumRow& row, unsigned sbit, doub
 // ---- sum-product (beliefPropagation.py:114-126) ---------------------------------------------------------
 // R of the edge whose tanh value is t, in a row whose tanh product is prod: any product, zero, subnormal and
 // NaN included (before the alpha scaling of the damped variant)
-template <int VARIANT>
+// IEEE_DIV: the quotient by the compiler's full division sequence.  div_nr's residual a - b q is below the
+// subnormal grid when the product is subnormal (a message of magnitude 1e-309 in the row), and its quotient then
+// misses numpy's by an ulp; check_row's rare path, which is where such rows go, pays for the scaling steps.
+template <int VARIANT, bool IEEE_DIV = false>
 QBP_HD double sp_message(double prod, double t, unsigned sbit, NpT np_tab)
 {
     const double ts = __builtin_fabs(t) < 1e-15 ? 1e-15 : t;         // t_safe (:122)
     // (a zero or denormal product: quotients of any size, down to the subnormals)
-    return check_message<VARIANT>(div_nr(prod, ts), sbit, np_tab);     // :123-126
+    return check_message<VARIANT>(IEEE_DIV ? prod / ts : div_nr(prod, ts), sbit, np_tab);     // :123-126
 }
 
 // Check update of one row held in registers: q[D] -> put(j, R_j), j = 0 .. D - 1.  put takes message j as
@@ -123,7 +126,7 @@ QBP_HD void check_row(const double (&q)[D], unsigned sbit, double alpha, bool sc
             QBP_COLD_BEGIN();
 #pragma unroll
             for (int j = 0; j < D; ++j) {
-                const double r = sp_message<VARIANT>(prod, t[j], sbit, np_tab);
+                const double r = sp_message<VARIANT, true>(prod, t[j], sbit, np_tab);
                 put(j, (VARIANT == 1 && scale) ? r * alpha : r);
             }
             QBP_COLD_END();

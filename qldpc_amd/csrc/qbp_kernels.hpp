@@ -571,8 +571,10 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         if constexpr (ONE_BAR) {
             // iteration it - 1 of this syndrome satisfied it (its flag is complete since the barrier above):
             // its posterior values, still in val[], are the outputs (beliefPropagationGPU.py:160-167)
-            if (active && it > 0 && !frozen && flag0[f_prev * S + slot] == 0) {
-                emit_decode(val, true, it - 1);
+            // (every active slot is in iteration wg_it: the scalar stands for the per-slot `it`, which these builds
+            // do not keep)
+            if (active && wg_it > 0 && !frozen && flag0[f_prev * S + slot] == 0) {
+                emit_decode(val, true, wg_it - 1);
                 frozen = true;
             }
         }
@@ -669,7 +671,8 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             const bool conv = flag0[f_cur * S + slot] == 0;
             // (ONE_BAR: this block runs once per syndrome; reading the limit from the kernel-argument
             // segment here is also what tells tools/valu_mix.py so -- its rule for once-per-syndrome code)
-            const bool last = it == (ONE_BAR ? COLD(max_iter) : max_iter) - 1;
+            const int it_now = ONE_BAR ? wg_it : it;
+            const bool last = it_now == (ONE_BAR ? COLD(max_iter) : max_iter) - 1;
             // (BUDGETS: the end of budget bj is an emission too -- for row bj -- whether it is the last one or not)
             bool emit_now = conv || last;
             if constexpr (BUDGETS) emit_now = conv || it == ck_it;
@@ -766,7 +769,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                         }
                     }
                 } else {
-                    emit_decode(val, conv, it);
+                    emit_decode(val, conv, it_now);
                 }
             }
             if (conv) frozen = true;
@@ -797,8 +800,6 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 }
                 ++it;
             }
-        } else if (active) {
-            ++it;                                                 // (ONE_BAR, not the last iteration)
         }
         {   // next phase
             const int t = f_prev; f_prev = f_cur; f_cur = f_next; f_next = ONE_BAR ? t : f_prev;

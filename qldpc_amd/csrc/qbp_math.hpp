@@ -371,10 +371,25 @@ QBP_HD unsigned np_bfe(unsigned x)
 // replaced in place, so the zero low dword of the result costs no instruction.  The operand's exponent field
 // (times 2^20) and its top 16 mantissa bits are subtracted in one go -- a bit-field extract and an and-or form
 // E << 20 | m16 -- which is the same as subtracting the exponent after the mask: E << 20 has no bits below 16.
+// The entry's byte offset -- the top 5 mantissa bits times 8, bits 15-19 of the high dword moved to bits 3-7 --
+// comes out of the value shifted by 4 that the subtraction needs anyway: its byte 1 is bits 12-19 of the high
+// dword, and `and 0xf8` with a byte-1 source select is one instruction where shift and mask were two.
+QBP_HD unsigned np_lut_off(unsigned hi_shr4)
+{
+#ifdef QBP_DEVICE_BITS
+    unsigned r;
+    asm("v_and_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD"
+        : "=v"(r) : "v"(hi_shr4), "s"(0xf8u));
+    return r;
+#else
+    return (hi_shr4 >> 8) & 0xf8u;
+#endif
+}
 QBP_HD double np_rcp14(unsigned v_hi, NpT T)
 {
-    const double e = np_ld_f64(T, NP_OFF_LUT + ((v_hi >> 12) & 0xf8u));
-    const unsigned em16 = (v_hi & 0x7ff00000u) | np_bfe<4, 16>(v_hi);          // v_bfe + v_and_or
+    const unsigned m16 = np_bfe<4, 16>(v_hi);
+    const double e = np_ld_f64(T, NP_OFF_LUT + np_lut_off(m16));
+    const unsigned em16 = (v_hi & 0x7ff00000u) | m16;                          // v_bfe + v_and_or
     return np_from_hi_lo((np_hi(e) - em16) & 0xffff0000u, np_lo(e));
 }
 // its high dword (the low one is 0)
@@ -384,8 +399,12 @@ QBP_HD unsigned np_rcp14_hi(unsigned v_hi, NpT T) { return np_hi(np_rcp14(v_hi, 
 // second table
 QBP_HD double np_rcp14_12(unsigned p_hi, NpT T)
 {
-    const double e = np_ld_f64(T, NP_OFF_LUT_P + ((p_hi >> 12) & 0xf8u));
-    return np_from_hi_lo((np_hi(e) - (p_hi >> 4)) & 0xffff0000u, np_lo(e));
+    unsigned s4 = p_hi >> 4;
+#ifdef QBP_DEVICE_BITS
+    asm("" : "+v"(s4));       // (one shift for both uses: the compiler would otherwise shift by 12 for the offset)
+#endif
+    const double e = np_ld_f64(T, NP_OFF_LUT_P + np_lut_off(s4));
+    return np_from_hi_lo((np_hi(e) - s4) & 0xffff0000u, np_lo(e));
 }
 
 // Byte offset of the log-table pair of R from its high dword: bits 16-19 (the top four mantissa bits) times 16.

@@ -130,8 +130,9 @@ def demangle(sym):
     return sym
 
 
-def loop_mix(insts):
-    """VALU instructions per execution of the main loop's always-executed part, by class."""
+def loop_mix(insts, counted=None):
+    """VALU instructions per execution of the main loop's always-executed part, by class.
+    counted: a list that receives (address, mnemonic, class) of every instruction counted (tools/valu_by_line.py)."""
     # the main loop: the phase loop of the kernel is the one that synchronises -- of all backward branches whose
     # span contains a workgroup barrier (inner loops -- sampling, emission, rare paths -- hold none), the one
     # whose span holds the most FP64 arithmetic, among equals the tightest (the compiler rotates the phase loop
@@ -195,6 +196,8 @@ def loop_mix(insts):
         if c:
             mix[c] += 1
             mnems[m] += 1
+            if counted is not None:
+                counted.append((a, m, c))
         elif m.startswith("ds_"):
             other["lds"] += 1
         elif m.startswith("s_barrier"):
