@@ -129,12 +129,38 @@ void qbp_destroy(qbp_handle* h);
  * (used by the CPU test-suite).  info[8] = {kernel kind (1 on-chip, 2 general-H), DC, DV, max row
  * weight, max column weight, isolated variables, padded (0/1), LDS bytes of one slot}.  When the
  * on-chip kernel applies, the optional outputs receive its tables: tab_var [DC][m] (variable of
- * edge j of check c, -1 = padding), tab_nbr [DC][DV][m] (LDS word offsets j'*m + c' of the column
- * of that variable in ascending check order, DC*m = the zero word), tab_writer [m] (bit j: edge
+ * edge j of check c, -1 = padding), tab_nbr [DC][DV][m] (the column of that variable as edges j'*m + c'
+ * in ascending check order, DC*m = no edge; a description of the columns -- where the kernel keeps their
+ * messages: qbp_plan_r_layout), tab_writer [m] (bit j: edge
  * (c, j) is the first of its column).
  */
 int qbp_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, int32_t info[8],
              int32_t* tab_var, uint16_t* tab_nbr, uint32_t* tab_writer);
+
+/*
+ * Host-only: where the on-chip kernel keeps the check->variable messages of a matrix in LDS when a workgroup
+ * decodes S syndromes at once (col_order as in qbp_column_order).
+ *   - A slot holds one record of DV doubles per variable that has a check.
+ *   - A record holds the messages of the variable's column, adjacent and in summation order; its other words
+ *     are 0.0 and may stand in front of the messages or behind them.
+ *   - Message words of different records never overlap.  Zero words may: a record can begin on the trailing
+ *     zeros of the record before it.
+ *   - Behind the last slot follow, once per workgroup, an all-zero record and one dump word (written, never read).
+ * Outputs (optional), both [DC][m] and relative to the slot, in doubles:
+ *   tab_gather  the record of the variable of edge j of check c;
+ *   tab_store   that edge's own word inside the record.
+ *   A padding edge has info[1] and info[1] + DV: the zero record and the dump word, which the kernel takes
+ *   relative to the LAST slot.
+ * info[8]:
+ *   [0] DV                                   [1] doubles per slot
+ *   [2] doubles of one copy of the messages  [3] LDS bytes of a workgroup with one copy (0: S slots do not fit)
+ *   [4] LDS bytes with the two copies of the one-barrier forced kernel (0: no such launch at this S)
+ *   [5] byte offset of the second copy from the first
+ *   [6] byte offset of the first copy in the workgroup's LDS   [7] 0
+ * QBP_E_UNSUPPORTED when the matrix does not run on the on-chip kernel.
+ */
+int qbp_plan_r_layout(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, int32_t col_order,
+                      int32_t S, int32_t info[8], uint16_t* tab_gather, uint16_t* tab_store);
 
 /*
  * Host-only: the order in which the kernels add up the check->variable messages of every column

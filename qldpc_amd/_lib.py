@@ -58,6 +58,7 @@ SIGNATURES = {
     "qbp_create": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_VP)]),
     "qbp_destroy": (None, [_VP]),
     "qbp_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
+    "qbp_plan_r_layout": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP]),
     "qbp_column_order": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP]),
     "qbp_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double,
                                    C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP, _VP]),
@@ -239,9 +240,11 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name, None)
-            if fn is None and name.startswith("qbp_window_") and LIB_PATH != _DEFAULT_LIB_PATH:
+            if (fn is None and (name.startswith("qbp_window_") or name == "qbp_plan_r_layout")
+                    and LIB_PATH != _DEFAULT_LIB_PATH):
                 # a QBP_LIB_PATH build from before sliding-window decoding (tools/bench_window.py times its
-                # whole-matrix path): everything else works, a window call raises QbpError
+                # whole-matrix path) or from before the variable-major message layout (A/B runs against it):
+                # everything else works, such a call raises QbpError
                 setattr(lib, name, _missing(name))
                 continue
             if fn is None:

@@ -265,11 +265,12 @@ struct qbp_handle {
     int num_cu = 0;
     bool fused_ok = false;
     int dc = DC_SMALL, dv = DV_SMALL;   // instantiation used by this matrix
+    int r_stride = 0;                   // on-chip kernel: doubles of one slot's message records (HostTables)
     bool padded = false;
     std::vector<int32_t> row_ptr, col_idx;
     // device tables for the fused kernel
     DevBuf<int32_t> d_tab_var;
-    DevBuf<uint16_t> d_tab_nbr;
+    DevBuf<uint16_t> d_tab_gather, d_tab_store;
     DevBuf<uint32_t> d_tab_writer;
     DevBuf<int32_t> d_iso;
     int n_iso = 0;
@@ -343,7 +344,7 @@ struct qbp_handle {
     // (QBP_FLAG_DENSE_F_COLSUM; built at the first such call)
     struct ColumnOrderTables {
         int state = 0;               // 0 not built, 1 ready, -1 not expressible (QBP_E_UNSUPPORTED)
-        DevBuf<uint16_t> tab_nbr;
+        DevBuf<uint16_t> tab_gather, tab_store;
         DevBuf<uint32_t> tab_writer;
         DevBuf<int32_t> col_edge, sedge, vpos, vrow;
     } f_order;
@@ -388,13 +389,13 @@ using qbp::LaunchCfg;
 // slot_counters: counter ints per slot (2 * n_budgets rows in the launches of qbp_mc_run_budgets)
 // hist_words: bins of the workgroup's iteration histogram in the launches of qbp_mc_run_spectrum (max_iter + 1; with
 // them a residual-weight word per slot), else 0
-size_t fused_lds_bytes(int dc, int m, int n, int S, bool two_copies = false, bool r0_table = false,
+size_t fused_lds_bytes(int dc, int m, int n, int S, int r_stride, bool two_copies = false, bool r0_table = false,
                        int slot_counters = qbp::NUM_COUNTERS, int hist_words = 0)
 {
-    const size_t slot_stride = (size_t)dc * m + 2;
+    const size_t r_doubles = qbp::fused_r_doubles(r_stride, dc == DC_SMALL ? DV_SMALL : DV_WIDE, S);   // one copy of R
     size_t lds = (size_t)qbp::NP_LDS_BYTES +      // tables of tanh / arctanh (qbp_math.hpp), at the start
                  (two_copies ? (size_t)qbp::FUSED_R2_OFF_BYTES : 0) + (r0_table ? (size_t)2 * dc * m * 8 : 0) +
-                 ((size_t)S * slot_stride + (size_t)dc * m + 3 * (size_t)S) * 8 +
+                 (r_doubles + (size_t)dc * m + 3 * (size_t)S) * 8 +
                  (6 * (size_t)S + 1 + (size_t)S * (size_t)slot_counters + (size_t)dc * m) * 4 +
                  2 * (size_t)S * (((size_t)n + 3) / 4) * 4 +    // err_lds[2][S][n4] (Monte-Carlo builds)
                  (hist_words ? ((size_t)S + (size_t)hist_words) * 4 : 0);
@@ -407,7 +408,10 @@ struct HostTables {
     int max_row = 0, max_col = 0, dc = DC_SMALL, dv = DV_SMALL;
     bool fused_ok = false, padded = false;
     std::vector<int32_t> tab_var;      // [dc][m]
-    std::vector<uint16_t> tab_nbr;     // [dc][dv][m]
+    std::vector<uint16_t> tab_nbr;     // [dc][dv][m]  the columns as edge lists: filled for qbp_plan only (no kernel reads it)
+    std::vector<uint16_t> tab_gather;  // [dc][m]      the R records of the on-chip kernel (qbp_kernels.hpp)
+    std::vector<uint16_t> tab_store;   // [dc][m]
+    int r_stride = 0;                  // doubles of one slot's records
     std::vector<uint32_t> tab_writer;  // [m]
     std::vector<int32_t> iso, col_ptr, col_edge;
     // streaming kernel: checks / variables sorted by weight class (qbp_stream.hpp)
@@ -488,7 +492,8 @@ static bool dense_f_column_order(const std::vector<int>& rows, int m, std::vecto
 // col_order: 0 = every column's entries in ascending check order (np.sum(R, axis=0) of a C-ordered R adds row
 // by row); 1 = the order of a Fortran-ordered R (dense_f_column_order).  All kernels add a column's messages
 // left to right in the order of these tables.
-int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, HostTables& T, int col_order = 0)
+int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, HostTables& T, int col_order = 0,
+                 bool with_nbr = false)
 {
     if (!row_ptr || m < 0 || n < 0) return fail(QBP_E_INVALID, "bad matrix arguments");
     if (m == 0 || n == 0) return fail(QBP_E_INVALID, "empty matrix (%d x %d)", m, n);
@@ -529,13 +534,34 @@ int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, H
     }
     if (T.max_row <= DC_SMALL && T.max_col <= DV_SMALL) { T.dc = DC_SMALL; T.dv = DV_SMALL; }
     else { T.dc = DC_WIDE; T.dv = DV_WIDE; }
+    // R records of the on-chip kernel (layout and invariant: qbp_kernels.hpp, fused_r_doubles).  A column of d < DV
+    // checks has DV - d zero words to place: as many as the record before left free at its end go in front, where
+    // the two records then overlap; the rest go behind.  DV = 3: columns of degree 1 take two words on average, of
+    // degree 2 two and a half, of degree 3 three.
+    std::vector<int> rec_base((size_t)n, 0), rec_lead((size_t)n, 0);
+    if (T.max_col <= T.dv) {
+        int words = 0, tail = 0;
+        for (int v = 0; v < n; ++v) {
+            const int d = (int)cols[v].size();
+            if (d == 0) continue;
+            const int lead = std::min(tail, T.dv - d);
+            rec_base[v] = words - lead;
+            rec_lead[v] = lead;
+            words = rec_base[v] + T.dv;
+            tail = T.dv - d - lead;
+        }
+        T.r_stride = words;
+    }
     T.fused_ok = (m <= qbp::FUSED_MAX_THREADS) && T.max_row <= T.dc && T.max_col <= T.dv &&
-                 fused_lds_bytes(T.dc, m, n, 1) <= 160 * 1024;
+                 fused_lds_bytes(T.dc, m, n, 1, T.r_stride) <= 160 * 1024;
     if (T.fused_ok) {
         const int DC = T.dc, DV = T.dv, zoff = DC * m;
         T.tab_var.assign((size_t)DC * m, -1);
-        T.tab_nbr.assign((size_t)DC * DV * m, (uint16_t)zoff);
+        if (with_nbr) T.tab_nbr.assign((size_t)DC * DV * m, (uint16_t)zoff);
         T.tab_writer.assign(m, 0u);
+        // padding edges gather the zero record (r_stride) and store to the dump word behind it
+        T.tab_gather.assign((size_t)DC * m, (uint16_t)T.r_stride);
+        T.tab_store.assign((size_t)DC * m, (uint16_t)(T.r_stride + DV));
         for (int c = 0; c < m; ++c) {
             const int deg = row_ptr[c + 1] - row_ptr[c];
             if (deg < DC) T.padded = true;
@@ -543,8 +569,11 @@ int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, H
                 const int v = col_idx[row_ptr[c] + j];
                 T.tab_var[(size_t)j * m + c] = v;
                 const auto& col = cols[v];
-                for (size_t k = 0; k < col.size(); ++k)
-                    T.tab_nbr[((size_t)j * DV + k) * m + c] = (uint16_t)(col[k].second * m + col[k].first);
+                T.tab_gather[(size_t)j * m + c] = (uint16_t)rec_base[v];
+                for (size_t k = 0; k < col.size(); ++k) {
+                    if (with_nbr) T.tab_nbr[((size_t)j * DV + k) * m + c] = (uint16_t)(col[k].second * m + col[k].first);
+                    if (col[k].first == c) T.tab_store[(size_t)j * m + c] = (uint16_t)(rec_base[v] + rec_lead[v] + (int)k);
+                }
                 if (col[0].first == c) T.tab_writer[c] |= 1u << j;     // (one lane per variable writes its outputs)
             }
         }
@@ -645,7 +674,7 @@ int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bo
     const int m = h->m;
     const int slot_counters = n_budgets > 0 ? 2 * n_budgets * qbp::NUM_COUNTERS : qbp::NUM_COUNTERS;
     auto lds_bytes = [&](int dc, int m_, int n_, int S_, bool two_copies = false, bool r0_table = false) {
-        return fused_lds_bytes(dc, m_, n_, S_, two_copies, r0_table, slot_counters, hist_words);
+        return fused_lds_bytes(dc, m_, n_, S_, h->r_stride, two_copies, r0_table, slot_counters, hist_words);
     };
     int S = h->opt_slots;
     if (S <= 0) {
@@ -667,12 +696,12 @@ int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bo
     S = std::min(S, std::max(1, qbp::FUSED_MAX_THREADS / std::max(m, 1)));
     if ((long long)S > B) S = (int)std::max<long long>(B, 1);
     cfg->dc = h->dc;
-    cfg->slot_stride = h->dc * m + 2;
+    cfg->slot_stride = h->r_stride;
     while (S > 1 && lds_bytes(h->dc, m, h->n, S) > 160 * 1024) --S;   // LDS-limited shapes
     // forced-iteration decode: the one-barrier kernel when two copies of the messages fit (the first one
     // below the constant offset of the second) without giving up a slot
     const bool two = forced && !mc && !h->opt_forced_two_barriers && h->dc == DC_SMALL &&
-                     (size_t)S * cfg->slot_stride * 8 <= (size_t)qbp::FUSED_R2_OFF_BYTES &&
+                     qbp::fused_r_doubles(h->r_stride, h->dv, S) * 8 <= (size_t)qbp::FUSED_R2_OFF_BYTES &&
                      lds_bytes(h->dc, m, h->n, S, true) <= 160 * 1024;
     cfg->one_barrier = two ? 1 : 0;
     h->last_one_barrier = cfg->one_barrier;
@@ -765,7 +794,8 @@ int resolve_column_order(qbp_handle* h, unsigned& flags, const double* host_prio
         if (rc == QBP_E_UNSUPPORTED) { F.state = -1; return rc; }
         if (rc) return rc;
         if (T.fused_ok) {
-            HIP_TRY(F.tab_nbr.upload(T.tab_nbr));
+            HIP_TRY(F.tab_gather.upload(T.tab_gather));
+            HIP_TRY(F.tab_store.upload(T.tab_store));
             HIP_TRY(F.tab_writer.upload(T.tab_writer));
         }
         HIP_TRY(F.col_edge.upload(T.col_edge));
@@ -1062,7 +1092,7 @@ try {
     h->col_idx.assign(col_idx, col_idx + E);
     h->max_row_deg = T.max_row;
     h->max_col_deg = T.max_col;
-    h->dc = T.dc; h->dv = T.dv; h->fused_ok = T.fused_ok; h->padded = T.padded;
+    h->dc = T.dc; h->dv = T.dv; h->fused_ok = T.fused_ok; h->padded = T.padded; h->r_stride = T.r_stride;
     h->n_iso = (int)T.iso.size();
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -1070,7 +1100,8 @@ try {
 
     if (T.fused_ok) {
         HIP_TRY(h->d_tab_var.upload(T.tab_var));
-        HIP_TRY(h->d_tab_nbr.upload(T.tab_nbr));
+        HIP_TRY(h->d_tab_gather.upload(T.tab_gather));
+        HIP_TRY(h->d_tab_store.upload(T.tab_store));
         HIP_TRY(h->d_tab_writer.upload(T.tab_writer));
     }
     HIP_TRY(h->d_iso.upload(T.iso));
@@ -1132,18 +1163,41 @@ int qbp_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t 
              int32_t* tab_var, uint16_t* tab_nbr, uint32_t* tab_writer)
 try {
     HostTables T;
-    int rc = build_tables(row_ptr, col_idx, m, n, T);
+    int rc = build_tables(row_ptr, col_idx, m, n, T, 0, tab_nbr != nullptr);
     if (rc) return rc;
     if (info) {
         info[0] = T.fused_ok ? 1 : 2; info[1] = T.dc; info[2] = T.dv; info[3] = T.max_row;
         info[4] = T.max_col; info[5] = (int32_t)T.iso.size(); info[6] = T.padded ? 1 : 0;
-        info[7] = T.fused_ok ? (int32_t)fused_lds_bytes(T.dc, m, n, 1) : 0;
+        info[7] = T.fused_ok ? (int32_t)fused_lds_bytes(T.dc, m, n, 1, T.r_stride) : 0;
     }
     if (T.fused_ok) {
         if (tab_var) std::memcpy(tab_var, T.tab_var.data(), T.tab_var.size() * sizeof(int32_t));
         if (tab_nbr) std::memcpy(tab_nbr, T.tab_nbr.data(), T.tab_nbr.size() * sizeof(uint16_t));
         if (tab_writer) std::memcpy(tab_writer, T.tab_writer.data(), T.tab_writer.size() * sizeof(uint32_t));
     }
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_plan_r_layout(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, int32_t col_order,
+                      int32_t S, int32_t info[8], uint16_t* tab_gather, uint16_t* tab_store)
+try {
+    HostTables T;
+    int rc = build_tables(row_ptr, col_idx, m, n, T, col_order);
+    if (rc) return rc;
+    if (!T.fused_ok) return fail(QBP_E_UNSUPPORTED, "the matrix does not run on the on-chip kernel");
+    if (S < 1 || (long long)S * m > qbp::FUSED_MAX_THREADS)
+        return fail(QBP_E_INVALID, "S = %d slots of %d checks are not a workgroup", S, m);
+    if (info) {
+        const size_t one = fused_lds_bytes(T.dc, m, n, S, T.r_stride), two = fused_lds_bytes(T.dc, m, n, S, T.r_stride, true);
+        const size_t copy = qbp::fused_r_doubles(T.r_stride, T.dv, S);
+        info[0] = T.dv; info[1] = T.r_stride; info[2] = (int32_t)copy;
+        info[3] = one <= 160 * 1024 ? (int32_t)one : 0;
+        info[4] = T.dc == DC_SMALL && copy * 8 <= (size_t)qbp::FUSED_R2_OFF_BYTES && two <= 160 * 1024 ? (int32_t)two : 0;
+        info[5] = qbp::FUSED_R2_OFF_BYTES; info[6] = qbp::NP_LDS_BYTES; info[7] = 0;
+    }
+    if (tab_gather) std::memcpy(tab_gather, T.tab_gather.data(), T.tab_gather.size() * sizeof(uint16_t));
+    if (tab_store) std::memcpy(tab_store, T.tab_store.data(), T.tab_store.size() * sizeof(uint16_t));
     return QBP_OK;
 }
 QBP_ABI_CATCH
@@ -1225,7 +1279,8 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     P.padded = h->padded ? 1 : 0;
     P.n_words4 = (h->n + 3) / 4;
     P.tab_var = h->d_tab_var.p;
-    P.tab_nbr = f_order ? h->f_order.tab_nbr.p : h->d_tab_nbr.p;
+    P.tab_gather = f_order ? h->f_order.tab_gather.p : h->d_tab_gather.p;
+    P.tab_store = f_order ? h->f_order.tab_store.p : h->d_tab_store.p;
     P.tab_writer = f_order ? h->f_order.tab_writer.p : h->d_tab_writer.p;
     P.iso_vars = h->d_iso.p; P.n_iso = h->n_iso;
     P.work_counter = h->d_work_counter.p;
@@ -2666,10 +2721,10 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     b.mc = &mc;
     // (a ladder's counter rows need LDS of their own: a matrix that fills the on-chip kernel's to the last
     // kilobyte goes to the general-H kernel)
-    const bool ladder_fits = !ladder || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false,
+    const bool ladder_fits = !ladder || fused_lds_bytes(h->dc, h->m, h->n, 1, h->r_stride, false, false,
                                                         2 * c.n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
     // (likewise the iteration histogram of qbp_mc_run_spectrum)
-    const bool hist_fits = !spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, false, false, qbp::NUM_COUNTERS,
+    const bool hist_fits = !spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, h->r_stride, false, false, qbp::NUM_COUNTERS,
                                                         max_iter + 1) <= 160 * 1024;
     if (layered) {
         b.flags = 0;                 // (forced iterations cannot change a count: the kernel's Monte-Carlo build exits early)

@@ -3,8 +3,9 @@
 // One lane per CHECK node.  A workgroup decodes S syndromes concurrently ("slots"); slot s owns
 // lanes [s*m, (s+1)*m).  A lane keeps its check's d_c variable->check messages Q in registers
 // for the whole decode; the only data exchanged between lanes are the check->variable messages
-// R, one double per edge, staged in LDS ([slot][edge j of the row][check c]: consecutive lanes
-// write consecutive addresses).  Per BP iteration a lane
+// R, one double per edge, staged in LDS, variable-major: [slot][variable v][k], k the position of the
+// check in v's column (ascending check order), so the DV messages of a variable are one contiguous
+// record and a lane needs one gather address and one store address per edge.  Per BP iteration a lane
 //   1. check step:   t_j = tanh(Q_j/2); row product; R_j = 2 atanh(clip(prod / t_j * sign))
 //                    -> ds_write R_j                          (beliefPropagation.py:114-126)
 //   2. barrier
@@ -21,8 +22,9 @@
 // immediately starts the next one, independent of its neighbours.
 //
 // Irregular rows/columns are padded: a missing edge has prior = +inf (its Q stays +inf, its tanh
-// is exactly 1.0, its hard bit 0), a missing column entry points at a per-slot LDS word that
-// holds 0.0 (x + 0.0 is exact) -- the kernel body has no degree-dependent branches.
+// is exactly 1.0, its hard bit 0) and gathers from an all-zero record behind the last slot; the words
+// a column with fewer than DV checks leaves free in its record hold 0.0 (x + 0.0 is exact) -- the
+// kernel body has no degree-dependent branches.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -68,8 +70,25 @@ namespace qbp {
 // Forced-iteration launches with ONE workgroup barrier per iteration keep two copies of the
 // check->variable messages in LDS; the second copy sits at this constant byte distance from the first
 // (a constant, so that the toggle costs nothing: it lands in the offset field of the ds instructions of a
-// loop unrolled by two).  The first copy, S * slot_stride doubles, must fit below it.
+// loop unrolled by two).  The first copy, fused_r_doubles() doubles, must fit below it.
 constexpr int FUSED_R2_OFF_BYTES = 57344;
+
+// One copy of R in LDS:
+//   [S][slot_stride]  the slots' records, laid out by the host (build_tables);
+//   [DV]              one all-zero record, which every padding edge gathers;
+//   [1]               one dump word, which every padding edge stores to and nobody reads.
+// A record is the DV consecutive words an edge gathers for its variable: the messages of the variable's column,
+// adjacent and in summation order, and zeros in the words left over.
+// INVARIANT: the message words of different records are disjoint; their zero words need not be.  A column with
+// fewer than DV checks may have its zeros in front of its messages (a zero adds nothing wherever it stands in the
+// left-to-right sum), and then shares them with the trailing zeros of the record before.  Zero words are written
+// once per launch and by no edge.
+// Why no 16-byte-aligned records for ds_read_b128: DV = 3 records padded to 32 bytes do not fit twice below
+// FUSED_R2_OFF_BYTES for [[288,12,18]]; DV = 4 records of 32 bytes put the 864 x 2592 space-time matrix of
+// [[144,12,12]] (column weights 3 and 2) past 160 KiB.
+// The tables address the zero record and the dump word relative to the slot, as slot_stride and slot_stride + DV;
+// the kernel moves those two behind the last slot ("per-lane static tables").
+constexpr size_t fused_r_doubles(int slot_stride, int dv, int S) { return (size_t)S * (size_t)slot_stride + dv + 1; }
 
 struct FusedParams {
     // problem
@@ -78,7 +97,7 @@ struct FusedParams {
     long long B;                // syndromes / trials in this launch
     int m, n;
     int S;                      // slots per workgroup
-    int slot_stride;            // doubles per slot in LDS (DC*m + 2)
+    int slot_stride;            // doubles per slot in LDS (the records of the variables)
     int max_iter;
     unsigned flags;
     int padded;                 // some row has fewer than DC edges (irregular H)
@@ -92,7 +111,8 @@ struct FusedParams {
     double* llr;
     // static tables of the code
     const int32_t* tab_var;     // [DC][m]   variable of edge j of check c, -1 = padding
-    const uint16_t* tab_nbr;    // [DC][DV][m] LDS word offsets of the column of that variable
+    const uint16_t* tab_gather; // [DC][m]   slot-relative word offset of the record of that variable (padding: slot_stride)
+    const uint16_t* tab_store;  // [DC][m]   ... of this edge's own word in it (padding: slot_stride + DV)
     const uint32_t* tab_writer; // [m] bit j: edge (c, j) is the first of its column
     const int32_t* iso_vars;    // variables with no check
     int n_iso;
@@ -228,11 +248,11 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     const bool leader = lane_valid && c == 0;
     const int sl = lane_valid ? slot : 0;
 
-    double* const Rs = smem + (size_t)sl * P.slot_stride;
-    const int zoff = DC * m;
+    const int stride = P.slot_stride;
+    const int r_doubles = S * stride + DV + 1;      // one copy of R (fused_r_doubles)
     // priors of this check's variables, [edge j][check c], shared by all slots (an LDS read per
     // use instead of 12 VGPRs per lane for the whole kernel)
-    double* const pri_lds = smem + (ONE_BAR ? FUSED_R2_OFF_BYTES / 8 : 0) + (size_t)S * P.slot_stride;
+    double* const pri_lds = smem + (ONE_BAR ? FUSED_R2_OFF_BYTES / 8 : 0) + r_doubles;
     // Early-exit launches: the check->variable messages of a syndrome's FIRST check step, which depend
     // on nothing but the priors and the check's syndrome bit -- r0_lds[bit][edge j][check c], computed once
     // per workgroup by the kernel's own check-step code (same bits).  At low error rates most syndromes
@@ -279,13 +299,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     };
 
     // ---- per-lane static tables (registers for the whole kernel) ---------------------------
-    // LDS word offsets of the columns of this check's variables.  The (6, 3) shape keeps one register
-    // per offset; the (8, 4) shape and the Monte-Carlo builds pack two 16-bit offsets per register
-    // (half the registers, one extra shift/mask per gather) -- their register budget is what limits them.
+    // Per edge, the word offsets (in a copy of R) of the record of its variable and of the edge's own word in
+    // that record: one register each, or (PACK_NBR) both as 16-bit halves of one register -- half the registers,
+    // one extra shift/mask per use.  A padding edge, whose table entries lie past the slot's records, gets the
+    // workgroup's zero record and dump word behind the last slot.
     constexpr bool PACK_NBR = (DC > 6 && QBP_WIDE_PACK != 0) || (MC && QBP_MC_PACK != 0) ||
                               (DC <= 6 && !MC && QBP_SMALL_PACK != 0);
-    constexpr int NBR_W = PACK_NBR ? (DV + 1) / 2 : DV;
-    unsigned nbr[DC][NBR_W];
+    unsigned gat[DC];              // (PACK_NBR: gather | store << 16)
+    unsigned sto[PACK_NBR ? 1 : DC];
     unsigned wmask = 0;
     unsigned vmask = 0;            // bit j: edge j of this check exists (not padding)
 #pragma unroll
@@ -296,17 +317,38 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
             pri_lds[j * m + c] = v >= 0 ? P.prior[v] : __builtin_inf();
             var_lds[j * m + c] = v;
         }
-#pragma unroll
-        for (int k = 0; k < DV; ++k)
-        {
-            const unsigned o = lane_valid ? P.tab_nbr[(j * DV + k) * m + c] : (unsigned)zoff;
-            if constexpr (PACK_NBR) {
-                if (k & 1) nbr[j][k / 2] |= o << 16; else nbr[j][k / 2] = o;
-            } else {
-                nbr[j][k] = o;      // (the compiler keeps the 18 byte addresses in registers)
-            }
+        unsigned og = lane_valid ? P.tab_gather[j * m + c] : (unsigned)stride;
+        unsigned os = lane_valid ? P.tab_store[j * m + c] : (unsigned)(stride + DV);
+        og += (unsigned)((og < (unsigned)stride ? sl : S - 1) * stride);
+        os += (unsigned)((os < (unsigned)stride ? sl : S - 1) * stride);
+        if constexpr (PACK_NBR) {
+            gat[j] = og | (os << 16);
+        } else {
+            gat[j] = og;            // (the compiler keeps the 12 byte addresses in registers)
+            sto[j] = os;
         }
     }
+    // word offsets of edge j: its variable's record, its own word
+    auto rec_of = [&](int j) -> unsigned {
+        if constexpr (PACK_NBR) {
+            // (opaque: otherwise the unpacked byte addresses are hoisted out of the iteration loop --
+            // loop-invariant -- and spilled to scratch)
+            unsigned pk = gat[j];
+            asm volatile("" : "+v"(pk));
+            return pk & 0xffffu;
+        } else {
+            return gat[j];
+        }
+    };
+    auto own_of = [&](int j) -> unsigned {
+        if constexpr (PACK_NBR) {
+            unsigned pk = gat[j];
+            asm volatile("" : "+v"(pk));
+            return pk >> 16;
+        } else {
+            return sto[j];
+        }
+    };
     if (lane_valid) wmask = P.tab_writer[c];
     if (lds_address(smem_all) != np_tab) __builtin_trap();
     np_tables_to_lds(smem_all, tid, blockDim.x);
@@ -352,9 +394,13 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     long long b = lane_valid ? (long long)blockIdx.x * S + slot : B;
     bool active = b < B;
 
+    // the zero record, and the trailing words of the records of columns with fewer than DV checks, which nobody
+    // writes afterwards (both copies): published by the barrier before the loop
+    for (int i = tid; i < r_doubles; i += blockDim.x) {
+        smem[i] = 0.0;
+        if constexpr (ONE_BAR) smem[FUSED_R2_OFF_BYTES / 8 + i] = 0.0;
+    }
     if (leader) {
-        Rs[zoff] = 0.0;
-        if constexpr (ONE_BAR) Rs[FUSED_R2_OFF_BYTES / 8 + zoff] = 0.0;
         flag0[slot] = 0;
         flag0[S + slot] = 0;
         flag0[2 * S + slot] = 0;
@@ -387,11 +433,15 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     }
 
     // The lane's own check->variable messages are needed again in the variable step (Q = value - R):
-    // kept in registers across barrier B1, or re-read from LDS (a conflict-free ds_read per edge, no
-    // vector-ALU cost) to save 2 * DC registers.  Measured (profiles/r02_ab_wide_mc.txt): the
-    // Monte-Carlo builds are 6.6 % faster re-reading (their hot loop then runs without scratch
-    // accesses); the (8, 4) shape is 4 % faster holding them, although that build spills 19
-    // registers and the re-reading one none -- its iteration is not bound by those reloads.
+    // kept in registers across barrier B1, or re-read from LDS through the edge's store address (one
+    // ds_read_b64 per edge, no vector-ALU cost, but a scatter over the banks like the store) to save
+    // 2 * DC registers.  The defaults date from the check-major layout (profiles/r02_ab_wide_mc.txt:
+    // Monte-Carlo builds 6.6 % faster re-reading, the (8, 4) shape 4 % faster holding), where the re-read
+    // was conflict-free and the Monte-Carlo builds spilled.  On the variable-major layout
+    // (profiles/r20_ab_r_layout.txt): the headline decode build is 2.2 % faster holding; every leg with
+    // these defaults is at or above its check-major time; the (6, 3) Monte-Carlo builds, which no longer
+    // spill either way, measured 2.2 % faster HOLDING at p = 0.05 (0.9 % at p = 0.01, inside that leg's
+    // spread) -- QBP_MC_HOLD_R=1 is the candidate for the next change, not yet run through the suite.
     constexpr bool HOLD_R = MC ? (QBP_MC_HOLD_R != 0 && DC <= 6) : (DC <= 6 ? QBP_SMALL_HOLD_R != 0 : QBP_WIDE_HOLD_R != 0);
 
     // ---- per-syndrome state ---------------------------------------------------------------
@@ -515,7 +565,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
 
     auto phase_body = [&](auto par_tag) -> bool {
         constexpr int PAR = decltype(par_tag)::value;
-        double* const Rw = ONE_BAR ? Rs + PAR * (FUSED_R2_OFF_BYTES / 8) : Rs;     // this phase's copy of R
+        double* const Rw = ONE_BAR ? smem + PAR * (FUSED_R2_OFF_BYTES / 8) : smem;     // this phase's copy of R
         double val_phase[DC];     // (two-barrier builds: the values do not outlive the phase)
         double (&val)[DC] = ONE_BAR ? val_keep : val_phase;
         if constexpr (MC && !SHOTS) {
@@ -554,12 +604,12 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
 #pragma unroll
                 for (int j = 0; j < DC; ++j) {
                     const double r = r0[j * m + c];
-                    Rw[j * m + c] = r;
+                    Rw[own_of(j)] = r;
                     if constexpr (HOLD_R) R[j] = r;
                 }
             } else {
                 check_step(Q, sbit, [&](int j, double r) {
-                    Rw[j * m + c] = r;
+                    Rw[own_of(j)] = r;
                     if constexpr (HOLD_R) R[j] = r;
                 });
             }
@@ -581,8 +631,10 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
         if (active) {
             bool odd = sbit != 0;                                 // parity of the row vs syndrome
             // Issue the LDS gathers of a group of edges before the first add (one lgkmcnt wait per
-            // group instead of two per edge): all 18 for the (6, 3) shape, two edges (8 + 2 reads) at
-            // a time for the (8, 4) shape, whose register budget is the tighter constraint.
+            // group instead of two per edge): all 18 for the (6, 3) shape, QBP_WIDE_JG edges at a time
+            // for the (8, 4) shape, whose register budget is the tighter constraint.  An edge's DV reads
+            // go off one address with immediate offsets, as ds_read_b64: records are not 16-byte aligned
+            // (24 bytes for DV = 3; for DV = 4 they overlap on their zero words, see fused_r_doubles).
             constexpr int JG = (DC * DV <= 18) ? DC : QBP_WIDE_JG;
 #pragma unroll
             for (int j0 = 0; j0 < DC; j0 += JG) {
@@ -590,23 +642,17 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 double rown[HOLD_R ? 1 : JG];
 #pragma unroll
                 for (int jj = 0; jj < JG; ++jj) {
+                    if (j0 + jj < DC) {
+                        const double* const rec = Rw + rec_of(j0 + jj);
+                        // (volatile: neighbouring words would otherwise be fetched by one ds_read2_b64,
+                        // which needs an address add of its own -- its offsets are too short for the second
+                        // copy -- and moves half the bytes per LDS cycle of ds_read_b64)
+                        const volatile __attribute__((address_space(3))) double* const rv =
+                            (const volatile __attribute__((address_space(3))) double*)rec;
 #pragma unroll
-                    for (int k = 0; k < DV; ++k)
-                        if (j0 + jj < DC) {
-                            if constexpr (PACK_NBR) {
-                                unsigned o;
-                                // (opaque: otherwise the 32 unpacked byte addresses are hoisted out
-                                // of the iteration loop -- loop-invariant -- and spilled to scratch)
-                                unsigned pk = nbr[j0 + jj][k / 2];
-                                asm volatile("" : "+v"(pk));
-                                o = (k & 1) ? pk >> 16 : pk & 0xffffu;
-                                rr[jj][k] = Rw[o];
-                            } else {
-                                rr[jj][k] = Rw[nbr[j0 + jj][k]];
-                            }
-                        }
-                    if constexpr (!HOLD_R)
-                        if (j0 + jj < DC) rown[jj] = Rw[(j0 + jj) * m + c];
+                        for (int k = 0; k < DV; ++k) rr[jj][k] = rv[k];
+                        if constexpr (!HOLD_R) rown[jj] = Rw[own_of(j0 + jj)];
+                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
