@@ -40,6 +40,20 @@ struct LaunchCfg {
     int r0_table;           // early-exit launch with the first check step's messages tabulated in LDS
 };
 
+// Before a launch with `lds` bytes of dynamic LDS: raise the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to it,
+// once per device and size.  lds_set: the call site's own `static thread_local size_t [64] = {0}`, one per kernel.
+inline hipError_t raise_dynamic_lds(const void* kernel, size_t lds, size_t (&lds_set)[64])
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (lds > 0 && (dev < 0 || dev >= 64 || lds_set[dev] < lds)) {
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
+    }
+    return hipSuccess;
+}
+
 // qbp_tu_fused.hip
 hipError_t launch_fused(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
 hipError_t launch_fused_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);

@@ -4,7 +4,8 @@
 //
 // One wavefront per record, in the frame of osd0_kernel (qbp_osd.hpp): the bit-packed full-width rows of
 // [H | residual syndrome] in LDS in their original column indexing, lane l owning rows l, l + 64, ..., the bitonic sort of
-// (|llr| bits, column), the lowest unused row with a 1 as the pivot of a column.  Instead of one sweep over all
+// (|llr| bits, column), the lowest unused row with a 1 as the pivot of a column -- the same pieces of
+// qbp_osd_parts.hpp: order, load, the pivot of one column, solution and the record's tail.  Instead of one sweep over all
 // columns, rounds: every cluster that still holds an unexplained syndrome bit activates its g least reliable
 // neighbouring variables (all of them for g = 0), and the columns activated in a round are eliminated in ascending rank
 // on the same rows.  Rows are full width, so a column that becomes active late already carries every earlier row
@@ -65,7 +66,7 @@ __global__ __launch_bounds__(64) void lsd_kernel(const LsdParams P)
 {
     extern __shared__ double lsd_smem[];
     const int lane = threadIdx.x;
-    const int m = P.m, n = P.n, W = P.W, NP = P.NP, RS = W + 1, g = P.bits_per_step;
+    const int m = P.m, n = P.n, W = P.W, NP = P.NP, g = P.bits_per_step;
     char* const base0 = reinterpret_cast<char*>(lsd_smem);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(base0);
     uint32_t* A = reinterpret_cast<uint32_t*>(base0);                // (after the sort: same bytes)
@@ -82,45 +83,19 @@ __global__ __launch_bounds__(64) void lsd_kernel(const LsdParams P)
     const long long total = P.count_ptr ? *P.count_ptr : P.count;
     for (long long item = blockIdx.x; item < total; item += gridDim.x) {
         const long long rec = P.list ? P.list[item] : item;
-        const double* llr = P.llr + rec * n;
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
 
         // ---- 1. order = argsort(|llr|), ties by column index (osd0_kernel's sort); rank = its inverse
-        for (int i = lane; i < NP; i += 64) {
-            keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;      // padding sorts behind everything
-            idx[i] = (uint16_t)i;
-        }
+        osd_order_fill(P, rec, keys, idx, lane, 64);
         for (int i = lane; i < n; i += 64) { sol[i] = hard[i] & 1u; act[i] = 0; }
         __syncthreads();
-        for (int k = 2; k <= NP; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < NP / 2; t += 64) {
-                    const int lo = ((t / j) * (2 * j)) + (t % j);
-                    const int hi = lo + j;
-                    const bool up = (lo & k) == 0;
-                    const unsigned long long ka = keys[lo], kb = keys[hi];
-                    const int ia = idx[lo], ib = idx[hi];
-                    if (osd_less(kb, ib, ka, ia) == up) {
-                        keys[lo] = kb; keys[hi] = ka; idx[lo] = (uint16_t)ib; idx[hi] = (uint16_t)ia;
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        osd_sort(keys, idx, NP, lane, 64);
         for (int k = lane; k < n; k += 64) rnk[idx[k]] = (uint16_t)k;    // (the n real columns sort before the padding)
         // ---- 2. A = [H | residual syndrome]; the seeds are clusters of one check
         // (A overwrites the sort keys: every lane passed the sort's last barrier)
-        unsigned sb = 0;                             // bit i: reduced syndrome bit of row lane + 64 i
-        for (int r = lane, i = 0; r < m; r += 64, ++i) {
-            for (int w = 0; w < W; ++w) A[r * RS + w] = P.hbits[r * W + w];
-            unsigned par = syn[r] & 1u;
-            for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-            A[r * RS + W] = par;
-            sb |= par << i;
-            pivcol[r] = -1;
-            label[r] = par ? r : -1;
-        }
+        unsigned sb = osd_wave_load(P, syn, sol, A, pivcol, W, lane,       // bit i: reduced syndrome bit of row lane + 64 i
+                                    [&](int r, unsigned par) { label[r] = par ? r : -1; });
         __syncthreads();
         unsigned used = 0;                           // bit i: row lane + 64 i already serves as a pivot row
         int rounds = 0, nactive = 0;
@@ -215,26 +190,10 @@ __global__ __launch_bounds__(64) void lsd_kernel(const LsdParams P)
                 while (todo) {                       // (uniform)
                     const int c = __shfl(mine, (int)__builtin_ctzll(todo));
                     todo &= todo - 1ull;
-                    const int wi = c >> 5;
-                    const uint32_t bit = 1u << (c & 31);
-                    int p = -1;
-                    unsigned has = 0;                // bit i: row lane + 64 i has a 1 in column c
-                    for (int base = 0, i = 0; base < m; base += 64, ++i) {
-                        const int r = base + lane;
-                        const bool one = r < m && (A[r * RS + wi] & bit);
-                        has |= (one ? 1u : 0u) << i;
-                        const unsigned long long mask = __ballot(one && !((used >> i) & 1u));
-                        if (p < 0 && mask) p = base + (int)__builtin_ctzll(mask);
-                    }
+                    unsigned has;
+                    const int p = osd_wave_find(A, m, W, c, lane, used, has);
                     if (p < 0) continue;             // the column depends on earlier ones: it stays active, no pivot
-                    if (lane == (p & 63)) used |= 1u << (p >> 6);
-                    const unsigned ps = A[p * RS + W] & 1u;
-                    for (int r = lane, i = 0; r < m; r += 64, ++i) {
-                        if (r != p && ((has >> i) & 1u)) {
-                            for (int w = 0; w <= W; ++w) A[r * RS + w] ^= A[p * RS + w];
-                            sb ^= ps << i;
-                        }
-                    }
+                    osd_wave_eliminate<0>(A, m, W, p, has, lane, used, sb);
                     if (lane == 0) pivcol[p] = c;
                     __syncthreads();
                 }
@@ -246,11 +205,7 @@ __global__ __launch_bounds__(64) void lsd_kernel(const LsdParams P)
         // ---- 4. e[pivot column] = reduced syndrome bit; solution = hard + e; the statistics
         const bool valid = !__ballot((sb & ~used) != 0u);
         int clusters = 0;
-        for (int r = lane; r < m; r += 64) {
-            const int c = pivcol[r];
-            if (c >= 0 && (A[r * RS + W] & 1u)) sol[c] ^= 1u;       // distinct pivot columns: no race
-            clusters += label[r] == r;
-        }
+        osd_wave_solution(A, pivcol, sol, m, W, lane, [&](int r) { clusters += label[r] == r; });
         for (int off = 32; off > 0; off >>= 1) clusters += __shfl_xor(clusters, off);
         __syncthreads();
         if (P.solution)
@@ -258,46 +213,8 @@ __global__ __launch_bounds__(64) void lsd_kernel(const LsdParams P)
         if (P.stats && lane < 4)
             P.stats[rec * 4 + lane] = lane == 0 ? rounds : lane == 1 ? nactive : lane == 2 ? clusters : (int)valid;
 
-        if constexpr (RECORDS) {
-            // classification of the output, as osd0_kernel's (paperResults_GPU.py:127-144)
-            const uint8_t* err = P.errors + rec * n;
-            unsigned long long lm = 0ull;
-            int ew = 0;
-            unsigned df = 0;
-            for (int i = lane; i < n; i += 64) {
-                const unsigned e = err[i] & 1u;
-                const unsigned res = sol[i] ^ e;
-                ew += (int)e;
-                df |= res;
-                if (res) lm ^= P.lx_cols[i];
-            }
-            unsigned miss = 0;                       // (detection @ H.T) % 2 != syndrome: exactly the records with valid = 0
-            for (int r = lane; r < m; r += 64) {
-                unsigned par = syn[r] & 1u;
-                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-                miss |= par;
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                lm ^= __shfl_xor(lm, off);
-                ew += __shfl_xor(ew, off);
-                df |= __shfl_xor(df, off);
-                miss |= __shfl_xor(miss, off);
-            }
-            if (lane == 0) {
-                auto add = [&](int i) {
-                    atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
-                };
-                const bool logical = lm != 0ull;
-                if (!miss && !logical && df) add(5);
-                if (logical) {
-                    add(1);
-                    add(ew < P.half_distance ? 3 : 4);
-                    add(8);
-                }
-                if (!df) add(9);
-                if (miss) add(10);
-            }
-        }
+        // classification of the output, as osd0_kernel's (its `bad`: exactly the records with valid = 0)
+        if constexpr (RECORDS) osd_tail_wave(P, rec, sol, syn, lane);
         __syncthreads();
     }
 }

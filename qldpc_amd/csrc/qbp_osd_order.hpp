@@ -1,10 +1,10 @@
 // Order-w OSD on the GPU: the OSD-0 solution and a search over flip sets of the least reliable non-pivot
 // columns (combination sweep "CS" or exhaustive "E"); the spec is in include/qbp.h (qbp_osd_batch) and DESIGN §3b.
 //
-// One wavefront per record, as osd0_kernel, with the same OsdParams (Monte-Carlo records, redo list).  The sort
-// and the elimination are osd0_kernel's, except that the sweep runs to the rank of H: the search needs the
-// fully reduced matrix A, and its non-pivot columns T.  Kept apart from osd0_kernel (not shared helpers) so that
-// the OSD-0 kernel's code, registers and bits stay exactly what they were.
+// One wavefront per record, as osd0_kernel, with the same OsdParams (Monte-Carlo records, redo list).  The order, the
+// elimination and the record's tail are osd0_kernel's -- the same pieces of qbp_osd_parts.hpp -- except that the sweep
+// runs to the rank of H: the search needs the fully reduced matrix A, and its non-pivot columns T.  The search
+// (steps 5-8) is this kernel's own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -111,60 +111,17 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
 
-#if QBP_OSD_ORDERED
-        // ---- 1. order: the record's row of P.order, as osd0_kernel's ordered build (0xffff: no column)
-        (void)keys;
-        {
-            const int32_t* ord = P.order + rec * n;
-            for (int i = lane; i < NP; i += 64) {
-                const int c = i < n ? ord[i] : -1;
-                idx[i] = (uint16_t)(c >= 0 && c < n ? c : 0xffff);
-            }
-        }
+        // ---- 1. order: ascending (osd_order_key(llr), column), or the record's row of P.order
+        osd_order_fill(P, rec, keys, idx, lane, 64);
         for (int i = lane; i < n; i += 64) {
             sol[i] = hard[i] & 1u;
             absl[i] = __builtin_fabs(llr[i]);
             cinfo[i] = -1;
         }
         __syncthreads();
-#else
-        // ---- 1. order: ascending (osd_order_key(llr), column), as osd0_kernel
-        for (int i = lane; i < NP; i += 64) {
-            keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;
-            idx[i] = (uint16_t)i;
-        }
-        for (int i = lane; i < n; i += 64) {
-            sol[i] = hard[i] & 1u;
-            absl[i] = __builtin_fabs(llr[i]);
-            cinfo[i] = -1;
-        }
-        __syncthreads();
-        for (int k = 2; k <= NP; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = lane; t < NP / 2; t += 64) {
-                    const int lo = ((t / j) * (2 * j)) + (t % j);
-                    const int hi = lo + j;
-                    const bool up = (lo & k) == 0;
-                    const unsigned long long ka = keys[lo], kb = keys[hi];
-                    const int ia = idx[lo], ib = idx[hi];
-                    if (osd_less(kb, ib, ka, ia) == up) {
-                        keys[lo] = kb; keys[hi] = ka; idx[lo] = (uint16_t)ib; idx[hi] = (uint16_t)ia;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-#endif
+        osd_sort(keys, idx, NP, lane, 64);
         // ---- 2. A = [H | residual syndrome], residual = syndrome + hard @ H.T
-        unsigned sb = 0;                             // bit i: reduced syndrome bit of row lane + 64 i
-        for (int r = lane, i = 0; r < m; r += 64, ++i) {
-            for (int w = 0; w < W; ++w) A[r * RS + w] = P.hbits[r * W + w];
-            unsigned par = syn[r] & 1u;
-            for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-            A[r * RS + W] = par;
-            sb |= par << i;
-            pivcol[r] = -1;
-        }
+        unsigned sb = osd_wave_load(P, syn, sol, A, pivcol, W, lane);   // bit i: reduced syndrome bit of row lane + 64 i
         __syncthreads();
         // ---- 3. Gauss-Jordan in reliability order up to the rank of H (no early end: the search reads A)
         int rank = 0;
@@ -174,40 +131,11 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
 #if QBP_OSD_ORDERED
             if (c >= n) continue;                    // (uniform) not a column: skipped
 #endif
-            const int wi = c >> 5;
-            const uint32_t bit = 1u << (c & 31);
-            int p = -1;
-            unsigned has = 0;
-            for (int b0 = 0, i = 0; b0 < m; b0 += 64, ++i) {
-                const int r = b0 + lane;
-                const bool one = r < m && (A[r * RS + wi] & bit);
-                has |= (one ? 1u : 0u) << i;
-                const unsigned long long msk = __ballot(one && !((used >> i) & 1u));
-                if (p < 0 && msk) p = b0 + (int)__builtin_ctzll(msk);
-            }
+            unsigned has;
+            const int p = osd_wave_find(A, m, W, c, lane, used, has);
             if (p < 0) continue;
+            osd_wave_eliminate<WW>(A, m, W, p, has, lane, used, sb);
             ++rank;
-            if (lane == (p & 63)) used |= 1u << (p >> 6);
-            if constexpr (WW > 0) {
-                uint32_t prow[WW];
-#pragma unroll
-                for (int w = 0; w < WW; ++w) prow[w] = A[p * RS + w];
-                for (int r = lane, i = 0; r < m; r += 64, ++i) {
-                    if (r != p && ((has >> i) & 1u)) {
-#pragma unroll
-                        for (int w = 0; w < WW; ++w) A[r * RS + w] ^= prow[w];
-                        sb ^= (prow[WW - 1] & 1u) << i;
-                    }
-                }
-            } else {
-                const unsigned ps = A[p * RS + W] & 1u;
-                for (int r = lane, i = 0; r < m; r += 64, ++i) {
-                    if (r != p && ((has >> i) & 1u)) {
-                        for (int w = 0; w <= W; ++w) A[r * RS + w] ^= A[p * RS + w];
-                        sb ^= ps << i;
-                    }
-                }
-            }
             if (lane == 0) { pivcol[p] = c; cinfo[c] = p; }
             __syncthreads();
         }
@@ -215,10 +143,7 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         const bool inconsistent = __ballot((sb & ~used) != 0u) != 0ull;
         if (inconsistent && lane == 0) osd_flag_inconsistent(P, rec);
         // ---- 4. OSD-0: e[pivot column] = reduced syndrome bit
-        for (int r = lane; r < m; r += 64) {
-            const int c = pivcol[r];
-            if (c >= 0 && (A[r * RS + W] & 1u)) sol[c] ^= 1u;
-        }
+        osd_wave_solution(A, pivcol, sol, m, W, lane);
         __syncthreads();
         if (!inconsistent) {
             // ---- 5. T = non-pivot columns in sort order (ordered builds: in the given order); cinfo[T[t]] = ~t
@@ -307,80 +232,8 @@ __global__ __launch_bounds__(64) void osd_order_kernel(const OsdParams P, const 
         }
         if (P.solution)
             for (int i = lane; i < n; i += 64) P.solution[rec * n + i] = sol[i];
-
-#if QBP_OSD_SHOTS
-        if (!(inconsistent && P.redo != nullptr)) {      // (else: the row-swapping kernel's record)
-            unsigned long long lm = 0ull;
-            for (int i = lane; i < n; i += 64)
-                if (sol[i]) lm ^= P.lx_cols[i];
-            unsigned bad = 0;
-            for (int r = lane; r < m; r += 64) {
-                unsigned par = syn[r] & 1u;
-                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-                bad |= par;
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                lm ^= __shfl_xor(lm, off);
-                bad |= __shfl_xor(bad, off);
-            }
-            if (lane == 0) osd_shot_result(P, rec, lm, bad != 0u);
-        }
-#else
-        if (P.errors) {
-            // classification of the OSD output (paperResults_GPU.py:127-144), as osd0_kernel
-            const uint8_t* err = P.errors + rec * n;
-            unsigned long long lm = 0ull;
-            int ew = 0;
-            unsigned df = 0;
-#if QBP_OSD_SPECTRUM
-            int rw = 0;                              // weight of the residual
-#endif
-            for (int i = lane; i < n; i += 64) {
-                const unsigned e = err[i] & 1u;
-                const unsigned res = sol[i] ^ e;
-                ew += (int)e;
-                df |= res;
-#if QBP_OSD_SPECTRUM
-                rw += (int)res;
-#endif
-                if (res) lm ^= P.lx_cols[i];
-            }
-            unsigned bad = 0;
-            for (int r = lane; r < m; r += 64) {
-                unsigned par = syn[r] & 1u;
-                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-                bad |= par;
-            }
-            for (int off = 32; off > 0; off >>= 1) {
-                lm ^= __shfl_xor(lm, off);
-                ew += __shfl_xor(ew, off);
-                df |= __shfl_xor(df, off);
-                bad |= __shfl_xor(bad, off);
-#if QBP_OSD_SPECTRUM
-                rw += __shfl_xor(rw, off);
-#endif
-            }
-            if (lane == 0) {
-                auto add = [&](int i) {
-                    atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
-                };
-                const bool logical = lm != 0ull;
-#if QBP_OSD_SPECTRUM
-                if (rw)
-                    atomicAdd(reinterpret_cast<unsigned long long*>(
-                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + rw), 1ull);
-#endif
-                if (!bad && !logical && df) add(5);
-                if (logical) {
-                    add(1);
-                    add(ew < P.half_distance ? 3 : 4);
-                    add(8);
-                }
-                if (!df) add(9);
-                if (bad) add(10);
-            }
-        }
-#endif
+        // ---- 9. the record's tail (a listed shot is the row-swapping kernel's record)
+        if (osd_counts_record(P, inconsistent)) osd_tail_wave(P, rec, sol, syn, lane);
         __syncthreads();
     }
 }

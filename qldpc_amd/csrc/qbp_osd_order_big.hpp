@@ -3,13 +3,13 @@
 // candidate search.  The spec is in include/qbp.h (qbp_osd_batch) and DESIGN §3b.
 //
 // One workgroup of 1024 threads per record; the working copy is H[:, order] in SORTED column order, 64-bit word
-// planes, transposed, in the per-workgroup global workspace (qbp_osd.hpp).  The sweep only touches the word planes
+// planes, transposed, in the per-workgroup global workspace (qbp_osd_parts.hpp).  The sweep only touches the word planes
 // from the current block on, and that is exact: a pivot row is zero left of its pivot column (earlier pivot columns
 // were cleared in it; an earlier non-pivot column had no 1 in any row without a pivot when the sweep passed it), so
 // the reduced column of a non-pivot column is final once the sweep has passed it.  The search reads those columns
 // straight from the workspace.
-// Kept apart from osd0_blocked_kernel and osd_order_kernel (not shared helpers) so that those kernels' code,
-// registers and bits stay exactly what they were.
+// The order, the blocks of the sweep (osd_block_*) and the record's tail are the pieces of qbp_osd_parts.hpp that
+// osd0_blocked_kernel is built from; the search (steps 5-8) is this kernel's own.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -40,15 +40,8 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
     extern __shared__ double osd_smem[];
     __shared__ unsigned s_piv[3];
     __shared__ unsigned s_nact[2];
-    __shared__ unsigned long long s_lm, s_item, s_best;
-#if QBP_OSD_SHOTS
-    __shared__ int s_bad;
-#else
-    __shared__ int s_ew, s_df, s_bad;
-#endif
-#if QBP_OSD_SPECTRUM
-    __shared__ int s_rw;                      // weight of the residual
-#endif
+    __shared__ unsigned long long s_item, s_best;
+    __shared__ OsdTally s_tally;              // (the search borrows .lm and .bad: the tail zeroes them first)
     typedef unsigned long long u64;
     const int tid = threadIdx.x, nt = 1024;
     const int m = P.m, n = P.n, NP = P.NP;
@@ -91,42 +84,11 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
         const double* llr = P.llr + rec * n;
         const uint8_t* hard = P.hard + rec * n;
         const uint8_t* syn = P.syndromes + rec * m;
-#if QBP_OSD_ORDERED
-        // ---- 1. ordering = the record's row of P.order (-1: an entry outside [0, n), and the padding)
-        (void)keys;
-        {
-            const int32_t* ord = P.order + rec * n;
-            for (int i = tid; i < NP; i += nt) {
-                const int c = i < n ? ord[i] : -1;
-                idx[i] = c >= 0 && c < n ? c : -1;
-            }
-        }
+        // ---- 1. ordering = argsort(|llr|), ties by column index, or the record's row of P.order
+        osd_order_fill(P, rec, keys, idx, tid, nt);
         for (int i = tid; i < n; i += nt) sol[i] = hard[i] & 1u;
         __syncthreads();
-#else
-        // ---- 1. ordering = argsort(|llr|), ties by column index, as osd0_blocked_kernel
-        for (int i = tid; i < NP; i += nt) {
-            keys[i] = i < n ? osd_order_key(llr[i]) : ~0ull;
-            idx[i] = i;
-        }
-        for (int i = tid; i < n; i += nt) sol[i] = hard[i] & 1u;
-        __syncthreads();
-        for (int k = 2; k <= NP; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int t = tid; t < NP / 2; t += nt) {
-                    const int lo = ((t / j) * (2 * j)) + (t % j);
-                    const int hi = lo + j;
-                    const bool up = (lo & k) == 0;
-                    const u64 ka = keys[lo], kb = keys[hi];
-                    const int ia = idx[lo], ib = idx[hi];
-                    if (osd_less(kb, ib, ka, ia) == up) {
-                        keys[lo] = kb; keys[hi] = ka; idx[lo] = ib; idx[hi] = ia;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-#endif
+        osd_sort(keys, idx, NP, tid, nt);
         int pc[RPT];                          // pivot column (original index) of this thread's rows, -1: none yet
         unsigned sb = 0;                      // bit i: reduced syndrome bit of row tid + i * nt
         const int Wc = Wk.wc_max;             // word planes: all n sorted columns, then the syndrome bit
@@ -163,99 +125,19 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
         while (k0 < n && rank < P.rank) {
             // (before anyone reads a row again or overwrites pos / Qs / the table)
             __syncthreads();
-            const int wk = k0 >> 6, sh = k0 & 63, nw = Wc - wk;
-            int T = 8;
-            while (T > 1 && ((k0 & (T - 1)) || ((size_t)nw << T) * 8 > (size_t)Wk.lds_table)) T >>= 1;
-            const int Tc = n - k0 < T ? n - k0 : T;
-            unsigned bd[RPT];             // bits 0-7: the row's bits in the block's columns, 8-15: its set D
-#pragma unroll
-            for (int i = 0; i < RPT; ++i) {
-                const int r = tid + i * nt;
-                bd[i] = r < m ? (unsigned)(At[(size_t)wk * m + r] >> sh) & ((1u << Tc) - 1u) : 0u;
-            }
+            const OsdBlock B = osd_block_shape(k0, n, Wc, Wk.lds_table);
+            unsigned bd[RPT];
             int prow[8];
-            bool any = false;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                prow[j] = -1;
-                if (j >= Tc || rank >= P.rank) continue;          // (uniform)
-                unsigned cand = ~0u;
-#pragma unroll
-                for (int i = RPT - 1; i >= 0; --i) {
-                    const u64 b = __ballot(pc[i] < 0 && ((bd[i] >> j) & 1u));
-                    if (b) {
-                        const int l = __builtin_ctzll(b);
-                        const unsigned v = (unsigned)__builtin_amdgcn_readlane((int)bd[i], l);
-                        cand = ((unsigned)((tid & ~63) + l + i * nt) << 16) | v;
-                    }
-                }
-                unsigned* const slot = &s_piv[col_ctr % 3u];
-                if ((tid & 63) == 0 && cand != ~0u) atomicMin(slot, cand);
-                __syncthreads();
-                const unsigned key = *slot;                       // first unused row with a 1
-                if (tid == 0) s_piv[(col_ctr + 2u) % 3u] = ~0u;   // (the slot of two columns ahead: idle now)
-                ++col_ctr;
-                if (key == ~0u) continue;                         // depends on earlier columns
-                ++rank;
-                any = true;
-                const int p = (int)(key >> 16);
-                const unsigned upd = (key & 0xffffu) | (0x100u << j);
-                prow[j] = p;
-#pragma unroll
-                for (int i = 0; i < RPT; ++i) {
-                    const int r = tid + i * nt;
-                    if (r == p) pc[i] = idx[k0 + j];
-                    else if ((bd[i] >> j) & 1u) bd[i] ^= upd;
-                }
-            }
-            k0 += T;
+            osd_block_bytes<RPT>(At, m, B, bd, tid, nt);
+            const bool any = osd_block_pivots<RPT>(idx, s_piv, k0, B.Tc, P.rank, rank, col_ctr, pc, bd, prow, tid, nt);
+            k0 += B.T;
             if (!any) continue;
-            unsigned* const nact = &s_nact[blk_ctr & 1u];
-            {
-#pragma unroll
-                for (int i = 0; i < RPT; ++i) {
-                    const bool a = (bd[i] >> 8) != 0u;
-                    const u64 b = __ballot(a);
-                    if (b) {
-                        unsigned base = 0;
-                        if ((tid & 63) == 0) base = atomicAdd(nact, (unsigned)__builtin_popcountll(b));
-                        base = (unsigned)__builtin_amdgcn_readfirstlane((int)base);
-                        if (a) act[base + (unsigned)__builtin_popcountll(b & ((1ull << (tid & 63)) - 1ull))] =
-                                   ((unsigned)(tid + i * nt) << 8) | (bd[i] >> 8);
-                    }
-                }
-                if (tid == 0) s_nact[(blk_ctr + 1u) & 1u] = 0u;       // (the next block's counter: idle now)
-            }
-            ++blk_ctr;
-            // the block's pivot rows as they were when the block began -> LDS
-            for (int it = tid; it < 8 * nw; it += nt) {
-                const int j = it / nw, w = it - j * nw;
-                int p = -1;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) if (q == j) p = prow[q];
-                Qs[it] = p >= 0 ? At[(size_t)(wk + w) * m + p] : 0ull;
-            }
+            const unsigned* const nact = osd_block_act<RPT>(act, s_nact, blk_ctr, bd, tid, nt);
+            osd_block_stage(Qs, At, m, B, prow, tid, nt);
             __syncthreads();
-            // every XOR combination of them
-            for (int it = tid; it < (nw << T); it += nt) {
-                const int x = it / nw, w = it - x * nw;
-                u64 v = 0ull;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) if ((x >> j) & 1) v ^= Qs[j * nw + w];
-                table[it] = v;
-            }
+            osd_block_table(table, Qs, B, tid, nt);
             __syncthreads();
-            {
-#pragma unroll
-                for (int i = 0; i < RPT; ++i)
-                    if (bd[i] >> 8) sb ^= ((unsigned)table[(size_t)(bd[i] >> 8) * nw + nw - 1] & 1u) << i;
-                const int na = (int)*nact, items = na * nw;
-                for (int it = tid; it < items; it += nt) {
-                    const int w = it / na;
-                    const unsigned e = act[it - w * na];
-                    At[(size_t)(wk + w) * m + (e >> 8)] ^= table[(size_t)(e & 0xffu) * nw + w];
-                }
-            }
+            osd_block_update<RPT>(At, m, table, act, (int)*nact, B, bd, sb, tid, nt);
         }
         // a syndrome outside the column space: the OSD-0 output of the row-swapping kernel (redo list), no search
         bool inconsistent;
@@ -273,7 +155,7 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
         if (!inconsistent) {              // (uniform)
             // ---- 5. per column: pivot row; T = non-pivot columns in sort order (ordered builds: the given order)
             for (int i = tid; i < n; i += nt) { cm[i] = 0ull; cinfo[i] = -1; }
-            if (tid == 0) { s_lm = ~0ull; s_best = ~0ull; s_bad = 0; }
+            if (tid == 0) { s_tally.lm = ~0ull; s_best = ~0ull; s_tally.bad = 0u; }
             __syncthreads();
 #pragma unroll
             for (int i = 0; i < RPT; ++i)
@@ -337,13 +219,13 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
             }
             // least cost (a sum of fabs from +0.0: its bit pattern is monotone), then the lowest index at that cost
             const u64 bcb = (u64)__double_as_longlong(bc);
-            if (bi == -2) s_bad = 1;
-            if (bi >= 0) atomicMin(&s_lm, bcb);
+            if (bi == -2) s_tally.bad = 1u;
+            if (bi >= 0) atomicMin(&s_tally.lm, bcb);
             __syncthreads();
-            if (bi >= 0 && bcb == s_lm) atomicMin(&s_best, (u64)bi);
+            if (bi >= 0 && bcb == s_tally.lm) atomicMin(&s_best, (u64)bi);
             __syncthreads();
-            const long long win = s_bad ? 0 : (long long)s_best;
-            __syncthreads();                  // (s_lm and s_bad are the tail's from here on)
+            const long long win = s_tally.bad ? 0 : (long long)s_best;
+            __syncthreads();                  // (s_tally is the tail's from here on)
             // ---- 8. apply the winning flip set
             if (win > 0) {
                 u64 fm = 0ull;
@@ -362,87 +244,12 @@ __global__ __launch_bounds__(1024) void osd_order_blocked_kernel(const OsdParams
                 if (tid == 0 && tx >= 0) sol[idx[kx]] ^= 1u;
             }
         }
-        // ---- 9. the build's tail, as osd0_blocked_kernel
-#if QBP_OSD_SHOTS
-        if (tid == 0) { s_lm = 0ull; s_bad = 0; }
-#else
-        if (tid == 0) { s_lm = 0ull; s_ew = 0; s_df = 0; s_bad = 0; }
-#endif
-#if QBP_OSD_SPECTRUM
-        if (tid == 0) s_rw = 0;
-#endif
+        // ---- 9. the record's tail, as osd0_blocked_kernel (a listed shot is the row-swapping kernel's record)
+        if (tid == 0) s_tally = OsdTally{};
         __syncthreads();
         if (P.solution)
             for (int i = tid; i < n; i += nt) P.solution[rec * n + i] = sol[i];
-#if QBP_OSD_SHOTS
-        if (!(inconsistent && P.redo != nullptr)) {      // (uniform; else: the row-swapping kernel's record)
-            u64 lm = 0ull;
-            unsigned bad = 0;
-            for (int i = tid; i < n; i += nt)
-                if (sol[i]) lm ^= P.lx_cols[i];
-            for (int r = tid; r < m; r += nt) {
-                unsigned par = syn[r] & 1u;
-                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-                bad |= par;
-            }
-            if (lm) atomicXor(&s_lm, lm);
-            if (bad) atomicOr(&s_bad, 1);
-            __syncthreads();
-            if (tid == 0) osd_shot_result(P, rec, s_lm, s_bad != 0);
-        }
-#else
-        if (P.errors) {
-            const uint8_t* err = P.errors + rec * n;
-            u64 lm = 0ull;
-            int ew = 0;
-            unsigned df = 0, bad = 0;
-#if QBP_OSD_SPECTRUM
-            int rw = 0;
-#endif
-            for (int i = tid; i < n; i += nt) {
-                const unsigned e = err[i] & 1u;
-                const unsigned res = sol[i] ^ e;
-                ew += (int)e;
-                df |= res;
-#if QBP_OSD_SPECTRUM
-                rw += (int)res;
-#endif
-                if (res) lm ^= P.lx_cols[i];
-            }
-#if QBP_OSD_SPECTRUM
-            if (rw) atomicAdd(&s_rw, rw);
-#endif
-            for (int r = tid; r < m; r += nt) {
-                unsigned par = syn[r] & 1u;
-                for (int e = P.row_ptr[r]; e < P.row_ptr[r + 1]; ++e) par ^= sol[P.col_idx[e]];
-                bad |= par;
-            }
-            if (lm) atomicXor(&s_lm, lm);
-            if (ew) atomicAdd(&s_ew, ew);
-            if (df) atomicOr(&s_df, 1);
-            if (bad) atomicOr(&s_bad, 1);
-            __syncthreads();
-            if (tid == 0) {
-                auto add = [&](int i) {
-                    atomicAdd(reinterpret_cast<unsigned long long*>(P.counters + i), 1ull);
-                };
-                const bool logical = s_lm != 0ull;
-#if QBP_OSD_SPECTRUM
-                if (s_rw)
-                    atomicAdd(reinterpret_cast<unsigned long long*>(
-                                  P.spectrum + (long long)mc_spectrum_row(false, logical) * (n + 1) + s_rw), 1ull);
-#endif
-                if (!s_bad && !logical && s_df) add(5);
-                if (logical) {
-                    add(1);
-                    add(s_ew < P.half_distance ? 3 : 4);
-                    add(8);
-                }
-                if (!s_df) add(9);
-                if (s_bad) add(10);
-            }
-        }
-#endif
+        if (osd_counts_record(P, inconsistent)) osd_tail_block(P, rec, sol, syn, s_tally, tid, nt);   // (uniform)
         __syncthreads();
     }
 }

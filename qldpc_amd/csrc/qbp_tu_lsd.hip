@@ -14,14 +14,8 @@ hipError_t lsd_launch_k(const LsdParams& P, unsigned grid, size_t lds, hipStream
 {
     auto kern = lsd_kernel<RECORDS>;
     static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
+    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, s, P);
     return hipGetLastError();
 }

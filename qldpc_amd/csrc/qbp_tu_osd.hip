@@ -8,52 +8,38 @@
 // With -DQBP_ORDERED_TU: all of them once more, which take the column order of every record from the caller instead of
 // sorting (qbp_osd_batch_ordered); no histogram kernels either.
 #define QBP_DEFINE_KERNELS 1
-#ifdef QBP_ORDERED_TU
+#if defined(QBP_ORDERED_TU)
 #define QBP_OSD_ORDERED 1
-#undef QBP_OSD_TIMING
-#define osd0_kernel osd0_ordered_kernel
-#define osd0_big_kernel osd0_big_ordered_kernel
-#define osd0_blocked_kernel osd0_blocked_ordered_kernel
-#define osd_order_kernel osd_order_ordered_kernel
-#define osd_order_blocked_kernel osd_order_blocked_ordered_kernel
-#define launch_osd_small launch_osd_small_ordered
-#define launch_osd_order launch_osd_order_ordered
-#define launch_osd_big launch_osd_big_ordered
-#define launch_osd_blocked launch_osd_blocked_ordered
-#define launch_osd_order_blocked launch_osd_order_blocked_ordered
-#endif
-#ifdef QBP_SHOTS_TU
+#define QBP_OSD_TU_SUFFIX _ordered
+#elif defined(QBP_SHOTS_TU)
 #define QBP_OSD_SHOTS 1
-#undef QBP_OSD_TIMING
-#define osd0_kernel osd0_shots_kernel
-#define osd0_big_kernel osd0_big_shots_kernel
-#define osd0_blocked_kernel osd0_blocked_shots_kernel
-#define osd_order_kernel osd_order_shots_kernel
-#define osd_order_blocked_kernel osd_order_blocked_shots_kernel
-#define launch_osd_small launch_osd_small_shots
-#define launch_osd_order launch_osd_order_shots
-#define launch_osd_big launch_osd_big_shots
-#define launch_osd_blocked launch_osd_blocked_shots
-#define launch_osd_order_blocked launch_osd_order_blocked_shots
-#endif
-#ifdef QBP_SPECTRUM_TU
+#define QBP_OSD_TU_SUFFIX _shots
+#elif defined(QBP_SPECTRUM_TU)
 #define QBP_OSD_SPECTRUM 1
+#define QBP_OSD_TU_SUFFIX _spectrum
+#endif
+#ifdef QBP_OSD_TU_SUFFIX
+// the unit's kernels and launch functions under names of their own: <stem><suffix>_kernel, launch_<...><suffix>
 #undef QBP_OSD_TIMING
-#define osd0_kernel osd0_spectrum_kernel
-#define osd0_big_kernel osd0_big_spectrum_kernel
-#define osd0_blocked_kernel osd0_blocked_spectrum_kernel
-#define osd_order_kernel osd_order_spectrum_kernel
-#define osd_order_blocked_kernel osd_order_blocked_spectrum_kernel
-#define launch_osd_small launch_osd_small_spectrum
-#define launch_osd_order launch_osd_order_spectrum
-#define launch_osd_big launch_osd_big_spectrum
-#define launch_osd_blocked launch_osd_blocked_spectrum
-#define launch_osd_order_blocked launch_osd_order_blocked_spectrum
+#define QBP_OSD_CAT_(a, b, c) a##b##c
+#define QBP_OSD_CAT(a, b, c) QBP_OSD_CAT_(a, b, c)
+#define QBP_OSD_KERNEL(stem) QBP_OSD_CAT(stem, QBP_OSD_TU_SUFFIX, _kernel)
+#define QBP_OSD_LAUNCH(name) QBP_OSD_CAT(name, QBP_OSD_TU_SUFFIX, )
+#define osd0_kernel QBP_OSD_KERNEL(osd0)
+#define osd0_big_kernel QBP_OSD_KERNEL(osd0_big)
+#define osd0_blocked_kernel QBP_OSD_KERNEL(osd0_blocked)
+#define osd_order_kernel QBP_OSD_KERNEL(osd_order)
+#define osd_order_blocked_kernel QBP_OSD_KERNEL(osd_order_blocked)
+#define launch_osd_small QBP_OSD_LAUNCH(launch_osd_small)
+#define launch_osd_order QBP_OSD_LAUNCH(launch_osd_order)
+#define launch_osd_big QBP_OSD_LAUNCH(launch_osd_big)
+#define launch_osd_blocked QBP_OSD_LAUNCH(launch_osd_blocked)
+#define launch_osd_order_blocked QBP_OSD_LAUNCH(launch_osd_order_blocked)
 #endif
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
-#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU) && !defined(QBP_ORDERED_TU)
+#ifndef QBP_OSD_TU_SUFFIX
 #include "qbp_hist.hpp"
 #endif
 #include "qbp_launch.hpp"
@@ -94,14 +80,8 @@ hipError_t launch_osd_order(int words_per_row, unsigned grid, size_t lds, const 
 hipError_t launch_osd_big(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s)
 {
     static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (lds > 0 && (dev < 0 || dev >= 64 || lds_set[dev] < lds)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(osd0_big_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
+    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(osd0_big_kernel), lds, lds_set);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(osd0_big_kernel, dim3(grid), dim3(256), lds, s, O, Wk);
     return hipGetLastError();
 }
@@ -111,14 +91,8 @@ static hipError_t launch_osd_blocked_rpt(unsigned grid, size_t lds, const OsdPar
                                          hipStream_t s)
 {
     static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(osd0_blocked_kernel<RPT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
+    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(osd0_blocked_kernel<RPT>), lds, lds_set);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(osd0_blocked_kernel<RPT>, dim3(grid), dim3(1024), lds, s, O, Wk);
     return hipGetLastError();
 }
@@ -141,14 +115,9 @@ static hipError_t launch_osd_order_blocked_rpt(unsigned grid, size_t lds, const 
                                                const OsdOrderBigArgs& X, hipStream_t s)
 {
     static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(osd_order_blocked_kernel<RPT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
+    const hipError_t e =
+        raise_dynamic_lds(reinterpret_cast<const void*>(osd_order_blocked_kernel<RPT>), lds, lds_set);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(osd_order_blocked_kernel<RPT>, dim3(grid), dim3(1024), lds, s, O, Wk, X);
     return hipGetLastError();
 }
@@ -180,7 +149,7 @@ extern "C" int qbp_debug_osd_timing(unsigned long long* out, int reset)
 }
 #endif
 
-#if !defined(QBP_SPECTRUM_TU) && !defined(QBP_SHOTS_TU) && !defined(QBP_ORDERED_TU)
+#ifndef QBP_OSD_TU_SUFFIX
 hipError_t launch_hist_minmax(int grid, const double* x, long long count, double* part, hipStream_t s)
 {
     hipLaunchKernelGGL(hist_minmax_kernel, dim3(grid), dim3(256), 0, s, x, count, part);
@@ -194,6 +163,6 @@ hipError_t launch_hist_bin(int grid, size_t lds, const double* msg, const uint8_
     hipLaunchKernelGGL(hist_bin_kernel, dim3(grid), dim3(256), lds, s, msg, errors, col_idx, B, E, n, edges, bins, hist);
     return hipGetLastError();
 }
-#endif  // !QBP_SPECTRUM_TU && !QBP_SHOTS_TU && !QBP_ORDERED_TU
+#endif  // !QBP_OSD_TU_SUFFIX
 
 }  // namespace qbp
