@@ -834,6 +834,85 @@ int64_t qbp_window_get_info(qbp_window* w, int32_t what, int32_t index);
 /* QBP_OPT_MC_WEIGHT_CHUNK: trials per chunk of qbp_window_mc_run_* (0 = default); any other option goes to every sub-handle. */
 int qbp_window_set_option(qbp_window* w, int32_t option, int64_t value);
 
+/*
+ * BP with a prior that differs per record.  Record b decodes syndromes[b] with the prior
+ *   prior_b[v] = (sel[b][v] & 1) ? prior1[v] : prior0[v]          (sel [B][n] bytes, only bit 0 counts)
+ * and is, bit for bit, qbp_decode_batch on that one syndrome with that prior vector: flooding schedule, QBP_SUM_PRODUCT or
+ * QBP_MIN_SUM (alpha the normalisation, clip_llr the clip, damping = 1: there is no damping argument).  Outputs (any may
+ * be NULL) have qbp_decode_batch's meaning: hard [B][n], converged [B], iters [B] (0-based iteration of the first
+ * syndrome match, max_iter - 1 if none), llr [B][n].  One workgroup per record with the record's whole state in LDS
+ * (bp_cond_kernel, qbp_cond.hpp).
+ *   QBP_E_INVALID      a null input, a NaN in prior0 or prior1 (host entry; +-inf are legal), max_iter < 1, an unknown
+ *                      variant, an OSD bit -- before any GPU work, outputs untouched;
+ *   QBP_E_UNSUPPORTED  QBP_DAMPED_SP; a column-sum order flag, QBP_FLAG_LAYERED, _RELAY, _GD, _LSD or _FAST_MATH; a matrix
+ *                      whose record state exceeds 160 KiB of LDS (as Relay-BP and BPGD) -- the same;
+ *   B = 0 succeeds and changes nothing.  QBP_FLAG_FORCE_FULL is accepted and changes no output.
+ */
+int qbp_decode_batch_cond(qbp_handle* h, const uint8_t* syndromes, const uint8_t* sel, const double* prior0,
+                          const double* prior1, int64_t B, int32_t max_iter, int32_t variant, double alpha,
+                          double clip_llr, uint32_t flags, uint8_t* hard, uint8_t* converged, int32_t* iters, double* llr);
+/* Same, all pointers are DEVICE pointers, enqueued on `stream`, asynchronous (no NaN check). */
+int qbp_decode_batch_cond_device(qbp_handle* h, const uint8_t* d_syndromes, const uint8_t* d_sel, const double* d_prior0,
+                                 const double* d_prior1, int64_t B, int32_t max_iter, int32_t variant, double alpha,
+                                 double clip_llr, uint32_t flags, uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters,
+                                 double* d_llr, void* stream);
+
+/*
+ * Two-stage decoding of a CSS code under Pauli noise (X/Z-correlated BP).  Sector A is the matrix `ha` with the part
+ * e_a of the error it detects, sector B the matrix `hb` with e_b; for the codes of codes/: ha = Hx detects Z and Y,
+ * hb = Hz detects X and Y, and a Y error flips the qubit's bit in both.  Per trial:
+ *   A.  qbp_decode_batch on ha with prior_a; with QBP_FLAG_OSD0 (| a method bit and an order) in `flags` the trials BP
+ *       leaves unconverged go through qbp_osd_batch.  x_a = the OSD solution where BP failed and OSD ran, else `hard`.
+ *   B.  qbp_decode_batch_cond on hb with sel = x_a, prior0 = prior_b0, prior1 = prior_b1; the same OSD rule gives x_b.
+ * For depolarizing noise of strength p (px = py = pz = p / 3) the conditional priors are prior_b0 = log(3 (1 - p) / p)
+ * and prior_b1 = log(pz / py) = 0 exactly; prior_b1 = prior_b0 = the marginal of sector B decodes the sectors
+ * independently.  variant: QBP_SUM_PRODUCT or QBP_MIN_SUM, for both stages; damping reaches stage A only (stage B has
+ * none).  flags: QBP_FLAG_FORCE_FULL and the OSD bits, as in qbp_mc_run.
+ *   QBP_E_INVALID      null pointers, NaN priors, probabilities outside [0, 1] or px + py + pz > 1, k outside 0..64;
+ *   QBP_E_UNSUPPORTED  QBP_DAMPED_SP, what qbp_decode_batch_cond refuses, and Relay-BP, BPGD, LSD or the layered
+ *                      schedule as a stage (out of scope) -- all before any GPU work.
+ *
+ * qbp_css_create borrows two handles the caller owns (same device, same n, else QBP_E_INVALID); qbp_css_destroy frees
+ * the object and leaves them alone.  They must outlive it, and no other call may use them while a qbp_css_* call runs.
+ *
+ * The sampler: Philox4x32-10 keyed by the seed on the counter (trial lo, trial hi, qubit / 4, QBP_CSS_PHILOX_STREAM),
+ * word qubit % 4 = u.  Counter word 3 is the sampler's stream: the Bernoulli draws of qbp_mc_run use 0 and 1, the
+ * fixed-weight sampler 2, this one 3.  With t1 = floor(pz 2^32), t2 = floor((pz + px) 2^32), t3 = floor(((pz + px) + py)
+ * 2^32), each at most 2^32 - 1: u < t1 is Z, else u < t2 is X, else u < t3 is Y, else no error.  errors_a = Z or Y,
+ * errors_b = X or Y, both [T][n] 0/1 bytes.  The rows do not depend on how a trial range is split.
+ *
+ * Monte-Carlo: counters [3][QBP_NUM_COUNTERS].  Rows 0 and 1 are the sectors, (e_a, x_a, La) and (e_b, x_b, Lb), in
+ * qbp_mc_run's layout with the sliding-window decoder's two rules: [5] also counts a correction OSD made valid, [10]
+ * counts the corrections that miss their syndrome (without OSD: the unconverged ones).  [6], [7] and [8] follow the BP
+ * stage of the sector.  Row 2 is the trial: [0] trials, [1] a logical error in either sector, [6] either BP
+ * unconverged, [8] the [1] among the [6], [9] both corrections equal to the errors, [10] either correction misses its
+ * syndrome; its other counters are 0.  qbp_css_mc_run ADDS to counters, qbp_css_mc_run_errors SETS them.  A call works
+ * in chunks of at most QBP_MC_OSD_MAX_TRIALS trials, each one chain of launches on the stream (sample or copy,
+ * syndromes, A, B, classify); counters do not depend on the chunk size (QBP_OPT_MC_WEIGHT_CHUNK through
+ * qbp_css_set_option) or on how the range is split.
+ */
+#define QBP_CSS_PHILOX_STREAM 3
+typedef struct qbp_css qbp_css;
+int qbp_css_create(qbp_handle* ha, qbp_handle* hb, qbp_css** out);
+void qbp_css_destroy(qbp_css* css);
+int qbp_css_set_option(qbp_css* css, int32_t option, int64_t value);
+int qbp_css_sample_errors(qbp_css* css, double px, double py, double pz, uint64_t seed, int64_t trial_begin, int64_t T,
+                          uint8_t* errors_a, uint8_t* errors_b);
+/* x_a, x_b [B][n], conv_a, conv_b [B] (the BP stages' converged flags); any output may be NULL. */
+int qbp_css_decode_batch(qbp_css* css, const uint8_t* syn_a, const uint8_t* syn_b, int64_t B, const double* prior_a,
+                         const double* prior_b0, const double* prior_b1, int32_t max_iter, int32_t variant, double alpha,
+                         double damping, double clip_llr, uint32_t flags, uint8_t* x_a, uint8_t* x_b, uint8_t* conv_a,
+                         uint8_t* conv_b);
+int qbp_css_mc_run(qbp_css* css, const uint8_t* La, int32_t ka, const uint8_t* Lb, int32_t kb, int32_t distance,
+                   double px, double py, double pz, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                   const double* prior_a, const double* prior_b0, const double* prior_b1, int32_t max_iter,
+                   int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                   int64_t counters[3 * QBP_NUM_COUNTERS]);
+int qbp_css_mc_run_errors(qbp_css* css, const uint8_t* La, int32_t ka, const uint8_t* Lb, int32_t kb, int32_t distance,
+                          const uint8_t* errors_a, const uint8_t* errors_b, int64_t T, const double* prior_a,
+                          const double* prior_b0, const double* prior_b1, int32_t max_iter, int32_t variant, double alpha,
+                          double damping, double clip_llr, uint32_t flags, int64_t counters[3 * QBP_NUM_COUNTERS]);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

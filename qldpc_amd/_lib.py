@@ -147,6 +147,22 @@ SIGNATURES = {
                                            C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
     "qbp_window_get_info": (C.c_int64, [_VP, C.c_int32, C.c_int32]),
     "qbp_window_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
+    "qbp_decode_batch_cond": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                        C.c_uint32, _VP, _VP, _VP, _VP]),
+    "qbp_decode_batch_cond_device": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_int32, C.c_double,
+                                               C.c_double, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_css_create": (C.c_int, [_VP, _VP, C.POINTER(_VP)]),
+    "qbp_css_destroy": (None, [_VP]),
+    "qbp_css_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
+    "qbp_css_sample_errors": (C.c_int, [_VP, C.c_double, C.c_double, C.c_double, C.c_uint64, C.c_int64, C.c_int64, _VP,
+                                        _VP]),
+    "qbp_css_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_double,
+                                       C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "qbp_css_mc_run": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                 C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_double,
+                                 C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_css_mc_run_errors": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, _VP, _VP, _VP,
+                                        C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
     "qbp_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
     "qbp_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_debug_math": (C.c_int, [_VP, C.c_int32, _VP, _VP, C.c_int64]),
@@ -443,6 +459,107 @@ class WindowDecoder:
         return cnt
 
 
+class CssDecoder:
+    """Two-stage decoder of a CSS code under Pauli noise (wraps a ``qbp_css`` over two ``Decoder`` objects it keeps
+    alive; include/qbp.h states the rule).  Sector A is ``dec_a`` (for the codes of codes/: Hx, which detects Z and Y),
+    sector B ``dec_b`` (Hz: X and Y).  Methods are serialised per object and hold both decoders' locks."""
+
+    def __init__(self, dec_a, dec_b):
+        if dec_a.n != dec_b.n:
+            raise ValueError(f"the two matrices have {dec_a.n} and {dec_b.n} columns")
+        self.a, self.b = dec_a, dec_b
+        self.n, self.ma, self.mb = dec_a.n, dec_a.m, dec_b.m
+        h = _VP()
+        _check(load().qbp_css_create(dec_a._h, dec_b._h, C.byref(h)))
+        self._h = h
+        self.device = dec_a.device
+        self._lock = threading.RLock()
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.qbp_css_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _call(self, fn, *args):
+        with self._lock, self.a._lock, self.b._lock:
+            _check(fn(self._h, *args))
+
+    def set_option(self, option, value):
+        self._call(load().qbp_css_set_option, int(option), int(value))
+
+    def _priors(self, *priors):
+        out = [np.ascontiguousarray(p, np.float64) for p in priors]
+        for p in out:
+            if p.shape != (self.n,):
+                raise ValueError(f"a prior must have shape ({self.n},), got {p.shape}")
+        return out
+
+    def _logicals(self, L):
+        L = np.ascontiguousarray(L, np.uint8)
+        if L.ndim != 2 or L.shape[1] != self.n:
+            raise ValueError(f"logical operators must have shape (k, {self.n}), got {L.shape}")
+        return L
+
+    def sample_errors(self, px, py, pz, trial_begin, T, seed=0):
+        """qbp_css_sample_errors -> (errors_a, errors_b) uint8[T, n]: Z or Y, X or Y."""
+        ea = np.empty((int(T), self.n), np.uint8)
+        eb = np.empty((int(T), self.n), np.uint8)
+        self._call(load().qbp_css_sample_errors, float(px), float(py), float(pz), int(seed), int(trial_begin), int(T),
+                   ea.ctypes.data, eb.ctypes.data)
+        return ea, eb
+
+    def decode(self, syn_a, syn_b, prior_a, prior_b0, prior_b1, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
+               clip_llr=20.0, flags=0):
+        """qbp_css_decode_batch -> (x_a, x_b uint8[B, n], conv_a, conv_b bool[B])."""
+        sa = np.ascontiguousarray(syn_a, np.uint8)
+        sb = np.ascontiguousarray(syn_b, np.uint8)
+        if sa.ndim != 2 or sa.shape[1] != self.ma or sb.shape != (sa.shape[0], self.mb):
+            raise ValueError(f"syndromes must have shapes (B, {self.ma}) and (B, {self.mb}), got {sa.shape}, {sb.shape}")
+        pa, p0, p1 = self._priors(prior_a, prior_b0, prior_b1)
+        B = sa.shape[0]
+        xa = np.empty((B, self.n), np.uint8)
+        xb = np.empty((B, self.n), np.uint8)
+        ca = np.empty(B, np.uint8)
+        cb = np.empty(B, np.uint8)
+        self._call(load().qbp_css_decode_batch, sa.ctypes.data, sb.ctypes.data, B, pa.ctypes.data, p0.ctypes.data,
+                   p1.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags),
+                   xa.ctypes.data, xb.ctypes.data, ca.ctypes.data, cb.ctypes.data)
+        return xa, xb, ca.astype(bool), cb.astype(bool)
+
+    def mc_run(self, La, Lb, distance, px, py, pz, prior_a, prior_b0, prior_b1, trial_begin, trial_end, seed=0, max_iter=50,
+               variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, counters=None):
+        """qbp_css_mc_run -> int64[3, 12] (sector A, sector B, the trial), ADDED to ``counters`` if given."""
+        La, Lb = self._logicals(La), self._logicals(Lb)
+        pa, p0, p1 = self._priors(prior_a, prior_b0, prior_b1)
+        cnt = np.zeros((3, NUM_COUNTERS), np.int64) if counters is None else counters
+        self._call(load().qbp_css_mc_run, La.ctypes.data, La.shape[0], Lb.ctypes.data, Lb.shape[0], int(distance),
+                   float(px), float(py), float(pz), int(seed), int(trial_begin), int(trial_end), pa.ctypes.data,
+                   p0.ctypes.data, p1.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping),
+                   float(clip_llr), int(flags), cnt.ctypes.data)
+        return cnt
+
+    def mc_run_errors(self, La, Lb, distance, errors_a, errors_b, prior_a, prior_b0, prior_b1, max_iter=50,
+                      variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """qbp_css_mc_run_errors -> int64[3, 12] (SET)."""
+        La, Lb = self._logicals(La), self._logicals(Lb)
+        ea = np.ascontiguousarray(errors_a, np.uint8)
+        eb = np.ascontiguousarray(errors_b, np.uint8)
+        if ea.ndim != 2 or ea.shape[1] != self.n or eb.shape != ea.shape:
+            raise ValueError(f"errors must both have shape (T, {self.n}), got {ea.shape}, {eb.shape}")
+        pa, p0, p1 = self._priors(prior_a, prior_b0, prior_b1)
+        cnt = np.zeros((3, NUM_COUNTERS), np.int64)
+        self._call(load().qbp_css_mc_run_errors, La.ctypes.data, La.shape[0], Lb.ctypes.data, Lb.shape[0], int(distance),
+                   ea.ctypes.data, eb.ctypes.data, ea.shape[0], pa.ctypes.data, p0.ctypes.data, p1.ctypes.data,
+                   int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags), cnt.ctypes.data)
+        return cnt
+
+
 class Decoder:
     """One parity-check matrix on one GPU (wraps a ``qbp_handle``).  Methods taking host arrays
     are serialised per Decoder (thread-safe); the ``*_device`` methods only enqueue work on the
@@ -531,6 +648,38 @@ class Decoder:
             self._h, d_syndromes, d_prior, int(B), int(max_iter), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_hard or None, d_converged or None,
             d_iters or None, d_llr or None, stream or None))
+
+    @_locked
+    def decode_cond(self, syndromes, sel, prior0, prior1, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, clip_llr=20.0,
+                    flags=0, want_llr=True):
+        """qbp_decode_batch_cond: record b decodes with ``np.where(sel[b] & 1, prior1, prior0)`` as its prior ->
+        (hard, converged, iters, llr or None) with ``decode``'s meaning."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")
+        B = syn.shape[0]
+        sl = np.ascontiguousarray(sel, np.uint8)
+        if sl.shape != (B, self.n):
+            raise ValueError(f"sel must have shape ({B}, {self.n}), got {sl.shape}")
+        p0 = np.ascontiguousarray(prior0, np.float64)
+        p1 = np.ascontiguousarray(prior1, np.float64)
+        if p0.shape != (self.n,) or p1.shape != (self.n,):
+            raise ValueError(f"prior0 and prior1 must have shape ({self.n},)")
+        hard = np.empty((B, self.n), np.uint8)
+        conv = np.empty(B, np.uint8)
+        iters = np.empty(B, np.int32)
+        llr = np.empty((B, self.n), np.float64) if want_llr else None
+        _check(load().qbp_decode_batch_cond(self._h, syn.ctypes.data, sl.ctypes.data, p0.ctypes.data, p1.ctypes.data, B,
+                                            int(max_iter), int(variant), float(alpha), float(clip_llr), int(flags),
+                                            hard.ctypes.data, conv.ctypes.data, iters.ctypes.data, _ptr(llr)))
+        return hard, conv.astype(bool), iters, llr
+
+    def decode_cond_device(self, d_syndromes, d_sel, d_prior0, d_prior1, B, max_iter, variant, alpha, clip_llr, flags,
+                           d_hard, d_converged, d_iters, d_llr, stream=0):
+        _check(load().qbp_decode_batch_cond_device(
+            self._h, d_syndromes, d_sel, d_prior0, d_prior1, int(B), int(max_iter), int(variant), float(alpha),
+            float(clip_llr), int(flags), d_hard or None, d_converged or None, d_iters or None, d_llr or None,
+            stream or None))
 
     @_locked
     def relay_configure(self, cfg):

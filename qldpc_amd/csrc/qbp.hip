@@ -23,6 +23,7 @@
 #include "qbp_hist.hpp"
 #include "qbp_relay.hpp"
 #include "qbp_gd.hpp"
+#include "qbp_cond.hpp"
 #include "qbp_lsd.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_window.hpp"
@@ -367,6 +368,10 @@ struct qbp_handle {
     int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
     double gd_llr = 0.0, gd_alpha = 1.0, gd_clip = 0.0;
     DevBuf<int32_t> d_gd_rounds;
+    // BP with a prior per record (qbp_decode_batch_cond): the second prior in sorted-variable order; scratch of the
+    // host-pointer entry
+    DevBuf<double> d_prior1_sorted, d_cond_prior1;
+    DevBuf<uint8_t> d_cond_sel;
     // localized statistics decoding (qbp_lsd_configure): bits_per_step, the checks of every column (CSC, beside
     // d_col_ptr); scratch of the host-pointer entry
     bool lsd_ready = false;
@@ -3787,6 +3792,432 @@ try {
         if (rc) return rc;
     }
     return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// ---- BP with a prior per record (qbp_cond.hpp) -------------------------------------------------------------------
+// Everything qbp_decode_batch_cond refuses apart from null pointers and NaN priors: host only, before any GPU work.
+static int cond_check(qbp_handle* h, long long B, int max_iter, int variant, uint32_t flags)
+{
+    const int rc = check_decode_args(h, B, max_iter, variant);
+    if (rc) return rc;
+    if (flags & (QBP_FLAG_OSD0 | OSD_ALL_BITS)) return fail(QBP_E_INVALID, "flags 0x%x: an OSD bit in a BP call", flags);
+    if (variant == QBP_DAMPED_SP)
+        return fail(QBP_E_UNSUPPORTED, "BP with a prior per record runs QBP_SUM_PRODUCT or QBP_MIN_SUM, not QBP_DAMPED_SP");
+    if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0 | QBP_FLAG_LAYERED |
+                 QBP_FLAG_FAST_MATH | SECOND_BP_BITS))
+        return fail(QBP_E_UNSUPPORTED, "flags 0x%x: BP with a prior per record has the flooding schedule, ascending column "
+                                       "sums and numpy's functions only, and no second stage", flags);
+    if (flags & ~(uint32_t)QBP_FLAG_FORCE_FULL) return fail(QBP_E_INVALID, "flags 0x%x: unknown bits", flags);
+    const size_t lds = qbp::cond_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT);
+    if (lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "BP with a prior per record keeps the messages and two rows of n doubles in LDS: "
+                                       "%d x %d with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
+    return QBP_OK;
+}
+
+static int cond_launch(qbp_handle* h, const RecordCall& c, const uint8_t* d_sel, const double* d_prior1, int max_iter,
+                       int variant, double alpha, double clip_llr, hipStream_t s)
+{
+    constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
+    const bool sp = variant == QBP_SUM_PRODUCT;
+    const size_t lds = qbp::cond_lds_bytes(h->m, h->n, h->E, sp);
+    const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::COND_MAX_THREADS);
+    qbp::CondParams P{};
+    int grid = 0;
+    // the wavefronts a CU holds at the kernel's registers, as bp_gd_kernel: min-sum 7 per SIMD, sum-product 5;
+    // QBP_OPT_BLOCKS_PER_CU overrides
+    const int rc = record_launch_setup(h, c, false, {"BP with a prior per record", lds, threads, sp ? 20 : 28, true}, s,
+                                       P.tab, P.io, &grid);
+    if (rc) return rc;
+    HIP_TRY(h->d_prior1_sorted.reserve((size_t)h->n));
+    HIP_TRY(qbp::launch_permute_prior(d_prior1, h->d_svar.p, h->d_prior1_sorted.p, h->n, s));
+    P.sel = d_sel; P.prior1_sorted = h->d_prior1_sorted.p;
+    P.max_iter = max_iter; P.alpha = alpha; P.clip_llr = clip_llr;
+    HIP_TRY(qbp::launch_cond(variant, P, grid, threads, lds, s));
+    return QBP_OK;
+}
+
+int qbp_decode_batch_cond_device(qbp_handle* h, const uint8_t* d_syndromes, const uint8_t* d_sel, const double* d_prior0,
+                                 const double* d_prior1, int64_t B, int32_t max_iter, int32_t variant, double alpha,
+                                 double clip_llr, uint32_t flags, uint8_t* d_hard, uint8_t* d_converged, int32_t* d_iters,
+                                 double* d_llr, void* stream)
+try {
+    const int rc = cond_check(h, B, max_iter, variant, flags);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_sel || !d_prior0 || !d_prior1) return fail(QBP_E_INVALID, "null input pointer");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    RecordCall c;
+    c.prior = d_prior0; c.max_items = B; c.syndromes = d_syndromes;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr;
+    return cond_launch(h, c, d_sel, d_prior1, max_iter, variant, alpha, clip_llr, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_decode_batch_cond(qbp_handle* h, const uint8_t* syndromes, const uint8_t* sel, const double* prior0,
+                          const double* prior1, int64_t B, int32_t max_iter, int32_t variant, double alpha,
+                          double clip_llr, uint32_t flags, uint8_t* hard, uint8_t* converged, int32_t* iters, double* llr)
+try {
+    int rc = cond_check(h, B, max_iter, variant, flags);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !sel || !prior0 || !prior1) return fail(QBP_E_INVALID, "null input pointer");
+    if ((rc = check_prior(h->n, prior0, false)) != QBP_OK || (rc = check_prior(h->n, prior1, false)) != QBP_OK) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HostStage st(h->stream);
+    const uint8_t* d_syn = st.in(h->d_syn, syndromes, b * m);
+    const uint8_t* d_sel = st.in(h->d_cond_sel, sel, b * n);
+    const double* d_p0 = st.in(h->d_prior, prior0, n);
+    const double* d_p1 = st.in(h->d_cond_prior1, prior1, n);
+    uint8_t* d_hard = st.out(h->d_hard, hard, b * n);
+    uint8_t* d_conv = st.out(h->d_conv, converged, b);
+    int32_t* d_iters = st.out(h->d_iters, iters, b);
+    double* d_llr = st.out(h->d_llr, llr, b * n);
+    if (st.failed()) return st.error();
+    return st.finish(qbp_decode_batch_cond_device(h, d_syn, d_sel, d_p0, d_p1, B, max_iter, variant, alpha, clip_llr, flags,
+                                                  d_hard, d_conv, d_iters, d_llr, h->stream));
+}
+QBP_ABI_CATCH
+
+// ---- Two-stage decoding of a CSS code under Pauli noise (include/qbp.h, qbp_css_*) ---------------------------------
+struct qbp_css {
+    qbp_handle* ha = nullptr;       // borrowed
+    qbp_handle* hb = nullptr;
+    int device = 0, n = 0;
+    hipStream_t stream = nullptr;
+    // one chunk: errors, syndromes, a stage's BP outputs and OSD solutions, the corrections, the failure list
+    DevBuf<uint8_t> d_ea, d_eb, d_syn_a, d_syn_b, d_hard, d_sol, d_conv_a, d_conv_b, d_xa, d_xb;
+    DevBuf<int32_t> d_it_a, d_it_b;
+    DevBuf<double> d_llr, d_prior_a, d_prior_b0, d_prior_b1;
+    DevBuf<long long> d_fail_list, d_counters;
+    DevBuf<unsigned long long> d_fail_count;    // [2]: one per stage
+    McInputs in_a, in_b;                        // the logical operators of the sectors, by column
+    long long opt_chunk = 0;
+};
+
+// One call of the chain: what every entry shares
+struct CssCall {
+    const double* prior_a; const double* prior_b0; const double* prior_b1;      // device
+    int32_t max_iter, variant; double alpha, damping, clip_llr; uint32_t flags;
+    int method, order;              // parse_osd_flags
+};
+
+// Everything a CSS call refuses apart from null pointers and NaN priors: host only, before any GPU work.
+static int css_check(qbp_css* css, int64_t B, int32_t max_iter, int32_t variant, uint32_t flags, int* method, int* order)
+{
+    if (!css) return fail(QBP_E_INVALID, "null CSS decoder");
+    if (flags & (QBP_FLAG_LAYERED | SECOND_BP_BITS))
+        return fail(QBP_E_UNSUPPORTED, "flags 0x%x: Relay-BP, BP guided decimation, LSD and the layered schedule are not "
+                                       "available as a stage of the CSS decoder", flags);
+    int rc = cond_check(css->hb, B, max_iter, variant, flags & ~(QBP_FLAG_OSD0 | OSD_ALL_BITS));
+    if (rc) return rc;
+    // (what stage A's qbp_decode_batch_device would refuse: its argument check -- it has none for alpha, damping or the
+    // clip -- and, below, its choice of kernel)
+    if ((rc = check_decode_args(css->ha, B, max_iter, variant)) != QBP_OK) return rc;
+    for (qbp_handle* h : {css->ha, css->hb}) {
+        if ((rc = parse_osd_flags(h, flags & ~(uint32_t)QBP_FLAG_FORCE_FULL, true, method, order)) != QBP_OK) return rc;
+        if (bp_kernel(h, B, 0, 0, false) < 0) return fail(QBP_E_UNSUPPORTED, "a sector's matrix does not fit the forced kernel");
+    }
+    return QBP_OK;
+}
+
+// One stage on B records (device pointers): BP through `decode` into hard / conv / it / llr; with OSD the solutions of
+// the unconverged records, and x = solution there, hard elsewhere.  Without OSD, BP writes x itself.
+extern "C++" {       // (a template: not in the C linkage of the entry points around it)
+template <class Decode>
+static int css_stage(qbp_css* css, qbp_handle* h, int stage, const uint8_t* d_syn, long long B, const CssCall& c,
+                     uint8_t* d_x, uint8_t* d_conv, int32_t* d_it, hipStream_t s, bool redo, const Decode& decode)
+{
+    const bool osd = (c.flags & (QBP_FLAG_OSD0 | OSD_METHOD_BITS)) != 0;
+    int rc = decode(osd ? css->d_hard.p : d_x, d_conv, d_it, osd ? css->d_llr.p : nullptr);
+    if (rc || !osd) return rc;
+    unsigned long long* const count = css->d_fail_count.p + stage;
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(unsigned long long), s));
+    HIP_TRY(qbp::launch_window_fail_list(d_conv, B, css->d_fail_list.p, count, s));
+    qbp::OsdParams O{};
+    O.count = B; O.count_ptr = reinterpret_cast<const long long*>(count); O.list = css->d_fail_list.p;
+    O.syndromes = d_syn; O.llr = css->d_llr.p; O.hard = css->d_hard.p; O.solution = css->d_sol.p;
+    // (redo: a caller's syndrome need not lie in the column space of the matrix; a Monte-Carlo syndrome is H e)
+    if ((rc = osd_launch(h, O, B, s, redo, c.method, c.order)) != QBP_OK) return rc;
+    HIP_TRY(qbp::launch_css_select(css->d_hard.p, css->d_sol.p, d_conv, B, css->n, d_x, s));
+    return QBP_OK;
+}
+}  // extern "C++"
+
+static int css_reserve(qbp_css* css, size_t b, bool osd)
+{
+    const size_t n = css->n;
+    HIP_TRY(css->d_xa.reserve(b * n));
+    HIP_TRY(css->d_xb.reserve(b * n));
+    HIP_TRY(css->d_conv_a.reserve(b));
+    HIP_TRY(css->d_conv_b.reserve(b));
+    HIP_TRY(css->d_it_a.reserve(b));
+    HIP_TRY(css->d_it_b.reserve(b));
+    if (osd) {
+        HIP_TRY(css->d_hard.reserve(b * n));
+        HIP_TRY(css->d_sol.reserve(b * n));
+        HIP_TRY(css->d_llr.reserve(b * n));
+        HIP_TRY(css->d_fail_list.reserve(b));
+        HIP_TRY(css->d_fail_count.reserve(2));
+    }
+    return QBP_OK;
+}
+
+// Both stages on B records, buffers reserved: x_a, x_b, conv and iterations of both BP stages (device, none null).
+// from_errors: the syndromes are H e (the Monte-Carlo entries), so OSD needs no redo pass.
+static int css_run(qbp_css* css, const uint8_t* d_syn_a, const uint8_t* d_syn_b, long long B, const CssCall& c,
+                   uint8_t* d_xa, uint8_t* d_xb, uint8_t* d_conv_a, uint8_t* d_conv_b, int32_t* d_it_a, int32_t* d_it_b,
+                   bool from_errors, hipStream_t s)
+{
+    const uint32_t bp_flags = c.flags & QBP_FLAG_FORCE_FULL;
+    int rc = css_stage(css, css->ha, 0, d_syn_a, B, c, d_xa, d_conv_a, d_it_a, s, !from_errors,
+                       [&](uint8_t* hard, uint8_t* conv, int32_t* it, double* llr) {
+                           return qbp_decode_batch_device(css->ha, d_syn_a, c.prior_a, B, c.max_iter, c.variant, c.alpha,
+                                                          c.damping, c.clip_llr, bp_flags, hard, conv, it, llr, s);
+                       });
+    if (rc) return rc;
+    return css_stage(css, css->hb, 1, d_syn_b, B, c, d_xb, d_conv_b, d_it_b, s, !from_errors,
+                     [&](uint8_t* hard, uint8_t* conv, int32_t* it, double* llr) {
+                         return qbp_decode_batch_cond_device(css->hb, d_syn_b, d_xa, c.prior_b0, c.prior_b1, B, c.max_iter,
+                                                             c.variant, c.alpha, c.clip_llr, bp_flags, hard, conv, it, llr,
+                                                             s);
+                     });
+}
+
+void qbp_css_destroy(qbp_css* css)
+try {
+    if (!css) return;
+    DeviceScope on_device(css->device);
+    if (css->stream) (void)hipStreamDestroy(css->stream);
+    delete css;
+}
+catch (...) {
+}
+
+int qbp_css_create(qbp_handle* ha, qbp_handle* hb, qbp_css** out)
+try {
+    if (!out) return fail(QBP_E_INVALID, "out is null");
+    *out = nullptr;
+    if (!ha || !hb) return fail(QBP_E_INVALID, "null handle");
+    if (ha->device != hb->device)
+        return fail(QBP_E_INVALID, "the two handles are on devices %d and %d", ha->device, hb->device);
+    if (ha->n != hb->n) return fail(QBP_E_INVALID, "the two matrices have %d and %d columns", ha->n, hb->n);
+    struct Guard {
+        qbp_css* c;
+        ~Guard() { if (c) qbp_css_destroy(c); }
+    } guard{new qbp_css()};
+    qbp_css* css = guard.c;
+    css->ha = ha; css->hb = hb; css->device = ha->device; css->n = ha->n;
+    DeviceScope on_device(css->device);
+    HIP_TRY(on_device.err);
+    HIP_TRY(hipStreamCreateWithFlags(&css->stream, hipStreamNonBlocking));
+    guard.c = nullptr;
+    *out = css;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_css_set_option(qbp_css* css, int32_t option, int64_t value)
+try {
+    if (!css) return fail(QBP_E_INVALID, "null CSS decoder");
+    if (option != QBP_OPT_MC_WEIGHT_CHUNK) return fail(QBP_E_INVALID, "unknown option %d", option);
+    if (value < 0 || value > QBP_MC_OSD_MAX_TRIALS) return fail(QBP_E_INVALID, "trials per chunk out of [0, 2^20]");
+    css->opt_chunk = value;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// The sampler's cumulative thresholds (include/qbp.h): Z, X, Y
+static int css_thresholds(double px, double py, double pz, unsigned thr[3])
+{
+    for (double p : {px, py, pz})
+        if (!(p >= 0.0 && p <= 1.0)) return fail(QBP_E_INVALID, "Pauli probability %g out of [0, 1]", p);
+    if (!((pz + px) + py <= 1.0)) return fail(QBP_E_INVALID, "px + py + pz = %g exceeds 1", (pz + px) + py);
+    thr[0] = mc_threshold(pz); thr[1] = mc_threshold(pz + px); thr[2] = mc_threshold((pz + px) + py);
+    return QBP_OK;
+}
+
+int qbp_css_sample_errors(qbp_css* css, double px, double py, double pz, uint64_t seed, int64_t trial_begin, int64_t T,
+                          uint8_t* errors_a, uint8_t* errors_b)
+try {
+    if (!css) return fail(QBP_E_INVALID, "null CSS decoder");
+    unsigned thr[3];
+    const int rc = css_thresholds(px, py, pz, thr);
+    if (rc) return rc;
+    if (trial_begin < 0 || T < 0) return fail(QBP_E_INVALID, "trial_begin and T must be >= 0");
+    if (T == 0) return QBP_OK;
+    if (!errors_a || !errors_b) return fail(QBP_E_INVALID, "null output pointer");
+    DeviceScope on_device(css->device);
+    HIP_TRY(on_device.err);
+    const size_t n = css->n;
+    const long long chunk = std::min<long long>(T, std::max<long long>(1, ((long long)1 << 28) / (long long)n));
+    HIP_TRY(css->d_ea.reserve((size_t)chunk * n));
+    HIP_TRY(css->d_eb.reserve((size_t)chunk * n));
+    for (int64_t a = 0; a < T; a += chunk) {
+        const long long t = std::min<long long>(chunk, T - a);
+        HIP_TRY(qbp::launch_css_sample_pauli(css->d_ea.p, css->d_eb.p, css->n, t, trial_begin + a, seed, thr[0], thr[1],
+                                             thr[2], css->stream));
+        HIP_TRY(hipMemcpyAsync(errors_a + (size_t)a * n, css->d_ea.p, (size_t)t * n, hipMemcpyDeviceToHost, css->stream));
+        HIP_TRY(hipMemcpyAsync(errors_b + (size_t)a * n, css->d_eb.p, (size_t)t * n, hipMemcpyDeviceToHost, css->stream));
+        HIP_TRY(hipStreamSynchronize(css->stream));
+    }
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// The three priors of a host entry: none null, none NaN
+static int css_check_priors(const qbp_css* css, const double* prior_a, const double* prior_b0, const double* prior_b1)
+{
+    if (!prior_a || !prior_b0 || !prior_b1) return fail(QBP_E_INVALID, "null prior");
+    for (const double* p : {prior_a, prior_b0, prior_b1}) {
+        const int rc = check_prior(css->n, p, false);
+        if (rc) return rc;
+    }
+    return QBP_OK;
+}
+
+int qbp_css_decode_batch(qbp_css* css, const uint8_t* syn_a, const uint8_t* syn_b, int64_t B, const double* prior_a,
+                         const double* prior_b0, const double* prior_b1, int32_t max_iter, int32_t variant, double alpha,
+                         double damping, double clip_llr, uint32_t flags, uint8_t* x_a, uint8_t* x_b, uint8_t* conv_a,
+                         uint8_t* conv_b)
+try {
+    CssCall c{nullptr, nullptr, nullptr, max_iter, variant, alpha, damping, clip_llr, flags, 0, 0};
+    int rc = css_check(css, B, max_iter, variant, flags, &c.method, &c.order);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!syn_a || !syn_b) return fail(QBP_E_INVALID, "null input pointer");
+    if ((rc = css_check_priors(css, prior_a, prior_b0, prior_b1)) != QBP_OK) return rc;
+    if (B > QBP_MC_OSD_MAX_TRIALS)
+        return fail(QBP_E_UNSUPPORTED, "qbp_css_decode_batch takes at most %d records per call", QBP_MC_OSD_MAX_TRIALS);
+    DeviceScope on_device(css->device);
+    HIP_TRY(on_device.err);
+    const size_t n = css->n, b = (size_t)B;
+    const bool osd = (flags & (QBP_FLAG_OSD0 | OSD_METHOD_BITS)) != 0;
+    if ((rc = css_reserve(css, b, osd)) != QBP_OK) return rc;
+    HostStage st(css->stream);
+    const uint8_t* d_sa = st.in(css->d_syn_a, syn_a, b * css->ha->m);
+    const uint8_t* d_sb = st.in(css->d_syn_b, syn_b, b * css->hb->m);
+    c.prior_a = st.in(css->d_prior_a, prior_a, n);
+    c.prior_b0 = st.in(css->d_prior_b0, prior_b0, n);
+    c.prior_b1 = st.in(css->d_prior_b1, prior_b1, n);
+    // (x_a is stage B's input whether the caller wants it or not: the outputs are the chunk buffers)
+    st.out(css->d_xa, x_a, b * n);
+    st.out(css->d_xb, x_b, b * n);
+    st.out(css->d_conv_a, conv_a, b);
+    st.out(css->d_conv_b, conv_b, b);
+    if (st.failed()) return st.error();
+    return st.finish(css_run(css, d_sa, d_sb, B, c, css->d_xa.p, css->d_xb.p, css->d_conv_a.p, css->d_conv_b.p,
+                             css->d_it_a.p, css->d_it_b.p, false, css->stream));
+}
+QBP_ABI_CATCH
+
+// The Monte-Carlo entries after their checks: chunk by chunk [sample,] syndromes, the two stages, classification.
+// d_ea / d_eb: the stored errors of all T trials (device), or null to draw them with thr.
+static int css_mc_run(qbp_css* css, const CssCall& c, const uint8_t* d_ea, const uint8_t* d_eb, const unsigned* thr,
+                      uint64_t seed, int64_t trial_begin, int64_t T, int32_t distance, long long* d_counters, hipStream_t s)
+{
+    const size_t n = css->n, ma = css->ha->m, mb = css->hb->m;
+    const bool osd = (c.flags & (QBP_FLAG_OSD0 | OSD_METHOD_BITS)) != 0;
+    const long long dflt = std::max<long long>(1, std::min<long long>(QBP_MC_OSD_MAX_TRIALS, ((long long)1 << 28) / (long long)n));
+    const long long chunk = std::min<long long>(css->opt_chunk > 0 ? css->opt_chunk : dflt, T);
+    int rc = css_reserve(css, (size_t)chunk, osd);
+    if (rc) return rc;
+    if (!d_ea) {
+        HIP_TRY(css->d_ea.reserve((size_t)chunk * n));
+        HIP_TRY(css->d_eb.reserve((size_t)chunk * n));
+    }
+    HIP_TRY(css->d_syn_a.reserve((size_t)chunk * ma));
+    HIP_TRY(css->d_syn_b.reserve((size_t)chunk * mb));
+    for (int64_t a = 0; a < T; a += chunk) {
+        const long long t = std::min<long long>(chunk, T - a);
+        const uint8_t* ea = d_ea ? d_ea + (size_t)a * n : css->d_ea.p;
+        const uint8_t* eb = d_eb ? d_eb + (size_t)a * n : css->d_eb.p;
+        if (!d_ea)
+            HIP_TRY(qbp::launch_css_sample_pauli(css->d_ea.p, css->d_eb.p, css->n, t, trial_begin + a, seed, thr[0], thr[1],
+                                                 thr[2], s));
+        HIP_TRY(qbp::launch_window_syndrome(ea, t, (int)ma, css->n, css->ha->d_row_ptr.p, css->ha->d_col_idx.p,
+                                            css->d_syn_a.p, s));
+        HIP_TRY(qbp::launch_window_syndrome(eb, t, (int)mb, css->n, css->hb->d_row_ptr.p, css->hb->d_col_idx.p,
+                                            css->d_syn_b.p, s));
+        rc = css_run(css, css->d_syn_a.p, css->d_syn_b.p, t, c, css->d_xa.p, css->d_xb.p, css->d_conv_a.p, css->d_conv_b.p,
+                     css->d_it_a.p, css->d_it_b.p, true, s);
+        if (rc) return rc;
+        qbp::CssClassify K{};
+        K.T = t; K.n = css->n; K.ma = (int)ma; K.mb = (int)mb;
+        K.e_a = ea; K.x_a = css->d_xa.p; K.e_b = eb; K.x_b = css->d_xb.p;
+        K.conv_a = css->d_conv_a.p; K.conv_b = css->d_conv_b.p; K.it_a = css->d_it_a.p; K.it_b = css->d_it_b.p;
+        K.row_ptr_a = css->ha->d_row_ptr.p; K.col_idx_a = css->ha->d_col_idx.p;
+        K.row_ptr_b = css->hb->d_row_ptr.p; K.col_idx_b = css->hb->d_col_idx.p;
+        K.l_a = css->in_a.d_lx_cols.p; K.l_b = css->in_b.d_lx_cols.p;
+        K.half_distance = distance / 2; K.counters = d_counters;
+        HIP_TRY(qbp::launch_css_classify(K, s));
+    }
+    return QBP_OK;
+}
+
+// Both Monte-Carlo host entries: errors_a null draws the errors.
+static int css_mc_host(qbp_css* css, const uint8_t* La, int32_t ka, const uint8_t* Lb, int32_t kb, int32_t distance,
+                       const uint8_t* errors_a, const uint8_t* errors_b, const unsigned* thr, uint64_t seed,
+                       int64_t trial_begin, int64_t T, const double* prior_a, const double* prior_b0,
+                       const double* prior_b1, CssCall c, int64_t* counters)
+{
+    int rc = css_check(css, T, c.max_iter, c.variant, c.flags, &c.method, &c.order);
+    if (rc) return rc;
+    if (!counters) return fail(QBP_E_INVALID, "counters is null");
+    for (int32_t k : {ka, kb})
+        if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k = %d logical operators (need 0..64)", k);
+    if ((ka > 0 && !La) || (kb > 0 && !Lb)) return fail(QBP_E_INVALID, "null logical operators");
+    if ((rc = css_check_priors(css, prior_a, prior_b0, prior_b1)) != QBP_OK) return rc;
+    const bool stored = thr == nullptr;
+    if (stored && T > 0 && (!errors_a || !errors_b)) return fail(QBP_E_INVALID, "errors is null");
+    if (stored) std::fill(counters, counters + 3 * QBP_NUM_COUNTERS, (int64_t)0);
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(css->device);
+    HIP_TRY(on_device.err);
+    const size_t n = css->n;
+    hipStream_t s = css->stream;
+    if ((rc = css->in_a.prepare_lx(n, La, ka, s)) != QBP_OK || (rc = css->in_b.prepare_lx(n, Lb, kb, s)) != QBP_OK) return rc;
+    HostStage st(s);
+    c.prior_a = st.in(css->d_prior_a, prior_a, n);
+    c.prior_b0 = st.in(css->d_prior_b0, prior_b0, n);
+    c.prior_b1 = st.in(css->d_prior_b1, prior_b1, n);
+    long long* d_cnt = st.zeroed(css->d_counters, 3 * QBP_NUM_COUNTERS);
+    st.add(counters, d_cnt, 3 * QBP_NUM_COUNTERS);
+    const uint8_t* d_ea = stored ? st.in(css->d_ea, errors_a, (size_t)T * n) : nullptr;
+    const uint8_t* d_eb = stored ? st.in(css->d_eb, errors_b, (size_t)T * n) : nullptr;
+    if (st.failed()) return st.error();
+    return st.finish(css_mc_run(css, c, d_ea, d_eb, thr, seed, trial_begin, T, distance, d_cnt, s));
+}
+
+int qbp_css_mc_run(qbp_css* css, const uint8_t* La, int32_t ka, const uint8_t* Lb, int32_t kb, int32_t distance,
+                   double px, double py, double pz, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                   const double* prior_a, const double* prior_b0, const double* prior_b1, int32_t max_iter,
+                   int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                   int64_t counters[3 * QBP_NUM_COUNTERS])
+try {
+    unsigned thr[3];
+    const int rc = css_thresholds(px, py, pz, thr);
+    if (rc) return rc;
+    if (trial_begin < 0) return fail(QBP_E_INVALID, "trial_begin must be >= 0");
+    if (trial_end < trial_begin) return fail(QBP_E_INVALID, "trial_end before trial_begin");
+    return css_mc_host(css, La, ka, Lb, kb, distance, nullptr, nullptr, thr, seed, trial_begin, trial_end - trial_begin,
+                       prior_a, prior_b0, prior_b1,
+                       CssCall{nullptr, nullptr, nullptr, max_iter, variant, alpha, damping, clip_llr, flags, 0, 0}, counters);
+}
+QBP_ABI_CATCH
+
+int qbp_css_mc_run_errors(qbp_css* css, const uint8_t* La, int32_t ka, const uint8_t* Lb, int32_t kb, int32_t distance,
+                          const uint8_t* errors_a, const uint8_t* errors_b, int64_t T, const double* prior_a,
+                          const double* prior_b0, const double* prior_b1, int32_t max_iter, int32_t variant, double alpha,
+                          double damping, double clip_llr, uint32_t flags, int64_t counters[3 * QBP_NUM_COUNTERS])
+try {
+    if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
+    return css_mc_host(css, La, ka, Lb, kb, distance, errors_a, errors_b, nullptr, 0, 0, T, prior_a, prior_b0, prior_b1,
+                       CssCall{nullptr, nullptr, nullptr, max_iter, variant, alpha, damping, clip_llr, flags, 0, 0}, counters);
 }
 QBP_ABI_CATCH
 

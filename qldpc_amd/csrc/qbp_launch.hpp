@@ -19,6 +19,8 @@ struct OsdOrderBigArgs;
 struct RelayParams;
 struct LayeredParams;
 struct GdParams;
+struct CondParams;
+struct CssClassify;
 struct LsdParams;
 struct WindowCommit;
 
@@ -144,6 +146,14 @@ hipError_t launch_relay(bool records, const RelayParams& P, int grid, int thread
 hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
 hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
+// qbp_tu_cond.hip: bp_cond_kernel<variant> (sum-product or min-sum; a prior per record), and the glue kernels of the
+// two-stage CSS decoder (qbp_cond.hpp): t1 <= t2 <= t3 are the sampler's cumulative thresholds (Z, X, Y)
+hipError_t launch_cond(int variant, const CondParams& P, int grid, int threads, size_t lds, hipStream_t s);
+hipError_t launch_css_sample_pauli(uint8_t* e_a, uint8_t* e_b, int n, long long T, long long trial_begin,
+                                   unsigned long long seed, unsigned t1, unsigned t2, unsigned t3, hipStream_t s);
+hipError_t launch_css_select(const uint8_t* hard, const uint8_t* sol, const uint8_t* conv, long long T, int n, uint8_t* x,
+                             hipStream_t s);
+hipError_t launch_css_classify(const CssClassify& P, hipStream_t s);
 // qbp_tu_lsd.hip: lsd_kernel<records> (batch build or Monte-Carlo failure records), one wavefront per record
 hipError_t launch_lsd(bool records, const LsdParams& P, unsigned grid, size_t lds, hipStream_t s);
 // qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)

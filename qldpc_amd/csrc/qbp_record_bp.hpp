@@ -1,18 +1,19 @@
-// The per-record BP iteration with the messages in LDS, stated once for bp_relay_kernel (qbp_relay.hpp) and
-// bp_gd_kernel (qbp_gd.hpp).
+// The per-record BP iteration with the messages in LDS, stated once for bp_relay_kernel (qbp_relay.hpp),
+// bp_gd_kernel (qbp_gd.hpp) and bp_cond_kernel (qbp_cond.hpp).
 //
-// Both kernels run one workgroup per record on the tables of the general-H kernel (qbp_generic.hpp: class-blocked,
+// The kernels run one workgroup per record on the tables of the general-H kernel (qbp_generic.hpp: class-blocked,
 // transposed message layout; srow / epos / vpos / vrow / svar), on ONE array of E messages updated in place -- a slot
 // holds the variable->check message before the check step and the check->variable message after it -- with two
 // workgroup barriers per iteration, which stay in the kernels' own loops:
 //   record_check_step_minsum  one thread per check of weight <= 8 (check_row of qbp_check.hpp), rows beyond that in passes;
+//   record_check_step_sumproduct  the same for the exact sum-product row (bp_cond_kernel);
 //   -- barrier A --
 //   record_variable_step   one thread per variable: V = colsum(R) + bias (ascending check), Q = V - R in place, and the
 //                          incremental syndrome test of the general-H kernel (parity bits in LDS, a counter of
 //                          unsatisfied checks);
 //   -- barrier B --
 //   counter zero <=> H hard == s.
-// Around the iteration: the parameter blocks both kernels embed (RecordTables, RecordIo), the record prologue
+// Around the iteration: the parameter blocks the kernels embed (RecordTables, RecordIo), the record prologue
 // (record_load_syndrome, record_prior_to_edges), the classification of a Monte-Carlo failure record (record_classify),
 // the hand-out of the next record (record_next_item) and the workgroup size (record_threads).
 // What a kernel keeps for itself: its LDS carve-up (it fills a RecordLds), its loop around the iteration (legs, rounds),
@@ -174,17 +175,17 @@ __device__ __forceinline__ void record_prior_to_edges(const RecordTables& G, con
                 double q[DD];                                                                  \
                 _Pragma("unroll") for (int j = 0; j < DD; ++j) q[j] = M[base + j * cnt];       \
                 auto put = [&](int j, double v) { M[base + j * cnt] = v; };                    \
-                check_row<2, DD, true>(q, sbit, alpha, true, RECORD_NP_TAB, put);              \
+                check_row<VARIANT, DD, true>(q, sbit, alpha, true, RECORD_NP_TAB, put);        \
             }                                                                                  \
         } break;
 
-__device__ __forceinline__ void record_check_step_minsum(const RecordTables& G, const RecordLds& S, double* Lw, double alpha)
+// The checks of weight <= 8 of either rule (VARIANT 2: min-sum, 0: the exact sum-product row on numpy's tables)
+template <int VARIANT>
+__device__ __forceinline__ void record_check_rows(const RecordTables& G, const RecordLds& S, double alpha)
 {
     constexpr int RC = GENERIC_MAX_ROW_CLASS;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
     double* const M = S.M;
-    const int first_long = G.row_off[RC + 1], n_long = G.row_off[RC + 2] - first_long;
-    const int lbase = G.row_base[RC + 1], n_ledges = G.E - lbase;
     for (int wp0 = tid - lane; wp0 < G.rpad_off[RC + 1]; wp0 += nt) {
         // one wavefront = 64 consecutive work items of ONE weight class (scalar class search)
         const int wpu = __builtin_amdgcn_readfirstlane(wp0);
@@ -199,6 +200,17 @@ __device__ __forceinline__ void record_check_step_minsum(const RecordTables& G, 
             default: break;
         }
     }
+}
+#undef QBP_RECORD_ROW_CLASS
+
+__device__ __forceinline__ void record_check_step_minsum(const RecordTables& G, const RecordLds& S, double* Lw, double alpha)
+{
+    constexpr int RC = GENERIC_MAX_ROW_CLASS;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    double* const M = S.M;
+    const int first_long = G.row_off[RC + 1], n_long = G.row_off[RC + 2] - first_long;
+    const int lbase = G.row_base[RC + 1], n_ledges = G.E - lbase;
+    record_check_rows<2>(G, S, alpha);
     // ---- checks of weight > 8: the minimum search one thread per check, the messages one per edge
     if (n_long > 0) {                                           // uniform
         for (int i = tid; i < n_long; i += nt) {
@@ -216,7 +228,39 @@ __device__ __forceinline__ void record_check_step_minsum(const RecordTables& G, 
         }
     }
 }
-#undef QBP_RECORD_ROW_CLASS
+
+// ---- check step, sum-product: the same on numpy's tanh / arctanh tables (bp_cond_kernel; bp_gd_kernel states these rows
+// in its own body: qbp_gd.hpp says why)
+__device__ __forceinline__ void record_check_step_sumproduct(const RecordTables& G, const RecordLds& S, double* Lw,
+                                                             double alpha)
+{
+    constexpr int RC = GENERIC_MAX_ROW_CLASS;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    double* const M = S.M;
+    const int first_long = G.row_off[RC + 1], n_long = G.row_off[RC + 2] - first_long;
+    const int lbase = G.row_base[RC + 1], n_ledges = G.E - lbase;
+    record_check_rows<0>(G, S, alpha);
+    // ---- checks of weight > 8: the per-edge work one thread per edge, the sequential part (np.prod in ascending column
+    //      order) one thread per check
+    if (n_long > 0) {                                           // uniform
+        for (int k = tid; k < n_ledges; k += nt) M[lbase + k] = tanh_half_msg<0>(M[lbase + k], RECORD_NP_TAB);
+        __syncthreads();
+        for (int i = tid; i < n_long; i += nt) {
+            const int deg = G.srow_deg[first_long + i];
+            const int p0 = G.epos[G.srow_e0[first_long + i]];   // entries contiguous from here
+            double prod = M[p0];
+            for (int j = 1; j < deg; ++j) prod = prod * M[p0 + j];
+            Lw[3 * i] = prod;
+        }
+        __syncthreads();
+        for (int k = tid; k < n_ledges; k += nt) {
+            const int i = G.long_edge_row[k];
+            const int w = first_long + i;
+            const unsigned sbit = (S.synw[w >> 5] >> (w & 31)) & 1u;
+            M[lbase + k] = sp_message<0>(Lw[3 * i], M[lbase + k], sbit, RECORD_NP_TAB);
+        }
+    }
+}
 
 // ---- variable step + incremental syndrome test ----------------------------------------------------------------------
 // Runs after barrier A.  V[x] = colsum(R) + bias_of(x), added in ascending check order; the new variable->check message
@@ -241,14 +285,18 @@ __device__ __forceinline__ void record_check_step_minsum(const RecordTables& G, 
                 if (val < 0.0) {                                                               \
                     _Pragma("unroll") for (int j = 0; j < DD; ++j) flip(G.vrow[base + j * cnt]);   \
                 }                                                                              \
-                _Pragma("unroll") for (int j = 0; j < DD; ++j) M[o[j]] = q_of(val, r[j]);      \
+                _Pragma("unroll") for (int j = 0; j < DD; ++j) M[o[j]] = q_of(val, r[j], o[j]); \
             }                                                                                  \
         } break;
 
-template <bool CLIP, typename Bias>
+// edge_rule (bp_cond_kernel's min-sum): edge_rule(o, q) is stored in slot o instead of q; the other kernels pass none.
+struct RecordNoEdgeRule {};
+template <bool CLIP, typename Bias, typename EdgeRule = RecordNoEdgeRule>
 __device__ __forceinline__ void record_variable_step(const RecordTables& G, const RecordLds& S, int p, int syn_weight,
-                                                     double clip, const Bias& bias_of)
+                                                     double clip, const Bias& bias_of,
+                                                     const EdgeRule& edge_rule = EdgeRule{})
 {
+    constexpr bool EDGE_RULE = !__is_same(EdgeRule, RecordNoEdgeRule);
     constexpr int CC = GENERIC_MAX_COL_CLASS;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
     const int mw = (G.m + 31) >> 5;
@@ -267,14 +315,13 @@ __device__ __forceinline__ void record_variable_step(const RecordTables& G, cons
         const unsigned old = atomicXor(&pbuf[cw >> 5], bit);
         delta += (old & bit) ? -1 : 1;
     };
-    auto q_of = [&](double val, double r) {
-        const double q = val - r;
+    auto q_of = [&](double val, double r, int o) {
+        double q = val - r;
         if constexpr (CLIP) {
             const double y = q < -clip ? -clip : q;
-            return y > clip ? clip : y;
-        } else {
-            return q;
+            q = y > clip ? clip : y;
         }
+        if constexpr (EDGE_RULE) return (double)edge_rule(o, q); else return q;
     };
     for (int x = tid; x < G.col_off[1]; x += nt) V[x] = 0.0 + bias_of(x);     // no check: an empty column sum
     for (int xp0 = tid - lane; xp0 < G.cpad_off[CC + 1]; xp0 += nt) {
@@ -303,7 +350,7 @@ __device__ __forceinline__ void record_variable_step(const RecordTables& G, cons
             for (int k = k0; k < k1; ++k) flip(G.vrow[k]);
         for (int k = k0; k < k1; ++k) {
             const int o = G.vpos[k];
-            M[o] = q_of(val, M[o]);
+            M[o] = q_of(val, M[o], o);
         }
     }
     if (delta) atomicAdd(&S.unsat[p], delta);

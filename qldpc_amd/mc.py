@@ -18,6 +18,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
     python -m qldpc_amd.mc --code 144 --p 0.05 --osd --spectrum out.npz
                                      (residual-weight spectra and the iteration histogram per point: run_spectrum)
+    python -m qldpc_amd.mc --code 144 --depolarizing 0.01 0.02 --trials 100000 --osd
+                                     (Pauli noise on both sectors, two-stage X/Z-correlated decoding: run_depolarizing)
     python -m qldpc_amd.mc --code 144 --weights 4 6 8 10 12 --prior-p 0.01 --trials 1000000 --osd --ler-at 0.001 0.003 0.01
                                      (errors of fixed weight, and the LER at any p from their failure fractions:
                                       run_weights, ler_from_weights)
@@ -204,6 +206,56 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         begin, end = shard_range(trials, rank, world)
         table[i] = runner(code, p, begin, end)
     return all_reduce(table) if all_reduce is not None else table
+
+
+def pauli_rates(p, bias=(1, 1, 1)):
+    """(px, py, pz) of Pauli noise of total strength ``p`` split in the proportions ``bias`` = (X, Y, Z); (1, 1, 1)
+    is depolarizing noise."""
+    b = [float(x) for x in bias]
+    if len(b) != 3 or min(b) < 0.0 or sum(b) <= 0.0:
+        raise ValueError(f"bias must be three weights >= 0 with a positive sum, got {bias!r}")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"p must be in [0, 1], got {p!r}")
+    return tuple(float(p) * x / sum(b) for x in b)
+
+
+def run_depolarizing(code_name, ps, trials, *, osd=False, osd_method="cs", osd_order=0, bias=(1, 1, 1), correlated=True,
+                     seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, rank=0,
+                     world=1, device=0):
+    """Logical error rates of a CSS code under Pauli noise, both sectors decoded (qbp_css_mc_run): returns the GLOBAL
+    table int64[len(ps), 3, 12] -- per point the counter rows of sector A (Hx, Lx: Z and Y errors), of sector B (Hz, Lz:
+    X and Y errors) and of the trial as a whole (row 2: [1] is a logical error in either sector).
+
+    ``correlated``: the second stage's prior is conditioned on the first stage's correction (``css.pauli_priors``);
+    False passes the marginal prior of sector B for both cases, which decodes the sectors independently on the same
+    errors -- the baseline.  ``bias``: the proportions of X, Y and Z in ``p``.  Trials are sharded over ranks as in
+    ``run_sweep`` and the tables summed with one all-reduce; errors are keyed by the global trial index, so the table
+    does not depend on the world size."""
+    from . import bp, css
+    flags = osd_run_flags(osd, osd_method, osd_order)
+    code = codes.load_code(code_name)
+    rates = [pauli_rates(p, bias) for p in ps]         # (before any GPU work)
+    priors = []
+    for px, py, pz in rates:
+        pa, b0, b1 = css.pauli_priors(px, py, pz, code.n)
+        if not correlated:
+            b0 = b1 = css.marginal_prior_b(px, py, pz, code.n)
+        priors.append((pa, b0, b1))
+    dec = _lib.CssDecoder(bp.decoder_for(code.Hx, device=device), bp.decoder_for(code.Hz, device=device))
+    begin, end = shard_range(trials, rank, world)
+    table = np.zeros((len(ps), 3, NUM_COUNTERS), np.int64)
+    for i, ((px, py, pz), (pa, b0, b1)) in enumerate(zip(rates, priors)):
+        dec.mc_run(code.Lx, code.Lz, code.distance, px, py, pz, pa, b0, b1, begin, end, seed=seed, max_iter=max_iter,
+                   variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags, counters=table[i])
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+        t = torch.from_numpy(table)
+        if dist.get_backend() == "nccl":
+            t = t.to(torch.device("cuda", device))
+        dist.all_reduce(t)
+        table = t.cpu().numpy()
+    return table
 
 
 def dem_prior(probs) -> np.ndarray:
@@ -743,6 +795,13 @@ def main(argv=None):
     ap.add_argument("--predictions-out", default=None, metavar="PRED.npy",
                     help="with --shots: write the predictions (uint64 masks, bit l = observable l) of this rank's "
                          "shots; with several ranks the file name gets .rank<r> before its extension")
+    ap.add_argument("--depolarizing", type=float, nargs="+", default=None, metavar="P",
+                    help="Pauli noise of total strength P on both sectors of the code, decoded in two stages with the "
+                         "second stage's prior conditioned on the first (run_depolarizing); with --osd")
+    ap.add_argument("--bias", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("X", "Y", "Z"),
+                    help="with --depolarizing: the proportions of X, Y and Z errors (default 1 1 1)")
+    ap.add_argument("--independent", action="store_true",
+                    help="with --depolarizing: decode the two sectors independently (the baseline)")
     ap.add_argument("--trials", type=int, default=10000)                          # :36
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--budgets", type=int, nargs="+", default=None,
@@ -848,6 +907,18 @@ def main(argv=None):
             ap.error("--layered does not combine with --budgets, --spectrum or --shots")
         if args.variant == "damped":
             ap.error("--layered needs --variant sum-product or min-sum")
+    if args.depolarizing is not None:
+        if (args.dem is not None or args.phenomenological is not None or args.shots is not None or args.budgets is not None
+                or args.spectrum is not None or args.weights is not None or relay is not None or gd is not None
+                or lsd is not None or args.layered):
+            ap.error("--depolarizing combines with --osd only")
+        if args.variant == "damped":
+            ap.error("--depolarizing needs --variant sum-product or min-sum")
+        try:
+            for p in args.depolarizing:
+                pauli_rates(p, args.bias)
+        except ValueError as e:
+            ap.error(f"--depolarizing: {e}")
     if args.budgets is not None:
         try:
             _lib.check_budgets(args.budgets)
@@ -962,6 +1033,30 @@ def main(argv=None):
     common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
                   damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
                   osd_order=args.osd_order, osd_large=args.osd_large, device=local)
+    if args.depolarizing is not None:
+        kw = {k: common[k] for k in ("seed", "max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",
+                                     "osd_order", "device")}
+        t0 = time.perf_counter()
+        table = run_depolarizing(args.code, args.depolarizing, args.trials, bias=tuple(args.bias),
+                                 correlated=not args.independent, rank=rank, world=world, **kw)
+        dt = time.perf_counter() - t0
+        if rank == 0:
+            rows = ("sector_a", "sector_b", "joint")
+            result = {"code": args.code, "depolarizing": list(args.depolarizing), "bias": list(args.bias),
+                      "correlated": not args.independent, "trials": args.trials, "max_iter": args.max_iter,
+                      "variant": args.variant, "osd": args.osd, "world_size": world, "seconds": dt,
+                      "points": [{"p": p, **{name: {k: int(v) for k, v in zip(_lib.COUNTER_NAMES, row)}
+                                             for name, row in zip(rows, point)},
+                                  "ler": int(point[2][1]) / max(int(point[2][0]), 1)}
+                                 for p, point in zip(args.depolarizing, table)]}
+            print(json.dumps(result))
+            if args.out:
+                with open(args.out, "w") as f:
+                    json.dump(result, f, indent=1)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
     if shot_data is not None:
         H, L, probs = dem_model
         kw = {k: common[k] for k in ("max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",

@@ -40,6 +40,8 @@ UNITS += [("qbp_tu_gd.hip", [])]
 UNITS += [("qbp_tu_window.hip", [])]
 # Localized statistics decoding (qbp_lsd_batch, QBP_FLAG_LSD): lsd_kernel<records>
 UNITS += [("qbp_tu_lsd.hip", [])]
+# BP with a prior per record (qbp_decode_batch_cond): bp_cond_kernel<variant>, and the glue kernels of qbp_css_*
+UNITS += [("qbp_tu_cond.hip", [])]
 
 
 def demangle(sym):
