@@ -2,8 +2,9 @@
 CPU oracle's pieces: the Pauli sampler (Philox in numpy, as tests/weight_oracle.py), the conditional prior per record,
 the chain (oracle.decode_batch record by record with the record's own prior vector, oracle.osd0 or
 tests/osd_order_oracle.py on what BP leaves unconverged) and the three counter rows (oracle.classify_trials per sector
-plus the joint row).  Also the hypergraph product of the Steane matrix with itself, a CSS pair with irregular columns
-and k = 16."""
+plus the joint row).  Also the hypergraph product of two classical matrices: the Steane matrix with itself, a CSS pair
+with irregular columns and k = 16, and with a 4 x 5 chain, a pair whose sectors differ (15 x 47 and 28 x 47, k = 4),
+with per-qubit biased priors for it."""
 import numpy as np
 
 import osd_order_oracle
@@ -85,7 +86,15 @@ def sector_counters(H, L, distance, errors, x, conv, iters):
 
 def counters(Hx, Hz, Lx, Lz, distance, e_a, e_b, prior_a, prior_b0, prior_b1, **kw):
     """qbp_css_mc_run_errors: int64[3, 12]."""
-    x_a, x_b, conv_a, conv_b, it_a, it_b = decode(Hx, Hz, _syn(Hx, e_a), _syn(Hz, e_b), prior_a, prior_b0, prior_b1, **kw)
+    decoded = decode(Hx, Hz, _syn(Hx, e_a), _syn(Hz, e_b), prior_a, prior_b0, prior_b1, **kw)
+    return classify(Hx, Hz, Lx, Lz, distance, e_a, e_b, decoded)
+
+
+def classify(Hx, Hz, Lx, Lz, distance, e_a, e_b, decoded):
+    """The three counter rows of what ``decode`` returned on the syndromes of (e_a, e_b): the decode does not look at
+    the logical operators, so one decode serves every (Lx, Lz), k = 0 included."""
+    x_a, x_b, conv_a, conv_b, it_a, it_b = decoded
+    Lx, Lz = np.asarray(Lx, np.uint8), np.asarray(Lz, np.uint8)
     out = np.zeros((3, 12), np.int64)
     out[0] = sector_counters(Hx, Lx, distance, e_a, x_a, conv_a, it_a)
     out[1] = sector_counters(Hz, Lz, distance, e_b, x_b, conv_b, it_b)
@@ -154,13 +163,95 @@ def logicals(H_commute, H_stab):
     return np.array(out, np.uint8).reshape(len(out), np.asarray(H_stab).shape[1])
 
 
-def hgp_steane():
-    """Hypergraph product of STEANE_H (3 x 7) with itself -> (Hx 21 x 58, Hz 21 x 58, Lx 16 x 58, Lz 16 x 58): the
-    [[58, 16, 3]] code; column weights 2 to 6 in both matrices.  Hx Lz^T = Hz Lx^T = Hx Hz^T = 0."""
-    H = STEANE_H
-    r, n = H.shape
-    Hx = np.hstack([np.kron(H, np.eye(n, dtype=np.uint8)), np.kron(np.eye(r, dtype=np.uint8), H.T)]) & 1
-    Hz = np.hstack([np.kron(np.eye(n, dtype=np.uint8), H), np.kron(H.T, np.eye(r, dtype=np.uint8))]) & 1
+CHAIN = np.array([[1, 1, 0, 0, 0], [0, 1, 1, 0, 0], [0, 0, 1, 1, 0], [0, 0, 0, 1, 1]], np.uint8)    # 4 x 5, full rank
+
+
+def hgp(H1, H2):
+    """Hypergraph product of two classical matrices H1 (r1 x n1) and H2 (r2 x n2) -> (Hx, Hz, Lx, Lz) on
+    n1 n2 + r1 r2 qubits: Hx = [H1 (x) I_n2 | I_r1 (x) H2^T] with r1 n2 rows, Hz = [I_n1 (x) H2 | H1^T (x) I_r2] with
+    n1 r2 rows.  Hx Lz^T = Hz Lx^T = Hx Hz^T = 0.  With H1 != H2 the two sectors differ in shape and weights."""
+    H1, H2 = np.asarray(H1, np.uint8), np.asarray(H2, np.uint8)
+    (r1, n1), (r2, n2) = H1.shape, H2.shape
+    eye = lambda k: np.eye(k, dtype=np.uint8)
+    Hx = np.hstack([np.kron(H1, eye(n2)), np.kron(eye(r1), H2.T)]) & 1
+    Hz = np.hstack([np.kron(eye(n1), H2), np.kron(H1.T, eye(r2))]) & 1
     Lx = logicals(Hz, Hx)          # X-type logicals commute with the Z checks; sector A's residuals live here
     Lz = logicals(Hx, Hz)
     return Hx.astype(np.uint8), Hz.astype(np.uint8), Lx, Lz
+
+
+def hgp_steane():
+    """Hypergraph product of STEANE_H (3 x 7) with itself -> (Hx 21 x 58, Hz 21 x 58, Lx 16 x 58, Lz 16 x 58): the
+    [[58, 16, 3]] code; column weights 2 to 6 in both matrices."""
+    return hgp(STEANE_H, STEANE_H)
+
+
+def hgp_asymmetric(tag):
+    """The two orientations of STEANE_H (3 x 7) x CHAIN (4 x 5), n = 47, k = 4: "wide_a" -> Hx 15 x 47 (column weights
+    1 .. 3, rows up to 6), Hz 28 x 47 (columns 1 .. 4, rows up to 5); "wide_b" -> the shapes exchanged."""
+    return hgp(STEANE_H, CHAIN) if tag == "wide_a" else hgp(CHAIN, STEANE_H)
+
+
+def biased_priors(n, seed=7):
+    """Per-qubit, biased Pauli rates and their three prior vectors (the formulas of qldpc_amd.css.pauli_priors,
+    per qubit): -> (prior_a, prior_b0, prior_b1) float64[n].  px ~ 0.02, py ~ 0.015, pz ~ 0.03, each spread over the
+    qubits, so no vector is constant, pz != py and prior_b1 = log(pz / py) takes both signs."""
+    rng = np.random.default_rng(seed)
+    px = 0.02 * rng.uniform(0.8, 1.25, n)
+    py = 0.015 * rng.uniform(0.5, 2.0, n)
+    pz = 0.03 * rng.uniform(0.8, 1.25, n)
+    return np.log((1 - py - pz) / (py + pz)), np.log((1 - px - py - pz) / px), np.log(pz / py)
+
+
+BIASED_RATES = (0.02, 0.015, 0.03)       # the sampler's scalar (px, py, pz) that go with biased_priors
+
+
+# ---- the inputs of tests/test_gpu_css_shapes.py, and their statement computed once -----------------------------------
+# The sampler takes scalar rates and the priors are per qubit: mismatched on purpose, a decoder is under test and not
+# a logical error rate.  Unconverged trials of the 2000 on the statement (row 0 / row 1, [6]), sum-product: wide_a
+# 699 / 19 to 25 (with the OSD mode: sector B's prior follows sector A's correction), wide_b 34 / 372 to 379; min-sum
+# (alpha 0.8): wide_a 401 / 64 to 66, wide_b 114 / 412 to 415.  tests/test_css_cpu.py asserts the five of each.
+ASYM_T, ASYM_B, ASYM_MAX_ITER, ASYM_DISTANCE = 2000, 200, 30, 3
+ASYM_SEED, ASYM_BEGIN = (9 << 32) + 5, (1 << 32) - 100           # the trial indices cross 2^32
+MIN_SUM = 2                                                      # QBP_MIN_SUM
+ASYM_MODES = {"none": dict(osd=None), "osd0": dict(osd=0), "cs7": dict(osd=("cs", 7)),
+              "minsum": dict(osd=None, variant=MIN_SUM, alpha=0.8), "minsum_osd0": dict(osd=0, variant=MIN_SUM, alpha=0.8)}
+_ASYM = {}
+
+
+def asym_inputs(tag):
+    """"wide_a" / "wide_b" -> the code, ASYM_T errors and the biased priors (shared: do not write to them)."""
+    if tag not in _ASYM:
+        Hx, Hz, Lx, Lz = hgp_asymmetric(tag)
+        n = Hx.shape[1]
+        ea, eb = sample_pauli(n, *BIASED_RATES, ASYM_SEED, ASYM_BEGIN, ASYM_T)
+        for a in (Hx, Hz, Lx, Lz, ea, eb):
+            a.setflags(write=False)
+        _ASYM[tag] = dict(Hx=Hx, Hz=Hz, Lx=Lx, Lz=Lz, d=ASYM_DISTANCE, n=n, ea=ea, eb=eb, priors=biased_priors(n))
+    return _ASYM[tag]
+
+
+def asym_decoded(tag, mode):
+    """``decode`` on the syndromes of the ASYM_T errors, once per (tag, mode)."""
+    s = asym_inputs(tag)
+    if ("decoded", mode) not in s:
+        s["decoded", mode] = decode(s["Hx"], s["Hz"], _syn(s["Hx"], s["ea"]), _syn(s["Hz"], s["eb"]), *s["priors"],
+                                    max_iter=ASYM_MAX_ITER, **ASYM_MODES[mode])
+    return s["decoded", mode]
+
+
+def asym_statement(tag, mode, Lx=None, Lz=None):
+    """The counters [3][12] of the ASYM_T trials (a fresh array), with other logical operators if given."""
+    s = asym_inputs(tag)
+    return classify(s["Hx"], s["Hz"], s["Lx"] if Lx is None else Lx, s["Lz"] if Lz is None else Lz, s["d"], s["ea"],
+                    s["eb"], asym_decoded(tag, mode))
+
+
+def asym_batch_syndromes(s):
+    """The syndromes of the first ASYM_B errors, every 13th of sector A and every 17th of sector B with a fifth of its
+    bits flipped: any syndrome is legal for a decode call, and these leave BP unconverged."""
+    rng = np.random.default_rng(4)
+    syn_a, syn_b = _syn(s["Hx"], s["ea"][:ASYM_B]), _syn(s["Hz"], s["eb"][:ASYM_B])
+    syn_b[::17] ^= (rng.random(syn_b[::17].shape) < 0.2).astype(np.uint8)
+    syn_a[::13] ^= (rng.random(syn_a[::13].shape) < 0.2).astype(np.uint8)
+    return syn_a, syn_b

@@ -80,6 +80,98 @@ def test_hgp_helper():
         assert w.min() >= 1 and len(set(w.tolist())) > 1      # irregular column weights
 
 
+def test_hgp_steane_is_the_product_of_the_steane_matrix_with_itself():
+    """hgp(STEANE, STEANE) returns the four arrays of the construction hgp_steane() had before hgp() existed, stated
+    here again, byte for byte (shape and dtype included)."""
+    H = co.STEANE_H
+    r, n = H.shape
+    Hx = np.hstack([np.kron(H, np.eye(n, dtype=np.uint8)), np.kron(np.eye(r, dtype=np.uint8), H.T)]) & 1
+    Hz = np.hstack([np.kron(np.eye(n, dtype=np.uint8), H), np.kron(H.T, np.eye(r, dtype=np.uint8))]) & 1
+    old = (Hx.astype(np.uint8), Hz.astype(np.uint8), co.logicals(Hz, Hx), co.logicals(Hx, Hz))
+    for got in (co.hgp_steane(), co.hgp(co.STEANE_H, co.STEANE_H)):
+        assert len(got) == 4
+        for x, y in zip(got, old):
+            assert x.dtype == y.dtype == np.uint8 and x.shape == y.shape and x.tobytes() == y.tobytes()
+
+
+@pytest.mark.parametrize("tag", ["wide_a", "wide_b"])
+def test_hgp_asymmetric_pair(tag):
+    Hx, Hz, Lx, Lz = co.hgp_asymmetric(tag)
+    small, large = ((15, 47), (28, 47))
+    assert (Hx.shape, Hz.shape) == ((small, large) if tag == "wide_a" else (large, small))
+    assert Lx.shape == Lz.shape == (4, 47) and all(a.dtype == np.uint8 for a in (Hx, Hz, Lx, Lz))
+    i64 = lambda a: a.astype(np.int64)
+    assert not (i64(Hx) @ i64(Hz).T % 2).any()
+    assert not (i64(Hx) @ i64(Lz).T % 2).any() and not (i64(Hz) @ i64(Lx).T % 2).any()
+    k = 47 - co.gf2_rank(Hx) - co.gf2_rank(Hz)
+    assert k == 4 and co.gf2_rank(i64(Lx) @ i64(Lz).T % 2) == k
+    # the 15-row matrix: column weights 1 .. 3, rows up to 6; the 28-row matrix: columns 1 .. 4, rows up to 5
+    H15, H28 = (Hx, Hz) if tag == "wide_a" else (Hz, Hx)
+    assert (H15.sum(axis=0).min(), H15.sum(axis=0).max(), H15.sum(axis=1).max()) == (1, 3, 6)
+    assert (H28.sum(axis=0).min(), H28.sum(axis=0).max(), H28.sum(axis=1).max()) == (1, 4, 5)
+    # the sizes the kernels' loops do not divide
+    assert 47 % 4 and 47 % 64 and 15 % 32 and 28 % 32
+    other = co.hgp_asymmetric("wide_b" if tag == "wide_a" else "wide_a")
+    assert other[0].shape == Hz.shape and other[1].shape == Hx.shape
+
+
+def test_biased_priors():
+    """The per-qubit priors of the asymmetric tests: three different vectors, none constant, prior_b1 of both signs --
+    and the values the formulas of css.pauli_priors give qubit by qubit."""
+    pa, b0, b1 = co.biased_priors(47)
+    assert pa.shape == b0.shape == b1.shape == (47,) and all(np.isfinite(p).all() for p in (pa, b0, b1))
+    assert (b1 < 0).sum() == 3 and (b1 > 0).sum() == 44
+    assert abs(b1.min() - -0.108) < 1e-3 and abs(b1.max() - 1.310) < 1e-3
+    assert not np.array_equal(pa, b0) and not np.array_equal(pa, b1) and not np.array_equal(b0, b1)
+    assert all(len(set(p.tolist())) == 47 for p in (pa, b0, b1))
+    rng = np.random.default_rng(7)
+    px, py, pz = (0.02 * rng.uniform(0.8, 1.25, 47), 0.015 * rng.uniform(0.5, 2.0, 47), 0.03 * rng.uniform(0.8, 1.25, 47))
+    for v in range(47):
+        one = css.pauli_priors(px[v], py[v], pz[v], 1)
+        assert (one[0][0], one[1][0], one[2][0]) == (pa[v], b0[v], b1[v])
+
+
+def test_classify_is_the_tail_of_counters():
+    Hx, Hz, Lx, Lz = co.hgp_asymmetric("wide_b")
+    pri = co.biased_priors(47)
+    ea, eb = co.sample_pauli(47, *co.BIASED_RATES, 5, 0, 150)
+    dec = co.decode(Hx, Hz, co._syn(Hx, ea), co._syn(Hz, eb), *pri, max_iter=10, osd=0)
+    want = co.counters(Hx, Hz, Lx, Lz, 3, ea, eb, *pri, max_iter=10, osd=0)
+    assert np.array_equal(co.classify(Hx, Hz, Lx, Lz, 3, ea, eb, dec), want) and want[2][1] > 0
+    none = co.classify(Hx, Hz, Lx[:0], Lz, 3, ea, eb, dec)
+    assert not none[0][[1, 3, 4, 8]].any() and np.array_equal(none[1], want[1]) and none[2][1] == want[1][1]
+
+
+@pytest.mark.parametrize("mode", ["none", "osd0", "cs7", "minsum", "minsum_osd0"])
+def test_asymmetric_inputs_tell_the_sectors_apart(mode):
+    """The inputs of tests/test_gpu_css_shapes.py on the statement alone: both orientations leave at least five trials
+    to either outcome of BP in both sectors, their counters differ, and so do rows 0 and 1 of each."""
+    got = {}
+    for tag in ("wide_a", "wide_b"):
+        s = co.asym_inputs(tag)
+        want = co.asym_statement(tag, mode)
+        assert all(5 <= want[r][6] <= co.ASYM_T - 5 for r in (0, 1)), (tag, want)
+        assert want[0][0] == want[1][0] == want[2][0] == co.ASYM_T
+        assert not np.array_equal(want[0], want[1]), (tag, want)
+        assert want[0][6] != want[1][6] and want[0][1] != want[1][1]
+        assert s["Hx"].shape[0] != s["Hz"].shape[0]
+        got[tag] = want
+    assert not np.array_equal(got["wide_a"], got["wide_b"])
+    assert not np.array_equal(got["wide_a"][0], got["wide_b"][0]) and not np.array_equal(got["wide_a"][1], got["wide_b"][1])
+
+
+@pytest.mark.parametrize("tag", ["wide_a", "wide_b"])
+def test_asymmetric_decode_batch_inputs(tag):
+    """The perturbed syndromes of the decode test leave five records to either outcome in both sectors."""
+    s = co.asym_inputs(tag)
+    syn_a, syn_b = co.asym_batch_syndromes(s)
+    assert syn_a.shape == (co.ASYM_B, s["Hx"].shape[0]) and syn_b.shape == (co.ASYM_B, s["Hz"].shape[0])
+    assert (syn_a[::13] != co._syn(s["Hx"], s["ea"][:co.ASYM_B])[::13]).any(axis=1).sum() >= 5
+    assert (syn_b[::17] != co._syn(s["Hz"], s["eb"][:co.ASYM_B])[::17]).any(axis=1).sum() >= 5
+    _, _, ca, cb, _, _ = co.decode(s["Hx"], s["Hz"], syn_a, syn_b, *s["priors"], max_iter=co.ASYM_MAX_ITER)
+    assert 5 <= (~ca).sum() <= co.ASYM_B - 5 and 5 <= (~cb).sum() <= co.ASYM_B - 5
+
+
 @pytest.mark.parametrize("name", ["[[72, 12, 6]]", "hgp"])
 def test_code_identities(name):
     if name == "hgp":
