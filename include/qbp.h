@@ -354,7 +354,20 @@ int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_
  *   stop_after >= 1 solutions, alpha (min-sum normalisation) and clip_llr as in rework/decoding.py, finite.
  * QBP_E_INVALID: a null pointer, L < 1, a leg_iters[l] < 1, stop_after < 1, anything not finite.  QBP_E_UNSUPPORTED: a
  * matrix whose per-record state -- E messages and three rows of n doubles -- does not fit the 160 KiB of LDS of one
- * workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not).
+ * workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not), unless
+ * QBP_OPT_RELAY_MEM allows the other memory layout:
+ *
+ * Two memory layouts (QBP_OPT_RELAY_MEM, set with qbp_set_option before or after qbp_relay_configure; every launch
+ * checks again and refuses, outputs untouched, what its value does not allow):
+ *   0 (default)  a record's whole state in LDS: 8 (E + 3 n) bytes + the bookkeeping (+ n in a Monte-Carlo call);
+ *   1            the E messages in a per-workgroup global workspace (grid x E doubles, it stays in L2 / Infinity
+ *                Cache), the prior and the memory strengths read from global memory; in LDS stay the n posterior
+ *                values and the bookkeeping: 8 n bytes + 12 (m / 32) (+ n).  QBP_E_UNSUPPORTED beyond 160 KiB of that:
+ *                n of about 20 400, 18 200 in a Monte-Carlo call (2592 x 7776 takes 69 KiB there, the 1008 x 8991
+ *                detector error model 79 KiB);
+ *   2            automatic: layout 0 where it fits its 160 KiB, else layout 1 (the limit is layout 1's).
+ * The outputs do not depend on the layout (same rules, same order of every sum).  QBP_INFO_THREADS, QBP_INFO_GRID and
+ * QBP_INFO_LDS_BYTES report the launch.
  *
  * One record (syndrome s, prior P [n] finite):
  *   1. Q = P on the edges, V = P, no best solution, found = 0, total = 0;
@@ -372,7 +385,8 @@ int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_
  *      converged = found > 0, iters = total, legs = legs entered, solutions = found.
  * qbp_relay_decode_batch: syndromes [B][m], prior [n] (host entry: a value that is not finite is QBP_E_INVALID) ->
  * hard [B][n], converged [B], iters [B], llr [B][n], legs [B], solutions [B]; any output may be NULL.  QBP_E_INVALID
- * without a configuration.  One workgroup per record, all of its state in LDS (bp_relay_kernel).
+ * without a configuration.  One workgroup per record, its state in LDS or (layout 1) the messages in global memory
+ * (bp_relay_kernel).
  *
  * QBP_FLAG_RELAY in a Monte-Carlo call: the first stage is the call's BP as without the flag; every trial it leaves
  * unconverged is decoded by the rules above from its syndrome and the call's prior (first-stage messages are not
@@ -380,7 +394,8 @@ int qbp_osd_batch_ordered_device(qbp_handle* h, uint32_t osd_flags, const uint8_
  * a solution (their hard decision misses the syndrome); [0], [6], [7] are the first stage's.  The record limits of
  * QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with QBP_FLAG_OSD0 or any OSD bit, or without a
  * configuration.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum and
- * qbp_decode_shots, and on matrices qbp_relay_configure refuses.
+ * qbp_decode_shots, and on matrices qbp_relay_configure refuses under the handle's QBP_OPT_RELAY_MEM (the Monte-Carlo
+ * build keeps n more bytes in LDS; the same function chooses the layout).
  */
 int qbp_relay_configure(qbp_handle* h, const double* gammas, int32_t L, const int32_t* leg_iters, int32_t stop_after,
                         double alpha, double clip_llr);
@@ -943,6 +958,9 @@ enum {
                                     at most 2^20).  Results do not depend on it (tests force several chunks) */
     QBP_OPT_LAYERED_SLOTS = 15,  /* layered BP: records decoded at once by one workgroup (0 = auto, at most 32; fewer
                                     where the LDS holds fewer).  Results do not depend on it (tests force 1 and 2) */
+    QBP_OPT_RELAY_MEM = 16,      /* Relay-BP, where a record's messages live (qbp_relay_configure): 0 LDS only, 1 a global
+                                    workspace always (tests reach it on small matrices), 2 automatic.  Results do not
+                                    depend on it */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */

@@ -48,6 +48,8 @@ OPT_NO_FIRST_STEP_TABLE = 12
 OPT_EARLY_EXIT_FULL_WG = 13
 OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per chunk (0 = default)
 OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
+OPT_RELAY_MEM = 16           # Relay-BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
+RELAY_MEM = {False: 0, True: 2, "force": 1}     # ``relay.RelayConfig.large`` -> OPT_RELAY_MEM
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
 INFO = dict(m=100, n=101, edges=102, max_row_deg=103, max_col_deg=104, kernel_kind=105,
             threads=106, lds_bytes=107, grid=108, num_cu=109, last_kernel=110, one_barrier=111)
@@ -683,9 +685,11 @@ class Decoder:
 
     @_locked
     def relay_configure(self, cfg):
-        """Store a Relay-BP configuration (``relay.RelayConfig``) in the handle: qbp_relay_configure."""
+        """Store a Relay-BP configuration (``relay.RelayConfig``) in the handle: OPT_RELAY_MEM from ``cfg.large``, then
+        qbp_relay_configure."""
         if cfg.n != self.n:
             raise ValueError(f"the relay configuration is for {cfg.n} variables, the matrix has {self.n}")
+        _check(load().qbp_set_option(self._h, OPT_RELAY_MEM, RELAY_MEM[cfg.large]))
         _check(load().qbp_relay_configure(self._h, cfg.gammas.ctypes.data, cfg.gammas.shape[0],
                                           cfg.leg_iters.ctypes.data, cfg.stop_after, cfg.alpha, cfg.clip_llr))
 

@@ -307,6 +307,7 @@ struct qbp_handle {
     DevBuf<int32_t> d_epos, d_cpos, d_long_edge_row;
     DevBuf<int32_t> d_vpos, d_vrow, d_lcol_ptr;      // general-H kernel: column-class tables
     DevBuf<double> d_wsL, d_prior_sorted;
+    DevBuf<double> d_wsM;           // Relay-BP, large build: [grid][E] messages
     int gcol_base[qbp::GENERIC_MAX_COL_CLASS + 2] = {0};
     int rpad_off[qbp::GENERIC_MAX_ROW_CLASS + 2] = {0}, cpad_off[qbp::GENERIC_MAX_COL_CLASS + 2] = {0};
     int opt_threads = 0;            // general-H kernel: threads per workgroup (0 = auto)
@@ -363,6 +364,7 @@ struct qbp_handle {
     double relay_alpha = 1.0, relay_clip = 0.0;
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
+    int opt_relay_mem = 0;          // QBP_OPT_RELAY_MEM
     // BP guided decimation (qbp_gd_configure); scratch of the host-pointer entry
     bool gd_ready = false;
     int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
@@ -2134,9 +2136,24 @@ try {
 QBP_ABI_CATCH
 
 // ---- Relay-BP (qbp_relay.hpp) ------------------------------------------------------------------------------------
-// The kernel keeps a record's whole state in LDS: matrices beyond that are QBP_E_UNSUPPORTED.
+// QBP_OPT_RELAY_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
+// global workspace; 2: there where the state does not fit the LDS.
+static bool relay_large(const qbp_handle* h, bool records)
+{
+    if (h->opt_relay_mem == 2) return qbp::relay_lds_bytes(h->m, h->n, h->E, records) > (size_t)160 * 1024;
+    return h->opt_relay_mem == 1;
+}
+
+// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
 static int relay_supported(const qbp_handle* h, bool records)
 {
+    if (h->opt_relay_mem != 0) {
+        const size_t need = qbp::relay_large_lds_bytes(h->m, h->n, records);
+        if (need > (size_t)160 * 1024)
+            return fail(QBP_E_UNSUPPORTED, "Relay-BP with the messages in global memory keeps a row of n doubles in LDS: "
+                                           "%d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
+        return QBP_OK;
+    }
     const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
     if (lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "Relay-BP keeps the messages and three rows of n doubles in LDS: %d x %d with %d "
@@ -2256,18 +2273,28 @@ static int record_decode_batch_host(qbp_handle* h, const uint8_t* syndromes, con
 static int relay_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream_t s)
 {
     constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
-    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
+    // (QBP_OPT_RELAY_MEM may have changed since qbp_relay_configure)
+    const int rc0 = relay_supported(h, records);
+    if (rc0) return rc0;
+    const bool large = relay_large(h, records);
+    const size_t lds = large ? qbp::relay_large_lds_bytes(h->m, h->n, records)
+                             : qbp::relay_lds_bytes(h->m, h->n, h->E, records);
     const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::RELAY_MAX_THREADS);
     qbp::RelayParams P{};
     int grid = 0;
-    // 28 wavefronts per CU at the kernel's registers; QBP_OPT_BLOCKS_PER_CU is not honoured
-    const int rc = record_launch_setup(h, c, records, {"Relay-BP", lds, threads, 28, false}, s, P.tab, P.io, &grid);
+    // wavefronts per CU at the kernel's registers: 28, large build 24; QBP_OPT_BLOCKS_PER_CU is not honoured
+    const int rc = record_launch_setup(h, c, records, {"Relay-BP", lds, threads, large ? 24 : 28, false}, s, P.tab, P.io,
+                                       &grid);
     if (rc) return rc;
+    if (large) {
+        HIP_TRY(h->d_wsM.reserve((size_t)grid * (size_t)h->E));
+        P.wsM = h->d_wsM.p;
+    }
     P.vinv = h->d_relay_vinv.p; P.prior = c.prior;
     P.gammas_sorted = h->d_relay_gammas.p; P.leg_iters = h->d_relay_iters.p;
     P.L = h->relay_L; P.stop_after = h->relay_stop_after; P.alpha = h->relay_alpha; P.clip_llr = h->relay_clip;
     P.legs = c.extra[0]; P.solutions = c.extra[1];
-    HIP_TRY(qbp::launch_relay(records, P, grid, threads, lds, s));
+    HIP_TRY(qbp::launch_relay(records, large, P, grid, threads, lds, s));
     return QBP_OK;
 }
 
@@ -3227,6 +3254,9 @@ try {
         case QBP_OPT_LAYERED_SLOTS:
             if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
             h->opt_layered_slots = (int)value; return QBP_OK;
+        case QBP_OPT_RELAY_MEM:
+            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "Relay-BP memory mode out of range");
+            h->opt_relay_mem = (int)value; return QBP_OK;
         case QBP_OPT_GENERAL_THREADS:
             if (value < 0 || value > 1024) return fail(QBP_E_INVALID, "threads per workgroup out of range");
             h->opt_threads = (int)value; return QBP_OK;

@@ -140,8 +140,10 @@ hipError_t launch_osd_order_blocked_shots(int rows_per_thread, unsigned grid, si
                                           const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
 hipError_t launch_osd_order_blocked_ordered(int rows_per_thread, unsigned grid, size_t lds, const OsdParams& O,
                                             const OsdBigWorkspace& Wk, const OsdOrderBigArgs& X, hipStream_t s);
-// qbp_tu_relay.hip: bp_relay_kernel, its batch build or (records) the build that reads Monte-Carlo failure records
-hipError_t launch_relay(bool records, const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s);
+// qbp_tu_relay.hip: bp_relay_kernel<records, large>: messages in LDS or (large) in a global workspace, the batch build
+// or (records) the build that reads Monte-Carlo failure records
+hipError_t launch_relay(bool records, bool large, const RelayParams& P, int grid, int threads, size_t lds,
+                        hipStream_t s);
 // qbp_tu_layered.hip: bp_layered_kernel<variant, mc> (sum-product or min-sum; batch or Monte-Carlo build)
 hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)

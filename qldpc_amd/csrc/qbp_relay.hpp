@@ -21,6 +21,20 @@
 // Two builds: RECORDS = false decodes B syndromes to outputs; RECORDS = true reads the failure records of a
 // Monte-Carlo launch (count and list in device memory, fail_syn, fail_err), decodes them and classifies the result
 // into the counters, as the OSD record kernels do.
+// Two memory layouts of each (QBP_OPT_RELAY_MEM): LARGE = false is the above; LARGE = true is the same
+// statement for matrices whose E messages do not fit -- space-time and detector-error-model matrices.  Its messages are
+// the workgroup's slice of a global workspace wsM[grid][E], which stays in L2 / Infinity Cache as the general-H kernel's
+// does (qbp_generic.hpp); the prior is read where the launch permuted it (prior_sorted) and the gamma row where the
+// configuration put it, so neither is copied.  In LDS stay V[n] (the bias reads the previous V[x], the same thread writes
+// the new one), the words, the syndrome and parity bits and best_hard: 8 n bytes + the words, 69 KiB for 2592 x 7776 in
+// the records build.
+// The shared steps reach the messages through RecordLds::M, a plain pointer, and are called unchanged; both barriers
+// stay where they are.  A message is written by one wavefront and read by another of the same workgroup across a
+// barrier: __syncthreads() is a workgroup-scope release, the barrier and a workgroup-scope acquire.  On gfx950 outside
+// threadgroup-split mode the compiler emits s_waitcnt lgkmcnt(0) and NO vmcnt(0) for that release: the wavefronts of a
+// workgroup share their CU's vector L1, which is write-through and keeps their memory operations in issue order, so a
+// store issued before the barrier is ordered before a load issued after it (DESIGN.md section 3b has what the ISA shows;
+// wsL of the LDS build and the general-H kernel's workspace rely on the same).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +60,8 @@ struct RelayParams {
     // ---- batch build: the outputs beyond RecordIo's (either may be null) -----------------------------------------------
     int32_t* legs;                  // [B] legs entered
     int32_t* solutions;             // [B] solutions found
+    // ---- LARGE build -----------------------------------------------------------------------------------------------------
+    double* wsM;                    // [grid][E] the messages of the workgroups' current records
 };
 
 // 32-bit words behind the doubles: logical mask (2), error weight, difference flag, unsatisfied checks [2], "write this
@@ -62,7 +78,14 @@ __host__ __device__ inline size_t relay_lds_bytes(int m, int n, int E, bool reco
     return (size_t)8 * ((size_t)E + 3 * (size_t)n) + 4 * relay_lds_words(m) + (records ? (((size_t)n + 7) & ~(size_t)7) : 0);
 }
 
-template <bool RECORDS>
+// Dynamic LDS of one workgroup of the LARGE build: V, the words, and (records build) best_hard
+__host__ __device__ inline size_t relay_large_lds_bytes(int m, int n, bool records)
+{
+    return (size_t)8 * (size_t)n + 4 * relay_lds_words(m) + (records ? (((size_t)n + 7) & ~(size_t)7) : 0);
+}
+
+// LARGE: the messages in the workgroup's slice of P.wsM, prior and gammas read in place.
+template <bool RECORDS, bool LARGE = false>
 __global__ __launch_bounds__(RELAY_MAX_THREADS) void bp_relay_kernel(const RelayParams P)
 {
     extern __shared__ __attribute__((aligned(16))) double relay_smem[];
@@ -71,11 +94,14 @@ __global__ __launch_bounds__(RELAY_MAX_THREADS) void bp_relay_kernel(const Relay
     const RecordIo& io = P.io;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int m = G.m, n = G.n, E = G.E;
-    double* const M = relay_smem;                   // [E] messages, in place
-    double* const V = M + E;                        // [n] posterior values, sorted-variable order
-    double* const prior_t = V + n;                  // [n]
-    double* const gam = prior_t + n;                // [n] the current leg's memory strengths
-    unsigned* const words = reinterpret_cast<unsigned*>(gam + n);
+    // [E] messages, in place
+    double* const M = LARGE ? P.wsM + (size_t)blockIdx.x * (size_t)E : relay_smem;
+    double* const V = LARGE ? relay_smem : M + E;   // [n] posterior values, sorted-variable order
+    double* const prior_lds = V + n;                // [n] (not LARGE)
+    double* const gam_lds = prior_lds + n;          // [n] the current leg's memory strengths (not LARGE)
+    const double* const prior_t = LARGE ? G.prior_sorted : prior_lds;
+    const double* gam = gam_lds;                    // (LARGE: the leg's row of P.gammas_sorted)
+    unsigned* const words = reinterpret_cast<unsigned*>(LARGE ? V + n : gam_lds + n);
     const int mw = (m + 31) >> 5;
     unsigned* const better = words + 6;
     const RecordLds S{M, V, reinterpret_cast<unsigned long long*>(words), reinterpret_cast<int*>(words + 2),
@@ -86,7 +112,8 @@ __global__ __launch_bounds__(RELAY_MAX_THREADS) void bp_relay_kernel(const Relay
     const int n_long = G.row_off[RC + 2] - G.row_off[RC + 1];
     double* const Lw = G.wsL + (size_t)blockIdx.x * 3 * (n_long > 0 ? n_long : 1);
 
-    for (int x = tid; x < n; x += nt) prior_t[x] = G.prior_sorted[x];   // (published by the record's first barrier)
+    if constexpr (!LARGE)
+        for (int x = tid; x < n; x += nt) prior_lds[x] = G.prior_sorted[x];   // (published by the record's first barrier)
     const long long count = record_count<RECORDS>(io, S);
     const bool dynamic = count > (long long)gridDim.x;
 
@@ -118,7 +145,8 @@ __global__ __launch_bounds__(RELAY_MAX_THREADS) void bp_relay_kernel(const Relay
         for (int leg = 0; leg < P.L; ++leg) {
             ++legs;
             // (the last readers of gam passed barrier B of the previous leg; barrier A publishes the new row)
-            for (int x = tid; x < n; x += nt) gam[x] = P.gammas_sorted[(size_t)leg * n + x];
+            if constexpr (LARGE) gam = P.gammas_sorted + (size_t)leg * n;
+            else for (int x = tid; x < n; x += nt) gam_lds[x] = P.gammas_sorted[(size_t)leg * n + x];
             const int T = P.leg_iters[leg];
             bool solved = false;
             for (int t = 0; t < T && !solved; ++t) {

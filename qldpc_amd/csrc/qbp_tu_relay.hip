@@ -1,4 +1,5 @@
-// libqbp.so, translation unit of the Relay-BP kernel (qbp_relay.hpp): the batch build and the records build.
+// libqbp.so, translation unit of the Relay-BP kernels (qbp_relay.hpp): the batch build and the records build of
+// bp_relay_kernel, each with the messages in LDS and (LARGE) in a global workspace.
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
@@ -8,10 +9,10 @@
 namespace qbp {
 namespace {
 
-template <bool RECORDS>
+template <bool RECORDS, bool LARGE>
 hipError_t relay_launch_k(const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s)
 {
-    auto kern = bp_relay_kernel<RECORDS>;
+    auto kern = bp_relay_kernel<RECORDS, LARGE>;
     static thread_local size_t lds_set[64] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -27,9 +28,14 @@ hipError_t relay_launch_k(const RelayParams& P, int grid, int threads, size_t ld
 
 }  // namespace
 
-hipError_t launch_relay(bool records, const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s)
+hipError_t launch_relay(bool records, bool large, const RelayParams& P, int grid, int threads, size_t lds,
+                        hipStream_t s)
 {
-    return records ? relay_launch_k<true>(P, grid, threads, lds, s) : relay_launch_k<false>(P, grid, threads, lds, s);
+    if (large)
+        return records ? relay_launch_k<true, true>(P, grid, threads, lds, s)
+                       : relay_launch_k<false, true>(P, grid, threads, lds, s);
+    return records ? relay_launch_k<true, false>(P, grid, threads, lds, s)
+                   : relay_launch_k<false, false>(P, grid, threads, lds, s);
 }
 
 }  // namespace qbp

@@ -834,6 +834,9 @@ def main(argv=None):
     ap.add_argument("--relay", type=int, nargs=2, default=None, metavar=("LEGS", "ITERS"),
                     help="Relay-BP instead of OSD on the trials BP does not converge on: LEGS legs of ITERS min-sum "
                          "iterations each (with --alpha and --clip-llr; not with --osd, --budgets, --spectrum, --shots)")
+    ap.add_argument("--relay-large", action="store_true",
+                    help="with --relay: also on matrices whose record state passes 160 KiB of LDS (space-time and "
+                         "detector-error-model matrices): their messages live in a global workspace")
     ap.add_argument("--relay-gamma0", type=float, default=0.125, help="memory strength of leg 0, every variable")
     ap.add_argument("--relay-interval", type=float, nargs=2, default=(-0.24, 0.66), metavar=("LO", "HI"),
                     help="later legs draw a strength per variable uniformly from [LO, HI] (seeded by --seed)")
@@ -863,6 +866,8 @@ def main(argv=None):
     except ValueError as e:
         ap.error(str(e))
     relay = None
+    if args.relay_large and args.relay is None:
+        ap.error("--relay-large needs --relay")
     if args.relay is not None:
         if args.osd:
             ap.error("--relay and --osd exclude each other")
@@ -870,7 +875,7 @@ def main(argv=None):
             ap.error("--relay does not combine with --budgets, --spectrum or --shots")
         relay = dict(legs=args.relay[0], iters=args.relay[1], gamma0=args.relay_gamma0,
                      interval=tuple(args.relay_interval), seed=args.seed, stop_after=args.relay_stop, alpha=args.alpha,
-                     clip_llr=args.clip_llr)
+                     clip_llr=args.clip_llr, large=args.relay_large)
         try:
             from . import relay as relay_mod
             relay_mod.as_config(relay, 1)

@@ -7,6 +7,11 @@ iterations per syndrome, the lightest of the first few solutions.
 
 ``RelayConfig`` is the same configuration as an object, for the ``relay=`` argument of ``mc.run_sweep``, ``mc.run_dem``
 and ``mc.run_weights`` (trials the first-stage BP leaves unconverged go to Relay-BP instead of OSD).
+
+``large``: where a record's messages live.  False (default): in LDS, and a matrix whose record state passes 160 KiB
+(34 rounds of the [[72,12,6]] phenomenological matrix, 2592 x 7776) is refused; True: in LDS where they fit, else in a
+per-workgroup global workspace (the space-time and detector-error-model matrices); "force": the workspace always (tests).
+The outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -36,9 +41,10 @@ def relay_gammas(n, legs, gamma0, interval, seed=0):
 
 class RelayConfig:
     """gammas float64[L, n], leg_iters int32[L], stop_after, alpha, clip_llr -- validated as qbp_relay_configure does
-    (ValueError where the library answers QBP_E_INVALID)."""
+    (ValueError where the library answers QBP_E_INVALID) --, and ``large`` (False, True or "force": QBP_OPT_RELAY_MEM 0,
+    2 or 1)."""
 
-    def __init__(self, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0):
+    def __init__(self, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0, large=False):
         g = np.ascontiguousarray(gammas, np.float64)
         it = np.asarray(leg_iters)
         if g.ndim != 2 or g.shape[0] < 1 or g.shape[1] < 1:
@@ -51,6 +57,9 @@ class RelayConfig:
             raise ValueError(f"stop_after must be an integer >= 1, got {stop_after!r}")
         if not np.all(np.isfinite(g)) or not np.isfinite(alpha) or not np.isfinite(clip_llr):
             raise ValueError("gammas, alpha and clip_llr must be finite")
+        if not (isinstance(large, bool) or large == "force"):
+            raise ValueError(f"large must be False, True or 'force', got {large!r}")
+        self.large = large
         self.gammas = g
         self.leg_iters = np.ascontiguousarray(it, np.int32)
         self.stop_after, self.alpha, self.clip_llr = int(stop_after), float(alpha), float(clip_llr)
@@ -59,16 +68,22 @@ class RelayConfig:
     def n(self):
         return self.gammas.shape[1]
 
+    def as_dict(self):
+        """The dict form ``as_config`` reads back."""
+        return dict(gammas=self.gammas, leg_iters=self.leg_iters, stop_after=self.stop_after, alpha=self.alpha,
+                    clip_llr=self.clip_llr, large=self.large)
+
 
 def as_config(relay, n):
     """The ``relay=`` argument of the Monte-Carlo drivers as a ``RelayConfig`` for n variables.  A ``RelayConfig``, or a
     dict: either ``gammas`` and ``leg_iters`` (as ``performRelayBP``), or ``legs``, ``iters`` (per leg), ``gamma0``,
-    ``interval`` and optionally ``seed`` (``relay_gammas``); both forms take ``stop_after``, ``alpha``, ``clip_llr``."""
+    ``interval`` and optionally ``seed`` (``relay_gammas``); both forms take ``stop_after``, ``alpha``, ``clip_llr``
+    and ``large``."""
     if isinstance(relay, RelayConfig):
         cfg = relay
     elif isinstance(relay, dict):
         d = dict(relay)
-        rest = {k: d.pop(k) for k in ("stop_after", "alpha", "clip_llr") if k in d}
+        rest = {k: d.pop(k) for k in ("stop_after", "alpha", "clip_llr", "large") if k in d}
         if "gammas" in d:
             gammas, leg_iters = d.pop("gammas"), d.pop("leg_iters")
         else:
@@ -85,18 +100,20 @@ def as_config(relay, n):
     return cfg
 
 
-def performRelayBPBatch(H, syndromes, prior, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0, device=None):
+def performRelayBPBatch(H, syndromes, prior, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0, device=None,
+                        large=False):
     """Relay-BP of B syndromes uint8[B, m] on the GPU -> ``RelayResult(hard uint8[B, n], converged bool[B],
-    iters int32[B], llr float64[B, n], legs int32[B], solutions int32[B])``."""
+    iters int32[B], llr float64[B, n], legs int32[B], solutions int32[B])``.  ``large``: as in ``RelayConfig``."""
     from . import bp
-    cfg = RelayConfig(gammas, leg_iters, stop_after, alpha, clip_llr)
+    cfg = RelayConfig(gammas, leg_iters, stop_after, alpha, clip_llr, large)
     dec = bp.decoder_for(H, device=bp.DEVICE if device is None else device)
     return RelayResult(*dec.relay_decode(syndromes, prior, cfg))
 
 
-def performRelayBP(H, syndrome, prior, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0, device=None):
+def performRelayBP(H, syndrome, prior, gammas, leg_iters, stop_after=1, alpha=1.0, clip_llr=20.0, device=None,
+                   large=False):
     """Relay-BP of one syndrome, in the shape of the reference's decoders: ``(candidateError, converged, values,
     iterations)`` -- iterations executed over all legs."""
     r = performRelayBPBatch(H, np.asarray(syndrome).reshape(1, -1), prior, gammas, leg_iters, stop_after, alpha,
-                            clip_llr, device)
+                            clip_llr, device, large)
     return r.hard[0], bool(r.converged[0]), r.llr[0], int(r.iters[0])
