@@ -438,10 +438,28 @@ int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, con
  *
  * qbp_layered_configure stores the level tables of `order` (host array, NULL = default) in the handle.
  * QBP_E_INVALID: not a permutation.  QBP_E_UNSUPPORTED: a matrix whose per-record state -- E messages, the posterior and
- * the prior -- does not fit the 160 KiB of LDS of one workgroup (864 x 2592 fits; 2592 x 7776 does not).
+ * the prior -- does not fit the 160 KiB of LDS of one workgroup (864 x 2592 fits; 2592 x 7776 does not), unless
+ * QBP_OPT_LAYERED_MEM allows the other memory layout:
+ *
+ * Two memory layouts (QBP_OPT_LAYERED_MEM, set with qbp_set_option before or after qbp_layered_configure; every call
+ * with QBP_FLAG_LAYERED checks again and refuses, host only and outputs untouched, what its value does not allow):
+ *   0 (default)  a record's whole state in LDS: per workgroup numpy's tables (counted for both variants at
+ *                configuration) and the prior, per slot 8 (E + n) bytes + the bookkeeping: 39 rounds of the [[72,12,6]]
+ *                phenomenological matrix (1404 x 4212) fit, 40 do not;
+ *   1            the E messages of every slot in a per-workgroup global workspace (grid x S x E doubles, CSR order; a
+ *                row's messages are read and written by one thread for the whole launch; it stays in L2 / Infinity
+ *                Cache), the prior read from global memory when a slot takes a record; in LDS stay the tables, per
+ *                slot the n posterior values, the syndrome bits and the bookkeeping: 8 n + 4 (m / 32) bytes.
+ *                QBP_E_UNSUPPORTED beyond 160 KiB of that with one slot: n of about 20 000 (2592 x 7776 takes 64 KiB
+ *                there, the 1008 x 8991 detector error model 74 KiB);
+ *   2            automatic: layout 0 where a single slot fits its 160 KiB, else layout 1 (the limit is layout 1's).
+ * The outputs do not depend on the layout (same rules, same order of every operation).  QBP_OPT_LAYERED_SLOTS and the
+ * workgroups per CU follow the layout's own LDS figure; QBP_INFO_THREADS, QBP_INFO_GRID and QBP_INFO_LDS_BYTES report
+ * the launch.  Sliding windows (qbp_window_*) take no layered stage in either layout.
  *
  * QBP_FLAG_LAYERED in a call: qbp_decode_batch(_device) decode by the rules above (bp_layered_kernel: one workgroup
- * decodes several records at once, all state in LDS; QBP_OPT_LAYERED_SLOTS).  QBP_FLAG_FORCE_FULL runs all iterations
+ * decodes several records at once, all state in LDS or (layout 1) the messages in global memory;
+ * QBP_OPT_LAYERED_SLOTS).  QBP_FLAG_FORCE_FULL runs all iterations
  * and keeps the outputs of the first converged one.  The Monte-Carlo entries run the layered decoder as their first
  * stage on stored errors: qbp_mc_run_errors on the caller's, the sampled entries on the errors
  * qbp_mc_sample_errors[_probs|_weight] return, drawn chunk by chunk (QBP_OPT_MC_WEIGHT_CHUNK) -- counters do not depend
@@ -450,7 +468,8 @@ int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, con
  * count and is dropped there; QBP_FLAG_FAST_MATH is ignored.
  * QBP_E_INVALID: the flag without a configuration, with QBP_DAMPED_SP, with any column-sum order flag (there is no
  * column sum), or a prior that is not finite at a host entry.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets,
- * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and qbp_check_messages.
+ * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and qbp_check_messages, and on matrices
+ * qbp_layered_configure refuses under the handle's QBP_OPT_LAYERED_MEM.
  */
 int qbp_layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* order_in,
                      int32_t* order_out, int32_t* level_ptr, int32_t* n_levels);
@@ -961,6 +980,9 @@ enum {
     QBP_OPT_RELAY_MEM = 16,      /* Relay-BP, where a record's messages live (qbp_relay_configure): 0 LDS only, 1 a global
                                     workspace always (tests reach it on small matrices), 2 automatic.  Results do not
                                     depend on it */
+    QBP_OPT_LAYERED_MEM = 17,    /* layered BP, where a record's messages live (qbp_layered_configure): 0 LDS only, 1 a
+                                    global workspace always (tests reach it on small matrices), 2 automatic.  Results do
+                                    not depend on it */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */

@@ -50,6 +50,8 @@ OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per
 OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
 OPT_RELAY_MEM = 16           # Relay-BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
 RELAY_MEM = {False: 0, True: 2, "force": 1}     # ``relay.RelayConfig.large`` -> OPT_RELAY_MEM
+OPT_LAYERED_MEM = 17         # layered BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
+LAYERED_MEM = {False: 0, True: 2}               # ``Decoder.layered_configure(large=)`` -> OPT_LAYERED_MEM
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
 INFO = dict(m=100, n=101, edges=102, max_row_deg=103, max_col_deg=104, kernel_kind=105,
             threads=106, lds_bytes=107, grid=108, num_cu=109, last_kernel=110, one_barrier=111)
@@ -600,9 +602,15 @@ class Decoder:
 
     # ---- host buffers ----------------------------------------------------------------------
     @_locked
-    def layered_configure(self, order=None):
+    def layered_configure(self, order=None, large=None):
         """Store the level tables of the layered schedule in the handle (qbp_layered_configure).  ``order``: a
-        permutation of the checks, None = the default order."""
+        permutation of the checks, None = the default order.  ``large``: None leaves the handle's OPT_LAYERED_MEM as
+        it is; False writes 0 (a record's state in LDS only: matrices beyond 160 KiB are refused); True writes 2
+        (the messages in a global workspace where the LDS does not hold them)."""
+        if large is not None:
+            if not isinstance(large, bool):
+                raise ValueError(f"large must be None, False or True, got {large!r}")
+            _check(load().qbp_set_option(self._h, OPT_LAYERED_MEM, LAYERED_MEM[large]))
         oin = None
         if order is not None:
             oin = np.ascontiguousarray(order, np.int32)

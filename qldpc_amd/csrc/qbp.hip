@@ -384,6 +384,8 @@ struct qbp_handle {
     int layered_levels = 0, layered_max_width = 0;
     int opt_layered_slots = 0;      // QBP_OPT_LAYERED_SLOTS (0 = auto)
     DevBuf<int32_t> d_layered_order, d_layered_level_ptr;
+    int opt_layered_mem = 0;        // QBP_OPT_LAYERED_MEM
+    DevBuf<double> d_layered_wsR;   // layered BP, large build: [grid][S][E] messages
 };
 
 namespace {
@@ -2027,21 +2029,48 @@ static int check_csr(const int32_t* row_ptr, const int32_t* col_idx, int m, int 
     return QBP_OK;
 }
 
+// QBP_OPT_LAYERED_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
+// global workspace; 2: there where the single-slot state (by the sum-product size, as qbp_layered_configure counts)
+// does not fit the LDS.
+static bool layered_large(const qbp_handle* h)
+{
+    if (h->opt_layered_mem == 2) return qbp::layered_lds_bytes(h->m, h->n, h->E, 1, true) > (size_t)160 * 1024;
+    return h->opt_layered_mem == 1;
+}
+
+// Dynamic LDS of a workgroup with S slots in the build `large`
+static size_t layered_build_lds(const qbp_handle* h, bool large, int S, bool tables)
+{
+    return large ? qbp::layered_large_lds_bytes(h->m, h->n, S, tables)
+                 : qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables);
+}
+
 // Slots per workgroup: about one work item per thread in the widest level, at most LAYERED_MAX_SLOTS and what keeps
 // two workgroups' LDS on a CU; one slot always (qbp_layered_configure refuses what does not fit with one).
-static int layered_slots(const qbp_handle* h, long long B, bool tables)
+static int layered_slots(const qbp_handle* h, long long B, bool tables, bool large)
 {
     int S = h->opt_layered_slots;
     if (S <= 0) {
         S = std::max(1, std::min(qbp::LAYERED_MAX_SLOTS, qbp::LAYERED_THREADS / std::max(1, h->layered_max_width)));
-        while (S > 1 && qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables) > (size_t)80 * 1024) --S;
+        while (S > 1 && layered_build_lds(h, large, S, tables) > (size_t)80 * 1024) --S;
     }
-    while (S > 1 && qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables) > (size_t)160 * 1024) --S;
+    while (S > 1 && layered_build_lds(h, large, S, tables) > (size_t)160 * 1024) --S;
     return (int)std::max<long long>(1, std::min<long long>(S, B));
 }
 
+// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
 static int layered_supported(const qbp_handle* h)
 {
+    if (h->opt_layered_mem != 0) {
+        const size_t need = qbp::layered_large_lds_bytes(h->m, h->n, 1, true);
+        if (need > (size_t)160 * 1024) {
+            const size_t fixed = qbp::layered_large_lds_bytes(h->m, 0, 1, true);
+            return fail(QBP_E_UNSUPPORTED, "layered BP with the messages in global memory keeps the posterior, n doubles, "
+                                           "in LDS: %d x %d needs %zu B (limit 160 KiB: n <= %zu with %d checks)",
+                        h->m, h->n, need, fixed < (size_t)160 * 1024 ? ((size_t)160 * 1024 - fixed) / 8 : (size_t)0, h->m);
+        }
+        return QBP_OK;
+    }
     const size_t lds = qbp::layered_lds_bytes(h->m, h->n, h->E, 1, true);
     if (lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "layered BP keeps the messages, the posterior and the prior of a record in LDS: "
@@ -2061,7 +2090,7 @@ static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant,
     if (variant == QBP_DAMPED_SP) return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with QBP_DAMPED_SP: no damped layered schedule");
     if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0))
         return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with a column-sum order flag: the layered schedule has no column sum");
-    return QBP_OK;
+    return layered_supported(h);        // (QBP_OPT_LAYERED_MEM may have changed since qbp_layered_configure)
 }
 
 // One launch of bp_layered_kernel (device pointers): the batch build, or (c.mc) the Monte-Carlo build on stored errors
@@ -2070,9 +2099,12 @@ static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
     if (c.B > MAX_LAUNCH)
         return fail(QBP_E_UNSUPPORTED, "layered BP decodes at most 2^30 syndromes per call (got %lld)", c.B);
+    const int rc0 = layered_supported(h);
+    if (rc0) return rc0;
     const bool tables = c.variant == QBP_SUM_PRODUCT;
-    const int S = layered_slots(h, c.B, tables);
-    const size_t lds = qbp::layered_lds_bytes(h->m, h->n, h->E, S, tables);
+    const bool large = layered_large(h);
+    const int S = layered_slots(h, c.B, tables, large);
+    const size_t lds = layered_build_lds(h, large, S, tables);
     // resident workgroups per CU: the LDS, and five wavefronts per SIMD at the kernel's registers
     int per_cu = (int)std::max<size_t>(1, std::min<size_t>(5, ((size_t)160 * 1024) / lds));
     if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
@@ -2093,8 +2125,13 @@ static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
         P.fail_list = c.mc->fail_list; P.fail_count = c.mc->fail_count; P.fail_syn = c.mc->fail_syn;
         P.fail_hard = c.mc->fail_hard; P.fail_err = c.mc->fail_err; P.fail_llr = c.mc->fail_llr;
     }
+    if (large) {
+        // a slice of E doubles per slot of every workgroup; grown when a launch needs more, never shrunk
+        HIP_TRY(h->d_layered_wsR.reserve((size_t)grid * (size_t)S * (size_t)h->E));
+        P.wsR = h->d_layered_wsR.p;
+    }
     h->last_threads = qbp::LAYERED_THREADS; h->last_lds = (int)lds; h->last_grid = grid;
-    HIP_TRY(qbp::launch_layered(c.mc != nullptr, c.variant, P, grid, lds, s));
+    HIP_TRY(qbp::launch_layered(c.mc != nullptr, large, c.variant, P, grid, lds, s));
     return QBP_OK;
 }
 
@@ -3254,6 +3291,9 @@ try {
         case QBP_OPT_LAYERED_SLOTS:
             if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
             h->opt_layered_slots = (int)value; return QBP_OK;
+        case QBP_OPT_LAYERED_MEM:
+            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "layered BP memory mode out of range");
+            h->opt_layered_mem = (int)value; return QBP_OK;
         case QBP_OPT_RELAY_MEM:
             if (value < 0 || value > 2) return fail(QBP_E_INVALID, "Relay-BP memory mode out of range");
             h->opt_relay_mem = (int)value; return QBP_OK;

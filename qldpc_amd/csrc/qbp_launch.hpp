@@ -144,8 +144,10 @@ hipError_t launch_osd_order_blocked_ordered(int rows_per_thread, unsigned grid, 
 // or (records) the build that reads Monte-Carlo failure records
 hipError_t launch_relay(bool records, bool large, const RelayParams& P, int grid, int threads, size_t lds,
                         hipStream_t s);
-// qbp_tu_layered.hip: bp_layered_kernel<variant, mc> (sum-product or min-sum; batch or Monte-Carlo build)
-hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s);
+// qbp_tu_layered.hip: bp_layered_kernel<variant, mc, large> (sum-product or min-sum; batch or Monte-Carlo build; the
+// messages in LDS or (large) in a global workspace)
+hipError_t launch_layered(bool mc, bool large, int variant, const LayeredParams& P, int grid, size_t lds,
+                          hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
 hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
 // qbp_tu_cond.hip: bp_cond_kernel<variant> (sum-product or min-sum; a prior per record), and the glue kernels of the

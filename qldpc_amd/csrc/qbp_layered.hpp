@@ -22,6 +22,14 @@
 //                  record computes depends on S, the grid or its neighbours.
 // Two builds: MC = false decodes B syndromes to outputs; MC = true reads stored errors [T][n], forms the syndromes,
 // decodes and classifies with mc_count_trial, or leaves the failure records the OSD and Relay record kernels read.
+//
+// Two memory layouts (QBP_OPT_LAYERED_MEM).  LARGE = false: everything above in LDS.  LARGE = true, for matrices whose
+// single-slot state passes 160 KiB: the R of slot s in the workgroup's slice of a global workspace,
+// wsR[blockIdx.x][S][E] in CSR order, the prior read in place when a slot turns fresh; V[S][n], the syndrome bits, the
+// slot words and the tables stay in LDS.  The item -> (slot, check) mapping of a level is the same in every iteration,
+// so a row's messages are read and written by one and the same thread for the whole launch: no other thread ever
+// touches them, and nothing orders global memory between threads.  A fresh slot's slice is not zeroed; its first
+// iteration reads R as +0.0 instead (V - (+0.0): the same bits), so the previous record's messages are never seen.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,6 +71,8 @@ struct LayeredParams {
     unsigned long long* fail_count;
     uint8_t *fail_syn, *fail_hard, *fail_err;
     double* fail_llr;
+    // ---- large build ------------------------------------------------------------------------------------------------
+    double* wsR;                    // [grid][S][E] messages (null in the LDS build)
 };
 
 // 32-bit words behind the doubles.  Workgroup: [0] "a slot is active", [2 .. 25] the 12 counters (64 bit).  Per slot:
@@ -81,9 +91,16 @@ __host__ __device__ inline size_t layered_lds_bytes(int m, int n, int E, int S, 
            4 * ((size_t)LAYERED_WG_WORDS + (size_t)S * layered_slot_words(m));
 }
 
+// The large build: V[S][n] and the words; R in the workspace, no copy of the prior
+__host__ __device__ inline size_t layered_large_lds_bytes(int m, int n, int S, bool tables)
+{
+    return (tables ? (size_t)NP_LDS_BYTES : 0) + 8 * (size_t)S * (size_t)n +
+           4 * ((size_t)LAYERED_WG_WORDS + (size_t)S * layered_slot_words(m));
+}
+
 enum : unsigned { LAYERED_ACTIVE = 1u, LAYERED_FRESH = 2u, LAYERED_FROZEN = 4u };
 
-template <int VARIANT, bool MC>
+template <int VARIANT, bool MC, bool LARGE>
 __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const LayeredParams P)
 {
     static_assert(VARIANT == 0 || VARIANT == 2, "sum-product or min-sum");
@@ -92,11 +109,17 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
     constexpr int TAB = VARIANT == 0 ? NP_LDS_DOUBLES : 0;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
     const int m = P.m, n = P.n, E = P.E, S = P.S;
-    const int stride = E + n;
+    const int stride = LARGE ? n : E + n;                   // doubles of a slot in LDS
     const int mw = (m + 31) >> 5;
     const int sw = (int)layered_slot_words(m);
-    double* const prior_l = layered_smem + TAB;            // [n]
-    double* const slots = prior_l + n;                      // [S][E + n]: R, then V
+    double* const prior_l = layered_smem + TAB;            // [n] (LDS build only)
+    double* const slots = prior_l + (LARGE ? 0 : n);        // [S][E + n]: R, then V; large build [S][n]: V
+    // the messages and the posterior of slot s
+    auto s_R = [&](int s) {
+        if constexpr (LARGE) return P.wsR + ((size_t)blockIdx.x * S + s) * (size_t)E;
+        else return slots + (size_t)s * stride;
+    };
+    auto s_V = [&](int s) { return slots + (size_t)s * stride + (LARGE ? 0 : E); };
     unsigned* const words = reinterpret_cast<unsigned*>(slots + (size_t)S * stride);
     unsigned long long* const cnt = reinterpret_cast<unsigned long long*>(words + 2);      // [12]
     unsigned* const sl = words + LAYERED_WG_WORDS;          // [S][sw]
@@ -115,7 +138,8 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
     const int last_it = P.max_iter - 1;
 
     if constexpr (VARIANT == 0) np_tables_to_lds(layered_smem, tid, nt);
-    for (int x = tid; x < n; x += nt) prior_l[x] = P.prior[x];
+    if constexpr (!LARGE)
+        for (int x = tid; x < n; x += nt) prior_l[x] = P.prior[x];
     if (tid < LAYERED_WG_WORDS) words[tid] = 0u;
     if (tid < S) {
         const long long rec = (long long)blockIdx.x * S + tid;
@@ -135,11 +159,17 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
     };
 
     for (;;) {
-        // ================= fresh slots: R = +0.0, V = prior, the syndrome bits ====================================
+        // ================= fresh slots: R = +0.0 (large build: read as +0.0 in iteration 0), V = prior, the syndrome
+        // bits =========================================================================================================
         for (int s = 0; s < S; ++s) {
             if (!(*s_state(s) & LAYERED_FRESH)) continue;   // uniform
-            double* const R = slots + (size_t)s * stride;
-            for (int k = tid; k < stride; k += nt) R[k] = k < E ? 0.0 : prior_l[k - E];
+            if constexpr (LARGE) {
+                double* const V = s_V(s);
+                for (int k = tid; k < n; k += nt) V[k] = P.prior[k];
+            } else {
+                double* const R = s_R(s);
+                for (int k = tid; k < stride; k += nt) R[k] = k < E ? 0.0 : prior_l[k - E];
+            }
             const long long rec = *s_rec(s);
             unsigned* const synw = s_syn(s);
             for (int c0 = tid - lane; c0 < m; c0 += nt) {   // c0 is wave-uniform
@@ -173,8 +203,14 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
                 if (!(*s_state(s) & LAYERED_ACTIVE)) continue;
                 const int c = P.order[lp + k];
                 const int e0 = P.row_ptr[c], deg = P.row_ptr[c + 1] - e0;
-                double* const R = slots + (size_t)s * stride + e0;      // the row's messages
-                double* const V = slots + (size_t)s * stride + E;
+                double* const R = s_R(s) + e0;                  // the row's messages
+                double* const V = s_V(s);
+                // (large build: in iteration 0 the slice still holds the previous record's messages)
+                const bool first = LARGE && *s_it(s) == 0;
+                auto rd = [&](int j) {
+                    if constexpr (LARGE) return first ? 0.0 : R[j];
+                    else return R[j];
+                };
                 const int32_t* const col = P.col_idx + e0;
                 const unsigned sbit = (s_syn(s)[c >> 5] >> (c & 31)) & 1u;
 #define QBP_LAYERED_ROW(DD)                                                                        \
@@ -182,7 +218,7 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
                     int vv[DD];                                                                    \
                     double d[DD], q[DD];                                                           \
                     _Pragma("unroll") for (int j = 0; j < DD; ++j) vv[j] = col[j];                 \
-                    _Pragma("unroll") for (int j = 0; j < DD; ++j) d[j] = V[vv[j]] - R[j];         \
+                    _Pragma("unroll") for (int j = 0; j < DD; ++j) d[j] = V[vv[j]] - rd(j);        \
                     _Pragma("unroll") for (int j = 0; j < DD; ++j) q[j] = VARIANT == 2 ? clipq(d[j]) : d[j]; \
                     auto put = [&](int j, double r) { R[j] = r; V[vv[j]] = d[j] + r; };            \
                     check_row<VARIANT, DD, true>(q, sbit, P.alpha, true, np_tab, put);             \
@@ -195,22 +231,22 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
                         // rows beyond 8: two passes in this thread, d recomputed (the row's variables are distinct,
                         // and message j is overwritten only after its own d was read)
                         if constexpr (VARIANT == 2) {
-                            const MinSumRow row = minsum_row([&](int j) { return clipq(V[col[j]] - R[j]); }, deg);
+                            const MinSumRow row = minsum_row([&](int j) { return clipq(V[col[j]] - rd(j)); }, deg);
                             for (int j = 0; j < deg; ++j) {
                                 const int v = col[j];
-                                const double dj = V[v] - R[j];
+                                const double dj = V[v] - rd(j);
                                 const double r = minsum_message(clipq(dj), row, sbit, P.alpha);
                                 R[j] = r; V[v] = dj + r;
                             }
                         } else {
                             double prod = 0.0;
                             for (int j = 0; j < deg; ++j) {
-                                const double t = tanh_half_msg<VARIANT>(V[col[j]] - R[j], np_tab);
+                                const double t = tanh_half_msg<VARIANT>(V[col[j]] - rd(j), np_tab);
                                 prod = (j == 0) ? t : prod * t;
                             }
                             for (int j = 0; j < deg; ++j) {
                                 const int v = col[j];
-                                const double dj = V[v] - R[j];
+                                const double dj = V[v] - rd(j);
                                 const double r = sp_message<VARIANT>(prod, tanh_half_msg<VARIANT>(dj, np_tab), sbit, np_tab);
                                 R[j] = r; V[v] = dj + r;
                             }
@@ -226,7 +262,7 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
         for (int i = tid; i < S * m; i += nt) {
             const int s = i / m, c = i - s * m;
             if (!(*s_state(s) & LAYERED_ACTIVE)) continue;
-            const double* const V = slots + (size_t)s * stride + E;
+            const double* const V = s_V(s);
             unsigned par = (s_syn(s)[c >> 5] >> (c & 31)) & 1u;
             for (int e = P.row_ptr[c]; e < P.row_ptr[c + 1]; ++e) par ^= V[P.col_idx[e]] < 0.0 ? 1u : 0u;
             if (par) *s_unsat(s) = 1u;                      // (every writer stores the same value)
@@ -241,7 +277,7 @@ __global__ __launch_bounds__(LAYERED_THREADS) void bp_layered_kernel(const Layer
             const bool solved = *s_unsat(s) == 0u;
             if (!solved && *s_it(s) < last_it) continue;
             const long long rec = *s_rec(s);
-            const double* const V = slots + (size_t)s * stride + E;
+            const double* const V = s_V(s);
             if constexpr (MC) {
                 const bool to_osd = P.fail_list != nullptr && !solved;
                 const uint8_t* const err = P.errors_in + rec * n;

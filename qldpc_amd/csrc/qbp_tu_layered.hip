@@ -1,5 +1,5 @@
-// libqbp.so, translation unit of the layered BP kernel (qbp_layered.hpp): sum-product and min-sum, the batch build and
-// the Monte-Carlo build.
+// libqbp.so, translation unit of the layered BP kernels (qbp_layered.hpp): sum-product and min-sum, the batch build and
+// the Monte-Carlo build of bp_layered_kernel, each with the messages in LDS and (LARGE) in a global workspace.
 #include <hip/hip_runtime.h>
 
 #include "../../include/qbp.h"
@@ -9,10 +9,10 @@
 namespace qbp {
 namespace {
 
-template <int VARIANT, bool MC>
+template <int VARIANT, bool MC, bool LARGE>
 hipError_t layered_launch_k(const LayeredParams& P, int grid, size_t lds, hipStream_t s)
 {
-    auto kern = bp_layered_kernel<VARIANT, MC>;
+    auto kern = bp_layered_kernel<VARIANT, MC, LARGE>;
     static thread_local size_t lds_set[64] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -26,14 +26,23 @@ hipError_t layered_launch_k(const LayeredParams& P, int grid, size_t lds, hipStr
     return hipGetLastError();
 }
 
+template <int VARIANT>
+hipError_t layered_launch_v(bool mc, bool large, const LayeredParams& P, int grid, size_t lds, hipStream_t s)
+{
+    if (large)
+        return mc ? layered_launch_k<VARIANT, true, true>(P, grid, lds, s)
+                  : layered_launch_k<VARIANT, false, true>(P, grid, lds, s);
+    return mc ? layered_launch_k<VARIANT, true, false>(P, grid, lds, s)
+              : layered_launch_k<VARIANT, false, false>(P, grid, lds, s);
+}
+
 }  // namespace
 
-hipError_t launch_layered(bool mc, int variant, const LayeredParams& P, int grid, size_t lds, hipStream_t s)
+hipError_t launch_layered(bool mc, bool large, int variant, const LayeredParams& P, int grid, size_t lds,
+                          hipStream_t s)
 {
-    if (variant == QBP_MIN_SUM)
-        return mc ? layered_launch_k<2, true>(P, grid, lds, s) : layered_launch_k<2, false>(P, grid, lds, s);
-    if (variant == QBP_SUM_PRODUCT)
-        return mc ? layered_launch_k<0, true>(P, grid, lds, s) : layered_launch_k<0, false>(P, grid, lds, s);
+    if (variant == QBP_MIN_SUM) return layered_launch_v<2>(mc, large, P, grid, lds, s);
+    if (variant == QBP_SUM_PRODUCT) return layered_launch_v<0>(mc, large, P, grid, lds, s);
     return hipErrorInvalidValue;
 }
 

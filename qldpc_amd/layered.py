@@ -8,6 +8,11 @@ sets the flooding schedule oscillates on.
 
 ``layered=True`` on ``Decoder.decode``, ``mc.run_sweep``, ``mc.run_dem`` and ``mc.run_weights`` selects the same decoder
 there (OSD and Relay-BP act on what it leaves unconverged).
+
+``large``: where a record's messages live.  False (default): in LDS, and a matrix whose single-slot state passes
+160 KiB (40 rounds of the [[72,12,6]] phenomenological matrix, 2592 x 7776) is refused; True: in LDS where they fit,
+else in a per-workgroup global workspace (the space-time and detector-error-model matrices, n up to about 20 000).
+``layered="large"`` is the same choice on the Monte-Carlo drivers.  The outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -38,9 +43,11 @@ def layered_order(H, order=None):
 
 
 def performLayeredBPBatch(H, syndromes, initialBelief, maxIter=50, variant="sum-product", alpha=1.0, clip_llr=20.0,
-                          order=None, device=None):
+                          order=None, device=None, large=False):
     """Layered BP of B syndromes uint8[B, m] -> ``(hard uint8[B, n], converged bool[B], iters int32[B],
-    llr float64[B, n])``."""
+    llr float64[B, n])``.  ``large``: see the module's text."""
+    if not isinstance(large, bool):
+        raise ValueError(f"large must be False or True, got {large!r}")
     from . import bp
     v = _variant(variant)
     prior = np.ascontiguousarray(initialBelief, np.float64)
@@ -48,14 +55,14 @@ def performLayeredBPBatch(H, syndromes, initialBelief, maxIter=50, variant="sum-
         raise ValueError("layered BP needs a finite prior")
     dec = bp.decoder_for(H, device=bp.DEVICE if device is None else device)
     with dec._lock:                      # (the order and the decode of one call belong together)
-        dec.layered_configure(order)
+        dec.layered_configure(order, large)
         return dec.decode(syndromes, prior, maxIter, v, alpha, 1.0, clip_llr, layered=True)
 
 
 def performLayeredBP(H, syndrome, initialBelief, maxIter=50, variant="sum-product", alpha=1.0, clip_llr=20.0,
-                     order=None, device=None):
+                     order=None, device=None, large=False):
     """Layered BP of one syndrome, in the shape of rework/decoding.py's decoders: ``(candidateError, converged,
     values, iterations)``."""
     hard, conv, iters, llr = performLayeredBPBatch(H, np.asarray(syndrome).reshape(1, -1), initialBelief, maxIter,
-                                                   variant, alpha, clip_llr, order, device)
+                                                   variant, alpha, clip_llr, order, device, large)
     return hard[0].astype(np.int8), bool(conv[0]), llr[0], int(iters[0])

@@ -124,18 +124,29 @@ def _configure_relay(dec, relay):
 
 
 def layered_run_flags(flags, layered, variant) -> int:
-    """``flags`` of a sweep with ``layered`` (False / None, True = the default order, or a permutation of the checks):
-    | FLAG_LAYERED, BP runs the layered schedule.  ValueError with the damped variant, which has no layered form."""
+    """``flags`` of a sweep with ``layered`` (False / None, True = the default order, "large" = the default order, also
+    on matrices beyond the LDS, or a permutation of the checks): | FLAG_LAYERED, BP runs the layered schedule.
+    ValueError with the damped variant, which has no layered form, and with any other string."""
     if layered is None or layered is False:
         return flags
+    if isinstance(layered, str) and layered != "large":
+        raise ValueError(f"layered must be False, True, 'large' or an order of the checks, got {layered!r}")
     if int(variant) == _lib.DAMPED_SP:
         raise ValueError("layered=True needs variant sum-product or min-sum: there is no damped layered schedule")
     return flags | _lib.FLAG_LAYERED
 
 
 def _configure_layered(dec, layered):
-    if layered is not None and layered is not False:
-        dec.layered_configure(None if layered is True else layered)
+    """True: the default order, OPT_LAYERED_MEM 0 (LDS only, as ever); "large": the default order, OPT_LAYERED_MEM 2
+    (the messages in a global workspace where the LDS does not hold them); an array: that order, the option as it is."""
+    if layered is None or layered is False:
+        return
+    if isinstance(layered, str):
+        dec.layered_configure(None, large=True)
+    elif layered is True:
+        dec.layered_configure(None, large=False)
+    else:
+        dec.layered_configure(layered)
 
 
 def _on_device(shape, priors, begin, end, step, launch, world, device):
@@ -174,7 +185,9 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     not together with ``osd`` or ``relay``).
 
     ``layered``: True -- BP runs the layered (check-serial) schedule in its default order (FLAG_LAYERED); an array -- in
-    that order of the checks.  OSD and Relay act on what it leaves unconverged.
+    that order of the checks; "large" -- the default order, with the messages in a global workspace on matrices whose
+    record state passes 160 KiB of LDS (OPT_LAYERED_MEM 2; True refuses those).  OSD and Relay act on what it leaves
+    unconverged.
 
     ``relay``: a ``relay.RelayConfig`` or its dict form -- Relay-BP instead of OSD on the trials BP does not converge
     on (FLAG_RELAY; not together with ``osd``).
@@ -854,6 +867,9 @@ def main(argv=None):
     ap.add_argument("--layered", action="store_true",
                     help="BP runs the layered (check-serial) schedule in its default order instead of flooding "
                          "(sum-product or min-sum; not with --budgets, --spectrum, --shots)")
+    ap.add_argument("--layered-large", action="store_true",
+                    help="with --layered: also on matrices whose record state passes 160 KiB of LDS (space-time and "
+                         "detector-error-model matrices): their messages live in a global workspace")
     ap.add_argument("--relay-stop", type=int, default=1, metavar="S", help="stop after S solutions, keep the lightest")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
@@ -907,11 +923,15 @@ def main(argv=None):
             lsd = lsd_mod.check_bits_per_step(args.lsd)
         except ValueError as e:
             ap.error(f"--lsd: {e}")
+    if args.layered_large and not args.layered:
+        ap.error("--layered-large needs --layered")
     if args.layered:
         if args.budgets is not None or args.spectrum is not None or args.shots is not None:
             ap.error("--layered does not combine with --budgets, --spectrum or --shots")
         if args.variant == "damped":
             ap.error("--layered needs --variant sum-product or min-sum")
+        if args.layered_large:
+            args.layered = "large"          # (the drivers' layered= argument: True or "large")
     if args.depolarizing is not None:
         if (args.dem is not None or args.phenomenological is not None or args.shots is not None or args.budgets is not None
                 or args.spectrum is not None or args.weights is not None or relay is not None or gd is not None

@@ -32,7 +32,7 @@ UNITS += ([("qbp_tu_fused.hip", ["-DQBP_SHOTS_TU"])] +
 UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
 # Relay-BP (qbp_relay_decode_batch, QBP_FLAG_RELAY): bp_relay_kernel, batch and records builds
 UNITS += [("qbp_tu_relay.hip", [])]
-# Layered BP (QBP_FLAG_LAYERED): bp_layered_kernel<variant, mc>
+# Layered BP (QBP_FLAG_LAYERED): bp_layered_kernel<variant, mc, large>
 UNITS += [("qbp_tu_layered.hip", [])]
 # BP guided decimation (qbp_gd_decode_batch, QBP_FLAG_GD): bp_gd_kernel<variant, records>
 UNITS += [("qbp_tu_gd.hip", [])]
