@@ -490,7 +490,21 @@ int qbp_layered_configure(qbp_handle* h, const int32_t* order);
  *   and clip_llr finite (used by QBP_MIN_SUM only, as in rework/decoding.py).
  * QBP_E_INVALID: a value out of range or not finite, QBP_DAMPED_SP.  QBP_E_UNSUPPORTED: a matrix whose per-record
  * state -- E messages, two rows of n doubles, and numpy's function tables for sum-product -- does not fit the 160 KiB of
- * LDS of one workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not).
+ * LDS of one workgroup (every code of codes/ and the 864 x 2592 phenomenological matrix fit; 2592 x 7776 does not),
+ * unless QBP_OPT_GD_MEM allows the other memory layout:
+ *
+ * Two memory layouts (QBP_OPT_GD_MEM, set with qbp_set_option before or after qbp_gd_configure; every launch checks
+ * again and refuses, outputs untouched, what its value does not allow):
+ *   0 (default)  a record's whole state in LDS: 8 (E + 2 n) bytes + the bookkeeping (+ 3072 for sum-product's tables);
+ *   1            the E messages in a per-workgroup global workspace (grid x E doubles, it stays in L2 / Infinity
+ *                Cache), the working prior W not stored -- two bits per variable (decimated, sign) and the prior read
+ *                from global memory state it --; in LDS stay the n posterior values, the two bit maps and the
+ *                bookkeeping: 8 n + n / 4 + 12 (m / 32) bytes (+ 3072).  QBP_E_UNSUPPORTED beyond 160 KiB of that: n of
+ *                about 19 800, 19 400 for sum-product (2592 x 7776 takes 64 KiB, 67 KiB for sum-product; the
+ *                1008 x 8991 detector error model 73 KiB and 76 KiB);
+ *   2            automatic: layout 0 where it fits its 160 KiB, else layout 1 (the limit is layout 1's).
+ * The outputs do not depend on the layout (same rules, same order of every sum, every W[v] the same value).
+ * QBP_INFO_THREADS, QBP_INFO_GRID and QBP_INFO_LDS_BYTES report the launch.
  *
  * One record (syndrome s, prior P [n] finite):
  *   1. W = P (the working prior), Q = P on the edges, V = P, D = {} (the decimated set), total = 0, rounds = 0;
@@ -513,7 +527,8 @@ int qbp_layered_configure(qbp_handle* h, const int32_t* order);
  *   Every floating-point operation is rounded on its own; nothing is fused or reordered.
  * qbp_gd_decode_batch: syndromes [B][m], prior [n] (host entry: a value that is not finite is QBP_E_INVALID) ->
  * hard [B][n], converged [B], iters [B], llr [B][n], rounds [B]; any output may be NULL.  QBP_E_INVALID without a
- * configuration.  One workgroup per record, all of its state in LDS (bp_gd_kernel).
+ * configuration.  One workgroup per record, its state in LDS or (layout 1) the messages in global memory
+ * (bp_gd_kernel).
  *
  * QBP_FLAG_GD in a Monte-Carlo call: the first stage is the call's BP as without the flag (any variant, flooding or
  * QBP_FLAG_LAYERED); every trial it leaves unconverged is decoded by the rules above from its syndrome and the call's
@@ -521,7 +536,8 @@ int qbp_layered_configure(qbp_handle* h, const int32_t* order);
  * counts the records BPGD leaves unsolved (their hard decision misses the syndrome); [0], [6], [7] are the first
  * stage's.  The record limits of QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with
  * QBP_FLAG_OSD0, any OSD bit or QBP_FLAG_RELAY, or without a configuration.  QBP_E_UNSUPPORTED: in qbp_mc_run_budgets,
- * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum and qbp_decode_shots.
+ * qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum and qbp_decode_shots, and on matrices qbp_gd_configure refuses under
+ * the handle's QBP_OPT_GD_MEM (the same function chooses the layout).
  */
 int qbp_gd_configure(qbp_handle* h, int32_t iters_per_round, int32_t max_rounds, double decim_llr, int32_t variant,
                      double alpha, double clip_llr);
@@ -981,6 +997,9 @@ enum {
                                     workspace always (tests reach it on small matrices), 2 automatic.  Results do not
                                     depend on it */
     QBP_OPT_LAYERED_MEM = 17,    /* layered BP, where a record's messages live (qbp_layered_configure): 0 LDS only, 1 a
+                                    global workspace always (tests reach it on small matrices), 2 automatic.  Results do
+                                    not depend on it */
+    QBP_OPT_GD_MEM = 18,         /* BP guided decimation, where a record's messages live (qbp_gd_configure): 0 LDS only, 1 a
                                     global workspace always (tests reach it on small matrices), 2 automatic.  Results do
                                     not depend on it */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc

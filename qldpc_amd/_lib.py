@@ -50,6 +50,8 @@ OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per
 OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
 OPT_RELAY_MEM = 16           # Relay-BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
 RELAY_MEM = {False: 0, True: 2, "force": 1}     # ``relay.RelayConfig.large`` -> OPT_RELAY_MEM
+OPT_GD_MEM = 18              # BP guided decimation, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
+GD_MEM = {False: 0, True: 1, "auto": 2}         # ``gd.GDConfig.large`` -> OPT_GD_MEM
 OPT_LAYERED_MEM = 17         # layered BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
 LAYERED_MEM = {False: 0, True: 2}               # ``Decoder.layered_configure(large=)`` -> OPT_LAYERED_MEM
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
@@ -732,7 +734,9 @@ class Decoder:
 
     @_locked
     def gd_configure(self, cfg):
-        """Store a BP guided decimation configuration (``gd.GDConfig``) in the handle: qbp_gd_configure."""
+        """Store a BP guided decimation configuration (``gd.GDConfig``) in the handle: OPT_GD_MEM from ``cfg.large``,
+        then qbp_gd_configure."""
+        _check(load().qbp_set_option(self._h, OPT_GD_MEM, GD_MEM[cfg.large]))
         _check(load().qbp_gd_configure(self._h, cfg.iters_per_round, cfg.max_rounds, cfg.decim_llr, cfg.variant,
                                        cfg.alpha, cfg.clip_llr))
 

@@ -307,7 +307,8 @@ struct qbp_handle {
     DevBuf<int32_t> d_epos, d_cpos, d_long_edge_row;
     DevBuf<int32_t> d_vpos, d_vrow, d_lcol_ptr;      // general-H kernel: column-class tables
     DevBuf<double> d_wsL, d_prior_sorted;
-    DevBuf<double> d_wsM;           // Relay-BP, large build: [grid][E] messages
+    DevBuf<double> d_wsM;           // Relay-BP and BP guided decimation, large builds: [grid][E] messages (a call has
+                                    // one second stage, and neither kernel keeps messages from launch to launch)
     int gcol_base[qbp::GENERIC_MAX_COL_CLASS + 2] = {0};
     int rpad_off[qbp::GENERIC_MAX_ROW_CLASS + 2] = {0}, cpad_off[qbp::GENERIC_MAX_COL_CLASS + 2] = {0};
     int opt_threads = 0;            // general-H kernel: threads per workgroup (0 = auto)
@@ -365,6 +366,7 @@ struct qbp_handle {
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
     int opt_relay_mem = 0;          // QBP_OPT_RELAY_MEM
+    int opt_gd_mem = 0;             // QBP_OPT_GD_MEM
     // BP guided decimation (qbp_gd_configure); scratch of the host-pointer entry
     bool gd_ready = false;
     int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
@@ -2415,9 +2417,25 @@ try {
 QBP_ABI_CATCH
 
 // ---- BP guided decimation (qbp_gd.hpp) ---------------------------------------------------------------------------
-// The kernel keeps a record's whole state in LDS: matrices beyond that are QBP_E_UNSUPPORTED.
+// QBP_OPT_GD_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
+// global workspace; 2: there where the state does not fit the LDS.
+static bool gd_large(const qbp_handle* h, int variant)
+{
+    if (h->opt_gd_mem == 2)
+        return qbp::gd_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT) > (size_t)160 * 1024;
+    return h->opt_gd_mem == 1;
+}
+
+// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
 static int gd_supported(const qbp_handle* h, int variant)
 {
+    if (h->opt_gd_mem != 0) {
+        const size_t need = qbp::gd_large_lds_bytes(h->m, h->n, variant == QBP_SUM_PRODUCT);
+        if (need > (size_t)160 * 1024)
+            return fail(QBP_E_UNSUPPORTED, "BP guided decimation with the messages in global memory keeps a row of n "
+                                           "doubles in LDS: %d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
+        return QBP_OK;
+    }
     const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT);
     if (lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "BP guided decimation keeps the messages and two rows of n doubles in LDS: %d x %d "
@@ -2435,26 +2453,35 @@ static int check_gd_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
     if (other_entry)
         return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_GD is not available with iteration budgets, spectra or recorded shots");
     if (!h->gd_ready) return fail(QBP_E_INVALID, "QBP_FLAG_GD without qbp_gd_configure");
-    return QBP_OK;                      // (qbp_gd_configure has checked the LDS)
+    return gd_supported(h, h->gd_variant);      // (QBP_OPT_GD_MEM may have changed since qbp_gd_configure)
 }
 
 static int gd_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream_t s)
 {
     constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
     const bool sp = h->gd_variant == QBP_SUM_PRODUCT;
-    const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
+    // (QBP_OPT_GD_MEM may have changed since qbp_gd_configure)
+    const int rc0 = gd_supported(h, h->gd_variant);
+    if (rc0) return rc0;
+    const bool large = gd_large(h, h->gd_variant);
+    const size_t lds = large ? qbp::gd_large_lds_bytes(h->m, h->n, sp) : qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
     const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::GD_MAX_THREADS);
     qbp::GdParams P{};
     int grid = 0;
-    // the wavefronts a CU holds at the kernel's registers: min-sum 7 per SIMD, sum-product 5; QBP_OPT_BLOCKS_PER_CU
-    // overrides
-    const int rc = record_launch_setup(h, c, records, {"BP guided decimation", lds, threads, sp ? 20 : 28, true}, s, P.tab, P.io,
+    // the wavefronts a CU holds at the kernel's registers: min-sum 7 per SIMD, sum-product 5; the large build 6 and 4
+    // (80 and 109 registers); QBP_OPT_BLOCKS_PER_CU overrides
+    const int waves = large ? (sp ? 16 : 24) : (sp ? 20 : 28);
+    const int rc = record_launch_setup(h, c, records, {"BP guided decimation", lds, threads, waves, true}, s, P.tab, P.io,
                                        &grid);
     if (rc) return rc;
     P.iters_per_round = h->gd_iters; P.max_rounds = h->gd_max_rounds; P.decim_llr = h->gd_llr;
     P.alpha = h->gd_alpha; P.clip_llr = h->gd_clip;
     P.rounds = c.extra[0];
-    HIP_TRY(qbp::launch_gd(records, h->gd_variant, P, grid, threads, lds, s));
+    if (large) {
+        HIP_TRY(h->d_wsM.reserve((size_t)grid * (size_t)h->E));       // (Relay's buffer: qbp_handle says why)
+        P.wsM = h->d_wsM.p;
+    }
+    HIP_TRY(qbp::launch_gd(records, large, h->gd_variant, P, grid, threads, lds, s));
     return QBP_OK;
 }
 
@@ -3297,6 +3324,9 @@ try {
         case QBP_OPT_RELAY_MEM:
             if (value < 0 || value > 2) return fail(QBP_E_INVALID, "Relay-BP memory mode out of range");
             h->opt_relay_mem = (int)value; return QBP_OK;
+        case QBP_OPT_GD_MEM:
+            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "BP guided decimation memory mode out of range");
+            h->opt_gd_mem = (int)value; return QBP_OK;
         case QBP_OPT_GENERAL_THREADS:
             if (value < 0 || value > 1024) return fail(QBP_E_INVALID, "threads per workgroup out of range");
             h->opt_threads = (int)value; return QBP_OK;

@@ -26,6 +26,15 @@
 // Two builds: RECORDS = false decodes B syndromes to outputs; RECORDS = true reads the failure records of a Monte-Carlo
 // launch (count and list in device memory, fail_syn, fail_err), decodes them and classifies the result into the
 // counters, as the Relay-BP and OSD record kernels do.
+// Two memory layouts of each (QBP_OPT_GD_MEM): LARGE = false is the above; LARGE = true is the same statement for
+// matrices whose E messages do not fit -- space-time and detector-error-model matrices.  Its messages are the
+// workgroup's slice of a global workspace wsM[grid][E], as in bp_relay_kernel<RECORDS, true> (qbp_relay.hpp says what
+// orders a store before the barrier with a load after it); the shared steps reach them through RecordLds::M and are
+// called unchanged, the sum-product rows of this file go through the same pointer, and both barriers stay where they
+// are.  W[n] is not stored: a decimated variable holds exactly +-decim_llr and every other its prior, so a second n-bit
+// map (the sign) beside the decimated map states W, and the prior is read where the launch permuted it (prior_sorted).
+// In LDS stay the tables, V[n] (the arg-max reads it), the words and the two maps: 8 n bytes + the words, 65 288 B for
+// 2592 x 7776 (68 360 B with the tables).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -46,6 +55,8 @@ struct GdParams {
     double decim_llr, alpha, clip_llr;
     // ---- batch build: the output beyond RecordIo's (may be null) ------------------------------------------------------
     int32_t* rounds;                // [B] variables decimated
+    // ---- LARGE build -----------------------------------------------------------------------------------------------------
+    double* wsM;                    // [grid][E] the messages of the workgroups' current records
 };
 
 // 32-bit words behind the doubles: logical mask (2), error weight, difference flag, unsatisfied checks [2], next
@@ -63,6 +74,18 @@ __host__ __device__ inline size_t gd_lds_bytes(int m, int n, int E, bool tables)
     return (tables ? (size_t)NP_LDS_BYTES : 0) + (size_t)8 * ((size_t)E + 2 * (size_t)n) + 4 * gd_lds_words(m, n);
 }
 
+// The same of the LARGE build: a second map [nw], the signs of the decimated variables
+__host__ __device__ inline size_t gd_large_lds_words(int m, int n)
+{
+    const size_t mw = ((size_t)m + 31) >> 5, nw = ((size_t)n + 31) >> 5;
+    return ((size_t)GD_HEAD_WORDS + 3 * mw + 2 * nw + 1) & ~(size_t)1;
+}
+// Dynamic LDS of one workgroup of the LARGE build: (sum-product) the function tables, V [n], the words
+__host__ __device__ inline size_t gd_large_lds_bytes(int m, int n, bool tables)
+{
+    return (tables ? (size_t)NP_LDS_BYTES : 0) + (size_t)8 * (size_t)n + 4 * gd_large_lds_words(m, n);
+}
+
 // The arg-max key: larger |V| bits first, then the lower variable index.  (0, INT_MAX) is "no candidate": every
 // candidate beats it.
 struct GdKey {
@@ -74,7 +97,8 @@ __device__ __forceinline__ bool gd_better(const GdKey& a, const GdKey& b)
     return a.bits > b.bits || (a.bits == b.bits && a.var < b.var);
 }
 
-template <int VARIANT, bool RECORDS>
+// LARGE: the messages in the workgroup's slice of P.wsM, the working prior from the two maps and prior_sorted.
+template <int VARIANT, bool RECORDS, bool LARGE = false>
 __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
 {
     static_assert(VARIANT == 0 || VARIANT == 2, "sum-product or min-sum");
@@ -85,10 +109,11 @@ __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
     const RecordIo& io = P.io;
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
     const int m = G.m, n = G.n, E = G.E;
-    double* const M = gd_smem + TAB;                // [E] messages, in place
-    double* const V = M + E;                        // [n] posterior values, sorted-variable order
-    double* const Wp = V + n;                       // [n] working prior, sorted-variable order
-    unsigned* const words = reinterpret_cast<unsigned*>(Wp + n);
+    // [E] messages, in place
+    double* const M = LARGE ? P.wsM + (size_t)blockIdx.x * (size_t)E : gd_smem + TAB;
+    double* const V = LARGE ? gd_smem + TAB : M + E;    // [n] posterior values, sorted-variable order
+    double* const Wp = V + n;                       // [n] working prior, sorted-variable order (not LARGE)
+    unsigned* const words = reinterpret_cast<unsigned*>(LARGE ? V + n : Wp + n);
     const int mw = (m + 31) >> 5, nw = (n + 31) >> 5;
     unsigned long long* const am_bits = reinterpret_cast<unsigned long long*>(words + 8);      // [GD_MAX_WAVES]
     int* const am_var = reinterpret_cast<int*>(words + 8 + 2 * GD_MAX_WAVES);                  // [GD_MAX_WAVES]
@@ -97,6 +122,7 @@ __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
                       reinterpret_cast<int*>(words + 3), reinterpret_cast<int*>(words + 4), words + 6,
                       words + GD_HEAD_WORDS, words + GD_HEAD_WORDS + mw};
     unsigned* const decw = S.par + 2 * mw;          // [nw] decimated variables, by sorted position
+    unsigned* const sgnw = decw + nw;               // [nw] LARGE: those decimated to -decim_llr
 
     const int first_long = G.row_off[RC + 1], n_long = G.row_off[RC + 2] - first_long;
     const int lbase = G.row_base[RC + 1], n_ledges = E - lbase;
@@ -110,10 +136,15 @@ __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
     for (long long item = blockIdx.x; item < count;) {
         const long long rec = record_load_syndrome<RECORDS>(G, io, S, item);
         // ---- rule 1: W = V = prior, Q = prior on the edges, nothing decimated ----------------------------------------
-        for (int i = tid; i < nw; i += nt) decw[i] = 0u;
-        for (int x = tid; x < n; x += nt) {
-            const double pv = G.prior_sorted[x];
-            Wp[x] = pv; V[x] = pv;
+        if constexpr (LARGE) {
+            for (int i = tid; i < 2 * nw; i += nt) decw[i] = 0u;      // (both maps)
+            for (int x = tid; x < n; x += nt) V[x] = G.prior_sorted[x];
+        } else {
+            for (int i = tid; i < nw; i += nt) decw[i] = 0u;
+            for (int x = tid; x < n; x += nt) {
+                const double pv = G.prior_sorted[x];
+                Wp[x] = pv; V[x] = pv;
+            }
         }
         record_prior_to_edges(G, S, G.prior_sorted);
         __syncthreads();
@@ -185,7 +216,16 @@ __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
                 __syncthreads();                                          // ---- barrier A
                 // ================= variable step (rules 2.2 - 2.4) + incremental syndrome test (2.5) ================
                 const int p = total & 1;
-                record_variable_step<VARIANT == 2>(G, S, p, syn_weight, P.clip_llr, [&](int x) { return Wp[x]; });
+                if constexpr (LARGE) {
+                    // W of the sorted variable x: +-decim_llr where decimated, else its prior (every value W[x] held)
+                    record_variable_step<VARIANT == 2>(G, S, p, syn_weight, P.clip_llr, [&](int x) {
+                        const unsigned bit = 1u << (x & 31);
+                        if (decw[x >> 5] & bit) return (sgnw[x >> 5] & bit) ? -P.decim_llr : P.decim_llr;
+                        return G.prior_sorted[x];
+                    });
+                } else {
+                    record_variable_step<VARIANT == 2>(G, S, p, syn_weight, P.clip_llr, [&](int x) { return Wp[x]; });
+                }
                 __syncthreads();                                          // ---- barrier B
                 ++total;
                 solved = S.unsat[p] == 0;
@@ -217,7 +257,11 @@ __global__ __launch_bounds__(GD_MAX_THREADS) void bp_gd_kernel(const GdParams P)
             if (best.var == 0x7fffffff) break;                            // no candidate left (uniform)
             if (tid == 0) {
                 // (W and the map are read next after barrier A of the coming iteration; V is written after it)
-                Wp[best.pos] = V[best.pos] < 0.0 ? -P.decim_llr : P.decim_llr;
+                if constexpr (LARGE) {
+                    if (V[best.pos] < 0.0) sgnw[best.pos >> 5] |= 1u << (best.pos & 31);
+                } else {
+                    Wp[best.pos] = V[best.pos] < 0.0 ? -P.decim_llr : P.decim_llr;
+                }
                 decw[best.pos >> 5] |= 1u << (best.pos & 31);
             }
             ++rounds;

@@ -148,8 +148,10 @@ hipError_t launch_relay(bool records, bool large, const RelayParams& P, int grid
 // messages in LDS or (large) in a global workspace)
 hipError_t launch_layered(bool mc, bool large, int variant, const LayeredParams& P, int grid, size_t lds,
                           hipStream_t s);
-// qbp_tu_gd.hip: bp_gd_kernel<variant, records> (sum-product or min-sum; batch build or Monte-Carlo failure records)
-hipError_t launch_gd(bool records, int variant, const GdParams& P, int grid, int threads, size_t lds, hipStream_t s);
+// qbp_tu_gd.hip: bp_gd_kernel<variant, records, large> (sum-product or min-sum; batch build or Monte-Carlo failure
+// records; the messages in LDS or (large) in a global workspace)
+hipError_t launch_gd(bool records, bool large, int variant, const GdParams& P, int grid, int threads, size_t lds,
+                     hipStream_t s);
 // qbp_tu_cond.hip: bp_cond_kernel<variant> (sum-product or min-sum; a prior per record), and the glue kernels of the
 // two-stage CSS decoder (qbp_cond.hpp): t1 <= t2 <= t3 are the sampler's cumulative thresholds (Z, X, Y)
 hipError_t launch_cond(int variant, const CondParams& P, int grid, int threads, size_t lds, hipStream_t s);

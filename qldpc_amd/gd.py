@@ -7,6 +7,11 @@ Relay-BP, to decode what BP leaves unconverged.
 
 ``GDConfig`` is the same configuration as an object, for the ``gd=`` argument of ``mc.run_sweep``, ``mc.run_dem`` and
 ``mc.run_weights`` (trials the first-stage BP leaves unconverged go to BPGD instead of OSD).
+
+``large``: where a record's messages live.  False (default): in LDS, and a matrix whose record state passes 160 KiB
+(about 40 rounds of the [[72,12,6]] phenomenological matrix, 2592 x 7776) is refused; True: always in a per-workgroup
+global workspace; "auto": in LDS where they fit, else in the workspace (the space-time and detector-error-model
+matrices).  The outputs do not depend on it.
 """
 from __future__ import annotations
 
@@ -27,9 +32,13 @@ def _integer(name, value, lo):
 
 class GDConfig:
     """iters_per_round, max_rounds, decim_llr, variant, alpha, clip_llr -- validated as qbp_gd_configure does (ValueError
-    where the library answers QBP_E_INVALID)."""
+    where the library answers QBP_E_INVALID) --, and ``large`` (False, True or "auto": QBP_OPT_GD_MEM 0, 1 or 2)."""
 
-    def __init__(self, iters_per_round=8, max_rounds=0, decim_llr=25.0, variant=MIN_SUM, alpha=1.0, clip_llr=20.0):
+    def __init__(self, iters_per_round=8, max_rounds=0, decim_llr=25.0, variant=MIN_SUM, alpha=1.0, clip_llr=20.0,
+                 large=False):
+        if not (isinstance(large, bool) or (isinstance(large, str) and large == "auto")):
+            raise ValueError(f"large must be False, True or 'auto', got {large!r}")
+        self.large = large
         self.iters_per_round = _integer("iters_per_round", iters_per_round, 1)
         self.max_rounds = _integer("max_rounds", max_rounds, 0)
         if isinstance(variant, (bool, np.bool_)) or variant not in (SUM_PRODUCT, MIN_SUM):
@@ -50,7 +59,8 @@ def as_config(gd):
     if isinstance(gd, GDConfig):
         return gd
     if isinstance(gd, dict):
-        unknown = sorted(set(gd) - {"iters_per_round", "max_rounds", "decim_llr", "variant", "alpha", "clip_llr"})
+        unknown = sorted(set(gd) - {"iters_per_round", "max_rounds", "decim_llr", "variant", "alpha", "clip_llr",
+                                    "large"})
         if unknown:
             raise ValueError(f"unknown gd settings: {unknown}")
         return GDConfig(**gd)
@@ -58,19 +68,19 @@ def as_config(gd):
 
 
 def performBPGDBatch(H, syndromes, prior, iters_per_round=8, max_rounds=0, decim_llr=25.0, variant=MIN_SUM, alpha=1.0,
-                     clip_llr=20.0, device=None):
+                     clip_llr=20.0, device=None, large=False):
     """BPGD of B syndromes uint8[B, m] on the GPU -> ``GDResult(hard uint8[B, n], converged bool[B], iters int32[B],
-    llr float64[B, n], rounds int32[B])``."""
+    llr float64[B, n], rounds int32[B])``.  ``large``: as in ``GDConfig``."""
     from . import bp
-    cfg = GDConfig(iters_per_round, max_rounds, decim_llr, variant, alpha, clip_llr)
+    cfg = GDConfig(iters_per_round, max_rounds, decim_llr, variant, alpha, clip_llr, large)
     dec = bp.decoder_for(H, device=bp.DEVICE if device is None else device)
     return GDResult(*dec.gd_decode(syndromes, prior, cfg))
 
 
 def performBPGD(H, syndrome, initialBelief, iters_per_round=8, max_rounds=0, decim_llr=25.0, variant=MIN_SUM, alpha=1.0,
-                clip_llr=20.0, device=None):
+                clip_llr=20.0, device=None, large=False):
     """BPGD of one syndrome, in the shape of the reference's decoders: ``(candidateError, converged, values,
     iterations)`` -- iterations executed over all rounds."""
     r = performBPGDBatch(H, np.asarray(syndrome).reshape(1, -1), initialBelief, iters_per_round, max_rounds, decim_llr,
-                         variant, alpha, clip_llr, device)
+                         variant, alpha, clip_llr, device, large)
     return r.hard[0], bool(r.converged[0]), r.llr[0], int(r.iters[0])

@@ -182,7 +182,8 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     not together with ``osd``, ``relay`` or ``gd``).
 
     ``gd``: a ``gd.GDConfig`` or its dict form -- BP guided decimation on the trials BP does not converge on (FLAG_GD;
-    not together with ``osd`` or ``relay``).
+    not together with ``osd`` or ``relay``); its ``large`` (False, True, "auto") allows matrices whose record state
+    passes 160 KiB of LDS (OPT_GD_MEM).
 
     ``layered``: True -- BP runs the layered (check-serial) schedule in its default order (FLAG_LAYERED); an array -- in
     that order of the checks; "large" -- the default order, with the messages in a global workspace on matrices whose
@@ -857,6 +858,9 @@ def main(argv=None):
                     help="BP guided decimation on the trials BP does not converge on: rounds of T iterations, at most "
                          "ROUNDS variables decimated (with --alpha and --clip-llr; not with --osd, --relay, --budgets, "
                          "--spectrum, --shots)")
+    ap.add_argument("--gd-large", action="store_true",
+                    help="with --gd: also on matrices whose record state passes 160 KiB of LDS (space-time and "
+                         "detector-error-model matrices): their messages live in a global workspace")
     ap.add_argument("--gd-llr", type=float, default=25.0, metavar="X", help="the prior a decimated variable gets is +-X")
     ap.add_argument("--gd-variant", choices=("sum-product", "min-sum"), default="min-sum",
                     help="the BP that --gd runs between decimations")
@@ -898,6 +902,8 @@ def main(argv=None):
         except (ValueError, TypeError) as e:
             ap.error(f"--relay: {e}")
     gd = None
+    if args.gd_large and args.gd is None:
+        ap.error("--gd-large needs --gd")
     if args.gd is not None:
         if args.osd or args.relay is not None:
             ap.error("--gd excludes --osd and --relay")
@@ -905,7 +911,7 @@ def main(argv=None):
             ap.error("--gd does not combine with --budgets, --spectrum or --shots")
         gd = dict(iters_per_round=args.gd[0], max_rounds=args.gd[1], decim_llr=args.gd_llr,
                   variant=_lib.MIN_SUM if args.gd_variant == "min-sum" else _lib.SUM_PRODUCT, alpha=args.alpha,
-                  clip_llr=args.clip_llr)
+                  clip_llr=args.clip_llr, large="auto" if args.gd_large else False)
         try:
             from . import gd as gd_mod
             gd_mod.as_config(gd)

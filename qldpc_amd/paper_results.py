@@ -74,6 +74,12 @@ def main(argv=None):
     ap.add_argument("--lsd", type=int, default=None, metavar="G",
                     help="localized statistics decoding instead of OSD on BP failures: G variables per cluster and round, "
                          "0: all neighbours (not with --osd 0 or --osd-order)")
+    ap.add_argument("--gd", type=int, nargs=2, default=None, metavar=("T", "ROUNDS"),
+                    help="BP guided decimation (min-sum, mc.py's defaults) instead of OSD on BP failures: rounds of T "
+                         "iterations, at most ROUNDS variables decimated (not with --osd 0, --osd-order or --lsd)")
+    ap.add_argument("--gd-large", action="store_true",
+                    help="with --gd: also on matrices whose record state passes 160 KiB of LDS: their messages live in a "
+                         "global workspace")
     ap.add_argument("--osd-method", choices=("cs", "e"), default="cs",
                     help="with --osd-order W >= 1: combination sweep or exhaustive search")
     ap.add_argument("--osd-order", type=int, default=0,
@@ -88,13 +94,20 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.lsd is not None and (args.osd == 0 or args.osd_order):
         ap.error("--lsd excludes --osd 0 and --osd-order")
+    if args.gd_large and args.gd is None:
+        ap.error("--gd-large needs --gd")
+    if args.gd is not None and (args.osd == 0 or args.osd_order or args.lsd is not None):
+        ap.error("--gd excludes --osd 0, --osd-order and --lsd")
+    gd = None if args.gd is None else dict(iters_per_round=args.gd[0], max_rounds=args.gd[1],
+                                           large="auto" if args.gd_large else False)
     if args.osd is None:
-        args.osd = -1 if args.lsd is not None else 0
+        args.osd = -1 if args.lsd is not None or gd is not None else 0
     try:
-        mc.lsd_run_flags(mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order), args.lsd)
+        mc.lsd_run_flags(mc.gd_run_flags(mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order), gd), args.lsd)
     except ValueError as e:
         ap.error(str(e))
-    osd_name = (f"LSD-{args.lsd}" if args.lsd is not None else "no OSD" if args.osd != 0 else "OSD-0" if args.osd_order == 0
+    osd_name = (f"BPGD-{args.gd[0]}x{args.gd[1]}" if gd is not None else f"LSD-{args.lsd}" if args.lsd is not None
+                else "no OSD" if args.osd != 0 else "OSD-0" if args.osd_order == 0
                 else f"OSD-{args.osd_method.upper()}-{args.osd_order}")
 
     import sys
@@ -130,7 +143,8 @@ def main(argv=None):
         t0 = time.time()
         tables[name] = mc.run_sweep(name, args.p, args.trials, draws=args.draws, seed=args.seed,
                                     max_iter=args.max_iter, osd=args.osd == 0, osd_method=args.osd_method,
-                                    osd_order=args.osd_order, rank=rank, world=world, device=local, lsd=args.lsd)
+                                    osd_order=args.osd_order, rank=rank, world=world, device=local, lsd=args.lsd,
+                                    gd=gd)
         if rank == 0:
             dt = time.time() - t0
             for p, row in zip(args.p, tables[name]):
@@ -141,7 +155,7 @@ def main(argv=None):
         print(f"\n{'=' * 60}\nTotal time: {total:.1f}s ({total / 60:.1f} min)")
         meta = dict(physicalErrorRates=args.p, trials=args.trials, maxIter=args.max_iter,
                     draws=args.draws, osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
-                    osd_decoder=osd_name, lsd=args.lsd, seed=args.seed, world_size=world,
+                    osd_decoder=osd_name, lsd=args.lsd, gd=gd, seed=args.seed, world_size=world,
                     noise="XOR of two Bernoulli(p) draws" if args.draws == 2 else "Bernoulli(p)",
                     decoder="sum-product BP (libqbp, MI355X)", seconds=total,
                     counters={n: tables[n].tolist() for n in tables},

@@ -34,7 +34,7 @@ UNITS += [("qbp_tu_osd.hip", ["-DQBP_ORDERED_TU"])]
 UNITS += [("qbp_tu_relay.hip", [])]
 # Layered BP (QBP_FLAG_LAYERED): bp_layered_kernel<variant, mc, large>
 UNITS += [("qbp_tu_layered.hip", [])]
-# BP guided decimation (qbp_gd_decode_batch, QBP_FLAG_GD): bp_gd_kernel<variant, records>
+# BP guided decimation (qbp_gd_decode_batch, QBP_FLAG_GD): bp_gd_kernel<variant, records, large>
 UNITS += [("qbp_tu_gd.hip", [])]
 # Sliding-window decoding (qbp_window_*): window_*_kernel, the glue between the windows of one call
 UNITS += [("qbp_tu_window.hip", [])]
