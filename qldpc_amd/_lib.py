@@ -48,12 +48,27 @@ OPT_NO_FIRST_STEP_TABLE = 12
 OPT_EARLY_EXIT_FULL_WG = 13
 OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per chunk (0 = default)
 OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
-OPT_RELAY_MEM = 16           # Relay-BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
-RELAY_MEM = {False: 0, True: 2, "force": 1}     # ``relay.RelayConfig.large`` -> OPT_RELAY_MEM
-OPT_GD_MEM = 18              # BP guided decimation, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
-GD_MEM = {False: 0, True: 1, "auto": 2}         # ``gd.GDConfig.large`` -> OPT_GD_MEM
-OPT_LAYERED_MEM = 17         # layered BP, where a record's messages live: 0 LDS only, 1 global workspace, 2 automatic
-LAYERED_MEM = {False: 0, True: 2}               # ``Decoder.layered_configure(large=)`` -> OPT_LAYERED_MEM
+# Relay-BP, layered BP, BP guided decimation: where a record's messages live -- 0 LDS only, 1 global workspace, 2 automatic
+OPT_RELAY_MEM, OPT_LAYERED_MEM, OPT_GD_MEM = 16, 17, 18
+# family: (the option, ``large=`` -> its value, the accepted spellings in words).  ``relay.RelayConfig.large``,
+# ``Decoder.layered_configure(large=)`` and ``gd.GDConfig.large`` spell the same three values differently (README.md)
+MSG_MEM = {
+    "relay":   (OPT_RELAY_MEM,   {False: 0, True: 2, "force": 1}, "False, True or 'force'"),
+    "layered": (OPT_LAYERED_MEM, {False: 0, True: 2},             "False or True"),
+    "gd":      (OPT_GD_MEM,      {False: 0, True: 1, "auto": 2},  "False, True or 'auto'"),
+}
+RELAY_MEM, LAYERED_MEM, GD_MEM = (MSG_MEM[family][1] for family in ("relay", "layered", "gd"))
+
+
+def msg_mem_value(family, large, spelled=None):
+    """The option value of a family's ``large=``; ValueError for what the family does not accept (``spelled``: the
+    accepted spellings in words, where the caller accepts more than the table)."""
+    _, table, words = MSG_MEM[family]
+    if not isinstance(large, (bool, str)) or large not in table:        # (1 == True: no plain lookup)
+        raise ValueError(f"large must be {spelled or words}, got {large!r}")
+    return table[large]
+
+
 KERNEL_AUTO, KERNEL_ON_CHIP, KERNEL_GENERAL, KERNEL_STREAM = 0, 1, 2, 3
 INFO = dict(m=100, n=101, edges=102, max_row_deg=103, max_col_deg=104, kernel_kind=105,
             threads=106, lds_bytes=107, grid=108, num_cu=109, last_kernel=110, one_barrier=111)
@@ -602,6 +617,10 @@ class Decoder:
     def set_option(self, option, value):
         _check(load().qbp_set_option(self._h, int(option), int(value)))
 
+    def set_msg_mem(self, family, large, spelled=None):
+        """Write a family's option of MSG_MEM from its ``large=`` (``msg_mem_value``)."""
+        self.set_option(MSG_MEM[family][0], msg_mem_value(family, large, spelled))
+
     # ---- host buffers ----------------------------------------------------------------------
     @_locked
     def layered_configure(self, order=None, large=None):
@@ -610,9 +629,7 @@ class Decoder:
         it is; False writes 0 (a record's state in LDS only: matrices beyond 160 KiB are refused); True writes 2
         (the messages in a global workspace where the LDS does not hold them)."""
         if large is not None:
-            if not isinstance(large, bool):
-                raise ValueError(f"large must be None, False or True, got {large!r}")
-            _check(load().qbp_set_option(self._h, OPT_LAYERED_MEM, LAYERED_MEM[large]))
+            self.set_msg_mem("layered", large, "None, False or True")
         oin = None
         if order is not None:
             oin = np.ascontiguousarray(order, np.int32)
@@ -699,7 +716,7 @@ class Decoder:
         qbp_relay_configure."""
         if cfg.n != self.n:
             raise ValueError(f"the relay configuration is for {cfg.n} variables, the matrix has {self.n}")
-        _check(load().qbp_set_option(self._h, OPT_RELAY_MEM, RELAY_MEM[cfg.large]))
+        self.set_msg_mem("relay", cfg.large)
         _check(load().qbp_relay_configure(self._h, cfg.gammas.ctypes.data, cfg.gammas.shape[0],
                                           cfg.leg_iters.ctypes.data, cfg.stop_after, cfg.alpha, cfg.clip_llr))
 
@@ -736,7 +753,7 @@ class Decoder:
     def gd_configure(self, cfg):
         """Store a BP guided decimation configuration (``gd.GDConfig``) in the handle: OPT_GD_MEM from ``cfg.large``,
         then qbp_gd_configure."""
-        _check(load().qbp_set_option(self._h, OPT_GD_MEM, GD_MEM[cfg.large]))
+        self.set_msg_mem("gd", cfg.large)
         _check(load().qbp_gd_configure(self._h, cfg.iters_per_round, cfg.max_rounds, cfg.decim_llr, cfg.variant,
                                        cfg.alpha, cfg.clip_llr))
 

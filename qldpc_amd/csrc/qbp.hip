@@ -28,6 +28,7 @@
 #include "qbp_layered.hpp"
 #include "qbp_window.hpp"
 #include "qbp_launch.hpp"
+#include "qbp_msg_mem.hpp"
 
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
 static_assert(QBP_MC_MAX_BUDGETS == qbp::MAX_BUDGETS, "budget ladder length");
@@ -365,8 +366,8 @@ struct qbp_handle {
     double relay_alpha = 1.0, relay_clip = 0.0;
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
-    int opt_relay_mem = 0;          // QBP_OPT_RELAY_MEM
-    int opt_gd_mem = 0;             // QBP_OPT_GD_MEM
+    // QBP_OPT_RELAY_MEM, QBP_OPT_LAYERED_MEM, QBP_OPT_GD_MEM by qbp::MsgMemFamily (qbp_msg_mem.hpp states the rule)
+    int opt_msg_mem[qbp::MSG_MEM_FAMILIES] = {0};
     // BP guided decimation (qbp_gd_configure); scratch of the host-pointer entry
     bool gd_ready = false;
     int gd_iters = 0, gd_max_rounds = 0, gd_variant = 0;
@@ -386,7 +387,6 @@ struct qbp_handle {
     int layered_levels = 0, layered_max_width = 0;
     int opt_layered_slots = 0;      // QBP_OPT_LAYERED_SLOTS (0 = auto)
     DevBuf<int32_t> d_layered_order, d_layered_level_ptr;
-    int opt_layered_mem = 0;        // QBP_OPT_LAYERED_MEM
     DevBuf<double> d_layered_wsR;   // layered BP, large build: [grid][S][E] messages
 };
 
@@ -2031,13 +2031,12 @@ static int check_csr(const int32_t* row_ptr, const int32_t* col_idx, int m, int 
     return QBP_OK;
 }
 
-// QBP_OPT_LAYERED_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
-// global workspace; 2: there where the single-slot state (by the sum-product size, as qbp_layered_configure counts)
-// does not fit the LDS.
-static bool layered_large(const qbp_handle* h)
+// The workspace step of a large launch: `count` doubles in ws, grown when a launch needs more, never shrunk.
+static int large_workspace(DevBuf<double>& ws, size_t count, double** out)
 {
-    if (h->opt_layered_mem == 2) return qbp::layered_lds_bytes(h->m, h->n, h->E, 1, true) > (size_t)160 * 1024;
-    return h->opt_layered_mem == 1;
+    HIP_TRY(ws.reserve(count));
+    *out = ws.p;
+    return QBP_OK;
 }
 
 // Dynamic LDS of a workgroup with S slots in the build `large`
@@ -2060,24 +2059,25 @@ static int layered_slots(const qbp_handle* h, long long B, bool tables, bool lar
     return (int)std::max<long long>(1, std::min<long long>(S, B));
 }
 
-// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
-static int layered_supported(const qbp_handle* h)
+// QBP_OPT_LAYERED_MEM (qbp_msg_mem.hpp), decided on the single-slot state by the sum-product size.  Matrices beyond
+// the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only); *large: the build of a launch.
+static int layered_build(const qbp_handle* h, bool* large = nullptr)
 {
-    if (h->opt_layered_mem != 0) {
-        const size_t need = qbp::layered_large_lds_bytes(h->m, h->n, 1, true);
-        if (need > (size_t)160 * 1024) {
+    const qbp::MsgMemChoice c = qbp::msg_mem_choose(
+        h->opt_msg_mem[qbp::MSG_MEM_LAYERED], layered_build_lds(h, false, 1, true), layered_build_lds(h, true, 1, true),
+        [h](bool large_build, size_t need) {
+            if (!large_build) {
+                fail(QBP_E_UNSUPPORTED, "layered BP keeps the messages, the posterior and the prior of a record in LDS: "
+                                        "%d x %d with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, need);
+                return;
+            }
             const size_t fixed = qbp::layered_large_lds_bytes(h->m, 0, 1, true);
-            return fail(QBP_E_UNSUPPORTED, "layered BP with the messages in global memory keeps the posterior, n doubles, "
-                                           "in LDS: %d x %d needs %zu B (limit 160 KiB: n <= %zu with %d checks)",
-                        h->m, h->n, need, fixed < (size_t)160 * 1024 ? ((size_t)160 * 1024 - fixed) / 8 : (size_t)0, h->m);
-        }
-        return QBP_OK;
-    }
-    const size_t lds = qbp::layered_lds_bytes(h->m, h->n, h->E, 1, true);
-    if (lds > (size_t)160 * 1024)
-        return fail(QBP_E_UNSUPPORTED, "layered BP keeps the messages, the posterior and the prior of a record in LDS: "
-                                       "%d x %d with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
-    return QBP_OK;
+            fail(QBP_E_UNSUPPORTED, "layered BP with the messages in global memory keeps the posterior, n doubles, "
+                                    "in LDS: %d x %d needs %zu B (limit 160 KiB: n <= %zu with %d checks)",
+                 h->m, h->n, need, fixed < qbp::MSG_MEM_LDS_LIMIT ? (qbp::MSG_MEM_LDS_LIMIT - fixed) / 8 : (size_t)0, h->m);
+        });
+    if (large) *large = c.large;
+    return c.ok ? QBP_OK : QBP_E_UNSUPPORTED;
 }
 
 // QBP_FLAG_LAYERED of a call (host only, before any GPU work).  `other_entry`: the entries without a layered build
@@ -2092,7 +2092,7 @@ static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant,
     if (variant == QBP_DAMPED_SP) return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with QBP_DAMPED_SP: no damped layered schedule");
     if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0))
         return fail(QBP_E_INVALID, "QBP_FLAG_LAYERED with a column-sum order flag: the layered schedule has no column sum");
-    return layered_supported(h);        // (QBP_OPT_LAYERED_MEM may have changed since qbp_layered_configure)
+    return layered_build(h);            // (QBP_OPT_LAYERED_MEM may have changed since qbp_layered_configure)
 }
 
 // One launch of bp_layered_kernel (device pointers): the batch build, or (c.mc) the Monte-Carlo build on stored errors
@@ -2101,10 +2101,10 @@ static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
     if (c.B > MAX_LAUNCH)
         return fail(QBP_E_UNSUPPORTED, "layered BP decodes at most 2^30 syndromes per call (got %lld)", c.B);
-    const int rc0 = layered_supported(h);
+    bool large = false;
+    const int rc0 = layered_build(h, &large);
     if (rc0) return rc0;
     const bool tables = c.variant == QBP_SUM_PRODUCT;
-    const bool large = layered_large(h);
     const int S = layered_slots(h, c.B, tables, large);
     const size_t lds = layered_build_lds(h, large, S, tables);
     // resident workgroups per CU: the LDS, and five wavefronts per SIMD at the kernel's registers
@@ -2127,10 +2127,9 @@ static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
         P.fail_list = c.mc->fail_list; P.fail_count = c.mc->fail_count; P.fail_syn = c.mc->fail_syn;
         P.fail_hard = c.mc->fail_hard; P.fail_err = c.mc->fail_err; P.fail_llr = c.mc->fail_llr;
     }
-    if (large) {
-        // a slice of E doubles per slot of every workgroup; grown when a launch needs more, never shrunk
-        HIP_TRY(h->d_layered_wsR.reserve((size_t)grid * (size_t)S * (size_t)h->E));
-        P.wsR = h->d_layered_wsR.p;
+    if (large) {                 // a slice of E doubles per slot of every workgroup
+        const int rc = large_workspace(h->d_layered_wsR, (size_t)grid * (size_t)S * (size_t)h->E, &P.wsR);
+        if (rc) return rc;
     }
     h->last_threads = qbp::LAYERED_THREADS; h->last_lds = (int)lds; h->last_grid = grid;
     HIP_TRY(qbp::launch_layered(c.mc != nullptr, large, c.variant, P, grid, lds, s));
@@ -2156,7 +2155,7 @@ QBP_ABI_CATCH
 int qbp_layered_configure(qbp_handle* h, const int32_t* order)
 try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
-    int rc = layered_supported(h);
+    int rc = layered_build(h);
     if (rc) return rc;
     std::vector<int32_t> ord, lptr;
     if ((rc = layered_plan(h->row_ptr.data(), h->col_idx.data(), h->m, h->n, order, ord, lptr)) != QBP_OK) return rc;
@@ -2175,29 +2174,28 @@ try {
 QBP_ABI_CATCH
 
 // ---- Relay-BP (qbp_relay.hpp) ------------------------------------------------------------------------------------
-// QBP_OPT_RELAY_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
-// global workspace; 2: there where the state does not fit the LDS.
-static bool relay_large(const qbp_handle* h, bool records)
+// Dynamic LDS of a workgroup in the build `large`
+static size_t relay_build_lds(const qbp_handle* h, bool large, bool records)
 {
-    if (h->opt_relay_mem == 2) return qbp::relay_lds_bytes(h->m, h->n, h->E, records) > (size_t)160 * 1024;
-    return h->opt_relay_mem == 1;
+    return large ? qbp::relay_large_lds_bytes(h->m, h->n, records) : qbp::relay_lds_bytes(h->m, h->n, h->E, records);
 }
 
-// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
-static int relay_supported(const qbp_handle* h, bool records)
+// QBP_OPT_RELAY_MEM (qbp_msg_mem.hpp), decided on the batch or the records build.  Matrices beyond the LDS of the build
+// the option allows are QBP_E_UNSUPPORTED (host only); *large: the build of a launch.
+static int relay_build(const qbp_handle* h, bool records, bool* large = nullptr)
 {
-    if (h->opt_relay_mem != 0) {
-        const size_t need = qbp::relay_large_lds_bytes(h->m, h->n, records);
-        if (need > (size_t)160 * 1024)
-            return fail(QBP_E_UNSUPPORTED, "Relay-BP with the messages in global memory keeps a row of n doubles in LDS: "
-                                           "%d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
-        return QBP_OK;
-    }
-    const size_t lds = qbp::relay_lds_bytes(h->m, h->n, h->E, records);
-    if (lds > (size_t)160 * 1024)
-        return fail(QBP_E_UNSUPPORTED, "Relay-BP keeps the messages and three rows of n doubles in LDS: %d x %d with %d "
-                                       "entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
-    return QBP_OK;
+    const qbp::MsgMemChoice c = qbp::msg_mem_choose(
+        h->opt_msg_mem[qbp::MSG_MEM_RELAY], relay_build_lds(h, false, records), relay_build_lds(h, true, records),
+        [h](bool large_build, size_t need) {
+            if (large_build)
+                fail(QBP_E_UNSUPPORTED, "Relay-BP with the messages in global memory keeps a row of n doubles in LDS: "
+                                        "%d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
+            else
+                fail(QBP_E_UNSUPPORTED, "Relay-BP keeps the messages and three rows of n doubles in LDS: %d x %d with %d "
+                                        "entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, need);
+        });
+    if (large) *large = c.large;
+    return c.ok ? QBP_OK : QBP_E_UNSUPPORTED;
 }
 
 // QBP_FLAG_RELAY of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and
@@ -2210,7 +2208,7 @@ static int check_relay_flags(const qbp_handle* h, uint32_t flags, bool other_ent
     if (other_entry)
         return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_RELAY is not available with iteration budgets, spectra or recorded shots");
     if (!h->relay_ready) return fail(QBP_E_INVALID, "QBP_FLAG_RELAY without qbp_relay_configure");
-    return relay_supported(h, true);
+    return relay_build(h, true);        // (QBP_OPT_RELAY_MEM may have changed since qbp_relay_configure)
 }
 
 // One launch of bp_relay_kernel or bp_gd_kernel (device pointers): a batch of syndromes, or the failure records of a
@@ -2313,11 +2311,10 @@ static int relay_launch(qbp_handle* h, const RecordCall& c, bool records, hipStr
 {
     constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
     // (QBP_OPT_RELAY_MEM may have changed since qbp_relay_configure)
-    const int rc0 = relay_supported(h, records);
+    bool large = false;
+    const int rc0 = relay_build(h, records, &large);
     if (rc0) return rc0;
-    const bool large = relay_large(h, records);
-    const size_t lds = large ? qbp::relay_large_lds_bytes(h->m, h->n, records)
-                             : qbp::relay_lds_bytes(h->m, h->n, h->E, records);
+    const size_t lds = relay_build_lds(h, large, records);
     const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::RELAY_MAX_THREADS);
     qbp::RelayParams P{};
     int grid = 0;
@@ -2326,8 +2323,8 @@ static int relay_launch(qbp_handle* h, const RecordCall& c, bool records, hipStr
                                        &grid);
     if (rc) return rc;
     if (large) {
-        HIP_TRY(h->d_wsM.reserve((size_t)grid * (size_t)h->E));
-        P.wsM = h->d_wsM.p;
+        const int rcw = large_workspace(h->d_wsM, (size_t)grid * (size_t)h->E, &P.wsM);
+        if (rcw) return rcw;
     }
     P.vinv = h->d_relay_vinv.p; P.prior = c.prior;
     P.gammas_sorted = h->d_relay_gammas.p; P.leg_iters = h->d_relay_iters.p;
@@ -2353,7 +2350,7 @@ try {
             if (!std::isfinite(gammas[(size_t)l * n + v]))
                 return fail(QBP_E_INVALID, "gammas[%d][%zu] is not finite", l, v);
     }
-    const int rc = relay_supported(h, false);
+    const int rc = relay_build(h, false);
     if (rc) return rc;
     // the tables follow the kernel's variable order: sorted by column weight (build_tables)
     HostTables T;
@@ -2417,30 +2414,29 @@ try {
 QBP_ABI_CATCH
 
 // ---- BP guided decimation (qbp_gd.hpp) ---------------------------------------------------------------------------
-// QBP_OPT_GD_MEM: the build of a launch.  0: the kernel keeps a record's whole state in LDS; 1: the messages in the
-// global workspace; 2: there where the state does not fit the LDS.
-static bool gd_large(const qbp_handle* h, int variant)
+// Dynamic LDS of a workgroup in the build `large`
+static size_t gd_build_lds(const qbp_handle* h, bool large, bool sp)
 {
-    if (h->opt_gd_mem == 2)
-        return qbp::gd_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT) > (size_t)160 * 1024;
-    return h->opt_gd_mem == 1;
+    return large ? qbp::gd_large_lds_bytes(h->m, h->n, sp) : qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
 }
 
-// Matrices beyond the LDS of the build the option allows are QBP_E_UNSUPPORTED (host only).
-static int gd_supported(const qbp_handle* h, int variant)
+// QBP_OPT_GD_MEM (qbp_msg_mem.hpp), decided on the variant.  Matrices beyond the LDS of the build the option allows
+// are QBP_E_UNSUPPORTED (host only); *large: the build of a launch.
+static int gd_build(const qbp_handle* h, int variant, bool* large = nullptr)
 {
-    if (h->opt_gd_mem != 0) {
-        const size_t need = qbp::gd_large_lds_bytes(h->m, h->n, variant == QBP_SUM_PRODUCT);
-        if (need > (size_t)160 * 1024)
-            return fail(QBP_E_UNSUPPORTED, "BP guided decimation with the messages in global memory keeps a row of n "
-                                           "doubles in LDS: %d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
-        return QBP_OK;
-    }
-    const size_t lds = qbp::gd_lds_bytes(h->m, h->n, h->E, variant == QBP_SUM_PRODUCT);
-    if (lds > (size_t)160 * 1024)
-        return fail(QBP_E_UNSUPPORTED, "BP guided decimation keeps the messages and two rows of n doubles in LDS: %d x %d "
-                                       "with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, lds);
-    return QBP_OK;
+    const bool sp = variant == QBP_SUM_PRODUCT;
+    const qbp::MsgMemChoice c = qbp::msg_mem_choose(
+        h->opt_msg_mem[qbp::MSG_MEM_GD], gd_build_lds(h, false, sp), gd_build_lds(h, true, sp),
+        [h](bool large_build, size_t need) {
+            if (large_build)
+                fail(QBP_E_UNSUPPORTED, "BP guided decimation with the messages in global memory keeps a row of n "
+                                        "doubles in LDS: %d x %d needs %zu B (limit 160 KiB)", h->m, h->n, need);
+            else
+                fail(QBP_E_UNSUPPORTED, "BP guided decimation keeps the messages and two rows of n doubles in LDS: %d x %d "
+                                        "with %d entries needs %zu B (limit 160 KiB)", h->m, h->n, h->E, need);
+        });
+    if (large) *large = c.large;
+    return c.ok ? QBP_OK : QBP_E_UNSUPPORTED;
 }
 
 // QBP_FLAG_GD of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and shots
@@ -2453,7 +2449,7 @@ static int check_gd_flags(const qbp_handle* h, uint32_t flags, bool other_entry)
     if (other_entry)
         return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_GD is not available with iteration budgets, spectra or recorded shots");
     if (!h->gd_ready) return fail(QBP_E_INVALID, "QBP_FLAG_GD without qbp_gd_configure");
-    return gd_supported(h, h->gd_variant);      // (QBP_OPT_GD_MEM may have changed since qbp_gd_configure)
+    return gd_build(h, h->gd_variant);          // (QBP_OPT_GD_MEM may have changed since qbp_gd_configure)
 }
 
 static int gd_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream_t s)
@@ -2461,10 +2457,10 @@ static int gd_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream
     constexpr int RC = qbp::GENERIC_MAX_ROW_CLASS, CC = qbp::GENERIC_MAX_COL_CLASS;
     const bool sp = h->gd_variant == QBP_SUM_PRODUCT;
     // (QBP_OPT_GD_MEM may have changed since qbp_gd_configure)
-    const int rc0 = gd_supported(h, h->gd_variant);
+    bool large = false;
+    const int rc0 = gd_build(h, h->gd_variant, &large);
     if (rc0) return rc0;
-    const bool large = gd_large(h, h->gd_variant);
-    const size_t lds = large ? qbp::gd_large_lds_bytes(h->m, h->n, sp) : qbp::gd_lds_bytes(h->m, h->n, h->E, sp);
+    const size_t lds = gd_build_lds(h, large, sp);
     const int threads = qbp::record_threads(h->rpad_off[RC + 1], h->cpad_off[CC + 1], qbp::GD_MAX_THREADS);
     qbp::GdParams P{};
     int grid = 0;
@@ -2477,9 +2473,9 @@ static int gd_launch(qbp_handle* h, const RecordCall& c, bool records, hipStream
     P.iters_per_round = h->gd_iters; P.max_rounds = h->gd_max_rounds; P.decim_llr = h->gd_llr;
     P.alpha = h->gd_alpha; P.clip_llr = h->gd_clip;
     P.rounds = c.extra[0];
-    if (large) {
-        HIP_TRY(h->d_wsM.reserve((size_t)grid * (size_t)h->E));       // (Relay's buffer: qbp_handle says why)
-        P.wsM = h->d_wsM.p;
+    if (large) {                 // (Relay's buffer: qbp_handle says why)
+        const int rcw = large_workspace(h->d_wsM, (size_t)grid * (size_t)h->E, &P.wsM);
+        if (rcw) return rcw;
     }
     HIP_TRY(qbp::launch_gd(records, large, h->gd_variant, P, grid, threads, lds, s));
     return QBP_OK;
@@ -2497,7 +2493,7 @@ try {
         return fail(QBP_E_INVALID, "variant = %d: BP guided decimation runs QBP_SUM_PRODUCT or QBP_MIN_SUM", variant);
     if (!std::isfinite(alpha) || !std::isfinite(clip_llr))
         return fail(QBP_E_INVALID, "alpha = %g, clip_llr = %g: both must be finite", alpha, clip_llr);
-    const int rc = gd_supported(h, variant);
+    const int rc = gd_build(h, variant);
     if (rc) return rc;
     h->gd_iters = iters_per_round; h->gd_max_rounds = max_rounds; h->gd_llr = decim_llr; h->gd_variant = variant;
     h->gd_alpha = alpha; h->gd_clip = clip_llr;
@@ -3319,14 +3315,16 @@ try {
             if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
             h->opt_layered_slots = (int)value; return QBP_OK;
         case QBP_OPT_LAYERED_MEM:
-            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "layered BP memory mode out of range");
-            h->opt_layered_mem = (int)value; return QBP_OK;
         case QBP_OPT_RELAY_MEM:
-            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "Relay-BP memory mode out of range");
-            h->opt_relay_mem = (int)value; return QBP_OK;
-        case QBP_OPT_GD_MEM:
-            if (value < 0 || value > 2) return fail(QBP_E_INVALID, "BP guided decimation memory mode out of range");
-            h->opt_gd_mem = (int)value; return QBP_OK;
+        case QBP_OPT_GD_MEM: {
+            const int family = option == QBP_OPT_LAYERED_MEM ? qbp::MSG_MEM_LAYERED
+                             : option == QBP_OPT_RELAY_MEM   ? qbp::MSG_MEM_RELAY : qbp::MSG_MEM_GD;
+            static const char* const out_of_range[qbp::MSG_MEM_FAMILIES] = {       // (by qbp::MsgMemFamily)
+                "Relay-BP memory mode out of range", "layered BP memory mode out of range",
+                "BP guided decimation memory mode out of range"};
+            if (value < qbp::MSG_MEM_LDS || value > qbp::MSG_MEM_AUTO) return fail(QBP_E_INVALID, "%s", out_of_range[family]);
+            h->opt_msg_mem[family] = (int)value; return QBP_OK;
+        }
         case QBP_OPT_GENERAL_THREADS:
             if (value < 0 || value > 1024) return fail(QBP_E_INVALID, "threads per workgroup out of range");
             h->opt_threads = (int)value; return QBP_OK;

@@ -43,7 +43,7 @@ struct LaunchCfg {
 };
 
 // Before a launch with `lds` bytes of dynamic LDS: raise the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to it,
-// once per device and size.  lds_set: the call site's own `static thread_local size_t [64] = {0}`, one per kernel.
+// once per device and size.  lds_set: the largest size set so far on every device, one table per kernel.
 inline hipError_t raise_dynamic_lds(const void* kernel, size_t lds, size_t (&lds_set)[64])
 {
     int dev = 0;
@@ -54,6 +54,20 @@ inline hipError_t raise_dynamic_lds(const void* kernel, size_t lds, size_t (&lds
         if (dev >= 0 && dev < 64) lds_set[dev] = lds;
     }
     return hipSuccess;
+}
+
+// One launch of KERNEL with `lds` bytes of dynamic LDS: the attribute as above, the launch, hipGetLastError().  The
+// kernel is a template argument so that every instantiation has a table of its own.  (`lds > 0` above sets the
+// attribute no earlier or later than a plain `lds_set[dev] < lds` would: no size is below the zeros the table starts
+// with, so a launch without dynamic LDS never set it.)
+template <auto KERNEL, class... Args>
+hipError_t launch_dynamic_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args)
+{
+    static thread_local size_t lds_set[64] = {0};
+    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(KERNEL), lds, lds_set);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(KERNEL, grid, block, lds, s, args...);
+    return hipGetLastError();
 }
 
 // qbp_tu_fused.hip

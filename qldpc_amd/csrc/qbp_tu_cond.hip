@@ -17,12 +17,7 @@ namespace {
 template <int VARIANT>
 hipError_t cond_launch_k(const CondParams& P, int grid, int threads, size_t lds, hipStream_t s)
 {
-    auto kern = bp_cond_kernel<VARIANT>;
-    static thread_local size_t lds_set[64] = {0};
-    hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_cond_kernel<VARIANT>>(dim3(grid), dim3(threads), lds, s, P);
 }
 
 // blocks for `items` lanes' worth of work: at most CSS_MAX_GRID, the kernels stride over the rest

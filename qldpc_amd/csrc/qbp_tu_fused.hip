@@ -63,20 +63,10 @@ namespace {
 template <int DC, int DV, int VARIANT, bool MC, bool FORCE, int MAXT, int MINW, bool ONEBAR = false>
 hipError_t launch_k(const FusedParams& P, const LaunchCfg& cfg, hipStream_t stream)
 {
-    auto kern = bp_fused_kernel<DC, DV, VARIANT, MC, FORCE, MAXT, MINW, ONEBAR>;
     // the dynamic-LDS limit of an instantiation is raised once per device and size (the attribute
     // call costs a few microseconds, which matters for one-syndrome-per-call users)
-    static thread_local int lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < cfg.lds_bytes) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, cfg.lds_bytes);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = cfg.lds_bytes;
-    }
-    hipLaunchKernelGGL(kern, dim3(cfg.grid), dim3(cfg.threads), cfg.lds_bytes, stream, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_fused_kernel<DC, DV, VARIANT, MC, FORCE, MAXT, MINW, ONEBAR>>(
+        dim3(cfg.grid), dim3(cfg.threads), (size_t)cfg.lds_bytes, stream, P);
 }
 
 template <int VARIANT, bool MC, int MAXT, int MINW = 1>

@@ -12,18 +12,7 @@ namespace {
 template <int VARIANT, bool RECORDS, bool LARGE>
 hipError_t gd_launch_k(const GdParams& P, int grid, int threads, size_t lds, hipStream_t s)
 {
-    auto kern = bp_gd_kernel<VARIANT, RECORDS, LARGE>;
-    static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_gd_kernel<VARIANT, RECORDS, LARGE>>(dim3(grid), dim3(threads), lds, s, P);
 }
 
 }  // namespace

@@ -40,18 +40,7 @@ namespace {
 template <int VARIANT, bool MC, int MEM>
 hipError_t generic_launch_k(const GenericParams& G, int grid, int threads, size_t lds, hipStream_t s)
 {
-    auto kern = bp_generic_kernel<VARIANT, MC, MEM>;
-    static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, G);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_generic_kernel<VARIANT, MC, MEM>>(dim3(grid), dim3(threads), lds, s, G);
 }
 
 template <bool MC, int MEM>

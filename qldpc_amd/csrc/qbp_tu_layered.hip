@@ -12,18 +12,7 @@ namespace {
 template <int VARIANT, bool MC, bool LARGE>
 hipError_t layered_launch_k(const LayeredParams& P, int grid, size_t lds, hipStream_t s)
 {
-    auto kern = bp_layered_kernel<VARIANT, MC, LARGE>;
-    static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(LAYERED_THREADS), lds, s, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_layered_kernel<VARIANT, MC, LARGE>>(dim3(grid), dim3(LAYERED_THREADS), lds, s, P);
 }
 
 template <int VARIANT>

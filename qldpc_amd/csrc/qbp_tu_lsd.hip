@@ -12,12 +12,7 @@ namespace {
 template <bool RECORDS>
 hipError_t lsd_launch_k(const LsdParams& P, unsigned grid, size_t lds, hipStream_t s)
 {
-    auto kern = lsd_kernel<RECORDS>;
-    static thread_local size_t lds_set[64] = {0};
-    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64), lds, s, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<lsd_kernel<RECORDS>>(dim3(grid), dim3(64), lds, s, P);
 }
 
 }  // namespace

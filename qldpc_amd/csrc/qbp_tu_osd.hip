@@ -79,22 +79,14 @@ hipError_t launch_osd_order(int words_per_row, unsigned grid, size_t lds, const 
 
 hipError_t launch_osd_big(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk, hipStream_t s)
 {
-    static thread_local size_t lds_set[64] = {0};
-    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(osd0_big_kernel), lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(osd0_big_kernel, dim3(grid), dim3(256), lds, s, O, Wk);
-    return hipGetLastError();
+    return launch_dynamic_lds<osd0_big_kernel>(dim3(grid), dim3(256), lds, s, O, Wk);
 }
 
 template <int RPT>
 static hipError_t launch_osd_blocked_rpt(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk,
                                          hipStream_t s)
 {
-    static thread_local size_t lds_set[64] = {0};
-    const hipError_t e = raise_dynamic_lds(reinterpret_cast<const void*>(osd0_blocked_kernel<RPT>), lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(osd0_blocked_kernel<RPT>, dim3(grid), dim3(1024), lds, s, O, Wk);
-    return hipGetLastError();
+    return launch_dynamic_lds<osd0_blocked_kernel<RPT>>(dim3(grid), dim3(1024), lds, s, O, Wk);
 }
 
 // rows per thread: m <= 1024 * rows_per_thread (1, 2, 4 or 8)
@@ -114,12 +106,7 @@ template <int RPT>
 static hipError_t launch_osd_order_blocked_rpt(unsigned grid, size_t lds, const OsdParams& O, const OsdBigWorkspace& Wk,
                                                const OsdOrderBigArgs& X, hipStream_t s)
 {
-    static thread_local size_t lds_set[64] = {0};
-    const hipError_t e =
-        raise_dynamic_lds(reinterpret_cast<const void*>(osd_order_blocked_kernel<RPT>), lds, lds_set);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(osd_order_blocked_kernel<RPT>, dim3(grid), dim3(1024), lds, s, O, Wk, X);
-    return hipGetLastError();
+    return launch_dynamic_lds<osd_order_blocked_kernel<RPT>>(dim3(grid), dim3(1024), lds, s, O, Wk, X);
 }
 
 // order w on the blocked kernel's matrices; rows per thread as launch_osd_blocked

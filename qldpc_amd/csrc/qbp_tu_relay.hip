@@ -12,18 +12,7 @@ namespace {
 template <bool RECORDS, bool LARGE>
 hipError_t relay_launch_k(const RelayParams& P, int grid, int threads, size_t lds, hipStream_t s)
 {
-    auto kern = bp_relay_kernel<RECORDS, LARGE>;
-    static thread_local size_t lds_set[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || lds_set[dev] < lds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) lds_set[dev] = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, P);
-    return hipGetLastError();
+    return launch_dynamic_lds<bp_relay_kernel<RECORDS, LARGE>>(dim3(grid), dim3(threads), lds, s, P);
 }
 
 }  // namespace

@@ -19,6 +19,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _lib
+
 SUM_PRODUCT, MIN_SUM = 0, 2
 GDResult = namedtuple("GDResult", "hard converged iters llr rounds")
 _INT32_MAX = int(np.iinfo(np.int32).max)
@@ -36,8 +38,7 @@ class GDConfig:
 
     def __init__(self, iters_per_round=8, max_rounds=0, decim_llr=25.0, variant=MIN_SUM, alpha=1.0, clip_llr=20.0,
                  large=False):
-        if not (isinstance(large, bool) or (isinstance(large, str) and large == "auto")):
-            raise ValueError(f"large must be False, True or 'auto', got {large!r}")
+        _lib.msg_mem_value("gd", large)
         self.large = large
         self.iters_per_round = _integer("iters_per_round", iters_per_round, 1)
         self.max_rounds = _integer("max_rounds", max_rounds, 0)

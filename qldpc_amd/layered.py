@@ -46,8 +46,7 @@ def performLayeredBPBatch(H, syndromes, initialBelief, maxIter=50, variant="sum-
                           order=None, device=None, large=False):
     """Layered BP of B syndromes uint8[B, m] -> ``(hard uint8[B, n], converged bool[B], iters int32[B],
     llr float64[B, n])``.  ``large``: see the module's text."""
-    if not isinstance(large, bool):
-        raise ValueError(f"large must be False or True, got {large!r}")
+    _lib.msg_mem_value("layered", large)
     from . import bp
     v = _variant(variant)
     prior = np.ascontiguousarray(initialBelief, np.float64)

@@ -885,9 +885,10 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order, args.osd_large)
     except ValueError as e:
         ap.error(str(e))
+    for name in ("relay", "gd", "layered"):
+        if getattr(args, name + "_large") and getattr(args, name) in (None, False):
+            ap.error(f"--{name}-large needs --{name}")
     relay = None
-    if args.relay_large and args.relay is None:
-        ap.error("--relay-large needs --relay")
     if args.relay is not None:
         if args.osd:
             ap.error("--relay and --osd exclude each other")
@@ -902,8 +903,6 @@ def main(argv=None):
         except (ValueError, TypeError) as e:
             ap.error(f"--relay: {e}")
     gd = None
-    if args.gd_large and args.gd is None:
-        ap.error("--gd-large needs --gd")
     if args.gd is not None:
         if args.osd or args.relay is not None:
             ap.error("--gd excludes --osd and --relay")
@@ -929,8 +928,6 @@ def main(argv=None):
             lsd = lsd_mod.check_bits_per_step(args.lsd)
         except ValueError as e:
             ap.error(f"--lsd: {e}")
-    if args.layered_large and not args.layered:
-        ap.error("--layered-large needs --layered")
     if args.layered:
         if args.budgets is not None or args.spectrum is not None or args.shots is not None:
             ap.error("--layered does not combine with --budgets, --spectrum or --shots")

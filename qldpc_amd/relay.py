@@ -19,6 +19,8 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import _lib
+
 RelayResult = namedtuple("RelayResult", "hard converged iters llr legs solutions")
 
 
@@ -57,8 +59,7 @@ class RelayConfig:
             raise ValueError(f"stop_after must be an integer >= 1, got {stop_after!r}")
         if not np.all(np.isfinite(g)) or not np.isfinite(alpha) or not np.isfinite(clip_llr):
             raise ValueError("gammas, alpha and clip_llr must be finite")
-        if not (isinstance(large, bool) or large == "force"):
-            raise ValueError(f"large must be False, True or 'force', got {large!r}")
+        _lib.msg_mem_value("relay", large)
         self.large = large
         self.gammas = g
         self.leg_iters = np.ascontiguousarray(it, np.int32)

@@ -6,7 +6,7 @@ import re
 
 import pytest
 
-import gd_large_util as gl
+import large_util as lu
 import record_kernel_util as ru
 from qldpc_amd import _lib, gd, mc, paper_results
 
@@ -19,7 +19,7 @@ def test_constant_equals_the_header():
     assert m and int(m.group(1)) == _lib.OPT_GD_MEM == 18
     values = [int(v) for v in re.findall(r"\bQBP_OPT_[A-Z0-9_]+\s*=\s*(\d+)", header)]
     assert values.count(18) == 1
-    assert _lib.GD_MEM == {False: gl.MEM_LDS, True: gl.MEM_LARGE, "auto": gl.MEM_AUTO}
+    assert _lib.GD_MEM == {False: lu.MEM_LDS, True: lu.MEM_LARGE, "auto": lu.MEM_AUTO}
 
 
 def test_the_header_states_the_large_figure_as_restated():
@@ -31,43 +31,43 @@ def test_the_header_states_the_large_figure_as_restated():
     # the wavefronts per CU of gd_launch are those the restated grid counts on
     host = open(os.path.join(ROOT, "qldpc_amd", "csrc", "qbp.hip")).read()
     assert "const int waves = large ? (sp ? 16 : 24) : (sp ? 20 : 28);" in host
-    assert gl.LARGE_WAVES_PER_CU == {True: 16, False: 24}
+    assert lu.GD_LARGE_WAVES_PER_CU == {True: 16, False: 24}
 
 
 def test_lds_figures_of_the_two_headline_matrices():
     assert ru.GD_HEAD_WORDS == 40 and ru.np_lds_bytes() == 3072
     # 2592 x 7776: 81 + 2 * 81 check words, 2 * 243 map words
-    assert gl.gd_large_lds_words(2592, 7776) == 40 + 3 * 81 + 2 * 243 + 1 == 770
-    assert gl.gd_large_lds_bytes(2592, 7776, False) == 8 * 7776 + 4 * 770 == 65288
-    assert gl.gd_large_lds_bytes(2592, 7776, True) == 65288 + 3072 == 68360
+    assert lu.gd_large_lds_words(2592, 7776) == 40 + 3 * 81 + 2 * 243 + 1 == 770
+    assert lu.gd_large_lds_bytes(2592, 7776, False) == 8 * 7776 + 4 * 770 == 65288
+    assert lu.gd_large_lds_bytes(2592, 7776, True) == 65288 + 3072 == 68360
     # the 1008 x 8991 hyperedge model
-    assert gl.gd_large_lds_words(1008, 8991) == 40 + 3 * 32 + 2 * 281 == 698
-    assert gl.gd_large_lds_bytes(1008, 8991, False) == 8 * 8991 + 4 * 698 == 74720
-    assert gl.gd_large_lds_bytes(1008, 8991, True) == 77792
+    assert lu.gd_large_lds_words(1008, 8991) == 40 + 3 * 32 + 2 * 281 == 698
+    assert lu.gd_large_lds_bytes(1008, 8991, False) == 8 * 8991 + 4 * 698 == 74720
+    assert lu.gd_large_lds_bytes(1008, 8991, True) == 77792
     for m, n in ((2592, 7776), (1008, 8991)):
         for tables in (False, True):
-            assert gl.gd_large_lds_bytes(m, n, tables) <= ru.LDS_LIMIT // 2        # (two workgroups per CU fit)
+            assert lu.gd_large_lds_bytes(m, n, tables) <= ru.LDS_LIMIT // 2        # (two workgroups per CU fit)
     # (their LDS builds are far beyond: 9 and 3 entries per column at the least)
     assert ru.gd_lds_bytes(2592, 7776, 9 * 2592, False) > ru.LDS_LIMIT < ru.gd_lds_bytes(1008, 8991, 3 * 8991, False)
 
 
 @pytest.mark.parametrize("tables,T", [(False, 41), (True, 40)], ids=["min_sum", "sum_product"])
 def test_first_round_count_past_the_lds_build(tables, T):
-    assert gl.first_rounds_beyond_the_lds_build(tables) == T
+    assert lu.gd_first_rounds_beyond_the_lds_build(tables) == T
     sh, before = ru.ph_shape(T), ru.ph_shape(T - 1)
     assert ru.gd_lds_bytes(before.m, before.n, before.E, tables) <= ru.LDS_LIMIT < ru.gd_lds_bytes(sh.m, sh.n, sh.E, tables)
     want = {False: (1476, 4428, 11772, 166304, 37264), True: (1440, 4320, 11484, 165304, 39416)}[tables]
-    assert (sh.m, sh.n, sh.E, ru.gd_lds_bytes(sh.m, sh.n, sh.E, tables), gl.gd_large_lds_bytes(sh.m, sh.n, tables)) == want
-    assert gl.gd_large_lds_bytes(sh.m, sh.n, tables) < ru.LDS_DEFAULT          # the large build fits, with room
+    assert (sh.m, sh.n, sh.E, ru.gd_lds_bytes(sh.m, sh.n, sh.E, tables), lu.gd_large_lds_bytes(sh.m, sh.n, tables)) == want
+    assert lu.gd_large_lds_bytes(sh.m, sh.n, tables) < ru.LDS_DEFAULT          # the large build fits, with room
 
 
 def test_upper_limit_of_the_large_build():
     # one check: 8 n + n / 4 bytes + 44 words (+ the tables)
-    n = gl.first_n_beyond_the_limit(1, False)
-    assert n == 19839 and gl.gd_large_lds_bytes(1, n - 1, False) == ru.LDS_LIMIT < gl.gd_large_lds_bytes(1, n, False) == 163848
-    n = gl.first_n_beyond_the_limit(1, True)
-    assert n == 19466 and gl.gd_large_lds_bytes(1, n - 1, True) == ru.LDS_LIMIT < gl.gd_large_lds_bytes(1, n, True) == 163848
-    assert gl.first_n_beyond_the_limit(2592, False) < 19839
+    n = lu.first_n_beyond_the_limit(lambda n: lu.gd_large_lds_bytes(1, n, False))
+    assert n == 19839 and lu.gd_large_lds_bytes(1, n - 1, False) == ru.LDS_LIMIT < lu.gd_large_lds_bytes(1, n, False) == 163848
+    n = lu.first_n_beyond_the_limit(lambda n: lu.gd_large_lds_bytes(1, n, True))
+    assert n == 19466 and lu.gd_large_lds_bytes(1, n - 1, True) == ru.LDS_LIMIT < lu.gd_large_lds_bytes(1, n, True) == 163848
+    assert lu.first_n_beyond_the_limit(lambda n: lu.gd_large_lds_bytes(2592, n, False)) < 19839
 
 
 def test_large_grid_of_the_41_round_matrix():
@@ -75,9 +75,9 @@ def test_large_grid_of_the_41_round_matrix():
     sh.work = ru.pad64(72 * 41) + ru.pad64(36 * 40) + ru.pad64(36)      # var_items: columns of weight 3, 2 and 1
     assert sh.work == 4544 and ru.gd_threads(sh) == 512
     # 8 wavefronts per workgroup: three of them in min-sum's 24 wavefronts, two in sum-product's 16
-    assert gl.gd_large_grid(sh, 8, 256, False) == 8 and gl.gd_large_grid(sh, 1 << 30, 256, False) == 3 * 256
-    assert gl.gd_large_grid(sh, 1 << 30, 256, True) == 2 * 256
-    assert gl.gd_large_grid(sh, 1 << 30, 256, True, blocks_per_cu=1) == 256
+    assert lu.gd_large_grid(sh, 8, 256, False) == 8 and lu.gd_large_grid(sh, 1 << 30, 256, False) == 3 * 256
+    assert lu.gd_large_grid(sh, 1 << 30, 256, True) == 2 * 256
+    assert lu.gd_large_grid(sh, 1 << 30, 256, True, blocks_per_cu=1) == 256
 
 
 def test_config_takes_large_and_its_dict_form():

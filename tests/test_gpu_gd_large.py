@@ -10,7 +10,7 @@ import functools
 import numpy as np
 import pytest
 
-import gd_large_util as gl
+import large_util as lu
 import gd_oracle as go
 import geometry_util as gu
 import record_kernel_util as ru
@@ -69,9 +69,9 @@ def launch(dec, syn_t, prior_t, B, n, what, stream):
 
 def expected_info(sh, B, num_cu, variant, mem, blocks=0):
     sp = variant == _lib.SUM_PRODUCT
-    if mem == gl.MEM_LARGE:
-        return dict(threads=ru.gd_threads(sh), grid=gl.gd_large_grid(sh, B, num_cu, sp, blocks),
-                    lds_bytes=gl.gd_large_lds_bytes(sh.m, sh.n, sp))
+    if mem == lu.MEM_LARGE:
+        return dict(threads=ru.gd_threads(sh), grid=lu.gd_large_grid(sh, B, num_cu, sp, blocks),
+                    lds_bytes=lu.gd_large_lds_bytes(sh.m, sh.n, sp))
     return dict(threads=ru.gd_threads(sh), grid=ru.gd_grid(sh, B, num_cu, sp, blocks),
                 lds_bytes=ru.gd_lds_bytes(sh.m, sh.n, sh.E, sp))
 
@@ -92,7 +92,7 @@ def test_forced_large_build_equals_statement_and_lds_build(case, variant, rounds
     B, n, sh = len(syn), H.shape[1], ru.Shape(H)
     syn_t, prior_t = gu.to_device(syn), gu.to_device(prior)
     got = {}
-    for mem in (gl.MEM_LARGE, gl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(H, mem)
         assert configure_raw(dec, cfg) == 0
         what = f"gd {case} variant {variant} max_rounds {rounds} mem {mem}"
@@ -101,7 +101,7 @@ def test_forced_large_build_equals_statement_and_lds_build(case, variant, rounds
         info = ru.info(dec)
         print(what, info, go.classes(want))
         assert info == expected_info(sh, B, dec.info("num_cu"), variant, mem)
-    ru.assert_same(got[gl.MEM_LARGE], got[gl.MEM_LDS], f"gd {case}: large build against LDS build")
+    ru.assert_same(got[lu.MEM_LARGE], got[lu.MEM_LDS], f"gd {case}: large build against LDS build")
 
 
 # ---- 2. one round past the LDS build's limit -----------------------------------------------------------------------------
@@ -111,7 +111,7 @@ NEAR_B, NEAR_P = 8, 0.01
 @functools.lru_cache(maxsize=None)
 def past_limit(variant):
     """The first round count past gd_lds_bytes for the variant: 8 records, rounds of 4 iterations, 12 decimations."""
-    T = gl.first_rounds_beyond_the_lds_build(variant == _lib.SUM_PRODUCT)
+    T = lu.gd_first_rounds_beyond_the_lds_build(variant == _lib.SUM_PRODUCT)
     c = ru.phenomenological(T, NEAR_P, 200 + T, NEAR_B)
     cfg = gd.GDConfig(4, 12, tg.LLR, variant, tg.ALPHA, 20.0)
     return c, cfg, statement(c.H, c.syn, c.prior, cfg)
@@ -121,7 +121,7 @@ def past_limit(variant):
 def test_one_round_past_the_limit(variant):
     c, cfg, want = past_limit(variant)
     sh, sp = c.shape, variant == _lib.SUM_PRODUCT
-    large_lds = gl.gd_large_lds_bytes(sh.m, sh.n, sp)
+    large_lds = lu.gd_large_lds_bytes(sh.m, sh.n, sp)
     assert ru.gd_lds_bytes(sh.m, sh.n, sh.E, sp) > ru.LDS_LIMIT > large_lds
     syn_t, prior_t = gu.to_device(c.syn), gu.to_device(c.prior)
     lib = _lib.load()
@@ -147,7 +147,7 @@ def test_one_round_past_the_limit(variant):
     small = launch(dec, syn_t, prior_t, 3, c.n, what + ", B = 3", gu.stream_ptr())
     ru.assert_same(small, ru.gd_want(want, slice(0, 3)), what + ", B = 3")
     # the option set back after the configuration: the launch checks again, with today's message
-    dec.set_option(_lib.OPT_GD_MEM, gl.MEM_LDS)
+    dec.set_option(_lib.OPT_GD_MEM, lu.MEM_LDS)
     with pytest.raises(_lib.QbpError) as e:
         ru.gd_launch(dec, syn_t, prior_t, NEAR_B, out, gu.stream_ptr())
     msg = lib.qbp_last_error()
@@ -169,7 +169,7 @@ def test_automatic_choice_keeps_the_lds_build_where_it_fits(variant):
     dec.gd_configure(with_large(cfg, "auto"))
     got = launch(dec, gu.to_device(syn[:40]), gu.to_device(prior), 40, 72, "gd 72 auto", gu.stream_ptr())
     ru.assert_same(got, ru.gd_want(want, slice(0, 40)), "gd 72 auto")
-    assert ru.info(dec) == expected_info(sh, 40, dec.info("num_cu"), variant, gl.MEM_LDS)
+    assert ru.info(dec) == expected_info(sh, 40, dec.info("num_cu"), variant, lu.MEM_LDS)
 
 
 # ---- 3. more records than workgroups: a workgroup reuses its slice of the workspace ---------------------------------------
@@ -179,7 +179,7 @@ def test_work_counter_with_the_messages_in_the_workspace(variant):
     H, syn, prior, cfg, ref = batch_inputs(("72", 0.1, 1), variant, 6)
     _, _, _, cfg_other, ref_other = batch_inputs(("72", 0.1, 1), other, 6)
     sh, n = ru.Shape(H), H.shape[1]
-    dec = fresh(H, gl.MEM_LARGE)
+    dec = fresh(H, lu.MEM_LARGE)
     assert configure_raw(dec, cfg) == 0
     num_cu = dec.info("num_cu")
     B = 3 * 2 * num_cu + 37                   # three records and more per workgroup at one and at two workgroups per CU
@@ -192,7 +192,7 @@ def test_work_counter_with_the_messages_in_the_workspace(variant):
             ts.on_own_stream(lambda s: got.__setitem__(blocks, launch(dec, syn_t, prior_t, B, n, what, s)))
         info = ru.info(dec)
         print(what, info, go.classes(ref))
-        assert info == expected_info(sh, B, num_cu, variant, gl.MEM_LARGE, blocks) and B >= 3 * info["grid"]
+        assert info == expected_info(sh, B, num_cu, variant, lu.MEM_LARGE, blocks) and B >= 3 * info["grid"]
         assert info["grid"] == blocks * num_cu
         ru.assert_same(got[blocks], ru.gd_want(ref, idx), what)
     ru.assert_same(got[1], got[2], "gd large: one against two workgroups per CU")
@@ -200,7 +200,7 @@ def test_work_counter_with_the_messages_in_the_workspace(variant):
     assert configure_raw(dec, cfg_other) == 0
     what = f"gd large variant {other} after {variant}"
     second = launch(dec, syn_t, prior_t, B, n, what, gu.stream_ptr())
-    assert ru.info(dec) == expected_info(sh, B, num_cu, other, gl.MEM_LARGE)
+    assert ru.info(dec) == expected_info(sh, B, num_cu, other, lu.MEM_LARGE)
     ru.assert_same(second, ru.gd_want(ref_other, idx), what)
     # and the first one again
     assert configure_raw(dec, cfg) == 0
@@ -223,13 +223,13 @@ def test_tied_posteriors_go_to_the_lowest_index(variant):
     assert tied >= 8
     syn_t, prior_t = gu.to_device(syn), gu.to_device(prior)
     got = {}
-    for mem in (gl.MEM_LARGE, gl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(H, mem)
         assert configure_raw(dec, cfg) == 0
         got[mem] = launch(dec, syn_t, prior_t, len(syn), 72, f"gd ties mem {mem}", gu.stream_ptr())
         assert np.array_equal(got[mem][4], want["rounds"]) and np.array_equal(got[mem][0], want["hard"])
         ru.assert_same(got[mem], ru.gd_want(want), f"gd ties mem {mem}")
-    ru.assert_same(got[gl.MEM_LARGE], got[gl.MEM_LDS], "gd ties: large build against LDS build")
+    ru.assert_same(got[lu.MEM_LARGE], got[lu.MEM_LDS], "gd ties: large build against LDS build")
 
 
 # ---- 5. the records build behind QBP_FLAG_GD ----------------------------------------------------------------------------
@@ -255,7 +255,7 @@ def test_mc_run_errors_equals_the_composition_and_the_lds_build(first):
     # the second stage's variant is the configuration's own: the other one than the first stage's, both get covered
     cfg = tg.config(_lib.SUM_PRODUCT if first == "min_sum" else _lib.MIN_SUM, 6)
     got = {}
-    for mem in (gl.MEM_LARGE, gl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(H, mem)
         assert configure_raw(dec, cfg) == 0
         variant, layered = first_stage(dec, first)
@@ -266,10 +266,10 @@ def test_mc_run_errors_equals_the_composition_and_the_lds_build(first):
         parts = dec.mc_run_errors(L, d, errors[:150], prior, **kw) + dec.mc_run_errors(L, d, errors[150:], prior, **kw)
         assert np.array_equal(parts, got[mem])
     want, failures = tg.compose(dec, H, L, d, errors, prior, cfg, variant, layered)
-    print(first, dict(zip(_lib.COUNTER_NAMES, got[gl.MEM_LARGE].tolist())), "failures", failures)
+    print(first, dict(zip(_lib.COUNTER_NAMES, got[lu.MEM_LARGE].tolist())), "failures", failures)
     assert failures >= 8 and want[6] == failures and want[0] == len(errors)
-    assert np.array_equal(got[gl.MEM_LARGE], want)
-    assert np.array_equal(got[gl.MEM_LARGE], got[gl.MEM_LDS])
+    assert np.array_equal(got[lu.MEM_LARGE], want)
+    assert np.array_equal(got[lu.MEM_LARGE], got[lu.MEM_LDS])
 
 
 DEM_TRIALS, DEM_SEED, DEM_RATE = 256, 9, 5.0
@@ -282,7 +282,7 @@ def test_mc_run_probs_on_the_detector_error_model(first):
     probs = np.minimum(0.5, c.probs * DEM_RATE)
     cfg = tg.config(_lib.MIN_SUM if first == "sum_product" else _lib.SUM_PRODUCT, 6)
     got = {}
-    for mem in (gl.MEM_LARGE, gl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(c.H, mem)
         assert configure_raw(dec, cfg) == 0
         variant, layered = first_stage(dec, first)
@@ -294,10 +294,10 @@ def test_mc_run_probs_on_the_detector_error_model(first):
         assert np.array_equal(parts, got[mem])
     errors = dec.mc_sample_errors_probs(probs, 0, DEM_TRIALS, seed=DEM_SEED)
     want, failures = tg.compose(dec, c.H, L, 0, errors, c.prior, cfg, variant, layered)
-    print(first, dict(zip(_lib.COUNTER_NAMES, got[gl.MEM_LARGE].tolist())), "failures", failures)
-    assert failures >= 8 and got[gl.MEM_LARGE][0] == DEM_TRIALS and got[gl.MEM_LARGE][6] == failures
-    assert np.array_equal(got[gl.MEM_LARGE], want)
-    assert np.array_equal(got[gl.MEM_LARGE], got[gl.MEM_LDS])
+    print(first, dict(zip(_lib.COUNTER_NAMES, got[lu.MEM_LARGE].tolist())), "failures", failures)
+    assert failures >= 8 and got[lu.MEM_LARGE][0] == DEM_TRIALS and got[lu.MEM_LARGE][6] == failures
+    assert np.array_equal(got[lu.MEM_LARGE], want)
+    assert np.array_equal(got[lu.MEM_LARGE], got[lu.MEM_LDS])
 
 
 def test_run_dem_takes_large():
@@ -313,7 +313,7 @@ def test_run_dem_takes_large():
     dec.gd_configure(with_large(cfg, True))
     direct = dec.mc_run_probs(np.ascontiguousarray(c.L, np.uint8), 0, probs, c.prior, 0, DEM_TRIALS, flags=_lib.FLAG_GD, **kw)
     print(dict(zip(_lib.COUNTER_NAMES, got.tolist())), ru.info(dec))
-    assert dec.info("lds_bytes") == gl.gd_large_lds_bytes(c.shape.m, c.shape.n, False)
+    assert dec.info("lds_bytes") == lu.gd_large_lds_bytes(c.shape.m, c.shape.n, False)
     assert got[0] == DEM_TRIALS and got[6] >= 8
     assert np.array_equal(got, direct) and np.array_equal(got, lds)
 
@@ -327,12 +327,12 @@ def test_mc_past_the_limit_is_refused_without_the_option_and_runs_with_it():
     dec.gd_configure(with_large(cfg, True))
     kw = dict(max_iter=tg.MC_ITERS, alpha=tg.ALPHA, flags=_lib.FLAG_GD)
     got = dec.mc_run_errors(L, 6, errors, c.prior, **kw)
-    assert dec.info("lds_bytes") == gl.gd_large_lds_bytes(c.shape.m, c.shape.n, False)
+    assert dec.info("lds_bytes") == lu.gd_large_lds_bytes(c.shape.m, c.shape.n, False)
     want, failures = tg.compose(dec, c.H, L, 6, errors, c.prior, cfg, _lib.SUM_PRODUCT, False)
     print(dict(zip(_lib.COUNTER_NAMES, got.tolist())), "failures", failures)
     assert failures >= 8 and got[6] == failures and np.array_equal(got, want)
     # without the option the Monte-Carlo call is refused before any GPU work
-    dec.set_option(_lib.OPT_GD_MEM, gl.MEM_LDS)
+    dec.set_option(_lib.OPT_GD_MEM, lu.MEM_LDS)
     with pytest.raises(_lib.QbpError) as e:
         dec.mc_run_errors(L, 6, errors, c.prior, **kw)
     assert e.value.code == _lib.E_UNSUPPORTED and b"160 KiB" in _lib.load().qbp_last_error()
@@ -349,7 +349,7 @@ def one_check(n):
 def test_upper_refusal_and_option_range(variant):
     lib = _lib.load()
     sp = variant == _lib.SUM_PRODUCT
-    n = gl.first_n_beyond_the_limit(1, sp)
+    n = lu.first_n_beyond_the_limit(lambda n: lu.gd_large_lds_bytes(1, n, sp))
     assert n == (19466 if sp else 19839)
     dec = fresh(one_check(n))
     out = ru.RecordOutputs(2, n, EXTRA)
@@ -359,7 +359,7 @@ def test_upper_refusal_and_option_range(variant):
             dec.gd_configure(gd.GDConfig(4, 2, tg.LLR, variant, large=large))
         msg = lib.qbp_last_error()
         assert e.value.code == _lib.E_UNSUPPORTED
-        assert b"global memory" in msg and str(gl.gd_large_lds_bytes(1, n, sp)).encode() in msg and b"160 KiB" in msg
+        assert b"global memory" in msg and str(lu.gd_large_lds_bytes(1, n, sp)).encode() in msg and b"160 KiB" in msg
         with pytest.raises(_lib.QbpError) as e:             # nothing was configured: no launch
             ru.gd_launch(dec, syn_t, prior_t, 2, out, gu.stream_ptr())
         assert e.value.code == _lib.E_INVALID and out.untouched()

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import geometry_util as gu
-import layered_large_util as ll
+import large_util as lu
 import layered_oracle as lo
 import record_kernel_util as ru
 import test_gpu_layered as tl
@@ -60,9 +60,9 @@ def batch_statement(name, kind, variant, alpha, max_iter):
 
 
 def expected_info(sh, width, B, tables, slots, large, num_cu, blocks=0):
-    S = ll.layered_slots(sh, width, B, tables, slots, large)
-    return S, dict(threads=ru.LAYERED_THREADS, grid=ll.layered_grid(sh, S, B, num_cu, tables, large, blocks),
-                   lds_bytes=ll.lds_bytes(sh, S, tables, large))
+    S = lu.layered_slots(sh, width, B, tables, slots, large)
+    return S, dict(threads=ru.LAYERED_THREADS, grid=lu.layered_grid(sh, S, B, num_cu, tables, large, blocks),
+                   lds_bytes=lu.layered_build_lds(sh, S, tables, large))
 
 
 # ---- 1. the forced large build against the statement and against the LDS build ------------------------------------------
@@ -80,10 +80,10 @@ def test_forced_large_build_equals_statement_and_lds_build(name, kind):
     width = max(ru.level_widths(H, order))
     syn_t, prior_t = gu.to_device(syn), gu.to_device(prior)
     out = gu.Outputs(B, n)
-    decs = {mem: fresh(H, mem) for mem in (ll.MEM_LARGE, ll.MEM_LDS)}
+    decs = {mem: fresh(H, mem) for mem in (lu.MEM_LARGE, lu.MEM_LDS)}
     for dec in decs.values():
         assert configure_raw(dec, order) == 0
-    num_cu = decs[ll.MEM_LDS].info("num_cu")
+    num_cu = decs[lu.MEM_LDS].info("num_cu")
     for variant, alpha in VARIANTS:
         tables = variant == _lib.SUM_PRODUCT
         for max_iter in ITERS:
@@ -97,16 +97,16 @@ def test_forced_large_build_equals_statement_and_lds_build(name, kind):
                                              alpha=alpha, flags=LAYERED)
                     gu.assert_same(got[mem], want, what)
                     assert dec.info("last_kernel") == 4
-                    S, info = expected_info(sh, width, B, tables, slots, mem == ll.MEM_LARGE, num_cu)
+                    S, info = expected_info(sh, width, B, tables, slots, mem == lu.MEM_LARGE, num_cu)
                     assert ru.info(dec) == info, (what, S, ru.info(dec), info)
-                gu.assert_same(got[ll.MEM_LARGE], got[ll.MEM_LDS], f"{name} {kind}: large build against LDS build")
-    print(name, kind, "widest level", width, ru.info(decs[ll.MEM_LARGE]), ru.info(decs[ll.MEM_LDS]))
+                gu.assert_same(got[lu.MEM_LARGE], got[lu.MEM_LDS], f"{name} {kind}: large build against LDS build")
+    print(name, kind, "widest level", width, ru.info(decs[lu.MEM_LARGE]), ru.info(decs[lu.MEM_LDS]))
 
 
 def test_automatic_choice_keeps_the_lds_build_where_it_fits():
     H, syn, prior = batch_inputs("72")
     sh = ru.Shape(H)
-    assert not ll.auto_is_large(sh)
+    assert not lu.layered_auto_is_large(sh)
     dec = fresh(H)
     dec.layered_configure(None, large=True)
     out = gu.Outputs(40, 72)
@@ -149,7 +149,7 @@ def past_launch(dec, syn_t, prior_t, B, out, variant, alpha, what):
 def test_one_round_past_the_limit():
     c = past_limit()
     sh = c.shape
-    assert ru.layered_lds_bytes(sh.m, sh.n, sh.E, 1, True) > ru.LDS_LIMIT > ll.layered_large_lds_bytes(sh.m, sh.n, 1, True)
+    assert ru.layered_lds_bytes(sh.m, sh.n, sh.E, 1, True) > ru.LDS_LIMIT > lu.layered_large_lds_bytes(sh.m, sh.n, 1, True)
     widths = {k: ru.level_widths(c.H, past_order(k)) for k in KINDS}
     print({k: (len(w), max(w)) for k, w in widths.items()})
     assert widths["default"] == [360] * 4 and len(widths["random"]) == 28      # (360 > 256 threads: two passes a level)
@@ -191,14 +191,14 @@ def test_one_round_past_the_limit():
             gu.assert_same(small, tuple(x[:3] for x in want), what + ", B = 3")
     # the option set back after the configuration: every launch checks again, with today's message
     variant, alpha = VARIANTS[1]
-    dec.set_option(_lib.OPT_LAYERED_MEM, ll.MEM_LDS)
+    dec.set_option(_lib.OPT_LAYERED_MEM, lu.MEM_LDS)
     with pytest.raises(_lib.QbpError) as e:
         gu.launch(dec, syn_t, prior_t, PAST_B, out, max_iter=PAST_ITERS, variant=variant, alpha=alpha, flags=LAYERED)
     msg = _lib.load().qbp_last_error()
     assert e.value.code == _lib.E_UNSUPPORTED and b"160 KiB" in msg and b"the prior of a record in LDS" in msg
     gu.torch().cuda.synchronize()
     assert all(out.poisoned(k, 0) for k in gu.NAMES)
-    dec.set_option(_lib.OPT_LAYERED_MEM, ll.MEM_AUTO)
+    dec.set_option(_lib.OPT_LAYERED_MEM, lu.MEM_AUTO)
     again = past_launch(dec, syn_t, prior_t, PAST_B, out, variant, alpha, "layered T = 40 again")
     gu.assert_same(again, past_statement("random", variant, alpha), "layered T = 40 again")
 
@@ -209,7 +209,7 @@ def test_more_records_than_slots(slots):
     H, syn, prior = batch_inputs("72")
     sh, n, base = ru.Shape(H), H.shape[1], len(syn)
     width = max(ru.level_widths(H, lo.order_of(H, "default")))
-    dec = fresh(H, ll.MEM_LARGE)
+    dec = fresh(H, lu.MEM_LARGE)
     assert configure_raw(dec, None) == 0
     prior_t = gu.to_device(prior)
     num_cu = dec.info("num_cu")
@@ -246,7 +246,7 @@ def test_force_full_returns_the_early_exit_bits(name):
     B, n = len(syn), H.shape[1]
     syn_t, prior_t = gu.to_device(syn), gu.to_device(prior)
     out = gu.Outputs(B, n)
-    decs = {mem: fresh(H, mem) for mem in (ll.MEM_LARGE, ll.MEM_LDS)}
+    decs = {mem: fresh(H, mem) for mem in (lu.MEM_LARGE, lu.MEM_LDS)}
     for dec in decs.values():
         assert configure_raw(dec, None) == 0
     for variant, alpha in VARIANTS:
@@ -258,7 +258,7 @@ def test_force_full_returns_the_early_exit_bits(name):
                 got[mem] = gu.decode(dec, syn_t, prior_t, B, out, what, max_iter=max_iter, variant=variant, alpha=alpha,
                                      flags=LAYERED | _lib.FLAG_FORCE_FULL)
                 gu.assert_same(got[mem], want, what)
-            gu.assert_same(got[ll.MEM_LARGE], got[ll.MEM_LDS], f"{name} forced: large build against LDS build")
+            gu.assert_same(got[lu.MEM_LARGE], got[lu.MEM_LDS], f"{name} forced: large build against LDS build")
 
 
 # ---- 5. the Monte-Carlo build ------------------------------------------------------------------------------------------------
@@ -284,7 +284,7 @@ def mc_statement(name, variant, alpha):
 
 
 def mc_decoders(H):
-    decs = {mem: fresh(H, mem) for mem in (ll.MEM_LARGE, ll.MEM_LDS)}
+    decs = {mem: fresh(H, mem) for mem in (lu.MEM_LARGE, lu.MEM_LDS)}
     for dec in decs.values():
         assert configure_raw(dec, None) == 0
     return decs
@@ -304,16 +304,16 @@ def test_mc_run_errors_equals_statement_and_the_lds_build(name, variant, alpha):
     for mem, dec in mc_decoders(H).items():
         got[mem] = dec.mc_run_errors(L, d, errors, prior, **kw)
         assert dec.info("last_kernel") == 4
-        info = expected_info(sh, width, len(errors), variant == _lib.SUM_PRODUCT, 0, mem == ll.MEM_LARGE, dec.info("num_cu"))[1]
+        info = expected_info(sh, width, len(errors), variant == _lib.SUM_PRODUCT, 0, mem == lu.MEM_LARGE, dec.info("num_cu"))[1]
         assert ru.info(dec) == info
         assert np.array_equal(dec.mc_run_errors(L, d, errors[:31], prior, **kw)
                               + dec.mc_run_errors(L, d, errors[31:], prior, **kw), got[mem])
         with ts.layered_slots_option(dec, 1):
             assert np.array_equal(dec.mc_run_errors(L, d, errors, prior, **kw), got[mem])
-    print(name, dict(zip(_lib.COUNTER_NAMES, got[ll.MEM_LARGE].tolist())), "failures", failures)
+    print(name, dict(zip(_lib.COUNTER_NAMES, got[lu.MEM_LARGE].tolist())), "failures", failures)
     assert 8 <= failures < len(errors)
-    assert np.array_equal(got[ll.MEM_LARGE], want)
-    assert np.array_equal(got[ll.MEM_LARGE], got[ll.MEM_LDS])
+    assert np.array_equal(got[lu.MEM_LARGE], want)
+    assert np.array_equal(got[lu.MEM_LARGE], got[lu.MEM_LDS])
 
 
 @pytest.mark.parametrize("stage", ["osd0", "relay"])
@@ -328,7 +328,7 @@ def test_second_stages_act_on_the_large_builds_failure_records(name, stage):
     assert len(f) >= 8
     decs = mc_decoders(H)
     det = hard.copy()
-    helper = decs[ll.MEM_LDS]
+    helper = decs[lu.MEM_LDS]
     if stage == "relay":
         cfg = tl.relay_config(H.shape[1])
         for dec in decs.values():
@@ -345,10 +345,10 @@ def test_second_stages_act_on_the_large_builds_failure_records(name, stage):
     want[10] = invalid
     got = {mem: dec.mc_run_errors(L, d, errors, prior, max_iter=MC_ITERS, variant=variant, alpha=alpha, flags=flags)
            for mem, dec in decs.items()}
-    print(name, stage, dict(zip(_lib.COUNTER_NAMES, got[ll.MEM_LARGE].tolist())))
-    assert got[ll.MEM_LARGE][6] == len(f)
-    assert np.array_equal(got[ll.MEM_LARGE], want)
-    assert np.array_equal(got[ll.MEM_LARGE], got[ll.MEM_LDS])
+    print(name, stage, dict(zip(_lib.COUNTER_NAMES, got[lu.MEM_LARGE].tolist())))
+    assert got[lu.MEM_LARGE][6] == len(f)
+    assert np.array_equal(got[lu.MEM_LARGE], want)
+    assert np.array_equal(got[lu.MEM_LARGE], got[lu.MEM_LDS])
 
 
 @pytest.mark.parametrize("name", ["72", "dem_synth"])
@@ -359,7 +359,7 @@ def test_mc_run_weight_does_not_depend_on_the_build_the_split_or_the_chunk(name)
     variant, alpha = VARIANTS[1]
     kw = dict(seed=9, max_iter=MC_ITERS, variant=variant, alpha=alpha, flags=LAYERED)
     decs = mc_decoders(H)
-    errors = decs[ll.MEM_LDS].mc_sample_errors_weight(w, 5, T, seed=9)
+    errors = decs[lu.MEM_LDS].mc_sample_errors_weight(w, 5, T, seed=9)
     syn = gu.syndromes_of(H, errors)
     hard, conv, iters, _ = lo.layered_decode_batch(H, syn, prior, MC_ITERS, variant, alpha, 20.0, None, "level")
     want = oracle.classify_trials(H, L, d, errors, syn, hard, conv, iters)
@@ -381,14 +381,14 @@ def one_check(n):
 
 def test_upper_refusal_and_option_range():
     lib = _lib.load()
-    limit = ll.n_limit(1)
+    limit = lu.layered_n_limit(1)
     n = limit + 1
-    for mem in (ll.MEM_AUTO, ll.MEM_LARGE):
+    for mem in (lu.MEM_AUTO, lu.MEM_LARGE):
         dec = fresh(one_check(n), mem)
         rc = configure_raw(dec, None)
         msg = lib.qbp_last_error()
         assert rc == _lib.E_UNSUPPORTED
-        assert b"global memory" in msg and str(ll.layered_large_lds_bytes(1, n, 1, True)).encode() in msg
+        assert b"global memory" in msg and str(lu.layered_large_lds_bytes(1, n, 1, True)).encode() in msg
         assert b"160 KiB" in msg and f"n <= {limit}".encode() in msg
     out = gu.Outputs(2, n)
     out.poison()
@@ -400,7 +400,7 @@ def test_upper_refusal_and_option_range():
     # the widest matrix the option accepts configures; without the option it is refused as ever
     dec = fresh(one_check(limit))
     dec.layered_configure(None, large=True)
-    dec.set_option(_lib.OPT_LAYERED_MEM, ll.MEM_LDS)
+    dec.set_option(_lib.OPT_LAYERED_MEM, lu.MEM_LDS)
     counters = np.full(12, 7, np.int64)
     Lx = np.zeros((1, limit), np.uint8)
     Lx[0, 0] = 1
@@ -439,7 +439,7 @@ def test_run_dem_takes_large():
     kw = dict(prior=c.prior, seed=9, max_iter=MC_ITERS, variant=_lib.MIN_SUM, alpha=0.8, osd=True)
     plain = mc.run_dem(c.H, c.L, probs, 2000, layered=True, **kw)
     dec = bp.decoder_for(c.H, device=bp.DEVICE)
-    assert not ll.auto_is_large(c.shape)
+    assert not lu.layered_auto_is_large(c.shape)
     large = mc.run_dem(c.H, c.L, probs, 2000, layered="large", **kw)
     print(dict(zip(_lib.COUNTER_NAMES, large.tolist())))
     assert large[0] == 2000 and large[6] >= 64

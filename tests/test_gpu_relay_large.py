@@ -11,7 +11,7 @@ import pytest
 
 import geometry_util as gu
 import record_kernel_util as ru
-import relay_large_util as rl
+import large_util as lu
 import relay_oracle as ro
 import test_gpu_record_kernel_sizes as ts
 import test_gpu_relay as tr
@@ -73,7 +73,7 @@ def test_forced_large_build_equals_statement_and_lds_build(case):
     B, n, sh = len(syn), H.shape[1], ru.Shape(H)
     syn_t, prior_t = gu.to_device(syn), gu.to_device(prior)
     got = {}
-    for mem in (rl.MEM_LARGE, rl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(H, mem)
         assert configure_raw(dec, cfg) == 0
         what = f"relay {case} mem {mem}"
@@ -82,13 +82,13 @@ def test_forced_large_build_equals_statement_and_lds_build(case):
         info = ru.info(dec)
         print(what, info, ro.classes(want))
         num_cu = dec.info("num_cu")
-        if mem == rl.MEM_LARGE:
-            assert info == dict(threads=ru.relay_threads(sh), grid=rl.relay_large_grid(sh, B, num_cu),
-                                lds_bytes=rl.relay_large_lds_bytes(sh.m, sh.n))
+        if mem == lu.MEM_LARGE:
+            assert info == dict(threads=ru.relay_threads(sh), grid=lu.relay_large_grid(sh, B, num_cu),
+                                lds_bytes=lu.relay_large_lds_bytes(sh.m, sh.n))
         else:
             assert info == dict(threads=ru.relay_threads(sh), grid=ru.relay_grid(sh, B, num_cu),
                                 lds_bytes=ru.relay_lds_bytes(sh.m, sh.n, sh.E))
-    ru.assert_same(got[rl.MEM_LARGE], got[rl.MEM_LDS], f"relay {case}: large build against LDS build")
+    ru.assert_same(got[lu.MEM_LARGE], got[lu.MEM_LDS], f"relay {case}: large build against LDS build")
 
 
 # ---- 2. one round past the LDS build's limit -----------------------------------------------------------------------------
@@ -105,7 +105,7 @@ def past_limit():
 def test_one_round_past_the_limit():
     c, cfg, want = past_limit()
     sh = c.shape
-    assert ru.relay_lds_bytes(sh.m, sh.n, sh.E) > ru.LDS_LIMIT > rl.relay_large_lds_bytes(sh.m, sh.n)
+    assert ru.relay_lds_bytes(sh.m, sh.n, sh.E) > ru.LDS_LIMIT > lu.relay_large_lds_bytes(sh.m, sh.n)
     syn_t, prior_t = gu.to_device(c.syn), gu.to_device(c.prior)
     # large=False: today's refusal, and no output is touched
     dec = fresh(c.H)
@@ -122,19 +122,19 @@ def test_one_round_past_the_limit():
     ru.assert_same(got, ru.relay_want(want), "relay T = 34")
     info = ru.info(dec)
     print(c.H.shape, info, ro.classes(want))
-    assert info["lds_bytes"] == rl.relay_large_lds_bytes(sh.m, sh.n) and info["grid"] == NEAR_B == 8
+    assert info["lds_bytes"] == lu.relay_large_lds_bytes(sh.m, sh.n) and info["grid"] == NEAR_B == 8
     assert info["threads"] == ru.relay_threads(sh)
     # a second, smaller launch on the same handle
     small = launch(dec, syn_t, prior_t, 3, c.n, "relay T = 34, B = 3", gu.stream_ptr())
     ru.assert_same(small, ru.relay_want(want, slice(0, 3)), "relay T = 34, B = 3")
     # the option set back after the configuration: the launch checks again, with today's message
-    dec.set_option(_lib.OPT_RELAY_MEM, rl.MEM_LDS)
+    dec.set_option(_lib.OPT_RELAY_MEM, lu.MEM_LDS)
     with pytest.raises(_lib.QbpError) as e:
         ru.relay_launch(dec, syn_t, prior_t, NEAR_B, out, gu.stream_ptr())
     msg = _lib.load().qbp_last_error()
     assert e.value.code == _lib.E_UNSUPPORTED and b"160 KiB" in msg and b"three rows of n doubles in LDS" in msg
     assert out.untouched()
-    dec.set_option(_lib.OPT_RELAY_MEM, rl.MEM_AUTO)
+    dec.set_option(_lib.OPT_RELAY_MEM, lu.MEM_AUTO)
     again = launch(dec, syn_t, prior_t, NEAR_B, c.n, "relay T = 34 again", gu.stream_ptr())
     ru.assert_same(again, ru.relay_want(want), "relay T = 34 again")
 
@@ -153,16 +153,16 @@ def test_automatic_choice_keeps_the_lds_build_where_it_fits():
 def test_work_counter_with_the_messages_in_the_workspace():
     H, syn, prior, cfg, ref = ts.relay_small_ref("72", 0.1, 1)
     sh, n = ru.Shape(H), H.shape[1]
-    dec = fresh(H, rl.MEM_LARGE)
+    dec = fresh(H, lu.MEM_LARGE)
     assert configure_raw(dec, cfg) == 0
-    B = 2 * rl.relay_large_grid(sh, 1 << 30, dec.info("num_cu")) + 37
+    B = 2 * lu.relay_large_grid(sh, 1 << 30, dec.info("num_cu")) + 37
     idx = ts.spread(B, 256, 5)
     syn_t, prior_t = gu.to_device(syn[idx]), gu.to_device(prior)
     got = []
     ts.on_own_stream(lambda s: got.append(launch(dec, syn_t, prior_t, B, n, f"relay large B {B}", s)))
     info = ru.info(dec)
     print(info, "B", B, ro.classes(ref))
-    assert B == 2 * info["grid"] + 37 and info["lds_bytes"] == rl.relay_large_lds_bytes(sh.m, sh.n)
+    assert B == 2 * info["grid"] + 37 and info["lds_bytes"] == lu.relay_large_lds_bytes(sh.m, sh.n)
     ru.assert_same(got[0], ru.relay_want(ref, idx), f"relay large B {B}")
 
 
@@ -176,18 +176,18 @@ def test_mc_run_errors_equals_the_composition_and_the_lds_build(tag, first):
     cfg = tr.config(n, 4)
     kw = dict(max_iter=ts.MC_ITERS, variant=variant, alpha=tr.ALPHA, flags=_lib.FLAG_RELAY)
     got = {}
-    for mem in (rl.MEM_LARGE, rl.MEM_LDS):
+    for mem in (lu.MEM_LARGE, lu.MEM_LDS):
         dec = fresh(H, mem)
         assert configure_raw(dec, cfg) == 0
         got[mem] = dec.mc_run_errors(L, d, errors, prior, **kw)
         sh = ru.Shape(H)
-        assert dec.info("lds_bytes") == (rl.relay_large_lds_bytes(sh.m, sh.n, True) if mem == rl.MEM_LARGE
+        assert dec.info("lds_bytes") == (lu.relay_large_lds_bytes(sh.m, sh.n, True) if mem == lu.MEM_LARGE
                                          else ru.relay_lds_bytes(sh.m, sh.n, sh.E, True))
     want, failures = tr.compose(dec, H, L, d, errors, prior, cfg, variant)
-    print(tag, first, dict(zip(_lib.COUNTER_NAMES, got[rl.MEM_LARGE].tolist())), "failures", failures)
+    print(tag, first, dict(zip(_lib.COUNTER_NAMES, got[lu.MEM_LARGE].tolist())), "failures", failures)
     assert failures >= 64 and want[6] == failures and want[0] == len(errors)
-    assert np.array_equal(got[rl.MEM_LARGE], want)
-    assert np.array_equal(got[rl.MEM_LARGE], got[rl.MEM_LDS])
+    assert np.array_equal(got[lu.MEM_LARGE], want)
+    assert np.array_equal(got[lu.MEM_LARGE], got[lu.MEM_LDS])
 
 
 # ---- 5. the records build past the limit ---------------------------------------------------------------------------------
@@ -207,7 +207,7 @@ def test_mc_run_probs_past_the_limit():
     kw = dict(seed=MC_SEED, max_iter=ts.MC_ITERS, alpha=tr.ALPHA, flags=_lib.FLAG_RELAY)
     got = dec.mc_run_probs(L, 6, probs, prior, 0, MC_TRIALS, **kw)
     sh = c.shape
-    assert dec.info("lds_bytes") == rl.relay_large_lds_bytes(sh.m, sh.n, True)
+    assert dec.info("lds_bytes") == lu.relay_large_lds_bytes(sh.m, sh.n, True)
     errors = dec.mc_sample_errors_probs(probs, 0, MC_TRIALS, seed=MC_SEED)
     want, failures = tr.compose(dec, c.H, L, 6, errors, prior, cfg, _lib.SUM_PRODUCT)
     print(dict(zip(_lib.COUNTER_NAMES, got.tolist())), "failures", failures)
@@ -216,7 +216,7 @@ def test_mc_run_probs_past_the_limit():
     parts = dec.mc_run_probs(L, 6, probs, prior, 0, 77, **kw) + dec.mc_run_probs(L, 6, probs, prior, 77, MC_TRIALS, **kw)
     assert np.array_equal(parts, got)
     # without the option the Monte-Carlo call is refused before any GPU work
-    dec.set_option(_lib.OPT_RELAY_MEM, rl.MEM_LDS)
+    dec.set_option(_lib.OPT_RELAY_MEM, lu.MEM_LDS)
     with pytest.raises(_lib.QbpError) as e:
         dec.mc_run_probs(L, 6, probs, prior, 0, MC_TRIALS, **kw)
     assert e.value.code == _lib.E_UNSUPPORTED and b"160 KiB" in _lib.load().qbp_last_error()
@@ -232,14 +232,14 @@ def one_check(n):
 def test_upper_refusal_and_option_range():
     lib = _lib.load()
     # 1 x 20 475: the first width whose large build passes 160 KiB (8 n + 48 bytes)
-    n = rl.first_n_beyond_the_limit(1)
+    n = lu.first_n_beyond_the_limit(lambda n: lu.relay_large_lds_bytes(1, n))
     dec = fresh(one_check(n))
     cfg = relay.RelayConfig(np.zeros((1, n)), [3], large=True)
     with pytest.raises(_lib.QbpError) as e:
         dec.relay_configure(cfg)
     msg = lib.qbp_last_error()
     assert e.value.code == _lib.E_UNSUPPORTED
-    assert b"global memory" in msg and str(rl.relay_large_lds_bytes(1, n)).encode() in msg and b"160 KiB" in msg
+    assert b"global memory" in msg and str(lu.relay_large_lds_bytes(1, n)).encode() in msg and b"160 KiB" in msg
     out = ru.RecordOutputs(2, n, EXTRA)
     with pytest.raises(_lib.QbpError) as e:             # nothing was configured: no launch
         ru.relay_launch(dec, gu.to_device(np.zeros((2, 1), np.uint8)), gu.to_device(np.ones(n)), 2, out, gu.stream_ptr())
@@ -257,7 +257,7 @@ def test_upper_refusal_and_option_range():
                         _lib.FLAG_RELAY, counters.ctypes.data)
     msg = lib.qbp_last_error()
     assert rc == _lib.E_UNSUPPORTED and np.all(counters == 7)
-    assert b"global memory" in msg and str(rl.relay_large_lds_bytes(1, n, True)).encode() in msg
+    assert b"global memory" in msg and str(lu.relay_large_lds_bytes(1, n, True)).encode() in msg
     # the option's range
     for bad in (3, -1):
         with pytest.raises(_lib.QbpError) as e:

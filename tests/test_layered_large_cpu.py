@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-import layered_large_util as ll
+import large_util as lu
 import record_kernel_util as ru
 from qldpc_amd import _lib, layered, mc
 
@@ -19,7 +19,7 @@ def test_constant_equals_the_header():
     assert m and int(m.group(1)) == _lib.OPT_LAYERED_MEM == 17
     values = [int(v) for v in re.findall(r"\bQBP_OPT_[A-Z0-9_]+\s*=\s*(\d+)", header)]
     assert values.count(17) == 1
-    assert _lib.LAYERED_MEM == {False: ll.MEM_LDS, True: ll.MEM_AUTO}
+    assert _lib.LAYERED_MEM == {False: lu.MEM_LDS, True: lu.MEM_AUTO}
 
 
 def test_the_header_states_the_large_figure_as_restated():
@@ -34,38 +34,38 @@ def test_lds_figures_of_the_shapes_the_option_exists_for():
     # 40 rounds of the [[72,12,6]] phenomenological matrix: one round past the LDS build, far inside the large one
     sh = ru.ph_shape(40)
     assert (sh.m, sh.n, sh.E) == (1440, 4320, 11484)
-    assert ll.slot_words(1440) == 56
+    assert lu.layered_slot_words(1440) == 56
     assert ru.layered_lds_bytes(sh.m, sh.n, sh.E, 1, True) == tables + 8 * (11484 + 2 * 4320) + 4 * 88 > ru.LDS_LIMIT
-    assert ll.layered_large_lds_bytes(sh.m, sh.n, 1, True) == tables + 8 * 4320 + 4 * 88 < ru.LDS_DEFAULT
-    assert ll.auto_is_large(sh) and not ll.auto_is_large(ru.ph_shape(39))
+    assert lu.layered_large_lds_bytes(sh.m, sh.n, 1, True) == tables + 8 * 4320 + 4 * 88 < ru.LDS_DEFAULT
+    assert lu.layered_auto_is_large(sh) and not lu.layered_auto_is_large(ru.ph_shape(39))
     # [[288,12,18]], 18 rounds (every row of weight 8 but the first 144) and the 1008 x 8991 detector error model
     # (E is whatever it is: the large figure does not depend on it, and the LDS figure passes the limit with E = n)
     for m, n, E in ((2592, 7776, 8 * 2592 - 144), (1008, 8991, 8991)):
-        assert ru.layered_lds_bytes(m, n, E, 1, True) > ru.LDS_LIMIT > ll.layered_large_lds_bytes(m, n, 1, True)
+        assert ru.layered_lds_bytes(m, n, E, 1, True) > ru.LDS_LIMIT > lu.layered_large_lds_bytes(m, n, 1, True)
         assert ru.layered_lds_bytes(m, n, E, 1, False) > ru.LDS_LIMIT
-    assert ll.layered_large_lds_bytes(2592, 7776, 1, True) == tables + 8 * 7776 + 4 * (32 + 92)
-    assert ru.LDS_DEFAULT < ll.layered_large_lds_bytes(2592, 7776, 1, True) < 80 * 1024
+    assert lu.layered_large_lds_bytes(2592, 7776, 1, True) == tables + 8 * 7776 + 4 * (32 + 92)
+    assert ru.LDS_DEFAULT < lu.layered_large_lds_bytes(2592, 7776, 1, True) < 80 * 1024
     # where the large figure first passes 160 KiB
     for m in (1, 1008):
-        n = ll.n_limit(m)
-        assert ll.layered_large_lds_bytes(m, n, 1, True) <= ru.LDS_LIMIT < ll.layered_large_lds_bytes(m, n + 1, 1, True)
-    assert ll.n_limit(1) == (ru.LDS_LIMIT - tables - 4 * (32 + 12)) // 8 and 19500 < ll.n_limit(1008) < ll.n_limit(1) < 20500
+        n = lu.layered_n_limit(m)
+        assert lu.layered_large_lds_bytes(m, n, 1, True) <= ru.LDS_LIMIT < lu.layered_large_lds_bytes(m, n + 1, 1, True)
+    assert lu.layered_n_limit(1) == (ru.LDS_LIMIT - tables - 4 * (32 + 12)) // 8 and 19500 < lu.layered_n_limit(1008) < lu.layered_n_limit(1) < 20500
 
 
 def test_slots_and_grid_follow_the_build():
     # 2592 x 7776, widest level 648: one slot in either build; the large build is what fits
     sh = ru.Shape.__new__(ru.Shape)
     sh.m, sh.n, sh.E = 2592, 7776, 8 * 2592 - 144
-    assert ll.layered_slots(sh, 648, 1 << 20, True, 0, True) == 1
-    assert ll.layered_slots(sh, 648, 1 << 20, True, 2, True) == 2         # two slots: 2 x 62 KiB of V
-    assert ll.layered_slots(sh, 648, 1 << 20, True, 3, True) == 2         # a third does not fit 160 KiB
-    assert ll.layered_grid(sh, 1, 1 << 20, 256, True, True) == 2 * 256    # two workgroups' LDS per CU
+    assert lu.layered_slots(sh, 648, 1 << 20, True, 0, True) == 1
+    assert lu.layered_slots(sh, 648, 1 << 20, True, 2, True) == 2         # two slots: 2 x 62 KiB of V
+    assert lu.layered_slots(sh, 648, 1 << 20, True, 3, True) == 2         # a third does not fit 160 KiB
+    assert lu.layered_grid(sh, 1, 1 << 20, 256, True, True) == 2 * 256    # two workgroups' LDS per CU
     # [[72,12,6]], widest level 18 of the default order: the large build holds more slots under 80 KiB
     sh72 = ru.Shape.__new__(ru.Shape)
     sh72.m, sh72.n, sh72.E = 36, 72, 216
-    assert ll.layered_slots(sh72, 18, 1 << 20, False, 0, True) == ll.layered_slots(sh72, 18, 1 << 20, False, 0, False) == 14
-    assert ll.layered_slots(sh72, 1, 1 << 20, True, 0, False) == ru.layered_slots(sh72, 1, 1 << 20, True) == 32
-    assert ll.layered_grid(sh72, 3, 37, 256, False, True, 1) == 13 and ll.layered_grid(sh72, 3, 10 ** 6, 256, False, True, 1) == 256
+    assert lu.layered_slots(sh72, 18, 1 << 20, False, 0, True) == lu.layered_slots(sh72, 18, 1 << 20, False, 0, False) == 14
+    assert lu.layered_slots(sh72, 1, 1 << 20, True, 0, False) == ru.layered_slots(sh72, 1, 1 << 20, True) == 32
+    assert lu.layered_grid(sh72, 3, 37, 256, False, True, 1) == 13 and lu.layered_grid(sh72, 3, 10 ** 6, 256, False, True, 1) == 256
 
 
 class _Stub:
@@ -85,9 +85,9 @@ class _Stub:
 def test_layered_large_reaches_the_option_write():
     dec = _Stub()
     mc._configure_layered(dec, "large")
-    assert dec.writes == [(17, ll.MEM_AUTO)] and dec.orders == [None]
+    assert dec.writes == [(17, lu.MEM_AUTO)] and dec.orders == [None]
     mc._configure_layered(dec, True)
-    assert dec.writes[-1] == (17, ll.MEM_LDS) and dec.orders[-1] is None
+    assert dec.writes[-1] == (17, lu.MEM_LDS) and dec.orders[-1] is None
     order = np.array([2, 0, 1])
     before = list(dec.writes)
     mc._configure_layered(dec, order)

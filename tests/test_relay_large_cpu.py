@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import record_kernel_util as ru
-import relay_large_util as rl
+import large_util as lu
 from qldpc_amd import _lib, mc, relay
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +19,7 @@ def test_constant_equals_the_header():
     assert m and int(m.group(1)) == _lib.OPT_RELAY_MEM == 16
     values = [int(v) for v in re.findall(r"\bQBP_OPT_[A-Z0-9_]+\s*=\s*(\d+)", header)]
     assert values.count(16) == 1
-    assert _lib.RELAY_MEM == {False: rl.MEM_LDS, True: rl.MEM_AUTO, "force": rl.MEM_LARGE}
+    assert _lib.RELAY_MEM == {False: lu.MEM_LDS, True: lu.MEM_AUTO, "force": lu.MEM_LARGE}
 
 
 def test_the_header_states_the_large_figure_as_restated():
@@ -33,25 +33,25 @@ def test_lds_figures_of_the_three_shapes():
     sh = ru.ph_shape(34)
     assert (sh.m, sh.n, sh.E) == (1224, 3672, 9756)
     assert ru.relay_lds_bytes(sh.m, sh.n, sh.E) == 8 * (9756 + 3 * 3672) + 4 * 126 == 166680 > ru.LDS_LIMIT
-    assert rl.relay_large_lds_bytes(sh.m, sh.n) == 8 * 3672 + 4 * 126 == 29880 < ru.LDS_DEFAULT
+    assert lu.relay_large_lds_bytes(sh.m, sh.n) == 8 * 3672 + 4 * 126 == 29880 < ru.LDS_DEFAULT
     assert ru.relay_lds_bytes(*[getattr(ru.ph_shape(33), k) for k in "mnE"]) <= ru.LDS_LIMIT
     # [[288,12,18]], 18 rounds: the records build
-    assert rl.relay_lds_words(2592) == 252
-    assert rl.relay_large_lds_bytes(2592, 7776, True) == 8 * 7776 + 4 * 252 + 7776 == 70992
+    assert lu.relay_lds_words(2592) == 252
+    assert lu.relay_large_lds_bytes(2592, 7776, True) == 8 * 7776 + 4 * 252 + 7776 == 70992
     assert ru.LDS_DEFAULT < 70992 < ru.LDS_LIMIT
     # where the large figure first passes 160 KiB: one check, n = 20 475 (records build: 18 200)
-    n = rl.first_n_beyond_the_limit(1)
-    assert n == 20475 and rl.relay_large_lds_bytes(1, n) == 163848 and rl.relay_large_lds_bytes(1, n - 1) == ru.LDS_LIMIT
-    assert rl.first_n_beyond_the_limit(1, records=True) == 18200
+    n = lu.first_n_beyond_the_limit(lambda n: lu.relay_large_lds_bytes(1, n))
+    assert n == 20475 and lu.relay_large_lds_bytes(1, n) == 163848 and lu.relay_large_lds_bytes(1, n - 1) == ru.LDS_LIMIT
+    assert lu.first_n_beyond_the_limit(lambda n: lu.relay_large_lds_bytes(1, n, True)) == 18200
     # (1 x 20 000 fits the batch build and not the records build)
-    assert rl.relay_large_lds_bytes(1, 20000) == 160048 <= ru.LDS_LIMIT < rl.relay_large_lds_bytes(1, 20000, True) == 180048
+    assert lu.relay_large_lds_bytes(1, 20000) == 160048 <= ru.LDS_LIMIT < lu.relay_large_lds_bytes(1, 20000, True) == 180048
 
 
 def test_large_grid_of_the_34_round_matrix():
     sh = ru.ph_shape(34)
     sh.work = ru.pad64(72 * 34) + ru.pad64(36 * 33) + ru.pad64(36)      # var_items: columns of weight 3, 2 and 1
     assert sh.work == 3776 and ru.relay_threads(sh) == 960
-    assert rl.relay_large_grid(sh, 8, 256) == 8 and rl.relay_large_grid(sh, 1 << 30, 256) == 256
+    assert lu.relay_large_grid(sh, 8, 256) == 8 and lu.relay_large_grid(sh, 1 << 30, 256) == 256
 
 
 def test_config_round_trips_large_through_its_dict_form():
