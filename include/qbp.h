@@ -559,7 +559,25 @@ int qbp_gd_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const 
  * qbp_lsd_configure stores bits_per_step = g >= 0 in the handle (QBP_E_INVALID otherwise).  QBP_E_UNSUPPORTED: a matrix
  * of more than 2048 rows or 65535 columns, or whose per-record state -- the bit-packed rows of [H | syndrome] and the
  * cluster tables -- exceeds the 160 KiB of LDS of one workgroup (the codes of codes/ and 432 x 1296 fit; 864 x 2592
- * does not).
+ * does not), unless QBP_OPT_LSD_MEM allows the other memory layout:
+ *
+ * Two memory layouts (QBP_OPT_LSD_MEM, set with qbp_set_option before or after qbp_lsd_configure; every call checks
+ * it again; a value outside 0..2 is QBP_E_INVALID):
+ *   0 (default)  lsd_kernel only: one wavefront per record, all m rows and the cluster tables in LDS, the limits above;
+ *   1            lsd_large_kernel always: one workgroup of 256 threads per record, the rows in a per-workgroup global
+ *                workspace owned by the handle ((W + 1) 32-bit words per check, W = ceil(n / 32), row-major), the
+ *                cluster tables alone in LDS.  Only the rows of active checks exist: a row that was never changed equals
+ *                its original row of [H | r], and rules 4-6 change a row only while it has a 1 in an active column,
+ *                whose checks are all active -- so a check's row is written from the CSR when the check turns active,
+ *                and the pivot search and the XORs of rule 6 look at the active checks alone.  The work of a record
+ *                scales with its clusters, not with m x n.  Limits: n <= 65535 (rank and column share a 32-bit key)
+ *                and lsd_large_lds_bytes(m, n, NP) = 64 + max(8 NP while that fits, 20 m) + 2 NP + 4 n + m bytes,
+ *                rounded up to 16 (NP: the power of two >= n), <= 160 KiB -- 2592 x 7776 and 1008 x 8991 fit; m is
+ *                bounded by nothing else.  At most two workgroups per CU (the workspace: grid x m x (W + 1) words, plus
+ *                the sort keys where they do not fit the LDS -- 650 MB on 2592 x 7776 with 256 CUs);
+ *   2            lsd_large_kernel where lsd_kernel is refused (by bytes or by its 2048 rows), lsd_kernel elsewhere.
+ * The outputs do not depend on the layout (same rules, same bits).  Refusals are host only, before any GPU work, with
+ * the byte count in the message; QBP_INFO_THREADS, QBP_INFO_GRID and QBP_INFO_LDS_BYTES report the launch.
  *
  * One record (syndrome s [m], posterior llr [n], hard decision hard [n]):
  *   1. rank[v] = position of column v in the ascending order of (|llr[v]| by bit pattern, NaN last, v): OSD-0's order;
@@ -586,15 +604,18 @@ int qbp_gd_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const 
  * with r = 0 returns hard with stats {0, 0, 0, 1}.
  *
  * qbp_lsd_batch: syndromes [B][m], llr [B][n], hard [B][n] -> solution [B][n], stats [B][4] (may be NULL).
- * QBP_E_INVALID without a configuration.  One wavefront per record, all of its state in LDS (lsd_kernel).
+ * QBP_E_INVALID without a configuration.  One wavefront per record, all of its state in LDS (lsd_kernel), or the build
+ * QBP_OPT_LSD_MEM selects.
  *
  * QBP_FLAG_LSD in a Monte-Carlo call: the first stage is the call's BP as without the flag (any variant, flooding or
  * QBP_FLAG_LAYERED); every trial it leaves unconverged is decoded by the rules above from its syndrome and the first
  * stage's posterior and hard decision, and classified on the result like an OSD output: the counters OSD-0 fills.
  * counters[10] counts the records with valid = 0 (their solution misses the syndrome); [0], [6], [7] are the first
- * stage's.  The record limits of QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).  QBP_E_INVALID: together with
- * QBP_FLAG_OSD0, any OSD bit, QBP_FLAG_RELAY or QBP_FLAG_GD, or without a configuration.  QBP_E_UNSUPPORTED: in
- * qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and the window entries.
+ * stage's.  The second stage is the build QBP_OPT_LSD_MEM selects (QBP_E_UNSUPPORTED where qbp_lsd_configure would
+ * refuse under the handle's option).  The record limits of QBP_FLAG_OSD0 apply (QBP_MC_OSD_MAX_TRIALS).
+ * QBP_E_INVALID: together with QBP_FLAG_OSD0, any OSD bit, QBP_FLAG_RELAY or QBP_FLAG_GD, or without a configuration.
+ * QBP_E_UNSUPPORTED: in qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, qbp_decode_shots and the
+ * window entries.
  */
 int qbp_lsd_configure(qbp_handle* h, int32_t bits_per_step);
 int qbp_lsd_batch(qbp_handle* h, const uint8_t* syndromes, const double* llr, const uint8_t* hard, int64_t B,
@@ -1002,6 +1023,9 @@ enum {
     QBP_OPT_GD_MEM = 18,         /* BP guided decimation, where a record's messages live (qbp_gd_configure): 0 LDS only, 1 a
                                     global workspace always (tests reach it on small matrices), 2 automatic.  Results do
                                     not depend on it */
+    QBP_OPT_LSD_MEM = 19,        /* localized statistics decoding, where a record's rows of [H | syndrome] live
+                                    (qbp_lsd_configure): 0 LDS only, 1 a global workspace always (tests reach it on small
+                                    matrices), 2 automatic.  Results do not depend on it */
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */

@@ -50,12 +50,15 @@ OPT_MC_WEIGHT_CHUNK = 14     # qbp_mc_run_weight: trials sampled and decoded per
 OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgroup (0 = auto)
 # Relay-BP, layered BP, BP guided decimation: where a record's messages live -- 0 LDS only, 1 global workspace, 2 automatic
 OPT_RELAY_MEM, OPT_LAYERED_MEM, OPT_GD_MEM = 16, 17, 18
+OPT_LSD_MEM = 19             # localized statistics decoding: where a record's rows live, the same three values
 # family: (the option, ``large=`` -> its value, the accepted spellings in words).  ``relay.RelayConfig.large``,
-# ``Decoder.layered_configure(large=)`` and ``gd.GDConfig.large`` spell the same three values differently (README.md)
+# ``Decoder.layered_configure(large=)`` and ``gd.GDConfig.large`` spell the same three values differently (README.md);
+# ``Decoder.lsd_configure(large=)`` spells them as Relay-BP does
 MSG_MEM = {
     "relay":   (OPT_RELAY_MEM,   {False: 0, True: 2, "force": 1}, "False, True or 'force'"),
     "layered": (OPT_LAYERED_MEM, {False: 0, True: 2},             "False or True"),
     "gd":      (OPT_GD_MEM,      {False: 0, True: 1, "auto": 2},  "False, True or 'auto'"),
+    "lsd":     (OPT_LSD_MEM,     {False: 0, True: 2, "force": 1}, "False, True or 'force'"),
 }
 RELAY_MEM, LAYERED_MEM, GD_MEM = (MSG_MEM[family][1] for family in ("relay", "layered", "gd"))
 
@@ -785,14 +788,20 @@ class Decoder:
                                                  stream or None))
 
     @_locked
-    def lsd_configure(self, bits_per_step):
-        """Store the bits_per_step of localized statistics decoding in the handle: qbp_lsd_configure."""
+    def lsd_configure(self, bits_per_step, large=False):
+        """Store the bits_per_step of localized statistics decoding in the handle: OPT_LSD_MEM from ``large`` -- False
+        the LDS kernel only, True the large build (rows in a global workspace) where the LDS kernel does not take the
+        matrix, "force" the large build always --, then qbp_lsd_configure.  The option is rewritten on EVERY call: the
+        default ``large=False`` puts back 0 whatever ``set_option(OPT_LSD_MEM, ...)`` wrote before (set the option
+        after this call, or pass ``large``)."""
+        self.set_msg_mem("lsd", large)
         _check(load().qbp_lsd_configure(self._h, int(bits_per_step)))
 
     @_locked
-    def lsd(self, syndromes, llr, hard, bits_per_step=None, want_stats=True):
+    def lsd(self, syndromes, llr, hard, bits_per_step=None, want_stats=True, large=False):
         """Localized statistics decoding of B decoder outputs (host arrays; qbp_lsd_batch) -> ``(solution uint8[B, n],
-        stats int32[B, 4])``; ``bits_per_step``: configure first (None: the handle's configuration)."""
+        stats int32[B, 4])``; ``bits_per_step``: configure first, with ``large`` as in ``lsd_configure``, which
+        rewrites OPT_LSD_MEM (None: the handle's configuration and option stay, ``large`` is not looked at)."""
         syn = np.ascontiguousarray(syndromes, np.uint8)
         l = np.ascontiguousarray(llr, np.float64)
         hd = np.ascontiguousarray(hard, np.uint8)
@@ -801,7 +810,7 @@ class Decoder:
         if l.shape != (syn.shape[0], self.n) or hd.shape != l.shape:
             raise ValueError(f"llr and hard must have shape ({syn.shape[0]}, {self.n})")
         if bits_per_step is not None:
-            self.lsd_configure(bits_per_step)
+            self.lsd_configure(bits_per_step, large)
         sol = np.empty_like(hd)
         stats = np.empty((syn.shape[0], 4), np.int32) if want_stats else None
         _check(load().qbp_lsd_batch(self._h, syn.ctypes.data, l.ctypes.data, hd.ctypes.data, syn.shape[0],

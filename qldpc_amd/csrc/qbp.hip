@@ -25,6 +25,7 @@
 #include "qbp_gd.hpp"
 #include "qbp_cond.hpp"
 #include "qbp_lsd.hpp"
+#include "qbp_lsd_large.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_window.hpp"
 #include "qbp_launch.hpp"
@@ -366,7 +367,8 @@ struct qbp_handle {
     double relay_alpha = 1.0, relay_clip = 0.0;
     DevBuf<double> d_relay_gammas;
     DevBuf<int32_t> d_relay_iters, d_relay_vinv, d_relay_legs, d_relay_sol;
-    // QBP_OPT_RELAY_MEM, QBP_OPT_LAYERED_MEM, QBP_OPT_GD_MEM by qbp::MsgMemFamily (qbp_msg_mem.hpp states the rule)
+    // QBP_OPT_RELAY_MEM, QBP_OPT_LAYERED_MEM, QBP_OPT_GD_MEM, QBP_OPT_LSD_MEM by qbp::MsgMemFamily (qbp_msg_mem.hpp states
+    // the rule)
     int opt_msg_mem[qbp::MSG_MEM_FAMILIES] = {0};
     // BP guided decimation (qbp_gd_configure); scratch of the host-pointer entry
     bool gd_ready = false;
@@ -378,7 +380,8 @@ struct qbp_handle {
     DevBuf<double> d_prior1_sorted, d_cond_prior1;
     DevBuf<uint8_t> d_cond_sel;
     // localized statistics decoding (qbp_lsd_configure): bits_per_step, the checks of every column (CSC, beside
-    // d_col_ptr); scratch of the host-pointer entry
+    // d_col_ptr); scratch of the host-pointer entry.  The large build's rows and sort keys use d_osd_At and d_osd_keys:
+    // a call has one second stage, and calls on a handle are serial
     bool lsd_ready = false;
     int lsd_bits = 0;
     DevBuf<int32_t> d_lsd_col_row, d_lsd_stats;
@@ -2540,16 +2543,36 @@ try {
 QBP_ABI_CATCH
 
 // ---- Localized statistics decoding (qbp_lsd.hpp) ------------------------------------------------------------------
-// The kernel keeps a record's rows of [H | syndrome] and its cluster tables in LDS, a lane tracks its rows in a 32-bit
-// mask, and columns are 16-bit: matrices beyond that are QBP_E_UNSUPPORTED.
-static int lsd_supported(const qbp_handle* h)
+// Dynamic LDS of a workgroup in the build `large` (lsd_kernel: before rounding up to 16)
+static size_t lsd_build_lds(const qbp_handle* h, bool large)
 {
-    const size_t lds = qbp::lsd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP);
-    if (lds > (size_t)160 * 1024 || h->m > 64 * 32 || h->n > 65535)
-        return fail(QBP_E_UNSUPPORTED, "localized statistics decoding keeps the bit-packed rows of H and its cluster tables "
-                                       "in LDS: %d x %d needs %zu B (limits: 160 KiB, 2048 rows, 65535 columns)",
-                    h->m, h->n, lds);
-    return QBP_OK;
+    return large ? qbp::lsd_large_lds_bytes(h->m, h->n, h->osd_NP) : qbp::lsd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP);
+}
+
+// QBP_OPT_LSD_MEM (qbp_msg_mem.hpp).  lsd_kernel keeps a record's rows of [H | syndrome] and its cluster tables in LDS,
+// a lane tracks its rows in a 32-bit mask, and columns are 16-bit in both kernels; lsd_large_kernel keeps the tables
+// alone in LDS.  A limit that is no byte count enters the choice as a size beyond the LDS: 2049 rows are a matter for
+// the large build.  Matrices beyond the limits of the build the option allows are QBP_E_UNSUPPORTED (host only);
+// *large: the build of a launch.
+static int lsd_build(const qbp_handle* h, bool* large = nullptr)
+{
+    const size_t beyond = qbp::MSG_MEM_LDS_LIMIT + 1;
+    const size_t lds = lsd_build_lds(h, false), lds_large = lsd_build_lds(h, true);
+    const bool wide = h->n > 65535;
+    const qbp::MsgMemChoice c = qbp::msg_mem_choose(
+        h->opt_msg_mem[qbp::MSG_MEM_LSD], h->m > 64 * 32 || wide ? std::max(lds, beyond) : lds,
+        wide ? std::max(lds_large, beyond) : lds_large, [&](bool large_build, size_t) {
+            if (large_build)
+                fail(QBP_E_UNSUPPORTED, "localized statistics decoding with the rows in global memory keeps its cluster "
+                                        "tables in LDS: %d x %d needs %zu B (limits: 160 KiB, 65535 columns)",
+                     h->m, h->n, lds_large);
+            else
+                fail(QBP_E_UNSUPPORTED, "localized statistics decoding keeps the bit-packed rows of H and its cluster tables "
+                                        "in LDS: %d x %d needs %zu B (limits: 160 KiB, 2048 rows, 65535 columns)",
+                     h->m, h->n, lds);
+        });
+    if (large) *large = c.large;
+    return c.ok ? QBP_OK : QBP_E_UNSUPPORTED;
 }
 
 // QBP_FLAG_LSD of a Monte-Carlo call (host only, before any GPU work).  `other_entry`: the budgets, spectrum and shots
@@ -2563,18 +2586,40 @@ static int check_lsd_flags(const qbp_handle* h, uint32_t flags, bool other_entry
     if (other_entry)
         return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_LSD is not available with iteration budgets, spectra or recorded shots");
     if (!h->lsd_ready) return fail(QBP_E_INVALID, "QBP_FLAG_LSD without qbp_lsd_configure");
-    return QBP_OK;                      // (qbp_lsd_configure has checked the limits)
+    return lsd_build(h);                // (QBP_OPT_LSD_MEM may have changed since qbp_lsd_configure)
 }
 
-// One launch of lsd_kernel (device pointers in P: a batch, or the failure records of a Monte-Carlo launch)
+// One launch of lsd_kernel or lsd_large_kernel (device pointers in P: a batch, or the failure records of a Monte-Carlo
+// launch)
 static int lsd_launch(qbp_handle* h, qbp::LsdParams& P, long long max_items, bool records, hipStream_t s)
 {
+    // (QBP_OPT_LSD_MEM may have changed since qbp_lsd_configure)
+    bool large = false;
+    const int rc0 = lsd_build(h, &large);
+    if (rc0) return rc0;
     const int rc = osd_prepare(h);      // (the bit-packed rows of H)
     if (rc) return rc;
     P.m = h->m; P.n = h->n; P.W = h->osd_W; P.NP = h->osd_NP;
     P.hbits = h->d_hbits.p; P.row_ptr = h->d_row_ptr.p; P.col_idx = h->d_col_idx.p;
     P.col_ptr = h->d_col_ptr.p; P.col_row = h->d_lsd_col_row.p;
     P.bits_per_step = h->lsd_bits;
+    if (large) {
+        // one workgroup of four wavefronts per record; per CU the least of: two (the rows stay within the workspace of
+        // osd_launch_swaps, d_osd_At [2 num_cu][(W + 1) m] -- 2592 x 7776: one per CU by its LDS, 650 MB on 256 CUs), what
+        // the LDS holds, and QBP_OPT_BLOCKS_PER_CU where it is set
+        const qbp::LsdLargeLayout L = qbp::lsd_large_layout(h->m, h->n, h->osd_NP);
+        long long per_cu = std::max<long long>(1, std::min<long long>(2, (long long)(qbp::MSG_MEM_LDS_LIMIT / L.bytes)));
+        if (h->opt_blocks_per_cu > 0) per_cu = std::min<long long>(per_cu, h->opt_blocks_per_cu);
+        const long long grid = std::max<long long>(1, std::min<long long>(max_items, (long long)h->num_cu * per_cu));
+        qbp::LsdLargeWorkspace Wk{};
+        Wk.keys_in_lds = L.keys_in_lds; Wk.region0 = (int)L.region0;
+        HIP_TRY(h->d_osd_At.reserve((size_t)grid * (size_t)h->m * ((size_t)h->osd_W + 1)));
+        if (!L.keys_in_lds) { HIP_TRY(h->d_osd_keys.reserve((size_t)grid * (size_t)h->osd_NP)); }
+        Wk.rows = h->d_osd_At.p; Wk.keys = h->d_osd_keys.p;
+        h->last_threads = qbp::LSD_LARGE_THREADS; h->last_lds = (int)L.bytes; h->last_grid = (int)grid;
+        HIP_TRY(qbp::launch_lsd_large(records, P, Wk, (unsigned)grid, L.bytes, s));
+        return QBP_OK;
+    }
     const size_t lds = (qbp::lsd_lds_bytes(h->m, h->n, h->osd_W, h->osd_NP) + 15) & ~(size_t)15;
     // one wavefront per workgroup: as many per CU as the LDS holds, up to osd0_kernel's 32; QBP_OPT_BLOCKS_PER_CU overrides
     long long per_cu = std::max<long long>(1, std::min<long long>(32, (long long)(((size_t)160 * 1024) / lds)));
@@ -2589,7 +2634,7 @@ int qbp_lsd_configure(qbp_handle* h, int32_t bits_per_step)
 try {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (bits_per_step < 0) return fail(QBP_E_INVALID, "bits_per_step = %d (need >= 0)", bits_per_step);
-    int rc = lsd_supported(h);
+    int rc = lsd_build(h);
     if (rc) return rc;
     if (!h->d_lsd_col_row.p) {
         // the checks of every column in ascending order, at the offsets of d_col_ptr
@@ -2633,6 +2678,8 @@ try {
     if (!h->lsd_ready) return fail(QBP_E_INVALID, "qbp_lsd_batch without qbp_lsd_configure");
     if (B == 0) return QBP_OK;
     if (!syndromes || !llr || !hard || !solution) return fail(QBP_E_INVALID, "null pointer");
+    const int rc = lsd_build(h);        // (QBP_OPT_LSD_MEM may have changed since qbp_lsd_configure: before any copy)
+    if (rc) return rc;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
     const size_t m = h->m, n = h->n, b = (size_t)B;
@@ -3316,12 +3363,14 @@ try {
             h->opt_layered_slots = (int)value; return QBP_OK;
         case QBP_OPT_LAYERED_MEM:
         case QBP_OPT_RELAY_MEM:
-        case QBP_OPT_GD_MEM: {
+        case QBP_OPT_GD_MEM:
+        case QBP_OPT_LSD_MEM: {
             const int family = option == QBP_OPT_LAYERED_MEM ? qbp::MSG_MEM_LAYERED
-                             : option == QBP_OPT_RELAY_MEM   ? qbp::MSG_MEM_RELAY : qbp::MSG_MEM_GD;
+                             : option == QBP_OPT_RELAY_MEM   ? qbp::MSG_MEM_RELAY
+                             : option == QBP_OPT_GD_MEM      ? qbp::MSG_MEM_GD : qbp::MSG_MEM_LSD;
             static const char* const out_of_range[qbp::MSG_MEM_FAMILIES] = {       // (by qbp::MsgMemFamily)
                 "Relay-BP memory mode out of range", "layered BP memory mode out of range",
-                "BP guided decimation memory mode out of range"};
+                "BP guided decimation memory mode out of range", "localized statistics decoding memory mode out of range"};
             if (value < qbp::MSG_MEM_LDS || value > qbp::MSG_MEM_AUTO) return fail(QBP_E_INVALID, "%s", out_of_range[family]);
             h->opt_msg_mem[family] = (int)value; return QBP_OK;
         }

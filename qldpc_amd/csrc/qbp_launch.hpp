@@ -22,6 +22,7 @@ struct GdParams;
 struct CondParams;
 struct CssClassify;
 struct LsdParams;
+struct LsdLargeWorkspace;
 struct WindowCommit;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
@@ -176,6 +177,9 @@ hipError_t launch_css_select(const uint8_t* hard, const uint8_t* sol, const uint
 hipError_t launch_css_classify(const CssClassify& P, hipStream_t s);
 // qbp_tu_lsd.hip: lsd_kernel<records> (batch build or Monte-Carlo failure records), one wavefront per record
 hipError_t launch_lsd(bool records, const LsdParams& P, unsigned grid, size_t lds, hipStream_t s);
+// lsd_large_kernel<records> (qbp_lsd_large.hpp): one workgroup of 256 threads per record, the rows in the workspace
+hipError_t launch_lsd_large(bool records, const LsdParams& P, const LsdLargeWorkspace& Wk, unsigned grid, size_t lds,
+                            hipStream_t s);
 // qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)
 hipError_t launch_window_gather(const uint8_t* r, long long B, int m, const int32_t* checks, int mk, uint8_t* syn,
                                 hipStream_t s);

@@ -7,6 +7,7 @@
 //   3, eight pivots      osd_block_shape / _bytes / _pivots / _act / _stage / _table / _update
 //                                                                        osd0_blocked_kernel, osd_order_blocked_kernel
 //   record tail          osd_tally, osd_tally_wave / osd_tally_block, osd_count_record  (osd_tail_wave, osd_tail_block)
+// lsd_large_kernel (qbp_lsd_large.hpp) takes 1 and the workgroup's record tail; its rows live in a global workspace.
 //
 // Every piece is __forceinline__ and takes (tid, nt) -- (lane, 64) in the one-wavefront kernels -- and, where the
 // kernels differ in it, the type of a column index (uint16_t in LDS, int in the workspace kernels).  None of them holds

@@ -6,7 +6,9 @@ unsatisfied, in the order of BP's reliabilities, and only the small systems insi
 
 ``bits_per_step``: the variables an invalid cluster activates per round (0: all of its neighbours).  The ``lsd=``
 argument of ``mc.run_sweep``, ``mc.run_dem`` and ``mc.run_weights`` sends the trials the first-stage BP leaves
-unconverged through LSD instead of OSD.
+unconverged through LSD instead of OSD.  ``large``: False -- the kernel that keeps a record's rows in LDS, which refuses
+matrices beyond 160 KiB or 2048 rows; True -- beyond those the build with the rows in a global workspace
+(QBP_OPT_LSD_MEM = 2); "force" -- that build always.  The output does not depend on it.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ def check_bits_per_step(value):
     return int(value)
 
 
-def performLSDBatch(H, syndromes, llr, hard, bits_per_step=1, device=None):
+def performLSDBatch(H, syndromes, llr, hard, bits_per_step=1, device=None, large=False):
     """LSD of B records on the GPU: syndromes uint8[B, m], BP's posteriors float64[B, n] and hard decisions uint8[B, n]
     -> ``(solutions int8[B, n], stats int32[B, 4])``, stats = rounds, active variables, clusters, valid."""
     from . import bp
@@ -39,13 +41,13 @@ def performLSDBatch(H, syndromes, llr, hard, bits_per_step=1, device=None):
     if l.shape != (syn.shape[0], n) or hd.shape != l.shape:
         raise ValueError(f"llr and hard must have shape ({syn.shape[0]}, {n}), got {l.shape} and {hd.shape}")
     dec = bp.decoder_for(H, device=bp.DEVICE if device is None else device)
-    sol, stats = dec.lsd(syn, l, hd, g)
+    sol, stats = dec.lsd(syn, l, hd, g, large=large)
     return sol.astype(np.int8), stats
 
 
-def performLSD(H, syndrome, llr, hard, bits_per_step=1, device=None):
+def performLSD(H, syndrome, llr, hard, bits_per_step=1, device=None, large=False):
     """LSD of one record, in the shape of the reference's ``performOSD``: -> solution int8[n]."""
     syn, l, hd = np.asarray(syndrome), np.asarray(llr), np.asarray(hard)
     if syn.ndim != 1 or l.ndim != 1 or hd.ndim != 1:
         raise ValueError("syndrome, llr and hard must be vectors")
-    return performLSDBatch(H, syn[None, :], l[None, :], hd[None, :], bits_per_step, device)[0][0]
+    return performLSDBatch(H, syn[None, :], l[None, :], hd[None, :], bits_per_step, device, large)[0][0]

@@ -94,10 +94,14 @@ def gd_run_flags(flags, gd) -> int:
     return flags | _lib.FLAG_GD
 
 
-def lsd_run_flags(flags, lsd) -> int:
+def lsd_run_flags(flags, lsd, lsd_large=False) -> int:
     """``flags`` of a sweep with ``lsd`` (None, or the bits_per_step of localized statistics decoding): | FLAG_LSD, the
-    trials BP leaves unconverged go to LSD.  ValueError together with OSD, Relay-BP or BPGD: one second stage per run."""
+    trials BP leaves unconverged go to LSD.  ValueError together with OSD, Relay-BP or BPGD: one second stage per run;
+    for an ``lsd_large`` that ``Decoder.lsd_configure(large=)`` does not accept, or one without ``lsd``."""
+    _lib.msg_mem_value("lsd", lsd_large)
     if lsd is None:
+        if lsd_large:
+            raise ValueError("lsd_large= needs lsd=")
         return flags
     if flags & (_lib.FLAG_OSD0 | _lib.FLAG_OSD_CS | _lib.FLAG_OSD_E | _lib.FLAG_OSD_LARGE | _lib.FLAG_RELAY | _lib.FLAG_GD):
         raise ValueError("lsd= excludes osd=True, relay= and gd=: one second stage per run")
@@ -106,9 +110,9 @@ def lsd_run_flags(flags, lsd) -> int:
     return flags | _lib.FLAG_LSD
 
 
-def _configure_lsd(dec, lsd):
+def _configure_lsd(dec, lsd, lsd_large=False):
     if lsd is not None:
-        dec.lsd_configure(lsd)
+        dec.lsd_configure(lsd, lsd_large)
 
 
 def _configure_gd(dec, gd):
@@ -175,11 +179,13 @@ NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial record
 
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
-              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None):
+              world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None,
+              lsd_large=False):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
 
     ``lsd``: the bits_per_step (>= 0) of localized statistics decoding on the trials BP does not converge on (FLAG_LSD;
-    not together with ``osd``, ``relay`` or ``gd``).
+    not together with ``osd``, ``relay`` or ``gd``); ``lsd_large`` (False, True, "force"; ``lsd.py``) allows matrices
+    whose rows pass 160 KiB of LDS or number more than 2048 (OPT_LSD_MEM).
 
     ``gd``: a ``gd.GDConfig`` or its dict form -- BP guided decimation on the trials BP does not converge on (FLAG_GD;
     not together with ``osd`` or ``relay``); its ``large`` (False, True, "auto") allows matrices whose record state
@@ -198,7 +204,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -206,7 +212,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd)
+        _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
         step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
@@ -302,7 +308,7 @@ def _dem_args(H, L, probs, prior):
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
-            layered=False, gd=None, window=None, check_round=None, lsd=None):
+            layered=False, gd=None, window=None, check_round=None, lsd=None, lsd_large=False):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -313,13 +319,13 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
     tests (with ``window`` the runner is also passed ``window=(W, F), check_round=``); by default the HIP library and
-    torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``: as in ``run_sweep``.
+    torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``: as in ``run_sweep``.
 
     ``window``: ``(W, F)`` -- the sliding-window decoder (qbp_window_mc_run_probs; ``window.py``) with the round of
     every check in ``check_round``; "not_converged" then counts the trials with a window BP did not converge on.  Not
     together with ``relay``, ``layered``, ``gd`` or ``lsd``.  Sharded and reduced exactly like the plain path."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if window is not None:
@@ -346,7 +352,7 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         dec = bp.decoder_for(H, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd)
+        _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
         step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
@@ -626,16 +632,17 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
-                device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None):
+                device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None,
+                lsd_large=False):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``: as in ``run_sweep``."""
+    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``: as in ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd), layered, variant)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
@@ -644,7 +651,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
         dec = bp.decoder_for(code.Hx, device=device)
         _configure_relay(dec, relay)
         _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd)
+        _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
@@ -657,18 +664,20 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
 
 def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
                        alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False,
-                       rank=0, world=1, device=0, runner=None, all_reduce=None):
+                       rank=0, world=1, device=0, runner=None, all_reduce=None, lsd=None, lsd_large=False):
     """``run_weights`` for any matrix H [m, n] with logical operators / observables L [k, n] (k <= 64) and the
     decoder's LLRs ``prior`` [n].  The weight classes are the strata of UNIFORM noise -- every column failing with the
     same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
-    does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``."""
-    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
+    does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``.  ``lsd``,
+    ``lsd_large``: as in ``run_sweep``."""
+    flags = lsd_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), lsd, lsd_large)
     L, _, prior, n = _dem_args(H, L, None, prior)
     weights = check_weights(weights, n)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
         dec = bp.decoder_for(H, device=device)
+        _configure_lsd(dec, lsd, lsd_large)
         return _weights_on_device(dec, L, distance, weights, prior, begin, end, seed=seed, max_iter=max_iter,
                                   variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
                                   flags=flags, world=world, device=device)
@@ -868,6 +877,9 @@ def main(argv=None):
                     help="localized statistics decoding on the trials BP does not converge on: every invalid cluster "
                          "activates its G least reliable neighbours per round, 0: all of them (not with --osd, --relay, "
                          "--gd, --budgets, --spectrum, --shots, --window)")
+    ap.add_argument("--lsd-large", action="store_true",
+                    help="with --lsd: also on matrices whose rows pass 160 KiB of LDS or number more than 2048 (space-time "
+                         "and detector-error-model matrices): the rows of the active checks live in a global workspace")
     ap.add_argument("--layered", action="store_true",
                     help="BP runs the layered (check-serial) schedule in its default order instead of flooding "
                          "(sum-product or min-sum; not with --budgets, --spectrum, --shots)")
@@ -917,6 +929,8 @@ def main(argv=None):
         except (ValueError, TypeError) as e:
             ap.error(f"--gd: {e}")
     lsd = None
+    if args.lsd_large and args.lsd is None:
+        ap.error("--lsd-large needs --lsd")
     if args.lsd is not None:
         if args.osd or args.relay is not None or args.gd is not None:
             ap.error("--lsd excludes --osd, --relay and --gd")
@@ -1140,20 +1154,20 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               layered=args.layered, gd=gd, lsd=lsd, **common)
+                               layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
             return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered, gd=gd,
-                             lsd=lsd, **common)
+                             lsd=lsd, lsd_large=args.lsd_large, **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
                            layered=args.layered, gd=gd, window=args.window, check_round=check_round, lsd=lsd,
-                           **common)[None, :]
+                           lsd_large=args.lsd_large, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

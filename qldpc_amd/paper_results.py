@@ -74,6 +74,9 @@ def main(argv=None):
     ap.add_argument("--lsd", type=int, default=None, metavar="G",
                     help="localized statistics decoding instead of OSD on BP failures: G variables per cluster and round, "
                          "0: all neighbours (not with --osd 0 or --osd-order)")
+    ap.add_argument("--lsd-large", action="store_true",
+                    help="with --lsd: also on matrices whose rows pass 160 KiB of LDS or number more than 2048: the rows "
+                         "of the active checks live in a global workspace")
     ap.add_argument("--gd", type=int, nargs=2, default=None, metavar=("T", "ROUNDS"),
                     help="BP guided decimation (min-sum, mc.py's defaults) instead of OSD on BP failures: rounds of T "
                          "iterations, at most ROUNDS variables decimated (not with --osd 0, --osd-order or --lsd)")
@@ -94,6 +97,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.lsd is not None and (args.osd == 0 or args.osd_order):
         ap.error("--lsd excludes --osd 0 and --osd-order")
+    if args.lsd_large and args.lsd is None:
+        ap.error("--lsd-large needs --lsd")
     if args.gd_large and args.gd is None:
         ap.error("--gd-large needs --gd")
     if args.gd is not None and (args.osd == 0 or args.osd_order or args.lsd is not None):
@@ -103,7 +108,8 @@ def main(argv=None):
     if args.osd is None:
         args.osd = -1 if args.lsd is not None or gd is not None else 0
     try:
-        mc.lsd_run_flags(mc.gd_run_flags(mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order), gd), args.lsd)
+        mc.lsd_run_flags(mc.gd_run_flags(mc.osd_run_flags(args.osd == 0, args.osd_method, args.osd_order), gd), args.lsd,
+                         args.lsd_large)
     except ValueError as e:
         ap.error(str(e))
     osd_name = (f"BPGD-{args.gd[0]}x{args.gd[1]}" if gd is not None else f"LSD-{args.lsd}" if args.lsd is not None
@@ -144,7 +150,7 @@ def main(argv=None):
         tables[name] = mc.run_sweep(name, args.p, args.trials, draws=args.draws, seed=args.seed,
                                     max_iter=args.max_iter, osd=args.osd == 0, osd_method=args.osd_method,
                                     osd_order=args.osd_order, rank=rank, world=world, device=local, lsd=args.lsd,
-                                    gd=gd)
+                                    lsd_large=args.lsd_large, gd=gd)
         if rank == 0:
             dt = time.time() - t0
             for p, row in zip(args.p, tables[name]):

@@ -38,7 +38,7 @@ UNITS += [("qbp_tu_layered.hip", [])]
 UNITS += [("qbp_tu_gd.hip", [])]
 # Sliding-window decoding (qbp_window_*): window_*_kernel, the glue between the windows of one call
 UNITS += [("qbp_tu_window.hip", [])]
-# Localized statistics decoding (qbp_lsd_batch, QBP_FLAG_LSD): lsd_kernel<records>
+# Localized statistics decoding (qbp_lsd_batch, QBP_FLAG_LSD): lsd_kernel<records>, lsd_large_kernel<records>
 UNITS += [("qbp_tu_lsd.hip", [])]
 # BP with a prior per record (qbp_decode_batch_cond): bp_cond_kernel<variant>, and the glue kernels of qbp_css_*
 UNITS += [("qbp_tu_cond.hip", [])]
