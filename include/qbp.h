@@ -682,6 +682,58 @@ int qbp_mc_run_budgets_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, 
                               uint32_t flags, int64_t* d_counters, void* stream);
 
 /*
+ * Monte-Carlo with posterior-LLR histograms per iteration budget: qbp_mc_run_budgets -- the same trials, sampler,
+ * decoder, OSD and counters [n_budgets][QBP_NUM_COUNTERS], digit for digit -- plus the binned form of the lists
+ * BP_per_Iteration.py:46-60, 82-90 (llrs_per_iter, llrs_per_iter_after_OSD) and rework/Alvarado.py:122, 159-162
+ * (llr_data[...]["true_0"] / ["true_1"]) collect value by value.
+ *   hist [n_budgets][QBP_LLR_HIST_ROWS][bins + 3], int64, ADDED to.  For budget row j let (hard, conv, it, llr) be what
+ *   qbp_decode_batch returns for the trial's syndrome with max_iter = budgets[j].  Every one of the trial's n values
+ *   llr[v] -- the columns without a check too, whose value is the prior -- adds 1 to
+ *       hist[j][2 * !conv + error[v]][col(llr[v])].
+ *   The histograms are of BP's output: no OSD bit changes them.
+ *   Columns of a row, for edges = np.linspace(llr_lo, llr_hi, bins + 1), which the host computes:
+ *       0             x < llr_lo (-inf included)
+ *       1 .. bins     the bin np.histogram(x, bins, range=(llr_lo, llr_hi)) puts x in: left-closed, the last bin closed
+ *                     on both sides
+ *       bins + 1      x > llr_hi (+inf included)
+ *       bins + 2      NaN
+ *   llrs_per_iter[j] is the sum of the four rows of budget j, llrs_per_iter_after_OSD[j] rows 2 + 3; Alvarado's true_0 /
+ *   true_1 are rows 0 + 2 / rows 1 + 3 with one budget.  Identities: sum(hist[j]) = n counters[j][0]; rows 2 + 3 sum to
+ *   n counters[j][6]; rows 1 + 3 sum to the total weight of the errors, whatever j.
+ * Kernels of their own (bp_fused_llrhist_kernel, bp_generic_llrhist_kernel: the budgets builds, binning every emission
+ * into a table the workgroup keeps in LDS as 32-bit counts); every matrix qbp_mc_run_budgets takes.  A count stays
+ * below 2^32 because the host launches at most (2^32 - 1) / n trials at a time (QBP_OPT_LLR_HIST_CHUNK lowers that;
+ * results do not depend on it).  The table has to fit beside the decoder's state: QBP_LLR_HIST_WORDS(n_budgets, bins)
+ * <= QBP_LLR_HIST_MAX_WORDS, which admits 9 budgets x 128 bins, 1 budget x 1024 bins and up to 2045 bins.
+ * QBP_E_INVALID, before any GPU work and with both outputs untouched: a null hist, bins < 1, llr_lo or llr_hi not
+ * finite or llr_lo >= llr_hi, a table beyond the cap, and whatever qbp_mc_run_budgets refuses.  Flags, OSD bits, the
+ * records-per-budget rule and QBP_E_UNSUPPORTED cases are those of qbp_mc_run_budgets.
+ */
+#define QBP_LLR_HIST_ROWS 4
+#define QBP_LLR_HIST_MAX_WORDS 8192
+#define QBP_LLR_HIST_WORDS(n_budgets, bins) ((int64_t)(n_budgets) * QBP_LLR_HIST_ROWS * ((int64_t)(bins) + 3))
+int qbp_mc_run_llr_hist(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                        int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* prior,
+                        const int32_t* budgets, int32_t n_budgets, int32_t variant, double alpha, double damping,
+                        double clip_llr, uint32_t flags, double llr_lo, double llr_hi, int32_t bins, int64_t* counters,
+                        int64_t* hist);
+/* Asynchronous form (as qbp_mc_run_budgets_device): d_prior, d_counters and d_hist are device pointers, both outputs
+ * ADDED to; Lx, probs and budgets stay host pointers.  The handle keeps ONE set of edges (and one table of sampler
+ * thresholds) on the device, rewritten -- and possibly reallocated -- on the calling stream when a call brings others:
+ * calls with different edges or probs on different streams must not be in flight on one handle at the same time. */
+int qbp_mc_run_llr_hist_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, const double* probs,
+                               int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                               const double* d_prior, const int32_t* budgets, int32_t n_budgets, int32_t variant,
+                               double alpha, double damping, double clip_llr, uint32_t flags, double llr_lo,
+                               double llr_hi, int32_t bins, int64_t* d_counters, int64_t* d_hist, void* stream);
+/* The same on T GIVEN error patterns (as qbp_mc_run_errors: counters [n_budgets][QBP_NUM_COUNTERS] SET, not added to);
+ * hist is ADDED to.  This is how a fixture made by the reference's own loop goes through the product path. */
+int qbp_mc_run_errors_llr_hist(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                               int64_t T, const double* prior, const int32_t* budgets, int32_t n_budgets,
+                               int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                               double llr_lo, double llr_hi, int32_t bins, int64_t* counters, int64_t* hist);
+
+/*
  * Monte-Carlo with two distributions per call: qbp_mc_run_probs -- the same trials, sampler, decoder, OSD and
  * counters, digit for digit -- plus two tables, both ADDED to like the counters (rework/main.py:65-112,
  * spectrum.py:37-54).
@@ -1029,6 +1081,10 @@ enum {
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */
+    QBP_OPT_LLR_HIST_CHUNK = 120, /* tests: qbp_mc_run_llr_hist* launches at most this many trials at a time (0 = default,
+                                    the most that keeps the 32-bit counts of a workgroup below 2^32: (2^32 - 1) / n; larger
+                                    values mean that too).  Results do not depend on it.  Not 20: tests/test_lsd_large_cpu.py
+                                    pins 19 as the last option number below 99, and 100 .. 111 are the QBP_INFO_* values */
     QBP_INFO_M = 100, QBP_INFO_N = 101, QBP_INFO_EDGES = 102, QBP_INFO_MAX_ROW_DEG = 103,
     QBP_INFO_MAX_COL_DEG = 104, QBP_INFO_KERNEL_KIND = 105, /* 1 on-chip, 2 general-H, 3 streaming */
     QBP_INFO_THREADS = 106, QBP_INFO_LDS_BYTES = 107, QBP_INFO_GRID = 108, QBP_INFO_NUM_CU = 109,

@@ -38,6 +38,8 @@ MC_OSD_MAX_TRIALS = 1 << 20
 MC_MAX_BUDGETS = 16          # QBP_MC_MAX_BUDGETS: rows of one qbp_mc_run_budgets call
 SPECTRUM_ROWS = 4            # QBP_SPECTRUM_ROWS: weights_found_BP, _OSD, _BP_error, _OSD_error (rework/main.py)
 MC_SPECTRUM_MAX_ITER = 1024  # QBP_MC_SPECTRUM_MAX_ITER: iteration limit of qbp_mc_run_spectrum
+LLR_HIST_ROWS = 4            # QBP_LLR_HIST_ROWS: 2 * (BP did not converge) + (the bit's true value)
+LLR_HIST_MAX_WORDS = 8192    # QBP_LLR_HIST_MAX_WORDS: n_budgets * LLR_HIST_ROWS * (bins + 3) of one qbp_mc_run_llr_hist call
 NUM_COUNTERS = 12
 COUNTER_NAMES = ("trials", "logical_error", "BPs_fault", "BPs_miscorrected", "incorrectable",
                  "degenerateErrors", "not_converged", "sum_iterations",
@@ -51,6 +53,7 @@ OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgr
 # Relay-BP, layered BP, BP guided decimation: where a record's messages live -- 0 LDS only, 1 global workspace, 2 automatic
 OPT_RELAY_MEM, OPT_LAYERED_MEM, OPT_GD_MEM = 16, 17, 18
 OPT_LSD_MEM = 19             # localized statistics decoding: where a record's rows live, the same three values
+OPT_LLR_HIST_CHUNK = 120     # qbp_mc_run_llr_hist: trials per launch (0 = default: the most 32-bit counts allow)
 # family: (the option, ``large=`` -> its value, the accepted spellings in words).  ``relay.RelayConfig.large``,
 # ``Decoder.layered_configure(large=)`` and ``gd.GDConfig.large`` spell the same three values differently (README.md);
 # ``Decoder.lsd_configure(large=)`` spells them as Relay-BP does
@@ -111,6 +114,16 @@ SIGNATURES = {
     "qbp_mc_run_budgets_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
                                             C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32,
                                             C.c_double, C.c_double, C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_run_llr_hist": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64,
+                                      C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32, C.c_double,
+                                      C.c_double, C.c_double, C.c_uint32, C.c_double, C.c_double, C.c_int32, _VP, _VP]),
+    "qbp_mc_run_llr_hist_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32,
+                                             C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, C.c_int32, C.c_int32,
+                                             C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_double, C.c_double,
+                                             C.c_int32, _VP, _VP, _VP]),
+    "qbp_mc_run_errors_llr_hist": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int64, _VP, _VP, C.c_int32,
+                                             C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_double,
+                                             C.c_double, C.c_int32, _VP, _VP]),
     "qbp_mc_run_spectrum": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_uint64,
                                       C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double,
                                       C.c_double, C.c_double, C.c_uint32, _VP, _VP, _VP]),
@@ -227,6 +240,30 @@ def check_budgets(budgets):
     if np.any(np.diff(b.astype(np.int64)) <= 0):
         raise ValueError(f"budgets must be strictly ascending, got {budgets!r}")
     return np.ascontiguousarray(b, np.int32)
+
+
+def check_llr_hist(bins, lo, hi, n_budgets):
+    """The table of ``qbp_mc_run_llr_hist`` as ``(bins, lo, hi)``: an integer ``bins`` >= 1, a finite range with
+    lo < hi, and ``n_budgets * LLR_HIST_ROWS * (bins + 3)`` words within ``LLR_HIST_MAX_WORDS`` (ValueError otherwise
+    -- the library refuses the same values with QBP_E_INVALID)."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 1:
+        raise ValueError(f"bins must be an integer >= 1, got {bins!r}")
+    try:
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"the LLR range must be two numbers, got {(lo, hi)!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"the LLR range must be finite with lo < hi, got ({lo}, {hi})")
+    words = int(n_budgets) * LLR_HIST_ROWS * (int(bins) + 3)
+    if words > LLR_HIST_MAX_WORDS:
+        raise ValueError(f"{n_budgets} budgets x {LLR_HIST_ROWS} rows x ({bins} bins + 3) = {words} words exceed "
+                         f"LLR_HIST_MAX_WORDS = {LLR_HIST_MAX_WORDS}")
+    return int(bins), lo, hi
+
+
+def llr_hist_edges(bins, lo, hi):
+    """The bin edges of ``qbp_mc_run_llr_hist``: ``np.linspace(lo, hi, bins + 1)``, as the library computes them."""
+    return np.linspace(float(lo), float(hi), int(bins) + 1)
 
 
 class QbpError(RuntimeError):
@@ -827,10 +864,12 @@ class Decoder:
         m + 10 n bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
-    def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None):
+    def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None,
+                    after=()):
         """The host form ``fn`` of a sampled Monte-Carlo entry over [trial_begin, trial_end): ``source`` are its
         arguments between distance and the range, ``limit`` those between the prior and the variant, ``decoder`` is
-        (variant, alpha, damping, clip_llr, flags) and ``outputs`` the int64 arrays it adds to, which are returned."""
+        (variant, alpha, damping, clip_llr, flags), ``after`` the arguments between the flags and the outputs, and
+        ``outputs`` the int64 arrays it adds to, which are returned."""
         Lx = np.ascontiguousarray(Lx, np.uint8)
         pr = np.ascontiguousarray(prior, np.float64)
         if Lx.ndim != 2 or Lx.shape[1] != self.n:
@@ -844,26 +883,31 @@ class Decoder:
         for a in range(begin, end, step):
             _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), *source, a, min(a + step, end),
                                        pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
-                                       float(clip_llr), int(flags), *(o.ctypes.data for o in outputs)))
+                                       float(clip_llr), int(flags), *after, *(o.ctypes.data for o in outputs)))
         return outputs
 
-    def _mc_stored(self, fn, Lx, distance, errors, prior, max_iter, decoder, tables=()):
+    def _mc_stored(self, fn, Lx, distance, errors, prior, max_iter, decoder, tables=(), rows=None, after=(), step=None):
         """The host form ``fn`` of a stored-error entry on error patterns uint8[T, n]: the counters, summed over the
-        parts of a long list (a call SETS its counters); ``tables`` are added to by every part."""
+        parts of a long list (a call SETS its counters); ``tables`` are added to by every part.  ``max_iter``: the
+        limit, or the tuple of arguments that stands in its place (a ladder: budgets, their number) with ``rows``
+        counter rows; ``after``: arguments between the flags and the counters."""
         Lx = np.ascontiguousarray(Lx, np.uint8)
         pr = np.ascontiguousarray(prior, np.float64)
         err = np.ascontiguousarray(errors, np.uint8)
         if Lx.ndim != 2 or Lx.shape[1] != self.n or pr.shape != (self.n,) or err.ndim != 2 or err.shape[1] != self.n:
             raise ValueError("bad shapes")
         variant, alpha, damping, clip_llr, flags = decoder
-        total = np.zeros(NUM_COUNTERS, np.int64)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(len(err), 1)
+        shape = NUM_COUNTERS if rows is None else (int(rows), NUM_COUNTERS)
+        limit = max_iter if isinstance(max_iter, tuple) else (int(max_iter),)
+        total = np.zeros(shape, np.int64)
+        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(len(err), 1)
         for a in range(0, len(err), step):
-            part = np.zeros(NUM_COUNTERS, np.int64)
+            part = np.zeros(shape, np.int64)
             chunk = err[a:a + step]
             _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), chunk.ctypes.data, len(chunk),
-                                       pr.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping),
-                                       float(clip_llr), int(flags), part.ctypes.data, *(t.ctypes.data for t in tables)))
+                                       pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
+                                       float(clip_llr), int(flags), *after, part.ctypes.data,
+                                       *(t.ctypes.data for t in tables)))
             total += part
         return total
 
@@ -1071,6 +1115,59 @@ class Decoder:
             self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
             int(trial_begin), int(trial_end), d_prior, bud.ctypes.data, len(bud), int(variant), float(alpha),
             float(damping), float(clip_llr), int(flags), d_counters, stream or None))
+
+    def _llr_hist_table(self, n_budgets, bins, hist):
+        """The table of the LLR-histogram calls (a new zeroed one, or the caller's, which is added to)."""
+        shape = (int(n_budgets), LLR_HIST_ROWS, int(bins) + 3)
+        if hist is None:
+            return np.zeros(shape, np.int64)
+        if not (isinstance(hist, np.ndarray) and hist.dtype == np.int64 and hist.shape == shape and hist.flags.c_contiguous):
+            raise ValueError(f"hist must be a C-contiguous int64 array of shape {shape}")
+        return hist
+
+    @_locked
+    def mc_run_llr_hist(self, Lx, distance, probs, prior, budgets, bins, llr_range, trial_begin, trial_end, draws=1,
+                        seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, hist=None):
+        """``mc_run_budgets`` plus the posterior-LLR histograms per budget (qbp_mc_run_llr_hist): returns ``(counters
+        int64[K, 12], hist int64[K, 4, bins + 3])``.  ``hist[j, 2 * (not converged) + true bit, c]`` counts the
+        posterior values of budget j in column c: 0 below ``llr_range[0]``, 1 .. bins the bins of ``np.histogram(x,
+        bins, range=llr_range)``, bins + 1 above ``llr_range[1]``, bins + 2 NaN.  A given ``hist`` is added to."""
+        bud = check_budgets(budgets)
+        bins, lo, hi = check_llr_hist(bins, *llr_range, len(bud))
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        hist = self._llr_hist_table(len(bud), bins, hist)
+        return tuple(self._mc_sampled("qbp_mc_run_llr_hist", Lx, distance, (probs.ctypes.data, int(draws), int(seed)),
+                                      trial_begin, trial_end, prior, (bud.ctypes.data, len(bud)),
+                                      (variant, alpha, damping, clip_llr, flags),
+                                      [np.zeros((len(bud), NUM_COUNTERS), np.int64), hist],
+                                      step=self.mc_budgets_step(len(bud)), after=(lo, hi, bins)))
+
+    def mc_run_llr_hist_device(self, Lx, distance, probs, d_prior, budgets, bins, llr_range, trial_begin, trial_end,
+                               d_counters, d_hist, draws=1, seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
+                               clip_llr=20.0, flags=0, stream=0):
+        """``mc_run_llr_hist`` on device buffers: d_counters int64[K, 12] and d_hist int64[K, 4, bins + 3] are added
+        to.  One call: with FLAG_OSD0 the caller splits ranges by ``mc_budgets_step(K)``."""
+        bud = check_budgets(budgets)
+        bins, lo, hi = check_llr_hist(bins, *llr_range, len(bud))
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        probs = self._probs(np.full(self.n, float(probs)) if np.ndim(probs) == 0 else probs)
+        _check(load().qbp_mc_run_llr_hist_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), probs.ctypes.data, int(draws), int(seed),
+            int(trial_begin), int(trial_end), d_prior, bud.ctypes.data, len(bud), int(variant), float(alpha),
+            float(damping), float(clip_llr), int(flags), lo, hi, bins, d_counters, d_hist or None, stream or None))
+
+    @_locked
+    def mc_run_errors_llr_hist(self, Lx, distance, errors, prior, budgets, bins, llr_range, variant=SUM_PRODUCT,
+                               alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, hist=None):
+        """``mc_run_llr_hist`` on GIVEN error patterns uint8[T, n] (qbp_mc_run_errors_llr_hist): ``(counters int64[K,
+        12], hist int64[K, 4, bins + 3])``."""
+        bud = check_budgets(budgets)
+        bins, lo, hi = check_llr_hist(bins, *llr_range, len(bud))
+        hist = self._llr_hist_table(len(bud), bins, hist)
+        total = self._mc_stored("qbp_mc_run_errors_llr_hist", Lx, distance, errors, prior, (bud.ctypes.data, len(bud)),
+                                (variant, alpha, damping, clip_llr, flags), (hist,), rows=len(bud), after=(lo, hi, bins),
+                                step=self.mc_budgets_step(len(bud)))
+        return total, hist
 
     @_locked
     def check_messages(self, syndromes, prior, variant, alpha=1.0, damping=1.0, clip_llr=20.0,

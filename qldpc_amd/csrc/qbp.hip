@@ -34,6 +34,9 @@
 static_assert(QBP_NUM_COUNTERS == qbp::NUM_COUNTERS, "counter layout");
 static_assert(QBP_MC_MAX_BUDGETS == qbp::MAX_BUDGETS, "budget ladder length");
 static_assert(QBP_SPECTRUM_ROWS == qbp::SPECTRUM_ROWS, "spectrum rows");
+static_assert(QBP_LLR_HIST_ROWS == qbp::LLR_HIST_ROWS, "LLR histogram rows");
+static_assert(QBP_LLR_HIST_WORDS(9, 128) <= QBP_LLR_HIST_MAX_WORDS && QBP_LLR_HIST_WORDS(1, 1024) <= QBP_LLR_HIST_MAX_WORDS,
+              "LLR histogram cap");
 
 namespace {
 
@@ -226,6 +229,8 @@ struct McInputs {
     int lx_cache_k = -1;
     DevBuf<uint32_t> d_thr;                  // a sampler threshold per column, [n rounded up to 4] (zero in the padding)
     std::vector<uint32_t> thr_cache;
+    DevBuf<double> d_llr_edges;              // qbp_mc_run_llr_hist: np.linspace(lo, hi, bins + 1)
+    std::vector<double> edges_cache;
 
     int prepare_lx(size_t n, const uint8_t* Lx, int32_t k, hipStream_t s)
     {
@@ -255,6 +260,21 @@ struct McInputs {
         HIP_TRY(hipMemcpyAsync(d_thr.p, thr.data(), n4 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
         thr_cache.swap(thr);
+        return QBP_OK;
+    }
+    int prepare_edges(int bins, double lo, double hi, hipStream_t s)
+    {
+        // np.linspace(lo, hi, bins + 1): start + i * step, the last edge exactly hi (as qbp_message_histograms)
+        std::vector<double> edges((size_t)bins + 1);
+        const double step = (hi - lo) / (double)bins;
+        for (int i = 0; i < bins; ++i) edges[i] = (double)i * step + lo;
+        edges[bins] = hi;
+        if (edges_cache == edges) return QBP_OK;
+        edges_cache.clear();
+        HIP_TRY(d_llr_edges.reserve(edges.size()));
+        HIP_TRY(hipMemcpyAsync(d_llr_edges.p, edges.data(), edges.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        edges_cache.swap(edges);
         return QBP_OK;
     }
 };
@@ -305,6 +325,7 @@ struct qbp_handle {
     DevBuf<uint8_t> d_wsE;           // general-H Monte-Carlo: sampled errors
     DevBuf<uint8_t> d_weight_err;    // qbp_mc_run_weight: the fixed-weight errors of one chunk, [chunk][n]
     long long opt_weight_chunk = 0;  // QBP_OPT_MC_WEIGHT_CHUNK (0 = default)
+    long long opt_llr_hist_chunk = 0;   // QBP_OPT_LLR_HIST_CHUNK (0 = default)
     DevBuf<int32_t> d_srow, d_srow_e0, d_srow_deg, d_svar, d_sedge;   // weight-class tables
     DevBuf<int32_t> d_epos, d_cpos, d_long_edge_row;
     DevBuf<int32_t> d_vpos, d_vrow, d_lcol_ptr;      // general-H kernel: column-class tables
@@ -403,8 +424,9 @@ using qbp::LaunchCfg;
 // slot_counters: counter ints per slot (2 * n_budgets rows in the launches of qbp_mc_run_budgets)
 // hist_words: bins of the workgroup's iteration histogram in the launches of qbp_mc_run_spectrum (max_iter + 1; with
 // them a residual-weight word per slot), else 0
+// llr_bytes: the workgroup's posterior-LLR table in the launches of qbp_mc_run_llr_hist (llr_hist_lds_bytes), else 0
 size_t fused_lds_bytes(int dc, int m, int n, int S, int r_stride, bool two_copies = false, bool r0_table = false,
-                       int slot_counters = qbp::NUM_COUNTERS, int hist_words = 0)
+                       int slot_counters = qbp::NUM_COUNTERS, int hist_words = 0, size_t llr_bytes = 0)
 {
     const size_t r_doubles = qbp::fused_r_doubles(r_stride, dc == DC_SMALL ? DV_SMALL : DV_WIDE, S);   // one copy of R
     size_t lds = (size_t)qbp::NP_LDS_BYTES +      // tables of tanh / arctanh (qbp_math.hpp), at the start
@@ -412,7 +434,8 @@ size_t fused_lds_bytes(int dc, int m, int n, int S, int r_stride, bool two_copie
                  (r_doubles + (size_t)dc * m + 3 * (size_t)S) * 8 +
                  (6 * (size_t)S + 1 + (size_t)S * (size_t)slot_counters + (size_t)dc * m) * 4 +
                  2 * (size_t)S * (((size_t)n + 3) / 4) * 4 +    // err_lds[2][S][n4] (Monte-Carlo builds)
-                 (hist_words ? ((size_t)S + (size_t)hist_words) * 4 : 0);
+                 (hist_words ? ((size_t)S + (size_t)hist_words) * 4 : 0) +
+                 (llr_bytes ? llr_bytes + 8 : 0);               // (from the next 8-byte boundary)
     return (lds + 15) & ~(size_t)15;
 }
 
@@ -682,13 +705,14 @@ int build_tables(const int32_t* row_ptr, const int32_t* col_idx, int m, int n, H
 
 // n_budgets: rows of a qbp_mc_run_budgets launch (its slots keep 2 * n_budgets counter rows in LDS), else 0
 // hist_words: max_iter + 1 in a qbp_mc_run_spectrum launch (the workgroup's iteration histogram in LDS), else 0
+// llr_bytes: llr_hist_lds_bytes in a qbp_mc_run_llr_hist launch (the workgroup's posterior-LLR table in LDS), else 0
 int make_cfg(qbp_handle* h, long long B, LaunchCfg* cfg, bool forced = false, bool mc = false, int n_budgets = 0,
-             int hist_words = 0)
+             int hist_words = 0, size_t llr_bytes = 0)
 {
     const int m = h->m;
     const int slot_counters = n_budgets > 0 ? 2 * n_budgets * qbp::NUM_COUNTERS : qbp::NUM_COUNTERS;
     auto lds_bytes = [&](int dc, int m_, int n_, int S_, bool two_copies = false, bool r0_table = false) {
-        return fused_lds_bytes(dc, m_, n_, S_, h->r_stride, two_copies, r0_table, slot_counters, hist_words);
+        return fused_lds_bytes(dc, m_, n_, S_, h->r_stride, two_copies, r0_table, slot_counters, hist_words, llr_bytes);
     };
     int S = h->opt_slots;
     if (S <= 0) {
@@ -912,6 +936,11 @@ struct McArgs {
     int det_row_bytes;
     const unsigned long long* actual;
     unsigned long long* predictions;
+    // qbp_mc_run_llr_hist (a ladder too): the table, the edges on the device and their number - 1, else null / 0
+    long long* llr_hist;
+    const double* llr_edges;
+    int llr_bins;
+    size_t llr_lds() const { return llr_hist ? qbp::llr_hist_lds_bytes(n_budgets, llr_bins) : 0; }
 };
 
 template <typename Params>
@@ -926,6 +955,7 @@ static void put_mc(Params& P, const McArgs& a)
     for (int j = 0; j < a.n_budgets; ++j) P.budgets[j] = a.budgets[j];
     P.spectrum = a.spectrum; P.iter_hist = a.iter_hist;
     P.det_bits = a.det_bits; P.det_row_bytes = a.det_row_bytes; P.actual = a.actual; P.predictions = a.predictions;
+    P.llr_hist = a.llr_hist; P.llr_edges = a.llr_edges; P.llr_bins = a.llr_bins;
 }
 
 // Per-call arguments of a BP launch, whichever kernel runs it (device pointers; outputs may be null).
@@ -977,7 +1007,10 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     const size_t budget_lds = c.mc ? (size_t)2 * c.mc->n_budgets * qbp::NUM_COUNTERS * 4 : 0;
     // (qbp_mc_run_spectrum: its residual-weight word and iteration histogram, likewise)
     const size_t spectrum_lds = c.mc && c.mc->spectrum ? (((size_t)c.max_iter + 2) * 4 + 7) & ~(size_t)7 : 0;
-    const GenericGeom g = generic_geometry(h, B, inplace, budget_lds + spectrum_lds);
+    // (qbp_mc_run_llr_hist: its table, likewise -- bytes that a split R then leaves to it)
+    // (its doubles need an 8-byte boundary, which the tables in front of it -- 4 E bytes of positions -- may miss)
+    const size_t llr_lds = c.mc && c.mc->llr_hist ? c.mc->llr_lds() + 8 : 0;
+    const GenericGeom g = generic_geometry(h, B, inplace, budget_lds + spectrum_lds + llr_lds);
     if (g.lds > (size_t)160 * 1024)
         return fail(QBP_E_UNSUPPORTED, "m = %d checks need %zu B of LDS for the parity bits (limit 160 KiB)",
                     h->m, g.lds);
@@ -1026,8 +1059,9 @@ static int generic_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
         if (!c.mc->det_bits) HIP_TRY(h->d_wsE.reserve((size_t)g.grid * ((n + 3) / 4) * 4));
         put_mc(G, *c.mc);
         G.wsE = h->d_wsE.p;
-        G.budget_tab_off = (int)(g.lds - budget_lds - spectrum_lds);
-        G.spectrum_off = (int)(g.lds - spectrum_lds);
+        G.budget_tab_off = (int)(g.lds - budget_lds - spectrum_lds - llr_lds);
+        G.spectrum_off = (int)(g.lds - spectrum_lds - llr_lds);
+        G.llr_hist_off = (int)((g.lds - llr_lds + 7) & ~(size_t)7);
     }
     HIP_TRY(qbp::launch_generic(c.mc != nullptr, g.mem, variant, G, g.grid, g.threads, g.lds, s));
     return QBP_OK;
@@ -1284,7 +1318,7 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     const bool mc = c.mc != nullptr, f_order = c.col_mode == 1;
     LaunchCfg cfg;
     int rc = make_cfg(h, c.B, &cfg, (c.flags & QBP_FLAG_FORCE_FULL) != 0, mc, mc ? c.mc->n_budgets : 0,
-                      mc && c.mc->spectrum ? c.max_iter + 1 : 0);
+                      mc && c.mc->spectrum ? c.max_iter + 1 : 0, mc ? c.mc->llr_lds() : 0);
     if (rc) return rc;
     FusedParams P{};
     P.m = h->m; P.n = h->n;
@@ -1312,6 +1346,9 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
     if (mc && P.det_bits)               // recorded shots (qbp_decode_shots): builds of their own
         HIP_TRY(fast ? qbp::launch_fused_shots_fast_math(mc, c.variant, P, cfg, s)
                      : qbp::launch_fused_shots(mc, c.variant, P, cfg, s));
+    else if (mc && P.llr_hist)          // posterior-LLR histograms per budget (qbp_mc_run_llr_hist): builds of their own
+        HIP_TRY(fast ? qbp::launch_fused_llrhist_fast_math(mc, c.variant, P, cfg, s)
+                     : qbp::launch_fused_llrhist(mc, c.variant, P, cfg, s));
     else if (mc && P.spectrum)          // residual-weight and iteration tables (qbp_mc_run_spectrum): builds of their own
         HIP_TRY(fast ? qbp::launch_fused_spectrum_fast_math(mc, c.variant, P, cfg, s)
                      : qbp::launch_fused_spectrum(mc, c.variant, P, cfg, s));
@@ -2723,16 +2760,22 @@ struct McCall {
     McDecoder dec;
     const double* d_prior = nullptr;
     // the outputs, all added to
-    enum Out { COUNTERS, LADDER, SPECTRUM } out = COUNTERS;   // qbp_mc_run_budgets*: LADDER, qbp_mc_run*_spectrum*: SPECTRUM
+    // qbp_mc_run_budgets*: LADDER, qbp_mc_run*_spectrum*: SPECTRUM, qbp_mc_run*_llr_hist*: LLRHIST (a ladder too)
+    enum Out { COUNTERS, LADDER, SPECTRUM, LLRHIST } out = COUNTERS;
     int64_t* d_counters = nullptr;           // [rows()][QBP_NUM_COUNTERS]
-    const int32_t* budgets = nullptr;        // LADDER: host [n_budgets], a counter row each
+    const int32_t* budgets = nullptr;        // ladder(): host [n_budgets], a counter row each
     int32_t n_budgets = 0;
+    int64_t* d_llr_hist = nullptr;           // LLRHIST: [n_budgets][QBP_LLR_HIST_ROWS][llr_bins + 3]
+    double llr_lo = 0.0, llr_hi = 0.0;       // LLRHIST: the range of the bins
+    int32_t llr_bins = 0;
     int64_t* d_spectrum = nullptr;           // SPECTRUM: [QBP_SPECTRUM_ROWS][n + 1]
     int64_t* d_iter_hist = nullptr;          // SPECTRUM: [max_iter + 1], may be null
 
     int64_t trials() const { return trial_end - trial_begin; }
-    size_t rows() const { return out == LADDER ? (size_t)n_budgets : 1; }     // counter rows = failure-record planes
-    int32_t last_iter() const { return out == LADDER ? budgets[n_budgets - 1] : dec.max_iter; }
+    bool ladder() const { return out == LADDER || out == LLRHIST; }
+    size_t rows() const { return ladder() ? (size_t)n_budgets : 1; }          // counter rows = failure-record planes
+    int32_t last_iter() const { return ladder() ? budgets[n_budgets - 1] : dec.max_iter; }
+    size_t llr_cells() const { return out == LLRHIST ? (size_t)QBP_LLR_HIST_WORDS(n_budgets, llr_bins) : 0; }
     // sampled trials that no BP kernel draws itself: fixed weight, and the layered kernel, which decodes stored errors only
     bool chunked() const
     {
@@ -2779,7 +2822,17 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
             return fail(QBP_E_INVALID, "max_iter = %d beyond QBP_MC_SPECTRUM_MAX_ITER = %d", c.dec.max_iter,
                         QBP_MC_SPECTRUM_MAX_ITER);
     }
-    if (c.out == McCall::LADDER && (rc = check_budgets(c.budgets, c.n_budgets)) != QBP_OK) return rc;
+    if (c.out == McCall::LLRHIST) {
+        if (!c.d_llr_hist) return fail(QBP_E_INVALID, "hist is null");
+        if (c.llr_bins < 1) return fail(QBP_E_INVALID, "bins = %d must be >= 1", c.llr_bins);
+        if (!std::isfinite(c.llr_lo) || !std::isfinite(c.llr_hi) || !(c.llr_lo < c.llr_hi))
+            return fail(QBP_E_INVALID, "the LLR range [%g, %g] must be finite with llr_lo < llr_hi", c.llr_lo, c.llr_hi);
+    }
+    if (c.ladder() && (rc = check_budgets(c.budgets, c.n_budgets)) != QBP_OK) return rc;
+    if (c.out == McCall::LLRHIST && QBP_LLR_HIST_WORDS(c.n_budgets, c.llr_bins) > QBP_LLR_HIST_MAX_WORDS)
+        return fail(QBP_E_INVALID, "%d budgets x %d rows x (%d bins + 3) = %lld words beyond QBP_LLR_HIST_MAX_WORDS = %d",
+                    c.n_budgets, QBP_LLR_HIST_ROWS, c.llr_bins, (long long)QBP_LLR_HIST_WORDS(c.n_budgets, c.llr_bins),
+                    QBP_LLR_HIST_MAX_WORDS);
     if ((rc = check_mc_errors(h, c.errors, c.trial_begin)) != QBP_OK) return rc;
     if ((rc = check_decode_args(h, c.trials(), c.last_iter(), c.dec.variant)) != QBP_OK) return rc;
     // ladders and spectra have neither a Relay or guided-decimation stage nor a layered build
@@ -2829,7 +2882,7 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
 {
     const int64_t T = c.trials();
     const size_t rows = c.rows();
-    const bool ladder = c.out == McCall::LADDER, spectrum = c.out == McCall::SPECTRUM;
+    const bool ladder = c.ladder(), spectrum = c.out == McCall::SPECTRUM;
     const int32_t max_iter = c.last_iter();
     // Relay-BP instead of OSD on the trials the first stage leaves unconverged: its bit goes to no BP launch
     const bool relay = (c.dec.flags & QBP_FLAG_RELAY) != 0;
@@ -2849,6 +2902,9 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     if (osd && (rc = mc_fail_records(h, mc, rows, (size_t)T, true, s)) != QBP_OK) return rc;
     mc.n_budgets = ladder ? c.n_budgets : 0; mc.budgets = ladder ? c.budgets : nullptr;
     mc.spectrum = reinterpret_cast<long long*>(c.d_spectrum); mc.iter_hist = reinterpret_cast<long long*>(c.d_iter_hist);
+    if (c.out == McCall::LLRHIST) {
+        mc.llr_hist = reinterpret_cast<long long*>(c.d_llr_hist); mc.llr_edges = h->mc_in.d_llr_edges.p; mc.llr_bins = c.llr_bins;
+    }
     mc.lx_cols = h->mc_in.d_lx_cols.p; mc.trial_begin = c.trial_begin; mc.seed = c.errors.seed;
     mc.threshold = mc_threshold(c.errors.p); mc.draws = c.errors.draws; mc.half_distance = c.distance / 2;
     mc.thr_cols = c.errors.kind == McErrors::PROBS ? h->mc_in.d_thr.p : nullptr;
@@ -2858,10 +2914,10 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     b.prior = c.d_prior; b.B = T; b.max_iter = max_iter; b.variant = c.dec.variant;
     b.alpha = c.dec.alpha; b.damping = c.dec.damping; b.clip_llr = c.dec.clip_llr; b.flags = flags;
     b.mc = &mc;
-    // (a ladder's counter rows need LDS of their own: a matrix that fills the on-chip kernel's to the last
-    // kilobyte goes to the general-H kernel)
+    // (a ladder's counter rows -- and the table of qbp_mc_run_llr_hist -- need LDS of their own: a matrix that fills
+    // the on-chip kernel's to the last kilobyte goes to the general-H kernel)
     const bool ladder_fits = !ladder || fused_lds_bytes(h->dc, h->m, h->n, 1, h->r_stride, false, false,
-                                                        2 * c.n_budgets * qbp::NUM_COUNTERS) <= 160 * 1024;
+                                                        2 * c.n_budgets * qbp::NUM_COUNTERS, 0, mc.llr_lds()) <= 160 * 1024;
     // (likewise the iteration histogram of qbp_mc_run_spectrum)
     const bool hist_fits = !spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, h->r_stride, false, false, qbp::NUM_COUNTERS,
                                                         max_iter + 1) <= 160 * 1024;
@@ -2933,6 +2989,25 @@ static int mc_run(qbp_handle* h, const McCall& c, hipStream_t s)
     int rc = mc_prepare(h, c.Lx, c.k, s);
     if (rc) return rc;
     if (c.errors.kind == McErrors::PROBS && (rc = h->mc_in.prepare_thr((size_t)h->n, c.errors.probs, s)) != QBP_OK) return rc;
+    if (c.out == McCall::LLRHIST) {
+        if ((rc = h->mc_in.prepare_edges(c.llr_bins, c.llr_lo, c.llr_hi, s)) != QBP_OK) return rc;
+        // A workgroup keeps 32-bit counts, and one launch adds at most n per trial to a cell of one workgroup -- all of
+        // the launch's trials, should one workgroup decode them all: n * (trials of a launch) <= 2^32 - 1.
+        const long long bound = std::max<long long>(1, 0xffffffffll / std::max(h->n, 1));
+        const long long step = h->opt_llr_hist_chunk > 0 ? std::min(h->opt_llr_hist_chunk, bound) : bound;
+        if (c.trials() > step) {
+            const bool stored = c.errors.kind == McErrors::STORED;      // (its range starts at 0: the rows move instead)
+            for (int64_t a = c.trial_begin; a < c.trial_end; a += step) {
+                McCall part = c;
+                const int64_t len = std::min<int64_t>(step, c.trial_end - a);
+                part.trial_begin = stored ? 0 : a;
+                part.trial_end = part.trial_begin + len;
+                if (stored) part.errors.d_errors = c.errors.d_errors + (size_t)(a - c.trial_begin) * (size_t)h->n;
+                if ((rc = mc_launch(h, part, s)) != QBP_OK) return rc;
+            }
+            return QBP_OK;
+        }
+    }
     if (!c.chunked()) return mc_launch(h, c, s);
     // the errors qbp_mc_sample_errors* returns, drawn chunk by chunk into the handle's buffer and run as stored errors:
     // the global trial index lives in the sampler only, the pipeline indexes a chunk's trials from 0
@@ -2960,11 +3035,13 @@ static int mc_run_device(qbp_handle* h, const McCall& c, void* stream)
 // Every host-array entry: the check, the prior (and stored errors) uploaded, counters (and spectrum tables) zeroed on
 // the device, the launches, and the results copied back and ADDED to the caller's arrays.  Stored-error entries SET the
 // counters: the caller's are zeroed first, also when there is no pattern.  A failed run synchronises, then returns.
+// `spectrum`: the first table of the call -- spectrum of a SPECTRUM call, hist of an LLRHIST call -- else null.
 static int mc_run_host(qbp_handle* h, McCall c, const double* prior, const uint8_t* errors, int64_t* counters,
                        int64_t* spectrum, int64_t* iter_hist)
 {
     // (the check asks of these only whether they are null: the handle's buffers take their place below)
-    c.d_prior = prior; c.d_counters = counters; c.d_spectrum = spectrum; c.errors.d_errors = errors;
+    c.d_prior = prior; c.d_counters = counters; c.errors.d_errors = errors;
+    (c.out == McCall::LLRHIST ? c.d_llr_hist : c.d_spectrum) = spectrum;
     int rc = check_mc_call(h, c, prior);
     if (rc) return rc;
     const bool stored = c.errors.kind == McErrors::STORED, tables = c.out == McCall::SPECTRUM;
@@ -2986,6 +3063,11 @@ static int mc_run_host(qbp_handle* h, McCall c, const double* prior, const uint8
         st.add(iter_hist, d_tab + spec_cells, hist_cells);
         c.d_spectrum = reinterpret_cast<int64_t*>(d_tab);
         c.d_iter_hist = iter_hist ? c.d_spectrum + spec_cells : nullptr;
+    }
+    if (c.out == McCall::LLRHIST) {
+        long long* d_tab = st.zeroed(h->d_spectrum, c.llr_cells());
+        st.add(spectrum, d_tab, c.llr_cells());
+        c.d_llr_hist = reinterpret_cast<int64_t*>(d_tab);
     }
     if (st.failed()) return st.error();
     return st.finish(mc_run(h, c, h->stream));
@@ -3137,6 +3219,52 @@ try {
                        {0, variant, alpha, damping, clip_llr, flags});
     c.out = McCall::LADDER; c.budgets = budgets; c.n_budgets = n_budgets;
     return mc_run_host(h, c, prior, nullptr, counters, nullptr, nullptr);
+}
+QBP_ABI_CATCH
+
+// A ladder call that also fills the posterior-LLR table
+static McCall llr_hist_call(McCall c, const int32_t* budgets, int32_t n_budgets, double llr_lo, double llr_hi, int32_t bins,
+                            int64_t* d_hist = nullptr)
+{
+    c.out = McCall::LLRHIST; c.budgets = budgets; c.n_budgets = n_budgets;
+    c.llr_lo = llr_lo; c.llr_hi = llr_hi; c.llr_bins = bins; c.d_llr_hist = d_hist;
+    return c;
+}
+
+int qbp_mc_run_llr_hist_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, const double* probs,
+                               int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                               const double* d_prior, const int32_t* budgets, int32_t n_budgets, int32_t variant,
+                               double alpha, double damping, double clip_llr, uint32_t flags, double llr_lo,
+                               double llr_hi, int32_t bins, int64_t* d_counters, int64_t* d_hist, void* stream)
+try {
+    return mc_run_device(h, llr_hist_call(mc_call(Lx_host, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs},
+                                                  trial_begin, trial_end, {0, variant, alpha, damping, clip_llr, flags},
+                                                  d_prior, d_counters),
+                                          budgets, n_budgets, llr_lo, llr_hi, bins, d_hist), stream);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_llr_hist(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const double* probs,
+                        int32_t draws, uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* prior,
+                        const int32_t* budgets, int32_t n_budgets, int32_t variant, double alpha, double damping,
+                        double clip_llr, uint32_t flags, double llr_lo, double llr_hi, int32_t bins, int64_t* counters,
+                        int64_t* hist)
+try {
+    return mc_run_host(h, llr_hist_call(mc_call(Lx, k, distance, {McErrors::PROBS, draws, seed, 0.0, probs}, trial_begin,
+                                                trial_end, {0, variant, alpha, damping, clip_llr, flags}),
+                                        budgets, n_budgets, llr_lo, llr_hi, bins), prior, nullptr, counters, hist, nullptr);
+}
+QBP_ABI_CATCH
+
+// (T patterns instead of a sampler: counters SET, hist added to)
+int qbp_mc_run_errors_llr_hist(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, const uint8_t* errors,
+                               int64_t T, const double* prior, const int32_t* budgets, int32_t n_budgets,
+                               int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                               double llr_lo, double llr_hi, int32_t bins, int64_t* counters, int64_t* hist)
+try {
+    return mc_run_host(h, llr_hist_call(mc_call(Lx, k, distance, {McErrors::STORED}, 0, T,
+                                                {0, variant, alpha, damping, clip_llr, flags}),
+                                        budgets, n_budgets, llr_lo, llr_hi, bins), prior, errors, counters, hist, nullptr);
 }
 QBP_ABI_CATCH
 
@@ -3358,6 +3486,9 @@ try {
         case QBP_OPT_MC_WEIGHT_CHUNK:
             if (value < 0 || value > (1 << 20)) return fail(QBP_E_INVALID, "trials per chunk out of [0, 2^20]");
             h->opt_weight_chunk = value; return QBP_OK;
+        case QBP_OPT_LLR_HIST_CHUNK:
+            if (value < 0) return fail(QBP_E_INVALID, "trials per launch must be >= 0");
+            h->opt_llr_hist_chunk = value; return QBP_OK;
         case QBP_OPT_LAYERED_SLOTS:
             if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
             h->opt_layered_slots = (int)value; return QBP_OK;

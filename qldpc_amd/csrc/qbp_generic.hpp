@@ -37,6 +37,7 @@
 #include <stdint.h>
 
 #include "qbp_check.hpp"
+#include "qbp_hist_bin.hpp"
 #include "qbp_mc.hpp"
 
 namespace qbp {
@@ -150,6 +151,13 @@ struct GenericParams {
     int det_row_bytes;
     const unsigned long long* actual;
     unsigned long long* predictions;
+    // QBP_MC_LLRHIST builds (qbp_mc_run_llr_hist; as the on-chip kernel, qbp_kernels.hpp): llr_hist [n_budgets]
+    // [LLR_HIST_ROWS][llr_bins + 3], atomically added to; llr_edges [llr_bins + 1].  The workgroup's table
+    // (llr_hist_lds_bytes: edges and scale, then the counts) sits llr_hist_off bytes into its dynamic LDS.
+    long long* llr_hist;
+    const double* llr_edges;
+    int llr_bins;
+    int llr_hist_off;
 };
 
 // Dynamic LDS of one workgroup: messages (LDSMSG) + syndrome bits + two parity buffers + counters
@@ -281,6 +289,8 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
     constexpr bool BUDGETS = MC && QBP_MC_BUDGETS != 0;     // checkpoints at a ladder of budgets (qbp_mc_run_budgets)
     constexpr bool SPECTRUM = MC && QBP_MC_SPECTRUM != 0;   // residual-weight / iteration tables (qbp_mc_run_spectrum)
     constexpr bool SHOTS = MC && QBP_MC_SHOTS != 0;         // recorded shots in, observable predictions out (qbp_decode_shots)
+    constexpr bool LLRHIST = MC && QBP_MC_LLRHIST != 0;     // posterior-LLR histograms per budget (qbp_mc_run_llr_hist)
+    static_assert(!LLRHIST || BUDGETS, "the LLR histogram builds are budgets builds");
     extern __shared__ __attribute__((aligned(16))) double gsm_all[];
     constexpr NpT np_tab = 0u;          // = the LDS address of gsm_all (no static LDS in this kernel: checked below)
     double* const gsm = gsm_all + NP_LDS_DOUBLES;
@@ -390,6 +400,14 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
     if constexpr (SPECTRUM) {
         for (int i = tid; i <= P.max_iter + 1; i += nt) mc_resw[i] = 0;     // (published by the syndrome loop's barriers)
     }
+    // LLRHIST: the workgroup's edges, scale and counts (every emission adds to them with LDS atomics)
+    double* const llr_le = LLRHIST ? reinterpret_cast<double*>(reinterpret_cast<char*>(gsm_all) + P.llr_hist_off) : nullptr;
+    unsigned* const llr_tab = LLRHIST ? reinterpret_cast<unsigned*>(llr_le + P.llr_bins + 2) : nullptr;
+    if constexpr (LLRHIST) {                                                 // (published by the syndrome loop's barriers)
+        for (int i = tid; i <= P.llr_bins; i += nt) llr_le[i] = P.llr_edges[i];
+        if (tid == 0) llr_le[P.llr_bins + 1] = (double)P.llr_bins / (P.llr_edges[P.llr_bins] - P.llr_edges[0]);
+        for (int i = tid; i < P.n_budgets * LLR_HIST_ROWS * (P.llr_bins + 3); i += nt) llr_tab[i] = 0u;
+    }
     const int first_long = P.row_off[RC + 1], n_long = P.row_off[RC + 2] - first_long;
     const int lbase = P.row_base[RC + 1], n_ledges = E - lbase;
     const int first_lcol = P.col_off[CC + 1], n_lcol = P.col_off[CC + 2] - first_lcol;
@@ -426,7 +444,7 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             // (beliefPropagationGPU.py:195)
             for (int g = tid; g < n4; g += nt)
                 reinterpret_cast<unsigned*>(err)[g] =
-#if QBP_MC_SPECTRUM  // (builds of qbp_mc_run_spectrum: per-qubit thresholds, or stored errors)
+#if QBP_MC_SPECTRUM || QBP_MC_LLRHIST  // (builds of qbp_mc_run_spectrum / _llr_hist: per-qubit thresholds, or stored errors)
                     P.errors_in ? mc_stored_quad(P.errors_in + b * n, g, n)
                                 : mc_error_quad_cols((unsigned long long)(P.trial_begin + b), g, P.draws, P.seed,
                                                      P.thr_cols);
@@ -511,6 +529,12 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             unsigned long long lm = 0ull;
             int ew = 0, df = 0;
             int rw = 0;                                      // SPECTRUM: weight of the residual (this thread's share)
+            // LLRHIST: plane bj, rows 2 * !conv + error bit; a thread's consecutive values that fall into one cell
+            // are merged into one LDS atomic
+            const int llr_ncol = LLRHIST ? P.llr_bins + 3 : 0;
+            unsigned* const llr_rows = LLRHIST ? llr_tab + (bj * LLR_HIST_ROWS + (conv ? 0 : 2)) * llr_ncol : nullptr;
+            int llr_cell = -1;
+            unsigned llr_run = 0;
             for (int x = tid; x < n; x += nt) {
                 double val;
                 if (x < P.col_off[1]) {
@@ -542,6 +566,14 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                     }
                 } else if constexpr (MC) {
                     const unsigned e = err[v];
+                    if constexpr (LLRHIST) {
+                        const int cell = (int)(e & 1u) * llr_ncol + llr_hist_col(val, llr_le, P.llr_bins);
+                        if (cell != llr_cell) {
+                            if (llr_run) atomicAdd(&llr_rows[llr_cell], llr_run);
+                            llr_cell = cell; llr_run = 0;
+                        }
+                        ++llr_run;
+                    }
                     if (to_osd) {
                         P.fail_llr[rec * n + v] = val;
                         P.fail_hard[rec * n + v] = (uint8_t)hd;
@@ -557,6 +589,9 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
                     if (P.llr) P.llr[b * n + v] = val;
                     if (P.hard) P.hard[b * n + v] = (uint8_t)hd;
                 }
+            }
+            if constexpr (LLRHIST) {
+                if (llr_run) atomicAdd(&llr_rows[llr_cell], llr_run);
             }
             if constexpr (MC) {
                 if (to_osd) {
@@ -805,6 +840,19 @@ __global__ __launch_bounds__(1024) void bp_generic_kernel(const GenericParams P)
             for (int i = tid; i <= P.max_iter; i += nt)
                 if (it_hist[i])
                     atomicAdd(reinterpret_cast<unsigned long long*>(P.iter_hist + i), (unsigned long long)it_hist[i]);
+    }
+    if constexpr (LLRHIST) {
+        // llr_hist[j][r][col] += exact[j] for the unconverged rows, the sum of from[0 .. j] for the converged ones:
+        // one thread per cell, one global atomic per non-zero cell
+        __syncthreads();
+        const int ncol = P.llr_bins + 3;
+        for (int t = tid; t < P.n_budgets * LLR_HIST_ROWS * ncol; t += nt) {
+            const int j = t / (LLR_HIST_ROWS * ncol), rc = t - j * (LLR_HIST_ROWS * ncol);
+            unsigned long long sum = llr_tab[t];
+            if (rc < 2 * ncol)
+                for (int jj = 0; jj < j; ++jj) sum += llr_tab[jj * LLR_HIST_ROWS * ncol + rc];
+            if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(P.llr_hist + t), sum);
+        }
     }
     if constexpr (BUDGETS) {
         // counters[j][i] += exact[j][i] + from[0 .. j][i]

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "qbp_hist_bin.hpp"
+
 namespace qbp {
 
 #ifdef QBP_DEFINE_KERNELS   /* non-template kernels: defined in their translation unit only */
@@ -63,10 +65,7 @@ __global__ __launch_bounds__(256) void hist_bin_kernel(const double* msg, const 
         const int e = (int)(i - b * E);
         const double v = msg[i];
         if (!(v >= first && v <= last)) continue;      // (NaN or outside: np.histogram drops them)
-        int k = (int)((v - first) * norm);
-        k = k < 0 ? 0 : (k > bins - 1 ? bins - 1 : k);
-        while (k > 0 && v < le[k]) --k;                 // the estimate can be one off next to an edge
-        while (k < bins - 1 && v >= le[k + 1]) ++k;
+        const int k = hist_bin_of(v, le, bins, first, norm);
         const unsigned cls = errors[b * n + col_idx[e]] & 1u;
         atomicAdd(&lh[cls * bins + k], 1u);
     }

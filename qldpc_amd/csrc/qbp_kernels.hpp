@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "qbp_check.hpp"
+#include "qbp_hist_bin.hpp"
 #include "qbp_mc.hpp"
 
 // Register-budget choices of the shapes that do not fit 128 registers otherwise (A/B switches for
@@ -154,6 +155,11 @@ struct FusedParams {
     int det_row_bytes;
     const unsigned long long* actual;
     unsigned long long* predictions;
+    // QBP_MC_LLRHIST builds (qbp_mc_run_llr_hist; budgets as above): llr_hist [n_budgets][LLR_HIST_ROWS][llr_bins + 3],
+    // atomically added to; llr_edges [llr_bins + 1], np.linspace(lo, hi, llr_bins + 1) from the host
+    long long* llr_hist;
+    const double* llr_edges;
+    int llr_bins;
 };
 
 // Rarely used launch parameters (output pointers, Monte-Carlo settings, ...) are re-read from the
@@ -204,6 +210,8 @@ __device__ __forceinline__ void mc_classify(unsigned long long* mc_lmask, int* m
 //   var_lds[DC][m], err_lds[2][S][n4] bytes (MC),
 //   then 32-bit words again in the QBP_MC_SPECTRUM builds: mc_resw[S] (residual weight accumulator of the slot),
 //   it_hist[max_iter + 1] (the workgroup's iteration histogram)
+//   or, in the QBP_MC_LLRHIST builds, from the next 8-byte boundary: the workgroup's posterior-LLR table
+//   (llr_hist_lds_bytes: edges and scale as doubles, then the counts)
 template <int DC, int DV, int VARIANT, bool MC, bool FORCE_FULL, int MAX_THREADS, int MIN_WAVES_PER_SIMD,
           bool ONE_BARRIER = false>
 __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kernel(const FusedParams P)
@@ -234,6 +242,14 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     // forms the parity of lx_cols over the support of the hard decision -- the observable prediction -- which the slot
     // leader stores, with the converged flag, and compares with the recorded observables.
     constexpr bool SHOTS = MC && QBP_MC_SHOTS != 0;
+    // LLRHIST (qbp_mc_run_llr_hist; the -DQBP_LLRHIST_TU builds only, which are BUDGETS builds): every emission -- a
+    // checkpoint, the last budget or the trial's convergence, classified here or left to OSD -- bins the posterior
+    // value of each of the trial's n variables into the workgroup's table in LDS, plane bj, row 2 * !conv + error bit.
+    // The unconverged rows are exact per budget; a converged trial is binned once, in the plane of the budget it
+    // converged in, and counts for every later one: the prefix sum is formed when the workgroup ends, with the
+    // counters'.  Counts are 32 bits: the host keeps n * (trials of a launch) below 2^32.
+    constexpr bool LLRHIST = MC && QBP_MC_LLRHIST != 0;
+    static_assert(!LLRHIST || BUDGETS, "the LLR histogram builds are budgets builds");
     // dynamic LDS: the tables of the two elementary functions (qbp_math.hpp, NpImage) first -- a constant
     // address, so that a table access is a row offset plus an immediate -- then the carve described above
     extern __shared__ __attribute__((aligned(16))) double smem_all[];
@@ -291,6 +307,13 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     // SPECTRUM: mc_resw[S] then it_hist[max_iter + 1], behind the error bytes (recomputed where used, as err_buf)
     auto spec_words = [&]() -> int* {
         return var_lds + DC * m + 2 * S * COLD(n_words4);
+    };
+
+    // LLRHIST: [llr_bins + 1] edges and the scale, then the counts [n_budgets][LLR_HIST_ROWS][llr_bins + 3], behind
+    // the error bytes on an 8-byte boundary (recomputed where used, as err_buf)
+    auto llr_edges_lds = [&]() -> double* {
+        return reinterpret_cast<double*>(
+            (reinterpret_cast<uintptr_t>(var_lds + DC * m + 2 * S * COLD(n_words4)) + 7) & ~(uintptr_t)7);
     };
 
     // ---- check step of one row: q[DC] -> put(j, r) for its DC edges (qbp_check.hpp) -----------------
@@ -430,6 +453,16 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
     if constexpr (SPECTRUM) {
         int* const it_hist = spec_words() + S;
         for (int i = tid; i <= P.max_iter; i += blockDim.x) it_hist[i] = 0;
+    }
+    if constexpr (LLRHIST) {
+        const int bins = COLD(llr_bins);
+        double* const le = llr_edges_lds();
+        const double* const ge = COLD(llr_edges);
+        for (int i = tid; i <= bins; i += blockDim.x) le[i] = ge[i];
+        if (tid == 0) le[bins + 1] = (double)bins / (ge[bins] - ge[0]);
+        unsigned* const tab = reinterpret_cast<unsigned*>(le + bins + 2);
+        const int cells = COLD(n_budgets) * LLR_HIST_ROWS * (bins + 3);
+        for (int i = tid; i < cells; i += blockDim.x) tab[i] = 0u;
     }
 
     // The lane's own check->variable messages are needed again in the variable step (Q = value - R):
@@ -576,7 +609,7 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 err_par ^= 1u;
                 unsigned* const err_words = reinterpret_cast<unsigned*>(err_buf());
                 const unsigned long long trial = (unsigned long long)(COLD(trial_begin) + b);
-#if QBP_MC_SPECTRUM      /* per-qubit thresholds, or stored errors (qbp_mc_run_errors_spectrum) */
+#if QBP_MC_SPECTRUM || QBP_MC_LLRHIST   /* per-qubit thresholds, or stored errors (qbp_mc_run_errors_spectrum, _llr_hist) */
                 const uint32_t* const thr = COLD(thr_cols);
                 const uint8_t* const ein = COLD(errors_in);
                 for (int g = c; g < P.n_words4; g += m)
@@ -804,6 +837,34 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                     if (ew) atomicAdd(&mc_weight[slot], ew);
                     if (df) atomicOr(&mc_diff[slot], 1);
                     }
+                    if constexpr (LLRHIST) {
+                        // this lane's variables into plane bj, rows 2 * !conv + error bit, behind the classification
+                        // (its accumulators are dead by now): a run of equal cells among the lane's own values, in edge
+                        // order, is one LDS atomic; only the previous cell and the length of its run are kept
+                        const int bins = ca->llr_bins, ncol = bins + 3;
+                        const double* const le = llr_edges_lds();
+                        unsigned* const rows = reinterpret_cast<unsigned*>(const_cast<double*>(le) + bins + 2) +
+                                               (bj * LLR_HIST_ROWS + (conv ? 0 : 2)) * ncol;
+                        int prev = -1;                       // the run of equal cells so far, and its length
+                        unsigned run = 0u;
+#pragma unroll
+                        for (int j = 0; j < DC; ++j) {
+                            if ((wmask >> j) & 1u) {
+                                const int cell = (int)((ebits >> j) & 1u) * ncol + llr_hist_col(val[j], le, bins);
+                                if (cell != prev) {
+                                    if (run) atomicAdd(&rows[prev], run);
+                                    prev = cell; run = 0u;
+                                }
+                                ++run;
+                            }
+                        }
+                        if (run) atomicAdd(&rows[prev], run);
+                        const unsigned char* const err_lds = err_buf();
+                        for (int i = c; i < n_iso; i += m) {         // isolated variables: the value is the prior
+                            const int v = COLD(iso_vars)[i];
+                            atomicAdd(&rows[(int)(err_lds[v] & 1u) * ncol + llr_hist_col(COLD(prior)[v], le, bins)], 1u);
+                        }
+                    }
                     if (c == 0) {
                         mc_pending = true;
                         if constexpr (!SHOTS) { mc_pending_conv = conv; mc_pending_it = it; }
@@ -908,6 +969,19 @@ __global__ __launch_bounds__(MAX_THREADS, MIN_WAVES_PER_SIMD) void bp_fused_kern
                 }
                 if (sum)
                     atomicAdd(reinterpret_cast<unsigned long long*>(COLD(counters) + t), (unsigned long long)sum);
+            }
+            if constexpr (LLRHIST) {
+                // llr_hist[j][r][col] += exact[j] for the unconverged rows, the sum of from[0 .. j] for the converged
+                // ones: one thread per cell, one atomic per non-zero cell and workgroup
+                const int bins = COLD(llr_bins), ncol = bins + 3;
+                const unsigned* const lt = reinterpret_cast<const unsigned*>(llr_edges_lds() + bins + 2);
+                for (int t = tid; t < K * LLR_HIST_ROWS * ncol; t += blockDim.x) {
+                    const int j = t / (LLR_HIST_ROWS * ncol), rc = t - j * (LLR_HIST_ROWS * ncol);
+                    unsigned long long sum = lt[t];
+                    if (rc < 2 * ncol)
+                        for (int jj = 0; jj < j; ++jj) sum += lt[jj * LLR_HIST_ROWS * ncol + rc];
+                    if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(COLD(llr_hist) + t), sum);
+                }
             }
         }
     }

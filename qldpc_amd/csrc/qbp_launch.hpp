@@ -91,6 +91,10 @@ hipError_t launch_fused_spectrum_fast_math(bool mc, int variant, const FusedPara
 hipError_t launch_fused_shots(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
 hipError_t launch_fused_shots_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
                                         hipStream_t s);
+// budgets builds that also bin the posterior LLRs of every emission (P.llr_hist; qbp_mc_run_llr_hist): -DQBP_LLRHIST_TU
+hipError_t launch_fused_llrhist(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s);
+hipError_t launch_fused_llrhist_fast_math(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg,
+                                          hipStream_t s);
 hipError_t launch_debug_math(int kind, const double* x, double* y, long long count, hipStream_t s);
 hipError_t launch_mc_sample(uint8_t* errors, int n, long long T, long long trial_begin, int draws,
                             unsigned long long seed, unsigned threshold, hipStream_t s);
@@ -100,7 +104,8 @@ hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long 
 // rows of exactly `weight` ones (mc_sample_weight_kernel; 0 <= weight <= n); clears errors [T][n] first, on s
 hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
                                    unsigned long long seed, hipStream_t s);
-// qbp_tu_generic.hip (Monte-Carlo launches with G.det_bits go to the -DQBP_SHOTS_TU builds, with G.spectrum to the
+// qbp_tu_generic.hip (Monte-Carlo launches with G.det_bits go to the -DQBP_SHOTS_TU builds, with G.llr_hist to the
+// -DQBP_LLRHIST_TU builds, with G.spectrum to the
 // -DQBP_SPECTRUM_TU builds, with G.n_budgets to the
 // -DQBP_BUDGETS_TU builds, others with G.thr_cols to the -DQBP_COLS_TU builds)
 hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G, int grid, int threads,

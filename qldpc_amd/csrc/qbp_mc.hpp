@@ -37,11 +37,28 @@
 #define QBP_MC_SHOTS 0
 #endif
 
+#ifndef QBP_MC_LLRHIST
+// 1: the Monte-Carlo kernels also bin the posterior LLRs of every emission -- per iteration budget, by BP's converged
+// flag and by the true value of the bit -- into a table the workgroup keeps in LDS (qbp_mc_run_llr_hist).  Set,
+// together with QBP_MC_COLS and QBP_MC_BUDGETS, by the translation units compiled for that (-DQBP_LLRHIST_TU), which
+// give those kernels names of their own: the other builds keep their code, registers, scratch and LDS.  These builds
+// take stored errors too (errors_in), as the QBP_MC_SPECTRUM builds do.
+#define QBP_MC_LLRHIST 0
+#endif
+
 namespace qbp {
 
 constexpr int NUM_COUNTERS = 12;
 constexpr int MAX_BUDGETS = 16;        // QBP_MC_MAX_BUDGETS of include/qbp.h
 constexpr int SPECTRUM_ROWS = 4;       // QBP_SPECTRUM_ROWS of include/qbp.h
+constexpr int LLR_HIST_ROWS = 4;       // QBP_LLR_HIST_ROWS of include/qbp.h: 2 * !converged + error bit
+
+// Bytes of a workgroup's posterior-LLR table in LDS (QBP_MC_LLRHIST builds), 8-byte aligned: [bins + 1] edges and the
+// bin estimate's scale as doubles, then [n_budgets][LLR_HIST_ROWS][bins + 3] 32-bit counts.
+__host__ __device__ inline size_t llr_hist_lds_bytes(int n_budgets, int bins)
+{
+    return ((size_t)bins + 2) * 8 + (((size_t)n_budgets * LLR_HIST_ROWS * ((size_t)bins + 3) + 1) & ~(size_t)1) * 4;
+}
 
 // Row of spectrum[SPECTRUM_ROWS][n + 1] a trial with a non-zero residual goes to (rework/main.py:96-110): by BP's
 // converged flag and by whether the residual is a logical operator -- never by whether OSD ran or was valid.

@@ -6,8 +6,21 @@
 // running trial at a ladder of iteration budgets (qbp_mc_run_budgets; per-qubit thresholds always); and once more with
 // -DQBP_SPECTRUM_TU: the builds that add residual weights and iteration indices to tables (qbp_mc_run_spectrum; per-qubit
 // thresholds or stored errors); and once more with -DQBP_SHOTS_TU: the builds that decode recorded shots
-// (qbp_decode_shots: detection events read from memory, observable predictions written).
-#if defined(QBP_SHOTS_TU)
+// (qbp_decode_shots: detection events read from memory, observable predictions written); and once more with
+// -DQBP_LLRHIST_TU: budgets builds that also bin the posterior LLRs of every emission (qbp_mc_run_llr_hist; per-qubit
+// thresholds or stored errors).
+#if defined(QBP_LLRHIST_TU)
+#define QBP_MC_COLS 1
+#define QBP_MC_BUDGETS 1
+#define QBP_MC_LLRHIST 1
+#ifdef QBP_FAST_TU
+#define bp_fused_kernel bp_fused_llrhist_kernel_fast_math
+#define launch_fused launch_fused_llrhist_fast_math
+#else
+#define bp_fused_kernel bp_fused_llrhist_kernel
+#define launch_fused launch_fused_llrhist
+#endif
+#elif defined(QBP_SHOTS_TU)
 #define QBP_MC_SHOTS 1
 #ifdef QBP_FAST_TU
 #define bp_fused_kernel bp_fused_shots_kernel_fast_math
@@ -100,7 +113,8 @@ hipError_t launch_variant(int variant, const FusedParams& P, const LaunchCfg& cf
 
 hipError_t launch_fused(bool mc, int variant, const FusedParams& P, const LaunchCfg& cfg, hipStream_t s)
 {
-#if defined(QBP_COLS_TU) || defined(QBP_BUDGETS_TU) || defined(QBP_SPECTRUM_TU) || defined(QBP_SHOTS_TU)
+#if defined(QBP_COLS_TU) || defined(QBP_BUDGETS_TU) || defined(QBP_SPECTRUM_TU) || defined(QBP_SHOTS_TU) || \
+    defined(QBP_LLRHIST_TU)
     if (!mc) return hipErrorInvalidValue;       // (Monte-Carlo builds only)
     return launch_variant<true>(variant, P, cfg, s);
 #else

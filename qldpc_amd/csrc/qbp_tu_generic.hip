@@ -11,7 +11,14 @@
 // With -DQBP_SPECTRUM_TU: those three again, adding residual weights and iteration indices to tables
 // (qbp_mc_run_spectrum).
 // With -DQBP_SHOTS_TU: three that decode recorded shots (qbp_decode_shots).
-#if defined(QBP_SHOTS_TU)
+// With -DQBP_LLRHIST_TU: the budgets builds once more, binning the posterior LLRs of every emission
+// (qbp_mc_run_llr_hist).
+#if defined(QBP_LLRHIST_TU)
+#define QBP_MC_COLS 1
+#define QBP_MC_BUDGETS 1
+#define QBP_MC_LLRHIST 1
+#define bp_generic_kernel bp_generic_llrhist_kernel
+#elif defined(QBP_SHOTS_TU)
 #define QBP_MC_SHOTS 1
 #define bp_generic_kernel bp_generic_shots_kernel
 #elif defined(QBP_SPECTRUM_TU)
@@ -58,7 +65,14 @@ hipError_t generic_launch_v(int variant, const GenericParams& G, int grid, int t
 #define QBP_CAT2(a, b) a##b
 #define QBP_CAT(a, b) QBP_CAT2(a, b)
 
-#if defined(QBP_SHOTS_TU)
+#if defined(QBP_LLRHIST_TU)
+// launch_generic_llrhist_mem0 / _mem1 / _mem2 (Monte-Carlo only)
+hipError_t QBP_CAT(launch_generic_llrhist_mem, QBP_GENERIC_MEM)(int variant, const GenericParams& G, int grid, int threads,
+                                                                size_t lds, hipStream_t s)
+{
+    return generic_launch_v<true, QBP_GENERIC_MEM>(variant, G, grid, threads, lds, s);
+}
+#elif defined(QBP_SHOTS_TU)
 // launch_generic_shots_mem0 / _mem1 / _mem2 (Monte-Carlo only)
 hipError_t QBP_CAT(launch_generic_shots_mem, QBP_GENERIC_MEM)(int variant, const GenericParams& G, int grid, int threads,
                                                               size_t lds, hipStream_t s)
@@ -97,7 +111,10 @@ hipError_t QBP_CAT(launch_generic_mem, QBP_GENERIC_MEM)(bool mc, int variant, co
 #endif
 
 #if QBP_GENERIC_MEM == 0 && !defined(QBP_COLS_TU) && !defined(QBP_BUDGETS_TU) && !defined(QBP_SPECTRUM_TU) && \
-    !defined(QBP_SHOTS_TU)
+    !defined(QBP_SHOTS_TU) && !defined(QBP_LLRHIST_TU)
+hipError_t launch_generic_llrhist_mem0(int, const GenericParams&, int, int, size_t, hipStream_t);
+hipError_t launch_generic_llrhist_mem1(int, const GenericParams&, int, int, size_t, hipStream_t);
+hipError_t launch_generic_llrhist_mem2(int, const GenericParams&, int, int, size_t, hipStream_t);
 hipError_t launch_generic_shots_mem0(int, const GenericParams&, int, int, size_t, hipStream_t);
 hipError_t launch_generic_shots_mem1(int, const GenericParams&, int, int, size_t, hipStream_t);
 hipError_t launch_generic_shots_mem2(int, const GenericParams&, int, int, size_t, hipStream_t);
@@ -122,6 +139,13 @@ hipError_t launch_generic(bool mc, int mem, int variant, const GenericParams& G,
             case GENERIC_MEM_LDS:   return launch_generic_shots_mem1(variant, G, grid, threads, lds, s);
             case GENERIC_MEM_SPLIT: return launch_generic_shots_mem2(variant, G, grid, threads, lds, s);
             default:                return launch_generic_shots_mem0(variant, G, grid, threads, lds, s);
+        }
+    }
+    if (mc && G.llr_hist) {           // posterior-LLR histograms per iteration budget (qbp_mc_run_llr_hist)
+        switch (mem) {
+            case GENERIC_MEM_LDS:   return launch_generic_llrhist_mem1(variant, G, grid, threads, lds, s);
+            case GENERIC_MEM_SPLIT: return launch_generic_llrhist_mem2(variant, G, grid, threads, lds, s);
+            default:                return launch_generic_llrhist_mem0(variant, G, grid, threads, lds, s);
         }
     }
     if (mc && G.spectrum) {           // residual-weight and iteration tables (qbp_mc_run_spectrum)

@@ -16,6 +16,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
                                      (decode RECORDED shots to observable predictions: run_shots)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
+    python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 --llr-hist 128 -30 30 --out ladder.json
+                                     (and the posterior-LLR histograms per limit: run_llr_hist; table in ladder.npz)
     python -m qldpc_amd.mc --code 144 --p 0.05 --osd --spectrum out.npz
                                      (residual-weight spectra and the iteration histogram per point: run_spectrum)
     python -m qldpc_amd.mc --code 144 --depolarizing 0.01 0.02 --trials 100000 --osd
@@ -507,14 +509,102 @@ def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, dra
     return all_reduce(table) if all_reduce is not None else table
 
 
-def bp_per_iteration(code_names, p, budgets, trials, osd=True, **kwargs):
+def _split_llr_hist(flat, K, bins):
+    """[K * 12 + K * 4 * (bins + 3)] -> (counters [K, 12], hist [K, 4, bins + 3]): the layout the LLR-histogram runs
+    reduce in one piece."""
+    flat = np.asarray(flat, np.int64).ravel()
+    a = K * NUM_COUNTERS
+    return flat[:a].reshape(K, NUM_COUNTERS).copy(), flat[a:].reshape(K, _lib.LLR_HIST_ROWS, bins + 3).copy()
+
+
+def _llr_hist_on_device(dec, L, distance, probs, prior, budgets, bins, llr_range, begin, end, *, draws, seed, variant,
+                        alpha, damping, clip_llr, osd, flags, world, device):
+    """One rank's slice of a ladder with its LLR table on the device -- counters and table side by side in one int64
+    row -- then the one all-reduce of the whole row."""
+    K = len(budgets)
+
+    def launch(i, d_prior, a, b, d_out, stream):
+        dec.mc_run_llr_hist_device(L, distance, probs, d_prior, budgets, bins, llr_range, a, b, d_out,
+                                   d_out + 8 * K * NUM_COUNTERS, draws=draws, seed=seed, variant=variant, alpha=alpha,
+                                   damping=damping, clip_llr=clip_llr, flags=flags, stream=stream)
+    step = dec.mc_budgets_step(K) if osd else NO_STEP      # OSD keeps records per trial and budget
+    width = K * NUM_COUNTERS + K * _lib.LLR_HIST_ROWS * (bins + 3)
+    return _on_device((1, width), [prior], begin, end, step, launch, world, device)
+
+
+def run_llr_hist(code_name, p, trials, budgets, bins, llr_range, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0,
+                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
+                 device=0, runner=None, all_reduce=None):
+    """``run_budgets`` plus the distribution of BP's posterior LLRs per iteration limit (qbp_mc_run_llr_hist).  Returns
+    GLOBAL ``(counters int64[K, 12], hist int64[K, 4, bins + 3], edges float64[bins + 1])``: the counters are
+    ``run_budgets``' digit for digit; ``hist[j, 2 * (BP did not converge) + true bit, c]`` counts, over all trials and
+    all n bits, the posterior values a decode with ``max_iter=budgets[j]`` returns, in column c -- 0 below
+    ``llr_range[0]``, 1 .. bins the bins of ``np.histogram(x, bins, range=llr_range)`` (``edges``), bins + 1 above
+    ``llr_range[1]``, bins + 2 NaN.  The lists of BP_per_Iteration.py:46-60 binned: ``llrs_per_iter[j]`` is
+    ``hist[j].sum(0)``, ``llrs_per_iter_after_OSD[j]`` is ``hist[j, 2] + hist[j, 3]``.  Sharded like ``run_budgets``;
+    counters and table are reduced in ONE all-reduce.  ValueError, before any GPU work, for what the library refuses
+    (``_lib.check_budgets``, ``_lib.check_llr_hist``).
+    ``runner(code, p, budgets, bins, llr_range, begin, end) -> (int64[K, 12], int64[K, 4, bins + 3])`` and
+    ``all_reduce`` are injection points for the CPU tests; by default the HIP library and torch.distributed."""
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
+    budgets = _lib.check_budgets(budgets)
+    bins, lo, hi = _lib.check_llr_hist(bins, *llr_range, len(budgets))
+    code = codes.load_code(code_name)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(code.Hx, device=device)
+        flat = _llr_hist_on_device(dec, code.Lx, code.distance, float(p), prior_of(p, code.n), budgets, bins, (lo, hi),
+                                   begin, end, draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping,
+                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
+    else:
+        flat = np.concatenate([np.asarray(a, np.int64).ravel()
+                               for a in runner(code, p, budgets, bins, (lo, hi), begin, end)])[None, :]
+        flat = all_reduce(flat) if all_reduce is not None else flat
+    return (*_split_llr_hist(flat, len(budgets), bins), _lib.llr_hist_edges(bins, lo, hi))
+
+
+def run_dem_llr_hist(H, L, probs, trials, budgets, bins, llr_range, *, prior=None, distance=0, draws=1, seed=0,
+                     variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
+                     osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None):
+    """``run_dem_budgets`` with the table of ``run_llr_hist``: GLOBAL ``(counters int64[K, 12], hist int64[K, 4, bins +
+    3], edges)`` for a matrix with a probability per column.  Arguments as ``run_dem`` and ``run_llr_hist``;
+    ``runner(H, L, probs, prior, budgets, bins, llr_range, begin, end) -> (int64[K, 12], int64[K, 4, bins + 3])``."""
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
+    budgets = _lib.check_budgets(budgets)
+    bins, lo, hi = _lib.check_llr_hist(bins, *llr_range, len(budgets))
+    L, probs, prior, n = _dem_args(H, L, probs, prior)
+    begin, end = shard_range(int(trials), rank, world)
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        flat = _llr_hist_on_device(dec, L, distance, probs, prior, budgets, bins, (lo, hi), begin, end, draws=draws,
+                                   seed=seed, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
+                                   flags=flags, world=world, device=device)
+    else:
+        flat = np.concatenate([np.asarray(a, np.int64).ravel()
+                               for a in runner(H, L, probs, prior, budgets, bins, (lo, hi), begin, end)])[None, :]
+        flat = all_reduce(flat) if all_reduce is not None else flat
+    return (*_split_llr_hist(flat, len(budgets), bins), _lib.llr_hist_edges(bins, lo, hi))
+
+
+def bp_per_iteration(code_names, p, budgets, trials, osd=True, llr_bins=None, llr_range=None, **kwargs):
     """The result dictionary of BP_per_Iteration.py:85-88: per code name ``logicalErrors``, ``degeneracies`` and
     ``OSD_invocations`` (rates per trial, one entry per iteration limit) and ``iterations`` (the limits).  One
-    ``run_budgets`` pass per code; ``kwargs`` go to it.  The script's per-limit LLR lists (``llrs_per_iter*``, its
-    violin plots) are not produced."""
+    ``run_budgets`` pass per code; ``kwargs`` go to it.
+
+    With ``llr_bins`` and ``llr_range=(lo, hi)`` the pass is ``run_llr_hist`` and every entry gains the script's
+    per-limit LLR lists (:46-60, :82-90, its violin plots) as histograms: ``llrs_per_iter_hist`` and
+    ``llrs_per_iter_after_OSD_hist`` (the posteriors of the trials BP left unconverged), int64[K, llr_bins + 3] each
+    with the columns of ``run_llr_hist``, and ``llr_edges``.  Without them the result is what it always was."""
+    if (llr_bins is None) != (llr_range is None):
+        raise ValueError("llr_bins and llr_range go together")
     results = {}
     for name in code_names:
-        table = run_budgets(name, p, trials, budgets, osd=osd, **kwargs)
+        if llr_bins is None:
+            table = run_budgets(name, p, trials, budgets, osd=osd, **kwargs)
+        else:
+            table, hist, edges = run_llr_hist(name, p, trials, budgets, llr_bins, llr_range, osd=osd, **kwargs)
         t = np.maximum(table[:, 0], 1).astype(np.float64)
         results[name] = {
             "logicalErrors": (table[:, 1] / t).tolist(),            # :76-79
@@ -522,7 +612,20 @@ def bp_per_iteration(code_names, p, budgets, trials, osd=True, **kwargs):
             "OSD_invocations": (table[:, 6] / t).tolist(),          # :58-64, :81 (trials BP left unconverged)
             "iterations": [int(b) for b in budgets],
         }
+        if llr_bins is not None:
+            results[name].update(llrs_per_iter_hist=hist.sum(axis=1), llrs_per_iter_after_OSD_hist=hist[:, 2] + hist[:, 3],
+                                 llr_edges=edges)
     return results
+
+
+def llr_distributions(code_name, p, trials, max_iter, bins, llr_range, **kwargs):
+    """The posterior-LLR distributions of rework/Alvarado.py:122, 159-162, split by the TRUE value of the bit:
+    ``{"true_0": int64[bins + 3], "true_1": int64[bins + 3], "edges": float64[bins + 1]}`` over all bits of ``trials``
+    decodes with ``max_iter`` (``run_llr_hist`` with one budget: rows 0 + 2 and 1 + 3; columns as there -- [1:bins + 1]
+    are ``np.histogram``'s counts of the script's ``llr_data[...]["true_0"]`` / ``["true_1"]`` lists).  ``kwargs`` go
+    to ``run_llr_hist``."""
+    _, hist, edges = run_llr_hist(code_name, p, trials, [int(max_iter)], bins, llr_range, **kwargs)
+    return {"true_0": hist[0, 0] + hist[0, 2], "true_1": hist[0, 1] + hist[0, 3], "edges": edges}
 
 
 def _split_spectrum(flat, n, max_iter):
@@ -830,6 +933,10 @@ def main(argv=None):
     ap.add_argument("--budgets", type=int, nargs="+", default=None,
                     help="a ladder of iteration limits decoded in ONE pass instead of --max-iter (one --p): a result "
                          "line per limit (run_budgets / run_dem_budgets)")
+    ap.add_argument("--llr-hist", nargs=3, default=None, metavar=("BINS", "LO", "HI"),
+                    help="with --budgets: also the histograms of BP's posterior LLRs per limit, by converged flag and "
+                         "true bit, over BINS bins of [LO, HI] plus below / above / NaN columns (run_llr_hist / "
+                         "run_dem_llr_hist); with --out the table goes to the .npz beside it")
     ap.add_argument("--spectrum", default=None, metavar="OUT.npz",
                     help="also collect the residual-weight spectra and the iteration histogram of every point "
                          "(run_spectrum / run_dem_spectrum) and write counters, weights, iterations to this .npz")
@@ -968,6 +1075,14 @@ def main(argv=None):
             ap.error(f"--budgets: {e}")
         if args.dem is None and len(args.p) != 1:
             ap.error("--budgets takes one --p")
+    if args.llr_hist is not None:
+        if args.budgets is None:
+            ap.error("--llr-hist needs --budgets")
+        try:
+            args.llr_hist = _lib.check_llr_hist(int(args.llr_hist[0]), float(args.llr_hist[1]), float(args.llr_hist[2]),
+                                                len(args.budgets))
+        except ValueError as e:
+            ap.error(f"--llr-hist: {e}")
     if args.spectrum is not None:
         if args.budgets is not None:
             ap.error("--spectrum does not combine with --budgets")
@@ -1132,7 +1247,19 @@ def main(argv=None):
         points = list(args.budgets)      # one row per iteration limit
         del common["max_iter"]
 
+        llr_tables = {}                  # table and edges of the last sweep (the timed one)
+
         def sweep(trials, ps, rank, world):          # (the whole ladder, also for the warm-up)
+            if args.llr_hist is not None:
+                bins, lo, hi = args.llr_hist
+                if dem_model is None:
+                    cnt, llr_tables["hist"], llr_tables["edges"] = run_llr_hist(
+                        args.code, args.p[0], trials, points, bins, (lo, hi), rank=rank, world=world, **common)
+                else:
+                    cnt, llr_tables["hist"], llr_tables["edges"] = run_dem_llr_hist(
+                        *dem_model, trials, points, bins, (lo, hi), distance=args.distance, rank=rank, world=world,
+                        **common)
+                return cnt
             if dem_model is None:
                 return run_budgets(args.code, args.p[0], trials, points, rank=rank, world=world, **common)
             return run_dem_budgets(*dem_model, trials, points, distance=args.distance, rank=rank, world=world, **common)
@@ -1225,6 +1352,14 @@ def main(argv=None):
                      p=np.asarray([np.nan if p is None else p for p in points], np.float64))
             print(f"spectra written to {args.spectrum}: weights {tables['weights'].shape}, "
                   f"iterations {tables['iterations'].shape}")
+        if args.llr_hist is not None:
+            h = llr_tables["hist"]
+            print(f"posterior-LLR histograms {h.shape}: {int(h.sum())} values, {int(h[:, :, 1:-2].sum())} inside "
+                  f"[{args.llr_hist[1]}, {args.llr_hist[2]}], {int(h[:, :, -1].sum())} NaN")
+            if args.out:
+                npz = os.path.splitext(args.out)[0] + ".npz"
+                np.savez(npz, counters=table, llr_hist=h, llr_edges=llr_tables["edges"], budgets=np.asarray(points))
+                print(f"LLR histograms written to {npz}")
         if args.out:
             with open(args.out, "w") as f:
                 model = {"code": args.code} if dem_model is None else {"dem": model_name, "distance": args.distance}

@@ -42,6 +42,10 @@ UNITS += [("qbp_tu_window.hip", [])]
 UNITS += [("qbp_tu_lsd.hip", [])]
 # BP with a prior per record (qbp_decode_batch_cond): bp_cond_kernel<variant>, and the glue kernels of qbp_css_*
 UNITS += [("qbp_tu_cond.hip", [])]
+# Monte-Carlo with posterior-LLR histograms per iteration budget (qbp_mc_run_llr_hist): bp_fused_llrhist_kernel,
+# bp_generic_llrhist_kernel (last, so that the rows before them are the earlier tables')
+UNITS += [("qbp_tu_fused.hip", ["-DQBP_LLRHIST_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_LLRHIST_TU", f"-DQBP_GENERIC_MEM={i}"])
+                                                         for i in range(3)]
 
 
 def demangle(sym):
