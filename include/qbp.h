@@ -105,9 +105,12 @@ enum {
                                  stage (any variant, flooding or QBP_FLAG_LAYERED) does not converge on go through BP
                                  guided decimation (qbp_gd_decode_batch, as configured by qbp_gd_configure), then to
                                  classification */
-    QBP_FLAG_LSD = 4096u      /* the same entries only: those trials go through localized statistics decoding
+    QBP_FLAG_LSD = 4096u,     /* the same entries only: those trials go through localized statistics decoding
                                  (qbp_lsd_batch, as configured by qbp_lsd_configure) on the first stage's posterior and
                                  hard decision, then to classification */
+    QBP_FLAG_QUANT = 8192u    /* qbp_mc_run, _device, _errors, _probs(_device), _weight(_device) only: the first stage is
+                                 fixed-point min-sum (qbp_quant_decode_batch, as configured by qbp_quant_configure below)
+                                 instead of double-precision BP */
 };
 /* The order w of QBP_FLAG_OSD_CS / QBP_FLAG_OSD_E, in bits 16..23 of the flags (a macro: the enum above holds
  * single bits only).  CS: 1 <= w <= 64, E: 1 <= w <= 12. */
@@ -474,6 +477,62 @@ int qbp_relay_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, con
 int qbp_layered_plan(const int32_t* row_ptr, const int32_t* col_idx, int32_t m, int32_t n, const int32_t* order_in,
                      int32_t* order_out, int32_t* level_ptr, int32_t* n_levels);
 int qbp_layered_configure(qbp_handle* h, const int32_t* order);
+
+/*
+ * Fixed-point min-sum BP: messages of q bits, saturating integer arithmetic, what an FPGA or ASIC decoder runs.  The
+ * reference has no such decoder; the rules below are this build's specification (tests/quant_oracle.py states them in
+ * numpy, and the kernel reproduces that statement bit for bit -- integer sums are exact in any order).
+ *
+ * qbp_quant_configure stores, per handle: `bits` q, 2 <= q <= 16, with M = 2^(q-1) - 1; `scale`, a finite double > 0,
+ * integer units per unit of LLR; the normalisation alpha_num / 2^alpha_shift, 0 <= alpha_shift <= 15 and
+ * 1 <= alpha_num <= 2^alpha_shift; the offset beta, 0 <= beta <= M.  QBP_E_INVALID: a parameter out of range.
+ * QBP_E_UNSUPPORTED: a column of more than 32767 entries (|V| stays below 2^31), or a matrix whose single-record state
+ * -- E messages of 1 byte (q <= 8) or 2, the posterior and the quantised prior as int32 -- does not fit the 160 KiB of
+ * LDS of one workgroup.  A later call replaces the configuration.
+ *
+ * One record (syndrome s, double prior [n], max_iter >= 1):
+ *   1. P[v] = 0 if prior[v] is NaN, else clamp(rint(prior[v] * scale), -M, M): one IEEE double multiply, rint rounds
+ *      half to even, +-inf clamps to +-M;
+ *   2. Q[c,v] = P[v] on every edge;
+ *   3. iteration t = 0 .. max_iter - 1, check step, for every edge (c,v):
+ *        neg  = s_c XOR (parity of the number of u != v in row c with Q[c,u] < 0; zero counts as positive),
+ *        mag  = min over u != v of |Q[c,u]|, M if there is no such u (a row of weight 1),
+ *        mag' = max(((mag * alpha_num) >> alpha_shift) - beta, 0),
+ *        R[c,v] = neg ? -mag' : mag';
+ *   4. variable step: V[v] = P[v] + sum over c of R[c,v], an exact int32 without saturation;
+ *      Q[c,v] = clamp(V[v] - R[c,v], -M, M);
+ *   5. hard = V < 0; H hard == s: converged at iteration t;
+ *   6. outputs: hard and posterior_q = V (int32) of the first converged iteration, else of the last; converged; iters
+ *      (0-based, max_iter - 1 if none) as qbp_decode_batch; llr[v] = (double)V[v], an exact conversion without a
+ *      division: the LLR in units of 1 / scale, which is what OSD and LSD sort by and add up.  Isolated variables keep
+ *      V = P;
+ *   7. QBP_FLAG_FORCE_FULL runs all iterations and keeps the outputs of the first converged one.
+ *
+ * qbp_quant_decode_batch(_device): B records by these rules (bp_quant_kernel: one workgroup decodes several records at
+ * once, messages as int8 / int16 and V as int32 in LDS, no FP64 inside the iteration; QBP_OPT_QUANT_SLOTS).  hard is
+ * required; converged, iters, posterior_q [B][n] and llr [B][n] may be null.  flags: QBP_FLAG_FORCE_FULL; QBP_FLAG_FAST_MATH
+ * is ignored; every other bit is QBP_E_INVALID.  QBP_E_INVALID: no configuration, a NaN prior at the host entry (the
+ * device entry applies rule 1).  Outputs do not depend on B, the grid, the slots or the stream.
+ *
+ * QBP_FLAG_QUANT in qbp_mc_run(_device), qbp_mc_run_errors, qbp_mc_run_probs(_device), qbp_mc_run_weight(_device): the
+ * first stage on stored errors -- the caller's, or the errors qbp_mc_sample_errors[_probs|_weight] return, drawn chunk by
+ * chunk (QBP_OPT_MC_WEIGHT_CHUNK); counters do not depend on the chunk or on how a trial range is split.  The `prior`
+ * argument is quantised by rule 1 (per-column priors of a detector error model included).  QBP_FLAG_OSD0, the order-w
+ * OSD bits, QBP_FLAG_RELAY, QBP_FLAG_GD and QBP_FLAG_LSD act on its failure records unchanged, with llr = (double)V and
+ * the hard decision of the last iteration (Relay-BP and BPGD start again from the double `prior`).  alpha, damping and
+ * clip_llr of the call are ignored, as are QBP_FLAG_FAST_MATH and QBP_FLAG_FORCE_FULL (it cannot change a count).
+ * QBP_E_INVALID: the flag without a configuration, with QBP_FLAG_LAYERED, with a variant other than QBP_MIN_SUM, with
+ * any column-sum order flag, or a NaN prior at a host entry.  QBP_E_UNSUPPORTED: in qbp_decode_batch(_device),
+ * qbp_decode_batch_cond, qbp_mc_run_budgets, qbp_mc_run_spectrum, qbp_mc_run_errors_spectrum, the qbp_mc_run*_llr_hist
+ * entries, qbp_decode_shots, qbp_check_messages, and the qbp_window_* and qbp_css_* entries.
+ */
+int qbp_quant_configure(qbp_handle* h, int32_t bits, double scale, int32_t alpha_num, int32_t alpha_shift, int32_t beta);
+int qbp_quant_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, int32_t max_iter,
+                           uint32_t flags, uint8_t* hard, uint8_t* converged, int32_t* iters, int32_t* posterior_q,
+                           double* llr);
+int qbp_quant_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                  int32_t max_iter, uint32_t flags, uint8_t* d_hard, uint8_t* d_converged,
+                                  int32_t* d_iters, int32_t* d_posterior_q, double* d_llr, void* stream);
 
 /*
  * BP guided decimation (BPGD; Yao, Gokduman, Pfister, "Belief propagation decoding of quantum LDPC codes with guided
@@ -1081,6 +1140,8 @@ enum {
     QBP_OPT_DEBUG_THROW = 99,    /* tests (null handle allowed): raise inside the entry point -- 1 std::bad_alloc
                                     (-> QBP_E_NOMEM), 2 std::runtime_error, 3 a non-standard exception
                                     (-> QBP_E_INVALID): no exception crosses the ABI */
+    QBP_OPT_QUANT_SLOTS = 121,   /* fixed-point min-sum: records decoded at once by one workgroup (0 = auto, at most 32;
+                                    fewer where the LDS holds fewer).  Results do not depend on it (tests force 1 and 3) */
     QBP_OPT_LLR_HIST_CHUNK = 120, /* tests: qbp_mc_run_llr_hist* launches at most this many trials at a time (0 = default,
                                     the most that keeps the 32-bit counts of a workgroup below 2^32: (2^32 - 1) / n; larger
                                     values mean that too).  Results do not depend on it.  Not 20: tests/test_lsd_large_cpu.py
@@ -1088,7 +1149,8 @@ enum {
     QBP_INFO_M = 100, QBP_INFO_N = 101, QBP_INFO_EDGES = 102, QBP_INFO_MAX_ROW_DEG = 103,
     QBP_INFO_MAX_COL_DEG = 104, QBP_INFO_KERNEL_KIND = 105, /* 1 on-chip, 2 general-H, 3 streaming */
     QBP_INFO_THREADS = 106, QBP_INFO_LDS_BYTES = 107, QBP_INFO_GRID = 108, QBP_INFO_NUM_CU = 109,
-    QBP_INFO_LAST_KERNEL = 110, /* kernel of the last decode launch: 1 on-chip, 2 general-H, 3 streaming, 4 layered */
+    QBP_INFO_LAST_KERNEL = 110, /* kernel of the last decode launch: 1 on-chip, 2 general-H, 3 streaming, 4 layered,
+                                   5 fixed-point min-sum */
     QBP_INFO_ONE_BARRIER = 111  /* 1 if the last on-chip launch geometry used the one-barrier forced kernel */
 };
 int qbp_set_option(qbp_handle* h, int32_t option, int64_t value);

@@ -32,6 +32,7 @@ FLAG_RELAY = 512             # Monte-Carlo calls: Relay-BP (qbp_relay_configure)
 FLAG_LAYERED = 1024          # the layered (check-serial) schedule instead of flooding (qbp_layered_configure)
 FLAG_GD = 2048               # Monte-Carlo calls: BP guided decimation (qbp_gd_configure) on the trials BP leaves
 FLAG_LSD = 4096              # Monte-Carlo calls: localized statistics decoding (qbp_lsd_configure) on those trials
+FLAG_QUANT = 8192            # Monte-Carlo calls: fixed-point min-sum (qbp_quant_configure) as the first stage
 OSD_ORDER_SHIFT = 16         # QBP_OSD_ORDER_FLAGS(w) = w << 16
 OSD_MAX_ORDER = {"cs": 64, "e": 12}
 MC_OSD_MAX_TRIALS = 1 << 20
@@ -53,6 +54,7 @@ OPT_LAYERED_SLOTS = 15       # layered BP: records decoded at once by one workgr
 # Relay-BP, layered BP, BP guided decimation: where a record's messages live -- 0 LDS only, 1 global workspace, 2 automatic
 OPT_RELAY_MEM, OPT_LAYERED_MEM, OPT_GD_MEM = 16, 17, 18
 OPT_LSD_MEM = 19             # localized statistics decoding: where a record's rows live, the same three values
+OPT_QUANT_SLOTS = 121        # fixed-point min-sum: records decoded at once by one workgroup (0 = auto)
 OPT_LLR_HIST_CHUNK = 120     # qbp_mc_run_llr_hist: trials per launch (0 = default: the most 32-bit counts allow)
 # family: (the option, ``large=`` -> its value, the accepted spellings in words).  ``relay.RelayConfig.large``,
 # ``Decoder.layered_configure(large=)`` and ``gd.GDConfig.large`` spell the same three values differently (README.md);
@@ -165,6 +167,10 @@ SIGNATURES = {
     "qbp_lsd_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
+    "qbp_quant_configure": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32]),
+    "qbp_quant_decode_batch": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_quant_decode_batch_device": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_uint32, _VP, _VP, _VP, _VP, _VP,
+                                                _VP]),
     "qbp_window_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP,
                                   _VP]),
     "qbp_window_create": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, C.c_int32, C.c_int32, C.c_int32,
@@ -317,10 +323,11 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name, None)
-            if (fn is None and (name.startswith("qbp_window_") or name == "qbp_plan_r_layout")
+            if (fn is None and (name.startswith(("qbp_window_", "qbp_quant_")) or name == "qbp_plan_r_layout")
                     and LIB_PATH != _DEFAULT_LIB_PATH):
                 # a QBP_LIB_PATH build from before sliding-window decoding (tools/bench_window.py times its
-                # whole-matrix path) or from before the variable-major message layout (A/B runs against it):
+                # whole-matrix path), from before the variable-major message layout (A/B runs against it) or from
+                # before fixed-point min-sum (tools/bench_quant.py times its double-precision rows on it):
                 # everything else works, such a call raises QbpError
                 setattr(lib, name, _missing(name))
                 continue
@@ -709,6 +716,38 @@ class Decoder:
                                        float(clip_llr), int(flags), hard.ctypes.data,
                                        conv.ctypes.data, iters.ctypes.data, _ptr(llr)))
         return hard, conv.astype(bool), iters, llr
+
+    @_locked
+    def quant_configure(self, cfg):
+        """Store a fixed-point min-sum configuration (``quant.QuantConfig``) in the handle (qbp_quant_configure)."""
+        num, shift = cfg.alpha
+        _check(load().qbp_quant_configure(self._h, int(cfg.bits), float(cfg.scale), int(num), int(shift), int(cfg.beta)))
+
+    @_locked
+    def quant_decode(self, syndromes, prior, max_iter=50, flags=0, want_posterior=True, want_llr=True):
+        """qbp_quant_decode_batch in the stored configuration -> (hard, converged, iters, posterior_q int32[B, n] or
+        None, llr float64[B, n] = posterior_q as doubles, or None)."""
+        syn = np.ascontiguousarray(syndromes, np.uint8)
+        if syn.ndim != 2 or syn.shape[1] != self.m:
+            raise ValueError(f"syndromes must have shape (B, {self.m}), got {syn.shape}")
+        pr = np.ascontiguousarray(prior, np.float64)
+        if pr.shape != (self.n,):
+            raise ValueError(f"initialBelief must have shape ({self.n},), got {pr.shape}")
+        B = syn.shape[0]
+        hard = np.empty((B, self.n), np.uint8)
+        conv = np.empty(B, np.uint8)
+        iters = np.empty(B, np.int32)
+        post = np.empty((B, self.n), np.int32) if want_posterior else None
+        llr = np.empty((B, self.n), np.float64) if want_llr else None
+        _check(load().qbp_quant_decode_batch(self._h, syn.ctypes.data, pr.ctypes.data, B, int(max_iter), int(flags),
+                                             hard.ctypes.data, conv.ctypes.data, iters.ctypes.data, _ptr(post), _ptr(llr)))
+        return hard, conv.astype(bool), iters, post, llr
+
+    def quant_decode_device(self, d_syndromes, d_prior, B, max_iter, flags, d_hard, d_converged, d_iters, d_posterior_q,
+                            d_llr, stream=0):
+        _check(load().qbp_quant_decode_batch_device(
+            self._h, d_syndromes, d_prior, int(B), int(max_iter), int(flags), d_hard or None, d_converged or None,
+            d_iters or None, d_posterior_q or None, d_llr or None, stream or None))
 
     # ---- device buffers (raw pointers, e.g. torch tensors' data_ptr()) ----------------------
     def decode_device(self, d_syndromes, d_prior, B, max_iter, variant, alpha, damping, clip_llr,

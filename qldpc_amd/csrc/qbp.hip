@@ -27,6 +27,7 @@
 #include "qbp_lsd.hpp"
 #include "qbp_lsd_large.hpp"
 #include "qbp_layered.hpp"
+#include "qbp_quant.hpp"
 #include "qbp_window.hpp"
 #include "qbp_launch.hpp"
 #include "qbp_msg_mem.hpp"
@@ -412,6 +413,12 @@ struct qbp_handle {
     int opt_layered_slots = 0;      // QBP_OPT_LAYERED_SLOTS (0 = auto)
     DevBuf<int32_t> d_layered_order, d_layered_level_ptr;
     DevBuf<double> d_layered_wsR;   // layered BP, large build: [grid][S][E] messages
+    // fixed-point min-sum (qbp_quant_configure); scratch of the host-pointer entry
+    bool quant_ready = false;
+    int quant_bits = 0, quant_num = 1, quant_shift = 0, quant_beta = 0;
+    double quant_scale = 1.0;
+    int opt_quant_slots = 0;        // QBP_OPT_QUANT_SLOTS (0 = auto)
+    DevBuf<int32_t> d_quant_post;
 };
 
 namespace {
@@ -1367,6 +1374,9 @@ static int fused_launch(qbp_handle* h, const BpCall& c, hipStream_t s)
 // (layered BP, defined with its configuration further down)
 static int check_layered_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry);
 static int layered_launch(qbp_handle* h, const BpCall& c, hipStream_t s);
+// (fixed-point min-sum, likewise)
+static int check_quant_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry);
+static int quant_launch(qbp_handle* h, const BpCall& c, int32_t* posterior_q, hipStream_t s);
 
 int qbp_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior,
                             int64_t B, int32_t max_iter, int32_t variant, double alpha,
@@ -1376,6 +1386,7 @@ try {
     int rc = check_decode_args(h, B, max_iter, variant);
     if (rc) return rc;
     if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
+    if ((rc = check_quant_flags(h, flags, variant, true)) != QBP_OK) return rc;
     if (B == 0) return QBP_OK;
     if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
     if (B > (int64_t)1 << 40) return fail(QBP_E_INVALID, "B too large");
@@ -1489,6 +1500,7 @@ try {
         if ((rc = check_layered_flags(h, flags, variant, false)) != QBP_OK) return rc;
         if ((rc = check_prior(h->n, prior, true)) != QBP_OK) return rc;
     }
+    if ((rc = check_quant_flags(h, flags, variant, true)) != QBP_OK) return rc;
     if (flags & QBP_FLAG_DENSE_F_COLSUM_ITER0) {     // (the shortcut is judged on the host copy of the priors)
         int mode = 0;
         unsigned fl = flags;
@@ -1592,6 +1604,7 @@ try {
     int rc = check_decode_args(h, B, iteration + 1, variant);
     if (rc) return rc;
     if ((rc = check_layered_flags(h, flags, variant, true)) != QBP_OK) return rc;
+    if ((rc = check_quant_flags(h, flags, variant, true)) != QBP_OK) return rc;
     int col_mode = 0;                    // (only the column-sum order bits of `flags` are honoured)
     flags &= QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0 | QBP_FLAG_PAIRWISE_COLSUM;
     if (prior) { rc = resolve_column_order(h, flags, prior, &col_mode); if (rc) return rc; }
@@ -2213,6 +2226,155 @@ try {
 }
 QBP_ABI_CATCH
 
+// ---- fixed-point min-sum (qbp_quant.hpp) -------------------------------------------------------------------------
+// Slots per workgroup: about four work items per thread in the variable step, at most QUANT_MAX_SLOTS and what keeps
+// two workgroups' LDS on a CU; one slot always (qbp_quant_configure refuses what does not fit with one).
+static int quant_slots(const qbp_handle* h, long long B)
+{
+    const bool wide = h->quant_bits > 8;
+    int S = h->opt_quant_slots;
+    if (S <= 0) {
+        S = std::max(1, std::min(qbp::QUANT_MAX_SLOTS, 4 * qbp::QUANT_THREADS / std::max(1, h->n)));
+        while (S > 1 && qbp::quant_lds_bytes(h->m, h->n, h->E, S, wide) > (size_t)80 * 1024) --S;
+    }
+    while (S > 1 && qbp::quant_lds_bytes(h->m, h->n, h->E, S, wide) > (size_t)160 * 1024) --S;
+    return (int)std::max<long long>(1, std::min<long long>(S, B));
+}
+
+// QBP_FLAG_QUANT of a call (host only, before any GPU work).  `other_entry`: the entries without a fixed-point build
+// (double-precision batch decodes, budgets, spectra, histograms, recorded shots, message dumps).
+static int check_quant_flags(const qbp_handle* h, uint32_t flags, int variant, bool other_entry)
+{
+    if (!(flags & QBP_FLAG_QUANT)) return QBP_OK;
+    if (other_entry)
+        return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_QUANT is a first stage of qbp_mc_run, _errors, _probs and _weight only "
+                                       "(batches: qbp_quant_decode_batch)");
+    if (!h->quant_ready) return fail(QBP_E_INVALID, "QBP_FLAG_QUANT without qbp_quant_configure");
+    if (flags & QBP_FLAG_LAYERED) return fail(QBP_E_INVALID, "QBP_FLAG_QUANT with QBP_FLAG_LAYERED: one first stage per call");
+    if (variant != QBP_MIN_SUM) return fail(QBP_E_INVALID, "QBP_FLAG_QUANT with variant %d: fixed-point BP is QBP_MIN_SUM", variant);
+    if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0))
+        return fail(QBP_E_INVALID, "QBP_FLAG_QUANT with a column-sum order flag: integer sums have no order");
+    return QBP_OK;
+}
+
+// One launch of bp_quant_kernel (device pointers): the batch build, or (c.mc) the Monte-Carlo build on stored errors
+static int quant_launch(qbp_handle* h, const BpCall& c, int32_t* posterior_q, hipStream_t s)
+{
+    constexpr long long MAX_LAUNCH = (long long)1 << 30;       // (records are handed out through a 32-bit counter)
+    if (c.B > MAX_LAUNCH)
+        return fail(QBP_E_UNSUPPORTED, "fixed-point BP decodes at most 2^30 syndromes per call (got %lld)", c.B);
+    const bool wide = h->quant_bits > 8;
+    const int S = quant_slots(h, c.B);
+    const size_t lds = qbp::quant_lds_bytes(h->m, h->n, h->E, S, wide);
+    // resident workgroups per CU: the LDS, and eight wavefronts per SIMD
+    int per_cu = (int)std::max<size_t>(1, std::min<size_t>(8, ((size_t)160 * 1024) / lds));
+    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
+    const long long groups = (c.B + S - 1) / S;
+    const int grid = (int)std::max<long long>(1, std::min<long long>(groups, (long long)h->num_cu * per_cu));
+    HIP_TRY(hipMemsetAsync(h->d_work_counter.p, 0, sizeof(unsigned long long), s));
+    qbp::QuantParams P{};
+    P.m = h->m; P.n = h->n; P.E = h->E; P.S = S;
+    P.row_ptr = h->d_row_ptr.p; P.col_idx = h->d_col_idx.p; P.col_ptr = h->d_col_ptr.p; P.col_edge = h->d_col_edge.p;
+    P.prior = c.prior; P.work_counter = reinterpret_cast<unsigned*>(h->d_work_counter.p);
+    P.max_iter = c.max_iter; P.flags = (c.flags & QBP_FLAG_FORCE_FULL) ? qbp::QUANT_FORCE_FULL : 0u;
+    P.M = (1 << (h->quant_bits - 1)) - 1; P.scale = h->quant_scale;
+    P.alpha_num = h->quant_num; P.alpha_shift = h->quant_shift; P.beta = h->quant_beta; P.B = c.B;
+    P.syndromes = c.syndromes; P.hard = c.hard; P.converged = c.converged; P.iters = c.iters;
+    P.posterior_q = posterior_q; P.llr = c.llr;
+    if (c.mc) {
+        P.errors_in = c.mc->errors_in; P.lx_cols = c.mc->lx_cols; P.half_distance = c.mc->half_distance;
+        P.counters = c.mc->counters;
+        P.fail_list = c.mc->fail_list; P.fail_count = c.mc->fail_count; P.fail_syn = c.mc->fail_syn;
+        P.fail_hard = c.mc->fail_hard; P.fail_err = c.mc->fail_err; P.fail_llr = c.mc->fail_llr;
+    }
+    h->last_threads = qbp::QUANT_THREADS; h->last_lds = (int)lds; h->last_grid = grid; h->last_kernel = 5;
+    HIP_TRY(qbp::launch_quant(c.mc != nullptr, wide, P, grid, lds, s));
+    return QBP_OK;
+}
+
+int qbp_quant_configure(qbp_handle* h, int32_t bits, double scale, int32_t alpha_num, int32_t alpha_shift, int32_t beta)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (bits < 2 || bits > 16) return fail(QBP_E_INVALID, "bits = %d out of [2, 16]", bits);
+    const int M = (1 << (bits - 1)) - 1;
+    if (!std::isfinite(scale) || !(scale > 0.0)) return fail(QBP_E_INVALID, "scale = %g must be finite and > 0", scale);
+    if (alpha_shift < 0 || alpha_shift > 15) return fail(QBP_E_INVALID, "alpha_shift = %d out of [0, 15]", alpha_shift);
+    if (alpha_num < 1 || alpha_num > (1 << alpha_shift))
+        return fail(QBP_E_INVALID, "alpha_num = %d out of [1, 2^%d]", alpha_num, alpha_shift);
+    if (beta < 0 || beta > M) return fail(QBP_E_INVALID, "beta = %d out of [0, %d]", beta, M);
+    if (h->max_col_deg > 32767)
+        return fail(QBP_E_UNSUPPORTED, "fixed-point BP sums a column in int32: columns of at most 32767 entries (got %d)",
+                    h->max_col_deg);
+    const size_t lds = qbp::quant_lds_bytes(h->m, h->n, h->E, 1, bits > 8);
+    if (lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "fixed-point BP keeps the messages, the posterior and the prior of a record in LDS: "
+                                       "%d x %d with %d entries at %d bits needs %zu B (limit 160 KiB)", h->m, h->n, h->E,
+                    bits, lds);
+    h->quant_bits = bits; h->quant_scale = scale; h->quant_num = alpha_num; h->quant_shift = alpha_shift;
+    h->quant_beta = beta;
+    h->quant_ready = true;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// Everything qbp_quant_decode_batch refuses apart from null pointers and NaN priors: host only, before any GPU work.
+static int quant_check_batch(qbp_handle* h, int64_t B, int32_t max_iter, uint32_t flags)
+{
+    const int rc = check_decode_args(h, B, max_iter, QBP_MIN_SUM);
+    if (rc) return rc;
+    if (!h->quant_ready) return fail(QBP_E_INVALID, "qbp_quant_decode_batch without qbp_quant_configure");
+    if (flags & ~(uint32_t)(QBP_FLAG_FORCE_FULL | QBP_FLAG_FAST_MATH))
+        return fail(QBP_E_INVALID, "flags 0x%x: qbp_quant_decode_batch takes QBP_FLAG_FORCE_FULL only", flags);
+    return QBP_OK;
+}
+
+int qbp_quant_decode_batch_device(qbp_handle* h, const uint8_t* d_syndromes, const double* d_prior, int64_t B,
+                                  int32_t max_iter, uint32_t flags, uint8_t* d_hard, uint8_t* d_converged,
+                                  int32_t* d_iters, int32_t* d_posterior_q, double* d_llr, void* stream)
+try {
+    const int rc = quant_check_batch(h, B, max_iter, flags);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!d_syndromes || !d_prior) return fail(QBP_E_INVALID, "null input pointer");
+    if (!d_hard) return fail(QBP_E_INVALID, "hard is null");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    BpCall c;
+    c.syndromes = d_syndromes; c.prior = d_prior; c.B = B; c.max_iter = max_iter; c.variant = QBP_MIN_SUM;
+    c.flags = flags & QBP_FLAG_FORCE_FULL;
+    c.hard = d_hard; c.converged = d_converged; c.iters = d_iters; c.llr = d_llr;
+    return quant_launch(h, c, d_posterior_q, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_quant_decode_batch(qbp_handle* h, const uint8_t* syndromes, const double* prior, int64_t B, int32_t max_iter,
+                           uint32_t flags, uint8_t* hard, uint8_t* converged, int32_t* iters, int32_t* posterior_q,
+                           double* llr)
+try {
+    int rc = quant_check_batch(h, B, max_iter, flags);
+    if (rc) return rc;
+    if (B == 0) return QBP_OK;
+    if (!syndromes || !prior) return fail(QBP_E_INVALID, "null input pointer");
+    if (!hard) return fail(QBP_E_INVALID, "hard is null");
+    if ((rc = check_prior(h->n, prior, false)) != QBP_OK) return rc;
+    if (B > (int64_t)1 << 30) return fail(QBP_E_UNSUPPORTED, "fixed-point BP decodes at most 2^30 syndromes per call");
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    const size_t m = h->m, n = h->n, b = (size_t)B;
+    HostStage st(h->stream);
+    const uint8_t* d_syn = st.in(h->d_syn, syndromes, b * m);
+    const double* d_prior = st.in(h->d_prior, prior, n);
+    uint8_t* d_hard = st.out(h->d_hard, hard, b * n);
+    uint8_t* d_conv = st.out(h->d_conv, converged, b);
+    int32_t* d_iters = st.out(h->d_iters, iters, b);
+    int32_t* d_post = st.out(h->d_quant_post, posterior_q, b * n);
+    double* d_llr = st.out(h->d_llr, llr, b * n);
+    if (st.failed()) return st.error();
+    return st.finish(qbp_quant_decode_batch_device(h, d_syn, d_prior, B, max_iter, flags, d_hard, d_conv, d_iters, d_post,
+                                                   d_llr, h->stream));
+}
+QBP_ABI_CATCH
+
 // ---- Relay-BP (qbp_relay.hpp) ------------------------------------------------------------------------------------
 // Dynamic LDS of a workgroup in the build `large`
 static size_t relay_build_lds(const qbp_handle* h, bool large, bool records)
@@ -2776,10 +2938,12 @@ struct McCall {
     size_t rows() const { return ladder() ? (size_t)n_budgets : 1; }          // counter rows = failure-record planes
     int32_t last_iter() const { return ladder() ? budgets[n_budgets - 1] : dec.max_iter; }
     size_t llr_cells() const { return out == LLRHIST ? (size_t)QBP_LLR_HIST_WORDS(n_budgets, llr_bins) : 0; }
-    // sampled trials that no BP kernel draws itself: fixed weight, and the layered kernel, which decodes stored errors only
+    // sampled trials that no BP kernel draws itself: fixed weight, and the layered and fixed-point kernels, which decode
+    // stored errors only
     bool chunked() const
     {
-        return errors.kind == McErrors::WEIGHT || (errors.kind != McErrors::STORED && (dec.flags & QBP_FLAG_LAYERED));
+        return errors.kind == McErrors::WEIGHT ||
+               (errors.kind != McErrors::STORED && (dec.flags & (QBP_FLAG_LAYERED | QBP_FLAG_QUANT)));
     }
 };
 
@@ -2840,6 +3004,7 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
     if ((rc = check_gd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_lsd_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
+    if ((rc = check_quant_flags(h, c.dec.flags, c.dec.variant, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
     if (host_prior && (rc = check_prior(h->n, host_prior, (c.dec.flags & QBP_FLAG_LAYERED) != 0)) != QBP_OK) return rc;
     int osd_method = 0, osd_order = 0;
     if ((rc = parse_osd_flags(h, c.dec.flags & ~SECOND_BP_BITS, true, &osd_method, &osd_order)) != QBP_OK) return rc;
@@ -2921,7 +3086,10 @@ static int mc_launch(qbp_handle* h, const McCall& c, hipStream_t s)
     // (likewise the iteration histogram of qbp_mc_run_spectrum)
     const bool hist_fits = !spectrum || fused_lds_bytes(h->dc, h->m, h->n, 1, h->r_stride, false, false, qbp::NUM_COUNTERS,
                                                         max_iter + 1) <= 160 * 1024;
-    if (layered) {
+    if (flags & QBP_FLAG_QUANT) {
+        b.flags = 0;                 // (likewise; alpha, damping and the clip of the call are not read)
+        rc = quant_launch(h, b, nullptr, s);
+    } else if (layered) {
         b.flags = 0;                 // (forced iterations cannot change a count: the kernel's Monte-Carlo build exits early)
         h->last_kernel = 4;
         rc = layered_launch(h, b, s);
@@ -3329,6 +3497,7 @@ static int check_shots_args(qbp_handle* h, const uint8_t* Lx, int32_t k, const u
     if ((rc = check_gd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_lsd_flags(h, flags, true)) != QBP_OK) return rc;
     if ((rc = check_layered_flags(h, flags, 0, true)) != QBP_OK) return rc;
+    if ((rc = check_quant_flags(h, flags, 0, true)) != QBP_OK) return rc;
     if (host_prior && (rc = check_prior(h->n, host_prior, false)) != QBP_OK) return rc;
     rc = parse_osd_flags(h, flags, true, osd_method, osd_order);
     if (rc) return rc;
@@ -3492,6 +3661,9 @@ try {
         case QBP_OPT_LAYERED_SLOTS:
             if (value < 0 || value > qbp::LAYERED_MAX_SLOTS) return fail(QBP_E_INVALID, "layered slots out of [0, %d]", qbp::LAYERED_MAX_SLOTS);
             h->opt_layered_slots = (int)value; return QBP_OK;
+        case QBP_OPT_QUANT_SLOTS:
+            if (value < 0 || value > qbp::QUANT_MAX_SLOTS) return fail(QBP_E_INVALID, "fixed-point slots out of [0, %d]", qbp::QUANT_MAX_SLOTS);
+            h->opt_quant_slots = (int)value; return QBP_OK;
         case QBP_OPT_LAYERED_MEM:
         case QBP_OPT_RELAY_MEM:
         case QBP_OPT_GD_MEM:
@@ -3782,6 +3954,7 @@ static int window_check_call(qbp_window* w, int64_t B, int32_t max_iter, int32_t
 {
     if (!w) return fail(QBP_E_INVALID, "null window decoder");
     if (flags & QBP_FLAG_LSD) return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_LSD is not available in a window call");
+    if (flags & QBP_FLAG_QUANT) return fail(QBP_E_UNSUPPORTED, "QBP_FLAG_QUANT is not available in a window call");
     if (flags & ~(QBP_FLAG_FORCE_FULL | QBP_FLAG_OSD0 | OSD_ALL_BITS))
         return fail(QBP_E_INVALID, "flags 0x%x: a window call takes QBP_FLAG_FORCE_FULL and the OSD bits only", flags);
     for (qbp_handle* h : w->sub) {
@@ -4083,7 +4256,7 @@ static int cond_check(qbp_handle* h, long long B, int max_iter, int variant, uin
     if (variant == QBP_DAMPED_SP)
         return fail(QBP_E_UNSUPPORTED, "BP with a prior per record runs QBP_SUM_PRODUCT or QBP_MIN_SUM, not QBP_DAMPED_SP");
     if (flags & (QBP_FLAG_PAIRWISE_COLSUM | QBP_FLAG_DENSE_F_COLSUM | QBP_FLAG_DENSE_F_COLSUM_ITER0 | QBP_FLAG_LAYERED |
-                 QBP_FLAG_FAST_MATH | SECOND_BP_BITS))
+                 QBP_FLAG_FAST_MATH | SECOND_BP_BITS | QBP_FLAG_QUANT))
         return fail(QBP_E_UNSUPPORTED, "flags 0x%x: BP with a prior per record has the flooding schedule, ascending column "
                                        "sums and numpy's functions only, and no second stage", flags);
     if (flags & ~(uint32_t)QBP_FLAG_FORCE_FULL) return fail(QBP_E_INVALID, "flags 0x%x: unknown bits", flags);
@@ -4188,9 +4361,9 @@ struct CssCall {
 static int css_check(qbp_css* css, int64_t B, int32_t max_iter, int32_t variant, uint32_t flags, int* method, int* order)
 {
     if (!css) return fail(QBP_E_INVALID, "null CSS decoder");
-    if (flags & (QBP_FLAG_LAYERED | SECOND_BP_BITS))
-        return fail(QBP_E_UNSUPPORTED, "flags 0x%x: Relay-BP, BP guided decimation, LSD and the layered schedule are not "
-                                       "available as a stage of the CSS decoder", flags);
+    if (flags & (QBP_FLAG_LAYERED | SECOND_BP_BITS | QBP_FLAG_QUANT))
+        return fail(QBP_E_UNSUPPORTED, "flags 0x%x: Relay-BP, BP guided decimation, LSD, the layered schedule and "
+                                       "fixed-point BP are not available as a stage of the CSS decoder", flags);
     int rc = cond_check(css->hb, B, max_iter, variant, flags & ~(QBP_FLAG_OSD0 | OSD_ALL_BITS));
     if (rc) return rc;
     // (what stage A's qbp_decode_batch_device would refuse: its argument check -- it has none for alpha, damping or the

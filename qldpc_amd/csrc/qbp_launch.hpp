@@ -18,6 +18,7 @@ struct OsdBigWorkspace;
 struct OsdOrderBigArgs;
 struct RelayParams;
 struct LayeredParams;
+struct QuantParams;
 struct GdParams;
 struct CondParams;
 struct CssClassify;
@@ -168,6 +169,8 @@ hipError_t launch_relay(bool records, bool large, const RelayParams& P, int grid
 // messages in LDS or (large) in a global workspace)
 hipError_t launch_layered(bool mc, bool large, int variant, const LayeredParams& P, int grid, size_t lds,
                           hipStream_t s);
+// qbp_tu_quant.hip: bp_quant_kernel<message type, mc> (int8 messages for q <= 8, else int16; batch or Monte-Carlo build)
+hipError_t launch_quant(bool mc, bool wide, const QuantParams& P, int grid, size_t lds, hipStream_t s);
 // qbp_tu_gd.hip: bp_gd_kernel<variant, records, large> (sum-product or min-sum; batch build or Monte-Carlo failure
 // records; the messages in LDS or (large) in a global workspace)
 hipError_t launch_gd(bool records, bool large, int variant, const GdParams& P, int grid, int threads, size_t lds,

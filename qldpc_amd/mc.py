@@ -155,6 +155,27 @@ def _configure_layered(dec, layered):
         dec.layered_configure(layered)
 
 
+def quant_run_flags(flags, quant, layered, variant) -> int:
+    """``flags`` of a sweep with ``quant`` (None, a ``quant.QuantConfig`` or its dict form): | FLAG_QUANT, the first stage
+    is fixed-point min-sum.  ValueError for a bad configuration, together with ``layered``, or with a variant other than
+    min-sum."""
+    if quant is None:
+        return flags
+    from . import quant as quant_mod
+    quant_mod.as_config(quant)          # (a bad value raises here, before any GPU work)
+    if layered is not None and layered is not False:
+        raise ValueError("quant= excludes layered=: one first stage per run")
+    if int(variant) != _lib.MIN_SUM:
+        raise ValueError("quant= needs variant min-sum: fixed-point BP is min-sum")
+    return flags | _lib.FLAG_QUANT
+
+
+def _configure_quant(dec, quant):
+    if quant is not None:
+        from . import quant as quant_mod
+        dec.quant_configure(quant_mod.as_config(quant))
+
+
 def _on_device(shape, priors, begin, end, step, launch, world, device):
     """One rank's slice [begin, end) of a run on the device, then the ONE all-reduce of its int64 table of ``shape``
     (zeroed here; returned as a numpy array).  A point per entry of ``priors``, each owning an equal share of the
@@ -182,8 +203,12 @@ NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial record
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
               world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None,
-              lsd_large=False):
+              lsd_large=False, quant=None):
     """Returns the GLOBAL counter table int64[len(ps), 12] (after the reduce).
+
+    ``quant``: a ``quant.QuantConfig`` or its dict form -- the first stage is fixed-point min-sum (FLAG_QUANT; variant
+    min-sum only, not together with ``layered``); ``alpha``, ``damping`` and ``clip_llr`` are not read.  Every second
+    stage acts on what it leaves unconverged.
 
     ``lsd``: the bits_per_step (>= 0) of localized statistics decoding on the trials BP does not converge on (FLAG_LSD;
     not together with ``osd``, ``relay`` or ``gd``); ``lsd_large`` (False, True, "force"; ``lsd.py``) allows matrices
@@ -207,6 +232,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
+    flags = quant_run_flags(flags, quant, layered, variant)
     code = codes.load_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
@@ -216,6 +242,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
         _configure_gd(dec, gd)
         _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
+        _configure_quant(dec, quant)
         step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
@@ -310,7 +337,7 @@ def _dem_args(H, L, probs, prior):
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
-            layered=False, gd=None, window=None, check_round=None, lsd=None, lsd_large=False):
+            layered=False, gd=None, window=None, check_round=None, lsd=None, lsd_large=False, quant=None):
     """Monte-Carlo on a detector error model (``dem.parse_dem`` / ``dem.phenomenological``): column v of H [m, n]
     fails with probability probs[v] (qbp_mc_run_probs), BP [+ OSD] decodes the syndrome with ``prior`` (default
     ``dem_prior(probs)``), and a trial is a logical error when ``L @ (error ^ correction) != 0`` -- the
@@ -321,13 +348,14 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     the default 0 counts every logical error as "incorrectable" (a DEM does not say its distance).
     ``runner(H, L, probs, prior, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU
     tests (with ``window`` the runner is also passed ``window=(W, F), check_round=``); by default the HIP library and
-    torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``: as in ``run_sweep``.
+    torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``, ``quant``: as in ``run_sweep``.
 
     ``window``: ``(W, F)`` -- the sliding-window decoder (qbp_window_mc_run_probs; ``window.py``) with the round of
     every check in ``check_round``; "not_converged" then counts the trials with a window BP did not converge on.  Not
     together with ``relay``, ``layered``, ``gd`` or ``lsd``.  Sharded and reduced exactly like the plain path."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
+    flags = quant_run_flags(flags, quant, layered, variant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
     if window is not None:
@@ -335,6 +363,8 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
             raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with relay, layered or gd")
         if lsd is not None:
             raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with lsd")
+        if quant is not None:
+            raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with quant")
         if check_round is None:
             raise ValueError("window= needs check_round, the round of every check of H")
         W, F = (int(x) for x in window)
@@ -356,6 +386,7 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         _configure_gd(dec, gd)
         _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
+        _configure_quant(dec, quant)
         step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
 
         def launch(i, d_prior, a, b, d_out, stream):
@@ -736,16 +767,18 @@ def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, ma
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
                 damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1,
                 device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None,
-                lsd_large=False):
+                lsd_large=False, quant=None):
     """Monte-Carlo stratified by error weight (qbp_mc_run_weight): for every w of ``weights``, ``trials`` errors of
     exactly w ones, uniform among the C(n, w) patterns, decoded with the prior of error rate ``prior_p`` -- which fixes
     the decoder the failure fractions are measured for.  Returns the GLOBAL counter table int64[len(weights), 12];
     ``ler_from_weights`` turns it into the logical error rate at any p.  Shards, steps and reduces as ``run_sweep``
     does (trials of every weight are split over ranks; one all-reduce of the table).
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
-    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``: as in ``run_sweep``."""
+    the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``, ``quant``: as in
+    ``run_sweep``."""
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
+    flags = quant_run_flags(flags, quant, layered, variant)
     code = codes.load_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
@@ -756,6 +789,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
         _configure_gd(dec, gd)
         _configure_lsd(dec, lsd, lsd_large)
         _configure_layered(dec, layered)
+        _configure_quant(dec, quant)
         return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
                                   seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
@@ -767,13 +801,14 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
 
 def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
                        alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False,
-                       rank=0, world=1, device=0, runner=None, all_reduce=None, lsd=None, lsd_large=False):
+                       rank=0, world=1, device=0, runner=None, all_reduce=None, lsd=None, lsd_large=False, quant=None):
     """``run_weights`` for any matrix H [m, n] with logical operators / observables L [k, n] (k <= 64) and the
     decoder's LLRs ``prior`` [n].  The weight classes are the strata of UNIFORM noise -- every column failing with the
     same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
     does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``.  ``lsd``,
-    ``lsd_large``: as in ``run_sweep``."""
+    ``lsd_large``, ``quant``: as in ``run_sweep``."""
     flags = lsd_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), lsd, lsd_large)
+    flags = quant_run_flags(flags, quant, False, variant)
     L, _, prior, n = _dem_args(H, L, None, prior)
     weights = check_weights(weights, n)
     begin, end = shard_range(int(trials), rank, world)
@@ -781,6 +816,7 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
         from . import bp
         dec = bp.decoder_for(H, device=device)
         _configure_lsd(dec, lsd, lsd_large)
+        _configure_quant(dec, quant)
         return _weights_on_device(dec, L, distance, weights, prior, begin, end, seed=seed, max_iter=max_iter,
                                   variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
                                   flags=flags, world=world, device=device)
@@ -993,6 +1029,13 @@ def main(argv=None):
     ap.add_argument("--layered-large", action="store_true",
                     help="with --layered: also on matrices whose record state passes 160 KiB of LDS (space-time and "
                          "detector-error-model matrices): their messages live in a global workspace")
+    ap.add_argument("--quant", nargs=2, default=None, metavar=("BITS", "SCALE"),
+                    help="the first stage is fixed-point min-sum: messages of BITS bits (2..16), SCALE integer units per "
+                         "unit of LLR (needs --variant min-sum; not with --layered, --budgets, --spectrum, --shots, "
+                         "--window, --depolarizing)")
+    ap.add_argument("--quant-alpha", type=int, nargs=2, default=(1, 0), metavar=("NUM", "SHIFT"),
+                    help="with --quant: the normalisation NUM / 2^SHIFT (default 1 / 1)")
+    ap.add_argument("--quant-beta", type=int, default=0, metavar="B", help="with --quant: the offset, in integer units")
     ap.add_argument("--relay-stop", type=int, default=1, metavar="S", help="stop after S solutions, keep the lightest")
     ap.add_argument("--out", default=None, help="write the counter table as JSON")
     ap.add_argument("--gpus", type=int, default=0,
@@ -1056,6 +1099,19 @@ def main(argv=None):
             ap.error("--layered needs --variant sum-product or min-sum")
         if args.layered_large:
             args.layered = "large"          # (the drivers' layered= argument: True or "large")
+    quant = None
+    if args.quant is not None:
+        if (args.layered or args.budgets is not None or args.spectrum is not None or args.shots is not None
+                or args.window is not None or args.depolarizing is not None):
+            ap.error("--quant does not combine with --layered, --budgets, --spectrum, --shots, --window or --depolarizing")
+        if args.variant != "min-sum":
+            ap.error("--quant needs --variant min-sum")
+        try:
+            from . import quant as quant_mod
+            quant = quant_mod.QuantConfig(int(args.quant[0]), float(args.quant[1]), tuple(args.quant_alpha),
+                                          args.quant_beta)
+        except ValueError as e:
+            ap.error(f"--quant: {e}")
     if args.depolarizing is not None:
         if (args.dem is not None or args.phenomenological is not None or args.shots is not None or args.budgets is not None
                 or args.spectrum is not None or args.weights is not None or relay is not None or gd is not None
@@ -1281,20 +1337,20 @@ def main(argv=None):
 
         def sweep(trials, ps, rank, world):
             return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, **common)
+                               layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, quant=quant, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
             return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered, gd=gd,
-                             lsd=lsd, lsd_large=args.lsd_large, **common)
+                             lsd=lsd, lsd_large=args.lsd_large, quant=quant, **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
             return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
                            layered=args.layered, gd=gd, window=args.window, check_round=check_round, lsd=lsd,
-                           lsd_large=args.lsd_large, **common)[None, :]
+                           lsd_large=args.lsd_large, quant=quant, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()

@@ -83,6 +83,11 @@ def main(argv=None):
     ap.add_argument("--gd-large", action="store_true",
                     help="with --gd: also on matrices whose record state passes 160 KiB of LDS: their messages live in a "
                          "global workspace")
+    ap.add_argument("--quant", nargs=2, default=None, metavar=("BITS", "SCALE"),
+                    help="BP is fixed-point min-sum: messages of BITS bits (2..16), SCALE integer units per unit of LLR")
+    ap.add_argument("--quant-alpha", type=int, nargs=2, default=(1, 0), metavar=("NUM", "SHIFT"),
+                    help="with --quant: the normalisation NUM / 2^SHIFT (default 1 / 1)")
+    ap.add_argument("--quant-beta", type=int, default=0, metavar="B", help="with --quant: the offset, in integer units")
     ap.add_argument("--osd-method", choices=("cs", "e"), default="cs",
                     help="with --osd-order W >= 1: combination sweep or exhaustive search")
     ap.add_argument("--osd-order", type=int, default=0,
@@ -105,6 +110,14 @@ def main(argv=None):
         ap.error("--gd excludes --osd 0, --osd-order and --lsd")
     gd = None if args.gd is None else dict(iters_per_round=args.gd[0], max_rounds=args.gd[1],
                                            large="auto" if args.gd_large else False)
+    quant = None
+    if args.quant is not None:
+        try:
+            from . import quant as quant_mod
+            quant = quant_mod.QuantConfig(int(args.quant[0]), float(args.quant[1]), tuple(args.quant_alpha),
+                                          args.quant_beta)
+        except ValueError as e:
+            ap.error(f"--quant: {e}")
     if args.osd is None:
         args.osd = -1 if args.lsd is not None or gd is not None else 0
     try:
@@ -150,7 +163,8 @@ def main(argv=None):
         tables[name] = mc.run_sweep(name, args.p, args.trials, draws=args.draws, seed=args.seed,
                                     max_iter=args.max_iter, osd=args.osd == 0, osd_method=args.osd_method,
                                     osd_order=args.osd_order, rank=rank, world=world, device=local, lsd=args.lsd,
-                                    lsd_large=args.lsd_large, gd=gd)
+                                    lsd_large=args.lsd_large, gd=gd, quant=quant,
+                                    **({} if quant is None else {"variant": _lib.MIN_SUM}))
         if rank == 0:
             dt = time.time() - t0
             for p, row in zip(args.p, tables[name]):

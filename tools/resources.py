@@ -46,6 +46,9 @@ UNITS += [("qbp_tu_cond.hip", [])]
 # bp_generic_llrhist_kernel (last, so that the rows before them are the earlier tables')
 UNITS += [("qbp_tu_fused.hip", ["-DQBP_LLRHIST_TU"])] + [("qbp_tu_generic.hip", ["-DQBP_LLRHIST_TU", f"-DQBP_GENERIC_MEM={i}"])
                                                          for i in range(3)]
+# Fixed-point min-sum (qbp_quant_decode_batch, QBP_FLAG_QUANT): bp_quant_kernel<message type, mc> (after them, for the
+# same reason)
+UNITS += [("qbp_tu_quant.hip", [])]
 
 
 def demangle(sym):
