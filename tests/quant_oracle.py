@@ -70,3 +70,51 @@ def decode_batch(H, syndromes, prior, max_iter, bits, scale, alpha_num, alpha_sh
         done |= ok
     out_V[~done] = V[~done]
     return ((out_V < 0).astype(np.uint8), done, out_it, out_V.astype(np.int32), out_V.astype(np.float64))
+
+
+def decode_batch_edges(H, syndromes, prior, max_iter, bits, scale, alpha_num, alpha_shift, beta):
+    """decode_batch with the messages stored per entry of H, int64 [B, E] in row-major order of the entries, for
+    matrices whose dense [B, m, n] arrays are too large: the same rules 2-7 in the header's wording ("all the other
+    entries of the row" for every entry on its own), plain loops over the rows and the columns of the entry lists, the
+    same outputs.  tests/test_quant_cpu.py asserts that the two are equal on every case of quant_cases."""
+    H = (np.asarray(H) != 0)
+    m, n = H.shape
+    syn = np.asarray(syndromes).astype(np.int64) & 1
+    B = syn.shape[0]
+    M = M_of(bits)
+    P = quantize(prior, bits, scale)
+    assert P.shape == (n,)
+    edge_row, edge_col = np.nonzero(H)                                  # row after row, columns ascending
+    E = len(edge_row)
+    row_edges = [np.flatnonzero(edge_row == c) for c in range(m)]       # the entries of row c
+    col_edges = [np.flatnonzero(edge_col == v) for v in range(n)]       # the entries of column v
+    Q = np.tile(P[edge_col], (B, 1))                                    # rule 2
+    R = np.zeros((B, E), np.int64)
+    done = np.zeros(B, bool)
+    out_V = np.zeros((B, n), np.int64)
+    out_it = np.full(B, max_iter - 1, np.int32)
+    V = np.zeros((B, n), np.int64)
+    for t in range(max_iter):
+        for c in range(m):                                              # rule 3
+            es = row_edges[c]
+            for e in es:
+                others = Q[:, es[es != e]]                              # [B, d - 1]
+                neg = (syn[:, c] + (others < 0).sum(axis=1)) & 1
+                mag = np.abs(others).min(axis=1) if others.shape[1] else np.full(B, M, np.int64)
+                mag = np.maximum(((mag * alpha_num) >> alpha_shift) - beta, 0)
+                R[:, e] = np.where(neg == 1, -mag, mag)
+        for v in range(n):                                              # rule 4
+            es = col_edges[v]
+            V[:, v] = P[v] + R[:, es].sum(axis=1)
+            Q[:, es] = np.clip(V[:, v, None] - R[:, es], -M, M)
+        assert np.abs(V).max(initial=0) < 2 ** 31
+        hard = (V < 0).astype(np.int64)                                 # rule 5
+        ok = np.ones(B, bool)
+        for c in range(m):
+            ok &= (hard[:, edge_col[row_edges[c]]].sum(axis=1) & 1) == syn[:, c]
+        first = ok & ~done
+        out_V[first] = V[first]                                         # rule 6
+        out_it[first] = t
+        done |= ok
+    out_V[~done] = V[~done]
+    return ((out_V < 0).astype(np.uint8), done, out_it, out_V.astype(np.int32), out_V.astype(np.float64))

@@ -1,7 +1,8 @@
 """GPU: bp_quant_kernel against the numpy statement of fixed-point min-sum (tests/quant_oracle.py), bit for bit -- the
 batch build on seven matrices, four parameter sets, three iteration limits and two kinds of prior; the float
 cross-check through qbp_decode_batch on integer priors; launch geometries into poisoned buffers; and the Monte-Carlo
-build behind QBP_FLAG_QUANT against statement + classification, alone and under OSD, LSD and Relay-BP."""
+build behind QBP_FLAG_QUANT, at 6 bits (int8 messages) and at 16 (int16), against statement + classification, alone and
+under OSD, LSD and Relay-BP.  tests/test_gpu_quant_large.py goes on where these matrices end."""
 import numpy as np
 import pytest
 
@@ -188,7 +189,8 @@ def test_force_full_returns_the_early_exit_bits(name):
 
 # ---- 3. Monte-Carlo -------------------------------------------------------------------------------------------------------------
 MC_ITERS = 12
-MC_PARAMS = qc.PARAMS[1]
+MC_PARAMS = qc.PARAMS[1]                    # 6 bits: bp_quant_kernel<int8_t, true>
+MC_PARAMS_WIDE = qc.PARAMS[3]               # 16 bits: bp_quant_kernel<int16_t, true>
 
 
 def mc_case(name):
@@ -217,12 +219,22 @@ def expected(H, L, d, errors, prior, params=MC_PARAMS):
     return oracle.classify_trials(H, L, d, errors, syn, hard, conv, iters), (syn, hard, conv, iters, llr)
 
 
-@pytest.mark.parametrize("name", ["72", "irr37", "pheno"])
-def test_mc_counters_equal_statement_and_classification(name):
+MC_NAMES = ("72", "irr37", "pheno")
+MC_STAGES = ("osd0", "cs7", "lsd", "relay")
+
+
+def mc_id(*parts, params):
+    """The 6-bit runs keep the ids they had before the 16-bit ones (the int16 Monte-Carlo build) joined them."""
+    return "-".join(parts) + ("" if params is MC_PARAMS else f"-q{params[0]}")
+
+
+@pytest.mark.parametrize("name,params", [pytest.param(nm, p, id=mc_id(nm, params=p)) for p in (MC_PARAMS, MC_PARAMS_WIDE)
+                                         for nm in MC_NAMES])
+def test_mc_counters_equal_statement_and_classification(name, params):
     H, L, d, errors, prior, probs = mc_case(name)
-    want, (_, _, conv, _, _) = expected(H, L, d, errors, prior)
+    want, (_, _, conv, _, _) = expected(H, L, d, errors, prior, params)
     dec = fresh(H)
-    dec.quant_configure(cfg_of(MC_PARAMS))
+    dec.quant_configure(cfg_of(params))
     # (alpha, damping and the clip of the call are not read)
     kw = dict(max_iter=MC_ITERS, variant=_lib.MIN_SUM, alpha=0.3, damping=0.5, clip_llr=1.0, flags=QUANT)
     got = dec.mc_run_errors(L, d, errors, prior, **kw)
@@ -240,7 +252,7 @@ def test_mc_counters_equal_statement_and_classification(name):
             (dec.mc_sample_errors_probs(probs, 5, T, seed=9), lambda a, b: dec.mc_run_probs(L, d, probs, prior, a, b, seed=9, **kw)),
             (dec.mc_sample_errors_weight(w, 5, T, seed=9), lambda a, b: dec.mc_run_weight(L, d, w, prior, a, b, seed=9, **kw))]
     for errs, run in runs:
-        want_s, _ = expected(H, L, d, errs, prior)
+        want_s, _ = expected(H, L, d, errs, prior, params)
         assert np.array_equal(run(5, 5 + T), want_s)
         assert np.array_equal(run(5, 6) + run(6, 50) + run(50, 5 + T), want_s)
         dec.set_option(_lib.OPT_MC_WEIGHT_CHUNK, 7)
@@ -248,18 +260,18 @@ def test_mc_counters_equal_statement_and_classification(name):
         dec.set_option(_lib.OPT_MC_WEIGHT_CHUNK, 0)
 
 
-@pytest.mark.parametrize("stage", ["osd0", "cs7", "lsd", "relay"])
-@pytest.mark.parametrize("name", ["72", "irr37", "pheno"])
-def test_second_stages_act_on_the_quant_failure_records(name, stage):
+@pytest.mark.parametrize("name,stage,params", [pytest.param(nm, st, p, id=mc_id(nm, st, params=p))
+                                               for p in (MC_PARAMS, MC_PARAMS_WIDE) for st in MC_STAGES for nm in MC_NAMES])
+def test_second_stages_act_on_the_quant_failure_records(name, stage, params):
     """Counters = the statement -> qbp_osd_batch / qbp_lsd_batch / qbp_relay_decode_batch on its failures, with
     llr = (double)V -> numpy classification."""
     H, L, d, errors, prior, _ = mc_case(name)
     n = H.shape[1]
-    _, (syn, hard, conv, iters, llr) = expected(H, L, d, errors, prior)
+    _, (syn, hard, conv, iters, llr) = expected(H, L, d, errors, prior, params)
     f = np.flatnonzero(~conv)
     assert len(f) >= 8
     dec = fresh(H)
-    dec.quant_configure(cfg_of(MC_PARAMS))
+    dec.quant_configure(cfg_of(params))
     det = hard.copy()
     if stage == "relay":
         cfg = relay.RelayConfig(relay.relay_gammas(n, 3, 0.125, (-0.24, 0.66), 4), [10] * 3, 1, 0.9)

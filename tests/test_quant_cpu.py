@@ -1,5 +1,6 @@
 """No GPU: the numpy statement of fixed-point min-sum (tests/quant_oracle.py) against the reference-generated min-sum
-goldens and ``oracle.decode_batch``, ``quant.quantize_prior`` (rule 1), and the record classes of the test inputs."""
+goldens and ``oracle.decode_batch``, ``quant.quantize_prior`` (rule 1), its edge-indexed twin against it, and the record
+classes of the test inputs."""
 import numpy as np
 import pytest
 
@@ -86,6 +87,35 @@ def test_integer_priors_equal_the_references_min_sum(integer_case):
     assert min(counts) >= 4
     assert np.array_equal(hard, o_hard) and np.array_equal(conv, o_conv.astype(bool)) and np.array_equal(iters, o_iters)
     assert np.array_equal(llr, o_llr) and np.array_equal(V, llr.astype(np.int32))
+
+
+# ---- the edge-indexed twin of the statement ---------------------------------------------------------------------------------
+def assert_twin(got, want, what):
+    assert len(got) == len(want) == 5
+    for k, x, y in zip(("hard", "converged", "iters", "posterior_q", "llr"), got, want):
+        assert x.dtype == y.dtype and x.shape == y.shape, (what, k, x.dtype, y.dtype, x.shape, y.shape)
+        assert np.array_equal(x.view(np.uint64) if k == "llr" else x, y.view(np.uint64) if k == "llr" else y), (what, k)
+
+
+@pytest.mark.parametrize("kind", ["uniform", "mixed"])
+@pytest.mark.parametrize("name", qc.MATRICES)
+def test_edge_indexed_twin_equals_the_dense_statement(name, kind):
+    """decode_batch_edges against decode_batch in all five outputs, on every (name, kind, params, max_iter) the GPU tests
+    of the small matrices use: weight-0 and weight-1 rows, empty columns, +-inf priors and the unsatisfiable empty
+    check included."""
+    H, _, syn, prior = qc.case(name, kind)
+    for params in qc.PARAMS:
+        for max_iter in qc.MAX_ITERS:
+            got = qo.decode_batch_edges(H, syn, prior, max_iter, *params)
+            assert_twin(got, qc.statement(name, kind, params, max_iter), f"{name} {kind} {params} max_iter {max_iter}")
+
+
+def test_edge_indexed_twin_equals_the_dense_statement_on_the_issue_records():
+    H, _, syn, prior = qc.issue_case()
+    nan = prior.copy(); nan[9] = np.nan
+    for params in qc.PARAMS:
+        assert_twin(qo.decode_batch_edges(H, syn, prior, 30, *params), qo.decode_batch(H, syn, prior, 30, *params), params)
+    assert_twin(qo.decode_batch_edges(H, syn, nan, 30, *qc.PARAMS[2]), qo.decode_batch(H, syn, nan, 30, *qc.PARAMS[2]), "NaN")
 
 
 # ---- the test inputs hold every record class ------------------------------------------------------------------------------
