@@ -882,6 +882,73 @@ int qbp_mc_sample_errors_weight(qbp_handle* h, int32_t weight, uint64_t seed, in
                                 uint8_t* errors);
 
 /*
+ * EXHAUSTIVE enumeration of the errors of one weight: every pattern of a class instead of a sample of it.  The lowest
+ * weights dominate LER(p) at small p and are where sampling works worst (the first non-zero f_w is tiny); their classes
+ * are small enough to decode completely -- 59 640 patterns of weight 3 on [[72,12,6]], 17 178 876 of weight 4 on
+ * [[144,12,12]] -- which gives f_w exactly and the decoder's real minimum failing weight.
+ * The order (this build's specification; qldpc_amd/enumerate.py states it in Python integers): for n columns and weight
+ * w, rank r in [0, C(n, w)) is the r-th tuple of itertools.combinations(range(n), w), i.e. lexicographic order of the
+ * ascending column tuple.  w = 0 has one pattern, the zero row; w = n has one pattern.  Ranks are int64 and a call is
+ * valid only if C(n, w) <= 2^62.  The rank is the trial index: seed-free, and one int64 names a pattern.
+ * Unranking: for i = 0 .. w - 1, with lo = previous column + 1 (0 at first), take the smallest column c >= lo for which
+ * the remaining rank is below sum_{c' = lo .. c} C(n - 1 - c', w - 1 - i); subtract the sum up to c - 1.  By the
+ * hockey-stick identity that is a search on one monotone row of a binomial table: with D = C(n, w) - 1 - r, for
+ * t = w .. 1 the largest j below the previous one with C(j, t) <= D, column n - 1 - j, D -= C(j, t).  The host builds
+ * C(j, t) for 0 <= j <= n, 0 <= t <= w as uint64, entries above 2^63 - 1 saturated (harmless: every compared value is
+ * below 2^62); the handle owns the table and keeps it per (n, w).
+ * Two stages as qbp_mc_run_weight: a chunk of QBP_OPT_MC_WEIGHT_CHUNK ranks is written into the same handle buffer
+ * (mc_enum_weight_kernel, one lane per pattern, w searches and w byte stores), then decoded and classified by the
+ * pipeline of qbp_mc_run_errors.  Everything is as in qbp_mc_run_weight -- counters ADDED to, every flag it takes (OSD-0,
+ * order-w OSD, Relay, GD, LSD, layered, fixed-point, the large builds), the QBP_MC_OSD_MAX_TRIALS rule for the whole
+ * call -- except that there is no seed and the trial range is the rank range [rank_begin, rank_end).  The result does
+ * not depend on the chunk or on how the range is split; [0] of a whole class is C(n, weight).
+ * QBP_E_INVALID, before any GPU work and with the outputs untouched: weight outside [0, n], C(n, weight) > 2^62,
+ * rank_begin < 0, rank_end < rank_begin, rank_end > C(n, weight), and whatever qbp_mc_run_weight refuses.
+ */
+int qbp_mc_run_enum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, int32_t weight, int64_t rank_begin,
+                    int64_t rank_end, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                    double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form (as qbp_mc_run_weight_device). */
+int qbp_mc_run_enum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, int32_t weight,
+                           int64_t rank_begin, int64_t rank_end, const double* d_prior, int32_t max_iter,
+                           int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                           int64_t* d_counters, void* stream);
+/* The patterns of ranks [rank_begin, rank_begin + T) as qbp_mc_run_enum fills them: errors [T][n] host bytes (tests). */
+int qbp_mc_sample_errors_enum(qbp_handle* h, int32_t weight, int64_t rank_begin, int64_t T, uint8_t* errors);
+/* count[0] = C(n, weight).  Host only, no device needed.  QBP_E_INVALID (count untouched): n < 0, weight outside [0, n],
+ * C(n, weight) > 2^62. */
+int qbp_enum_count(int32_t n, int32_t weight, int64_t* count);
+
+/*
+ * WHICH patterns of an enumerated class the decoder fails on.  Per pattern e of ranks [rank_begin, rank_end): s = H e,
+ * actual = Lx e; (x, conv) is what qbp_decode_shots computes for s (BP, then the OSD bits of `flags` where BP did not
+ * converge); kind = (Lx x != actual) | 2 (!conv).  The pattern is captured when kind & what != 0, what in 1 .. 3
+ * (1 logical failures, 2 patterns BP did not converge on, 3 either).
+ *   found[0]: the number captured; it may exceed cap.  ranks [cap], kinds [cap] (null allowed with cap = 0): the first
+ *   min(found, cap) entries hold captured patterns, sorted by ascending rank when found <= cap; when found > cap which
+ *   cap of them are kept, and their order, is unspecified.  Entries beyond min(found, cap) are not written.
+ *   counters (ADDED to): those of qbp_decode_shots -- [0], [1], [6], [7], [8], [10].
+ * Flags are those qbp_decode_shots accepts (a second stage it does not take: QBP_E_UNSUPPORTED, as there); k in 1 .. 64.
+ * Chunk by chunk on the device, nothing returning to the host in between: mc_enum_weight_kernel fills a chunk of
+ * QBP_OPT_MC_WEIGHT_CHUNK rows (with OSD at most the records of one qbp_decode_shots call), enum_pack_kernel computes
+ * every row's b8 det_bits row and its actual word through the CSR arrays and the Lx columns, the launches of
+ * qbp_decode_shots run unchanged, enum_capture_kernel compares and compacts the hits (a ballot per wavefront, one atomic
+ * per wavefront, entries past cap dropped).  The result does not depend on the chunk or on how the range is split.
+ * QBP_E_INVALID, before any GPU work and with every output untouched: what qbp_mc_run_enum refuses of weight and ranks,
+ * what outside 1 .. 3, cap < 0, a null found, null ranks or kinds with cap > 0, and whatever qbp_decode_shots refuses.
+ */
+int qbp_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin, int64_t rank_end,
+                      const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
+                      double clip_llr, uint32_t flags, int32_t what, int64_t cap, int64_t* ranks, uint8_t* kinds,
+                      int64_t found[1], int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form: device pointers but Lx; the order of the entries is always unspecified; d_found [1] is ADDED to
+ * (the caller zeroes it), as d_counters is. */
+int qbp_enum_failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
+                             int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap,
+                             int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream);
+
+/*
  * Decode T RECORDED shots of a detector error model to observable predictions: the loop of
  * studies/studyComplete.py:91-109 (sampler.sample(shots, separate_observables=True); BP per shot;
  * L_matrix @ prediction % 2 != actual_observables[i]) for data that comes from stim's circuit sampler or from an

@@ -146,6 +146,19 @@ SIGNATURES = {
                                            C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                            C.c_double, C.c_uint32, _VP, _VP]),
     "qbp_mc_sample_errors_weight": (C.c_int, [_VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
+    "qbp_enum_count": (C.c_int, [C.c_int32, C.c_int32, _VP]),
+    "qbp_mc_run_enum": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, C.c_int32,
+                                  C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP]),
+    "qbp_mc_run_enum_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP,
+                                         C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, _VP,
+                                         _VP]),
+    "qbp_mc_sample_errors_enum": (C.c_int, [_VP, C.c_int32, C.c_int64, C.c_int64, _VP]),
+    "qbp_enum_failures": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, C.c_int32, C.c_int32,
+                                    C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_int32, C.c_int64, _VP, _VP, _VP,
+                                    _VP]),
+    "qbp_enum_failures_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, C.c_int32,
+                                           C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_int32,
+                                           C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
     "qbp_message_histograms": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -1021,6 +1034,69 @@ class Decoder:
             int(trial_end), d_prior, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr),
             int(flags), d_counters, stream or None))
 
+    @_locked
+    def mc_run_enum(self, Lx, distance, weight, prior, rank_begin, rank_end, max_iter=50, variant=SUM_PRODUCT,
+                    alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """``mc_run_weight`` on ENUMERATED patterns (qbp_mc_run_enum): counters int64[12] of the weight-``weight``
+        patterns of ranks [rank_begin, rank_end) in the order of ``itertools.combinations(range(n), weight)``.
+        [0] of the whole class is C(n, weight) and [1] / [0] its exact failure fraction."""
+        return self._mc_sampled("qbp_mc_run_enum", Lx, distance, (int(weight),), rank_begin, rank_end, prior,
+                                (int(max_iter),), (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros(NUM_COUNTERS, np.int64)])[0]
+
+    def mc_run_enum_device(self, Lx, distance, weight, d_prior, rank_begin, rank_end, d_counters, max_iter=50,
+                           variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, stream=0):
+        """``mc_run_enum`` on device buffers: d_counters int64[12] is added to.  One call: with FLAG_OSD0 the
+        caller splits ranges by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_mc_run_enum_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight), int(rank_begin), int(rank_end), d_prior,
+            int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags), d_counters,
+            stream or None))
+
+    @_locked
+    def enum_failures(self, Lx, weight, prior, rank_begin, rank_end, what=1, cap=1 << 20, max_iter=50,
+                      variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, counters=None):
+        """The failing patterns of ranks [rank_begin, rank_end) of weight ``weight`` (qbp_enum_failures): decoded as
+        ``decode_shots`` decodes their syndromes, kind = (Lx x != Lx e) | 2 (BP did not converge); captured when
+        ``kind & what`` (1 logical, 2 unconverged, 3 either).  Returns ``(ranks int64[F], kinds uint8[F], found,
+        counters int64[12])`` with F = min(found, cap), ascending in rank when found <= cap; a given ``counters``
+        array is added to."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        if counters is None:
+            counters = np.zeros(NUM_COUNTERS, np.int64)
+        elif not (isinstance(counters, np.ndarray) and counters.dtype == np.int64 and
+                  counters.shape == (NUM_COUNTERS,) and counters.flags.c_contiguous):
+            raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
+        cap = int(cap)
+        room = max(0, min(cap, int(rank_end) - int(rank_begin)))       # (no more can be captured)
+        ranks = np.zeros(room, np.int64)
+        kinds = np.zeros(room, np.uint8)
+        found = np.zeros(1, np.int64)
+        _check(load().qbp_enum_failures(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(weight), int(rank_begin), int(rank_end), pr.ctypes.data,
+            int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags), int(what),
+            cap if cap < 0 else room, ranks.ctypes.data if room else None, kinds.ctypes.data if room else None,
+            found.ctypes.data, counters.ctypes.data))
+        kept = min(int(found[0]), room)
+        return ranks[:kept], kinds[:kept], int(found[0]), counters
+
+    def enum_failures_device(self, Lx, weight, d_prior, rank_begin, rank_end, what, cap, d_ranks, d_kinds, d_found,
+                             d_counters, max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0,
+                             flags=0, stream=0):
+        """``enum_failures`` on device buffers (pointers as ints): d_ranks int64[cap] and d_kinds uint8[cap] in no
+        particular order, d_found int64[1] and d_counters int64[12] added to."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_enum_failures_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(weight), int(rank_begin), int(rank_end), d_prior, int(max_iter),
+            int(variant), float(alpha), float(damping), float(clip_llr), int(flags), int(what), int(cap),
+            d_ranks or None, d_kinds or None, d_found or None, d_counters, stream or None))
+
     def _spectrum_tables(self, max_iter, spectrum, iter_hist):
         """The two tables of the spectrum calls (new zeroed ones, or the caller's, which are added to)."""
         if int(max_iter) < 1:       # (beyond MC_SPECTRUM_MAX_ITER the library answers QBP_E_INVALID)
@@ -1323,6 +1399,13 @@ class Decoder:
         out = np.empty((int(T), self.n), np.uint8)
         _check(load().qbp_mc_sample_errors_weight(self._h, int(weight), int(seed), int(trial_begin), int(T),
                                                   out.ctypes.data))
+        return out
+
+    @_locked
+    def mc_sample_errors_enum(self, weight, rank_begin, T):
+        """Patterns uint8[T, n] of ranks rank_begin .. + T of weight ``weight``, as ``mc_run_enum`` fills them (tests)."""
+        out = np.empty((int(T), self.n), np.uint8)
+        _check(load().qbp_mc_sample_errors_enum(self._h, int(weight), int(rank_begin), int(T), out.ctypes.data))
         return out
 
     @_locked

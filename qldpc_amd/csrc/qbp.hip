@@ -324,7 +324,14 @@ struct qbp_handle {
     int opt_kernel = 0;             // 0 auto, 1 on-chip, 2 general-H (workgroup per syndrome), 3 streaming
     DevBuf<uint8_t> d_wsS;           // streaming kernel: transposed syndromes; general-H Monte-Carlo: syndromes
     DevBuf<uint8_t> d_wsE;           // general-H Monte-Carlo: sampled errors
-    DevBuf<uint8_t> d_weight_err;    // qbp_mc_run_weight: the fixed-weight errors of one chunk, [chunk][n]
+    DevBuf<uint8_t> d_weight_err;    // qbp_mc_run_weight, qbp_mc_run_enum, qbp_enum_failures: the errors of one chunk, [chunk][n]
+    // weight-w enumeration (qbp_mc_run_enum, qbp_enum_failures): C(j, t) for t <= binom_w, j <= n (enum_prepare); the
+    // shots of one chunk of qbp_enum_failures and what the shots launches say of them; scratch of its host entry
+    DevBuf<unsigned long long> d_binom;
+    int binom_w = -1;
+    DevBuf<uint8_t> d_enum_det, d_enum_conv, d_enum_kinds;
+    DevBuf<unsigned long long> d_enum_actual, d_enum_pred, d_enum_found;
+    DevBuf<long long> d_enum_ranks;
     long long opt_weight_chunk = 0;  // QBP_OPT_MC_WEIGHT_CHUNK (0 = default)
     long long opt_llr_hist_chunk = 0;   // QBP_OPT_LLR_HIST_CHUNK (0 = default)
     DevBuf<int32_t> d_srow, d_srow_e0, d_srow_deg, d_svar, d_sedge;   // weight-class tables
@@ -2897,12 +2904,13 @@ QBP_ABI_CATCH
 
 // Where the errors of a Monte-Carlo call come from; only the fields of `kind` are read.
 struct McErrors {
-    enum Kind { P, PROBS, WEIGHT, STORED } kind = P;
+    enum Kind { P, PROBS, WEIGHT, STORED, ENUM } kind = P;
     int32_t draws = 1;                       // P, PROBS
-    uint64_t seed = 0;                       // all but STORED
+    uint64_t seed = 0;                       // all but STORED and ENUM
     double p = 0.0;                          // P: every column fails with p
     const double* probs = nullptr;           // PROBS: a probability per column, host [n]
     int32_t weight = 0;                      // WEIGHT: exactly this many ones, uniform among the patterns
+                                             // ENUM: the patterns of this weight by rank (the trial index is the rank)
     const uint8_t* d_errors = nullptr;       // STORED: device [trials, n]; the trial range starts at 0
 };
 
@@ -2938,11 +2946,11 @@ struct McCall {
     size_t rows() const { return ladder() ? (size_t)n_budgets : 1; }          // counter rows = failure-record planes
     int32_t last_iter() const { return ladder() ? budgets[n_budgets - 1] : dec.max_iter; }
     size_t llr_cells() const { return out == LLRHIST ? (size_t)QBP_LLR_HIST_WORDS(n_budgets, llr_bins) : 0; }
-    // sampled trials that no BP kernel draws itself: fixed weight, and the layered and fixed-point kernels, which decode
-    // stored errors only
+    // trials that no BP kernel draws itself: fixed weight, sampled or enumerated, and the layered and fixed-point
+    // kernels, which decode stored errors only
     bool chunked() const
     {
-        return errors.kind == McErrors::WEIGHT ||
+        return errors.kind == McErrors::WEIGHT || errors.kind == McErrors::ENUM ||
                (errors.kind != McErrors::STORED && (dec.flags & (QBP_FLAG_LAYERED | QBP_FLAG_QUANT)));
     }
 };
@@ -2954,9 +2962,60 @@ static long long mc_chunk_trials(const qbp_handle* h, int64_t T)
     return std::min<long long>(h->opt_weight_chunk > 0 ? h->opt_weight_chunk : dflt, T);
 }
 
-static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial_begin)
+// C(n, w), or false above 2^62 (qbp_enum_count)
+static bool enum_count(int n, int w, int64_t* count)
+{
+    const int k = std::min(w, n - w);
+    unsigned __int128 c = 1;
+    for (int i = 0; i < k; ++i) {
+        c = c * (unsigned)(n - i) / (unsigned)(i + 1);          // C(n, i + 1): exact at every step
+        if (c > ((unsigned __int128)1 << 62)) return false;
+    }
+    *count = (int64_t)c;
+    return true;
+}
+
+// The rank range of an enumeration: weight in [0, n], C(n, weight) <= 2^62, 0 <= rank_begin <= rank_end <= C(n, weight)
+static int check_enum_range(const qbp_handle* h, int32_t weight, int64_t rank_begin, int64_t rank_end)
+{
+    if (weight < 0 || weight > h->n)
+        return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", weight, h->n);
+    int64_t count = 0;
+    if (!enum_count(h->n, weight, &count))
+        return fail(QBP_E_INVALID, "C(%d, %d) patterns are beyond 2^62", h->n, weight);
+    if (rank_begin < 0 || rank_end < rank_begin || rank_end > count)
+        return fail(QBP_E_INVALID, "ranks [%lld, %lld) out of [0, C(%d, %d) = %lld]", (long long)rank_begin,
+                    (long long)rank_end, h->n, weight, (long long)count);
+    return QBP_OK;
+}
+
+// The table mc_enum_weight_kernel searches, on the device: C(j, t) at t * (n + 1) + j for t <= w, j <= n, saturated at
+// 2^63 - 1.  Cached per weight (n is the handle's); uploaded as the tables of McInputs are.
+static int enum_prepare(qbp_handle* h, int32_t w, hipStream_t s)
+{
+    if (h->binom_w == w) return QBP_OK;
+    const size_t stride = (size_t)h->n + 1;
+    const unsigned long long sat = 0x7fffffffffffffffull;
+    std::vector<unsigned long long> tab(((size_t)w + 1) * stride, 0ull);
+    for (size_t j = 0; j < stride; ++j) tab[j] = 1ull;                       // C(j, 0)
+    for (size_t t = 1; t <= (size_t)w; ++t)
+        for (size_t j = 1; j < stride; ++j) {                                // C(0, t) = 0
+            const unsigned long long a = tab[t * stride + j - 1], b = tab[(t - 1) * stride + j - 1];
+            tab[t * stride + j] = a > sat - b ? sat : a + b;
+        }
+    h->binom_w = -1;
+    HIP_TRY(h->d_binom.reserve(tab.size()));
+    HIP_TRY(hipMemcpyAsync(h->d_binom.p, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    h->binom_w = w;
+    return QBP_OK;
+}
+
+// `trial_end`: the end of the range (an enumeration's ranks have an upper bound; no sampler's trials do)
+static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial_begin, int64_t trial_end)
 {
     if (e.kind == McErrors::STORED) return e.d_errors ? QBP_OK : fail(QBP_E_INVALID, "null pointer");
+    if (e.kind == McErrors::ENUM) return check_enum_range(h, e.weight, trial_begin, trial_end);
     if (e.kind == McErrors::WEIGHT) {
         if (e.weight < 0 || e.weight > h->n)
             return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", e.weight, h->n);
@@ -2997,7 +3056,7 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
         return fail(QBP_E_INVALID, "%d budgets x %d rows x (%d bins + 3) = %lld words beyond QBP_LLR_HIST_MAX_WORDS = %d",
                     c.n_budgets, QBP_LLR_HIST_ROWS, c.llr_bins, (long long)QBP_LLR_HIST_WORDS(c.n_budgets, c.llr_bins),
                     QBP_LLR_HIST_MAX_WORDS);
-    if ((rc = check_mc_errors(h, c.errors, c.trial_begin)) != QBP_OK) return rc;
+    if ((rc = check_mc_errors(h, c.errors, c.trial_begin, c.trial_end)) != QBP_OK) return rc;
     if ((rc = check_decode_args(h, c.trials(), c.last_iter(), c.dec.variant)) != QBP_OK) return rc;
     // ladders and spectra have neither a Relay or guided-decimation stage nor a layered build
     if ((rc = check_relay_flags(h, c.dec.flags, c.out != McCall::COUNTERS)) != QBP_OK) return rc;
@@ -3012,9 +3071,9 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
     if (c.k > 0 && !c.Lx) return fail(QBP_E_INVALID, "Lx is null");
     if (c.dec.flags & (QBP_FLAG_OSD0 | SECOND_BP_BITS)) {
         // QBP_MC_OSD_MAX_TRIALS bounds the records of one launch.  That is the whole call -- a fixed-weight call too,
-        // although it launches chunk by chunk -- except for layered sampled calls, which have always been held to it
+        // sampled or enumerated, although it launches chunk by chunk -- except for layered sampled calls, which have always been held to it
         // per chunk only: a longer range of those goes through.
-        const bool per_chunk = c.chunked() && c.errors.kind != McErrors::WEIGHT;
+        const bool per_chunk = c.chunked() && c.errors.kind != McErrors::WEIGHT && c.errors.kind != McErrors::ENUM;
         rc = check_mc_osd_trials(h, per_chunk ? mc_chunk_trials(h, c.trials()) : c.trials(), c.rows());
     }
     return rc;
@@ -3143,6 +3202,7 @@ static hipError_t mc_sample(qbp_handle* h, const McErrors& e, uint8_t* errors, l
 {
     // (the samplers do not depend on H: any matrix, whichever kernel decodes it)
     if (e.kind == McErrors::WEIGHT) return qbp::launch_mc_sample_weight(errors, h->n, e.weight, t, trial_begin, e.seed, s);
+    if (e.kind == McErrors::ENUM) return qbp::launch_mc_enum_weight(errors, h->n, e.weight, t, trial_begin, h->d_binom.p, s);
     if (e.kind == McErrors::PROBS)
         return qbp::launch_mc_sample_cols(errors, h->n, t, trial_begin, e.draws, e.seed, h->mc_in.d_thr.p, s);
     return qbp::launch_mc_sample(errors, h->n, t, trial_begin, e.draws, e.seed, mc_threshold(e.p), s);
@@ -3157,6 +3217,7 @@ static int mc_run(qbp_handle* h, const McCall& c, hipStream_t s)
     int rc = mc_prepare(h, c.Lx, c.k, s);
     if (rc) return rc;
     if (c.errors.kind == McErrors::PROBS && (rc = h->mc_in.prepare_thr((size_t)h->n, c.errors.probs, s)) != QBP_OK) return rc;
+    if (c.errors.kind == McErrors::ENUM && (rc = enum_prepare(h, c.errors.weight, s)) != QBP_OK) return rc;
     if (c.out == McCall::LLRHIST) {
         if ((rc = h->mc_in.prepare_edges(c.llr_bins, c.llr_lo, c.llr_hi, s)) != QBP_OK) return rc;
         // A workgroup keeps 32-bit counts, and one launch adds at most n per trial to a cell of one workgroup -- all of
@@ -3241,13 +3302,14 @@ static int mc_run_host(qbp_handle* h, McCall c, const double* prior, const uint8
     return st.finish(mc_run(h, c, h->stream));
 }
 
-// The three qbp_mc_sample_errors* entries: errors [T, n] of trials trial_begin .. + T, as the runs draw them.
+// The four qbp_mc_sample_errors* entries: errors [T, n] of trials trial_begin .. + T, as the runs draw them.
 static int mc_sample_host(qbp_handle* h, const McErrors& e, int64_t trial_begin, int64_t T, uint8_t* errors)
 {
     if (!h) return fail(QBP_E_INVALID, "null handle");
     if (T < 0) return fail(QBP_E_INVALID, "T must be >= 0");
     if (!errors) return fail(QBP_E_INVALID, "errors is null");
-    int rc = check_mc_errors(h, e, trial_begin);
+    // (a rank beyond 2^62 is refused before this sum is looked at)
+    int rc = check_mc_errors(h, e, trial_begin, trial_begin <= INT64_MAX - T ? trial_begin + T : INT64_MAX);
     if (rc) return rc;
     if (T == 0) return QBP_OK;
     if (T > ((int64_t)1 << 31)) return fail(QBP_E_INVALID, "at most 2^31 trials per call");
@@ -3255,6 +3317,7 @@ static int mc_sample_host(qbp_handle* h, const McErrors& e, int64_t trial_begin,
     HIP_TRY(on_device.err);
     hipStream_t s = h->stream;
     if (e.kind == McErrors::PROBS && (rc = h->mc_in.prepare_thr((size_t)h->n, e.probs, s)) != QBP_OK) return rc;
+    if (e.kind == McErrors::ENUM && (rc = enum_prepare(h, e.weight, s)) != QBP_OK) return rc;
     HIP_TRY(h->d_hard.reserve((size_t)T * (size_t)h->n));
     HIP_TRY(mc_sample(h, e, h->d_hard.p, T, trial_begin, s));
     HIP_TRY(hipMemcpyAsync(errors, h->d_hard.p, (size_t)T * (size_t)h->n, hipMemcpyDeviceToHost, s));
@@ -3339,6 +3402,44 @@ int qbp_mc_sample_errors_weight(qbp_handle* h, int32_t weight, uint64_t seed, in
                                 uint8_t* errors)
 try {
     return mc_sample_host(h, {McErrors::WEIGHT, 1, seed, 0.0, nullptr, weight}, trial_begin, T, errors);
+}
+QBP_ABI_CATCH
+
+int qbp_enum_count(int32_t n, int32_t weight, int64_t* count)
+try {
+    if (!count) return fail(QBP_E_INVALID, "count is null");
+    if (n < 0 || weight < 0 || weight > n) return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", weight, n);
+    int64_t c = 0;
+    if (!enum_count(n, weight, &c)) return fail(QBP_E_INVALID, "C(%d, %d) patterns are beyond 2^62", n, weight);
+    *count = c;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_enum_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t distance, int32_t weight,
+                           int64_t rank_begin, int64_t rank_end, const double* d_prior, int32_t max_iter,
+                           int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                           int64_t* d_counters, void* stream)
+try {
+    return mc_run_device(h, mc_call(Lx_host, k, distance, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin,
+                                    rank_end, {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters),
+                         stream);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_enum(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t distance, int32_t weight, int64_t rank_begin,
+                    int64_t rank_end, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                    double damping, double clip_llr, uint32_t flags, int64_t counters[QBP_NUM_COUNTERS])
+try {
+    return mc_run_host(h, mc_call(Lx, k, distance, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin, rank_end,
+                                  {max_iter, variant, alpha, damping, clip_llr, flags}), prior, nullptr, counters,
+                       nullptr, nullptr);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_sample_errors_enum(qbp_handle* h, int32_t weight, int64_t rank_begin, int64_t T, uint8_t* errors)
+try {
+    return mc_sample_host(h, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin, T, errors);
 }
 QBP_ABI_CATCH
 
@@ -3610,6 +3711,147 @@ try {
                                        variant, alpha, damping, clip_llr, flags, osd_method, osd_order,
                                        reinterpret_cast<uint64_t*>(d_pred), d_conv, reinterpret_cast<int64_t*>(d_cnt),
                                        h->stream));
+}
+QBP_ABI_CATCH
+
+// ---- failing patterns of an enumerated weight class (include/qbp.h: qbp_enum_failures) ----------------------------
+
+// Patterns per chunk of a qbp_enum_failures call over T ranks: the chunk of the Monte-Carlo entries, and with OSD no
+// more than the records of one shots call may take (16 GiB; QBP_MC_OSD_MAX_TRIALS is the largest chunk there is)
+static long long enum_failures_chunk(const qbp_handle* h, int64_t T, uint32_t flags)
+{
+    long long chunk = mc_chunk_trials(h, T);
+    if (flags & QBP_FLAG_OSD0)
+        chunk = std::min<long long>(chunk, (long long)(((size_t)16 << 30) / ((size_t)h->m + 10 * (size_t)h->n)));
+    return std::max<long long>(chunk, 1);
+}
+
+// Everything qbp_enum_failures refuses, host only and before any GPU work
+static int check_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin,
+                               int64_t rank_end, const double* prior, const double* host_prior, int32_t max_iter,
+                               int32_t variant, uint32_t flags, int32_t what, int64_t cap, const int64_t* ranks,
+                               const uint8_t* kinds, const int64_t* found, const int64_t* counters, int* osd_method,
+                               int* osd_order)
+{
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    int rc = check_enum_range(h, weight, rank_begin, rank_end);
+    if (rc) return rc;
+    if (what < 1 || what > 3) return fail(QBP_E_INVALID, "what = %d (need 1 logical, 2 unconverged, or 3 either)", what);
+    if (cap < 0) return fail(QBP_E_INVALID, "cap must be >= 0 (got %lld)", (long long)cap);
+    if (!found) return fail(QBP_E_INVALID, "found is null");
+    if (cap > 0 && (!ranks || !kinds)) return fail(QBP_E_INVALID, "ranks or kinds is null with cap > 0");
+    // the shots calls of the chunks: what qbp_decode_shots refuses (its rows are the handle's: Lx stands for them)
+    return check_shots_args(h, Lx, k, Lx, enum_failures_chunk(h, rank_end - rank_begin, flags), prior, host_prior, max_iter,
+                            variant, flags, counters, osd_method, osd_order);
+}
+
+// A checked call on the stream, every pointer but Lx_host a device pointer: chunk by chunk the enumeration, the shot
+// of every row, the launches of qbp_decode_shots, the capture.  Nothing returns to the host in between.
+static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
+                             int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int osd_method, int osd_order, int32_t what,
+                             int64_t cap, int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters,
+                             hipStream_t s)
+{
+    if (rank_end == rank_begin) return QBP_OK;
+    int rc = mc_prepare(h, Lx_host, k, s);
+    if (rc) return rc;
+    if ((rc = enum_prepare(h, weight, s)) != QBP_OK) return rc;
+    const long long chunk = enum_failures_chunk(h, rank_end - rank_begin, flags);
+    const size_t c = (size_t)chunk, n = (size_t)h->n, rb = ((size_t)h->m + 7) / 8;
+    HIP_TRY(h->d_weight_err.reserve(c * n));
+    HIP_TRY(h->d_enum_det.reserve(c * rb));
+    HIP_TRY(h->d_enum_actual.reserve(c));
+    HIP_TRY(h->d_enum_pred.reserve(c));
+    HIP_TRY(h->d_enum_conv.reserve(c));
+    for (int64_t a = rank_begin; a < rank_end; a += chunk) {
+        const long long t = std::min<long long>(chunk, rank_end - a);
+        HIP_TRY(qbp::launch_mc_enum_weight(h->d_weight_err.p, h->n, weight, t, a, h->d_binom.p, s));
+        HIP_TRY(qbp::launch_enum_pack(h->d_weight_err.p, t, h->m, h->n, h->d_row_ptr.p, h->d_col_idx.p,
+                                      h->mc_in.d_lx_cols.p, h->d_enum_det.p, h->d_enum_actual.p, s));
+        rc = decode_shots_impl(h, Lx_host, k, h->d_enum_det.p, reinterpret_cast<const uint64_t*>(h->d_enum_actual.p), t,
+                               d_prior, max_iter, variant, alpha, damping, clip_llr, flags, osd_method, osd_order,
+                               reinterpret_cast<uint64_t*>(h->d_enum_pred.p), h->d_enum_conv.p, d_counters, s);
+        if (rc) return rc;
+        HIP_TRY(qbp::launch_enum_capture(h->d_enum_pred.p, h->d_enum_actual.p, h->d_enum_conv.p, t, a, what, cap,
+                                         reinterpret_cast<long long*>(d_ranks), d_kinds,
+                                         reinterpret_cast<unsigned long long*>(d_found), s));
+    }
+    return QBP_OK;
+}
+
+int qbp_enum_failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
+                             int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap,
+                             int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream)
+try {
+    int osd_method = 0, osd_order = 0;
+    const int rc = check_enum_failures(h, Lx_host, k, weight, rank_begin, rank_end, d_prior, nullptr, max_iter, variant,
+                                       flags, what, cap, d_ranks, d_kinds, d_found, d_counters, &osd_method, &osd_order);
+    if (rc) return rc;
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    return enum_failures_run(h, Lx_host, k, weight, rank_begin, rank_end, d_prior, max_iter, variant, alpha, damping,
+                             clip_llr, flags, osd_method, osd_order, what, cap, d_ranks, d_kinds, d_found, d_counters,
+                             static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin, int64_t rank_end,
+                      const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
+                      double clip_llr, uint32_t flags, int32_t what, int64_t cap, int64_t* ranks, uint8_t* kinds,
+                      int64_t found[1], int64_t counters[QBP_NUM_COUNTERS])
+try {
+    int osd_method = 0, osd_order = 0;
+    int rc = check_enum_failures(h, Lx, k, weight, rank_begin, rank_end, prior, prior, max_iter, variant, flags, what,
+                                 cap, ranks, kinds, found, counters, &osd_method, &osd_order);
+    if (rc) return rc;
+    if (rank_end == rank_begin) { found[0] = 0; return QBP_OK; }
+    if (flags & QBP_FLAG_DENSE_F_COLSUM_ITER0) {     // (as qbp_decode_shots: judged on the host copy of the priors)
+        int mode = 0;
+        unsigned fl = flags;
+        rc = resolve_column_order(h, fl, prior, &mode);
+        if (rc) return rc;
+        if (mode == 0) flags = fl;
+    }
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    // (no more can be captured than the range holds)
+    const size_t room = (size_t)std::min<int64_t>(cap, rank_end - rank_begin);
+    std::vector<std::pair<long long, uint8_t>> hits;
+    unsigned long long n_found = 0;
+    {
+        HostStage st(h->stream);
+        const double* d_prior = st.in(h->d_prior, prior, (size_t)h->n);
+        long long* d_cnt = st.zeroed(h->d_counters, qbp::NUM_COUNTERS);
+        st.add(counters, d_cnt, qbp::NUM_COUNTERS);           // (ADDED to the caller's)
+        if (st.failed()) return st.error();
+        HIP_TRY(h->d_enum_ranks.reserve(room));
+        HIP_TRY(h->d_enum_kinds.reserve(room));
+        HIP_TRY(h->d_enum_found.reserve(1));
+        HIP_TRY(hipMemsetAsync(h->d_enum_found.p, 0, sizeof(unsigned long long), h->stream));
+        rc = st.finish(enum_failures_run(h, Lx, k, weight, rank_begin, rank_end, d_prior, max_iter, variant, alpha,
+                                         damping, clip_llr, flags, osd_method, osd_order, what, (int64_t)room,
+                                         reinterpret_cast<int64_t*>(h->d_enum_ranks.p), h->d_enum_kinds.p,
+                                         reinterpret_cast<int64_t*>(h->d_enum_found.p),
+                                         reinterpret_cast<int64_t*>(d_cnt), h->stream));
+        if (rc) return rc;
+    }
+    // (the stream is idle: finish synchronised)
+    HIP_TRY(hipMemcpy(&n_found, h->d_enum_found.p, sizeof(n_found), hipMemcpyDeviceToHost));
+    const size_t kept = (size_t)std::min<unsigned long long>(n_found, room);
+    std::vector<long long> r(kept);
+    std::vector<uint8_t> kd(kept);
+    if (kept) {
+        HIP_TRY(hipMemcpy(r.data(), h->d_enum_ranks.p, kept * sizeof(long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(kd.data(), h->d_enum_kinds.p, kept, hipMemcpyDeviceToHost));
+    }
+    hits.resize(kept);
+    for (size_t i = 0; i < kept; ++i) hits[i] = {r[i], kd[i]};
+    std::sort(hits.begin(), hits.end());                       // (ascending rank: specified when all were kept)
+    for (size_t i = 0; i < kept; ++i) { ranks[i] = hits[i].first; kinds[i] = hits[i].second; }
+    found[0] = (int64_t)n_found;
+    return QBP_OK;
 }
 QBP_ABI_CATCH
 

@@ -1067,6 +1067,91 @@ __global__ void mc_sample_weight_kernel(uint8_t* errors, int n, int w, long long
     }
 }
 
+// The weight-w enumeration (qbp_mc_run_enum, qbp_mc_sample_errors_enum; specification: include/qbp.h): row b of
+// errors [T][n] becomes the pattern of rank rank_begin + b in the lexicographic order of the ascending column tuples.
+// With D = C(n, w) - 1 - rank the rule of the header is the combinadic of D: for t = w .. 1 take the largest j below
+// the previous one with C(j, t) <= D, set column n - 1 - j and subtract C(j, t) (hockey stick: the sum over the
+// skipped columns is C(n - lo, t) - C(j + 1, t)).  binom [w + 1][n + 1] holds C(j, t) at t * (n + 1) + j, saturated at
+// 2^63 - 1 (every D is below 2^62); row t is monotone in j, so each step is a binary search in it.  One lane per
+// pattern, w searches and w byte stores; the row has to be ZERO on entry (launch_mc_enum_weight clears it).  j stays in
+// [t - 1, n - 1] whatever the table holds, so every store lands in the lane's own row.
+__global__ void mc_enum_weight_kernel(uint8_t* errors, int n, int w, long long T, long long rank_begin,
+                                      const unsigned long long* binom)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= T) return;
+    uint8_t* const row = errors + b * n;
+    const int stride = n + 1;
+    unsigned long long D = binom[(size_t)w * stride + n] - 1ull - (unsigned long long)(rank_begin + b);
+    int prev = n;
+    for (int t = w; t >= 1; --t) {
+        const unsigned long long* col = binom + (size_t)t * stride;
+        int lo = t - 1, hi = prev - 1;           // C(t - 1, t) = 0 <= D: the answer is in [lo, hi]
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (col[mid] <= D) lo = mid; else hi = mid - 1;
+        }
+        D -= col[lo];
+        row[n - 1 - lo] = 1;
+        prev = lo;
+    }
+}
+
+// qbp_enum_failures, between the enumeration and the shots launches: the shot of every error row.  Item (b, g) with
+// g < row_bytes packs checks 8 g .. 8 g + 7 of s = H e into byte g of det_bits [T][row_bytes] (stim's b8 layout,
+// mc_shot_bit), padding bits zero; item (b, row_bytes) is actual[b] = Lx e, bit l = logical operator l.
+__global__ void enum_pack_kernel(const uint8_t* errors, long long T, int m, int n, const int32_t* row_ptr,
+                                 const int32_t* col_idx, const unsigned long long* lx_cols, uint8_t* det_bits,
+                                 unsigned long long* actual)
+{
+    const int row_bytes = (m + 7) / 8;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * (row_bytes + 1)) return;
+    const long long b = i / (row_bytes + 1);
+    const int g = (int)(i - b * (row_bytes + 1));
+    const uint8_t* const row = errors + b * n;
+    if (g == row_bytes) {
+        unsigned long long a = 0ull;
+        for (int v = 0; v < n; ++v)
+            if (row[v] & 1) a ^= lx_cols[v];
+        actual[b] = a;
+        return;
+    }
+    unsigned bits = 0u;
+    for (int c = 8 * g; c < min(8 * g + 8, m); ++c) {
+        unsigned s = 0u;
+        for (int e = row_ptr[c]; e < row_ptr[c + 1]; ++e) s ^= row[col_idx[e]];
+        bits |= (s & 1u) << (c - 8 * g);
+    }
+    det_bits[b * row_bytes + g] = (uint8_t)bits;
+}
+
+// qbp_enum_failures, behind the shots launches: kind = (prediction != actual) | 2 (BP did not converge) of pattern
+// rank_begin + b; the patterns with kind & what are appended to ranks / kinds.  A wavefront counts its hits with one
+// ballot and reserves their places with one atomic on *found, which counts every hit; entries past cap are dropped.
+__global__ void enum_capture_kernel(const unsigned long long* predictions, const unsigned long long* actual,
+                                    const uint8_t* converged, long long T, long long rank_begin, int what,
+                                    long long cap, long long* ranks, uint8_t* kinds, unsigned long long* found)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    int kind = 0;
+    if (b < T) kind = (predictions[b] != actual[b] ? 1 : 0) | (converged[b] ? 0 : 2);
+    const bool hit = (kind & what) != 0;
+    const unsigned long long mask = __ballot(hit);
+    if (mask == 0ull) return;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int leader = __ffsll((long long)mask) - 1;
+    unsigned long long base = 0ull;
+    if (lane == leader) base = atomicAdd(found, (unsigned long long)__popcll(mask));
+    base = __shfl(base, leader);
+    if (!hit) return;
+    const unsigned long long pos = base + (unsigned long long)__popcll(mask & ((1ull << lane) - 1ull));
+    if (pos < (unsigned long long)cap) {
+        ranks[pos] = rank_begin + b;
+        kinds[pos] = (uint8_t)kind;
+    }
+}
+
 #endif  // QBP_DEFINE_KERNELS
 
 }  // namespace qbp

@@ -105,6 +105,17 @@ hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long 
 // rows of exactly `weight` ones (mc_sample_weight_kernel; 0 <= weight <= n); clears errors [T][n] first, on s
 hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
                                    unsigned long long seed, hipStream_t s);
+// row b = the weight-`weight` pattern of rank rank_begin + b (mc_enum_weight_kernel; 0 <= weight <= n); binom
+// [weight + 1][n + 1]: C(j, t) at t * (n + 1) + j, saturated; clears errors [T][n] first, on s
+hipError_t launch_mc_enum_weight(uint8_t* errors, int n, int weight, long long T, long long rank_begin,
+                                 const unsigned long long* binom, hipStream_t s);
+// qbp_enum_failures: the b8 syndrome row and the Lx word of every error row; the capture behind the shots launches
+hipError_t launch_enum_pack(const uint8_t* errors, long long T, int m, int n, const int32_t* row_ptr,
+                            const int32_t* col_idx, const unsigned long long* lx_cols, uint8_t* det_bits,
+                            unsigned long long* actual, hipStream_t s);
+hipError_t launch_enum_capture(const unsigned long long* predictions, const unsigned long long* actual,
+                               const uint8_t* converged, long long T, long long rank_begin, int what, long long cap,
+                               long long* ranks, uint8_t* kinds, unsigned long long* found, hipStream_t s);
 // qbp_tu_generic.hip (Monte-Carlo launches with G.det_bits go to the -DQBP_SHOTS_TU builds, with G.llr_hist to the
 // -DQBP_LLRHIST_TU builds, with G.spectrum to the
 // -DQBP_SPECTRUM_TU builds, with G.n_budgets to the

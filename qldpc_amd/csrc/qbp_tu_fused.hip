@@ -163,6 +163,39 @@ hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long
                        errors, n, weight, T, trial_begin, seed);
     return hipGetLastError();
 }
+
+hipError_t launch_mc_enum_weight(uint8_t* errors, int n, int weight, long long T, long long rank_begin,
+                                 const unsigned long long* binom, hipStream_t s)
+{
+    // (the buffer is the weight sampler's: cleared for the same reason)
+    hipError_t e = hipMemsetAsync(errors, 0, (size_t)T * (size_t)n, s);
+    if (e != hipSuccess || weight == 0) return e;
+    const int threads = 256;
+    hipLaunchKernelGGL(mc_enum_weight_kernel, dim3((unsigned)((T + threads - 1) / threads)), dim3(threads), 0, s,
+                       errors, n, weight, T, rank_begin, binom);
+    return hipGetLastError();
+}
+
+hipError_t launch_enum_pack(const uint8_t* errors, long long T, int m, int n, const int32_t* row_ptr,
+                            const int32_t* col_idx, const unsigned long long* lx_cols, uint8_t* det_bits,
+                            unsigned long long* actual, hipStream_t s)
+{
+    const long long items = T * ((m + 7) / 8 + 1);
+    const int threads = 256;
+    hipLaunchKernelGGL(enum_pack_kernel, dim3((unsigned)((items + threads - 1) / threads)), dim3(threads), 0, s,
+                       errors, T, m, n, row_ptr, col_idx, lx_cols, det_bits, actual);
+    return hipGetLastError();
+}
+
+hipError_t launch_enum_capture(const unsigned long long* predictions, const unsigned long long* actual,
+                               const uint8_t* converged, long long T, long long rank_begin, int what, long long cap,
+                               long long* ranks, uint8_t* kinds, unsigned long long* found, hipStream_t s)
+{
+    const int threads = 256;
+    hipLaunchKernelGGL(enum_capture_kernel, dim3((unsigned)((T + threads - 1) / threads)), dim3(threads), 0, s,
+                       predictions, actual, converged, T, rank_begin, what, cap, ranks, kinds, found);
+    return hipGetLastError();
+}
 #endif  // QBP_DEFINE_KERNELS
 
 }  // namespace qbp

@@ -25,6 +25,9 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
     python -m qldpc_amd.mc --code 144 --weights 4 6 8 10 12 --prior-p 0.01 --trials 1000000 --osd --ler-at 0.001 0.003 0.01
                                      (errors of fixed weight, and the LER at any p from their failure fractions:
                                       run_weights, ler_from_weights)
+    python -m qldpc_amd.mc --code 72 --enumerate 1 2 3 --prior-p 0.01 --osd --failures out.npz --failures-what either
+                                     (EVERY error of these weights: exact failure fractions and the failing patterns,
+                                      run_enumerate, enumerate.failing_patterns; with --weights one LER from both)
 """
 from __future__ import annotations
 
@@ -826,6 +829,100 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
     return all_reduce(table) if all_reduce is not None else table
 
 
+def _enumerate_on_device(dec, L, distance, weights, prior, rank, world, *, max_iter, variant, alpha, damping, clip_llr,
+                         osd, flags, device):
+    """One rank's share of the ranks of every weight class on the device, then the one all-reduce of the
+    [len(weights), 12] table (``_on_device`` with a range per point: a class has C(n, w) patterns)."""
+    import torch
+    from . import enumerate as enum_mod
+    dev = torch.device("cuda", device)
+    d_table = torch.zeros((len(weights), NUM_COUNTERS), dtype=torch.int64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
+    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD | _lib.FLAG_LSD)) else NO_STEP    # (per-trial records)
+    for w, d_out in zip(weights, d_table):
+        begin, end = shard_range(enum_mod.count(dec.n, w), rank, world)
+        for a in range(begin, end, step):
+            dec.mc_run_enum_device(L, distance, w, d_prior.data_ptr(), a, min(a + step, end), d_out.data_ptr(),
+                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                                   flags=flags, stream=stream)
+    if world > 1:
+        import torch.distributed as dist
+        dist.all_reduce(d_table)                     # the one RCCL collective of the run
+    torch.cuda.synchronize(dev)
+    return d_table.cpu().numpy()
+
+
+def run_enumerate(code_name, weights, *, prior_p, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
+                  clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0, world=1, device=0,
+                  runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None, lsd_large=False, quant=None):
+    """``run_weights`` on EVERY pattern of each weight instead of sampled ones (qbp_mc_run_enum): the C(n, w) patterns
+    of every w of ``weights`` in the order of ``enumerate.unrank``, each class sharded over ranks by
+    ``shard_range(C(n, w), rank, world)``; one all-reduce.  Row i of the GLOBAL table has [0] == C(n, weights[i]) exactly
+    and [1] / [0] is the exact f_w (``ler_from_weights(..., exact_weights=weights)``).  A class of more than 2^62
+    patterns is a ValueError.  ``runner(code, w, begin, end) -> int64[12]`` gets a rank range; the other keywords are
+    ``run_weights``'s."""
+    from . import enumerate as enum_mod
+    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
+    flags = quant_run_flags(flags, quant, layered, variant)
+    code = codes.load_code(code_name)
+    weights = check_weights(weights, code.n)
+    counts = [enum_mod.count(code.n, w) for w in weights]
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(code.Hx, device=device)
+        _configure_relay(dec, relay)
+        _configure_gd(dec, gd)
+        _configure_lsd(dec, lsd, lsd_large)
+        _configure_layered(dec, layered)
+        _configure_quant(dec, quant)
+        return _enumerate_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), rank, world,
+                                    max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                                    osd=osd, flags=flags, device=device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, (w, c) in enumerate(zip(weights, counts)):
+        table[i] = runner(code, w, *shard_range(c, rank, world))
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def run_enumerate_matrix(H, L, weights, *, prior, distance=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
+                         damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
+                         world=1, device=0, runner=None, all_reduce=None, lsd=None, lsd_large=False, quant=None):
+    """``run_enumerate`` for any matrix, as ``run_weights_matrix`` is ``run_weights`` for any matrix.
+    ``runner(H, L, w, prior, begin, end) -> int64[12]``."""
+    from . import enumerate as enum_mod
+    flags = lsd_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), lsd, lsd_large)
+    flags = quant_run_flags(flags, quant, False, variant)
+    L, _, prior, n = _dem_args(H, L, None, prior)
+    weights = check_weights(weights, n)
+    counts = [enum_mod.count(n, w) for w in weights]
+    if runner is None:
+        from . import bp
+        dec = bp.decoder_for(H, device=device)
+        _configure_lsd(dec, lsd, lsd_large)
+        _configure_quant(dec, quant)
+        return _enumerate_on_device(dec, L, distance, weights, prior, rank, world, max_iter=max_iter, variant=variant,
+                                    alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd, flags=flags, device=device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, (w, c) in enumerate(zip(weights, counts)):
+        table[i] = runner(H, L, w, prior, *shard_range(c, rank, world))
+    return all_reduce(table) if all_reduce is not None else table
+
+
+def merge_weight_tables(enum_table, enum_weights, sampled_table, sampled_weights):
+    """An enumerated table (``run_enumerate``) and a sampled one (``run_weights``) as one ``(table, weights)`` for
+    ``ler_from_weights`` -- pass ``exact_weights=enum_weights`` there.  A weight present in both is a ValueError."""
+    a, b = np.asarray(enum_table, np.int64), np.asarray(sampled_table, np.int64)
+    wa, wb = [int(w) for w in enum_weights], [int(w) for w in sampled_weights]
+    if a.ndim != 2 or b.ndim != 2 or a.shape[0] != len(wa) or b.shape[0] != len(wb) or a.shape[1] != b.shape[1]:
+        raise ValueError(f"tables of shapes {a.shape} and {b.shape} for {len(wa)} and {len(wb)} weights")
+    both = sorted(set(wa) & set(wb))
+    if both:
+        raise ValueError(f"weights {both} are enumerated and sampled: keep one of the two rows")
+    return np.concatenate([a, b]), wa + wb
+
+
 def binomial_weights(n, p):
     """B(n, w, p) = C(n, w) p^w (1 - p)^(n - w) for w = 0 .. n as float64[n + 1], through ``math.lgamma`` (n = 7776
     does not overflow)."""
@@ -842,7 +939,7 @@ def binomial_weights(n, p):
     return out
 
 
-def ler_from_weights(table, weights, n, ps):
+def ler_from_weights(table, weights, n, ps, exact_weights=()):
     """The logical error rate under uniform noise of rate p, for every p of ``ps``, from the counter table of a
     fixed-weight run (``run_weights``: row i = weight ``weights[i]``, [0] trials, [1] logical errors).  Returns a dict
     of float64 arrays over ``ps``:
@@ -850,9 +947,14 @@ def ler_from_weights(table, weights, n, ps):
       ``ler_high`` ler + sum of B(n, w, p) over the weights NOT sampled: those are unknown, not assumed zero
                    (``unsampled_mass`` is that sum);
       ``stderr``   sqrt(sum of B^2 f_w (1 - f_w) / trials_w), the binomial error of the sampled part;
-    and ``p`` itself.  A weight without trials counts as not sampled; a weight listed twice is a ValueError."""
+    and ``p`` itself.  A weight without trials counts as not sampled; a weight listed twice is a ValueError.
+    ``exact_weights``: weights of ``weights`` whose row is a whole enumerated class (``run_enumerate``): f_w is exact and
+    adds nothing to ``stderr``; its [0] must be C(n, w) (ValueError otherwise)."""
     table = np.asarray(table, np.int64)
     weights = check_weights(weights, n)
+    exact = set(check_weights(list(exact_weights), n)) if len(exact_weights) else set()
+    if not exact <= set(weights):
+        raise ValueError(f"exact_weights {sorted(exact - set(weights))} are not among the weights {weights!r}")
     if table.ndim != 2 or table.shape[0] != len(weights) or table.shape[1] < 2:
         raise ValueError(f"table must have shape ({len(weights)}, {NUM_COUNTERS}), got {table.shape}")
     if len(set(weights)) != len(weights):
@@ -863,10 +965,12 @@ def ler_from_weights(table, weights, n, ps):
     var = np.zeros(n + 1)                      # f (1 - f) / trials
     for w, row in zip(weights, table):
         t = int(row[0])
+        if w in exact and t != math.comb(n, w):
+            raise ValueError(f"weight {w} is listed as exact, but its row has {t} trials, not C({n}, {w}) = {math.comb(n, w)}")
         if t > 0:
             sampled[w] = True
             f[w] = int(row[1]) / t
-            var[w] = f[w] * (1.0 - f[w]) / t
+            var[w] = 0.0 if w in exact else f[w] * (1.0 - f[w]) / t
     out = {k: np.zeros(len(ps)) for k in ("ler", "ler_high", "stderr", "unsampled_mass")}
     out["p"] = ps
     for i, p in enumerate(ps):
@@ -979,10 +1083,20 @@ def main(argv=None):
     ap.add_argument("--weights", type=int, nargs="+", default=None,
                     help="errors of exactly these weights instead of --p (run_weights): a result line per weight; "
                          "needs --prior-p")
+    ap.add_argument("--enumerate", type=int, nargs="+", default=None, metavar="W",
+                    help="decode EVERY error of these weights (run_enumerate): exact failure fractions, a result line "
+                         "per weight; needs --prior-p; with --weights the two tables give one --ler-at estimate in "
+                         "which the enumerated weights carry no error bar")
+    ap.add_argument("--failures", default=None, metavar="OUT.npz",
+                    help="with --enumerate: also write the failing patterns of every enumerated weight (ranks, kinds, "
+                         "columns; enumerate.failing_patterns) to this .npz (flooding BP [+ --osd] only)")
+    ap.add_argument("--failures-what", choices=("logical", "unconverged", "either"), default="logical")
+    ap.add_argument("--failures-cap", type=int, default=1 << 20, metavar="N",
+                    help="with --failures: keep at most N patterns per weight")
     ap.add_argument("--prior-p", type=float, default=None,
-                    help="with --weights: the error rate the decoder's prior is built for")
+                    help="with --weights / --enumerate: the error rate the decoder's prior is built for")
     ap.add_argument("--ler-at", type=float, nargs="+", default=None, metavar="P",
-                    help="with --weights: print the logical error rate at these p (ler_from_weights)")
+                    help="with --weights / --enumerate: print the logical error rate at these p (ler_from_weights)")
     ap.add_argument("--draws", type=int, default=1, choices=(1, 2))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--variant", choices=("sum-product", "damped", "min-sum"), default="sum-product")
@@ -1144,21 +1258,34 @@ def main(argv=None):
             ap.error("--spectrum does not combine with --budgets")
         if not 1 <= args.max_iter <= _lib.MC_SPECTRUM_MAX_ITER:
             ap.error(f"--spectrum takes --max-iter in [1, {_lib.MC_SPECTRUM_MAX_ITER}]")
-    if args.weights is not None:
+    if args.weights is not None or args.enumerate is not None:
         if args.dem is not None or args.budgets is not None or args.spectrum is not None or args.shots is not None:
-            ap.error("--weights does not combine with --dem, --budgets, --spectrum or --shots")
+            ap.error("--weights / --enumerate do not combine with --dem, --budgets, --spectrum or --shots")
         if args.prior_p is None or not 0.0 < args.prior_p < 1.0:
-            ap.error("--weights needs --prior-p in (0, 1)")
+            ap.error("--weights / --enumerate need --prior-p in (0, 1)")
         if any(not 0.0 <= p <= 1.0 for p in args.ler_at or []):
             ap.error("--ler-at takes probabilities in [0, 1]")
         try:
-            check_weights(args.weights, codes.load_code(args.code).n)
-            if len(set(args.weights)) != len(args.weights):
+            n_code = codes.load_code(args.code).n
+            listed = check_weights((args.weights or []) + (args.enumerate or []), n_code)
+            if len(set(listed)) != len(listed):
                 raise ValueError("a weight is listed twice")
+            if args.enumerate is not None:
+                from . import enumerate as enum_mod
+                for w in args.enumerate:
+                    enum_mod.count(n_code, w)
         except ValueError as e:
-            ap.error(f"--weights: {e}")
-    elif args.prior_p is not None or args.ler_at is not None:
-        ap.error("--prior-p and --ler-at need --weights")
+            ap.error(f"--weights / --enumerate: {e}")
+        if args.enumerate is not None and (args.depolarizing is not None or args.phenomenological is not None
+                                           or args.window is not None):
+            ap.error("--enumerate does not combine with --depolarizing, --phenomenological or --window")
+        if args.failures is not None and (args.enumerate is None or relay is not None or gd is not None or lsd is not None
+                                          or args.layered or quant is not None):
+            ap.error("--failures needs --enumerate and flooding BP [+ --osd] (not --relay, --gd, --lsd, --layered, --quant)")
+        if args.failures_cap < 0:
+            ap.error("--failures-cap must be >= 0 (with --enumerate)")
+    elif args.prior_p is not None or args.ler_at is not None or args.failures is not None:
+        ap.error("--prior-p, --ler-at and --failures need --weights or --enumerate")
     dem_model = None
     if args.dem is not None:
         from . import dem
@@ -1295,6 +1422,57 @@ def main(argv=None):
             if args.out:
                 with open(args.out, "w") as f:
                     json.dump(result, f, indent=1)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+    if args.enumerate is not None:
+        from . import bp, enumerate as enum_mod
+        kw = {k: v for k, v in common.items() if k not in ("draws", "seed")}
+        stages = dict(relay=relay, layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, quant=quant)
+        code = codes.load_code(args.code)
+        t0 = time.perf_counter()
+        table = run_enumerate(args.code, args.enumerate, prior_p=args.prior_p, rank=rank, world=world, **stages, **kw)
+        dt = time.perf_counter() - t0
+        weights, exact = list(args.enumerate), list(args.enumerate)
+        if args.weights is not None:       # sampled weights beside the enumerated ones: one table for the LER
+            sampled = run_weights(args.code, args.weights, args.trials, prior_p=args.prior_p, seed=args.seed, rank=rank,
+                                  world=world, **stages, **kw)
+            table, weights = merge_weight_tables(table, exact, sampled, args.weights)
+        failures = {}
+        if args.failures is not None and rank == 0:      # (one GPU: a class this small needs no more)
+            fkw = {k: kw[k] for k in ("max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",
+                                      "osd_order", "osd_large", "device")}
+            for w in exact:
+                f = enum_mod.failing_patterns(code.Hx, code.Lx, w, prior=prior_of(args.prior_p, code.n),
+                                              what=args.failures_what, cap=args.failures_cap, **fkw)
+                failures.update({f"ranks_w{w}": f["ranks"], f"kinds_w{w}": f["kinds"], f"columns_w{w}": f["columns"],
+                                 f"found_w{w}": np.int64(f["found"])})
+                print(f"  weight={w}: {f['found']} failing patterns ({args.failures_what}), {len(f['ranks'])} kept")
+            np.savez(args.failures, weights=np.asarray(exact, np.int64), what=args.failures_what, **failures)
+            print(f"failing patterns written to {args.failures}")
+        if rank == 0:
+            rows, ler_rows = [], []
+            for w, row in zip(weights, table):
+                s = summarize(row)
+                s.update(weight=w, prior_p=args.prior_p, exact=w in exact)
+                rows.append(s)
+                print(f"  weight={w} ({'all ' + str(int(row[0])) + ' patterns' if w in exact else 'sampled'}): "
+                      f"f_w={s['ler']:.6e}, BP-only f_w={s['ler_bp_only']:.6e}, not converged={s['not_converged']}")
+            done = sum(int(table[i][0]) for i, w in enumerate(weights) if w in exact)
+            print(f"{len(exact)} weight classes, {done} patterns on {world} GPU(s): {dt:.3f} s")
+            if args.ler_at:
+                est = ler_from_weights(table, weights, code.n, args.ler_at, exact_weights=exact)
+                for i, p in enumerate(args.ler_at):
+                    ler_rows.append({k: float(est[k][i]) for k in ("p", "ler", "ler_high", "stderr", "unsampled_mass")})
+                    print(f"  p={p}: LER={est['ler'][i]:.6e} +- {est['stderr'][i]:.1e} (at most {est['ler_high'][i]:.6e}: "
+                          f"the weights not covered carry {est['unsampled_mass'][i]:.3e})")
+            if args.out:
+                with open(args.out, "w") as f:
+                    json.dump({"code": args.code, "enumerate": exact, "weights": args.weights, "prior_p": args.prior_p,
+                               "trials": args.trials, "max_iter": args.max_iter, "variant": args.variant, "osd": args.osd,
+                               "osd_method": args.osd_method, "osd_order": args.osd_order, "world_size": world,
+                               "seconds": dt, "points": rows, "ler": ler_rows}, f, indent=1)
         if world > 1:
             import torch.distributed as dist
             dist.destroy_process_group()
