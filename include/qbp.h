@@ -1162,6 +1162,54 @@ int qbp_css_mc_run_errors(qbp_css* css, const uint8_t* La, int32_t ka, const uin
                           const double* prior_b0, const double* prior_b1, int32_t max_iter, int32_t variant, double alpha,
                           double damping, double clip_llr, uint32_t flags, int64_t counters[3 * QBP_NUM_COUNTERS]);
 
+/* ---- Distance upper bound: randomized information-set search over ker H --------------------------------------------
+ * QDistRnd's algorithm (Pryadko, Shabashov, Kozin 2022): an upper bound on the weight of the lightest vector of ker H
+ * that a row of L detects -- the distance of one sector of a CSS code (H = Hx, L = Lx, or H = Hz, L = Lz), or the weight
+ * of the lightest undetectable logical fault of a detector error model (its H and L).  tests/distance_oracle.py states
+ * the same rules in numpy; the kernel (qbp_distance.hpp) reproduces them bit for bit.
+ *
+ * Inputs: H is the handle's matrix [m][n].  G [r][n] 0/1 bytes: every row in ker H, rows may be dependent (a basis of
+ * ker H makes the search complete; any subset still gives a valid bound).  L [k][n] 0/1 bytes, 1 <= k <= 64.  A 64-bit
+ * seed.  Global trial indices [trial_begin, trial_end).
+ *
+ * Trial t:
+ *   1. Column order.  key[v] = word v & 3 of Philox4x32-10 on the counter (lo32(t), hi32(t), v >> 2,
+ *      QBP_DISTANCE_PHILOX_STREAM) with the key (lo32(seed), hi32(seed)).  Counter word 3 is the stream: the Bernoulli
+ *      draws use 0 and 1, qbp_mc_run_weight 2, the Pauli sampler 3, this search 4.  The order is the columns sorted
+ *      ascending by (key[v], v).
+ *   2. Elimination.  Gauss-Jordan on a copy of G, columns in that order: the pivot of a column is the lowest not yet
+ *      used row with a 1 in it; if there is none the column is skipped; otherwise the pivot row is XORed into every
+ *      other row that has a 1 there and is marked used.  It stops when every row is used or the columns are exhausted.
+ *   3. Candidates.  For every row i of the reduced matrix: w_i its weight, lm_i the 64-bit mask whose bit l is
+ *      parity(L[l] & row_i).  The row is a candidate when lm_i != 0 (a zero row never is).
+ *   4. The trial's result is the candidate with the smallest (w_i, i); without a candidate the trial has no result.
+ *
+ * Call result: hist [n + 1] is ADDED to: hist[w] += 1 for every trial with a result.  result[4] is SET: the trials run,
+ * the smallest w (-1 if no trial had a result), the smallest trial index that reached it (-1), that trial's row i (-1).
+ * codeword [n]: that row as 0/1 bytes; logical_mask: its lm.  Either may be NULL; both are untouched when there is no
+ * result.  Results do not depend on the grid, the stream or how a range is split: the hist of two adjacent ranges adds
+ * up to the hist of their union, and the best of the union is the smaller (w, trial) of the two.
+ *
+ * Host pointers only; the call synchronises before it returns, like qbp_mc_run.  There is no _device form.  Before any
+ * GPU work the library checks through the handle's CSR that every row of G satisfies H g = 0, so the returned weight
+ * is a valid upper bound whatever the caller passed.
+ * QBP_E_INVALID, with every output untouched: a null h, G, L, result or hist; r < 1; k outside 1..64;
+ * trial_end < trial_begin, or more than 2^47 trials in one call; a row of G outside ker H.
+ * QBP_E_UNSUPPORTED, before any GPU work and with every output untouched: r > 2048 (a lane tracks its rows in a
+ * 32-bit mask, as in the LSD kernel), n > 65535 (16-bit column indices), or a trial state -- the sort keys, 8 bytes
+ * for each of the columns rounded up to a power of two, overlaid with the rows, 4 (n / 32 + 1) bytes each, plus two
+ * bytes per sorted column -- beyond 160 KiB of LDS.  There is no global-workspace build.
+ * trial_begin == trial_end succeeds with result = {0, -1, -1, -1}.
+ * One wavefront per trial, a grid-stride loop over the trials; QBP_OPT_BLOCKS_PER_CU sets the workgroups per CU, and
+ * QBP_INFO_THREADS, QBP_INFO_GRID and QBP_INFO_LDS_BYTES report the launch.  G and L are bit-packed once per call into
+ * buffers the handle owns.  codeword and logical_mask come from a second launch of one wavefront that repeats the
+ * best trial.
+ */
+#define QBP_DISTANCE_PHILOX_STREAM 4
+int qbp_distance_search(qbp_handle* h, const uint8_t* G, int32_t r, const uint8_t* L, int32_t k,
+                        uint64_t seed, int64_t trial_begin, int64_t trial_end,
+                        int64_t result[4], int64_t* hist, uint8_t* codeword, uint64_t* logical_mask);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

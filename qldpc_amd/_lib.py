@@ -178,6 +178,8 @@ SIGNATURES = {
     "qbp_lsd_configure": (C.c_int, [_VP, C.c_int32]),
     "qbp_lsd_batch": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     "qbp_lsd_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
+    "qbp_distance_search": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, _VP,
+                                      _VP]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
     "qbp_quant_configure": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32]),
@@ -910,6 +912,35 @@ class Decoder:
         """``lsd`` on device buffers (pointers as ints; d_stats may be 0), enqueued on `stream`."""
         _check(load().qbp_lsd_batch_device(self._h, d_syndromes, d_llr, d_hard, int(B), d_solution, d_stats or None,
                                            stream or None))
+
+    @_locked
+    def distance_search(self, G, L, trial_begin, trial_end, seed=0, hist=None, want_codeword=True):
+        """Randomized information-set search over ker H for the lightest vector a row of ``L`` detects
+        (qbp_distance_search; include/qbp.h states the trial).  ``G`` uint8[r, n]: rows of ker H (the library checks
+        them); ``L`` uint8[k, n], 1 <= k <= 64.  Returns ``(result int64[4], hist int64[n + 1], codeword uint8[n] or
+        None, logical_mask int or None)``: result = (trials run, smallest weight or -1, the first trial that reached
+        it, its row); ``hist`` is added to when given (in place), else starts from zero; the last two are None when
+        no trial had a result or ``want_codeword`` is False."""
+        G = np.ascontiguousarray(G, np.uint8)
+        L = np.ascontiguousarray(L, np.uint8)
+        if G.ndim != 2 or G.shape[1] != self.n:
+            raise ValueError(f"G must have shape (r, {self.n}), got {G.shape}")
+        if L.ndim != 2 or L.shape[1] != self.n:
+            raise ValueError(f"L must have shape (k, {self.n}), got {L.shape}")
+        if hist is None:
+            hist = np.zeros(self.n + 1, np.int64)
+        elif not (isinstance(hist, np.ndarray) and hist.dtype == np.int64 and hist.shape == (self.n + 1,)
+                  and hist.flags.c_contiguous):
+            raise ValueError(f"hist must be a contiguous int64 array of shape ({self.n + 1},)")
+        result = np.zeros(4, np.int64)
+        codeword = np.zeros(self.n, np.uint8) if want_codeword else None
+        mask = np.zeros(1, np.uint64) if want_codeword else None
+        _check(load().qbp_distance_search(self._h, G.ctypes.data, G.shape[0], L.ctypes.data, L.shape[0],
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, int(trial_begin), int(trial_end),
+                                          result.ctypes.data, hist.ctypes.data, _ptr(codeword), _ptr(mask)))
+        if not want_codeword or result[1] < 0:
+            return result, hist, None, None
+        return result, hist, codeword, int(mask[0])
 
     def mc_osd_step(self):
         """Trials one qbp_mc_run call may cover with FLAG_OSD0, FLAG_RELAY, FLAG_GD or FLAG_LSD (per-trial records:

@@ -26,6 +26,7 @@
 #include "qbp_cond.hpp"
 #include "qbp_lsd.hpp"
 #include "qbp_lsd_large.hpp"
+#include "qbp_distance.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_quant.hpp"
 #include "qbp_window.hpp"
@@ -414,6 +415,11 @@ struct qbp_handle {
     bool lsd_ready = false;
     int lsd_bits = 0;
     DevBuf<int32_t> d_lsd_col_row, d_lsd_stats;
+    // distance search (qbp_distance_search): the bit-packed rows of G and L of the call; its histogram, then the
+    // call's best word, the capture launch's two words and logical mask; the captured row
+    DevBuf<uint32_t> d_dist_gbits, d_dist_lbits;
+    DevBuf<long long> d_dist_out;
+    DevBuf<uint8_t> d_dist_codeword;
     // layered BP (qbp_layered_configure): the checks level after level, the level boundaries
     bool layered_ready = false;
     int layered_levels = 0, layered_max_width = 0;
@@ -2897,6 +2903,113 @@ try {
     int32_t* d_stats = st.out(h->d_lsd_stats, stats, b * 4);
     if (st.failed()) return st.error();
     return st.finish(qbp_lsd_batch_device(h, d_syn, d_llr, d_hard, B, d_sol, d_stats, h->stream));
+}
+QBP_ABI_CATCH
+
+// ---- Distance upper bound (qbp_distance.hpp) ------------------------------------------------------------------------
+// rows [count][n] 0/1 bytes -> [count][W] words, bit v & 31 of word v >> 5
+static std::vector<uint32_t> dist_pack_rows(const uint8_t* rows, size_t count, size_t n, size_t W)
+{
+    std::vector<uint32_t> bits(count * W, 0u);
+    for (size_t i = 0; i < count; ++i)
+        for (size_t v = 0; v < n; ++v)
+            if (rows[i * n + v] & 1u) bits[i * W + (v >> 5)] |= 1u << (v & 31);
+    return bits;
+}
+
+int qbp_distance_search(qbp_handle* h, const uint8_t* G, int32_t r, const uint8_t* L, int32_t k, uint64_t seed,
+                        int64_t trial_begin, int64_t trial_end, int64_t result[4], int64_t* hist, uint8_t* codeword,
+                        uint64_t* logical_mask)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (!G || !L || !result || !hist) return fail(QBP_E_INVALID, "null pointer");
+    if (r < 1) return fail(QBP_E_INVALID, "r = %d (need >= 1)", r);
+    if (k < 1 || k > 64) return fail(QBP_E_INVALID, "k must be in 1..64 (got %d)", k);
+    if (trial_end < trial_begin)
+        return fail(QBP_E_INVALID, "trial_end %lld < trial_begin %lld", (long long)trial_end, (long long)trial_begin);
+    const unsigned long long total = (unsigned long long)trial_end - (unsigned long long)trial_begin;
+    if (total > (1ull << qbp::DIST_TRIAL_BITS))
+        return fail(QBP_E_INVALID, "%llu trials in one call (at most 2^%d)", total, qbp::DIST_TRIAL_BITS);
+    const size_t n = (size_t)h->n;
+    const int W = (h->n + 31) / 32;
+    int NP = 4;
+    while (NP < h->n) NP <<= 1;
+    const size_t lds = (qbp::dist_lds_bytes(r, W, NP) + 15) & ~(size_t)15;
+    if (r > qbp::DIST_MAX_ROWS || h->n > qbp::DIST_MAX_COLS || lds > (size_t)160 * 1024)
+        return fail(QBP_E_UNSUPPORTED, "the distance search keeps the bit-packed rows of G and its sort keys in LDS: %d x %d "
+                                       "needs %zu B (limits: 160 KiB, %d rows, %d columns)",
+                    r, h->n, lds, qbp::DIST_MAX_ROWS, qbp::DIST_MAX_COLS);
+    // H g = 0 for every row g of G: what makes the weight found an upper bound
+    for (int i = 0; i < r; ++i) {
+        const uint8_t* g = G + (size_t)i * n;
+        for (int c = 0; c < h->m; ++c) {
+            unsigned par = 0;
+            for (int e = h->row_ptr[c]; e < h->row_ptr[c + 1]; ++e) par ^= g[h->col_idx[e]] & 1u;
+            if (par) return fail(QBP_E_INVALID, "row %d of G is not in ker H (check %d)", i, c);
+        }
+    }
+    if (total == 0) {
+        result[0] = 0; result[1] = result[2] = result[3] = -1;
+        return QBP_OK;
+    }
+    const std::vector<uint32_t> gbits = dist_pack_rows(G, (size_t)r, n, (size_t)W);
+    const std::vector<uint32_t> lbits = dist_pack_rows(L, (size_t)k, n, (size_t)W);
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    hipStream_t s = h->stream;
+    HostStage st(s);
+    qbp::DistParams P{};
+    P.r = r; P.n = h->n; P.W = W; P.NP = NP; P.k = k;
+    P.gbits = st.in(h->d_dist_gbits, gbits.data(), gbits.size());
+    P.lbits = st.in(h->d_dist_lbits, lbits.data(), lbits.size());
+    P.seed = seed; P.trial_begin = trial_begin; P.count = (long long)total;
+    // d_dist_out: hist [n + 1] | best | found [2] | logical mask
+    long long* d_out = st.zeroed(h->d_dist_out, n + 5);
+    if (st.failed()) return st.error();
+    HIP_TRY(h->d_dist_codeword.reserve(n));
+    P.hist = reinterpret_cast<unsigned long long*>(d_out);
+    P.best = P.hist + n + 1;
+    P.found = d_out + n + 2;
+    P.codeword = h->d_dist_codeword.p;
+    P.logical_mask = P.hist + n + 4;
+    HIP_TRY(hipMemsetAsync(P.best, 0xff, sizeof(unsigned long long), s));
+    // one wavefront per workgroup: as many per CU as the LDS holds, up to osd0_kernel's 32; QBP_OPT_BLOCKS_PER_CU overrides
+    long long per_cu = std::max<long long>(1, std::min<long long>(32, (long long)(((size_t)160 * 1024) / lds)));
+    if (h->opt_blocks_per_cu > 0) per_cu = h->opt_blocks_per_cu;
+    const long long grid = std::max<long long>(1, std::min<long long>((long long)total, (long long)h->num_cu * per_cu));
+    h->last_threads = 64; h->last_lds = (int)lds; h->last_grid = (int)grid;
+    HIP_TRY(qbp::launch_dist_search(false, P, (unsigned)grid, lds, s));
+    unsigned long long best = ~0ull;
+    HIP_TRY(hipMemcpyAsync(&best, P.best, sizeof(best), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    long long found[2] = {-1, -1};
+    unsigned long long lm = 0;
+    std::vector<uint8_t> row;
+    if (best != ~0ull) {
+        // the best trial once more, by one wavefront that stores its row: nothing races for codeword and logical_mask
+        P.trial_begin = trial_begin + (long long)(best & ((1ull << qbp::DIST_TRIAL_BITS) - 1ull));
+        P.count = 1;
+        HIP_TRY(qbp::launch_dist_search(true, P, 1u, lds, s));
+        row.resize(n);
+        HIP_TRY(hipMemcpyAsync(found, P.found, sizeof(found), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&lm, P.logical_mask, sizeof(lm), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(row.data(), P.codeword, n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (found[0] != (long long)(best >> qbp::DIST_TRIAL_BITS))
+            return fail(QBP_E_HIP, "the repeated trial %lld gave weight %lld, the search %llu", P.trial_begin, found[0],
+                        best >> qbp::DIST_TRIAL_BITS);
+    }
+    st.add(hist, d_out, n + 1);
+    const int rc = st.finish(QBP_OK);
+    if (rc) return rc;
+    result[0] = (int64_t)total;
+    result[1] = result[2] = result[3] = -1;
+    if (best != ~0ull) {
+        result[1] = found[0]; result[2] = P.trial_begin; result[3] = found[1];
+        if (codeword) std::memcpy(codeword, row.data(), n);
+        if (logical_mask) *logical_mask = lm;
+    }
+    return QBP_OK;
 }
 QBP_ABI_CATCH
 

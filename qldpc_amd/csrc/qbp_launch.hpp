@@ -25,6 +25,7 @@ struct CssClassify;
 struct LsdParams;
 struct LsdLargeWorkspace;
 struct WindowCommit;
+struct DistParams;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -199,6 +200,9 @@ hipError_t launch_lsd(bool records, const LsdParams& P, unsigned grid, size_t ld
 // lsd_large_kernel<records> (qbp_lsd_large.hpp): one workgroup of 256 threads per record, the rows in the workspace
 hipError_t launch_lsd_large(bool records, const LsdParams& P, const LsdLargeWorkspace& Wk, unsigned grid, size_t lds,
                             hipStream_t s);
+// qbp_tu_distance.hip: dist_search_kernel<capture> (qbp_distance.hpp), one wavefront per trial; capture: the launch
+// that repeats the call's best trial and stores its row
+hipError_t launch_dist_search(bool capture, const DistParams& P, unsigned grid, size_t lds, hipStream_t s);
 // qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)
 hipError_t launch_window_gather(const uint8_t* r, long long B, int m, const int32_t* checks, int mk, uint8_t* syn,
                                 hipStream_t s);

@@ -203,6 +203,16 @@ def _on_device(shape, priors, begin, end, step, launch, world, device):
 NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial records: one launch per point
 
 
+def _mc_code(code_name):
+    """``codes.load_code`` for the Monte-Carlo entries, which classify logical errors against ``distance // 2``: a
+    code without a distance (``codes.register`` of a new code) is refused here, before any GPU work."""
+    code = codes.load_code(code_name)
+    if code.distance is None:
+        raise ValueError(f"code {code.name!r} has no distance: run qldpc_amd.distance.estimate(code) first (it sets "
+                         f"code.distance to the upper bound it finds), or give one to codes.from_matrices")
+    return code
+
+
 def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
               alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0, osd_large=False, rank=0,
               world=1, device=0, runner=None, all_reduce=None, relay=None, layered=False, gd=None, lsd=None,
@@ -236,7 +246,7 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     flags = quant_run_flags(flags, quant, layered, variant)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     if runner is None:
         from . import bp
@@ -285,7 +295,7 @@ def run_depolarizing(code_name, ps, trials, *, osd=False, osd_method="cs", osd_o
     does not depend on the world size."""
     from . import bp, css
     flags = osd_run_flags(osd, osd_method, osd_order)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     rates = [pauli_rates(p, bias) for p in ps]         # (before any GPU work)
     priors = []
     for px, py, pz in rates:
@@ -511,7 +521,7 @@ def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.
     tests; by default the HIP library and torch.distributed."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     budgets = _lib.check_budgets(budgets)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
@@ -583,7 +593,7 @@ def run_llr_hist(code_name, p, trials, budgets, bins, llr_range, *, draws=1, see
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     budgets = _lib.check_budgets(budgets)
     bins, lo, hi = _lib.check_llr_hist(bins, *llr_range, len(budgets))
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
@@ -707,7 +717,7 @@ def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant
     injection points for the CPU tests; by default the HIP library and torch.distributed."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     max_iter = _check_spectrum_max_iter(max_iter)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
         from . import bp
@@ -782,7 +792,7 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     flags = quant_run_flags(flags, quant, layered, variant)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     weights = check_weights(weights, code.n)
     begin, end = shard_range(int(trials), rank, world)
     if runner is None:
@@ -866,7 +876,7 @@ def run_enumerate(code_name, weights, *, prior_p, max_iter=50, variant=_lib.SUM_
     flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
     flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
     flags = quant_run_flags(flags, quant, layered, variant)
-    code = codes.load_code(code_name)
+    code = _mc_code(code_name)
     weights = check_weights(weights, code.n)
     counts = [enum_mod.count(code.n, w) for w in weights]
     if runner is None:

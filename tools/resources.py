@@ -49,6 +49,8 @@ UNITS += [("qbp_tu_fused.hip", ["-DQBP_LLRHIST_TU"])] + [("qbp_tu_generic.hip", 
 # Fixed-point min-sum (qbp_quant_decode_batch, QBP_FLAG_QUANT): bp_quant_kernel<message type, mc> (after them, for the
 # same reason)
 UNITS += [("qbp_tu_quant.hip", [])]
+# Distance upper bound (qbp_distance_search): dist_search_kernel<capture> (after them, for the same reason)
+UNITS += [("qbp_tu_distance.hip", [])]
 
 
 def demangle(sym):
