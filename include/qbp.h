@@ -1198,7 +1198,9 @@ int qbp_css_mc_run_errors(qbp_css* css, const uint8_t* La, int32_t ka, const uin
  * QBP_E_UNSUPPORTED, before any GPU work and with every output untouched: r > 2048 (a lane tracks its rows in a
  * 32-bit mask, as in the LSD kernel), n > 65535 (16-bit column indices), or a trial state -- the sort keys, 8 bytes
  * for each of the columns rounded up to a power of two, overlaid with the rows, 4 (n / 32 + 1) bytes each, plus two
- * bytes per sorted column -- beyond 160 KiB of LDS.  There is no global-workspace build.
+ * bytes per sorted column -- beyond 160 KiB of LDS.  The bytes are what bounds n in effect: 10 bytes per sorted column
+ * let at most 16384 of them fit, so n <= 16384 (with at most 63 rows there: exactly 160 KiB), and the 65535 check never
+ * is the one that fires.  There is no global-workspace build.
  * trial_begin == trial_end succeeds with result = {0, -1, -1, -1}.
  * One wavefront per trial, a grid-stride loop over the trials; QBP_OPT_BLOCKS_PER_CU sets the workgroups per CU, and
  * QBP_INFO_THREADS, QBP_INFO_GRID and QBP_INFO_LDS_BYTES report the launch.  G and L are bit-packed once per call into

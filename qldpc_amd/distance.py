@@ -43,7 +43,8 @@ def bound(H, L, trials=4096, seed=0, device=None, rank=0, world=1) -> dict:
     bit l = ``L[l] . codeword``; both None without a result), ``trial`` (the first trial that reached the weight, -1),
     ``hist`` int64[n + 1] (trials by the weight they found) and ``trials`` (trials run).  With ``world > 1`` the
     result is this rank's shard: ``merge`` joins shards, in any order.  A matrix beyond the kernel's limits (2048
-    rows of ``ker H``, 65535 columns, 160 KiB of LDS) raises the library's ``QbpError`` (``E_UNSUPPORTED``)."""
+    rows of ``ker H``, 160 KiB of LDS -- in effect n <= 16384: 10 bytes per sorted column, the columns rounded up to a
+    power of two) raises the library's ``QbpError`` (``E_UNSUPPORTED``)."""
     from . import bp
     Hd = _dense(H)
     L = np.ascontiguousarray(_dense(L))

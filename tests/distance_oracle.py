@@ -15,6 +15,15 @@ Trial t:
   4. The trial's result is the candidate with the smallest (w_i, i); none: the trial has no result.
 Call: hist[w] += 1 per trial with a result (ADDED to); result = (trials run, smallest w or -1, smallest trial index that
 reached it or -1, that trial's row i or -1); codeword = that row, logical_mask = its lm (both untouched without a result).
+
+WRONG STATEMENTS.  ``trial`` and ``search`` take optional keyword arguments, each of which replaces one rule above by a
+defect a kernel could have; the defaults are the rules.  tests/test_distance_large_cpu.py uses them to show that a case
+tells the defect from the statement (a GPU comparison on that case then means something about it):
+  ties="descending"     step 1 orders equal keys by descending column
+  pivot_rows=R          step 2 never chooses a row >= R as a pivot
+  column_budget=C       step 2 stops after the first C columns of the order
+  candidate_rows=R      step 3 never considers a row >= R
+  weight_columns=C      step 3 counts w_i over the columns < C only
 """
 import numpy as np
 
@@ -34,21 +43,27 @@ def column_keys(seed, t, n):
     return np.stack(words, axis=-1).reshape(4 * n4)[:n]
 
 
-def column_order(seed, t, n):
-    return np.argsort(column_keys(seed, t, n), kind="stable")         # ties in the key: by column index
+def column_order(seed, t, n, ties="ascending"):
+    keys = column_keys(seed, t, n)
+    if ties == "descending":                      # (a wrong statement)
+        return (n - 1 - np.argsort(keys[::-1], kind="stable")).astype(np.int64)
+    assert ties == "ascending"
+    return np.argsort(keys, kind="stable")                            # ties in the key: by column index
 
 
-def reduce_rows(G, order):
-    """Step 2 -> the reduced matrix uint8[r][n]."""
+def reduce_rows(G, order, pivot_rows=None, column_budget=None):
+    """Step 2 -> the reduced matrix uint8[r][n].  (pivot_rows, column_budget: wrong statements.)"""
     A = (np.asarray(G).astype(np.uint8) & 1).copy()
     r = A.shape[0]
     used = np.zeros(r, bool)
     left = r
-    for c in order:
+    for c in order if column_budget is None else order[:column_budget]:
         if left == 0:
             break
         has = A[:, c] != 0
         cand = np.flatnonzero(has & ~used)
+        if pivot_rows is not None:
+            cand = cand[cand < pivot_rows]
         if cand.size == 0:
             continue
         p = int(cand[0])
@@ -65,29 +80,29 @@ def logical_masks(A, L):
     return [sum(1 << int(l) for l in np.flatnonzero(row)) for row in par]
 
 
-def trial(G, L, seed, t):
-    """The result of trial t: (w, i, row uint8[n], lm) or None."""
+def trial(G, L, seed, t, ties="ascending", pivot_rows=None, column_budget=None, candidate_rows=None, weight_columns=None):
+    """The result of trial t: (w, i, row uint8[n], lm) or None.  (The keyword arguments: wrong statements.)"""
     n = np.asarray(G).shape[1]
-    A = reduce_rows(G, column_order(seed, t, n))
-    w = A.sum(axis=1, dtype=np.int64)
+    A = reduce_rows(G, column_order(seed, t, n, ties), pivot_rows, column_budget)
+    w = A[:, :weight_columns].sum(axis=1, dtype=np.int64)
     lm = logical_masks(A, L)
     best = None
-    for i in range(A.shape[0]):
+    for i in range(A.shape[0] if candidate_rows is None else min(A.shape[0], candidate_rows)):
         if lm[i] and (best is None or (int(w[i]), i) < best[:2]):
             best = (int(w[i]), i, A[i].copy(), lm[i])
     return best
 
 
-def search(G, L, seed, trial_begin, trial_end, hist=None):
+def search(G, L, seed, trial_begin, trial_end, hist=None, **wrong):
     """The call -> dict(result int64[4], hist int64[n + 1] (``hist`` added to, a copy), codeword uint8[n] or None,
-    logical_mask int or None)."""
+    logical_mask int or None).  (``wrong``: the keyword arguments of ``trial``.)"""
     G, L = np.asarray(G), np.asarray(L)
     n = G.shape[1]
     assert L.ndim == 2 and L.shape[1] == n and 1 <= L.shape[0] <= 64 and G.shape[0] >= 1
     hist = np.zeros(n + 1, np.int64) if hist is None else np.array(hist, np.int64)
     best = None                                   # (w, t, i, row, lm)
     for t in range(int(trial_begin), int(trial_end)):
-        res = trial(G, L, seed, t)
+        res = trial(G, L, seed, t, **wrong)
         if res is None:
             continue
         w, i, row, lm = res
