@@ -1212,6 +1212,78 @@ int qbp_distance_search(qbp_handle* h, const uint8_t* G, int32_t r, const uint8_
                         uint64_t seed, int64_t trial_begin, int64_t trial_end,
                         int64_t result[4], int64_t* hist, uint8_t* codeword, uint64_t* logical_mask);
 
+/* ---- Circuit-level noise: Pauli-frame simulation of CSS circuits ---------------------------------------------------
+ * A circuit of resets, CNOTs and measurements in the Z and X bases with Pauli noise is run for T records at once:
+ * sampled shots (qbp_frame_sample) or enumerated single faults (qbp_frame_faults), one propagation, two injectors.
+ * The outputs have the layout qbp_decode_shots_device reads: b8 detection rows and uint64 observable masks.
+ * tests/circuit_oracle.py states the same rules in numpy; the kernels (qbp_frame.hpp) reproduce them bit for bit.
+ *
+ * The op table: ops [n_ops][4] int32, one row (kind, q0, q1, rate class) per target or pair, in circuit order; q1 is
+ * read for QBP_FRAME_CX and QBP_FRAME_DEP2 only, the rate class for the four noise kinds only.  Measurement rows are
+ * numbered 0, 1, ... in table order: the measurement record.  Noise rows are numbered 0, 1, ... in table order: the
+ * sites.  Site j has K possible faults with codes 1 .. K: K = 1 for QBP_FRAME_XERR (the Pauli X) and QBP_FRAME_ZERR
+ * (the Pauli Z), 3 for QBP_FRAME_DEP1 (code = Pauli: 1 X, 2 Z, 3 Y), 15 for QBP_FRAME_DEP2 (code & 3 is the Pauli on
+ * q0, code >> 2 the Pauli on q1).  Faults are numbered by site, then by code: site_base[j] = sum of K over the sites
+ * before j.  Detector c is the XOR of the record bits det_idx[det_ptr[c] .. det_ptr[c + 1]), observable l that of
+ * obs_idx[obs_ptr[l] .. obs_ptr[l + 1]) (CSR, 32-bit; an index listed twice cancels).
+ *
+ * One record: X and Z frame bits per qubit, all zero at the start; row after row
+ *   QBP_FRAME_RZ / _RX   clear both bits of q0;
+ *   QBP_FRAME_CX q0->q1  X[q1] ^= X[q0], then Z[q0] ^= Z[q1];
+ *   QBP_FRAME_MZ         the next record bit is X[q0];        QBP_FRAME_MX: the next record bit is Z[q0];
+ *   a noise row          if the injector puts a fault with Pauli P on qubit q here: X[q] ^= P & 1, Z[q] ^= P >> 1 & 1.
+ * Injectors:
+ *   sampling    for site j of shot t, u = word j % 4 of Philox4x32-10 on the counter (lo32(t), hi32(t), j / 4,
+ *               QBP_FRAME_PHILOX_STREAM) with the key (lo32(seed), hi32(seed)) -- counter word 3 is the stream, 0 to 4
+ *               are taken by the other samplers.  The site faults iff u < thr, thr = floor(rates[class] 2^32), and
+ *               then its code is 1 + (u K) / thr in 64-bit integer arithmetic.  rates [n_rates] (host, doubles): a
+ *               rate per class; a rate that is negative, >= 1 or NaN is refused, and so is a class >= n_rates.
+ *   enumeration record f is fault f: exactly that fault happens, at its site, and nothing else.
+ * Outputs, either may be NULL: det_bits [T][ceil(m / 8)], detector c of record t is bit c % 8 of byte
+ * t * ceil(m / 8) + c / 8 and the padding bits of a row's last byte are zero; obs [T], bit l = observable l.  Record t
+ * of a call is shot shot_begin + t or fault fault_begin + t: the rows do not depend on how a range is split into
+ * calls, on begin % 32, on the chunk or on the stream.
+ *
+ * qbp_frame_create checks the tables, numbers records and sites and uploads them; the handle is bound to one device
+ * and has the thread and stream rules of a qbp_handle.  The frame bits [2 nq] and the record bits of 32 records are
+ * one 32-bit word each, column `lane` of a global workspace the handle owns; records go through it chunk by chunk
+ * (QBP_FRAME_OPT_CHUNK_LANES lanes of 32 records, by default as many as 256 MiB hold, at most 2^20), every chunk one
+ * launch of frame_sim_kernel and one of frame_assemble_kernel.  The _device forms take device pointers for det_bits
+ * and obs and enqueue on `stream` without synchronising; the host forms synchronise before they return.
+ * QBP_E_INVALID, host only, before any GPU work and with every output untouched: a null handle, ops (with
+ * n_ops > 0), out, rates, or CSR array (with m > 0 or k > 0 respectively); nq < 1; a kind outside 0 .. 8; a qubit
+ * outside [0, nq); a QBP_FRAME_CX or QBP_FRAME_DEP2 row with q0 == q1; a rate class outside
+ * [0, QBP_FRAME_MAX_CLASSES); m < 0; a CSR pointer array that does not start at 0 or decreases; a record index outside
+ * the measurement record; k outside 0 .. 64; T < 0; shot_begin < 0 or shot_begin + T beyond 2^63 - 1; a fault range
+ * outside [0, faults]; a bad rate.  QBP_E_UNSUPPORTED: more than 2^32 - 4 sites or 2^31 - 1 measurements.
+ * T = 0 succeeds and changes nothing.
+ */
+#define QBP_FRAME_PHILOX_STREAM 5
+#define QBP_FRAME_MAX_CLASSES 16
+enum { QBP_FRAME_RZ = 0, QBP_FRAME_RX = 1, QBP_FRAME_CX = 2, QBP_FRAME_MZ = 3, QBP_FRAME_MX = 4, QBP_FRAME_XERR = 5,
+       QBP_FRAME_ZERR = 6, QBP_FRAME_DEP1 = 7, QBP_FRAME_DEP2 = 8 };
+enum { QBP_FRAME_INFO_QUBITS = 0, QBP_FRAME_INFO_SITES = 1, QBP_FRAME_INFO_FAULTS = 2, QBP_FRAME_INFO_RECORDS = 3,
+       QBP_FRAME_INFO_DETECTORS = 4, QBP_FRAME_INFO_OBSERVABLES = 5,
+       QBP_FRAME_INFO_CHUNK_LANES = 6,      /* lanes (of 32 records) a chunk holds at the most */
+       QBP_FRAME_INFO_WORKSPACE_BYTES = 7,  /* the workspace as the last call left it */
+       QBP_FRAME_INFO_CHUNKS = 8,           /* chunks of the last call */
+       QBP_FRAME_INFO_CLASSES = 9 };        /* 1 + the largest rate class of the table */
+enum { QBP_FRAME_OPT_CHUNK_LANES = 1 };     /* 0 = default; rounded up to a multiple of 64 (tests force several chunks) */
+typedef struct qbp_frame qbp_frame;
+int qbp_frame_create(int32_t nq, const int32_t* ops, int64_t n_ops, const int32_t* det_ptr, const int32_t* det_idx,
+                     int32_t m, const int32_t* obs_ptr, const int32_t* obs_idx, int32_t k, int32_t device,
+                     qbp_frame** out);
+void qbp_frame_destroy(qbp_frame* f);
+int qbp_frame_sample(qbp_frame* f, const double* rates, int32_t n_rates, uint64_t seed, int64_t shot_begin, int64_t T,
+                     uint8_t* det_bits, uint64_t* obs);
+int qbp_frame_sample_device(qbp_frame* f, const double* rates, int32_t n_rates, uint64_t seed, int64_t shot_begin,
+                            int64_t T, uint8_t* d_det_bits, uint64_t* d_obs, void* stream);
+int qbp_frame_faults(qbp_frame* f, int64_t fault_begin, int64_t T, uint8_t* det_bits, uint64_t* obs);
+int qbp_frame_faults_device(qbp_frame* f, int64_t fault_begin, int64_t T, uint8_t* d_det_bits, uint64_t* d_obs,
+                            void* stream);
+int qbp_frame_set_option(qbp_frame* f, int32_t option, int64_t value);
+int64_t qbp_frame_get_info(qbp_frame* f, int32_t what);
+
 /* Tuning / introspection. */
 enum {
     QBP_OPT_SLOTS_PER_BLOCK = 1, /* syndromes decoded concurrently by one workgroup (0 = auto) */

@@ -180,6 +180,15 @@ SIGNATURES = {
     "qbp_lsd_batch_device": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, _VP, _VP, _VP]),
     "qbp_distance_search": (C.c_int, [_VP, _VP, C.c_int32, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, _VP,
                                       _VP]),
+    "qbp_frame_create": (C.c_int, [C.c_int32, _VP, C.c_int64, _VP, _VP, C.c_int32, _VP, _VP, C.c_int32, C.c_int32,
+                                   C.POINTER(_VP)]),
+    "qbp_frame_destroy": (None, [_VP]),
+    "qbp_frame_sample": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP, _VP]),
+    "qbp_frame_sample_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP, _VP, _VP]),
+    "qbp_frame_faults": (C.c_int, [_VP, C.c_int64, C.c_int64, _VP, _VP]),
+    "qbp_frame_faults_device": (C.c_int, [_VP, C.c_int64, C.c_int64, _VP, _VP, _VP]),
+    "qbp_frame_set_option": (C.c_int, [_VP, C.c_int32, C.c_int64]),
+    "qbp_frame_get_info": (C.c_int64, [_VP, C.c_int32]),
     "qbp_layered_plan": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP]),
     "qbp_layered_configure": (C.c_int, [_VP, _VP]),
     "qbp_quant_configure": (C.c_int, [_VP, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32]),
@@ -323,7 +332,7 @@ def _preload_hip_runtime():
 
 def _missing(name):
     def fn(*args):
-        raise QbpError(f"{LIB_PATH} has no {name} (a build without sliding-window decoding)")
+        raise QbpError(f"{LIB_PATH} has no {name} (a build from before that entry point)")
     return fn
 
 
@@ -338,11 +347,12 @@ def load():
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name, None)
-            if (fn is None and (name.startswith(("qbp_window_", "qbp_quant_")) or name == "qbp_plan_r_layout")
+            if (fn is None and (name.startswith(("qbp_window_", "qbp_quant_", "qbp_frame_")) or name == "qbp_plan_r_layout")
                     and LIB_PATH != _DEFAULT_LIB_PATH):
                 # a QBP_LIB_PATH build from before sliding-window decoding (tools/bench_window.py times its
                 # whole-matrix path), from before the variable-major message layout (A/B runs against it) or from
-                # before fixed-point min-sum (tools/bench_quant.py times its double-precision rows on it):
+                # before fixed-point min-sum (tools/bench_quant.py times its double-precision rows on it), or from
+                # before the Pauli-frame simulator (tools/bench_circuit.py times run_dem on it):
                 # everything else works, such a call raises QbpError
                 setattr(lib, name, _missing(name))
                 continue
@@ -540,6 +550,80 @@ class WindowDecoder:
                                                err.shape[0], pr.ctypes.data, int(max_iter), int(variant), float(alpha),
                                                float(damping), float(clip_llr), int(flags), cnt.ctypes.data))
         return cnt
+
+
+FRAME_INFO = dict(qubits=0, sites=1, faults=2, records=3, detectors=4, observables=5, chunk_lanes=6, workspace_bytes=7,
+                  chunks=8, classes=9)                 # QBP_FRAME_INFO_*
+FRAME_OPT_CHUNK_LANES = 1
+
+
+class FrameSim:
+    """GPU Pauli-frame simulator of one circuit on one GPU (wraps a ``qbp_frame``; include/qbp.h states the rules).
+    ``ops`` int32 [rows, 4]: (kind, q0, q1, rate class) per target or pair; detectors and observables as CSR lists of
+    measurement-record indices (``circuit.Circuit`` builds all of it).  Methods taking host arrays are serialised per
+    object; the ``*_device`` methods only enqueue work."""
+
+    def __init__(self, nq, ops, det_ptr, det_idx, obs_ptr, obs_idx, device=0):
+        self.ops = np.ascontiguousarray(ops, np.int32).reshape(-1, 4)
+        self.det_ptr, self.det_idx = np.ascontiguousarray(det_ptr, np.int32), np.ascontiguousarray(det_idx, np.int32)
+        self.obs_ptr, self.obs_idx = np.ascontiguousarray(obs_ptr, np.int32), np.ascontiguousarray(obs_idx, np.int32)
+        self.m, self.k = self.det_ptr.size - 1, self.obs_ptr.size - 1
+        h = _VP()
+        _check(load().qbp_frame_create(int(nq), _ptr(self.ops), self.ops.shape[0], _ptr(self.det_ptr), _ptr(self.det_idx),
+                                       self.m, _ptr(self.obs_ptr), _ptr(self.obs_idx), self.k, int(device), C.byref(h)))
+        self._h = h
+        self.device = int(device)
+        self._lock = threading.RLock()
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.qbp_frame_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self, what):
+        return int(load().qbp_frame_get_info(self._h, FRAME_INFO[what]))
+
+    @_locked
+    def set_option(self, option, value):
+        _check(load().qbp_frame_set_option(self._h, int(option), int(value)))
+
+    def _outputs(self, T, want_det, want_obs):
+        det = np.zeros((int(T), (self.m + 7) // 8), np.uint8) if want_det else None
+        obs = np.zeros(int(T), np.uint64) if want_obs else None
+        return det, obs
+
+    @_locked
+    def sample(self, rates, T, seed=0, shot_begin=0, want_det=True, want_obs=True):
+        """Shots ``shot_begin .. shot_begin + T - 1`` (qbp_frame_sample) -> ``(det_bits uint8 [T, ceil(m / 8)], masks
+        uint64 [T])``; ``rates`` float64 per rate class."""
+        r = np.ascontiguousarray(rates, np.float64)
+        det, obs = self._outputs(T, want_det, want_obs)
+        _check(load().qbp_frame_sample(self._h, r.ctypes.data, r.size, int(seed), int(shot_begin), int(T), _ptr(det),
+                                       _ptr(obs)))
+        return det, obs
+
+    def sample_device(self, rates, T, d_det_bits, d_obs, seed=0, shot_begin=0, stream=0):
+        """``sample`` into device buffers (pointers as ints, either may be 0), enqueued on ``stream``."""
+        r = np.ascontiguousarray(rates, np.float64)
+        _check(load().qbp_frame_sample_device(self._h, r.ctypes.data, r.size, int(seed), int(shot_begin), int(T),
+                                              d_det_bits or None, d_obs or None, stream or None))
+
+    @_locked
+    def faults(self, fault_begin, T, want_det=True, want_obs=True):
+        """Single faults ``fault_begin .. fault_begin + T - 1`` (qbp_frame_faults): the rows of ``sample``'s layout."""
+        det, obs = self._outputs(T, want_det, want_obs)
+        _check(load().qbp_frame_faults(self._h, int(fault_begin), int(T), _ptr(det), _ptr(obs)))
+        return det, obs
+
+    def faults_device(self, fault_begin, T, d_det_bits, d_obs, stream=0):
+        _check(load().qbp_frame_faults_device(self._h, int(fault_begin), int(T), d_det_bits or None, d_obs or None,
+                                              stream or None))
 
 
 class CssDecoder:

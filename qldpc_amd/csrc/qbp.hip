@@ -27,6 +27,7 @@
 #include "qbp_lsd.hpp"
 #include "qbp_lsd_large.hpp"
 #include "qbp_distance.hpp"
+#include "qbp_frame.hpp"
 #include "qbp_layered.hpp"
 #include "qbp_quant.hpp"
 #include "qbp_window.hpp"
@@ -3012,6 +3013,266 @@ try {
     return QBP_OK;
 }
 QBP_ABI_CATCH
+
+// ---- Pauli-frame simulation of CSS circuits (include/qbp.h: qbp_frame_*; qbp_frame.hpp) ----------------------------
+struct qbp_frame {
+    int device = 0, nq = 0, m = 0, k = 0, n_classes = 0;
+    long long n_ops = 0, n_sites = 0, n_faults = 0, n_rec = 0;
+    DevBuf<int4> d_ops;
+    DevBuf<uint32_t> d_site_info;
+    DevBuf<long long> d_site_base;
+    DevBuf<int32_t> d_det_ptr, d_det_idx, d_obs_ptr, d_obs_idx;
+    DevBuf<uint32_t> d_work;                 // frame [2 nq][W] | rec [n_rec][W] of one chunk
+    DevBuf<uint8_t> d_out_det;               // host entries
+    DevBuf<unsigned long long> d_out_obs;
+    hipStream_t stream = nullptr;
+    int num_cu = 1;
+    long long opt_chunk_lanes = 0, last_chunks = 0;
+};
+
+void qbp_frame_destroy(qbp_frame* f)
+try {
+    if (!f) return;
+    DeviceScope on_device(f->device);
+    if (f->stream) { (void)hipStreamSynchronize(f->stream); (void)hipStreamDestroy(f->stream); }
+    delete f;
+}
+catch (...) {
+}
+
+// a CSR list of measurement-record indices: `what` names it in the message
+static int frame_check_csr(const int32_t* ptr, const int32_t* idx, int32_t rows, long long n_rec, const char* what)
+{
+    if (rows == 0) return QBP_OK;
+    if (!ptr) return fail(QBP_E_INVALID, "null %s pointer array", what);
+    if (ptr[0] != 0) return fail(QBP_E_INVALID, "%s_ptr[0] = %d (need 0)", what, ptr[0]);
+    for (int32_t c = 0; c < rows; ++c)
+        if (ptr[c + 1] < ptr[c]) return fail(QBP_E_INVALID, "%s_ptr decreases at %d", what, c);
+    if (ptr[rows] > 0 && !idx) return fail(QBP_E_INVALID, "null %s index array", what);
+    for (int32_t e = 0; e < ptr[rows]; ++e)
+        if (idx[e] < 0 || idx[e] >= n_rec)
+            return fail(QBP_E_INVALID, "%s_idx[%d] = %d is outside the %lld measurement records", what, e, idx[e], n_rec);
+    return QBP_OK;
+}
+
+int qbp_frame_create(int32_t nq, const int32_t* ops, int64_t n_ops, const int32_t* det_ptr, const int32_t* det_idx,
+                     int32_t m, const int32_t* obs_ptr, const int32_t* obs_idx, int32_t k, int32_t device,
+                     qbp_frame** out)
+try {
+    if (!out) return fail(QBP_E_INVALID, "out is null");
+    *out = nullptr;
+    if (nq < 1) return fail(QBP_E_INVALID, "nq = %d (need >= 1)", nq);
+    if (n_ops < 0 || (n_ops > 0 && !ops)) return fail(QBP_E_INVALID, "null op table or n_ops < 0");
+    if (m < 0) return fail(QBP_E_INVALID, "m = %d (need >= 0)", m);
+    if (k < 0 || k > 64) return fail(QBP_E_INVALID, "k must be in 0..64 (got %d)", k);
+    std::vector<int4> rows((size_t)n_ops);
+    std::vector<uint32_t> site_info;
+    std::vector<long long> site_base;
+    long long n_rec = 0, n_faults = 0;
+    int n_classes = 0;
+    for (int64_t i = 0; i < n_ops; ++i) {
+        const int32_t kind = ops[4 * i], q0 = ops[4 * i + 1], q1 = ops[4 * i + 2], cls = ops[4 * i + 3];
+        if (kind < QBP_FRAME_RZ || kind > QBP_FRAME_DEP2) return fail(QBP_E_INVALID, "op %lld: kind %d", (long long)i, kind);
+        const bool pair = kind == QBP_FRAME_CX || kind == QBP_FRAME_DEP2;
+        if (q0 < 0 || q0 >= nq || (pair && (q1 < 0 || q1 >= nq)))
+            return fail(QBP_E_INVALID, "op %lld: a qubit outside [0, %d)", (long long)i, nq);
+        if (pair && q0 == q1) return fail(QBP_E_INVALID, "op %lld: a pair of equal qubits (%d)", (long long)i, q0);
+        int4 r{kind, q0, pair ? q1 : 0, 0};
+        if (kind == QBP_FRAME_MZ || kind == QBP_FRAME_MX) {
+            if (n_rec >= 2147483647ll) return fail(QBP_E_UNSUPPORTED, "more than 2^31 - 1 measurements");
+            r.w = (int)n_rec++;
+        } else if (kind >= QBP_FRAME_XERR) {
+            if (cls < 0 || cls >= QBP_FRAME_MAX_CLASSES)
+                return fail(QBP_E_INVALID, "op %lld: rate class %d outside [0, %d)", (long long)i, cls, QBP_FRAME_MAX_CLASSES);
+            if (site_info.size() >= 4294967292ull) return fail(QBP_E_UNSUPPORTED, "more than 2^32 - 4 sites");
+            const uint32_t K = kind == QBP_FRAME_DEP1 ? 3u : kind == QBP_FRAME_DEP2 ? 15u : 1u;
+            const uint32_t fixed = kind == QBP_FRAME_XERR ? 1u : kind == QBP_FRAME_ZERR ? 2u : 0u;
+            r.w = (int)(uint32_t)site_info.size();
+            site_info.push_back(K | fixed << 4 | (uint32_t)cls << 8);
+            site_base.push_back(n_faults);
+            n_faults += K;
+            n_classes = std::max(n_classes, cls + 1);
+        }
+        rows[(size_t)i] = r;
+    }
+    int rc = frame_check_csr(det_ptr, det_idx, m, n_rec, "det");
+    if (rc) return rc;
+    if ((rc = frame_check_csr(obs_ptr, obs_idx, k, n_rec, "obs")) != QBP_OK) return rc;
+    struct Guard {
+        qbp_frame* f;
+        ~Guard() { if (f) qbp_frame_destroy(f); }
+    } guard{new qbp_frame()};
+    qbp_frame* f = guard.f;
+    f->device = device; f->nq = nq; f->m = m; f->k = k; f->n_classes = n_classes;
+    f->n_ops = n_ops; f->n_sites = (long long)site_info.size(); f->n_faults = n_faults; f->n_rec = n_rec;
+    site_info.resize((site_info.size() + 3) / 4 * 4 + 4, 0u);      // the sampler reads whole groups of four
+    site_base.push_back(n_faults);
+    DeviceScope on_device(device);
+    HIP_TRY(on_device.err);
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device));
+    f->num_cu = std::max(1, prop.multiProcessorCount);
+    HIP_TRY(f->d_ops.upload(rows));
+    HIP_TRY(f->d_site_info.upload(site_info));
+    HIP_TRY(f->d_site_base.upload(site_base));
+    HIP_TRY(f->d_det_ptr.upload(m ? std::vector<int32_t>(det_ptr, det_ptr + m + 1) : std::vector<int32_t>(1, 0)));
+    HIP_TRY(f->d_det_idx.upload(m ? std::vector<int32_t>(det_idx, det_idx + det_ptr[m]) : std::vector<int32_t>()));
+    HIP_TRY(f->d_obs_ptr.upload(k ? std::vector<int32_t>(obs_ptr, obs_ptr + k + 1) : std::vector<int32_t>(1, 0)));
+    HIP_TRY(f->d_obs_idx.upload(k ? std::vector<int32_t>(obs_idx, obs_idx + obs_ptr[k]) : std::vector<int32_t>()));
+    HIP_TRY(hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking));
+    guard.f = nullptr;
+    *out = f;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+// lanes of 32 records a chunk holds at the most: QBP_FRAME_OPT_CHUNK_LANES, else what 256 MiB of workspace hold
+static long long frame_chunk_lanes(const qbp_frame* f)
+{
+    const long long words = 2ll * f->nq + f->n_rec;
+    long long lanes = f->opt_chunk_lanes > 0 ? f->opt_chunk_lanes : ((256ll << 20) / 4) / words;
+    lanes = std::min<long long>(lanes, 1ll << 20);
+    return std::max<long long>(64, (lanes + 63) / 64 * 64);
+}
+
+// Everything a frame call refuses, host only; sample: the thresholds of the rates
+static int frame_check_call(qbp_frame* f, bool sample, const double* rates, int32_t n_rates, int64_t begin, int64_t T,
+                            unsigned thr[QBP_FRAME_MAX_CLASSES])
+{
+    if (!f) return fail(QBP_E_INVALID, "null frame simulator");
+    if (T < 0) return fail(QBP_E_INVALID, "T = %lld (need >= 0)", (long long)T);
+    if (begin < 0 || begin > INT64_MAX - T) return fail(QBP_E_INVALID, "a record range outside [0, 2^63)");
+    if (!sample) {
+        if (begin + T > f->n_faults)
+            return fail(QBP_E_INVALID, "faults [%lld, %lld) of %lld", (long long)begin, (long long)(begin + T), f->n_faults);
+        return QBP_OK;
+    }
+    if (!rates || n_rates < 0) return fail(QBP_E_INVALID, "null rates");
+    if (f->n_classes > n_rates)
+        return fail(QBP_E_INVALID, "the circuit has rate class %d, the call %d rates", f->n_classes - 1, n_rates);
+    for (int c = 0; c < QBP_FRAME_MAX_CLASSES; ++c) thr[c] = 0u;
+    for (int c = 0; c < n_rates; ++c) {
+        if (!(rates[c] >= 0.0 && rates[c] < 1.0)) return fail(QBP_E_INVALID, "rates[%d] = %g is not in [0, 1)", c, rates[c]);
+        if (c < QBP_FRAME_MAX_CLASSES) thr[c] = mc_threshold(rates[c]);
+    }
+    return QBP_OK;
+}
+
+// The chunks of one call, enqueued on s: per chunk frame_sim_kernel, then frame_assemble_kernel.
+static int frame_run(qbp_frame* f, bool sample, const unsigned* thr, uint64_t seed, int64_t begin, int64_t T,
+                     uint8_t* d_det_bits, uint64_t* d_obs, hipStream_t s)
+{
+    if (T == 0 || (!d_det_bits && !d_obs)) return QBP_OK;
+    DeviceScope on_device(f->device);
+    HIP_TRY(on_device.err);
+    const long long lanes_all = (T + 31) / 32, cap = frame_chunk_lanes(f);
+    const long long W = std::min<long long>(cap, (lanes_all + 63) / 64 * 64);
+    const long long words = 2ll * f->nq + f->n_rec;
+    HIP_TRY(f->d_work.reserve((size_t)(words * W)));
+    const long long rb = (f->m + 7) / 8;
+    qbp::FrameParams P{};
+    P.ops = f->d_ops.p; P.n_ops = f->n_ops; P.site_info = f->d_site_info.p; P.site_base = f->d_site_base.p;
+    P.nq = f->nq; P.n_rec = (int)f->n_rec; P.W = W;
+    P.frame = f->d_work.p; P.rec = f->d_work.p + 2ll * f->nq * W;
+    P.seed = seed;
+    if (sample) std::copy(thr, thr + QBP_FRAME_MAX_CLASSES, P.thr);
+    P.det_ptr = f->d_det_ptr.p; P.det_idx = f->d_det_idx.p; P.m = f->m;
+    P.obs_ptr = f->d_obs_ptr.p; P.obs_idx = f->d_obs_idx.p; P.k = f->k;
+    f->last_chunks = 0;
+    for (long long a = 0; a < T; a += 32 * W) {
+        const long long t = std::min<long long>(32 * W, T - a);
+        P.begin = (unsigned long long)begin + (unsigned long long)a;
+        P.T = t;
+        P.det_bits = d_det_bits && rb ? d_det_bits + a * rb : nullptr;
+        P.obs = d_obs ? reinterpret_cast<unsigned long long*>(d_obs) + a : nullptr;
+        HIP_TRY(qbp::launch_frame_sim(sample, P, s));
+        const long long items = (P.det_bits ? t * rb : 0) + (P.obs ? t : 0);
+        const long long grid = std::min<long long>((items + qbp::FRAME_THREADS - 1) / qbp::FRAME_THREADS, 16ll * f->num_cu);
+        if (grid > 0) HIP_TRY(qbp::launch_frame_assemble(P, (unsigned)grid, s));
+        ++f->last_chunks;
+    }
+    return QBP_OK;
+}
+
+static int frame_host(qbp_frame* f, bool sample, const unsigned* thr, uint64_t seed, int64_t begin, int64_t T,
+                      uint8_t* det_bits, uint64_t* obs)
+{
+    if (T == 0) return QBP_OK;
+    DeviceScope on_device(f->device);
+    HIP_TRY(on_device.err);
+    HostStage st(f->stream);
+    const size_t rb = (size_t)(f->m + 7) / 8;
+    uint8_t* d_det = rb ? st.out(f->d_out_det, det_bits, (size_t)T * rb) : nullptr;
+    unsigned long long* d_obs = st.out(f->d_out_obs, reinterpret_cast<unsigned long long*>(obs), (size_t)T);
+    if (st.failed()) return st.error();
+    return st.finish(frame_run(f, sample, thr, seed, begin, T, d_det, reinterpret_cast<uint64_t*>(d_obs), f->stream));
+}
+
+int qbp_frame_sample_device(qbp_frame* f, const double* rates, int32_t n_rates, uint64_t seed, int64_t shot_begin,
+                            int64_t T, uint8_t* d_det_bits, uint64_t* d_obs, void* stream)
+try {
+    unsigned thr[QBP_FRAME_MAX_CLASSES];
+    const int rc = frame_check_call(f, true, rates, n_rates, shot_begin, T, thr);
+    if (rc) return rc;
+    return frame_run(f, true, thr, seed, shot_begin, T, d_det_bits, d_obs, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_frame_sample(qbp_frame* f, const double* rates, int32_t n_rates, uint64_t seed, int64_t shot_begin, int64_t T,
+                     uint8_t* det_bits, uint64_t* obs)
+try {
+    unsigned thr[QBP_FRAME_MAX_CLASSES];
+    const int rc = frame_check_call(f, true, rates, n_rates, shot_begin, T, thr);
+    if (rc) return rc;
+    return frame_host(f, true, thr, seed, shot_begin, T, det_bits, obs);
+}
+QBP_ABI_CATCH
+
+int qbp_frame_faults_device(qbp_frame* f, int64_t fault_begin, int64_t T, uint8_t* d_det_bits, uint64_t* d_obs,
+                            void* stream)
+try {
+    const int rc = frame_check_call(f, false, nullptr, 0, fault_begin, T, nullptr);
+    if (rc) return rc;
+    return frame_run(f, false, nullptr, 0, fault_begin, T, d_det_bits, d_obs, static_cast<hipStream_t>(stream));
+}
+QBP_ABI_CATCH
+
+int qbp_frame_faults(qbp_frame* f, int64_t fault_begin, int64_t T, uint8_t* det_bits, uint64_t* obs)
+try {
+    const int rc = frame_check_call(f, false, nullptr, 0, fault_begin, T, nullptr);
+    if (rc) return rc;
+    return frame_host(f, false, nullptr, 0, fault_begin, T, det_bits, obs);
+}
+QBP_ABI_CATCH
+
+int qbp_frame_set_option(qbp_frame* f, int32_t option, int64_t value)
+try {
+    if (!f) return fail(QBP_E_INVALID, "null frame simulator");
+    if (option != QBP_FRAME_OPT_CHUNK_LANES) return fail(QBP_E_INVALID, "unknown frame option %d", option);
+    if (value < 0) return fail(QBP_E_INVALID, "QBP_FRAME_OPT_CHUNK_LANES = %lld (need >= 0)", (long long)value);
+    f->opt_chunk_lanes = value;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int64_t qbp_frame_get_info(qbp_frame* f, int32_t what)
+try {
+    if (!f) return -1;
+    switch (what) {
+    case QBP_FRAME_INFO_QUBITS: return f->nq;
+    case QBP_FRAME_INFO_SITES: return f->n_sites;
+    case QBP_FRAME_INFO_FAULTS: return f->n_faults;
+    case QBP_FRAME_INFO_RECORDS: return f->n_rec;
+    case QBP_FRAME_INFO_DETECTORS: return f->m;
+    case QBP_FRAME_INFO_OBSERVABLES: return f->k;
+    case QBP_FRAME_INFO_CHUNK_LANES: return frame_chunk_lanes(f);
+    case QBP_FRAME_INFO_WORKSPACE_BYTES: return (int64_t)(f->d_work.cap * sizeof(uint32_t));
+    case QBP_FRAME_INFO_CHUNKS: return f->last_chunks;
+    case QBP_FRAME_INFO_CLASSES: return f->n_classes;
+    default: return -1;
+    }
+}
+catch (...) { return -1; }
 
 // ---- Monte-Carlo (include/qbp.h: qbp_mc_run*) --------------------------------------------------------------------
 

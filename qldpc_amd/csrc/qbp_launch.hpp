@@ -26,6 +26,7 @@ struct LsdParams;
 struct LsdLargeWorkspace;
 struct WindowCommit;
 struct DistParams;
+struct FrameParams;
 
 // (row weight, column weight) shapes the on-chip kernel is instantiated for: every code of the
 // reference's codes/ is (6, 3); (8, 4) covers their space-time matrices (spaceTime.py: row weight
@@ -203,6 +204,10 @@ hipError_t launch_lsd_large(bool records, const LsdParams& P, const LsdLargeWork
 // qbp_tu_distance.hip: dist_search_kernel<capture> (qbp_distance.hpp), one wavefront per trial; capture: the launch
 // that repeats the call's best trial and stores its row
 hipError_t launch_dist_search(bool capture, const DistParams& P, unsigned grid, size_t lds, hipStream_t s);
+// qbp_tu_frame.hip: frame_sim_kernel<sample> (qbp_frame.hpp), one lane per 32 records of the chunk P.W lanes wide, and
+// frame_assemble_kernel, which turns the chunk's measurement records into detector rows and observable masks
+hipError_t launch_frame_sim(bool sample, const FrameParams& P, hipStream_t s);
+hipError_t launch_frame_assemble(const FrameParams& P, unsigned grid, hipStream_t s);
 // qbp_tu_window.hip: the glue kernels of sliding-window decoding (qbp_window.hpp)
 hipError_t launch_window_gather(const uint8_t* r, long long B, int m, const int32_t* checks, int mk, uint8_t* syn,
                                 hipStream_t s);

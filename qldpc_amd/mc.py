@@ -14,6 +14,8 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
     python -m qldpc_amd.mc --dem circuit.dem --trials 1000000 --osd      (detector error model: run_dem)
     python -m qldpc_amd.mc --dem circuit.dem --shots dets.b8 --obs obs.b8 --osd --predictions-out pred.npy
                                      (decode RECORDED shots to observable predictions: run_shots)
+    python -m qldpc_amd.mc --circuit 72 6 --p 0.001 0.002 --shots 1000000 --osd [--basis X]
+                                     (circuit-level noise: the memory experiment sampled and decoded on the device: run_circuit)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 --llr-hist 128 -30 30 --out ladder.json
@@ -496,6 +498,57 @@ def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant
     cnt = np.asarray(cnt, np.int64)
     cnt = all_reduce(cnt) if all_reduce is not None else cnt
     return cnt, np.asarray(pred, np.uint64), np.asarray(conv, bool)
+
+
+def run_circuit(code, rounds, ps, shots, *, basis="Z", idle=True, detectors="basis", rates=None, seed=0, max_iter=50,
+                variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs", osd_order=0,
+                osd_large=False, flags=0, chunk=None, rank=0, world=1, device=0, reduce=True):
+    """Logical error rate of a CSS code under circuit-level noise (studies/studyComplete.py:72-109 without stim): the
+    memory experiment ``circuit.memory_experiment(code, rounds, basis, idle, detectors)`` and its detector error model
+    ``circuit.circuit_dem`` are built once; per point p the rates are ``{every class: p}`` (or ``rates[i]``, rates per
+    class as ``circuit.rates_array`` takes them, one entry per point) and the prior is ``dem_prior(dem.probs(rates))``.
+    Per chunk of shots qbp_frame_sample_device samples detection rows and observable masks on the device and
+    qbp_decode_shots_device decodes them with the masks as the recorded observables: nothing returns to the host
+    between chunks.  Returns the GLOBAL int64 [points, 12] counters of ``run_shots`` (LER = [1] / [0]); the shot range
+    is split over ranks with ``shard_range`` and the counters do not depend on ``chunk``, rank or world.
+    ``flags``: further decoder flags, or-ed with the OSD flags.  ``reduce=False``: this rank's counters, without the
+    all-reduce (tests add the ranks up themselves)."""
+    from . import bp, circuit as circuit_mod
+    flags = int(flags) | osd_run_flags(osd, osd_method, osd_order, osd_large)     # (before any GPU work)
+    ps = [float(p) for p in ps]
+    if rates is not None and len(rates) != len(ps):
+        raise ValueError(f"rates must have one entry per point ({len(ps)}), got {len(rates)}")
+    if int(max_iter) < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    cir = circuit_mod.memory_experiment(code, rounds, basis=basis, idle=idle, detectors=detectors)
+    point_rates = [circuit_mod.rates_array(p if rates is None else rates[i], cir.n_classes) for i, p in enumerate(ps)]
+    import torch
+    cdem = circuit_mod.circuit_dem(cir, device=device)
+    sim = cir.simulator(device)
+    dec = bp.decoder_for(cdem.H, device=device)
+    rb = (cdem.H.shape[0] + 7) // 8
+    step = min(dec.mc_osd_step() if (flags & _lib.FLAG_OSD0) else 1 << 20, 1 << 20)     # OSD keeps per-shot records
+    if chunk is not None:
+        step = max(1, min(step, int(chunk)))
+    begin, end = shard_range(int(shots), rank, world)
+    dev = torch.device("cuda", device)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
+    d_det = torch.zeros(max(min(step, end - begin), 1) * max(rb, 1), dtype=torch.uint8, device=dev)
+    d_obs = torch.zeros(max(min(step, end - begin), 1), dtype=torch.int64, device=dev)
+    d_priors = [torch.from_numpy(dem_prior(cdem.probs(r))).to(dev) for r in point_rates]
+    for i, r in enumerate(point_rates):
+        for a in range(begin, end, step):
+            t = min(step, end - a)
+            sim.sample_device(r, t, d_det.data_ptr(), d_obs.data_ptr(), seed=seed, shot_begin=a, stream=stream)
+            dec.decode_shots_device(cdem.L, d_det.data_ptr(), d_obs.data_ptr(), t, d_priors[i].data_ptr(), 0, 0,
+                                    d_table[i].data_ptr(), max_iter=max_iter, variant=variant, alpha=alpha,
+                                    damping=damping, clip_llr=clip_llr, flags=flags, stream=stream)
+    if world > 1 and reduce:
+        import torch.distributed as dist
+        dist.all_reduce(d_table)
+    torch.cuda.synchronize(dev)
+    return d_table.cpu().numpy()
 
 
 def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, draws, seed, variant, alpha, damping,
@@ -1046,6 +1099,17 @@ def rework_results(experiment, trials=10000, *, max_iter=100, osd=True, osd_meth
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--code", default="[[288, 12, 18]]")
+    ap.add_argument("--circuit", nargs=2, default=None, metavar=("CODE", "ROUNDS"),
+                    help="circuit-level noise: the memory experiment of CODE over ROUNDS rounds, sampled and decoded on the "
+                         "device (run_circuit); takes --p (every rate class), --shots N (a count here, not a file), "
+                         "--basis, --no-idle, --osd*, --max-iter, --variant, --alpha, --seed, --out")
+    ap.add_argument("--basis", default="Z", choices=("Z", "X"), help="--circuit: the memory basis")
+    ap.add_argument("--no-idle", action="store_true", help="--circuit: no idle noise")
+    ap.add_argument("--detectors", default="basis", choices=("basis", "all"),
+                    help="--circuit: detectors of the memory basis only, or of both check types")
+    ap.add_argument("--rates", type=float, nargs=4, default=None, metavar=("RESET", "CNOT", "IDLE", "MEAS"),
+                    help="--circuit: a rate per class instead of p for every class (one --p point, which then only labels "
+                         "the row)")
     ap.add_argument("--dem", default=None,
                     help="detector error model file (stim's text format) instead of --code / --p: run_dem")
     ap.add_argument("--phenomenological", nargs=2, default=None, metavar=("CODE", "ROUNDS"),
@@ -1171,6 +1235,37 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order, args.osd_large)
     except ValueError as e:
         ap.error(str(e))
+    if args.circuit is not None:
+        if args.p is None or args.shots is None or not str(args.shots).isdigit():
+            ap.error("--circuit needs --p and --shots N (with --circuit, --shots is a count, not a file of recorded shots)")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--circuit runs on one GPU from the command line (mc.run_circuit takes rank= and world=)")
+        if args.rates is not None and len(args.p) != 1:
+            ap.error("--rates needs exactly one --p point")
+        for name in ("dem", "obs", "budgets", "spectrum", "weights", "depolarizing", "relay", "gd", "lsd", "layered", "quant",
+                     "window", "enumerate", "phenomenological"):
+            if getattr(args, name, None) not in (None, False):
+                ap.error(f"--circuit does not combine with --{name}")
+        try:
+            rounds = int(args.circuit[1])
+            table = run_circuit(args.circuit[0], rounds, args.p, int(args.shots), basis=args.basis, idle=not args.no_idle,
+                                detectors=args.detectors,
+                                rates=None if args.rates is None else [args.rates],
+                                seed=args.seed, max_iter=args.max_iter, alpha=args.alpha,
+                                variant={"sum-product": _lib.SUM_PRODUCT, "damped": _lib.DAMPED_SP,
+                                         "min-sum": _lib.MIN_SUM}[args.variant],
+                                damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
+                                osd_order=args.osd_order, osd_large=args.osd_large)
+        except (ValueError, KeyError) as e:
+            ap.error(f"--circuit: {e}")
+        result = {"circuit": args.circuit[0], "rounds": rounds, "basis": args.basis, "detectors": args.detectors,
+                  "rates": args.rates, "shots": int(args.shots),
+                  "points": [dict(p=p, **summarize(row)) for p, row in zip(args.p, table)]}
+        print(json.dumps(result))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(result, f)
+        return 0
     for name in ("relay", "gd", "layered"):
         if getattr(args, name + "_large") and getattr(args, name) in (None, False):
             ap.error(f"--{name}-large needs --{name}")

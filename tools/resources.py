@@ -51,6 +51,8 @@ UNITS += [("qbp_tu_fused.hip", ["-DQBP_LLRHIST_TU"])] + [("qbp_tu_generic.hip", 
 UNITS += [("qbp_tu_quant.hip", [])]
 # Distance upper bound (qbp_distance_search): dist_search_kernel<capture> (after them, for the same reason)
 UNITS += [("qbp_tu_distance.hip", [])]
+# Pauli-frame simulation (qbp_frame_*): frame_sim_kernel<sample> and frame_assemble_kernel (after them, for the same reason)
+UNITS += [("qbp_tu_frame.hip", [])]
 
 
 def demangle(sym):
