@@ -1031,7 +1031,15 @@ class Decoder:
         m + 10 n bytes)."""
         return max(1, min(MC_OSD_MAX_TRIALS, (8 << 30) // (self.m + 10 * self.n)))
 
-    def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, step=None,
+    def mc_step(self, flags, whole, n_budgets=1):
+        """Trials one Monte-Carlo or shot call may cover: with FLAG_OSD0, FLAG_RELAY, FLAG_GD or FLAG_LSD it keeps
+        per-trial records, ``n_budgets`` of them in a ladder call, so ``mc_osd_step() // n_budgets`` (at least 1);
+        without them ``whole``, the caller's whole range (at least 1: the value is the step of a ``range``)."""
+        if int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD):
+            return max(1, self.mc_osd_step() // int(n_budgets))
+        return max(1, int(whole))
+
+    def _mc_sampled(self, fn, Lx, distance, source, trial_begin, trial_end, prior, limit, decoder, outputs, n_budgets=1,
                     after=()):
         """The host form ``fn`` of a sampled Monte-Carlo entry over [trial_begin, trial_end): ``source`` are its
         arguments between distance and the range, ``limit`` those between the prior and the variant, ``decoder`` is
@@ -1045,15 +1053,15 @@ class Decoder:
             raise ValueError(f"prior must have shape ({self.n},)")
         variant, alpha, damping, clip_llr, flags = decoder
         begin, end = int(trial_begin), int(trial_end)
-        # with OSD a call keeps per-trial records on the device: split long ranges
-        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(end - begin, 1)
+        step = self.mc_step(flags, end - begin, n_budgets)
         for a in range(begin, end, step):
             _check(getattr(load(), fn)(self._h, Lx.ctypes.data, Lx.shape[0], int(distance), *source, a, min(a + step, end),
                                        pr.ctypes.data, *limit, int(variant), float(alpha), float(damping),
                                        float(clip_llr), int(flags), *after, *(o.ctypes.data for o in outputs)))
         return outputs
 
-    def _mc_stored(self, fn, Lx, distance, errors, prior, max_iter, decoder, tables=(), rows=None, after=(), step=None):
+    def _mc_stored(self, fn, Lx, distance, errors, prior, max_iter, decoder, tables=(), rows=None, after=(),
+                   n_budgets=1):
         """The host form ``fn`` of a stored-error entry on error patterns uint8[T, n]: the counters, summed over the
         parts of a long list (a call SETS its counters); ``tables`` are added to by every part.  ``max_iter``: the
         limit, or the tuple of arguments that stands in its place (a ladder: budgets, their number) with ``rows``
@@ -1067,7 +1075,7 @@ class Decoder:
         shape = NUM_COUNTERS if rows is None else (int(rows), NUM_COUNTERS)
         limit = max_iter if isinstance(max_iter, tuple) else (int(max_iter),)
         total = np.zeros(shape, np.int64)
-        step = (step or self.mc_osd_step()) if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(len(err), 1)
+        step = self.mc_step(flags, len(err), n_budgets)
         for a in range(0, len(err), step):
             part = np.zeros(shape, np.int64)
             chunk = err[a:a + step]
@@ -1298,7 +1306,7 @@ class Decoder:
             raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
         pred = np.zeros(T, np.uint64)
         conv = np.zeros(T, np.uint8)
-        step = self.mc_osd_step() if (int(flags) & (FLAG_OSD0 | FLAG_RELAY | FLAG_GD | FLAG_LSD)) else max(T, 1)
+        step = self.mc_step(flags, T)
         for a in range(0, T, step):
             b = min(a + step, T)
             _check(load().qbp_decode_shots(
@@ -1319,7 +1327,7 @@ class Decoder:
 
     def mc_budgets_step(self, n_budgets):
         """Trials one qbp_mc_run_budgets call may cover with FLAG_OSD0: the records are kept per budget."""
-        return max(1, self.mc_osd_step() // int(n_budgets))
+        return self.mc_step(FLAG_OSD0, 0, n_budgets)
 
     @_locked
     def mc_run_budgets(self, Lx, distance, probs, prior, budgets, trial_begin, trial_end, draws=1, seed=0,
@@ -1331,7 +1339,7 @@ class Decoder:
         return self._mc_sampled("qbp_mc_run_budgets", Lx, distance, (probs.ctypes.data, int(draws), int(seed)),
                                 trial_begin, trial_end, prior, (bud.ctypes.data, len(bud)),
                                 (variant, alpha, damping, clip_llr, flags),
-                                [np.zeros((len(bud), NUM_COUNTERS), np.int64)], step=self.mc_budgets_step(len(bud)))[0]
+                                [np.zeros((len(bud), NUM_COUNTERS), np.int64)], n_budgets=len(bud))[0]
 
     def mc_run_budgets_device(self, Lx, distance, probs, d_prior, budgets, trial_begin, trial_end, d_counters,
                               draws=1, seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
@@ -1370,7 +1378,7 @@ class Decoder:
                                       trial_begin, trial_end, prior, (bud.ctypes.data, len(bud)),
                                       (variant, alpha, damping, clip_llr, flags),
                                       [np.zeros((len(bud), NUM_COUNTERS), np.int64), hist],
-                                      step=self.mc_budgets_step(len(bud)), after=(lo, hi, bins)))
+                                      n_budgets=len(bud), after=(lo, hi, bins)))
 
     def mc_run_llr_hist_device(self, Lx, distance, probs, d_prior, budgets, bins, llr_range, trial_begin, trial_end,
                                d_counters, d_hist, draws=1, seed=0, variant=SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -1396,7 +1404,7 @@ class Decoder:
         hist = self._llr_hist_table(len(bud), bins, hist)
         total = self._mc_stored("qbp_mc_run_errors_llr_hist", Lx, distance, errors, prior, (bud.ctypes.data, len(bud)),
                                 (variant, alpha, damping, clip_llr, flags), (hist,), rows=len(bud), after=(lo, hi, bins),
-                                step=self.mc_budgets_step(len(bud)))
+                                n_budgets=len(bud))
         return total, hist
 
     @_locked

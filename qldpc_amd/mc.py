@@ -34,6 +34,7 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
 from __future__ import annotations
 
 import argparse
+import collections
 import json
 import math
 import os
@@ -44,6 +45,7 @@ import numpy as np
 from . import _lib, codes
 
 NUM_COUNTERS = _lib.NUM_COUNTERS
+_VARIANTS = {"sum-product": _lib.SUM_PRODUCT, "damped": _lib.DAMPED_SP, "min-sum": _lib.MIN_SUM}   # (--variant)
 
 
 def shard_range(trials: int, rank: int, world: int):
@@ -181,28 +183,47 @@ def _configure_quant(dec, quant):
         dec.quant_configure(quant_mod.as_config(quant))
 
 
-def _on_device(shape, priors, begin, end, step, launch, world, device):
-    """One rank's slice [begin, end) of a run on the device, then the ONE all-reduce of its int64 table of ``shape``
-    (zeroed here; returned as a numpy array).  A point per entry of ``priors``, each owning an equal share of the
-    table: ``launch(i, d_prior, a, b, d_out, stream)`` enqueues trials [a, b) of point i, which add to the share at
-    address ``d_out``; ``step`` trials at the most per launch."""
+def _stages(variant, *, osd=False, osd_method="cs", osd_order=0, osd_large=False, relay=None, layered=False, gd=None,
+            lsd=None, lsd_large=False, quant=None):
+    """The decoder stages of a run, stated once: ``(flags, configure)`` -- the flags word of its calls, and
+    ``configure(dec)``, which sets a decoder up for them.  Every ValueError of a bad value or combination is raised
+    here, before any GPU work.  A driver that takes fewer stages passes fewer keywords."""
+    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
+    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
+    flags = quant_run_flags(flags, quant, layered, variant)
+
+    def configure(dec):
+        _configure_relay(dec, relay)
+        _configure_gd(dec, gd)
+        _configure_lsd(dec, lsd, lsd_large)
+        _configure_layered(dec, layered)
+        _configure_quant(dec, quant)
+    return flags, configure
+
+
+def _on_device(shape, priors, ranges, step, launch, world, device, reduce=True):
+    """One rank's share of a run on the device, then the ONE all-reduce of its int64 table of ``shape`` (zeroed here;
+    returned as a numpy array; ``reduce=False``: this rank's table as it is).  A point per entry of ``priors``, each
+    owning an equal share of the table; ``ranges``: this rank's ``(begin, end)`` -- a tuple, the same for every point
+    -- or a list of them, one per point.  ``launch(i, d_prior, a, b, d_out, stream)`` enqueues trials [a, b) of point
+    i, which add to the share at address ``d_out``; ``step`` trials at the most per launch
+    (``Decoder.mc_step``)."""
     import torch
     dev = torch.device("cuda", device)
     d_table = torch.zeros(shape, dtype=torch.int64, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     d_priors = [torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev) for prior in priors]
     shares = d_table.view(len(priors), d_table.numel() // max(len(priors), 1))
-    for i, (d_prior, d_out) in enumerate(zip(d_priors, shares)):
+    if isinstance(ranges, tuple):
+        ranges = [ranges] * len(priors)
+    for i, (d_prior, d_out, (begin, end)) in enumerate(zip(d_priors, shares, ranges)):
         for a in range(begin, end, step):
             launch(i, d_prior.data_ptr(), a, min(a + step, end), d_out.data_ptr(), stream)
-    if world > 1:
+    if world > 1 and reduce:
         import torch.distributed as dist
         dist.all_reduce(d_table)                     # the one RCCL collective of the run
     torch.cuda.synchronize(dev)
     return d_table.cpu().numpy()
-
-
-NO_STEP = 1 << 40        # without OSD or Relay a call keeps no per-trial records: one launch per point
 
 
 def _mc_code(code_name):
@@ -245,29 +266,23 @@ def run_sweep(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant=_l
     ``osd_method`` ("cs" or "e"; include/qbp.h).
     `runner(code, p, begin, end) -> int64[12]` and `all_reduce(int64 array) -> int64 array`
     are injection points for the CPU tests; by default the HIP library and torch.distributed."""
-    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
-    flags = quant_run_flags(flags, quant, layered, variant)
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               relay=relay, layered=layered, gd=gd, lsd=lsd, lsd_large=lsd_large, quant=quant)
     code = _mc_code(code_name)
-    table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
+    begin, end = shard_range(trials, rank, world)
     if runner is None:
         from . import bp
         dec = bp.decoder_for(code.Hx, device=device)
-        _configure_relay(dec, relay)
-        _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_layered(dec, layered)
-        _configure_quant(dec, quant)
-        step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
+        configure(dec)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_device(code.Lx, code.distance, ps[i], d_prior, a, b, d_out, draws=draws, seed=seed,
                               max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
                               flags=flags, stream=stream)
-        return _on_device((len(ps), NUM_COUNTERS), [prior_of(p, code.n) for p in ps], *shard_range(trials, rank, world),
-                          step, launch, world, device)
+        return _on_device((len(ps), NUM_COUNTERS), [prior_of(p, code.n) for p in ps], (begin, end),
+                          dec.mc_step(flags, end - begin), launch, world, device)
+    table = np.zeros((len(ps), NUM_COUNTERS), np.int64)
     for i, p in enumerate(ps):
-        begin, end = shard_range(trials, rank, world)
         table[i] = runner(code, p, begin, end)
     return all_reduce(table) if all_reduce is not None else table
 
@@ -349,6 +364,29 @@ def _dem_args(H, L, probs, prior):
     return L, probs, prior, n
 
 
+# What a run decodes, resolved once from a code name or from a matrix: H [m, n], L [k, n], the distance of the
+# miscorrected / incorrectable split, n, and per point the sampler's argument (``probs``: an error rate, or a
+# probability per column; None where the entry samples by other means) and the decoder's LLRs (``priors``).
+_Model = collections.namedtuple("_Model", "H L distance n probs priors")
+
+
+def _code_model(code, ps):
+    """The model of a built-in or registered code (``_mc_code``): its X sector, a point per error rate of ``ps``."""
+    return _Model(code.Hx, code.Lx, code.distance, code.n, [float(p) for p in ps], [prior_of(p, code.n) for p in ps])
+
+
+def _matrix_model(H, L, probs, prior, distance):
+    """The one-point model of a matrix with observables (``_dem_args`` checks and completes it)."""
+    L, probs, prior, n = _dem_args(H, L, probs, prior)
+    return _Model(H, L, distance, n, [probs], [prior])
+
+
+def _bind(runner, *lead):
+    """An injected ``runner`` with its leading arguments (the code and rate, or the matrix and its tables) bound: what
+    the shared body of a pair of drivers calls.  None stays None: the HIP library runs."""
+    return None if runner is None else lambda *args: runner(*lead, *args)
+
+
 def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
             variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
             osd_order=0, osd_large=False, rank=0, world=1, device=0, runner=None, all_reduce=None, relay=None,
@@ -368,11 +406,11 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
     ``window``: ``(W, F)`` -- the sliding-window decoder (qbp_window_mc_run_probs; ``window.py``) with the round of
     every check in ``check_round``; "not_converged" then counts the trials with a window BP did not converge on.  Not
     together with ``relay``, ``layered``, ``gd`` or ``lsd``.  Sharded and reduced exactly like the plain path."""
-    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
-    flags = quant_run_flags(flags, quant, layered, variant)
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               relay=relay, layered=layered, gd=gd, lsd=lsd, lsd_large=lsd_large, quant=quant)
     L, probs, prior, n = _dem_args(H, L, probs, prior)
     begin, end = shard_range(int(trials), rank, world)
+    extra = {}                          # (what a window adds to the runner's arguments)
     if window is not None:
         if relay is not None or gd is not None or (layered is not None and layered is not False):
             raise ValueError("window= runs flooding BP [+ OSD] inside a window: not with relay, layered or gd")
@@ -383,33 +421,24 @@ def run_dem(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max
         if check_round is None:
             raise ValueError("window= needs check_round, the round of every check of H")
         W, F = (int(x) for x in window)
-        if runner is None:
-            from . import window as window_mod
-            wdec = window_mod.decoder_for(H, check_round, W, F, device=device)
-
-            def launch(i, d_prior, a, b, d_out, stream):
-                wdec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed,
-                                         max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                         clip_llr=clip_llr, flags=flags, stream=stream)
-            return _on_device((NUM_COUNTERS,), [prior], begin, end, NO_STEP, launch, world, device)
-        cnt = np.asarray(runner(H, L, probs, prior, begin, end, window=(W, F), check_round=check_round), np.int64)
-        return all_reduce(cnt) if all_reduce is not None else cnt
+        extra = dict(window=(W, F), check_round=check_round)
     if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        _configure_relay(dec, relay)
-        _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_layered(dec, layered)
-        _configure_quant(dec, quant)
-        step = dec.mc_osd_step() if osd or any(x is not None for x in (relay, gd, lsd)) else NO_STEP   # (per-trial records)
+        if window is None:
+            from . import bp
+            dec = bp.decoder_for(H, device=device)
+            configure(dec)
+            step = dec.mc_step(flags, end - begin)
+        else:
+            from . import window as window_mod
+            dec = window_mod.decoder_for(H, check_round, W, F, device=device)
+            step = max(end - begin, 1)          # (one call: the window entry splits a long range into chunks itself)
 
         def launch(i, d_prior, a, b, d_out, stream):
             dec.mc_run_probs_device(L, distance, probs, d_prior, a, b, d_out, draws=draws, seed=seed, max_iter=max_iter,
                                     variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
                                     stream=stream)
-        return _on_device((NUM_COUNTERS,), [prior], begin, end, step, launch, world, device)
-    cnt = np.asarray(runner(H, L, probs, prior, begin, end), np.int64)
+        return _on_device((NUM_COUNTERS,), [prior], (begin, end), step, launch, world, device)
+    cnt = np.asarray(runner(H, L, probs, prior, begin, end, **extra), np.int64)
     return all_reduce(cnt) if all_reduce is not None else cnt
 
 
@@ -475,25 +504,19 @@ def run_shots(H, L, detections, observables=None, *, prior, max_iter=50, variant
         from . import bp
         dec = bp.decoder_for(H, device=device)
         dev = torch.device("cuda", device)
-        stream = torch.cuda.current_stream(dev)
-        d_cnt = torch.zeros(NUM_COUNTERS, dtype=torch.int64, device=dev)
-        d_prior = torch.from_numpy(prior).to(dev)
         d_det = torch.from_numpy(det[begin:end]).to(dev)
         d_act = torch.from_numpy(masks[begin:end].view(np.int64)).to(dev) if masks is not None else None
         d_pred = torch.zeros(end - begin, dtype=torch.int64, device=dev)
         d_conv = torch.zeros(end - begin, dtype=torch.uint8, device=dev)
-        step = dec.mc_osd_step() if (flags & _lib.FLAG_OSD0) else 1 << 40     # OSD keeps per-shot records
-        for a in range(0, end - begin, step):
-            t = min(step, end - begin - a)
-            dec.decode_shots_device(L, d_det.data_ptr() + a * rb, d_act.data_ptr() + 8 * a if d_act is not None else 0,
-                                    t, d_prior.data_ptr(), d_pred.data_ptr() + 8 * a, d_conv.data_ptr() + a,
-                                    d_cnt.data_ptr(), max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                    clip_llr=clip_llr, flags=flags, stream=stream.cuda_stream)
-        if world > 1:
-            import torch.distributed as dist
-            dist.all_reduce(d_cnt)
-        torch.cuda.synchronize(dev)
-        return d_cnt.cpu().numpy(), d_pred.cpu().numpy().view(np.uint64), d_conv.cpu().numpy().astype(bool)
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            o = a - begin                                     # (the per-shot buffers hold this rank's slice only)
+            dec.decode_shots_device(L, d_det.data_ptr() + o * rb, d_act.data_ptr() + 8 * o if d_act is not None else 0,
+                                    b - a, d_prior, d_pred.data_ptr() + 8 * o, d_conv.data_ptr() + o, d_out,
+                                    max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                                    flags=flags, stream=stream)
+        cnt = _on_device((NUM_COUNTERS,), [prior], (begin, end), dec.mc_step(flags, end - begin), launch, world, device)
+        return cnt, d_pred.cpu().numpy().view(np.uint64), d_conv.cpu().numpy().astype(bool)
     cnt, pred, conv = runner(H, L, det, masks, prior, begin, end)
     cnt = np.asarray(cnt, np.int64)
     cnt = all_reduce(cnt) if all_reduce is not None else cnt
@@ -527,39 +550,40 @@ def run_circuit(code, rounds, ps, shots, *, basis="Z", idle=True, detectors="bas
     sim = cir.simulator(device)
     dec = bp.decoder_for(cdem.H, device=device)
     rb = (cdem.H.shape[0] + 7) // 8
-    step = min(dec.mc_osd_step() if (flags & _lib.FLAG_OSD0) else 1 << 20, 1 << 20)     # OSD keeps per-shot records
+    step = min(dec.mc_step(flags, 1 << 20), 1 << 20)      # (a chunk's detection rows are a buffer: capped in any case)
     if chunk is not None:
         step = max(1, min(step, int(chunk)))
     begin, end = shard_range(int(shots), rank, world)
     dev = torch.device("cuda", device)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    d_table = torch.zeros((len(ps), NUM_COUNTERS), dtype=torch.int64, device=dev)
     d_det = torch.zeros(max(min(step, end - begin), 1) * max(rb, 1), dtype=torch.uint8, device=dev)
     d_obs = torch.zeros(max(min(step, end - begin), 1), dtype=torch.int64, device=dev)
-    d_priors = [torch.from_numpy(dem_prior(cdem.probs(r))).to(dev) for r in point_rates]
-    for i, r in enumerate(point_rates):
-        for a in range(begin, end, step):
-            t = min(step, end - a)
-            sim.sample_device(r, t, d_det.data_ptr(), d_obs.data_ptr(), seed=seed, shot_begin=a, stream=stream)
-            dec.decode_shots_device(cdem.L, d_det.data_ptr(), d_obs.data_ptr(), t, d_priors[i].data_ptr(), 0, 0,
-                                    d_table[i].data_ptr(), max_iter=max_iter, variant=variant, alpha=alpha,
-                                    damping=damping, clip_llr=clip_llr, flags=flags, stream=stream)
-    if world > 1 and reduce:
-        import torch.distributed as dist
-        dist.all_reduce(d_table)
-    torch.cuda.synchronize(dev)
-    return d_table.cpu().numpy()
+
+    def launch(i, d_prior, a, b, d_out, stream):          # (sample a chunk into the two buffers, then decode it)
+        sim.sample_device(point_rates[i], b - a, d_det.data_ptr(), d_obs.data_ptr(), seed=seed, shot_begin=a,
+                          stream=stream)
+        dec.decode_shots_device(cdem.L, d_det.data_ptr(), d_obs.data_ptr(), b - a, d_prior, 0, 0, d_out,
+                                max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
+                                flags=flags, stream=stream)
+    return _on_device((len(ps), NUM_COUNTERS), [dem_prior(cdem.probs(r)) for r in point_rates], (begin, end), step,
+                      launch, world, device, reduce=reduce)
 
 
-def _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, *, draws, seed, variant, alpha, damping,
-                      clip_llr, osd, flags, world, device):
-    """One rank's slice of a ladder on the device, then the one all-reduce of the [K, 12] table."""
-    def launch(i, d_prior, a, b, d_out, stream):
-        dec.mc_run_budgets_device(L, distance, probs, d_prior, budgets, a, b, d_out, draws=draws, seed=seed,
-                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
-                                  stream=stream)
-    step = dec.mc_budgets_step(len(budgets)) if osd else NO_STEP      # OSD keeps records per trial and budget
-    return _on_device((len(budgets), NUM_COUNTERS), [prior], begin, end, step, launch, world, device)
+def _budgets(model, run, trials, budgets, flags, *, rank, world, device, all_reduce, **decoder):
+    """The body of ``run_budgets`` and ``run_dem_budgets``: this rank's slice of the ladder on the one point of
+    ``model`` -- on the device with the one all-reduce of the [K, 12] table, or through ``run(budgets, begin, end)`` and
+    ``all_reduce``.  ``decoder``: the keywords of ``Decoder.mc_run_budgets_device``."""
+    begin, end = shard_range(int(trials), rank, world)
+    if run is None:
+        from . import bp
+        dec = bp.decoder_for(model.H, device=device)
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_budgets_device(model.L, model.distance, model.probs[0], d_prior, budgets, a, b, d_out, flags=flags,
+                                      stream=stream, **decoder)
+        return _on_device((len(budgets), NUM_COUNTERS), model.priors, (begin, end),
+                          dec.mc_step(flags, end - begin, len(budgets)), launch, world, device)
+    table = np.asarray(run(budgets, begin, end), np.int64).reshape(len(budgets), NUM_COUNTERS)
+    return all_reduce(table) if all_reduce is not None else table
 
 
 def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -575,15 +599,9 @@ def run_budgets(code_name, p, trials, budgets, *, draws=1, seed=0, variant=_lib.
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     budgets = _lib.check_budgets(budgets)
     code = _mc_code(code_name)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(code.Hx, device=device)
-        return _ladder_on_device(dec, code.Lx, code.distance, float(p), prior_of(p, code.n), budgets, begin, end,
-                                 draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping,
-                                 clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
-    table = np.asarray(runner(code, p, budgets, begin, end), np.int64).reshape(len(budgets), NUM_COUNTERS)
-    return all_reduce(table) if all_reduce is not None else table
+    return _budgets(_code_model(code, [p]), _bind(runner, code, p), trials, budgets, flags, rank=rank, world=world,
+                    device=device, all_reduce=all_reduce, draws=draws, seed=seed, variant=variant, alpha=alpha,
+                    damping=damping, clip_llr=clip_llr)
 
 
 def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, draws=1, seed=0,
@@ -594,16 +612,10 @@ def run_dem_budgets(H, L, probs, trials, budgets, *, prior=None, distance=0, dra
     ``runner(H, L, probs, prior, budgets, begin, end) -> int64[K, 12]``."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     budgets = _lib.check_budgets(budgets)
-    L, probs, prior, n = _dem_args(H, L, probs, prior)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        return _ladder_on_device(dec, L, distance, probs, prior, budgets, begin, end, draws=draws, seed=seed,
-                                 variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
-                                 flags=flags, world=world, device=device)
-    table = np.asarray(runner(H, L, probs, prior, budgets, begin, end), np.int64).reshape(len(budgets), NUM_COUNTERS)
-    return all_reduce(table) if all_reduce is not None else table
+    model = _matrix_model(H, L, probs, prior, distance)
+    return _budgets(model, _bind(runner, H, model.L, model.probs[0], model.priors[0]), trials, budgets, flags, rank=rank,
+                    world=world, device=device, all_reduce=all_reduce, draws=draws, seed=seed, variant=variant,
+                    alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
 def _split_llr_hist(flat, K, bins):
@@ -614,19 +626,28 @@ def _split_llr_hist(flat, K, bins):
     return flat[:a].reshape(K, NUM_COUNTERS).copy(), flat[a:].reshape(K, _lib.LLR_HIST_ROWS, bins + 3).copy()
 
 
-def _llr_hist_on_device(dec, L, distance, probs, prior, budgets, bins, llr_range, begin, end, *, draws, seed, variant,
-                        alpha, damping, clip_llr, osd, flags, world, device):
-    """One rank's slice of a ladder with its LLR table on the device -- counters and table side by side in one int64
-    row -- then the one all-reduce of the whole row."""
+def _llr_hist(model, run, trials, budgets, bins, llr_range, flags, *, rank, world, device, all_reduce, **decoder):
+    """The body of ``run_llr_hist`` and ``run_dem_llr_hist``: this rank's slice of the ladder with its LLR table on the
+    one point of ``model`` -- counters and table side by side in one int64 row, reduced in one piece -- on the device,
+    or through ``run(budgets, bins, llr_range, begin, end)`` and ``all_reduce``.  ``decoder``: the keywords of
+    ``Decoder.mc_run_llr_hist_device``."""
     K = len(budgets)
+    begin, end = shard_range(int(trials), rank, world)
+    if run is None:
+        from . import bp
+        dec = bp.decoder_for(model.H, device=device)
 
-    def launch(i, d_prior, a, b, d_out, stream):
-        dec.mc_run_llr_hist_device(L, distance, probs, d_prior, budgets, bins, llr_range, a, b, d_out,
-                                   d_out + 8 * K * NUM_COUNTERS, draws=draws, seed=seed, variant=variant, alpha=alpha,
-                                   damping=damping, clip_llr=clip_llr, flags=flags, stream=stream)
-    step = dec.mc_budgets_step(K) if osd else NO_STEP      # OSD keeps records per trial and budget
-    width = K * NUM_COUNTERS + K * _lib.LLR_HIST_ROWS * (bins + 3)
-    return _on_device((1, width), [prior], begin, end, step, launch, world, device)
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_llr_hist_device(model.L, model.distance, model.probs[0], d_prior, budgets, bins, llr_range, a, b,
+                                       d_out, d_out + 8 * K * NUM_COUNTERS, flags=flags, stream=stream, **decoder)
+        width = K * NUM_COUNTERS + K * _lib.LLR_HIST_ROWS * (bins + 3)
+        flat = _on_device((1, width), model.priors, (begin, end), dec.mc_step(flags, end - begin, K), launch, world,
+                          device)
+    else:
+        flat = np.concatenate([np.asarray(a, np.int64).ravel()
+                               for a in run(budgets, bins, llr_range, begin, end)])[None, :]
+        flat = all_reduce(flat) if all_reduce is not None else flat
+    return (*_split_llr_hist(flat, K, bins), _lib.llr_hist_edges(bins, *llr_range))
 
 
 def run_llr_hist(code_name, p, trials, budgets, bins, llr_range, *, draws=1, seed=0, variant=_lib.SUM_PRODUCT, alpha=1.0,
@@ -647,18 +668,9 @@ def run_llr_hist(code_name, p, trials, budgets, bins, llr_range, *, draws=1, see
     budgets = _lib.check_budgets(budgets)
     bins, lo, hi = _lib.check_llr_hist(bins, *llr_range, len(budgets))
     code = _mc_code(code_name)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(code.Hx, device=device)
-        flat = _llr_hist_on_device(dec, code.Lx, code.distance, float(p), prior_of(p, code.n), budgets, bins, (lo, hi),
-                                   begin, end, draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping,
-                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
-    else:
-        flat = np.concatenate([np.asarray(a, np.int64).ravel()
-                               for a in runner(code, p, budgets, bins, (lo, hi), begin, end)])[None, :]
-        flat = all_reduce(flat) if all_reduce is not None else flat
-    return (*_split_llr_hist(flat, len(budgets), bins), _lib.llr_hist_edges(bins, lo, hi))
+    return _llr_hist(_code_model(code, [p]), _bind(runner, code, p), trials, budgets, bins, (lo, hi), flags, rank=rank,
+                     world=world, device=device, all_reduce=all_reduce, draws=draws, seed=seed, variant=variant,
+                     alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
 def run_dem_llr_hist(H, L, probs, trials, budgets, bins, llr_range, *, prior=None, distance=0, draws=1, seed=0,
@@ -670,19 +682,10 @@ def run_dem_llr_hist(H, L, probs, trials, budgets, bins, llr_range, *, prior=Non
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     budgets = _lib.check_budgets(budgets)
     bins, lo, hi = _lib.check_llr_hist(bins, *llr_range, len(budgets))
-    L, probs, prior, n = _dem_args(H, L, probs, prior)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        flat = _llr_hist_on_device(dec, L, distance, probs, prior, budgets, bins, (lo, hi), begin, end, draws=draws,
-                                   seed=seed, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
-                                   flags=flags, world=world, device=device)
-    else:
-        flat = np.concatenate([np.asarray(a, np.int64).ravel()
-                               for a in runner(H, L, probs, prior, budgets, bins, (lo, hi), begin, end)])[None, :]
-        flat = all_reduce(flat) if all_reduce is not None else flat
-    return (*_split_llr_hist(flat, len(budgets), bins), _lib.llr_hist_edges(bins, lo, hi))
+    model = _matrix_model(H, L, probs, prior, distance)
+    return _llr_hist(model, _bind(runner, H, model.L, model.probs[0], model.priors[0]), trials, budgets, bins, (lo, hi),
+                     flags, rank=rank, world=world, device=device, all_reduce=all_reduce, draws=draws, seed=seed,
+                     variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
 def bp_per_iteration(code_names, p, budgets, trials, osd=True, llr_bins=None, llr_range=None, **kwargs):
@@ -734,20 +737,29 @@ def _split_spectrum(flat, n, max_iter):
             flat[:, b:b + max_iter + 1].copy())
 
 
-def _spectrum_on_device(dec, L, distance, probs_list, priors, begin, end, *, draws, seed, max_iter, variant, alpha,
-                        damping, clip_llr, osd, flags, world, device):
-    """One rank's slice of every point on the device -- counters, weights and iterations of a point side by side in
-    one int64 row -- then the one all-reduce of the whole table."""
-    n = dec.n
-    width = NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1) + max_iter + 1
+def _spectrum(model, run, trials, max_iter, flags, *, rank, world, device, all_reduce, **decoder):
+    """The body of ``run_spectrum`` and ``run_dem_spectrum``: this rank's slice of every point of ``model`` --
+    counters, weights and iterations of a point side by side in one int64 row, the table reduced in one piece -- on
+    the device, or through ``run(i, begin, end)`` per point and ``all_reduce``.  ``decoder``: the keywords of
+    ``Decoder.mc_run_spectrum_device``."""
+    n, points = model.n, len(model.priors)
+    begin, end = shard_range(int(trials), rank, world)
+    if run is None:
+        from . import bp
+        dec = bp.decoder_for(model.H, device=device)
 
-    def launch(i, d_prior, a, b, d_out, stream):
-        dec.mc_run_spectrum_device(L, distance, probs_list[i], d_prior, a, b, d_out, d_out + 8 * NUM_COUNTERS,
-                                   d_out + 8 * (NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)), draws=draws, seed=seed,
-                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
-                                   flags=flags, stream=stream)
-    step = dec.mc_osd_step() if osd else NO_STEP          # OSD keeps per-trial records
-    return _on_device((len(probs_list), width), priors, begin, end, step, launch, world, device)
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_spectrum_device(model.L, model.distance, model.probs[i], d_prior, a, b, d_out,
+                                       d_out + 8 * NUM_COUNTERS, d_out + 8 * (NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1)),
+                                       max_iter=max_iter, flags=flags, stream=stream, **decoder)
+        width = NUM_COUNTERS + _lib.SPECTRUM_ROWS * (n + 1) + max_iter + 1
+        flat = _on_device((points, width), model.priors, (begin, end), dec.mc_step(flags, end - begin), launch, world,
+                          device)
+    else:
+        flat = np.stack([np.concatenate([np.asarray(a, np.int64).ravel() for a in run(i, begin, end)])
+                         for i in range(points)]) if points else np.zeros((0, 0), np.int64)
+        flat = all_reduce(flat) if all_reduce is not None else flat
+    return _split_spectrum(flat, n, max_iter)
 
 
 def _check_spectrum_max_iter(max_iter):
@@ -771,19 +783,10 @@ def run_spectrum(code_name, ps, trials, *, draws=1, seed=0, max_iter=50, variant
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)   # (before any GPU work)
     max_iter = _check_spectrum_max_iter(max_iter)
     code = _mc_code(code_name)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(code.Hx, device=device)
-        flat = _spectrum_on_device(dec, code.Lx, code.distance, [float(p) for p in ps],
-                                   [prior_of(p, code.n) for p in ps], begin, end, draws=draws, seed=seed,
-                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
-        return _split_spectrum(flat, code.n, max_iter)
-    flat = np.stack([np.concatenate([np.asarray(a, np.int64).ravel() for a in runner(code, p, begin, end)])
-                     for p in ps]) if len(ps) else np.zeros((0, 0), np.int64)
-    flat = all_reduce(flat) if all_reduce is not None else flat
-    return _split_spectrum(flat, code.n, max_iter)
+    run = None if runner is None else lambda i, begin, end: runner(code, ps[i], begin, end)
+    return _spectrum(_code_model(code, ps), run, trials, max_iter, flags, rank=rank, world=world, device=device,
+                     all_reduce=all_reduce, draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping,
+                     clip_llr=clip_llr)
 
 
 def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, seed=0, max_iter=50,
@@ -794,18 +797,10 @@ def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, se
     ``run_dem``; ``runner(H, L, probs, prior, begin, end) -> (int64[12], int64[4, n + 1], int64[max_iter + 1])``."""
     flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
     max_iter = _check_spectrum_max_iter(max_iter)
-    L, probs, prior, n = _dem_args(H, L, probs, prior)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        flat = _spectrum_on_device(dec, L, distance, [probs], [prior], begin, end, draws=draws, seed=seed,
-                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                   clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
-        return _split_spectrum(flat, n, max_iter)
-    flat = np.concatenate([np.asarray(a, np.int64).ravel() for a in runner(H, L, probs, prior, begin, end)])[None, :]
-    flat = all_reduce(flat) if all_reduce is not None else flat
-    return _split_spectrum(flat, n, max_iter)
+    model = _matrix_model(H, L, probs, prior, distance)
+    run = None if runner is None else lambda i, begin, end: runner(H, model.L, model.probs[0], model.priors[0], begin, end)
+    return _spectrum(model, run, trials, max_iter, flags, rank=rank, world=world, device=device, all_reduce=all_reduce,
+                     draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
 def check_weights(weights, n):
@@ -819,15 +814,27 @@ def check_weights(weights, n):
     return [int(x) for x in w]
 
 
-def _weights_on_device(dec, L, distance, weights, prior, begin, end, *, seed, max_iter, variant, alpha, damping,
-                       clip_llr, osd, flags, world, device):
-    """One rank's slice of every weight on the device, then the one all-reduce of the [len(weights), 12] table."""
-    def launch(i, d_prior, a, b, d_out, stream):
-        dec.mc_run_weight_device(L, distance, weights[i], d_prior, a, b, d_out, seed=seed, max_iter=max_iter,
-                                 variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags,
-                                 stream=stream)
-    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD | _lib.FLAG_LSD)) else NO_STEP    # (per-trial records)
-    return _on_device((len(weights), NUM_COUNTERS), [prior] * len(weights), begin, end, step, launch, world, device)
+def _weights(model, run, weights, trials, flags, configure, *, rank, world, device, all_reduce, **decoder):
+    """The body of ``run_weights`` and ``run_weights_matrix``: this rank's slice of the trials of every weight, decoded
+    with the one prior of ``model`` -- on the device with the one all-reduce of the [len(weights), 12] table, or through
+    ``run(w, begin, end)`` per weight and ``all_reduce``.  ``decoder``: the keywords of
+    ``Decoder.mc_run_weight_device``."""
+    weights = check_weights(weights, model.n)
+    begin, end = shard_range(int(trials), rank, world)
+    if run is None:
+        from . import bp
+        dec = bp.decoder_for(model.H, device=device)
+        configure(dec)
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_weight_device(model.L, model.distance, weights[i], d_prior, a, b, d_out, flags=flags, stream=stream,
+                                     **decoder)
+        return _on_device((len(weights), NUM_COUNTERS), model.priors * len(weights), (begin, end),
+                          dec.mc_step(flags, end - begin), launch, world, device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, w in enumerate(weights):
+        table[i] = run(w, begin, end)
+    return all_reduce(table) if all_reduce is not None else table
 
 
 def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
@@ -842,27 +849,12 @@ def run_weights(code_name, weights, trials, *, prior_p, seed=0, max_iter=50, var
     ``runner(code, w, begin, end) -> int64[12]`` and ``all_reduce`` are injection points for the CPU tests; by default
     the HIP library and torch.distributed.  ``relay``, ``layered``, ``gd``, ``lsd``, ``lsd_large``, ``quant``: as in
     ``run_sweep``."""
-    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
-    flags = quant_run_flags(flags, quant, layered, variant)
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               relay=relay, layered=layered, gd=gd, lsd=lsd, lsd_large=lsd_large, quant=quant)
     code = _mc_code(code_name)
-    weights = check_weights(weights, code.n)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(code.Hx, device=device)
-        _configure_relay(dec, relay)
-        _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_layered(dec, layered)
-        _configure_quant(dec, quant)
-        return _weights_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), begin, end,
-                                  seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
-                                  clip_llr=clip_llr, osd=osd, flags=flags, world=world, device=device)
-    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
-    for i, w in enumerate(weights):
-        table[i] = runner(code, w, begin, end)
-    return all_reduce(table) if all_reduce is not None else table
+    return _weights(_code_model(code, [prior_p]), _bind(runner, code), weights, trials, flags, configure, rank=rank,
+                    world=world, device=device, all_reduce=all_reduce, seed=seed, max_iter=max_iter, variant=variant,
+                    alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
 def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_iter=50, variant=_lib.SUM_PRODUCT,
@@ -872,48 +864,38 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
     decoder's LLRs ``prior`` [n].  The weight classes are the strata of UNIFORM noise -- every column failing with the
     same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
     does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``.  ``lsd``,
-    ``lsd_large``, ``quant``: as in ``run_sweep``."""
-    flags = lsd_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), lsd, lsd_large)
-    flags = quant_run_flags(flags, quant, False, variant)
-    L, _, prior, n = _dem_args(H, L, None, prior)
-    weights = check_weights(weights, n)
-    begin, end = shard_range(int(trials), rank, world)
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_quant(dec, quant)
-        return _weights_on_device(dec, L, distance, weights, prior, begin, end, seed=seed, max_iter=max_iter,
-                                  variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd,
-                                  flags=flags, world=world, device=device)
-    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
-    for i, w in enumerate(weights):
-        table[i] = runner(H, L, w, prior, begin, end)
-    return all_reduce(table) if all_reduce is not None else table
+    ``lsd_large``, ``quant``: as in ``run_sweep``; of the stages of ``run_weights`` a matrix takes these and OSD."""
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               lsd=lsd, lsd_large=lsd_large, quant=quant)
+    model = _matrix_model(H, L, None, prior, distance)
+    run = None if runner is None else lambda w, begin, end: runner(H, model.L, w, model.priors[0], begin, end)
+    return _weights(model, run, weights, trials, flags, configure, rank=rank, world=world, device=device,
+                    all_reduce=all_reduce, seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                    clip_llr=clip_llr)
 
 
-def _enumerate_on_device(dec, L, distance, weights, prior, rank, world, *, max_iter, variant, alpha, damping, clip_llr,
-                         osd, flags, device):
-    """One rank's share of the ranks of every weight class on the device, then the one all-reduce of the
-    [len(weights), 12] table (``_on_device`` with a range per point: a class has C(n, w) patterns)."""
-    import torch
+def _enumerate(model, run, weights, flags, configure, *, rank, world, device, all_reduce, **decoder):
+    """The body of ``run_enumerate`` and ``run_enumerate_matrix``: ``_weights`` with a range per weight -- this rank's
+    share ``shard_range(C(n, w), rank, world)`` of the ranks of every class.  ``decoder``: the keywords of
+    ``Decoder.mc_run_enum_device``."""
     from . import enumerate as enum_mod
-    dev = torch.device("cuda", device)
-    d_table = torch.zeros((len(weights), NUM_COUNTERS), dtype=torch.int64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    d_prior = torch.from_numpy(np.ascontiguousarray(prior, np.float64)).to(dev)
-    step = dec.mc_osd_step() if osd or (flags & (_lib.FLAG_RELAY | _lib.FLAG_GD | _lib.FLAG_LSD)) else NO_STEP    # (per-trial records)
-    for w, d_out in zip(weights, d_table):
-        begin, end = shard_range(enum_mod.count(dec.n, w), rank, world)
-        for a in range(begin, end, step):
-            dec.mc_run_enum_device(L, distance, w, d_prior.data_ptr(), a, min(a + step, end), d_out.data_ptr(),
-                                   max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
-                                   flags=flags, stream=stream)
-    if world > 1:
-        import torch.distributed as dist
-        dist.all_reduce(d_table)                     # the one RCCL collective of the run
-    torch.cuda.synchronize(dev)
-    return d_table.cpu().numpy()
+    weights = check_weights(weights, model.n)
+    counts = [enum_mod.count(model.n, w) for w in weights]
+    ranges = [shard_range(c, rank, world) for c in counts]
+    if run is None:
+        from . import bp
+        dec = bp.decoder_for(model.H, device=device)
+        configure(dec)
+
+        def launch(i, d_prior, a, b, d_out, stream):
+            dec.mc_run_enum_device(model.L, model.distance, weights[i], d_prior, a, b, d_out, flags=flags, stream=stream,
+                                   **decoder)
+        return _on_device((len(weights), NUM_COUNTERS), model.priors * len(weights), ranges,
+                          dec.mc_step(flags, max(counts, default=1)), launch, world, device)
+    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
+    for i, (w, (begin, end)) in enumerate(zip(weights, ranges)):
+        table[i] = run(w, begin, end)
+    return all_reduce(table) if all_reduce is not None else table
 
 
 def run_enumerate(code_name, weights, *, prior_p, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0,
@@ -925,28 +907,12 @@ def run_enumerate(code_name, weights, *, prior_p, max_iter=50, variant=_lib.SUM_
     and [1] / [0] is the exact f_w (``ler_from_weights(..., exact_weights=weights)``).  A class of more than 2^62
     patterns is a ValueError.  ``runner(code, w, begin, end) -> int64[12]`` gets a rank range; the other keywords are
     ``run_weights``'s."""
-    from . import enumerate as enum_mod
-    flags = relay_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), relay)   # (before any GPU work)
-    flags = layered_run_flags(lsd_run_flags(gd_run_flags(flags, gd), lsd, lsd_large), layered, variant)
-    flags = quant_run_flags(flags, quant, layered, variant)
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               relay=relay, layered=layered, gd=gd, lsd=lsd, lsd_large=lsd_large, quant=quant)
     code = _mc_code(code_name)
-    weights = check_weights(weights, code.n)
-    counts = [enum_mod.count(code.n, w) for w in weights]
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(code.Hx, device=device)
-        _configure_relay(dec, relay)
-        _configure_gd(dec, gd)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_layered(dec, layered)
-        _configure_quant(dec, quant)
-        return _enumerate_on_device(dec, code.Lx, code.distance, weights, prior_of(prior_p, code.n), rank, world,
-                                    max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr,
-                                    osd=osd, flags=flags, device=device)
-    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
-    for i, (w, c) in enumerate(zip(weights, counts)):
-        table[i] = runner(code, w, *shard_range(c, rank, world))
-    return all_reduce(table) if all_reduce is not None else table
+    return _enumerate(_code_model(code, [prior_p]), _bind(runner, code), weights, flags, configure, rank=rank, world=world,
+                      device=device, all_reduce=all_reduce, max_iter=max_iter, variant=variant, alpha=alpha,
+                      damping=damping, clip_llr=clip_llr)
 
 
 def run_enumerate_matrix(H, L, weights, *, prior, distance=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0,
@@ -954,23 +920,13 @@ def run_enumerate_matrix(H, L, weights, *, prior, distance=0, max_iter=50, varia
                          world=1, device=0, runner=None, all_reduce=None, lsd=None, lsd_large=False, quant=None):
     """``run_enumerate`` for any matrix, as ``run_weights_matrix`` is ``run_weights`` for any matrix.
     ``runner(H, L, w, prior, begin, end) -> int64[12]``."""
-    from . import enumerate as enum_mod
-    flags = lsd_run_flags(osd_run_flags(osd, osd_method, osd_order, osd_large), lsd, lsd_large)
-    flags = quant_run_flags(flags, quant, False, variant)
-    L, _, prior, n = _dem_args(H, L, None, prior)
-    weights = check_weights(weights, n)
-    counts = [enum_mod.count(n, w) for w in weights]
-    if runner is None:
-        from . import bp
-        dec = bp.decoder_for(H, device=device)
-        _configure_lsd(dec, lsd, lsd_large)
-        _configure_quant(dec, quant)
-        return _enumerate_on_device(dec, L, distance, weights, prior, rank, world, max_iter=max_iter, variant=variant,
-                                    alpha=alpha, damping=damping, clip_llr=clip_llr, osd=osd, flags=flags, device=device)
-    table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
-    for i, (w, c) in enumerate(zip(weights, counts)):
-        table[i] = runner(H, L, w, prior, *shard_range(c, rank, world))
-    return all_reduce(table) if all_reduce is not None else table
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               lsd=lsd, lsd_large=lsd_large, quant=quant)
+    model = _matrix_model(H, L, None, prior, distance)
+    run = None if runner is None else lambda w, begin, end: runner(H, model.L, w, model.priors[0], begin, end)
+    return _enumerate(model, run, weights, flags, configure, rank=rank, world=world, device=device,
+                      all_reduce=all_reduce, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
+                      clip_llr=clip_llr)
 
 
 def merge_weight_tables(enum_table, enum_weights, sampled_table, sampled_weights):
@@ -1252,10 +1208,9 @@ def main(argv=None):
                                 detectors=args.detectors,
                                 rates=None if args.rates is None else [args.rates],
                                 seed=args.seed, max_iter=args.max_iter, alpha=args.alpha,
-                                variant={"sum-product": _lib.SUM_PRODUCT, "damped": _lib.DAMPED_SP,
-                                         "min-sum": _lib.MIN_SUM}[args.variant],
-                                damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
-                                osd_order=args.osd_order, osd_large=args.osd_large)
+                                variant=_VARIANTS[args.variant], damping=args.damping, clip_llr=args.clip_llr,
+                                osd=args.osd, osd_method=args.osd_method, osd_order=args.osd_order,
+                                osd_large=args.osd_large)
         except (ValueError, KeyError) as e:
             ap.error(f"--circuit: {e}")
         result = {"circuit": args.circuit[0], "rounds": rounds, "basis": args.basis, "detectors": args.detectors,
@@ -1473,11 +1428,10 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             dist.init_process_group(args.backend)
-    variant = {"sum-product": _lib.SUM_PRODUCT, "damped": _lib.DAMPED_SP,
-               "min-sum": _lib.MIN_SUM}[args.variant]
-    common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=variant, alpha=args.alpha,
-                  damping=args.damping, clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
-                  osd_order=args.osd_order, osd_large=args.osd_large, device=local)
+    common = dict(draws=args.draws, seed=args.seed, max_iter=args.max_iter, variant=_VARIANTS[args.variant],
+                  alpha=args.alpha, damping=args.damping, clip_llr=args.clip_llr, osd=args.osd,
+                  osd_method=args.osd_method, osd_order=args.osd_order, osd_large=args.osd_large, device=local)
+    stages = dict(relay=relay, layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, quant=quant)
     if args.depolarizing is not None:
         kw = {k: common[k] for k in ("seed", "max_iter", "variant", "alpha", "damping", "clip_llr", "osd", "osd_method",
                                      "osd_order", "device")}
@@ -1534,7 +1488,6 @@ def main(argv=None):
     if args.enumerate is not None:
         from . import bp, enumerate as enum_mod
         kw = {k: v for k, v in common.items() if k not in ("draws", "seed")}
-        stages = dict(relay=relay, layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, quant=quant)
         code = codes.load_code(args.code)
         t0 = time.perf_counter()
         table = run_enumerate(args.code, args.enumerate, prior_p=args.prior_p, rank=rank, world=world, **stages, **kw)
@@ -1619,21 +1572,18 @@ def main(argv=None):
         del common["draws"]
 
         def sweep(trials, ps, rank, world):
-            return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, relay=relay,
-                               layered=args.layered, gd=gd, lsd=lsd, lsd_large=args.lsd_large, quant=quant, **common)
+            return run_weights(args.code, ps, trials, prior_p=args.prior_p, rank=rank, world=world, **stages, **common)
     elif dem_model is None:
         points = args.p
 
         def sweep(trials, ps, rank, world):
-            return run_sweep(args.code, ps, trials, rank=rank, world=world, relay=relay, layered=args.layered, gd=gd,
-                             lsd=lsd, lsd_large=args.lsd_large, quant=quant, **common)
+            return run_sweep(args.code, ps, trials, rank=rank, world=world, **stages, **common)
     else:
         points = [None]                  # one point: the model's own probabilities
 
         def sweep(trials, ps, rank, world):
-            return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, relay=relay,
-                           layered=args.layered, gd=gd, window=args.window, check_round=check_round, lsd=lsd,
-                           lsd_large=args.lsd_large, quant=quant, **common)[None, :]
+            return run_dem(*dem_model, trials, distance=args.distance, rank=rank, world=world, window=args.window,
+                           check_round=check_round, **stages, **common)[None, :]
     # one-time setup, timed apart from the sweep: HIP context, the decoder of this code (tables, device
     # buffers, kernel images) and a first small launch of the kernels the sweep uses (0.3 - 0.4 s)
     t0 = time.perf_counter()
