@@ -949,6 +949,83 @@ int qbp_enum_failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, i
                              int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream);
 
 /*
+ * Monte-Carlo on circuit faults of a FIXED number: every trial has exactly `weight` firing fault SITES of a circuit,
+ * uniform among the C(N, weight) site sets, each with one of its K codes, uniform -- the circuit-level counterpart of
+ * qbp_mc_run_weight.  When every active site of a circuit fires independently with the same rate p and then takes one
+ * of its K codes uniformly (the frame sampler's own model, qbp_frame_sample, with one rate), the number of firing sites
+ * is Binomial(N, p), and given w of them the site set and the codes are uniform; so
+ * LER(p) = sum_w C(N, w) p^w (1 - p)^(N - w) f_w with N the ACTIVE sites (qldpc_amd/mc.py: run_circuit_weights, and
+ * ler_from_weights with n := N).  The strata are sites, not columns of the detector error model: a merged column's
+ * probability depends on how many faults of which (class, K) went into it, so column patterns of one weight are not
+ * equiprobable.  Propagation is linear: the detectors and observables of a fault set are the XOR of the columns of its
+ * faults, so a trial is an error row over the model's columns and everything behind the sampler is the stored-errors
+ * pipeline of qbp_mc_run_weight.
+ * The fault table (qbp_fault_table_set) names the N active sites -- first_fault [N], the site's first fault in the
+ * circuit's fault numbering (faults are numbered by site, then code), and K [N] in {1, 3, 15} -- and maps every fault
+ * to a column of H: fault_column [n_faults], -1 for a fault that flips nothing.
+ * The sampler (this build's specification; tests/fault_weight_oracle.py restates it in numpy).  For global trial index
+ * t, weight w, seed: Philox4x32-10 with the key (lo32(seed), hi32(seed)); counter word 3 is QBP_FAULT_PHILOX_STREAM
+ * (streams 0 to 5 are taken, see QBP_DISTANCE_PHILOX_STREAM and QBP_FRAME_PHILOX_STREAM).
+ *   Sites, by Floyd's algorithm exactly as qbp_mc_run_weight over N instead of n: for i = 0 .. w - 1
+ *     j = N - w + i
+ *     r = word i % 4 of the block at counter (lo32(t), hi32(t), i / 4, 6)
+ *     u = (uint64(r) * (j + 1)) >> 32
+ *     s_i = j if u is one of s_0 .. s_(i-1), else u.
+ *   Codes: for i = 0 .. w - 1
+ *     r' = word i % 4 of the block at counter (lo32(t), hi32(t), 0x80000000 | i / 4, 6)
+ *     c_i = (uint64(r') * K[s_i]) >> 32,  fault f_i = first_fault[s_i] + c_i.
+ *   Row: errors[t][v] = parity of the number of i with fault_column[f_i] == v.  Faults mapped to -1 contribute nothing;
+ *   two faults in one column cancel, which is the physics.  A row has at most w ones.
+ * Rows depend on (t, w, seed, table) only: not on how [trial_begin, trial_end) is split over calls, chunks, streams or
+ * GPUs.  Limits: 0 <= w <= min(N, QBP_FAULT_WEIGHT_MAX); N <= 2^32 - 4, the frame simulator's own site limit.
+ * Two stages as qbp_mc_run_weight: a chunk of QBP_OPT_MC_WEIGHT_CHUNK trials is sampled into the same handle buffer
+ * (mc_sample_fault_weight_kernel, one lane per trial; the lane's sites go to a workspace the handle owns, which is how a
+ * step sees the earlier ones), then decoded and classified by the pipeline of qbp_mc_run_errors -- no BP or OSD kernel
+ * is built for this.  `ew < distance / 2` is evaluated with the weight of the ROW, which may be below w.
+ */
+#define QBP_FAULT_PHILOX_STREAM 6
+#define QBP_FAULT_WEIGHT_MAX 256
+/* Validates on the host, uploads, and keeps the table on the handle; a second call replaces the first, n_sites = 0
+ * clears it (the arrays may then be null).  QBP_E_INVALID, with the handle's table as it was: a null array, n_sites < 0
+ * or > 2^32 - 4, n_faults < 0, K outside {1, 3, 15}, first_fault[s] < 0 or first_fault[s] + K[s] > n_faults, or a column
+ * outside [-1, n). */
+int qbp_fault_table_set(qbp_handle* h, int64_t n_sites, const int64_t* first_fault, const uint8_t* K, int64_t n_faults,
+                        const int32_t* fault_column);
+/* counters (ADDED to), flags, OSD bits, the QBP_MC_OSD_MAX_TRIALS rule and the QBP_E_UNSUPPORTED cases: those of
+ * qbp_mc_run_weight, as is every QBP_E_INVALID of it; additionally QBP_E_INVALID, before any GPU work and with the
+ * counters untouched, without a table or with weight > min(N, QBP_FAULT_WEIGHT_MAX). */
+int qbp_mc_run_fault_weight(qbp_handle* h, const uint8_t* L, int32_t k, int32_t distance, int32_t weight, uint64_t seed,
+                            int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form (as qbp_mc_run_weight_device). */
+int qbp_mc_run_fault_weight_device(qbp_handle* h, const uint8_t* L_host, int32_t k, int32_t distance, int32_t weight,
+                                   uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* d_prior,
+                                   int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                                   uint32_t flags, int64_t* d_counters, void* stream);
+/* The rows the sampler of qbp_mc_run_fault_weight fills for trials [trial_begin, trial_begin + T): errors [T][n] host
+ * bytes (tests). */
+int qbp_mc_sample_errors_fault_weight(qbp_handle* h, int32_t weight, uint64_t seed, int64_t trial_begin, int64_t T,
+                                      uint8_t* errors);
+/* WHICH trials of a fixed-weight fault run the decoder fails on: qbp_enum_failures with the filler swapped --
+ * mc_sample_fault_weight_kernel fills the chunk, then enum_pack_kernel, the launches of qbp_decode_shots and
+ * enum_capture_kernel run unchanged.  The captured int64 is the TRIAL INDEX; with the statement above it names the fault
+ * set (qldpc_amd/circuit.py: fault_sets).  kinds, what, cap, found, counters, the unwritten entries and the order are as
+ * in qbp_enum_failures.  QBP_E_INVALID, before any GPU work and with every output untouched: what
+ * qbp_mc_run_fault_weight refuses of the table, weight and trials, and what qbp_enum_failures refuses of the rest. */
+int qbp_fault_weight_failures(qbp_handle* h, const uint8_t* L, int32_t k, int32_t weight, uint64_t seed,
+                              int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                              int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                              int32_t what, int64_t cap, int64_t* trials, uint8_t* kinds, int64_t found[1],
+                              int64_t counters[QBP_NUM_COUNTERS]);
+/* Asynchronous form (as qbp_enum_failures_device). */
+int qbp_fault_weight_failures_device(qbp_handle* h, const uint8_t* L_host, int32_t k, int32_t weight, uint64_t seed,
+                                     int64_t trial_begin, int64_t trial_end, const double* d_prior, int32_t max_iter,
+                                     int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                                     int32_t what, int64_t cap, int64_t* d_trials, uint8_t* d_kinds, int64_t* d_found,
+                                     int64_t* d_counters, void* stream);
+
+/*
  * Decode T RECORDED shots of a detector error model to observable predictions: the loop of
  * studies/studyComplete.py:91-109 (sampler.sample(shots, separate_observables=True); BP per shot;
  * L_matrix @ prediction % 2 != actual_observables[i]) for data that comes from stim's circuit sampler or from an

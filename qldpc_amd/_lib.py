@@ -41,6 +41,7 @@ SPECTRUM_ROWS = 4            # QBP_SPECTRUM_ROWS: weights_found_BP, _OSD, _BP_er
 MC_SPECTRUM_MAX_ITER = 1024  # QBP_MC_SPECTRUM_MAX_ITER: iteration limit of qbp_mc_run_spectrum
 LLR_HIST_ROWS = 4            # QBP_LLR_HIST_ROWS: 2 * (BP did not converge) + (the bit's true value)
 LLR_HIST_MAX_WORDS = 8192    # QBP_LLR_HIST_MAX_WORDS: n_budgets * LLR_HIST_ROWS * (bins + 3) of one qbp_mc_run_llr_hist call
+FAULT_WEIGHT_MAX = 256       # QBP_FAULT_WEIGHT_MAX: firing sites of one trial of qbp_mc_run_fault_weight
 NUM_COUNTERS = 12
 COUNTER_NAMES = ("trials", "logical_error", "BPs_fault", "BPs_miscorrected", "incorrectable",
                  "degenerateErrors", "not_converged", "sum_iterations",
@@ -159,6 +160,20 @@ SIGNATURES = {
     "qbp_enum_failures_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _VP, C.c_int32,
                                            C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_int32,
                                            C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "qbp_fault_table_set": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int64, _VP]),
+    "qbp_mc_run_fault_weight": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int64,
+                                          _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                          _VP]),
+    "qbp_mc_run_fault_weight_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int64,
+                                                 C.c_int64, _VP, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                                 C.c_double, C.c_uint32, _VP, _VP]),
+    "qbp_mc_sample_errors_fault_weight": (C.c_int, [_VP, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP]),
+    "qbp_fault_weight_failures": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, _VP,
+                                            C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                            C.c_int32, C.c_int64, _VP, _VP, _VP, _VP]),
+    "qbp_fault_weight_failures_device": (C.c_int, [_VP, _VP, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int64,
+                                                   _VP, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                                   C.c_uint32, C.c_int32, C.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "qbp_check_messages": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
                                      C.c_double, C.c_int32, C.c_uint32, _VP]),
     "qbp_message_histograms": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_int32, C.c_double, C.c_double,
@@ -1220,6 +1235,85 @@ class Decoder:
             int(variant), float(alpha), float(damping), float(clip_llr), int(flags), int(what), int(cap),
             d_ranks or None, d_kinds or None, d_found or None, d_counters, stream or None))
 
+    @_locked
+    def fault_table_set(self, first_fault, K, fault_column):
+        """The fault table of the fixed-weight fault sampler (qbp_fault_table_set): ``first_fault`` int64 [N] and ``K``
+        [N] of the active sites (``circuit.fault_sites``), ``fault_column`` [faults] the column of every fault, -1 for
+        one that flips nothing (``CircuitDem.fault_column``).  Replaces an earlier table; N = 0 clears it."""
+        first = np.ascontiguousarray(first_fault, np.int64)
+        k = np.ascontiguousarray(K, np.uint8)
+        if first.ndim != 1 or k.shape != first.shape or not np.array_equal(k, np.asarray(K).ravel()):
+            raise ValueError("first_fault and K must be one-dimensional, of one length, K within a byte")
+        col = np.asarray(fault_column)
+        if col.ndim != 1 or np.any(col < -1) or np.any(col >= self.n):
+            raise ValueError(f"fault_column must be one-dimensional with entries in [-1, {self.n})")
+        col = np.ascontiguousarray(col, np.int32)
+        _check(load().qbp_fault_table_set(self._h, first.size, first.ctypes.data, k.ctypes.data, col.size,
+                                          col.ctypes.data))
+
+    @_locked
+    def mc_run_fault_weight(self, Lx, distance, weight, prior, trial_begin, trial_end, seed=0, max_iter=50,
+                            variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0):
+        """``mc_run_weight`` on exactly ``weight`` firing fault sites of the table of ``fault_table_set``, uniform among
+        the site sets, each with one of its codes (qbp_mc_run_fault_weight): counters int64[12] of trials
+        [trial_begin, trial_end)."""
+        return self._mc_sampled("qbp_mc_run_fault_weight", Lx, distance, (int(weight), int(seed)), trial_begin,
+                                trial_end, prior, (int(max_iter),), (variant, alpha, damping, clip_llr, flags),
+                                [np.zeros(NUM_COUNTERS, np.int64)])[0]
+
+    def mc_run_fault_weight_device(self, Lx, distance, weight, d_prior, trial_begin, trial_end, d_counters, seed=0,
+                                   max_iter=50, variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0,
+                                   stream=0):
+        """``mc_run_fault_weight`` on device buffers: d_counters int64[12] is added to.  One call: with FLAG_OSD0 the
+        caller splits ranges by ``mc_osd_step()``."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_mc_run_fault_weight_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(distance), int(weight), int(seed), int(trial_begin),
+            int(trial_end), d_prior, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr),
+            int(flags), d_counters, stream or None))
+
+    @_locked
+    def fault_weight_failures(self, Lx, weight, prior, trial_begin, trial_end, seed=0, what=1, cap=1 << 20, max_iter=50,
+                              variant=SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, flags=0, counters=None):
+        """The failing trials of [trial_begin, trial_end) of a fixed-weight fault run (qbp_fault_weight_failures):
+        ``enum_failures`` with the fault sampler as the filler.  Returns ``(trials int64[F], kinds uint8[F], found,
+        counters int64[12])`` with F = min(found, cap), ascending when found <= cap; ``circuit.fault_sets`` names the
+        faults of a trial."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        pr = np.ascontiguousarray(prior, np.float64)
+        if Lx.ndim != 2 or Lx.shape[1] != self.n:
+            raise ValueError(f"Lx must have shape (k, {self.n})")
+        if pr.shape != (self.n,):
+            raise ValueError(f"prior must have shape ({self.n},)")
+        if counters is None:
+            counters = np.zeros(NUM_COUNTERS, np.int64)
+        elif not (isinstance(counters, np.ndarray) and counters.dtype == np.int64 and
+                  counters.shape == (NUM_COUNTERS,) and counters.flags.c_contiguous):
+            raise ValueError(f"counters must be a C-contiguous int64 array of shape ({NUM_COUNTERS},)")
+        cap = int(cap)
+        room = max(0, min(cap, int(trial_end) - int(trial_begin)))       # (no more can be captured)
+        trials = np.zeros(room, np.int64)
+        kinds = np.zeros(room, np.uint8)
+        found = np.zeros(1, np.int64)
+        _check(load().qbp_fault_weight_failures(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(weight), int(seed), int(trial_begin), int(trial_end),
+            pr.ctypes.data, int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags),
+            int(what), cap if cap < 0 else room, trials.ctypes.data if room else None,
+            kinds.ctypes.data if room else None, found.ctypes.data, counters.ctypes.data))
+        kept = min(int(found[0]), room)
+        return trials[:kept], kinds[:kept], int(found[0]), counters
+
+    def fault_weight_failures_device(self, Lx, weight, d_prior, trial_begin, trial_end, what, cap, d_trials, d_kinds,
+                                     d_found, d_counters, seed=0, max_iter=50, variant=SUM_PRODUCT, alpha=1.0,
+                                     damping=1.0, clip_llr=20.0, flags=0, stream=0):
+        """``fault_weight_failures`` on device buffers (pointers as ints): d_trials int64[cap] and d_kinds uint8[cap] in
+        no particular order, d_found int64[1] and d_counters int64[12] added to."""
+        Lx = np.ascontiguousarray(Lx, np.uint8)
+        _check(load().qbp_fault_weight_failures_device(
+            self._h, Lx.ctypes.data, Lx.shape[0], int(weight), int(seed), int(trial_begin), int(trial_end), d_prior,
+            int(max_iter), int(variant), float(alpha), float(damping), float(clip_llr), int(flags), int(what), int(cap),
+            d_trials or None, d_kinds or None, d_found or None, d_counters, stream or None))
+
     def _spectrum_tables(self, max_iter, spectrum, iter_hist):
         """The two tables of the spectrum calls (new zeroed ones, or the caller's, which are added to)."""
         if int(max_iter) < 1:       # (beyond MC_SPECTRUM_MAX_ITER the library answers QBP_E_INVALID)
@@ -1522,6 +1616,14 @@ class Decoder:
         out = np.empty((int(T), self.n), np.uint8)
         _check(load().qbp_mc_sample_errors_weight(self._h, int(weight), int(seed), int(trial_begin), int(T),
                                                   out.ctypes.data))
+        return out
+
+    @_locked
+    def mc_sample_errors_fault_weight(self, weight, trial_begin, T, seed=0):
+        """Rows uint8[T, n] the sampler of ``mc_run_fault_weight`` fills for trials trial_begin .. + T (tests)."""
+        out = np.empty((int(T), self.n), np.uint8)
+        _check(load().qbp_mc_sample_errors_fault_weight(self._h, int(weight), int(seed), int(trial_begin), int(T),
+                                                        out.ctypes.data))
         return out
 
     @_locked

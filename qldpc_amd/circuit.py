@@ -364,6 +364,76 @@ def dem_from_fault_rows(circuit, det_bits, masks):
     return CircuitDem(H, L.reshape(k, n), kinds, counts, fault_column)
 
 
+FAULT_PHILOX_STREAM = 6          # QBP_FAULT_PHILOX_STREAM
+FAULT_WEIGHT_MAX = 256           # QBP_FAULT_WEIGHT_MAX
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox4x32_10(c0, c1, c2, c3, seed):
+    """Philox4x32-10 on uint64 arrays that hold 32-bit words, key (lo32(seed), hi32(seed)) -> the four output words."""
+    k0, k1 = np.uint64(int(seed) & 0xFFFFFFFF), np.uint64((int(seed) >> 32) & 0xFFFFFFFF)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0, p1 = c0 * np.uint64(0xD2511F53), c2 * np.uint64(0xCD9E8D57)
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & _M32, (p0 >> s32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & _M32, (k1 + np.uint64(0xBB67AE85)) & _M32
+    return c0, c1, c2, c3
+
+
+def _class_set(classes):
+    """Rate classes given as numbers or names of ``CLASSES`` -> a set of numbers; None stays None (every class)."""
+    if classes is None:
+        return None
+    out = {CLASSES[c] if isinstance(c, str) else int(c) for c in classes}
+    if any(c < 0 or c >= MAX_CLASSES for c in out):
+        raise ValueError(f"rate classes are 0 .. {MAX_CLASSES - 1}")
+    return out
+
+
+def fault_sites(circuit, classes=None):
+    """The ACTIVE sites of a fixed-weight fault run: ``(first_fault int64 [N], K int64 [N], N)`` of the sites whose rate
+    class is in ``classes`` (numbers or names of ``CLASSES``; None: every class), in site order; ``first_fault`` is
+    the site's first fault in the circuit's fault numbering.  A class left out means rate 0: its sites never fire and
+    do not count towards N."""
+    _, _, _, cls, K, base = circuit.sites()
+    keep = _class_set(classes)
+    on = np.ones(len(K), bool) if keep is None else np.isin(cls, sorted(keep))
+    return np.ascontiguousarray(base[:-1][on]), np.ascontiguousarray(K[on]), int(on.sum())
+
+
+def fault_sets(circuit, weight, seed, trials, classes=None):
+    """The faults of the trials of a fixed-weight fault run (include/qbp.h, qbp_mc_run_fault_weight, which states the
+    sampler): int64 [len(trials), weight] fault numbers, column i the fault of step i.  ``trials``: global trial
+    indices.  Fault f belongs to the site j with ``site_base[j] <= f < site_base[j + 1]`` of ``circuit.sites()`` and
+    has code ``f - site_base[j] + 1``.
+    ValueError: a weight outside [0, min(N, FAULT_WEIGHT_MAX)]."""
+    first, K, N = fault_sites(circuit, classes)
+    w, seed = int(weight), int(seed)
+    if not 0 <= w <= min(N, FAULT_WEIGHT_MAX):
+        raise ValueError(f"weight {w} out of [0, {min(N, FAULT_WEIGHT_MAX)}] (min of {N} active sites and "
+                         f"FAULT_WEIGHT_MAX)")
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed must fit 64 bits")
+    t = np.asarray(trials, np.int64).ravel().astype(np.uint64)
+    T = t.size
+    lo, hi = t & _M32, t >> np.uint64(32)
+    stream = np.full(T, FAULT_PHILOX_STREAM, np.uint64)
+    sites = np.zeros((T, w), np.int64)
+    out = np.zeros((T, w), np.int64)
+    Ku = K.astype(np.uint64)
+    for i in range(w):
+        if i % 4 == 0:
+            block = np.full(T, i // 4, np.uint64)
+            pick = _philox4x32_10(lo, hi, block, stream, seed)
+            code = _philox4x32_10(lo, hi, block | np.uint64(0x80000000), stream, seed)
+        j = N - w + i
+        u = ((pick[i % 4] * np.uint64(j + 1)) >> np.uint64(32)).astype(np.int64)
+        s = np.where((sites[:, :i] == u[:, None]).any(axis=1), j, u)
+        sites[:, i] = s
+        out[:, i] = first[s] + ((code[i % 4] * Ku[s]) >> np.uint64(32)).astype(np.int64)
+    return out
+
+
 def circuit_dem(circuit, device=0):
     """The detector error model of ``circuit``: every single fault is propagated on the GPU (qbp_frame_faults), then
     ``dem_from_fault_rows`` drops, merges and counts on the host."""

@@ -334,6 +334,13 @@ struct qbp_handle {
     DevBuf<uint8_t> d_enum_det, d_enum_conv, d_enum_kinds;
     DevBuf<unsigned long long> d_enum_actual, d_enum_pred, d_enum_found;
     DevBuf<long long> d_enum_ranks;
+    // fixed-weight fault sampling (qbp_fault_table_set): the active sites' first faults and K, the column of every
+    // fault; the sites one launch of the sampler picks, [weight][trials of a launch]
+    DevBuf<long long> d_fault_first;
+    DevBuf<uint8_t> d_fault_k;
+    DevBuf<int32_t> d_fault_col;
+    DevBuf<uint32_t> d_fault_picks;
+    long long fault_sites = 0;       // N; 0: no table
     long long opt_weight_chunk = 0;  // QBP_OPT_MC_WEIGHT_CHUNK (0 = default)
     long long opt_llr_hist_chunk = 0;   // QBP_OPT_LLR_HIST_CHUNK (0 = default)
     DevBuf<int32_t> d_srow, d_srow_e0, d_srow_deg, d_svar, d_sedge;   // weight-class tables
@@ -3278,13 +3285,14 @@ catch (...) { return -1; }
 
 // Where the errors of a Monte-Carlo call come from; only the fields of `kind` are read.
 struct McErrors {
-    enum Kind { P, PROBS, WEIGHT, STORED, ENUM } kind = P;
+    enum Kind { P, PROBS, WEIGHT, STORED, ENUM, FAULT } kind = P;
     int32_t draws = 1;                       // P, PROBS
     uint64_t seed = 0;                       // all but STORED and ENUM
     double p = 0.0;                          // P: every column fails with p
     const double* probs = nullptr;           // PROBS: a probability per column, host [n]
     int32_t weight = 0;                      // WEIGHT: exactly this many ones, uniform among the patterns
                                              // ENUM: the patterns of this weight by rank (the trial index is the rank)
+                                             // FAULT: exactly this many firing sites of the handle's fault table
     const uint8_t* d_errors = nullptr;       // STORED: device [trials, n]; the trial range starts at 0
 };
 
@@ -3320,11 +3328,16 @@ struct McCall {
     size_t rows() const { return ladder() ? (size_t)n_budgets : 1; }          // counter rows = failure-record planes
     int32_t last_iter() const { return ladder() ? budgets[n_budgets - 1] : dec.max_iter; }
     size_t llr_cells() const { return out == LLRHIST ? (size_t)QBP_LLR_HIST_WORDS(n_budgets, llr_bins) : 0; }
-    // trials that no BP kernel draws itself: fixed weight, sampled or enumerated, and the layered and fixed-point
-    // kernels, which decode stored errors only
+    // fixed weight, of columns (sampled or enumerated) or of fault sites: filled chunk by chunk
+    bool fixed_weight() const
+    {
+        return errors.kind == McErrors::WEIGHT || errors.kind == McErrors::ENUM || errors.kind == McErrors::FAULT;
+    }
+    // trials that no BP kernel draws itself: fixed weight, and the layered and fixed-point kernels, which decode stored
+    // errors only
     bool chunked() const
     {
-        return errors.kind == McErrors::WEIGHT || errors.kind == McErrors::ENUM ||
+        return fixed_weight() ||
                (errors.kind != McErrors::STORED && (dec.flags & (QBP_FLAG_LAYERED | QBP_FLAG_QUANT)));
     }
 };
@@ -3393,6 +3406,12 @@ static int check_mc_errors(const qbp_handle* h, const McErrors& e, int64_t trial
     if (e.kind == McErrors::WEIGHT) {
         if (e.weight < 0 || e.weight > h->n)
             return fail(QBP_E_INVALID, "weight = %d out of [0, %d] (n columns)", e.weight, h->n);
+    } else if (e.kind == McErrors::FAULT) {
+        if (h->fault_sites == 0) return fail(QBP_E_INVALID, "no fault table: call qbp_fault_table_set first");
+        const long long top = std::min<long long>(h->fault_sites, QBP_FAULT_WEIGHT_MAX);
+        if (e.weight < 0 || e.weight > top)
+            return fail(QBP_E_INVALID, "weight = %d out of [0, %lld] (min of %lld fault sites and QBP_FAULT_WEIGHT_MAX)",
+                        e.weight, top, h->fault_sites);
     } else {
         if (e.draws != 1 && e.draws != 2) return fail(QBP_E_INVALID, "draws must be 1 or 2 (got %d)", e.draws);
         if (e.kind == McErrors::P && !(e.p >= 0.0 && e.p <= 1.0)) return fail(QBP_E_INVALID, "p = %g out of [0, 1]", e.p);
@@ -3447,7 +3466,7 @@ static int check_mc_call(qbp_handle* h, const McCall& c, const double* host_prio
         // QBP_MC_OSD_MAX_TRIALS bounds the records of one launch.  That is the whole call -- a fixed-weight call too,
         // sampled or enumerated, although it launches chunk by chunk -- except for layered sampled calls, which have always been held to it
         // per chunk only: a longer range of those goes through.
-        const bool per_chunk = c.chunked() && c.errors.kind != McErrors::WEIGHT && c.errors.kind != McErrors::ENUM;
+        const bool per_chunk = c.chunked() && !c.fixed_weight();
         rc = check_mc_osd_trials(h, per_chunk ? mc_chunk_trials(h, c.trials()) : c.trials(), c.rows());
     }
     return rc;
@@ -3577,6 +3596,15 @@ static hipError_t mc_sample(qbp_handle* h, const McErrors& e, uint8_t* errors, l
     // (the samplers do not depend on H: any matrix, whichever kernel decodes it)
     if (e.kind == McErrors::WEIGHT) return qbp::launch_mc_sample_weight(errors, h->n, e.weight, t, trial_begin, e.seed, s);
     if (e.kind == McErrors::ENUM) return qbp::launch_mc_enum_weight(errors, h->n, e.weight, t, trial_begin, h->d_binom.p, s);
+    if (e.kind == McErrors::FAULT) {
+        // the picks of one launch: at most 2^26 words, and never fewer than a workgroup's trials
+        const long long stride = std::min<long long>(t, std::max<long long>(256, ((long long)1 << 26) / std::max(e.weight, 1)));
+        const hipError_t err = h->d_fault_picks.reserve((size_t)e.weight * (size_t)stride);
+        if (err != hipSuccess) return err;
+        return qbp::launch_mc_sample_fault_weight(errors, h->n, e.weight, t, trial_begin, e.seed, h->d_fault_first.p,
+                                                  h->d_fault_k.p, h->d_fault_col.p, (unsigned)h->fault_sites,
+                                                  h->d_fault_picks.p, stride, s);
+    }
     if (e.kind == McErrors::PROBS)
         return qbp::launch_mc_sample_cols(errors, h->n, t, trial_begin, e.draws, e.seed, h->mc_in.d_thr.p, s);
     return qbp::launch_mc_sample(errors, h->n, t, trial_begin, e.draws, e.seed, mc_threshold(e.p), s);
@@ -3814,6 +3842,71 @@ QBP_ABI_CATCH
 int qbp_mc_sample_errors_enum(qbp_handle* h, int32_t weight, int64_t rank_begin, int64_t T, uint8_t* errors)
 try {
     return mc_sample_host(h, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin, T, errors);
+}
+QBP_ABI_CATCH
+
+int qbp_fault_table_set(qbp_handle* h, int64_t n_sites, const int64_t* first_fault, const uint8_t* K, int64_t n_faults,
+                        const int32_t* fault_column)
+try {
+    if (!h) return fail(QBP_E_INVALID, "null handle");
+    if (n_sites < 0 || n_sites > (int64_t)0xfffffffcll)
+        return fail(QBP_E_INVALID, "n_sites = %lld out of [0, 2^32 - 4]", (long long)n_sites);
+    if (n_sites > 0) {
+        if (!first_fault || !K || !fault_column) return fail(QBP_E_INVALID, "null pointer");
+        if (n_faults < 0) return fail(QBP_E_INVALID, "n_faults must be >= 0");
+        for (int64_t s = 0; s < n_sites; ++s) {
+            if (K[s] != 1 && K[s] != 3 && K[s] != 15)
+                return fail(QBP_E_INVALID, "K[%lld] = %d (a site has 1, 3 or 15 faults)", (long long)s, (int)K[s]);
+            if (first_fault[s] < 0 || first_fault[s] > n_faults - (int64_t)K[s])
+                return fail(QBP_E_INVALID, "site %lld: faults [%lld, %lld + %d) out of [0, %lld)", (long long)s,
+                            (long long)first_fault[s], (long long)first_fault[s], (int)K[s], (long long)n_faults);
+        }
+        for (int64_t f = 0; f < n_faults; ++f)
+            if (fault_column[f] < -1 || fault_column[f] >= h->n)
+                return fail(QBP_E_INVALID, "fault_column[%lld] = %d out of [-1, %d)", (long long)f, fault_column[f], h->n);
+    }
+    DeviceScope on_device(h->device);
+    HIP_TRY(on_device.err);
+    HIP_TRY(hipDeviceSynchronize());          // (a sampler that still reads the table it replaces)
+    h->fault_sites = 0;
+    if (n_sites == 0) return QBP_OK;
+    HIP_TRY(h->d_fault_first.reserve((size_t)n_sites));
+    HIP_TRY(h->d_fault_k.reserve((size_t)n_sites));
+    HIP_TRY(h->d_fault_col.reserve((size_t)n_faults));
+    HIP_TRY(hipMemcpy(h->d_fault_first.p, first_fault, (size_t)n_sites * sizeof(long long), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_fault_k.p, K, (size_t)n_sites, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->d_fault_col.p, fault_column, (size_t)n_faults * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->fault_sites = n_sites;
+    return QBP_OK;
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_fault_weight_device(qbp_handle* h, const uint8_t* L_host, int32_t k, int32_t distance, int32_t weight,
+                                   uint64_t seed, int64_t trial_begin, int64_t trial_end, const double* d_prior,
+                                   int32_t max_iter, int32_t variant, double alpha, double damping, double clip_llr,
+                                   uint32_t flags, int64_t* d_counters, void* stream)
+try {
+    return mc_run_device(h, mc_call(L_host, k, distance, {McErrors::FAULT, 1, seed, 0.0, nullptr, weight}, trial_begin,
+                                    trial_end, {max_iter, variant, alpha, damping, clip_llr, flags}, d_prior, d_counters),
+                         stream);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_run_fault_weight(qbp_handle* h, const uint8_t* L, int32_t k, int32_t distance, int32_t weight, uint64_t seed,
+                            int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                            int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                            int64_t counters[QBP_NUM_COUNTERS])
+try {
+    return mc_run_host(h, mc_call(L, k, distance, {McErrors::FAULT, 1, seed, 0.0, nullptr, weight}, trial_begin,
+                                  trial_end, {max_iter, variant, alpha, damping, clip_llr, flags}), prior, nullptr,
+                       counters, nullptr, nullptr);
+}
+QBP_ABI_CATCH
+
+int qbp_mc_sample_errors_fault_weight(qbp_handle* h, int32_t weight, uint64_t seed, int64_t trial_begin, int64_t T,
+                                      uint8_t* errors)
+try {
+    return mc_sample_host(h, {McErrors::FAULT, 1, seed, 0.0, nullptr, weight}, trial_begin, T, errors);
 }
 QBP_ABI_CATCH
 
@@ -4100,16 +4193,18 @@ static long long enum_failures_chunk(const qbp_handle* h, int64_t T, uint32_t fl
     return std::max<long long>(chunk, 1);
 }
 
-// Everything qbp_enum_failures refuses, host only and before any GPU work
-static int check_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin,
+// Everything qbp_enum_failures and qbp_fault_weight_failures refuse, host only and before any GPU work; `e`: the filler,
+// ENUM or FAULT
+static int check_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, const McErrors& e, int64_t rank_begin,
                                int64_t rank_end, const double* prior, const double* host_prior, int32_t max_iter,
                                int32_t variant, uint32_t flags, int32_t what, int64_t cap, const int64_t* ranks,
                                const uint8_t* kinds, const int64_t* found, const int64_t* counters, int* osd_method,
                                int* osd_order)
 {
     if (!h) return fail(QBP_E_INVALID, "null handle");
-    int rc = check_enum_range(h, weight, rank_begin, rank_end);
+    int rc = check_mc_errors(h, e, rank_begin, rank_end);
     if (rc) return rc;
+    if (rank_end < rank_begin) return fail(QBP_E_INVALID, "trial_end must be >= trial_begin");
     if (what < 1 || what > 3) return fail(QBP_E_INVALID, "what = %d (need 1 logical, 2 unconverged, or 3 either)", what);
     if (cap < 0) return fail(QBP_E_INVALID, "cap must be >= 0 (got %lld)", (long long)cap);
     if (!found) return fail(QBP_E_INVALID, "found is null");
@@ -4120,8 +4215,9 @@ static int check_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int3
 }
 
 // A checked call on the stream, every pointer but Lx_host a device pointer: chunk by chunk the enumeration, the shot
-// of every row, the launches of qbp_decode_shots, the capture.  Nothing returns to the host in between.
-static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
+// of every row, the launches of qbp_decode_shots, the capture.  Nothing returns to the host in between.  `e`: the filler
+// of the rows (mc_sample), the enumeration or the fixed-weight fault sampler, whose trial index is captured instead.
+static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, const McErrors& e, int64_t rank_begin,
                              int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
                              double damping, double clip_llr, uint32_t flags, int osd_method, int osd_order, int32_t what,
                              int64_t cap, int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters,
@@ -4130,7 +4226,7 @@ static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, i
     if (rank_end == rank_begin) return QBP_OK;
     int rc = mc_prepare(h, Lx_host, k, s);
     if (rc) return rc;
-    if ((rc = enum_prepare(h, weight, s)) != QBP_OK) return rc;
+    if (e.kind == McErrors::ENUM && (rc = enum_prepare(h, e.weight, s)) != QBP_OK) return rc;
     const long long chunk = enum_failures_chunk(h, rank_end - rank_begin, flags);
     const size_t c = (size_t)chunk, n = (size_t)h->n, rb = ((size_t)h->m + 7) / 8;
     HIP_TRY(h->d_weight_err.reserve(c * n));
@@ -4140,7 +4236,7 @@ static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, i
     HIP_TRY(h->d_enum_conv.reserve(c));
     for (int64_t a = rank_begin; a < rank_end; a += chunk) {
         const long long t = std::min<long long>(chunk, rank_end - a);
-        HIP_TRY(qbp::launch_mc_enum_weight(h->d_weight_err.p, h->n, weight, t, a, h->d_binom.p, s));
+        HIP_TRY(mc_sample(h, e, h->d_weight_err.p, t, a, s));
         HIP_TRY(qbp::launch_enum_pack(h->d_weight_err.p, t, h->m, h->n, h->d_row_ptr.p, h->d_col_idx.p,
                                       h->mc_in.d_lx_cols.p, h->d_enum_det.p, h->d_enum_actual.p, s));
         rc = decode_shots_impl(h, Lx_host, k, h->d_enum_det.p, reinterpret_cast<const uint64_t*>(h->d_enum_actual.p), t,
@@ -4154,30 +4250,32 @@ static int enum_failures_run(qbp_handle* h, const uint8_t* Lx_host, int32_t k, i
     return QBP_OK;
 }
 
-int qbp_enum_failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
-                             int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
-                             double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap,
-                             int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream)
-try {
+// The _device entries of the two fillers: the check, then the launches.
+static int failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, const McErrors& e, int64_t rank_begin,
+                           int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
+                           double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap,
+                           int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream)
+{
     int osd_method = 0, osd_order = 0;
-    const int rc = check_enum_failures(h, Lx_host, k, weight, rank_begin, rank_end, d_prior, nullptr, max_iter, variant,
+    const int rc = check_enum_failures(h, Lx_host, k, e, rank_begin, rank_end, d_prior, nullptr, max_iter, variant,
                                        flags, what, cap, d_ranks, d_kinds, d_found, d_counters, &osd_method, &osd_order);
     if (rc) return rc;
     DeviceScope on_device(h->device);
     HIP_TRY(on_device.err);
-    return enum_failures_run(h, Lx_host, k, weight, rank_begin, rank_end, d_prior, max_iter, variant, alpha, damping,
+    return enum_failures_run(h, Lx_host, k, e, rank_begin, rank_end, d_prior, max_iter, variant, alpha, damping,
                              clip_llr, flags, osd_method, osd_order, what, cap, d_ranks, d_kinds, d_found, d_counters,
                              static_cast<hipStream_t>(stream));
 }
-QBP_ABI_CATCH
 
-int qbp_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin, int64_t rank_end,
-                      const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
-                      double clip_llr, uint32_t flags, int32_t what, int64_t cap, int64_t* ranks, uint8_t* kinds,
-                      int64_t found[1], int64_t counters[QBP_NUM_COUNTERS])
-try {
+// The host-array entries of the two fillers: the check, the prior uploaded, the run on the handle's stream and buffers,
+// the captured entries sorted and copied back.
+static int failures_host(qbp_handle* h, const uint8_t* Lx, int32_t k, const McErrors& e, int64_t rank_begin,
+                         int64_t rank_end, const double* prior, int32_t max_iter, int32_t variant, double alpha,
+                         double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap, int64_t* ranks,
+                         uint8_t* kinds, int64_t* found, int64_t* counters)
+{
     int osd_method = 0, osd_order = 0;
-    int rc = check_enum_failures(h, Lx, k, weight, rank_begin, rank_end, prior, prior, max_iter, variant, flags, what,
+    int rc = check_enum_failures(h, Lx, k, e, rank_begin, rank_end, prior, prior, max_iter, variant, flags, what,
                                  cap, ranks, kinds, found, counters, &osd_method, &osd_order);
     if (rc) return rc;
     if (rank_end == rank_begin) { found[0] = 0; return QBP_OK; }
@@ -4204,7 +4302,7 @@ try {
         HIP_TRY(h->d_enum_kinds.reserve(room));
         HIP_TRY(h->d_enum_found.reserve(1));
         HIP_TRY(hipMemsetAsync(h->d_enum_found.p, 0, sizeof(unsigned long long), h->stream));
-        rc = st.finish(enum_failures_run(h, Lx, k, weight, rank_begin, rank_end, d_prior, max_iter, variant, alpha,
+        rc = st.finish(enum_failures_run(h, Lx, k, e, rank_begin, rank_end, d_prior, max_iter, variant, alpha,
                                          damping, clip_llr, flags, osd_method, osd_order, what, (int64_t)room,
                                          reinterpret_cast<int64_t*>(h->d_enum_ranks.p), h->d_enum_kinds.p,
                                          reinterpret_cast<int64_t*>(h->d_enum_found.p),
@@ -4226,6 +4324,49 @@ try {
     for (size_t i = 0; i < kept; ++i) { ranks[i] = hits[i].first; kinds[i] = hits[i].second; }
     found[0] = (int64_t)n_found;
     return QBP_OK;
+}
+
+int qbp_enum_failures_device(qbp_handle* h, const uint8_t* Lx_host, int32_t k, int32_t weight, int64_t rank_begin,
+                             int64_t rank_end, const double* d_prior, int32_t max_iter, int32_t variant, double alpha,
+                             double damping, double clip_llr, uint32_t flags, int32_t what, int64_t cap,
+                             int64_t* d_ranks, uint8_t* d_kinds, int64_t* d_found, int64_t* d_counters, void* stream)
+try {
+    return failures_device(h, Lx_host, k, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin, rank_end, d_prior,
+                           max_iter, variant, alpha, damping, clip_llr, flags, what, cap, d_ranks, d_kinds, d_found,
+                           d_counters, stream);
+}
+QBP_ABI_CATCH
+
+int qbp_enum_failures(qbp_handle* h, const uint8_t* Lx, int32_t k, int32_t weight, int64_t rank_begin, int64_t rank_end,
+                      const double* prior, int32_t max_iter, int32_t variant, double alpha, double damping,
+                      double clip_llr, uint32_t flags, int32_t what, int64_t cap, int64_t* ranks, uint8_t* kinds,
+                      int64_t found[1], int64_t counters[QBP_NUM_COUNTERS])
+try {
+    return failures_host(h, Lx, k, {McErrors::ENUM, 1, 0, 0.0, nullptr, weight}, rank_begin, rank_end, prior, max_iter,
+                         variant, alpha, damping, clip_llr, flags, what, cap, ranks, kinds, found, counters);
+}
+QBP_ABI_CATCH
+
+int qbp_fault_weight_failures_device(qbp_handle* h, const uint8_t* L_host, int32_t k, int32_t weight, uint64_t seed,
+                                     int64_t trial_begin, int64_t trial_end, const double* d_prior, int32_t max_iter,
+                                     int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                                     int32_t what, int64_t cap, int64_t* d_trials, uint8_t* d_kinds, int64_t* d_found,
+                                     int64_t* d_counters, void* stream)
+try {
+    return failures_device(h, L_host, k, {McErrors::FAULT, 1, seed, 0.0, nullptr, weight}, trial_begin, trial_end,
+                           d_prior, max_iter, variant, alpha, damping, clip_llr, flags, what, cap, d_trials, d_kinds,
+                           d_found, d_counters, stream);
+}
+QBP_ABI_CATCH
+
+int qbp_fault_weight_failures(qbp_handle* h, const uint8_t* L, int32_t k, int32_t weight, uint64_t seed,
+                              int64_t trial_begin, int64_t trial_end, const double* prior, int32_t max_iter,
+                              int32_t variant, double alpha, double damping, double clip_llr, uint32_t flags,
+                              int32_t what, int64_t cap, int64_t* trials, uint8_t* kinds, int64_t found[1],
+                              int64_t counters[QBP_NUM_COUNTERS])
+try {
+    return failures_host(h, L, k, {McErrors::FAULT, 1, seed, 0.0, nullptr, weight}, trial_begin, trial_end, prior,
+                         max_iter, variant, alpha, damping, clip_llr, flags, what, cap, trials, kinds, found, counters);
 }
 QBP_ABI_CATCH
 

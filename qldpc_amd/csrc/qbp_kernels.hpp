@@ -1067,6 +1067,50 @@ __global__ void mc_sample_weight_kernel(uint8_t* errors, int n, int w, long long
     }
 }
 
+// The fixed-weight FAULT sampler (qbp_mc_run_fault_weight, qbp_mc_sample_errors_fault_weight; specification:
+// include/qbp.h): trial trial_begin + b picks w of the N fault sites by Floyd's algorithm, as the sampler above picks
+// columns, draws one of the K[s] codes of every picked site from a second Philox block (counter word 2 with its top bit
+// set), and toggles column fault_column[first_fault[s] + code] of row b of errors [T][n]; a fault mapped to -1 toggles
+// nothing, two faults of one column cancel.  One lane per trial.  Sites are not columns, so the row cannot be the
+// membership map: the lane's picks go to picks [w][stride] (trial-minor: lane b owns column b, a wavefront's accesses
+// coalesce), and step i tests u against rows 0 .. i - 1 of its own column -- a lane reads back its own stores only.  No
+// LDS and no indexed register array; unrolled by four so that the Philox words are indexed statically.  The rows have
+// to be ZERO on entry (launch_mc_sample_fault_weight clears them).  N <= 2^32 - 4, so j + 1 does not wrap; every picked
+// s is in [0, N), first_fault[s] + code < n_faults and every column is in [-1, n) by the checks of qbp_fault_table_set.
+constexpr unsigned FAULT_PHILOX_WORD3 = 6u;   // QBP_FAULT_PHILOX_STREAM of include/qbp.h
+__global__ void mc_sample_fault_weight_kernel(uint8_t* errors, int n, int w, long long T, long long trial_begin,
+                                              unsigned long long seed, const long long* first_fault,
+                                              const uint8_t* site_k, const int32_t* fault_column, unsigned n_sites,
+                                              uint32_t* picks, long long stride)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= T) return;
+    const unsigned long long trial = (unsigned long long)(trial_begin + b);
+    uint8_t* const row = errors + b * n;
+    uint32_t* const mine = picks + b;
+    for (int i0 = 0; i0 < w; i0 += 4) {
+        unsigned c[4] = {(unsigned)trial, (unsigned)(trial >> 32), (unsigned)(i0 >> 2), FAULT_PHILOX_WORD3};
+        unsigned d[4] = {(unsigned)trial, (unsigned)(trial >> 32), 0x80000000u | (unsigned)(i0 >> 2), FAULT_PHILOX_WORD3};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        philox4x32_10(d, (unsigned)seed, (unsigned)(seed >> 32));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (i0 + k < w) {
+                const int i = i0 + k;
+                const unsigned j = n_sites - (unsigned)w + (unsigned)i;
+                const unsigned u = __umulhi(c[k], j + 1u);       // (r (j + 1)) >> 32, in [0, j]
+                bool taken = false;
+                for (int q = 0; q < i; ++q) taken |= mine[(long long)q * stride] == u;
+                const unsigned s = taken ? j : u;
+                mine[(long long)i * stride] = s;
+                const long long f = first_fault[s] + (long long)__umulhi(d[k], (unsigned)site_k[s]);
+                const int v = fault_column[f];
+                if (v >= 0) row[v] ^= 1;
+            }
+        }
+    }
+}
+
 // The weight-w enumeration (qbp_mc_run_enum, qbp_mc_sample_errors_enum; specification: include/qbp.h): row b of
 // errors [T][n] becomes the pattern of rank rank_begin + b in the lexicographic order of the ascending column tuples.
 // With D = C(n, w) - 1 - rank the rule of the header is the combinadic of D: for t = w .. 1 take the largest j below

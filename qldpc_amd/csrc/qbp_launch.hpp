@@ -107,6 +107,13 @@ hipError_t launch_mc_sample_cols(uint8_t* errors, int n, long long T, long long 
 // rows of exactly `weight` ones (mc_sample_weight_kernel; 0 <= weight <= n); clears errors [T][n] first, on s
 hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
                                    unsigned long long seed, hipStream_t s);
+// row b = the columns of `weight` faults at distinct sites (mc_sample_fault_weight_kernel; 0 <= weight <= n_sites); the
+// three tables are those of qbp_fault_table_set; picks [weight][stride] is workspace, stride >= 1 trials per launch;
+// clears errors [T][n] first, on s
+hipError_t launch_mc_sample_fault_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
+                                         unsigned long long seed, const long long* first_fault, const uint8_t* site_k,
+                                         const int32_t* fault_column, unsigned n_sites, uint32_t* picks,
+                                         long long stride, hipStream_t s);
 // row b = the weight-`weight` pattern of rank rank_begin + b (mc_enum_weight_kernel; 0 <= weight <= n); binom
 // [weight + 1][n + 1]: C(j, t) at t * (n + 1) + j, saturated; clears errors [T][n] first, on s
 hipError_t launch_mc_enum_weight(uint8_t* errors, int n, int weight, long long T, long long rank_begin,

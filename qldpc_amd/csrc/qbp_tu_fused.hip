@@ -164,6 +164,28 @@ hipError_t launch_mc_sample_weight(uint8_t* errors, int n, int weight, long long
     return hipGetLastError();
 }
 
+static_assert(QBP_FAULT_PHILOX_STREAM == FAULT_PHILOX_WORD3, "Philox counter word 3 of the fixed-weight fault sampler");
+
+hipError_t launch_mc_sample_fault_weight(uint8_t* errors, int n, int weight, long long T, long long trial_begin,
+                                         unsigned long long seed, const long long* first_fault, const uint8_t* site_k,
+                                         const int32_t* fault_column, unsigned n_sites, uint32_t* picks,
+                                         long long stride, hipStream_t s)
+{
+    // (the buffer is the weight sampler's, and a row is toggled, not set: cleared for the same reason)
+    hipError_t e = hipMemsetAsync(errors, 0, (size_t)T * (size_t)n, s);
+    if (e != hipSuccess || weight == 0) return e;
+    const int threads = 256;
+    // picks holds the sites of `stride` trials: the launches of one call follow each other on s and share it
+    for (long long a = 0; a < T; a += stride) {
+        const long long t = T - a < stride ? T - a : stride;
+        hipLaunchKernelGGL(mc_sample_fault_weight_kernel, dim3((unsigned)((t + threads - 1) / threads)), dim3(threads), 0,
+                           s, errors + (size_t)a * (size_t)n, n, weight, t, trial_begin + a, seed, first_fault, site_k,
+                           fault_column, n_sites, picks, stride);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_mc_enum_weight(uint8_t* errors, int n, int weight, long long T, long long rank_begin,
                                  const unsigned long long* binom, hipStream_t s)
 {

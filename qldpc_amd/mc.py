@@ -16,6 +16,9 @@ for every world size -- that is the multi-GPU correctness test (tests/test_mc_di
                                      (decode RECORDED shots to observable predictions: run_shots)
     python -m qldpc_amd.mc --circuit 72 6 --p 0.001 0.002 --shots 1000000 --osd [--basis X]
                                      (circuit-level noise: the memory experiment sampled and decoded on the device: run_circuit)
+    python -m qldpc_amd.mc --circuit 72 6 --fault-weights 2 4 6 8 --prior-p 0.001 --trials 1000000 --osd --ler-at 1e-4 1e-3
+                                     (exactly w firing fault sites, and the circuit-level LER at any p from their failure
+                                      fractions: run_circuit_weights, ler_from_weights)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 40 50 60 70 80 90
                                      (a ladder of iteration limits in one pass: run_budgets, BP_per_Iteration.py)
     python -m qldpc_amd.mc --code 288 --p 0.01 --osd --budgets 10 20 30 --llr-hist 128 -30 30 --out ladder.json
@@ -803,34 +806,36 @@ def run_dem_spectrum(H, L, probs, trials, *, prior=None, distance=0, draws=1, se
                      draws=draws, seed=seed, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr)
 
 
-def check_weights(weights, n):
+def check_weights(weights, n, what="n columns"):
     """The weights of a fixed-weight run as a list of ints in [0, n] (ValueError otherwise -- the library refuses the
-    same values with QBP_E_INVALID)."""
+    same values with QBP_E_INVALID); ``what``: what n counts, for the message."""
     w = np.asarray(weights)
     if w.ndim != 1 or w.dtype.kind not in "iu":
         raise ValueError(f"weights must be a list of integers, got {weights!r}")
     if np.any(w < 0) or np.any(w > n):
-        raise ValueError(f"weights must lie in [0, {n}] (n columns), got {weights!r}")
+        raise ValueError(f"weights must lie in [0, {n}] ({what}), got {weights!r}")
     return [int(x) for x in w]
 
 
-def _weights(model, run, weights, trials, flags, configure, *, rank, world, device, all_reduce, **decoder):
-    """The body of ``run_weights`` and ``run_weights_matrix``: this rank's slice of the trials of every weight, decoded
-    with the one prior of ``model`` -- on the device with the one all-reduce of the [len(weights), 12] table, or through
-    ``run(w, begin, end)`` per weight and ``all_reduce``.  ``decoder``: the keywords of
-    ``Decoder.mc_run_weight_device``."""
-    weights = check_weights(weights, model.n)
+def _weights(model, run, weights, trials, flags, configure, *, rank, world, device, all_reduce,
+             entry="mc_run_weight_device", top=None, reduce=True, **decoder):
+    """The body of ``run_weights``, ``run_weights_matrix`` and ``run_circuit_weights``: this rank's slice of the trials
+    of every weight, decoded with the one prior of ``model`` -- on the device with the one all-reduce of the
+    [len(weights), 12] table, or through ``run(w, begin, end)`` per weight and ``all_reduce``.  ``entry``: the
+    ``Decoder`` method that enqueues a range of one weight, ``decoder`` its keywords; ``top``: the largest weight it
+    takes and what that counts, ``(number, words)`` -- default the n columns of the model."""
+    weights = check_weights(weights, *((model.n,) if top is None else top))
     begin, end = shard_range(int(trials), rank, world)
     if run is None:
         from . import bp
         dec = bp.decoder_for(model.H, device=device)
         configure(dec)
+        enqueue = getattr(dec, entry)
 
         def launch(i, d_prior, a, b, d_out, stream):
-            dec.mc_run_weight_device(model.L, model.distance, weights[i], d_prior, a, b, d_out, flags=flags, stream=stream,
-                                     **decoder)
+            enqueue(model.L, model.distance, weights[i], d_prior, a, b, d_out, flags=flags, stream=stream, **decoder)
         return _on_device((len(weights), NUM_COUNTERS), model.priors * len(weights), (begin, end),
-                          dec.mc_step(flags, end - begin), launch, world, device)
+                          dec.mc_step(flags, end - begin), launch, world, device, reduce=reduce)
     table = np.zeros((len(weights), NUM_COUNTERS), np.int64)
     for i, w in enumerate(weights):
         table[i] = run(w, begin, end)
@@ -863,7 +868,8 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
     """``run_weights`` for any matrix H [m, n] with logical operators / observables L [k, n] (k <= 64) and the
     decoder's LLRs ``prior`` [n].  The weight classes are the strata of UNIFORM noise -- every column failing with the
     same p; under per-column probabilities the patterns of one weight are not equiprobable, and ``ler_from_weights``
-    does not apply.  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``.  ``lsd``,
+    does not apply.  (The detector error model of a circuit is that case: ``run_circuit_weights`` stratifies it by the
+    number of firing fault SITES instead, for which the formula holds.)  ``distance`` as in ``run_dem``.  ``runner(H, L, w, prior, begin, end) -> int64[12]``.  ``lsd``,
     ``lsd_large``, ``quant``: as in ``run_sweep``; of the stages of ``run_weights`` a matrix takes these and OSD."""
     flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
                                lsd=lsd, lsd_large=lsd_large, quant=quant)
@@ -872,6 +878,96 @@ def run_weights_matrix(H, L, weights, trials, *, prior, distance=0, seed=0, max_
     return _weights(model, run, weights, trials, flags, configure, rank=rank, world=world, device=device,
                     all_reduce=all_reduce, seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping,
                     clip_llr=clip_llr)
+
+
+def _circuit_fault_model(code, rounds, weights, prior_p, classes, basis, idle, detectors, device):
+    """What a fixed-weight fault run of a memory experiment needs, built once: ``(circuit, CircuitDem, model, table,
+    weights)`` -- the one-point ``_Model`` on the DEM's H and L with the prior ``dem_prior(cdem.probs(rates))``,
+    ``rates`` being ``prior_p`` on the classes of ``classes`` (None: every class) and 0 elsewhere, ``table =
+    (first_fault, K, N)`` of the active sites, and the weights as ``check_weights`` returns them.  ValueError, before
+    any GPU work: ``prior_p`` outside (0, 1), an unknown class, no active site, or a weight outside
+    [0, min(N, FAULT_WEIGHT_MAX)]."""
+    from . import circuit as circuit_mod
+    prior_p = float(prior_p)
+    if not 0.0 < prior_p < 1.0:
+        raise ValueError(f"prior_p = {prior_p} out of (0, 1)")
+    cir = circuit_mod.memory_experiment(code, rounds, basis=basis, idle=idle, detectors=detectors)
+    table = circuit_mod.fault_sites(cir, classes)
+    N = table[2]
+    if N == 0:
+        raise ValueError(f"no fault site in the rate classes {classes!r}")
+    weights = check_weights(weights, min(N, _lib.FAULT_WEIGHT_MAX),
+                            f"min of N = {N} active fault sites and {_lib.FAULT_WEIGHT_MAX}")
+    active = range(cir.n_classes) if classes is None else sorted(circuit_mod._class_set(classes))
+    rates = circuit_mod.rates_array({int(c): prior_p for c in active}, cir.n_classes)
+    cdem = circuit_mod.circuit_dem(cir, device=device)
+    model = _matrix_model(cdem.H, cdem.L, cdem.probs(rates), None, 0)
+    return cir, cdem, model, table, weights
+
+
+def run_circuit_weights(code, rounds, weights, trials, *, prior_p, classes=None, basis="Z", idle=True, detectors="basis",
+                        seed=0, max_iter=50, variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False,
+                        osd_method="cs", osd_order=0, osd_large=False, lsd=None, lsd_large=False, quant=None, rank=0,
+                        world=1, device=0, reduce=True):
+    """Circuit-level Monte-Carlo stratified by the number of firing fault SITES (qbp_mc_run_fault_weight): the memory
+    experiment ``circuit.memory_experiment(code, rounds, basis, idle, detectors)`` and its detector error model are
+    built once, as in ``run_circuit``; for every w of ``weights``, ``trials`` fault sets of exactly w distinct active
+    sites, uniform among the C(N, w) site sets, each site with one of its K codes, uniform, are mapped to error rows
+    over the DEM's columns on the device and decoded by the pipeline of ``run_weights_matrix``.  Active sites: those
+    whose rate class is in ``classes`` (None: all; ``circuit.fault_sites``).  The prior is
+    ``dem_prior(cdem.probs(rates))`` with ``prior_p`` on the active classes and 0 elsewhere; it fixes the decoder the
+    failure fractions are measured for.
+
+    Returns ``(table int64[len(weights), 12], N)``.  When every active site fires with the same rate p, independently,
+    ``ler_from_weights(table, weights, N, ps)`` is the logical error rate at every p -- ``Circuit.sample``'s model with
+    one rate; unequal rates between active classes are out of scope (the site set given w is then not uniform).
+    Weights lie in [0, min(N, 256)].  Shards, steps and reduces as ``run_weights`` does; ``reduce=False``: this rank's
+    table.  ``lsd``, ``lsd_large``, ``quant``: as in ``run_weights_matrix``."""
+    flags, configure = _stages(variant, osd=osd, osd_method=osd_method, osd_order=osd_order, osd_large=osd_large,
+                               lsd=lsd, lsd_large=lsd_large, quant=quant)
+    _, cdem, model, (first, K, N), weights = _circuit_fault_model(code, rounds, weights, prior_p, classes, basis, idle,
+                                                                  detectors, device)
+
+    def configure_faults(dec):
+        configure(dec)
+        dec.fault_table_set(first, K, cdem.fault_column)
+    table = _weights(model, None, weights, trials, flags, configure_faults, rank=rank, world=world, device=device,
+                     all_reduce=None, entry="mc_run_fault_weight_device", reduce=reduce,
+                     top=(min(N, _lib.FAULT_WEIGHT_MAX), f"min of N = {N} active fault sites and {_lib.FAULT_WEIGHT_MAX}"),
+                     seed=seed, max_iter=max_iter, variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr)
+    return table, N
+
+
+def circuit_failing_faults(code, rounds, weight, trials, *, prior_p, classes=None, basis="Z", idle=True,
+                           detectors="basis", what="logical", cap=1 << 20, seed=0, max_iter=50,
+                           variant=_lib.SUM_PRODUCT, alpha=1.0, damping=1.0, clip_llr=20.0, osd=False, osd_method="cs",
+                           osd_order=0, osd_large=False, device=0):
+    """WHICH fault sets of ``run_circuit_weights`` the decoder fails on (qbp_fault_weight_failures): trials
+    [0, ``trials``) of weight ``weight`` are decoded as ``run_shots`` decodes their detection events (flooding BP
+    [+ OSD]) and those of kind ``what`` ("logical", "unconverged" or "either") are captured, at most ``cap`` of them.
+    Returns a dict: ``trials`` int64 [F] (ascending when found <= cap), ``kinds`` uint8 [F] (bit 0 a logical failure,
+    bit 1 BP did not converge), ``found``, ``counters`` int64 [12], ``N``, and ``faults`` int64 [F, weight], the fault
+    numbers of every captured trial (``circuit.fault_sets``), with ``sites`` and ``codes`` of the same shape: the site in
+    the circuit's site numbering and the code 1 .. K of every fault."""
+    from . import bp, circuit as circuit_mod
+    kinds_of = {"logical": 1, "unconverged": 2, "either": 3}
+    if what not in kinds_of:
+        raise ValueError(f"what must be one of {sorted(kinds_of)}, got {what!r}")
+    flags = osd_run_flags(osd, osd_method, osd_order, osd_large)
+    if int(cap) < 0 or int(trials) < 0:
+        raise ValueError("cap and trials must be >= 0")
+    cir, cdem, model, (first, K, N), (weight,) = _circuit_fault_model(code, rounds, [weight], prior_p, classes, basis,
+                                                                      idle, detectors, device)
+    dec =bp.decoder_for(model.H, device=device)
+    dec.fault_table_set(first, K, cdem.fault_column)
+    hit, kinds, found, counters = dec.fault_weight_failures(
+        model.L, weight, model.priors[0], 0, int(trials), seed=seed, what=kinds_of[what], cap=cap, max_iter=max_iter,
+        variant=variant, alpha=alpha, damping=damping, clip_llr=clip_llr, flags=flags)
+    faults = circuit_mod.fault_sets(cir, weight, seed, hit, classes)
+    base = cir.sites()[5]
+    sites = np.searchsorted(base, faults, side="right") - 1
+    return dict(trials=hit, kinds=kinds, found=found, counters=counters, N=N, faults=faults, sites=sites,
+                codes=faults - base[sites] + 1)
 
 
 def _enumerate(model, run, weights, flags, configure, *, rank, world, device, all_reduce, **decoder):
@@ -1066,6 +1162,12 @@ def main(argv=None):
     ap.add_argument("--rates", type=float, nargs=4, default=None, metavar=("RESET", "CNOT", "IDLE", "MEAS"),
                     help="--circuit: a rate per class instead of p for every class (one --p point, which then only labels "
                          "the row)")
+    ap.add_argument("--fault-weights", type=int, nargs="+", default=None, metavar="W",
+                    help="--circuit: fault sets of exactly these numbers of firing fault sites instead of --p / --shots "
+                         "(run_circuit_weights): a result line per weight; needs --prior-p, takes --trials, --ler-at, "
+                         "--classes, --osd*, --lsd, --quant")
+    ap.add_argument("--classes", nargs="+", default=None, choices=("reset", "cnot", "idle", "meas"),
+                    help="--fault-weights: the rate classes whose sites can fire (default: all); the others have rate 0")
     ap.add_argument("--dem", default=None,
                     help="detector error model file (stim's text format) instead of --code / --p: run_dem")
     ap.add_argument("--phenomenological", nargs=2, default=None, metavar=("CODE", "ROUNDS"),
@@ -1191,6 +1293,50 @@ def main(argv=None):
         osd_run_flags(args.osd, args.osd_method, args.osd_order, args.osd_large)
     except ValueError as e:
         ap.error(str(e))
+    if args.circuit is None and (args.fault_weights is not None or args.classes is not None):
+        ap.error("--fault-weights and --classes need --circuit")
+    if args.circuit is not None and args.fault_weights is not None:
+        if args.shots is not None or args.rates is not None:
+            ap.error("--fault-weights takes --trials and --prior-p, not --shots or --rates")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--circuit runs on one GPU from the command line (mc.run_circuit_weights takes rank= and world=)")
+        if args.prior_p is None or not 0.0 < args.prior_p < 1.0:
+            ap.error("--fault-weights needs --prior-p in (0, 1)")
+        if any(not 0.0 <= p <= 1.0 for p in args.ler_at or []):
+            ap.error("--ler-at takes probabilities in [0, 1]")
+        for name in ("dem", "obs", "budgets", "spectrum", "weights", "depolarizing", "relay", "gd", "layered", "window",
+                     "enumerate", "phenomenological", "failures"):
+            if getattr(args, name, None) not in (None, False):
+                ap.error(f"--fault-weights does not combine with --{name}")
+        try:
+            rounds = int(args.circuit[1])
+            quant = None
+            if args.quant is not None:
+                from . import quant as quant_mod
+                quant = quant_mod.QuantConfig(int(args.quant[0]), float(args.quant[1]), tuple(args.quant_alpha),
+                                              args.quant_beta)
+            t0 = time.perf_counter()
+            table, N = run_circuit_weights(args.circuit[0], rounds, args.fault_weights, args.trials, prior_p=args.prior_p,
+                                           classes=args.classes, basis=args.basis, idle=not args.no_idle,
+                                           detectors=args.detectors, seed=args.seed, max_iter=args.max_iter,
+                                           variant=_VARIANTS[args.variant], alpha=args.alpha, damping=args.damping,
+                                           clip_llr=args.clip_llr, osd=args.osd, osd_method=args.osd_method,
+                                           osd_order=args.osd_order, osd_large=args.osd_large, lsd=args.lsd,
+                                           lsd_large=args.lsd_large, quant=quant)
+            result = {"circuit": args.circuit[0], "rounds": rounds, "basis": args.basis, "detectors": args.detectors,
+                      "classes": args.classes, "prior_p": args.prior_p, "sites": N, "trials": args.trials,
+                      "seconds": time.perf_counter() - t0,
+                      "points": [dict(weight=w, **summarize(row)) for w, row in zip(args.fault_weights, table)]}
+            if args.ler_at:
+                est = ler_from_weights(table, args.fault_weights, N, args.ler_at)
+                result["ler_at"] = {k: [float(x) for x in v] for k, v in est.items()}
+        except (ValueError, KeyError) as e:
+            ap.error(f"--fault-weights: {e}")
+        print(json.dumps(result))
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(result, f)
+        return 0
     if args.circuit is not None:
         if args.p is None or args.shots is None or not str(args.shots).isdigit():
             ap.error("--circuit needs --p and --shots N (with --circuit, --shots is a count, not a file of recorded shots)")
